@@ -15,9 +15,10 @@ context (round 5: a context takes up to 512 windows -- encoder in chunks of <= 1
 --inflight (2) contexts, so two batches are in flight. The span is first H2D byte to last token id on the host. value = audio seconds / wall seconds; weak
 scaling for N > 1 (every rank its own clips; the weight arena is broadcast once over RCCL before the timed region). Rounds 1-4 called one CLIP pass a step
 and dealt the K passes into batches -- at the driver's K = 20 two batches of 70 windows, a job so small that the latency-bound decode chain is a third of it;
-that measurement is still in every line: `small_job`.
+that measurement is still in every --full line: `small_job`.
 
-Objects next to the contract fields:
+A plain run sets up, warms up, times the K steps and prints the line; --dump-outputs DIR writes what the last timed step returned (token ids and
+their probabilities) as .npy files. Everything else is measured only with --full, where these objects fill in next to the contract fields:
   roofline      algorithmic bytes (or flops) per launch / average launch duration, hipEvent pairs on the launch stream (one batch of the size the timed
                 region ran, one context at a time) minus the calibrated cost of an empty bracket; `traffic` = HBM bytes per launch from the committed PMC
                 pass (profiles/r06_pmc.json, collected at the timed batch size of 448 windows; counters cannot be collected inside a timed run). The two classes with the most kernel time are both in
@@ -94,29 +95,40 @@ def clip_start(group, prompt, n_greedy):
     ctx.decode_window_start(np.tile(np.asarray(prompt, np.int32), (k, 1)), n_greedy, force_first_timestamp=True, first_is_initial=True)
 
 
-def clip_finish(group):
-    ids, _ = group[0].decode_window_finish()
-    return ids.T
+def clip_finish(group, with_probs=False):
+    ids, ps = group[0].decode_window_finish()
+    return (ids.T, ps.T) if with_probs else ids.T
 
 
-def run_passes(sequence, prompt, n_greedy, max_in_flight):
+def run_passes(sequence, prompt, n_greedy, max_in_flight, with_probs=False):
     """Runs the slots of `sequence` in order with up to max_in_flight of them enqueued at once, each on its own context /
     HIP stream: the MFMA-bound encoder of one pass runs under the latency-bound decode chains of its neighbours. Every
-    pass does the full work; results come back in order. Returns the token ids of the last pass."""
+    pass does the full work; results come back in order. Returns the token ids of the last pass (with_probs: the pair
+    ids, probabilities of the chosen tokens)."""
+    finish = (lambda g: clip_finish(g, with_probs=True)) if with_probs else clip_finish
     pending, toks = [], None
     for g in sequence:
         while len(pending) >= max_in_flight or any(p is g for p in pending):
-            toks = clip_finish(pending.pop(0))
+            toks = finish(pending.pop(0))
         clip_start(g, prompt, n_greedy)
         pending.append(g)
     while pending:
-        toks = clip_finish(pending.pop(0))
+        toks = finish(pending.pop(0))
     return toks
 
 
 def log(msg):
     sys.stderr.write("[bench %7.1fs] %s\n" % (time.time() - T_START, msg))
     sys.stderr.flush()
+
+
+def dump_outputs(out_dir, **arrays):
+    """--dump-outputs: the arrays the timed path returned in its last step, one DIR/<name>.npy each (ids in float64, exact)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64 if a.dtype.kind in "iu" else np.float32))
+    log("outputs of the last step written to %s: %s" % (out_dir, ", ".join("%s %s" % (k, list(np.shape(v))) for k, v in arrays.items())))
 
 
 CPU_BASELINE_THREADS_MAX = 16      # ggml's spin-wait thread pool stops scaling (and can collapse) far below a big host's core count
@@ -413,10 +425,13 @@ def measure_batched(hip_model, hp, prompt, steps, warmup, B, C, inflight, rank, 
     import torch
     from whisper_amd import binding
     n_frames = WINDOW_SAMPLES // 160
+    pcm_of = {}          # n_clips -> the slot's PCM: the contexts of one batch size hold the same clips, synthesised once
 
     def make_slot(n_clips):
         """A context for n_clips clip passes in lock step + its inputs; clip j of every slot is the same seeded clip."""
-        host = torch.from_numpy(np.concatenate([synth_pcm(B, seed=100 + rank + 1000 * j) for j in range(n_clips)])).pin_memory()
+        if n_clips not in pcm_of:
+            pcm_of[n_clips] = np.concatenate([synth_pcm(B, seed=100 + rank + 1000 * j) for j in range(n_clips)])
+        host = torch.from_numpy(pcm_of[n_clips]).pin_memory()
         dev = host.cuda()
         mel = torch.empty((B * n_clips, hp.n_mels, n_frames), dtype=torch.float32, device="cuda")
         return (binding.HipContext(hip_model, B * n_clips), host if h2d else None, dev, mel)
@@ -454,7 +469,7 @@ def measure_batched(hip_model, hp, prompt, steps, warmup, B, C, inflight, rank, 
             run_passes(distinct, prompt, N_GREEDY, inflight)
     barrier()
     t0 = time.perf_counter()
-    toks = run_passes(sequence, prompt, N_GREEDY, inflight)
+    toks, probs = run_passes(sequence, prompt, N_GREEDY, inflight, with_probs=True)
     barrier()
     elapsed = time.perf_counter() - t0
     elapsed_local = elapsed
@@ -462,7 +477,7 @@ def measure_batched(hip_model, hp, prompt, steps, warmup, B, C, inflight, rank, 
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    out = {"elapsed": elapsed, "elapsed_local": elapsed_local, "toks": toks, "slots": slots, "last_slot": sequence[-1], "single_clip_ms": None, "kernels": {}, "lone_batch_ms": None, "plan": sizes,
+    out = {"elapsed": elapsed, "elapsed_local": elapsed_local, "toks": toks, "probs": probs, "slots": slots, "last_slot": sequence[-1], "single_clip_ms": None, "kernels": {}, "lone_batch_ms": None, "plan": sizes,
            "kernel_clips": int(slots[0][2].shape[0]) // B}
     if want_kernels and rank == 0:
         grp = slots[0]
@@ -883,6 +898,8 @@ def run_chunks(args, hip_model, hp, prompt, rank, world, dist, n_chunks, hyp, n_
         elapsed = float(t.item())
     if rank != 0:
         return None
+    if getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, token_ids=toks)
     value = n_chunks * 30.0 * args.steps / elapsed
     return {
         "metric": METRIC, "value": round(value, 2), "unit": "audio-seconds/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -928,16 +945,25 @@ def main():
     ap.add_argument("--plan", default=None, help="explicit batch sizes (clips) of the timed region for experiments, e.g. 16,4 (default: --steps batches of --clips-per-step clips)")
     ap.add_argument("--batch", type=int, default=16, help="shard256 / beam5: windows per lock-step batch")
     ap.add_argument("--beam-host", action="store_true", help="beam5: rank every step's candidates on the host (round 4's data path) instead of on the device")
-    ap.add_argument("--no-beam", action="store_true", help="skip the beam5 sub-object of the default line (BASELINE configs[2] on the large-v2 model)")
-    ap.add_argument("--no-workloads", action="store_true", help="skip the shard256 (large_v2.shard256) and v3stream sub-objects of the default line (BASELINE configs[3] and [4] on one rank)")
+    ap.add_argument("--no-beam", action="store_true", help="skip the beam5 sub-object of the --full line (BASELINE configs[2] on the large-v2 model)")
+    ap.add_argument("--no-workloads", action="store_true", help="skip the shard256 (large_v2.shard256) and v3stream sub-objects of the --full line (BASELINE configs[3] and [4] on one rank)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-single-stream", action="store_true")
-    ap.add_argument("--no-large", action="store_true", help="skip the large_v2 sub-object of the default line")
+    ap.add_argument("--no-large", action="store_true", help="skip the large_v2 sub-object of the --full line")
     ap.add_argument("--no-boundary", action="store_true", help="skip the through_boundary sub-object (the workload through libWhisper.so's batch runner)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo lets two ranks share one GPU in a dry run)")
     ap.add_argument("--device", type=int, default=-1, help="HIP device for this rank (default LOCAL_RANK)")
+    ap.add_argument("--full", action="store_true", help="measure and check everything beyond the headline as well: roofline and per-kernel tables, cpu_baseline, "
+                    "parity (+ timed_ids), small_job, through_boundary, single_stream, large_v2 (+ beam5, shard256), v3stream; the --no-* options above leave "
+                    "parts of it out. Without it a run sets up, warms up, times the steps and prints the line (those objects are null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path returned in its last step as "
+                    "DIR/<name>.npy (float32 / float64): token_ids and token_probs [windows][1 + greedy steps] of the last batch (--workload shard256 / beam5: "
+                    "token_ids of the last step); the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
+    if not args.full:
+        for k in ("no_small_job", "no_ids_check", "no_beam", "no_workloads", "no_cpu_baseline", "no_roofline", "no_single_stream", "no_large", "no_boundary"):
+            setattr(args, k, True)
     if args.model is None:
         args.model = {"clip": "medium", "shard256": "large-v2", "beam5": "large-v2", "v3stream": "large-v3"}[args.workload]
 
@@ -1034,6 +1060,8 @@ def main():
     inflight = min(inflight, len(batch_plan))
     if rank == 0:
         log("timed region done: %.3f s (batches of %s clips, %d in flight)" % (elapsed, batch_plan, inflight))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, token_ids=toks, token_probs=m["probs"])
     per_rank = None
     if world > 1:
         # every rank's own figure next to the job's (value = all ranks' audio / the slowest rank's time)

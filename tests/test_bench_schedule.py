@@ -85,3 +85,24 @@ def test_plan_batches_is_balanced_and_complete():
                 if steps >= inflight:
                     assert len(sizes) % inflight == 0 or len(sizes) == steps      # (one clip per batch: nothing left to round up with)
                 assert len(sizes) <= -(-steps // C) + inflight - 1
+
+
+def test_dump_outputs_writes_float_arrays_of_the_last_pass(monkeypatch, tmp_path):
+    """--dump-outputs: run_passes(with_probs=True) hands back the ids and probabilities of the LAST pass, and dump_outputs writes each
+    array as DIR/<name>.npy in float64 (ids, exact) or float32."""
+    import numpy as np
+
+    class Ctx:
+        def __init__(self, k):
+            self.k = k
+
+        def decode_window_finish(self):
+            return np.full((52, 7), self.k, np.int32), np.full((52, 7), 0.5 * self.k, np.float32)
+
+    monkeypatch.setattr(bench, "clip_start", lambda g, prompt, n_greedy: None)
+    ids, probs = bench.run_passes([(Ctx(1),), (Ctx(2),), (Ctx(51865),)], [1, 2, 3], 51, 2, with_probs=True)
+    assert ids.shape == (7, 52) and (ids == 51865).all() and (probs == np.float32(0.5 * 51865)).all()
+    bench.dump_outputs(str(tmp_path / "out"), token_ids=ids, token_probs=probs)
+    a, p = np.load(tmp_path / "out" / "token_ids.npy"), np.load(tmp_path / "out" / "token_probs.npy")
+    assert a.dtype == np.float64 and p.dtype == np.float32
+    assert np.array_equal(a, ids) and np.array_equal(p, probs)

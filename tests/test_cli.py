@@ -245,10 +245,12 @@ def test_mgpu_harness_one_rank_matches_the_cli(exe, tmp_path):
         w.setframerate(16000)
         w.writeframes(np.clip(np.round(pcm * 32768.0), -32768, 32767).astype("<i2").tobytes())
     out = str(tmp_path / "t.txt")
-    r = subprocess.run([build.MGPU_BIN, "-n", "1", "-m", model, "-f", wav, "-l", case["lang"], "-o", out],
+    # the harness's own deadlines end before the test's: a stalled rendezvous or job then ends the rank too (a killed parent would leave it
+    # running on the device) and its stderr says where it stood
+    r = subprocess.run([build.MGPU_BIN, "-n", "1", "-m", model, "-f", wav, "-l", case["lang"], "-o", out, "-timeout", "120", "-job-timeout", "240"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     print(r.stdout.decode(), r.stderr.decode()[-3000:])
-    assert r.returncode == 0
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
     line = json.loads(r.stdout.decode().strip().splitlines()[-1])
     assert line["ranks"] == 1 and line["windows"] >= 1
     got = open(out).read().splitlines()

@@ -5,7 +5,7 @@
 #   tests     pytest -m gpu (full suite, no -x)              -> $out/test.log
 #   poison    the full suite again under WH_DEBUG_POISON=0xFF (stale-memory / guard-region check) -> $out/test_poison.log
 #   smoke     __graft_entry__.smoke() in three fresh processes
-#   bench     python bench.py                                 -> $out/bench.json
+#   bench     python bench.py --full                          -> $out/bench.json
 #   prof      rocprofv3 --kernel-trace --stats over bench.py  -> $out/bench_kernel_stats.csv
 #   pmc       FETCH_SIZE / WRITE_SIZE passes (separate runs)  -> $out/r_pmc.json
 #   workloads shard256 / beam5 / v3stream bench lines
@@ -38,7 +38,7 @@ if has smoke; then
 fi
 if has bench; then
   echo "== bench"; date
-  timeout 900 python bench.py > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"
+  timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"
   python - <<PY
 import json
 d=json.load(open("$out/bench.json"))
@@ -66,7 +66,7 @@ if has workloads; then
   echo "== workloads"; date
   timeout 400 python bench.py --workload shard256 --steps 1 --warmup 1 > $out/shard256.json 2> $out/shard256.err; tail -c 600 $out/shard256.json
   timeout 400 python bench.py --workload beam5 --steps 8 --warmup 2 > $out/beam5.json 2> $out/beam5.err; tail -c 600 $out/beam5.json
-  timeout 400 python bench.py --workload v3stream --steps 16 --warmup 1 --no-cpu-baseline > $out/v3.json 2> $out/v3.err; head -c 400 $out/v3.json
+  timeout 400 python bench.py --full --workload v3stream --steps 16 --warmup 1 --no-cpu-baseline > $out/v3.json 2> $out/v3.err; head -c 400 $out/v3.json
 fi
 if has extra; then
   echo "== extra: $EXTRA_CMD"; date

@@ -5,7 +5,7 @@ timeout 300 python -c "from whisper_amd import canary; canary.run_all()" 2>&1 | 
 echo "== op tests"; timeout 900 python -m pytest tests/test_gpu_ops.py -m gpu -q -x -k "flash or exp_table" -rP 2>&1 | grep -E "table kernel|passed|failed|Error|flash_attention table" | tail -30
 DEF=$(python -c "from whisper_amd import binding as b; print(b.TUNE_DEFAULT & ~b.TUNE_ATTN_ENC_TABLE)")
 TAB=$(python -c "from whisper_amd import binding as b; print(b.TUNE_DEFAULT | b.TUNE_ATTN_ENC_TABLE)")
-run() { WH_TUNING=$2 timeout 400 python bench.py --steps 32 --warmup 1 --no-cpu-baseline --no-single-stream --no-large --no-boundary > $out/$1.json 2> $out/$1.err
+run() { WH_TUNING=$2 timeout 400 python bench.py --full --steps 32 --warmup 1 --no-cpu-baseline --no-single-stream --no-large --no-boundary > $out/$1.json 2> $out/$1.err
   python - <<PY
 import json
 d=json.load(open("$out/$1.json")); k=d["kernels"]["attentionEnc"]

@@ -5,7 +5,7 @@ timeout 300 python -c "from whisper_amd import canary; canary.run_all()" 2>&1 | 
 echo "== tests"; timeout 1500 python -m pytest tests -m gpu -q -rP > $out/test.log 2>&1; echo "pytest rc=$?"; grep -E "passed|failed|FAILED|Error" $out/test.log | tail -8; grep -E "beam 5 on" $out/test.log
 DEF=$(python -c "from whisper_amd import binding as b; print(b.TUNE_DEFAULT)")
 MT8=$(python -c "from whisper_amd import binding as b; print(b.TUNE_DEFAULT | b.TUNE_GEMV_MT8)")
-run() { WH_TUNING=$2 timeout 400 python bench.py --steps 32 --warmup 1 --no-cpu-baseline --no-single-stream --no-large --no-boundary > $out/$1.json 2> $out/$1.err
+run() { WH_TUNING=$2 timeout 400 python bench.py --full --steps 32 --warmup 1 --no-cpu-baseline --no-single-stream --no-large --no-boundary > $out/$1.json 2> $out/$1.err
   python - <<PY
 import json
 d=json.load(open("$out/$1.json")); k=d["kernels"]["gemvFused"]

@@ -15,7 +15,7 @@ FE=$(python -c "from whisper_amd import binding as b; print((b.TUNE_DEFAULT & ~b
 echo "== model-level tests with ${MODEL_TUNING:-W4}"; date
 MT=$W4; [ "$MODEL_TUNING" = FE ] && MT=$FE
 WH_TUNING=$MT timeout 900 python -m pytest tests/test_gpu_model.py -m gpu -q -x 2>&1 | tail -4
-run() { WH_TUNING=$2 timeout 400 python bench.py --steps 32 --warmup 1 --no-cpu-baseline --no-single-stream --no-large --no-boundary > $out/$1.json 2> $out/$1.err
+run() { WH_TUNING=$2 timeout 400 python bench.py --full --steps 32 --warmup 1 --no-cpu-baseline --no-single-stream --no-large --no-boundary > $out/$1.json 2> $out/$1.err
   python - <<PY
 import json
 d=json.load(open("$out/$1.json")); k=d["kernels"]["gemmTiled"]

@@ -8,7 +8,7 @@ echo "== tests"; date
 timeout 1500 python -m pytest tests -m gpu -q -rP > $out/test.log 2>&1; echo "pytest rc=$?" | tee -a $out/test.log
 grep -E "passed|failed|FAILED|Error|device-ranked" $out/test.log | tail -25
 echo "== bench (default)"; date
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"; tail -5 $out/bench.err
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"; tail -5 $out/bench.err
 python - <<PY
 import json
 d=json.load(open("$out/bench.json"))
@@ -23,7 +23,7 @@ print("large_v2", {k:l.get(k) for k in ("value","ms_per_step","batch_plan","erro
 print("large roofline", json.dumps({k:(l.get("roofline") or {}).get(k) for k in ("kernel","frac","decode_chain","end_to_end")})[:900])
 PY
 echo "== bench (driver invocation)"; date
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --no-large --no-single-stream --no-boundary --no-cpu-baseline > $out/bench_k20.json 2> $out/bench_k20.err; echo "bench k20 rc=$?"
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-large --no-single-stream --no-boundary --no-cpu-baseline > $out/bench_k20.json 2> $out/bench_k20.err; echo "bench k20 rc=$?"
 python -c "
 import json; d=json.load(open('$out/bench_k20.json')); print({k:d[k] for k in ('value','ms_per_step','steps')}, d['config']['batch_plan'], json.dumps(d['roofline']['end_to_end'])[:300])"
 echo "== kernel trace of the driver invocation"; date

@@ -11,7 +11,7 @@ grep -E "passed|failed|FAILED|Error" $out/test.log | tail -12
 grep -E "ranks . on . device|PARITY MODE|lock step vs" $out/test.log | tail -12
 echo "== smoke"; timeout 300 python -c "import __graft_entry__ as e; e.smoke()" > $out/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $out/smoke.log
 echo "== bench (default)"; date
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"; tail -3 $out/bench.err
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"; tail -3 $out/bench.err
 python - <<PY
 import json
 d=json.load(open("$out/bench.json"))
@@ -36,11 +36,11 @@ PMC_WINDOWS=224 timeout 500 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-f
 cd $R
 python tools/pmc_summary.py /tmp/pmc_fetch /tmp/pmc_write $out/pmc_algo.json $out/r_pmc.json 2>&1 | tail -14
 echo "== bench (driver invocation)"; date
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_k20.json 2> $out/bench_k20.err; echo "bench k20 rc=$?"
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_k20.json 2> $out/bench_k20.err; echo "bench k20 rc=$?"
 python -c "
 import json; d=json.load(open('$out/bench_k20.json')); print({k:d[k] for k in ('value','ms_per_step','steps')}, d['config']['batch_plan'], json.dumps(d['roofline']['end_to_end'])[:200]); print('large', (d.get('large_v2') or {}).get('value'), 'boundary', (d.get('through_boundary') or {}).get('value'))"
 echo "== workloads"; date
 timeout 400 python bench.py --workload shard256 --steps 1 --warmup 1 --batch 128 > $out/shard256.json 2> $out/shard256.err; tail -c 400 $out/shard256.json; echo
 timeout 400 python bench.py --workload beam5 --steps 8 --warmup 2 > $out/beam5.json 2> $out/beam5.err; tail -c 300 $out/beam5.json; echo
-timeout 400 python bench.py --workload v3stream --no-cpu-baseline --no-single-stream --no-boundary --no-large > $out/v3.json 2> $out/v3.err; head -c 300 $out/v3.json; echo
+timeout 400 python bench.py --full --workload v3stream --no-cpu-baseline --no-single-stream --no-boundary --no-large > $out/v3.json 2> $out/v3.err; head -c 300 $out/v3.json; echo
 date

@@ -14,11 +14,11 @@ cd $R
 f=$(find /tmp/prof_bench1 -name "*kernel_stats.csv" | head -1); cp $f $out/bench_kernel_stats_one_context.csv 2>/dev/null
 head -6 $out/bench_kernel_stats_one_context.csv | cut -c1-150
 echo "== bench (driver invocation)"; date
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_k20.json 2> $out/bench_k20.err; echo "bench k20 rc=$?"; tail -2 $out/bench_k20.err
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_k20.json 2> $out/bench_k20.err; echo "bench k20 rc=$?"; tail -2 $out/bench_k20.err
 python -c "
 import json; d=json.load(open('$out/bench_k20.json')); print({k:d[k] for k in ('value','ms_per_step','steps','warmup')}, d['config']['clips_per_step'], json.dumps(d['roofline']['end_to_end'])[:120]); print('small_job', d['small_job']['value'], 'large', (d.get('large_v2') or {}).get('value'), 'boundary', (d.get('through_boundary') or {}).get('value'), 'single', (d.get('single_stream') or {}).get('value'), 'ids', d['parity']['timed_ids']['consistent'])"
 echo "== bench (default)"; date
-timeout 600 python bench.py > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"; tail -2 $out/bench.err
+timeout 600 python bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"; tail -2 $out/bench.err
 python -c "
 import json; d=json.load(open('$out/bench.json')); print({k:d[k] for k in ('value','ms_per_step','steps','warmup')}, 'small_job', d['small_job']['value'], 'e2e', d['roofline']['end_to_end']['frac'], 'top', d['roofline']['kernel'], d['roofline']['frac'], 'hbm', d['roofline']['hbm_kernel']['frac'], d['roofline']['hbm_kernel']['avg_launch_us'])"
 left=$(( ${2:-560} - ( $(date +%s) - T0 ) ))

@@ -6,6 +6,6 @@ date
 timeout 2400 python -m pytest tests -m gpu -q -rP --durations=15 > $out/test.log 2>&1; echo "pytest rc=$?" | tee -a $out/test.log
 grep -E "passed|failed|FAILED|^ERROR" $out/test.log | tail -15
 date
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"; python -c "
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"; python -c "
 import json; d=json.loads(open('$out/bench.json').read().strip().splitlines()[-1]); print(d['value'], d['unit'], d['ms_per_step'], 'small_job', d.get('small_job',{}).get('value'), 'roofline', d['roofline'].get('frac'), d['roofline'].get('which'))"
 date

@@ -9,8 +9,8 @@ WH_DEBUG_POISON=0xFF timeout 1500 python -m pytest tests -m gpu -q > $out/test_p
 grep -E "passed|failed|FAILED|^ERROR|WH_GUARD_VIOLATION" $out/test_poison.log | tail -8
 timeout 300 python -c "import __graft_entry__ as e; e.smoke()" > $out/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $out/smoke.log
 date
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_driver.json 2> $out/bench_driver.err; echo "bench(driver) rc=$?"
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_driver.json 2> $out/bench_driver.err; echo "bench(driver) rc=$?"
 python -c "
 import json
 for f in ('bench.json','bench_driver.json'):

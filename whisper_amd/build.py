@@ -107,7 +107,9 @@ def build_mgpu(force: bool = False):
 
 
 ABI_SRC = os.path.join(ROOT, "tests", "abi_caller", "caller.cpp")
-ABI_REF_BIN = os.path.join(LIB_DIR, "abi-caller-ref")      # built from the REFERENCE's own headers (only where /root/reference exists)
+# built from the REFERENCE's own headers (only where REFERENCE_ROOT exists) into the git-ignored oracle/_ref/, which travels with the tree
+# to machines that have no reference tree: there the test finds the binary, as it finds the oracle's libraries
+ABI_REF_BIN = os.path.join(ROOT, "oracle", "_ref", "abi-caller-ref")
 ABI_OUR_BIN = os.path.join(LIB_DIR, "abi-caller-our")      # the same source against include/whisperApi.h
 REFERENCE_ROOT = "/root/reference"
 
@@ -122,8 +124,9 @@ def build_abi_callers(force: bool = False):
         _run(["g++", "-std=c++20", "-O1", "-I" + os.path.join(ROOT, "include"), ABI_SRC, "-o", ABI_OUR_BIN] + link)
     ref_hdr = os.path.join(REFERENCE_ROOT, "Whisper", "API", "whisperComLight.h")
     if os.path.exists(ref_hdr) and (force or _newer(ABI_REF_BIN, [ABI_SRC, HOST_LIB])):
+        os.makedirs(os.path.dirname(ABI_REF_BIN), exist_ok=True)
         _run(["g++", "-std=c++20", "-O1", "-D__stdcall=", "-D__cdecl=", "-DUSE_REFERENCE_HEADERS", "-I" + REFERENCE_ROOT, ABI_SRC,
-              "-o", ABI_REF_BIN] + link)
+              "-o", ABI_REF_BIN, "-L" + LIB_DIR, "-lWhisper", "-Wl,-rpath,$ORIGIN/" + os.path.relpath(LIB_DIR, os.path.dirname(ABI_REF_BIN))])
     return ABI_OUR_BIN
 
 
