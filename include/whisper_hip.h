@@ -400,6 +400,25 @@ WH_API int wh_op_decoder_cross_attention( void* stream, const float* x, const fl
 /* softMax over rows with the reference's FP16 exp table semantics (softMax.hlsl / ggml.c:5030-5090): in place, FP32 */
 WH_API int wh_op_soft_max( void* stream, float* x, int rows, int cols );
 
+/* ---- op-level entry points of the beam step's kernels (the routes wh_decode and wh_beam_window_* take). Device pointers. ---- */
+
+/* The decoder's vocabulary softmax (same semantics as wh_op_soft_max), out of place: probs [rows][cols] = softmax( logits [rows][cols] ).
+ * Takes the kernel the option "beam_regs" selects (the row in registers up to 52224 columns, the three-pass kernel beyond). */
+WH_API int wh_op_vocab_soft_max( void* stream, const float* logits, float* probs, int rows, int cols );
+/* wh_sample_best on probabilities [rows][nVocab]: out [rows]. tokenBeg .. nVocab - 1 are the timestamps; the specials are < tokenBeg. */
+WH_API int wh_op_sample_best( void* stream, const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot,
+	int forceTimestamp, int isInitial, wh_token_data* out );
+/* wh_beam_candidates on probabilities [rows][nVocab]: out [rows][width], width 1 .. 8. */
+WH_API int wh_op_beam_candidates( void* stream, const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot,
+	int forceTimestamp, int isInitial, int width, wh_token_data* out );
+/* The ranked beam step's self-attention cache reorder: sequence j continues sequence parents[ j ]. Caches FP16 [layers][maxSeq][heads][keyStride][64]
+ * (cacheK, cacheV; scratchK / scratchV of the same size serve the two-phase copy); rowsDev[ j ] rows of sequence j move, clamped to [0, keyStride].
+ * group > 1 with sequences % group == 0 and the option "reorder_group": the sequences of each group of `group` consecutive ones move in one launch
+ * (rows = rowsDev of the group's first sequence; a parent outside its group leaves that sequence as it is); otherwise the two-phase copy.
+ * Every parents[ j ] MUST lie in [0, sequences): the device reads them as they are. Bad sizes: WH_E_INVALIDARG. */
+WH_API int wh_op_reorder_self_cache( void* stream, void* cacheK, void* cacheV, void* scratchK, void* scratchV, const int32_t* parents,
+	const int32_t* rowsDev, int layers, int sequences, int maxSeq, int heads, int keyStride, int group );
+
 #ifdef __cplusplus
 }
 #endif

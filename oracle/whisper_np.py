@@ -525,3 +525,27 @@ def sample_best(probs, token_beg, token_sot, token_solm, token_not, force_timest
         res += 1
     i = int(order[res])
     return dict(id=i, tid=tid, p=float(np.float32(p[i])), pt=float(pt), ptsum=float(np.float32(sum_ts)))
+
+
+def beam_candidates(probs, token_beg, token_sot, token_solm, token_not, force_timestamp=False, is_initial=False, width=1):
+    """The `width` best continuations of one row under sampleBest's rules (wh_beam_candidates; the reference declares beam search
+    and implements only the greedy strategy). Candidate 0 is sample_best's pick. The next ones are the best remaining tokens under
+    the same mask (text tokens when the timestamps win or are forced, timestamps above beg+100 when `is_initial`), sot / solm / not
+    skipped, exact ties to the lower index. When fewer than `width` tokens survive the mask, the last candidate is repeated with
+    p = 0. Returns a list of `width` dicts (id, tid, p, pt, ptsum); tid / pt / ptsum are candidate 0's."""
+    first = sample_best(probs, token_beg, token_sot, token_solm, token_not, force_timestamp, is_initial)
+    p = np.asarray(probs, np.float64)
+    n = len(p)
+    max_tx = max(-1.0, p[:token_beg].max())
+    i1 = min(token_beg + 101, n) if is_initial else n
+    alive = np.ones(n, bool)
+    alive[i1:] = False
+    if float(p[token_beg:i1].sum()) > max_tx or force_timestamp:
+        alive[:token_beg] = False
+    alive[[token_sot, token_solm, token_not, first["id"]]] = False
+    idx = np.nonzero(alive)[0]
+    idx = idx[np.argsort(-p[idx], kind="stable")][:width - 1]
+    out = [first] + [dict(first, id=int(i), p=float(np.float32(p[i]))) for i in idx]
+    while len(out) < width:
+        out.append(dict(out[-1], p=0.0))
+    return out

@@ -590,3 +590,112 @@ def test_parity_mode_at_medium_shape_vs_one_thread(ref_lib_available, tmp_path):
     w.close()
     ctx.close()
     m.close()
+
+
+def _f64_product(a, w, bias=None, res=None):
+    """float64 reference on the device: a [M][K], w [N][K] (FP16), bias [N], res [M][N]."""
+    want = a.double() @ w.double().T
+    if bias is not None:
+        want += bias.double()
+    if res is not None:
+        want += res.double()
+    return want
+
+
+@pytest.mark.parametrize("N,K", [(51864, 1024), (51865, 1024), (51866, 1024), (51864, 1280), (51865, 1280), (51866, 1280)])
+def test_vocabulary_product_routes_give_the_same_bits(N, K):
+    """Option vocab_lds (round 6, default): the vocabulary product of 33 .. 128 rows on gemmDecTile's 64 x 64 tiles (one or two row tiles) against gemmAllRows
+    (vocab_lds 0): the same K quarters added in the same order, so the same bits -- at the row-tile edges 33 / 40 / 64 / 65 / 100 / 128 and the three vocabulary
+    sizes -- and both within the float64 bound of test_mul_mat_decode_rows. 32 and 129 rows are the route's edges (the gemv and the big-batch kernels): the option
+    changes nothing there."""
+    g = torch.Generator(device="cuda").manual_seed(N + K)
+    w = (0.05 * torch.randn((N, K), generator=g, device="cuda")).half()
+    L = binding.lib()
+    for M in (32, 33, 40, 64, 65, 100, 128, 129):
+        a = torch.randn((M, K), generator=g, device="cuda").half()
+        want = _f64_product(a, w)
+        outs = {}
+        try:
+            for on in (1, 0):
+                binding.set_option("vocab_lds", on)
+                out = torch.full((M, N), float("nan"), dtype=torch.float32, device="cuda")
+                binding.check(L.wh_op_mul_mat(None, ptr(a), ptr(w), None, None, ptr(out), M, N, K))
+                torch.cuda.synchronize()
+                outs[on] = out
+        finally:
+            binding.set_option("vocab_lds", binding.get_option_default("vocab_lds"))
+        for on in (1, 0):
+            d = float((outs[on].double() - want).abs().max())
+            print("vocabulary product %3dx%dx%d vocab_lds %d: maxdiff %.3e" % (M, N, K, on, d))
+            assert d < 2e-5 * max(1.0, np.sqrt(K / 128)), (M, on)
+        assert torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32)), ("vocab_lds 1 and 0 differ", M, N, K)
+
+
+@pytest.mark.parametrize("N,K", [(4096, 1024), (5120, 1280)])
+@pytest.mark.parametrize("M", [33, 48, 64, 65, 80, 96, 97])
+def test_two_k_tiles_per_ring_slot_one_tile_path(M, N, K, golden):
+    """Option dec_lds_ks (round 6, default 2) on the one-tile path: 33 .. 128 rows against N >= 2048 and K <= 2048 (the MLP up-projection, the QKV product) run
+    launchDecRowsOneTile, which an FP16 epilogue reaches by default (the FP32 epilogue only with the diagnostic dec_wide_rows 2). dec_lds_ks 2 takes gemmDecTile's
+    K-pair instances for 4 row tiles (33 .. 64 rows) and 6 row tiles (65 .. 96 rows); dec_lds_ks 1 one K tile per ring slot. 97 rows take the 8-row-tile instance
+    under both settings (the edge). The GELU outputs (FP16) and the FP32 accumulators of the same instances are the same bits under both settings; the
+    accumulators are within the float64 bound and the GELU outputs within test_mul_mat_gelu's bound of the table GELU of the float64 product."""
+    g = torch.Generator(device="cuda").manual_seed(M * 7 + N + K)
+    a = torch.randn((M, K), generator=g, device="cuda").half()
+    w = (0.05 * torch.randn((N, K), generator=g, device="cuda")).half()
+    bias = torch.randn(N, generator=g, device="cuda")
+    want = _f64_product(a, w, bias)
+    L = binding.lib()
+    gelu, acc = {}, {}
+    try:
+        for ks in (2, 1):
+            binding.set_option("dec_lds_ks", ks)
+            binding.set_option("dec_wide_rows", binding.get_option_default("dec_wide_rows"))
+            o16 = torch.full((M, N), float("nan"), dtype=torch.float16, device="cuda")
+            binding.check(L.wh_op_mul_mat_gelu(None, ptr(a), ptr(w), ptr(bias), ptr(o16), M, N, K))
+            binding.set_option("dec_wide_rows", 2)
+            o32 = torch.full((M, N), float("nan"), dtype=torch.float32, device="cuda")
+            binding.check(L.wh_op_mul_mat(None, ptr(a), ptr(w), ptr(bias), None, ptr(o32), M, N, K))
+            torch.cuda.synchronize()
+            gelu[ks], acc[ks] = o16, o32
+    finally:
+        binding.set_option("dec_lds_ks", binding.get_option_default("dec_lds_ks"))
+        binding.set_option("dec_wide_rows", binding.get_option_default("dec_wide_rows"))
+    table = torch.from_numpy(golden["table_gelu"].astype(np.int32)).cuda()
+    want16 = table[(want.float().half().view(torch.int16).to(torch.int32) & 0xFFFF).long()].to(torch.int16).view(torch.float16).float()
+    for ks in (2, 1):
+        d = float((acc[ks].double() - want).abs().max())
+        dg = (gelu[ks].float() - want16).abs()
+        print("one-tile decode product %dx%dx%d dec_lds_ks %d: accumulators maxdiff %.3e, GELU outputs differ at %d of %d" % (M, N, K, ks, d, int((dg > 0).sum()), M * N))
+        assert d < 2e-5 * max(1.0, np.sqrt(K / 128)), ks
+        assert float((dg > 0).float().mean()) < 0.02 and bool((dg <= torch.clamp(want16.abs() * 2.0 ** -10, min=4e-3)).all()), ks
+    assert torch.equal(acc[1].view(torch.int32), acc[2].view(torch.int32)), ("dec_lds_ks 2 and 1: accumulators differ", M, N, K)
+    assert torch.equal(gelu[1].view(torch.int16), gelu[2].view(torch.int16)), ("dec_lds_ks 2 and 1: GELU outputs differ", M, N, K)
+
+
+@pytest.mark.parametrize("M,N,K", [(320, 1024, 4096), (448, 1024, 4096), (384, 1280, 5120), (320, 1024, 2176), (320, 1024, 2304)])
+def test_two_k_tiles_per_ring_slot_big_batch_path(M, N, K):
+    """Option dec_lds_ks on the 64 x 32 path of the big batches (129 .. 512 rows where 64 x 64 tiles leave fewer than 192 workgroups: the MLP down-projection):
+    with K >= 2048 and K % 512 == 0, dec_lds_ks 2 takes the K-pair instance and dec_lds_ks 1 one K tile per slot -- the same bits, and within the float64
+    bound. K = 2176 (K % 256: gemmDecRows) and K = 2304 (K % 512: one K tile per slot) run the same kernel under both settings (the route's edges)."""
+    g = torch.Generator(device="cuda").manual_seed(M * 7 + N + K)
+    a = torch.randn((M, K), generator=g, device="cuda").half()
+    w = (0.05 * torch.randn((N, K), generator=g, device="cuda")).half()
+    bias = torch.randn(N, generator=g, device="cuda")
+    res = torch.randn((M, N), generator=g, device="cuda")
+    want = _f64_product(a, w, bias, res)
+    L = binding.lib()
+    outs = {}
+    try:
+        for ks in (2, 1):
+            binding.set_option("dec_lds_ks", ks)
+            out = torch.full((M, N), float("nan"), dtype=torch.float32, device="cuda")
+            binding.check(L.wh_op_mul_mat(None, ptr(a), ptr(w), ptr(bias), ptr(res), ptr(out), M, N, K))
+            torch.cuda.synchronize()
+            outs[ks] = out
+    finally:
+        binding.set_option("dec_lds_ks", binding.get_option_default("dec_lds_ks"))
+    for ks in (2, 1):
+        d = float((outs[ks].double() - want).abs().max())
+        print("decode product %dx%dx%d dec_lds_ks %d: maxdiff %.3e" % (M, N, K, ks, d))
+        assert d < 2e-5 * max(1.0, np.sqrt(K / 128)), ks
+    assert torch.equal(outs[1].view(torch.int32), outs[2].view(torch.int32)), ("dec_lds_ks 2 and 1 differ", M, N, K)

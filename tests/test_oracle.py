@@ -301,3 +301,34 @@ def test_split_cross_attention_is_the_table_softmax():
                     local = wn.exp16((s[a:b] - s[a:b].max()).astype(np.float32)) * np.exp(np.float64(s[a:b].max()) - np.float64(m))
                     differs += int((np.abs(local - e_ref[a:b]) > 0).sum())
             assert differs > 0
+
+
+def test_beam_candidates_restatement(golden, tiny_model):
+    """wn.beam_candidates is built on the pinned sample_best: width 1 IS sample_best on the fixture's probability rows (both rule sets), the
+    next candidates are the best remaining tokens under the same mask with the specials skipped, and a row with fewer surviving tokens than
+    `width` repeats its last candidate with p = 0."""
+    sp = gf.special_tokens(tiny_model.hparams)
+    specials = (sp["beg"], sp["sot"], sp["solm"], sp["not_"])
+    for i in range(5):
+        probs = wn.softmax_table(golden["logits%d" % i][None, :])[0]
+        for force, initial in ((False, False), (True, i == 0), (False, True)):
+            want = wn.sample_best(probs, *specials, force, initial)
+            assert wn.beam_candidates(probs, *specials, force, initial, width=1) == [want]
+            c = wn.beam_candidates(probs, *specials, force, initial, width=8)
+            ids = [x["id"] for x in c]
+            assert c[0] == want and len(set(ids)) == 8 and not set(ids[1:]) & {sp["sot"], sp["solm"], sp["not_"]}
+            assert all(a["p"] >= b["p"] for a, b in zip(c, c[1:]))
+            assert all(x["tid"] == want["tid"] and x["pt"] == want["pt"] and x["ptsum"] == want["ptsum"] for x in c)
+    # hand-made rows: ties to the lower index, specials skipped after candidate 0, the initial cap, fewer survivors than width
+    beg = 20
+    p = np.zeros(beg + 3, np.float32)
+    p[[3, 5, 7, 9]] = [0.25, 0.25, 0.125, 0.25]
+    p[beg:] = 1.0 / 64
+    c = wn.beam_candidates(p, beg, 5, 6, 8, width=4)
+    assert [x["id"] for x in c] == [3, 9, 7, beg] and [x["p"] for x in c] == [0.25, 0.25, 0.125, 1.0 / 64]
+    c = wn.beam_candidates(p, beg, 5, 6, 8, force_timestamp=True, width=5)
+    assert [x["id"] for x in c] == [beg, beg + 1, beg + 2, beg + 2, beg + 2] and [x["p"] for x in c] == [1.0 / 64] * 3 + [0.0, 0.0]
+    q = np.zeros(beg + 200, np.float32)
+    q[beg + 150], q[beg + 100], q[beg + 40] = 0.5, 0.25, 0.125
+    c = wn.beam_candidates(q, beg, 5, 6, 8, force_timestamp=True, is_initial=True, width=3)
+    assert [x["id"] for x in c] == [beg + 100, beg + 40, beg]

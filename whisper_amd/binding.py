@@ -48,6 +48,7 @@ EXPORTS = [
     "wh_buffer_alloc", "wh_buffer_free", "wh_buffer_upload", "wh_buffer_upload_async", "wh_buffer_download",
     "wh_mel_spectrogram", "wh_encode", "wh_encode_windows", "wh_decode", "wh_sample_best", "wh_beam_candidates", "wh_reorder_self_cache", "wh_beam_window_start", "wh_beam_window_continue", "wh_beam_window_status", "wh_beam_window_records", "wh_decode_greedy", "wh_decode_window_start", "wh_decode_window_finish", "wh_decode_window_continue", "wh_decode_window_fetch", "wh_decode_window_start_ragged", "wh_decode_window_ready", "wh_mel_spectrogram_window", "wh_mel_spectrogram_batch", "wh_profile_enable", "wh_profile_read", "wh_debug_read", "wh_debug_probe", "wh_debug_set_tuning", "wh_debug_set_option", "wh_debug_get_option",
     "wh_op_mul_mat", "wh_op_mul_mat_gelu", "wh_op_layer_norm", "wh_op_flash_attention", "wh_op_soft_max", "wh_op_decoder_attention", "wh_op_decoder_cross_attention",
+    "wh_op_vocab_soft_max", "wh_op_sample_best", "wh_op_beam_candidates", "wh_op_reorder_self_cache",
 ]
 
 
@@ -157,6 +158,10 @@ def lib():
         L.wh_op_soft_max.argtypes = [vp, vp, i32, i32]
         L.wh_op_decoder_attention.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32]
         L.wh_op_decoder_cross_attention.argtypes = [vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, i32, i32, i32, i32, i32]
+        L.wh_op_vocab_soft_max.argtypes = [vp, vp, vp, i32, i32]
+        L.wh_op_sample_best.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
+        L.wh_op_beam_candidates.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
+        L.wh_op_reorder_self_cache.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32]
         _lib = L
     return _lib
 

@@ -272,6 +272,9 @@ namespace wh
 					if( !skip ) best = better( best, ArgMax{ p[ c ], c } );
 				}
 				best = blockArgMax( best, sha );
+				// no token left under the mask (fewer than `width` survive): the rest repeats the last candidate with probability 0 below, not the
+				// sentinel's token 0 at -inf (candidate 0 of an empty row keeps sampleBest's own answer)
+				if( found > 0 && ( best.i < 0 || best.i >= nVocab ) ) break;
 				taken[ nTaken++ ] = best.i;
 				const bool special = best.i == tokenSot || best.i == tokenSolm || best.i == tokenNot;
 				// sampleBest gives up after four rounds and takes the fourth token whatever it is: only candidate 0 can meet that rule

@@ -81,8 +81,9 @@ namespace wh
 		int crossMfma = 1;			 // "cross_mfma": the cross-attention of a decode step for hypothesis groups (beam search): 1 = attentionDecM (scores and P.V on the matrix cores, every
 									 // load of the first half in flight at once), 0 = attentionDecG<NQ, true> (rounds 2-5)
 		int vocabLds = 1;			 // "vocab_lds": the vocabulary product of 33 .. 128 rows: 1 = gemmDecTile's 64 x 64 tiles (one or two row tiles), 0 = gemmAllRows (32 columns x all rows per workgroup, rounds 3-5)
-		int beamRegs = 1;			 // "beam_regs": the vocabulary softmax over rows (beam steps, wh_op_soft_max, wh_decode's probabilities): 1 = the row in registers (softMaxRowsReg: one
-									 // read and one write, the same bits: 37.8 -> 18.3 us at 40 rows), 0 = softMaxRows (three reads, two writes)
+		int beamRegs = 1;			 // "beam_regs": the vocabulary softmax over rows (launchVocabSoftMax: wh_decode's probabilities, beam steps, wh_op_vocab_soft_max; NOT wh_op_soft_max,
+									 // which is always softMaxRows): 1 = the row in registers (softMaxRowsReg, up to SC_PER * 1024 = 52224 columns, softMaxRows beyond: one read and one
+									 // write, the same bits: 37.8 -> 18.3 us at 40 rows), 0 = softMaxRows (three reads, two writes)
 		int reorderGroup = 1;		 // "reorder_group": the ranked beam step's cache reorder: 1 = reorderCacheGroup (a window's hypotheses in one launch through registers), 0 = the two-phase
 									 // copy through the scratch cache (round 4)
 		int gemmBigMinRows = 8192;	 // "gemm_big_min_rows": products of at least this many rows (and 300 tiles of 256 x 256) take the persistent 256 x 256 kernel (rounds 3-5: 16384;

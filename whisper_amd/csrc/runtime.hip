@@ -3102,6 +3102,52 @@ int wh_op_soft_max( void* stream, float* x, int rows, int cols )
 	return launchSoftMaxRows( x, rows, cols, (hipStream_t)stream );
 }
 
+int wh_op_vocab_soft_max( void* stream, const float* logits, float* probs, int rows, int cols )
+{
+	if( !logits || !probs || rows < 1 || cols < 1 ) { setError( "vocab_soft_max: null pointer or empty shape" ); return WH_E_INVALIDARG; }
+	return launchVocabSoftMax( logits, probs, rows, cols, (hipStream_t)stream );
+}
+
+static bool tokenArgsOk( const float* probs, const wh_token_data* out, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot )
+{
+	return probs && out && rows >= 1 && nVocab >= 1 && tokenBeg >= 1 && tokenBeg < nVocab && tokenSot >= 0 && tokenSot < tokenBeg && tokenSolm >= 0 &&
+		tokenSolm < tokenBeg && tokenNot >= 0 && tokenNot < tokenBeg;
+}
+
+int wh_op_sample_best( void* stream, const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot,
+	int forceTimestamp, int isInitial, wh_token_data* out )
+{
+	static_assert( sizeof( wh_token_data ) == sizeof( TokenData ), "token data layout" );
+	if( !tokenArgsOk( probs, out, rows, nVocab, tokenBeg, tokenSot, tokenSolm, tokenNot ) ) { setError( "sample_best: bad pointer, size or token id" ); return WH_E_INVALIDARG; }
+	return launchSampleBest( probs, rows, nVocab, tokenBeg, tokenSot, tokenSolm, tokenNot, forceTimestamp ? 1 : 0, isInitial ? 1 : 0, (TokenData*)out,
+		(hipStream_t)stream );
+}
+
+int wh_op_beam_candidates( void* stream, const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot,
+	int forceTimestamp, int isInitial, int width, wh_token_data* out )
+{
+	if( !tokenArgsOk( probs, out, rows, nVocab, tokenBeg, tokenSot, tokenSolm, tokenNot ) || width < 1 || width > 8 )
+	{
+		setError( "beam_candidates: bad pointer, size, token id or width (1 .. 8)" );
+		return WH_E_INVALIDARG;
+	}
+	return launchBeamCandidates( probs, rows, nVocab, tokenBeg, tokenSot, tokenSolm, tokenNot, forceTimestamp ? 1 : 0, isInitial ? 1 : 0, width,
+		(TokenData*)out, (hipStream_t)stream );
+}
+
+int wh_op_reorder_self_cache( void* stream, void* cacheK, void* cacheV, void* scratchK, void* scratchV, const int32_t* parents,
+	const int32_t* rowsDev, int layers, int sequences, int maxSeq, int heads, int keyStride, int group )
+{
+	if( !cacheK || !cacheV || !scratchK || !scratchV || !parents || !rowsDev ) { setError( "reorder_self_cache: null pointer" ); return WH_E_INVALIDARG; }
+	if( layers < 1 || sequences < 1 || sequences > maxSeq || heads < 1 || keyStride < 1 || group < 1 || group > sequences )
+	{
+		setError( "reorder_self_cache: need layers, heads, keyStride >= 1, 1 <= group <= sequences <= maxSeq" );
+		return WH_E_INVALIDARG;
+	}
+	return launchReorderCacheDev( (f16*)cacheK, (f16*)cacheV, (f16*)scratchK, (f16*)scratchV, parents, rowsDev, layers, sequences, maxSeq, heads,
+		keyStride, group, (hipStream_t)stream );
+}
+
 
 // ------------------------------------------------------------------------------------------------------------------
 // micro-benchmarks used by tools/gemm_probe.py (development aid; not on the product path)
