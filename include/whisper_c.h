@@ -28,6 +28,9 @@ int32_t whisperc_run_full( void* ctx, const float* pcm, uint32_t nSamples, const
 	const int32_t* promptTokens, int nPrompt, int nMaxTextCtx /* < 0 keeps the default 16384 */ );
 /* The same with eSamplingStrategy::BeamSearch and beam_search.beam_width = beamWidth (1 .. 8; the reference declares the strategy,
  * Whisper/API/sFullParams.h:10-13, and implements only Greedy): beamWidth hypotheses per window share one pass over its cross-attention K/V. */
+/* whisperc_run_full + sFullParams::offset_ms / duration_ms (0 = to the end): the range of the buffer that is transcribed */
+int32_t whisperc_run_full_range( void* ctx, const float* pcm, uint32_t nSamples, const char* language, uint32_t flags, int maxTokens,
+	const int32_t* promptTokens, int nPrompt, int nMaxTextCtx, int offsetMs, int durationMs );
 /* whisperc_run_full + sFullParams::audio_ctx (encoder positions / cross-attention keys per window; 0 = the model's) */
 int32_t whisperc_run_full_audio_ctx( void* ctx, const float* pcm, uint32_t nSamples, const char* language, uint32_t flags, int maxTokens,
 	const int32_t* promptTokens, int nPrompt, int nMaxTextCtx, int audioCtx );
@@ -61,6 +64,26 @@ int32_t whisperc_batch_run( void* runner, uint32_t count, const float* const* pc
 int32_t whisperc_tr_counts( void* result, uint32_t* segments, uint32_t* tokens );
 int32_t whisperc_tr_segment( void* result, uint32_t index, uint64_t* t0, uint64_t* t1, uint32_t* firstToken, uint32_t* countTokens, char* text, uint32_t textCap );
 int32_t whisperc_tr_token( void* result, uint32_t index, int32_t* id, float* p, float* pt, float* ptsum, uint64_t* t0, uint64_t* t1, float* vlen );
+/* Language detection (language "auto" / NULL / "" in the run entry points above: the language of every recording is detected on its first 30 s
+ * window, frame 0 whatever the run's offset, and the run continues with it).
+ * whisperc_detect_language: whisper_lang_auto_detect of the reference's CPU model (Whisper/source/whisper.cpp:2428-2495) on a mono FP32 16 kHz
+ *   buffer: the window at offsetMs, probs[ id ] for the first probsCap language ids (99 languages; may be NULL), *langId = the winner.
+ *   NOTE the reference's probs are a SECOND softmax over the language tokens' probabilities (exp( p ) / sum exp( p ) over numbers in [0, 1]):
+ *   a clear winner comes back as ~0.02, not ~0.9. Offset before the start / past the end, or a model that is not multilingual: E_INVALIDARG.
+ * whisperc_detected_language: what the last run (or whisperc_detect_language) on this context detected -- its code ("en", up to 4 characters + NUL)
+ *   and its probs entry; S_FALSE (1) when nothing was detected (a named language, an .en model, less than a second of audio).
+ * whisperc_debug_lang_probs: the host half on its own (no device): probs[ n ] from the n language-token probabilities p; returns the winner. */
+int32_t whisperc_detect_language( void* ctx, const float* pcm, uint32_t nSamples, int32_t offsetMs, float* probs, uint32_t probsCap, int32_t* langId );
+int32_t whisperc_detected_language( void* ctx, char* code5, float* p );
+int32_t whisperc_debug_lang_probs( const float* p, int32_t n, float* probs );
+/* Of a batch runner's per-stream result (whisperc_batch_run with language "auto": every stream gets ITS OWN language): the code and lang_probs entry
+ * of the language the stream was detected and transcribed in; S_FALSE when the language was named. */
+int32_t whisperc_tr_language( void* result, char* code5, float* p );
+/* wh_context_set_flags( flags, parityThreads ) of include/whisper_hip.h on the device context behind this iContext, for parity tests: with
+ * WH_FLAG_PARITY_EXACT (8) whisperc_detect_language returns the reference's lang_probs bit for bit. This context only. */
+int32_t whisperc_debug_context_flags( void* ctx, uint32_t flags, int32_t parityThreads );
+/* The code of language id (0 .. 98; the language token is sot + 1 + id) -> code5; S_FALSE beyond the table */
+int32_t whisperc_language_code( int32_t id, char* code5 );
 /* iContext::timingsPrint */
 int32_t whisperc_timings_print( void* ctx );
 /* One line of the profiler output, formatted like ProfileCollection::Measure::print (Whisper/Utils/ProfileCollection.cpp:113-170):

@@ -218,6 +218,19 @@ WH_API int wh_encode_windows( wh_context* c, const wh_mel_window* windows, int b
  * Synchronises the stream before returning when any host output is requested. */
 WH_API int wh_decode( wh_context* c, const int32_t* tokens, int batch, int nTokens, int nPast, float* logitsHost, float* probsHost );
 
+/* Language detection. Replaces whisper_lang_auto_detect (Whisper/source/whisper.cpp:2428-2495; the reference's GPU model has none).
+ * After wh_encode / wh_encode_windows of at least `batch` windows: one decoder step of [sot] at position 0 for windows 0 .. batch-1, then for every window
+ * the probabilities of the language tokens sot + 1 .. sot + n_lang under the full-vocabulary softmax -- what wh_decode's probsHost holds at those columns,
+ * bit for bit (under WH_FLAG_PARITY_EXACT: the reference's own bits) -- and the index of the largest (ties to the lower id). The [batch][n_vocab] rows are
+ * never written or downloaded on the timed path. The reference's lang_probs are a SECOND softmax over these numbers (exp( p ) / sum exp( p )), which the
+ * caller applies on the host if it wants them.
+ * langP: HOST [batch][n_lang] (may be NULL), best: HOST [batch]. Leaves the sequences as wh_encode left them, so the windows can be decoded right away
+ * without being encoded again. The probabilities wh_sample_best / wh_beam_candidates read belong to the last wh_decode and are UNDEFINED after this
+ * call (the timed path never writes the step's full rows): decode before sampling again. On a hypothesis-group context `batch` counts windows. WH_E_INVALIDARG on a model that is not multilingual. */
+WH_API int wh_lang_detect( wh_context* c, int batch, float* langP, int32_t* best );
+/* Language tokens of the model's vocabulary: n_vocab - 51766 (99 at 51865, 100 at the large-v3 shape), 0 for .en models. */
+WH_API int wh_model_lang_count( const wh_model* m );
+
 /* sTokenData of the reference (Whisper/Whisper/sTokenData.h): the result of ContextImpl::sampleBest. */
 typedef struct wh_token_data
 {
@@ -405,6 +418,10 @@ WH_API int wh_op_soft_max( void* stream, float* x, int rows, int cols );
 /* The decoder's vocabulary softmax (same semantics as wh_op_soft_max), out of place: probs [rows][cols] = softmax( logits [rows][cols] ).
  * Takes the kernel the option "beam_regs" selects (the row in registers up to 52224 columns, the three-pass kernel beyond). */
 WH_API int wh_op_vocab_soft_max( void* stream, const float* logits, float* probs, int rows, int cols );
+/* The language-detection kernel of wh_lang_detect on logits [rows][nVocab]: langP [rows][nLang] = the probabilities wh_op_vocab_soft_max gives at columns
+ * tokenSot + 1 .. tokenSot + nLang, bit for bit, without writing the other columns; best [rows] = the index (0 .. nLang - 1) of the largest, exact ties
+ * to the lower index. The row stays in registers: nVocab <= 52224; 1 <= nLang <= 1024 and the block inside the row, or WH_E_INVALIDARG. */
+WH_API int wh_op_lang_probs( void* stream, const float* logits, int rows, int nVocab, int tokenSot, int nLang, float* langP, int32_t* best );
 /* wh_sample_best on probabilities [rows][nVocab]: out [rows]. tokenBeg .. nVocab - 1 are the timestamps; the specials are < tokenBeg. */
 WH_API int wh_op_sample_best( void* stream, const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot,
 	int forceTimestamp, int isInitial, wh_token_data* out );

@@ -48,6 +48,7 @@ def lib():
         L.whisperc_is_multilingual.argtypes = [vp]
         L.whisperc_tokenize.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int32), C.c_int]
         L.whisperc_run_full.argtypes = [vp, vp, C.c_uint32, C.c_char_p, C.c_uint32, C.c_int, vp, C.c_int, C.c_int]
+        L.whisperc_run_full_range.argtypes = [vp, vp, C.c_uint32, C.c_char_p, C.c_uint32, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]
         L.whisperc_run_full_audio_ctx.argtypes = [vp, vp, C.c_uint32, C.c_char_p, C.c_uint32, C.c_int, vp, C.c_int, C.c_int, C.c_int]
         L.whisperc_run_full_beam.argtypes = [vp, vp, C.c_uint32, C.c_char_p, C.c_uint32, C.c_int, vp, C.c_int, C.c_int, C.c_int]
         L.whisperc_result_counts.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -66,8 +67,36 @@ def lib():
                                           C.POINTER(C.c_uint32), C.c_char_p, C.c_uint32]
         L.whisperc_tr_token.argtypes = [vp, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_float)]
+        L.whisperc_detect_language.argtypes = [vp, vp, C.c_uint32, C.c_int32, vp, C.c_uint32, C.POINTER(C.c_int32)]
+        L.whisperc_detected_language.argtypes = [vp, C.c_char_p, C.POINTER(C.c_float)]
+        L.whisperc_debug_lang_probs.argtypes = [vp, C.c_int32, vp]
+        L.whisperc_language_code.argtypes = [C.c_int32, C.c_char_p]
+        L.whisperc_tr_language.argtypes = [vp, C.c_char_p, C.POINTER(C.c_float)]
+        L.whisperc_debug_context_flags.argtypes = [vp, C.c_uint32, C.c_int32]
         _lib = L
     return _lib
+
+
+N_LANGUAGES = 99
+
+
+def language_codes() -> List[str]:
+    """The codes of the 99 languages in id order (the language token of id i is sot + 1 + i)."""
+    out = []
+    buf = C.create_string_buffer(8)
+    for i in range(N_LANGUAGES):
+        _check(lib().whisperc_language_code(i, buf), "languageCode")
+        out.append(buf.value.decode())
+    return out
+
+
+def finish_language_probs(p: np.ndarray):
+    """The host half of language detection on its own (no device): (winner id, lang_probs) from the language tokens' probabilities --
+    the reference's second softmax, exp( p ) / sum exp( p ) summed in descending order in single precision."""
+    p = np.ascontiguousarray(p, np.float32)
+    out = np.zeros(len(p), np.float32)
+    best = lib().whisperc_debug_lang_probs(p.ctypes.data_as(C.c_void_p), len(p), out.ctypes.data_as(C.c_void_p))
+    return best, out
 
 
 def set_host_loop_rules(mode: int):
@@ -149,11 +178,15 @@ class Context:
 
     def run_full(self, pcm: np.ndarray, language: str = "en", flags: int = 0, max_tokens: int = 0,
                  prompt: Optional[Sequence[int]] = None, n_max_text_ctx: int = -1, max_len: int = 0, thold_pt: float = 0.01,
-                 thold_ptsum: float = 0.01, beam_width: int = 0, audio_ctx: int = 0) -> int:
-        """runFull on mono float32 16 kHz PCM. Returns the HRESULT (0 = S_OK, 1 = S_FALSE: less than 1 s of audio).
+                 thold_ptsum: float = 0.01, beam_width: int = 0, audio_ctx: int = 0, offset_ms: int = 0, duration_ms: int = 0) -> int:
+        """runFull on mono float32 16 kHz PCM. Returns the HRESULT (0 = S_OK, 1 = S_FALSE: less than 1 s of audio). language "auto" (or ""): detected
+        on the window at frame 0, whatever the run's offset (detected_language tells which).
         With TOKEN_TIMESTAMPS in flags the tokens of results() carry t0 / t1 / vlen and max_len > 0 wraps the segments."""
         pcm = np.ascontiguousarray(pcm, np.float32)
         pt = np.ascontiguousarray(prompt if prompt is not None else [], np.int32)
+        if offset_ms or duration_ms:            # sFullParams::offset_ms / duration_ms: the range that is transcribed
+            return _check(lib().whisperc_run_full_range(self.h, pcm.ctypes.data_as(C.c_void_p), len(pcm), language.encode(), flags, max_tokens,
+                                                        pt.ctypes.data_as(C.c_void_p) if len(pt) else None, len(pt), n_max_text_ctx, offset_ms, duration_ms), "runFull")
         if audio_ctx:               # sFullParams::audio_ctx (ContextImpl.cpp:488-489)
             return _check(lib().whisperc_run_full_audio_ctx(self.h, pcm.ctypes.data_as(C.c_void_p), len(pcm), language.encode(), flags, max_tokens,
                                                             pt.ctypes.data_as(C.c_void_p) if len(pt) else None, len(pt), n_max_text_ctx, audio_ctx), "runFull")
@@ -179,6 +212,29 @@ class Context:
                                                 pt.ctypes.data_as(C.c_void_p) if len(pt) else None, len(pt), n_max_text_ctx,
                                                 prog, 4096, C.byref(n)), "runStreamed")
         return hr, list(prog[:min(n.value, 4096)])
+
+    def detect_language(self, pcm: np.ndarray, offset_ms: int = 0):
+        """whisper_lang_auto_detect on the 30 s window at offset_ms of mono float32 16 kHz PCM: (code, {code: p}). The p are the reference's
+        lang_probs: a SECOND softmax over the language tokens' probabilities, so a clear winner reads ~0.02, not ~0.9; their order is what counts."""
+        pcm = np.ascontiguousarray(pcm, np.float32)
+        probs = np.zeros(N_LANGUAGES, np.float32)
+        lang = C.c_int32(-1)
+        _check(lib().whisperc_detect_language(self.h, pcm.ctypes.data_as(C.c_void_p), len(pcm), offset_ms, probs.ctypes.data_as(C.c_void_p), len(probs),
+                                              C.byref(lang)), "detectLanguage")
+        codes = language_codes()
+        return codes[lang.value], {c: float(v) for c, v in zip(codes, probs)}
+
+    def set_device_flags(self, flags: int, parity_threads: int = 1):
+        """wh_context_set_flags on the device context behind this iContext (parity tests: binding.WH_FLAG_PARITY_EXACT)."""
+        _check(lib().whisperc_debug_context_flags(self.h, flags, parity_threads), "setDeviceFlags")
+
+    @property
+    def detected_language(self):
+        """(code, p) of what the last run with language "auto" (or detect_language) on this context detected; None when nothing was detected."""
+        code = C.create_string_buffer(8)
+        p = C.c_float()
+        hr = _check(lib().whisperc_detected_language(self.h, code, C.byref(p)), "detectedLanguage")
+        return (code.value.decode(), p.value) if hr == 0 else None
 
     def results(self):
         """getResults(Tokens | Timestamps): list of segments {t0, t1 (100 ns ticks), text, tokens[{id, p, pt, ptsum}]}."""
@@ -245,7 +301,8 @@ class BatchRunner:
     def run(self, streams, language: str = "en", flags: int = 0, max_tokens: int = 0, prompt: Optional[Sequence[int]] = None,
             n_max_text_ctx: int = -1, want_results: bool = True):
         """streams: list of float32 PCM arrays, or of (pcm, first_sample, count_samples) -- pieces of a recording share the array.
-        Returns (HRESULT, [segments per stream or None], [per-stream HRESULT])."""
+        Returns (HRESULT, [segments per stream or None], [per-stream HRESULT]). language "auto": every stream is detected on ITS OWN first window
+        and transcribed in its own language; self.languages then holds (code, p) per stream (None where nothing was detected)."""
         n = len(streams)
         keep, ptrs, lens, first, cnt = [], (C.c_void_p * n)(), (C.c_uint32 * n)(), (C.c_int64 * n)(), (C.c_int64 * n)()
         for i, s in enumerate(streams):
@@ -262,8 +319,12 @@ class BatchRunner:
                                       pt.ctypes.data_as(C.c_void_p) if len(pt) else None, len(pt), n_max_text_ctx, res, per)
         self.last_run_seconds = time.perf_counter() - t0          # the library call alone (bench.py)
         out = []
+        self.languages = []
         for i in range(n):
             out.append(read_result(res[i]) if (res[i] and want_results) else None)
+            code, p = C.create_string_buffer(8), C.c_float()
+            detected = bool(res[i]) and lib().whisperc_tr_language(res[i], code, C.byref(p)) == 0
+            self.languages.append((code.value.decode(), p.value) if detected else None)
             if res[i]:
                 lib().whisperc_release(res[i])
         _check(hr, "runFullBatch")

@@ -49,6 +49,7 @@ EXPORTS = [
     "wh_mel_spectrogram", "wh_encode", "wh_encode_windows", "wh_decode", "wh_sample_best", "wh_beam_candidates", "wh_reorder_self_cache", "wh_beam_window_start", "wh_beam_window_continue", "wh_beam_window_status", "wh_beam_window_records", "wh_decode_greedy", "wh_decode_window_start", "wh_decode_window_finish", "wh_decode_window_continue", "wh_decode_window_fetch", "wh_decode_window_start_ragged", "wh_decode_window_ready", "wh_mel_spectrogram_window", "wh_mel_spectrogram_batch", "wh_profile_enable", "wh_profile_read", "wh_debug_read", "wh_debug_probe", "wh_debug_set_tuning", "wh_debug_set_option", "wh_debug_get_option",
     "wh_op_mul_mat", "wh_op_mul_mat_gelu", "wh_op_layer_norm", "wh_op_flash_attention", "wh_op_soft_max", "wh_op_decoder_attention", "wh_op_decoder_cross_attention",
     "wh_op_vocab_soft_max", "wh_op_sample_best", "wh_op_beam_candidates", "wh_op_reorder_self_cache",
+    "wh_lang_detect", "wh_model_lang_count", "wh_op_lang_probs",
 ]
 
 
@@ -162,6 +163,9 @@ def lib():
         L.wh_op_sample_best.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
         L.wh_op_beam_candidates.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
         L.wh_op_reorder_self_cache.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32]
+        L.wh_lang_detect.argtypes = [vp, i32, vp, vp]
+        L.wh_model_lang_count.argtypes = [vp]
+        L.wh_op_lang_probs.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
         _lib = L
     return _lib
 
@@ -240,6 +244,13 @@ class HipModel:
     @classmethod
     def from_file(cls, path: str) -> "HipModel":
         return cls.from_ggml(gf.read_model(path))
+
+    def lang_count(self) -> int:
+        """Language tokens of the vocabulary (sot + 1 .. sot + n): 0 for .en models."""
+        n = lib().wh_model_lang_count(self.handle)
+        if n < 0:
+            check(n)
+        return n
 
     def arena(self):
         p = C.c_void_p()
@@ -376,6 +387,16 @@ class HipContext:
                               logits.ctypes.data_as(C.c_void_p) if want_logits else None,
                               probs.ctypes.data_as(C.c_void_p) if want_probs else None))
         return logits, probs
+
+    def lang_detect(self, batch: Optional[int] = None):
+        """whisper_lang_auto_detect for windows 0 .. batch-1 of the last encode (default: all of them): (p [batch][n_lang], best [batch]) -- the
+        full-vocabulary softmax probabilities of the language tokens and the index of the largest. The windows can be decoded right afterwards."""
+        b = self.batch if batch is None else batch
+        n_lang = self.model.lang_count()
+        p = np.empty((b, max(n_lang, 1)), np.float32)
+        best = np.empty(b, np.int32)
+        check(lib().wh_lang_detect(self.handle, b, p.ctypes.data_as(C.c_void_p), best.ctypes.data_as(C.c_void_p)))
+        return p, best
 
     def sample_best(self, batch: int, force_timestamp: bool = False, is_initial: bool = False):
         out = (TokenDataC * batch)()

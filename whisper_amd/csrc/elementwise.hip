@@ -341,6 +341,70 @@ namespace wh
 				if( c < cols ) y[ c ] = v[ i ] * inv;
 			}
 		}
+		// ---- language detection: the vocabulary softmax's statistics, only the language columns written (whisper.cpp:2428-2495) ----
+		// Row r of the logits stands rowStride floats behind row r - 1 (the first sequence of every hypothesis group). The row maximum, e = exp16( x - max ) and the
+		// double sum thread by thread in column order are softMaxRows' / softMaxRowsReg's, so p = e * float( 1 / sum ) at columns tokenSot + 1 .. tokenSot + nLang has
+		// the same bits as what those kernels write there; the 51865-float row of probabilities is never written. best = the language with the largest p, exact
+		// ties to the lower id. The row stays in registers between the two sweeps like softMaxRowsReg's (cols <= SC_PER * 1024; 124 VGPRs, no scratch). Reading it
+		// twice instead (46 VGPRs) was built and measured: 30.9 / 53.2 us at 64 / 448 rows x 51865 against 18.0 / 36.8 us for this one -- not kept. nLang <= 1024.
+		__global__ void __launch_bounds__( 1024 ) langProbsKernel( const float* __restrict__ in, long long rowStride, int cols, int tokenSot, int nLang,
+			float* __restrict__ langP, int* __restrict__ best )
+		{
+			__shared__ float shf[ 16 ];
+			__shared__ double shd[ 16 ];
+			__shared__ ArgMax sha[ 16 ];
+			const float* const x = in + (long long)blockIdx.x * rowStride;
+			float v[ SC_PER ];
+			float m = -INFINITY;
+	#pragma unroll
+			for( int i = 0; i < SC_PER; i++ )
+			{
+				const int c = threadIdx.x + 1024 * i;
+				const float t = x[ c < cols ? c : cols - 1 ];
+				v[ i ] = c < cols ? t : -INFINITY;
+				m = fmaxf( m, v[ i ] );
+			}
+			m = blockMax<16>( m, shf );
+			double s = 0.0;
+	#pragma unroll
+			for( int i = 0; i < SC_PER; i++ )
+			{
+				const float e = ( v[ i ] == -INFINITY ) ? 0.0f : exp16( v[ i ] - m );
+				s += (double)e;
+			}
+			s = blockSumD<16>( s, shd );
+			const float inv = (float)( 1.0 / s );
+			// the language block is at most 1024 columns: thread t owns language t (the few logits are read once more, from the cache)
+			ArgMax a = { -1.0f, 0x7fffffff };
+			if( (int)threadIdx.x < nLang )
+			{
+				const float x1 = x[ tokenSot + 1 + threadIdx.x ];
+				const float e = ( x1 == -INFINITY ) ? 0.0f : exp16( x1 - m );
+				a.v = e * inv;
+				a.i = threadIdx.x;
+				langP[ (long long)blockIdx.x * nLang + threadIdx.x ] = a.v;
+			}
+			a = blockArgMax( a, sha );
+			if( threadIdx.x == 0 ) best[ blockIdx.x ] = ( a.i < 0 || a.i >= nLang ) ? 0 : a.i;	  // (NaN compares false everywhere and leaves the sentinel)
+		}
+
+		// The same two outputs from probabilities that exist already (WH_FLAG_PARITY_EXACT: the reference's own bits, exact.hip): a gather and an argmax.
+		__global__ void __launch_bounds__( 1024 ) langGatherKernel( const float* __restrict__ probs, long long rowStride, int tokenSot, int nLang,
+			float* __restrict__ langP, int* __restrict__ best )
+		{
+			__shared__ ArgMax sha[ 16 ];
+			const float* const p = probs + (long long)blockIdx.x * rowStride;
+			ArgMax a = { -1.0f, 0x7fffffff };
+			if( (int)threadIdx.x < nLang )
+			{
+				a.v = p[ tokenSot + 1 + threadIdx.x ];
+				a.i = threadIdx.x;
+				langP[ (long long)blockIdx.x * nLang + threadIdx.x ] = a.v;
+			}
+			a = blockArgMax( a, sha );
+			if( threadIdx.x == 0 ) best[ blockIdx.x ] = ( a.i < 0 || a.i >= nLang ) ? 0 : a.i;
+		}
+
 		// ---- self-attention cache rows of sequence parents[j] -> sequence j (beam search: hypotheses change lineage) ----
 		// Two launches through a scratch copy, so that a permutation (j <- p while p <- q) reads only rows nobody has overwritten:
 		// phase 0: scratch[ j ] = cache[ parents[ j ] ], phase 1: cache[ j ] = scratch[ j ]; sequences with parents[ j ] == j are skipped.
@@ -974,6 +1038,30 @@ namespace wh
 			hipLaunchKernelGGL( softMaxRowsReg, dim3( rows ), dim3( 1024 ), 0, stream, logits, probs, nVocab );
 		else
 			hipLaunchKernelGGL( softMaxRows, dim3( rows ), dim3( 1024 ), 0, stream, logits, probs, nVocab );
+		WH_HIP( hipGetLastError() );
+		return 0;
+	}
+
+	int launchLangProbs( const float* logits, long long rowStride, int rows, int nVocab, int tokenSot, int nLang, float* langP, int* best, hipStream_t stream )
+	{
+		if( rows < 1 || nLang < 1 || nLang > 1024 || tokenSot < 0 || (long long)tokenSot + 1 + nLang > nVocab || rowStride < nVocab || nVocab > SC_PER * 1024 )
+		{
+			setError( "langProbs: the language block must lie inside the row and hold 1 .. 1024 tokens, the vocabulary at most 52224" );
+			return -1;
+		}
+		hipLaunchKernelGGL( langProbsKernel, dim3( rows ), dim3( 1024 ), 0, stream, logits, rowStride, nVocab, tokenSot, nLang, langP, best );
+		WH_HIP( hipGetLastError() );
+		return 0;
+	}
+
+	int launchLangGather( const float* probs, long long rowStride, int rows, int nVocab, int tokenSot, int nLang, float* langP, int* best, hipStream_t stream )
+	{
+		if( rows < 1 || nLang < 1 || nLang > 1024 || tokenSot < 0 || (long long)tokenSot + 1 + nLang > nVocab || rowStride < nVocab )
+		{
+			setError( "langGather: the language block must lie inside the row and hold 1 .. 1024 tokens" );
+			return -1;
+		}
+		hipLaunchKernelGGL( langGatherKernel, dim3( rows ), dim3( 1024 ), 0, stream, probs, rowStride, tokenSot, nLang, langP, best );
 		WH_HIP( hipGetLastError() );
 		return 0;
 	}

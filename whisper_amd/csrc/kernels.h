@@ -313,6 +313,11 @@ namespace wh
 	};
 	// probs[row] = table softmax( logits[row] ) (ggml.c:5030-5090)
 	int launchVocabSoftMax( const float* logits, float* probs, int rows, int nVocab, hipStream_t stream );
+	// language detection (whisper_lang_auto_detect, whisper.cpp:2428-2495): langP [rows][nLang] = the softmax probabilities of tokens tokenSot + 1 ..
+	// tokenSot + nLang of every row (row r at logits + r * rowStride), the bits launchVocabSoftMax writes at those columns; best [rows] = the index of the
+	// largest, ties to the lower. launchLangGather: the same from probabilities that exist already (the exact mode's).
+	int launchLangProbs( const float* logits, long long rowStride, int rows, int nVocab, int tokenSot, int nLang, float* langP, int* best, hipStream_t stream );
+	int launchLangGather( const float* probs, long long rowStride, int rows, int nVocab, int tokenSot, int nLang, float* langP, int* best, hipStream_t stream );
 	// ContextImpl::sampleBest on the device
 	int launchSampleBest( const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot,
 		int forceTimestamp, int isInitial, TokenData* out, hipStream_t stream );

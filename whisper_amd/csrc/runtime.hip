@@ -291,6 +291,8 @@ struct wh_context
 	MelWindow* melWindowsDev = nullptr;
 	TokenData* tokDataDev = nullptr;
 	uint8_t* sampleScratch = nullptr;		   // TUNE_SAMPLE_SPREAD: slice records of the spread sampler (allocated on first use, before any capture)
+	float* langP = nullptr;					   // wh_lang_detect: [maxBatch][n_lang] probabilities and [maxBatch] winners (allocated on first use)
+	int* langBest = nullptr;
 	TokenData* beamCand = nullptr;			   // beam search: [maxSeq][8] candidates (allocated on first use)
 	f16 *selfKScratch = nullptr, *selfVScratch = nullptr;	   // beam search: the copy a cache reorder goes through (allocated on first use)
 	// beam search on the device (wh_beam_window_*): per-window rules and state, the records of every step, the parents a step's reorder reads
@@ -2230,6 +2232,60 @@ int wh_decode( wh_context* c, const int32_t* tokens, int batch, int nTokens, int
 	return 0;
 }
 
+// Language tokens of a vocabulary: sot + 1 .. sot + n_lang, n_lang = n_vocab - 51766 (99 at 51865, 100 at the large-v3 shape); none below 51865 (.en models)
+static int langCount( const wh_hparams& hp ) { return hp.n_vocab >= 51865 ? hp.n_vocab - 51766 : 0; }
+
+int wh_model_lang_count( const wh_model* m )
+{
+	if( !m ) { setError( "model_lang_count: null model" ); return WH_E_INVALIDARG; }
+	return langCount( m->hp );
+}
+
+// whisper_lang_auto_detect (Whisper/source/whisper.cpp:2428-2495) for the windows of the last wh_encode: [sot] at position 0, the probabilities of the
+// language tokens. A one-token step of the context's ordinary route; on a hypothesis-group context every sequence of a group runs the step (the groups share
+// their cross-attention pass) and the group's first row is read. Nothing of the context's decoding state depends on a host-stepped decode: position 0 of the
+// self-attention caches is rewritten by the prompt of whatever decodes next.
+int wh_lang_detect( wh_context* c, int batch, float* langP, int32_t* best )
+{
+	if( !c || !best || batch <= 0 || batch > c->maxBatch ) { setError( "lang_detect: bad argument" ); return WH_E_INVALIDARG; }
+	if( !c->encoded ) { setError( "lang_detect: wh_encode has not run" ); return WH_E_NOT_READY; }
+	if( batch > c->lastEncBatch ) { setError( "lang_detect: more windows than the last wh_encode filled" ); return WH_E_INVALIDARG; }
+	WH_BIND( c->m );
+	const wh_hparams& hp = c->m->hp;
+	const int nLang = langCount( hp );
+	if( nLang <= 0 ) { setError( "lang_detect: the model is not multilingual" ); return WH_E_INVALIDARG; }
+	hipStream_t st = c->stream;
+	const int sot = specialIds( hp ).sot;
+	const int seqs = batch * c->hyp;
+	if( !c->langP )
+	{
+		WH_CHECK( c->alloc( c->langP, (int64_t)c->maxBatch * nLang, wh_context::DONT_CARE, "langP" ) );
+		WH_CHECK( c->alloc( c->langBest, (int64_t)c->maxBatch, wh_context::DONT_CARE, "langBest" ) );
+	}
+	int32_t* const stTok = c->pinTokens();
+	if( c->pinTokenCap() < seqs ) { setError( "lang_detect: staging too small" ); return WH_E_BOUNDS; }
+	WH_HIP( hipStreamSynchronize( st ) );	  // the staging may still be read by an earlier enqueue
+	for( int i = 0; i < seqs; i++ ) stTok[ i ] = sot;
+	WH_HIP( hipMemcpyAsync( c->tokensDev, stTok, sizeof( int32_t ) * seqs, hipMemcpyHostToDevice, st ) );
+	const long long rowStride = (long long)c->hyp * hp.n_vocab;
+	if( c->flags & WH_FLAG_PARITY_EXACT )
+	{
+		WH_CHECK( decodeExact( c, seqs, 1, 0 ) );
+		WH_CHECK( launchLangGather( c->probs, rowStride, batch, hp.n_vocab, sot, nLang, c->langP, c->langBest, st ) );
+	}
+	else
+	{
+		WH_CHECK( decodeGraph( c, seqs, 1, 0, false ) );
+		WH_CHECK( profiled( c, KC_SOFTMAX, 10.0 * batch * hp.n_vocab, 4.0 * batch * hp.n_vocab,
+			[ & ]() { return launchLangProbs( c->logits, rowStride, batch, hp.n_vocab, sot, nLang, c->langP, c->langBest, st ); } ) );
+	}
+	if( langP ) WH_HIP( hipMemcpyAsync( langP, c->langP, sizeof( float ) * batch * nLang, hipMemcpyDeviceToHost, st ) );
+	WH_HIP( hipMemcpyAsync( best, c->langBest, sizeof( int32_t ) * batch, hipMemcpyDeviceToHost, st ) );
+	WH_HIP( hipStreamSynchronize( st ) );
+	c->lastBatch = c->lastEncBatch * c->hyp;	  // as wh_encode left it
+	return 0;
+}
+
 // The sampler state and the positions of `batch` sequences -> device, through the pinned staging (asynchronous; the staging is
 // reused by the next call, which callers order behind a synchronisation of their own). positions == nullptr: `uniform` for all.
 static int uploadDecodeState( wh_context* c, int batch, const DecodeState& s, const int32_t* positions, int uniform )
@@ -3106,6 +3162,16 @@ int wh_op_vocab_soft_max( void* stream, const float* logits, float* probs, int r
 {
 	if( !logits || !probs || rows < 1 || cols < 1 ) { setError( "vocab_soft_max: null pointer or empty shape" ); return WH_E_INVALIDARG; }
 	return launchVocabSoftMax( logits, probs, rows, cols, (hipStream_t)stream );
+}
+
+int wh_op_lang_probs( void* stream, const float* logits, int rows, int nVocab, int tokenSot, int nLang, float* langP, int32_t* best )
+{
+	if( !logits || !langP || !best || rows < 1 || nVocab < 1 || nVocab > 52224 || nLang < 1 || nLang > 1024 || tokenSot < 0 || (int64_t)tokenSot + 1 + nLang > nVocab )
+	{
+		setError( "lang_probs: bad pointer or size (at most 52224 columns), or the language block tokenSot + 1 .. tokenSot + nLang (1 .. 1024 tokens) leaves the row" );
+		return WH_E_INVALIDARG;
+	}
+	return launchLangProbs( logits, nVocab, rows, nVocab, tokenSot, nLang, langP, best, (hipStream_t)stream );
 }
 
 static bool tokenArgsOk( const float* probs, const wh_token_data* out, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot )

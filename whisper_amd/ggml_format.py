@@ -367,6 +367,40 @@ def conditioned_model(layout, prompt_len: int, kind: str = "test-d128-ml", seed:
     return m
 
 
+LANGUAGE_CANDIDATES = (0, 1, 2, 3, 4, 6)      # en, zh, de, es, ru, fr
+
+
+def language_conditioned_model(layout, prompt_len: int, kind: str = "test-d128-ml", seed: int = 6, lang_ids=LANGUAGE_CANDIDATES, lang_gain: float = 0.3,
+                               lang_beta: float = 2.0, self_out_scale: float = 10.0, **kw) -> GgmlModel:
+    """conditioned_model for language detection ("auto"): the spoken language is decided by the audio, and the language token in
+    the prompt reaches the transcript.
+
+    (a) At decoder position 0 -- where whisper_lang_auto_detect feeds [sot] -- the language tokens sot + 1 + id, id in lang_ids, are
+        candidates like the text candidates of conditioned_model: all get +lang_gain * c_0 and each its own lang_beta * u / sqrt(d),
+        u orthogonal to c_0, so WHICH language wins depends on the cross-attention output, i.e. on the audio.
+    (b) The self-attention output projection of decoder layer 0 is kept (scaled by self_out_scale) instead of zeroed: in
+        conditioned_model every attn.out is zero, the residual stream of a position never sees the other positions, and the
+        transcript is the same under every language token. With it the language token of the prompt moves the sampled tokens."""
+    m = conditioned_model(layout, prompt_len, kind=kind, seed=seed, **kw)
+    hp = m.hparams
+    d = hp.n_text_state
+    sp = special_tokens(hp)
+    rng = np.random.default_rng(seed + 2)
+    c0 = m.tensors["decoder.positional_embedding"][0].astype(np.float32)
+    te = m.tensors["decoder.token_embedding.weight"].astype(np.float32)
+    for lid in lang_ids:
+        u = rng.standard_normal(d).astype(np.float32)
+        u -= (u @ c0) / d * c0
+        te[sp["sot"] + 1 + lid] += lang_gain * c0 + lang_beta * u / np.sqrt(d)
+    m.tensors["decoder.token_embedding.weight"] = te.astype(np.float16)
+    if self_out_scale:
+        src = synth_model(kind, seed=seed, w_std=0.02, attn_sharpness=4.0)      # the tensors conditioned_model started from
+        for nm in ("weight", "bias"):
+            key = "decoder.blocks.0.attn.out." + nm
+            m.tensors[key] = (src.tensors[key].astype(np.float32) * self_out_scale).astype(src.tensors[key].dtype)
+    return m
+
+
 def conditioned_layout(hp: HParams):
     """[timestamp <= 0.8 s, 5 text, two timestamps 6-10 s, 6 text, a timestamp 14-22 s, EOT]: two segments per window, the next
     window seeks to the last timestamp."""

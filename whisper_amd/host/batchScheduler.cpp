@@ -19,6 +19,7 @@
 // is the transcript of runFull on the same samples (tests/test_batch_api.py).
 #include "hostCommon.h"
 #include "hostLoop.h"
+#include "languageDetect.h"
 #include "results.h"
 #include <algorithm>
 #include <chrono>
@@ -29,6 +30,9 @@
 
 namespace Whisper
 {
+	// The device half of language detection, injected (languageDetect.h): this file names no entry point of the compute layer for it
+	pfnBatchLanguageDetector g_batchLanguageDetector = nullptr;
+
 	namespace
 	{
 		// What a stream's callbacks receive: results so far and the model; running anything through it is not possible.
@@ -91,6 +95,10 @@ namespace Whisper
 			std::vector<int> prompt;
 			std::unique_ptr<WindowScan> scan;
 			HRESULT status = S_OK;
+			// language "auto": the stream waits in its slot, not begun, until the group's next detection pre-pass has named its language
+			bool needsLanguage = false;
+			int languageId = -1;
+			float languageP = 0;
 		};
 
 		// Device buffers of the streams (PCM, spectrograms), recycled: hipFree waits for the whole device, i.e. for the OTHER group's
@@ -146,6 +154,8 @@ namespace Whisper
 			std::vector<wh_token_data> buf;
 			std::vector<int32_t> tokens, lens;
 			std::vector<wh_mel_window> windows;
+			std::vector<float> langP;
+			std::vector<int32_t> langBest;
 		};
 
 		// One call of iBatchRunner::run over the runner's groups (their wh_contexts outlive the call: KV caches, captured graphs)
@@ -182,6 +192,8 @@ namespace Whisper
 				{
 					TranscribeResult* r = new TranscribeResult();
 					fillResultData( s->ctx->resultAll, model->vocab, s->ctx->mediaTimeOffset, eResultFlags::Tokens | eResultFlags::Timestamps, *r );
+					r->languageId = s->languageId;
+					r->languageP = s->languageP;
 					results[ s->index ] = r;
 				}
 				s->run.reset();
@@ -231,13 +243,24 @@ namespace Whisper
 							hr = hrFromStatus( -1, "runFullBatch: stream admission" );
 						loaderBusy = true;
 					}
-					if( SUCCEEDED( hr ) )
+					if( SUCCEEDED( hr ) && model->vocab.isMultilingual() && isLanguageAuto( s->params.language ) )
 					{
-						if( s->params.flag( eFullParamsFlags::TokenTimestamps ) ) s->stamper.begin( s->pcm, (size_t)s->nSamples );
-						const sProgressSink none{ nullptr, nullptr };
-						s->run.reset( new StreamRun( s->params, model->vocab, model->hp, s->ctx, none, s->ctx->resultAll, s->promptPast, &s->stamper ) );
-						hr = s->run->begin( s->melLen );
+						// every stream gets ITS OWN language. Where StreamRun::begin returns before it reads the language (less than a second of
+						// audio, parameters it rejects) nothing is detected and begin answers as it does for a named language
+						if( languageDetectionMoot( s->params, s->melLen, model->hp ) )
+							s->params.language = makeLanguageKey( "en" );
+						else if( !g_batchLanguageDetector )
+						{
+							logError( "runFullBatch: language \"auto\" needs the language detector, which this build of the scheduler was not given" );
+							hr = E_NOTIMPL;
+						}
+						else
+						{
+							s->needsLanguage = true;	// begun by detectLanguages(), in the pre-pass of the round that admitted it
+							return true;
+						}
 					}
+					if( SUCCEEDED( hr ) ) hr = begin( *s );
 					if( hr != S_OK )
 					{
 						if( FAILED( hr ) ) fail( *s, hr );
@@ -250,16 +273,78 @@ namespace Whisper
 				return false;
 			}
 
-			// Every slot's next window; streams that end here leave and their slots are refilled. Then the round's device work is enqueued.
-			HRESULT startRound( Group& g )
+			HRESULT begin( Stream& s )
 			{
-				bool any = false;
+				if( s.params.flag( eFullParamsFlags::TokenTimestamps ) ) s.stamper.begin( s.pcm, (size_t)s.nSamples );
+				const sProgressSink none{ nullptr, nullptr };
+				s.run.reset( new StreamRun( s.params, model->vocab, model->hp, s.ctx, none, s.ctx->resultAll, s.promptPast, &s.stamper ) );
+				return s.run->begin( s.melLen );
+			}
+
+			// The detection pre-pass of a round (the "auto" branch of whisper_full, whisper.cpp:2788-2801, for a lock-step batch): the windows at FRAME 0
+			// of the streams that wait for their language -- whatever their offset_ms; every other slot a window of zeros -- are ONE encoder batch with the
+			// model's full audio context and ONE call of the detector; each stream then begins with its own language key (the prompts of a round are
+			// ragged anyway). The group is idle here: nothing of a window in progress is lost. The first windows are encoded again by the round itself
+			// (one encoder batch more per admission wave, not per stream; the results do not depend on it).
+			HRESULT detectLanguages( Group& g )
+			{
+				if( loaderBusy )
+				{
+					CHECK_WH( wh_context_synchronize( shared.loader ) );
+					loaderBusy = false;
+				}
+				const int nDev = languageTokenCount( model->hp ), n = std::min( nDev, (int)languageList().length );
+				g.windows.assign( (size_t)g.slots, wh_mel_window{ nullptr, 0, 0, 0 } );
+				for( int b = 0; b < g.slots; b++ )
+					if( g.slot[ b ] && g.slot[ b ]->needsLanguage ) g.windows[ b ] = wh_mel_window{ (const float*)g.slot[ b ]->melDev, g.slot[ b ]->melLen, 0, 0 };
+				g.langP.assign( (size_t)g.slots * nDev, 0.0f );
+				g.langBest.assign( (size_t)g.slots, 0 );
+				CHECK_WH( wh_context_set_audio_ctx( g.gpu, 0 ) );
+				CHECK_WH( wh_encode_windows( g.gpu, g.windows.data(), g.slots ) );
+				CHECK_WH( g_batchLanguageDetector( g.gpu, g.slots, g.langP.data(), g.langBest.data() ) );
+				CHECK_WH( wh_context_set_audio_ctx( g.gpu, common.audio_ctx ) );
+				std::vector<float> lp( (size_t)n );
+				for( int b = 0; b < g.slots; b++ )
+				{
+					Stream* s = g.slot[ b ];
+					if( !s || !s->needsLanguage ) continue;
+					s->needsLanguage = false;
+					s->languageId = finishLanguageProbs( g.langP.data() + (size_t)b * nDev, n, lp.data() );
+					if( s->languageId < 0 )
+					{
+						fail( *s, E_UNEXPECTED );
+						retire( g, b );
+						continue;
+					}
+					s->languageP = lp[ (size_t)s->languageId ];
+					const std::string code = languageCode( s->languageId );
+					s->params.language = makeLanguageKey( code.c_str() );
+					logInfo( "whisper_full: auto-detected language: %s (p = %f) [stream %u]", code.c_str(), s->languageP, s->index );
+					const HRESULT hr = begin( *s );
+					if( hr != S_OK )
+					{
+						if( FAILED( hr ) ) fail( *s, hr );
+						else s->status = hr;
+						retire( g, b );
+					}
+				}
+				return S_OK;
+			}
+
+			// Every slot's next window; streams that end here leave and their slots are refilled. Returns true when a slot holds a stream that waits for
+			// its language: the caller runs the detection pre-pass and calls again (slots the pre-pass emptied are refilled then; a stream that has
+			// its window of this round already keeps it).
+			bool nextWindows( Group& g, bool& any )
+			{
+				bool detect = false;
 				for( int b = 0; b < g.slots; b++ )
 				{
 					while( true )
 					{
 						if( !g.slot[ b ] && !admit( g, b ) ) break;
 						Stream& s = *g.slot[ b ];
+						if( s.needsLanguage ) { detect = true; break; }
+						if( s.scan ) break;
 						const HRESULT hr = s.run->nextWindow( s.prompt );
 						if( hr == S_OK )
 						{
@@ -276,6 +361,14 @@ namespace Whisper
 						retire( g, b );
 					}
 				}
+				return detect;
+			}
+
+			// The round: every slot's next window, then the round's device work is enqueued.
+			HRESULT startRound( Group& g )
+			{
+				bool any = false;
+				while( nextWindows( g, any ) ) CHECK( detectLanguages( g ) );
 				if( loaderBusy )
 				{
 					CHECK_WH( wh_context_synchronize( shared.loader ) );

@@ -15,6 +15,10 @@ namespace Whisper
 	class TranscribeResult : public ComObject<iTranscribeResult>, public ResultData
 	{
 	public:
+		// a batch runner's stream whose language was detected (language "auto"): its id and lang_probs entry; -1 = the language was named.
+		// Plain members behind the interface's methods: the vtable is the reference's (whisperc_tr_language reads them).
+		int languageId = -1;
+		float languageP = 0;
 		HRESULT getSize( sTranscribeLength& rdi ) const override
 		{
 			rdi.countSegments = (uint32_t)segments.size();

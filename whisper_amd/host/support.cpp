@@ -178,6 +178,8 @@ namespace Whisper
 		if( !lang ) return UINT32_MAX;
 		std::string s( lang );
 		for( char& c : s ) c = (char)tolower( (unsigned char)c );
+		// "auto": no language of the table -- the key that asks runFull / runStreamed / iBatchRunner::run to detect it (languageDetect.h)
+		if( s == "auto" ) return makeLanguageKey( "auto" );
 		const LangTable& t = langTable();
 		for( int i = 0; i < N_LANGS; i++ )
 			if( s == g_langs[ i ].code || s == g_langs[ i ].name ) return t.entries[ i ].key;

@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include "hostCommon.h"
 #include "hostLoop.h"
+#include "languageDetect.h"
 #include "results.h"
 #include <algorithm>
 #include <chrono>
@@ -136,6 +137,12 @@ namespace Whisper
 			HRESULT encodeWindow( wh_context* ctx, int seek );
 			int audioCtx = 0;	   // sFullParams::audio_ctx of the run in progress (0 = the model's)
 			HRESULT beamContext( int width );
+			HRESULT activeContext( const sFullParams& params, bool warn, wh_context*& active, int& beamWidth );
+			// language "auto" (languageDetect.h): what the last run / detectLanguage call found, -1 = nothing was detected
+			int detectedLang = -1;
+			float detectedP = 0;
+			HRESULT detectOnWindow( wh_context* ctx, int seek, std::vector<float>* probs, int& langId );
+			HRESULT resolveLanguage( sFullParams& params, bool& firstWindowEncoded );
 			HRESULT decodeWindowBeam( const std::vector<int>& prompt, int width, WindowScan& scan, int& steps );
 			HRESULT decodeWindowBeamDevice( const std::vector<int>& prompt, int width, WindowScan& scan, int& steps );
 
@@ -164,6 +171,15 @@ namespace Whisper
 				return S_OK;
 			}
 
+			// whisper_lang_auto_detect on a buffer of its own (whisperc_detect_language), and the language of the last run
+			HRESULT detectLanguage( const float* pcm, uint32_t nSamples, int offsetMs, float* probs, uint32_t probsCap, int& langId );
+			int lastDetectedLanguage( float& p ) const { p = detectedP; return detectedLang; }
+			// wh_context_set_flags on this context's device context (whisperc_debug_context_flags: the exact mode for parity tests)
+			HRESULT setDeviceFlags( uint32_t flags, int parityThreads )
+			{
+				CHECK_WH( wh_context_set_flags( gpu, flags, parityThreads ) );
+				return S_OK;
+			}
 			HRESULT runFull( const sFullParams& params, const iAudioBuffer* buffer ) override;
 			HRESULT runStreamed( const sFullParams& params, const sProgressSink& progress, const iAudioReader* reader ) override;
 			HRESULT runCapture( const sFullParams&, const sCaptureCallbacks&, const iAudioCapture* ) override { return E_NOTIMPL; }
@@ -628,12 +644,135 @@ namespace Whisper
 			return S_OK;
 		}
 
-		HRESULT ContextImpl::runFullImpl( const sFullParams& params, const sProgressSink& progress )
+		// The device context a run with these parameters works on (see runFullImpl)
+		HRESULT ContextImpl::activeContext( const sFullParams& params, bool warn, wh_context*& active, int& beamWidth )
+		{
+			beamWidth = 0;
+			if( params.strategy == eSamplingStrategy::BeamSearch && params.beam_search.beam_width >= 1 )
+			{
+				beamWidth = params.beam_search.beam_width;
+				if( beamWidth > 8 )
+				{
+					if( warn ) logWarning( "runFull: beam_width %d is more than this build decodes in lock step; using 8", beamWidth );
+					beamWidth = 8;
+				}
+				CHECK( beamContext( beamWidth ) );
+			}
+			active = beamWidth >= 1 ? gpuBeam : gpu;
+			return S_OK;
+		}
+
+		// whisper_lang_auto_detect (Whisper/source/whisper.cpp:2428-2495) on the window at `seek` of the context's spectrogram source: the encoder with the
+		// model's full audio context, [sot] at position 0 and the language tokens' probabilities on the device (wh_lang_detect), the reference's second
+		// softmax over them on the host (finishLanguageProbs). Like the reference, only the languages of the table take part (a vocabulary of the large-v3
+		// shape has one token more). Leaves the window encoded and ready to be decoded.
+		HRESULT ContextImpl::detectOnWindow( wh_context* ctx, int seek, std::vector<float>* probs, int& langId )
+		{
+			const int nDev = wh_model_lang_count( model->gpu );
+			const int n = std::min( nDev, (int)languageList().length );
+			if( n <= 0 ) return E_INVALIDARG;
+			audioCtx = 0;
+			CHECK_WH( wh_context_set_audio_ctx( ctx, 0 ) );
+			const auto t = Clock::now();
+			CHECK( encodeWindow( ctx, seek ) );
+			msEncode += msSince( t );
+			nEncode++;
+			std::vector<float> p( (size_t)nDev );
+			int32_t best = 0;
+			CHECK_WH( wh_lang_detect( ctx, 1, p.data(), &best ) );
+			std::vector<float> lp( (size_t)n );
+			langId = finishLanguageProbs( p.data(), n, lp.data() );
+			if( langId < 0 ) return E_UNEXPECTED;
+			// a vocabulary with more language tokens than the table has languages (the large-v3 shape's 100th): the device's winner may be one of them
+			if( best >= n )
+				logWarning( "language detection: the most probable language token (id %d, p = %f) is not in the table of %d languages; using %s", (int)best,
+					p[ (size_t)best ], n, languageCode( langId ).c_str() );
+			detectedLang = langId;
+			detectedP = lp[ (size_t)langId ];
+			if( probs ) probs->swap( lp );
+			return S_OK;
+		}
+
+		// The "auto" branch of whisper_full (whisper.cpp:2788-2801): detection on the window at FRAME 0 whatever offset_ms is, the winner replaces the
+		// language, the reference's log line. Nothing is detected where the run would not decode anything anyway: an .en model (the language is not read),
+		// less than a second of audio (S_FALSE), parameters StreamRun::begin rejects.
+		HRESULT ContextImpl::resolveLanguage( sFullParams& params, bool& firstWindowEncoded )
+		{
+			firstWindowEncoded = false;
+			detectedLang = -1;
+			detectedP = 0;
+			if( !model->vocab.isMultilingual() || !isLanguageAuto( params.language ) ) return S_OK;
+			const int seekStart = params.offset_ms / 10;
+			if( languageDetectionMoot( params, mel.length, model->hp ) )
+			{
+				params.language = makeLanguageKey( "en" );	   // never read: StreamRun::begin returns before the prompt is built
+				return S_OK;
+			}
+			if( mel.length <= 0 )
+			{
+				logError( "runFull: failed to auto-detect language: no audio at the start of the buffer" );
+				return E_INVALIDARG;
+			}
+			wh_context* active = nullptr;
+			int beamWidth = 0;
+			CHECK( activeContext( params, false, active, beamWidth ) );
+			int langId = -1;
+			CHECK( detectOnWindow( active, 0, nullptr, langId ) );
+			const std::string code = languageCode( langId );
+			params.language = makeLanguageKey( code.c_str() );
+			logInfo( "whisper_full: auto-detected language: %s (p = %f)", code.c_str(), detectedP );
+			firstWindowEncoded = seekStart == 0 && params.audio_ctx == 0;
+			// a streamed spectrogram remembers where its last window ended (MelSource::lastBufferEnd): a window that is encoded again starts from a clean state
+			if( !firstWindowEncoded ) mel.lastBufferEnd = -1;
+			return S_OK;
+		}
+
+		// whisper_lang_auto_detect as an entry point of its own: the spectrogram of the whole buffer (runFull's), the window at offsetMs / 10
+		HRESULT ContextImpl::detectLanguage( const float* pcm, uint32_t nSamples, int offsetMs, float* probs, uint32_t probsCap, int& langId )
+		{
+			langId = -1;
+			detectedLang = -1;
+			detectedP = 0;
+			if( !model->vocab.isMultilingual() )
+			{
+				logError( "detectLanguage: the model is not multilingual" );
+				return E_INVALIDARG;
+			}
+			const int seek = offsetMs / 10;
+			const int64_t melLen = nSamples / 160;
+			if( offsetMs < 0 )
+			{
+				logError( "whisper_lang_auto_detect: offset %dms is before the start of the audio", offsetMs );
+				return E_INVALIDARG;
+			}
+			if( seek >= melLen )
+			{
+				logError( "whisper_lang_auto_detect: offset %dms is past the end of the audio (%dms)", offsetMs, (int)melLen * 10 );
+				return E_INVALIDARG;
+			}
+			mel = MelSource{};
+			mel.length = melLen;
+			CHECK( ensureBuffer( pcmDev, pcmCapacity, (int64_t)nSamples * 4 ) );
+			CHECK( ensureBuffer( melDev, melCapacity, melLen * model->hp.n_mels * 4 ) );
+			CHECK_WH( wh_buffer_upload( gpu, pcmDev, pcm, (int64_t)nSamples * 4 ) );
+			int64_t got = 0;
+			CHECK_WH( wh_mel_spectrogram( gpu, (const float*)pcmDev, nSamples, (float*)melDev, &got ) );
+			std::vector<float> lp;
+			CHECK( detectOnWindow( gpu, seek, &lp, langId ) );
+			if( probs ) memcpy( probs, lp.data(), sizeof( float ) * std::min( (size_t)probsCap, lp.size() ) );
+			return S_OK;
+		}
+
+		HRESULT ContextImpl::runFullImpl( const sFullParams& paramsIn, const sProgressSink& progress )
 		{
 			// the stream's rules (seek range, prompt carry-over, stop rules, segments, callbacks) live in hostLoop.h, shared with the
 			// lock-step scheduler of runFullBatch; here: the device work of ONE stream, window after window
 			const Vocabulary& vocab = model->vocab;
 			const wh_hparams& hp = model->hp;
+			// language "auto": resolved HERE, before the stream's rules see the parameters (hostLoop.h knows languages of the table only)
+			sFullParams params = paramsIn;
+			bool firstWindowEncoded = false;
+			CHECK( resolveLanguage( params, firstWindowEncoded ) );
 			StreamRun run( params, vocab, hp, this, progress, resultAll, promptPast, &stamper );
 			const HRESULT hrBegin = run.begin( mel.length );
 			if( hrBegin != S_OK ) return hrBegin;
@@ -641,18 +780,9 @@ namespace Whisper
 			// window through decodeWindowBeam (width 1 included: there it must reproduce the greedy loop token for token). The Greedy strategy
 			// takes the device-side greedy loop.
 			int beamWidth = 0;
-			if( params.strategy == eSamplingStrategy::BeamSearch && params.beam_search.beam_width >= 1 )
-			{
-				beamWidth = params.beam_search.beam_width;
-				if( beamWidth > 8 )
-				{
-					logWarning( "runFull: beam_width %d is more than this build decodes in lock step; using 8", beamWidth );
-					beamWidth = 8;
-				}
-				CHECK( beamContext( beamWidth ) );
-			}
 			// the ONE device context this run works on: the window x hypotheses context of a beam search, else the stream's own
-			wh_context* const active = beamWidth >= 1 ? gpuBeam : gpu;
+			wh_context* active = nullptr;
+			CHECK( activeContext( params, true, active, beamWidth ) );
 			// overwrite audio_ctx (ContextImpl.cpp:488-489): encoder positions and cross-attention keys of every window of this run
 			audioCtx = params.audio_ctx;
 			CHECK_WH( wh_context_set_audio_ctx( active, audioCtx ) );
@@ -666,10 +796,16 @@ namespace Whisper
 					// enqueued without a host sync: the decoder's launches line up behind the encoder's on the context's stream.
 					// With WHISPER_PROFILE=1 the two are separated so that the "Encode" block means what it means in the reference.
 					const auto t = Clock::now();
-					CHECK( encodeWindow( active, run.seek ) );
-					if( gpuProfile ) CHECK_WH( wh_context_synchronize( active ) );	   // the context the encoder was queued on ("Encode" measures the encoder, not its enqueue)
-					msEncode += msSince( t );
-					nEncode++;
+					// the window language detection encoded (frame 0, the full audio context) is this run's first window: not encoded twice
+					const bool encoded = firstWindowEncoded && run.seek == 0;
+					firstWindowEncoded = false;
+					if( !encoded )
+					{
+						CHECK( encodeWindow( active, run.seek ) );
+						if( gpuProfile ) CHECK_WH( wh_context_synchronize( active ) );	   // the context the encoder was queued on ("Encode" measures the encoder, not its enqueue)
+						msEncode += msSince( t );
+						nEncode++;
+					}
 				}
 				const auto tDec = Clock::now();
 				WindowDecoder dec( active, hp.n_text_ctx );
@@ -857,6 +993,22 @@ namespace Whisper
 		}
 	}	// namespace
 
+	// the flat C exports below reach the two methods that are not part of iContext's vtable (every iContext of this library is a ContextImpl)
+	HRESULT contextDetectLanguage( void* ctx, const float* pcm, uint32_t nSamples, int offsetMs, float* probs, uint32_t probsCap, int& langId )
+	{
+		return static_cast<ContextImpl*>( (iContext*)ctx )->detectLanguage( pcm, nSamples, offsetMs, probs, probsCap, langId );
+	}
+	int contextDetectedLanguage( void* ctx, float& p )
+	{
+		return static_cast<ContextImpl*>( (iContext*)ctx )->lastDetectedLanguage( p );
+	}
+	HRESULT contextSetDeviceFlags( void* ctx, uint32_t flags, int parityThreads )
+	{
+		return static_cast<ContextImpl*>( (iContext*)ctx )->setDeviceFlags( flags, parityThreads );
+	}
+	// the lock-step scheduler's way to the device half of language detection (languageDetect.h): installed when the library is loaded
+	static const bool g_detectorInstalled = ( g_batchLanguageDetector = &wh_lang_detect, true );
+
 	HRESULT createContextImpl( const std::shared_ptr<LoadedModel>& model, iModel* owner, iContext** pp )
 	{
 		if( !pp ) return E_POINTER;
@@ -982,6 +1134,60 @@ WHISPER_EXPORT int32_t whisperc_special_tokens( void* model, int32_t* out8 )
 }
 WHISPER_EXPORT const char* whisperc_token_string( void* model, int token ) { return ( (iModel*)model )->stringFromToken( token ); }
 WHISPER_EXPORT int32_t whisperc_is_multilingual( void* model ) { return ( (iModel*)model )->isMultilingual(); }
+// whisper_lang_auto_detect (whisper.cpp:2428-2495) on a mono FP32 16 kHz buffer: probs[ id ] for the first probsCap language ids, *langId = the winner
+WHISPER_EXPORT int32_t whisperc_detect_language( void* ctx, const float* pcm, uint32_t nSamples, int32_t offsetMs, float* probs, uint32_t probsCap, int32_t* langId )
+{
+	if( !ctx || ( !pcm && nSamples ) ) return E_POINTER;
+	int id = -1;
+	const HRESULT hr = contextDetectLanguage( ctx, pcm, nSamples, offsetMs, probs, probsCap, id );
+	if( langId ) *langId = id;
+	return hr;
+}
+// the language the last run (language "auto") or whisperc_detect_language on this context found: code5 receives its code, *p its lang_probs entry
+WHISPER_EXPORT int32_t whisperc_detected_language( void* ctx, char* code5, float* p )
+{
+	if( !ctx ) return E_POINTER;
+	float prob = 0;
+	const int id = contextDetectedLanguage( ctx, prob );
+	if( code5 ) code5[ 0 ] = 0;
+	if( p ) *p = 0;
+	if( id < 0 ) return S_FALSE;
+	if( code5 ) snprintf( code5, 5, "%s", languageCode( id ).c_str() );
+	if( p ) *p = prob;
+	return S_OK;
+}
+// of a batch runner's per-stream result: the language the stream was transcribed in when it was detected (language "auto"); S_FALSE otherwise
+WHISPER_EXPORT int32_t whisperc_tr_language( void* result, char* code5, float* p )
+{
+	if( !result ) return E_POINTER;
+	if( code5 ) code5[ 0 ] = 0;
+	if( p ) *p = 0;
+	const TranscribeResult* r = dynamic_cast<const TranscribeResult*>( (iTranscribeResult*)result );
+	if( !r || r->languageId < 0 ) return S_FALSE;
+	if( code5 ) snprintf( code5, 5, "%s", languageCode( r->languageId ).c_str() );
+	if( p ) *p = r->languageP;
+	return S_OK;
+}
+// wh_context_set_flags( flags, parityThreads ) on the device context behind an iContext (tests: WH_FLAG_PARITY_EXACT = 8 makes whisperc_detect_language
+// compute the reference's bits). Per context, not process-wide; the greedy loop and beam search refuse the exact mode.
+WHISPER_EXPORT int32_t whisperc_debug_context_flags( void* ctx, uint32_t flags, int32_t parityThreads )
+{
+	if( !ctx ) return E_POINTER;
+	return contextSetDeviceFlags( ctx, flags, parityThreads );
+}
+// the code of language `id` (0 .. 98; the language token is sot + 1 + id): S_FALSE beyond the table
+WHISPER_EXPORT int32_t whisperc_language_code( int32_t id, char* code5 )
+{
+	if( !code5 ) return E_POINTER;
+	const std::string code = languageCode( id );
+	snprintf( code5, 5, "%s", code.c_str() );
+	return code.empty() ? S_FALSE : S_OK;
+}
+// the host half of whisper_lang_auto_detect on its own (no device): lang_probs from the n probabilities p; returns the winner
+WHISPER_EXPORT int32_t whisperc_debug_lang_probs( const float* p, int32_t n, float* probs )
+{
+	return finishLanguageProbs( p, n, probs );
+}
 // flags: eFullParamsFlags bits; language: ASCII code; returns the HRESULT of runFull
 WHISPER_EXPORT int32_t whisperc_run_full( void* ctx, const float* pcm, uint32_t nSamples, const char* language, uint32_t flags, int maxTokens,
 	const int32_t* promptTokens, int nPrompt, int nMaxTextCtx )
@@ -995,6 +1201,28 @@ WHISPER_EXPORT int32_t whisperc_run_full( void* ctx, const float* pcm, uint32_t 
 	p.max_tokens = maxTokens;
 	p.prompt_tokens = promptTokens;
 	p.prompt_n_tokens = nPrompt;
+	if( nMaxTextCtx >= 0 ) p.n_max_text_ctx = nMaxTextCtx;
+	iAudioBuffer* buf = nullptr;
+	CHECK( createAudioBuffer( std::vector<float>( pcm, pcm + nSamples ), {}, &buf ) );
+	const HRESULT hr = c->runFull( p, buf );
+	buf->Release();
+	return hr;
+}
+// whisperc_run_full + sFullParams::offset_ms / duration_ms (the range of the buffer that is transcribed; language "auto" still detects on frame 0)
+WHISPER_EXPORT int32_t whisperc_run_full_range( void* ctx, const float* pcm, uint32_t nSamples, const char* language, uint32_t flags, int maxTokens,
+	const int32_t* promptTokens, int nPrompt, int nMaxTextCtx, int offsetMs, int durationMs )
+{
+	if( !ctx || ( !pcm && nSamples ) ) return E_POINTER;
+	iContext* c = (iContext*)ctx;
+	sFullParams p;
+	CHECK( c->fullDefaultParams( eSamplingStrategy::Greedy, &p ) );
+	p.flags = (eFullParamsFlags)flags;
+	p.language = makeLanguageKey( language ? language : "en" );
+	p.max_tokens = maxTokens;
+	p.prompt_tokens = promptTokens;
+	p.prompt_n_tokens = nPrompt;
+	p.offset_ms = offsetMs;
+	p.duration_ms = durationMs;
 	if( nMaxTextCtx >= 0 ) p.n_max_text_ctx = nMaxTextCtx;
 	iAudioBuffer* buf = nullptr;
 	CHECK( createAudioBuffer( std::vector<float>( pcm, pcm + nSamples ), {}, &buf ) );
