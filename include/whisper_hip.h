@@ -386,7 +386,10 @@ WH_API int wh_debug_probe( wh_context* c, int kind, int variant, int M, int N, i
 
 /* MlContext::mulMat with an FP16 weight (ComputeShaders/mulMatTiled.hlsl, mulMatByRowTiled.hlsl):
  * out[m][n] = sum_k fp16(a[m][k]) * w[n][k] (+ bias[n]) (+ residual[m][n]); a: FP16 [M][K] (already rounded, which is
- * what ggml does at ggml.c:4588-4611), w: FP16 [N][K], out FP32 [M][N]. bias/residual may be NULL. */
+ * what ggml does at ggml.c:4588-4611), w: FP16 [N][K], out FP32 [M][N]. bias/residual may be NULL.
+ * Scratch: the K-split shapes (32 < M <= 128, N <= 2048, K >= 2048) keep their partial tiles in a buffer the library owns, one per
+ * (device, stream), allocated by the first such call on that stream and reused by every later one. Calls on different streams may
+ * therefore run concurrently; calls on one stream are ordered by it. */
 WH_API int wh_op_mul_mat( void* stream, const void* aF16, const void* wF16, const float* bias, const float* residual,
 	float* out, int M, int N, int K );
 /* mulMat + addRepeatGelu (ComputeShaders/addRepeatGelu.hlsl): out FP16 [M][N] = gelu16( acc + bias ) */

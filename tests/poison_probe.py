@@ -1,8 +1,8 @@
 """Helper of tests/test_00_canary.py::test_results_do_not_depend_on_stale_device_memory (run as a subprocess).
 
 Runs the hot path on the d = 128 test model -- spectrogram, encoder, a parity-mode and a fast-path decode step, a greedy
-window through the captured graph at batch 1, and the lock-step batch path at 10 windows (fused self-attention block) --
-and prints one JSON line of digests. The parent runs it with and without WH_DEBUG_POISON and compares the lines.
+window through the captured graph at batch 1, the lock-step batch path at 10 windows (fused self-attention block), and the
+exact mode across an audio_ctx override -- and prints one JSON line of digests. The parent runs it with and without WH_DEBUG_POISON and compares the lines.
 """
 import hashlib
 import json
@@ -49,6 +49,19 @@ def main():
         # the streamed spectrogram (runStreamed's per-window normalisation)
         w = ctx.mel_spectrogram_window(torch.from_numpy(pcm).cuda(), 200, 700)
         out["melwin_b%d" % batch] = digest(w.cpu().numpy())
+        # the exact mode: its buffers come from the context's allocator too (poisoned, guarded, verified by close()); audio_ctx 1 then the full window
+        # again makes the second encode larger than the first one the buffers were allocated by
+        ctx.set_flags(binding.WH_FLAG_PARITY_EXACT, 2)
+        ctx.encode(melb, offs)
+        toks = np.tile(np.asarray([[sp["sot"], sp["not_"]]], np.int32), (batch, 1))
+        exact = {"prompt": ctx.decode(toks, 0)[0], "step": ctx.decode(np.full((batch, 1), sp["beg"], np.int32), 2)[0]}
+        for name, n_ctx in (("ctx1", 1), ("full", 0)):
+            ctx.set_audio_ctx(n_ctx)
+            ctx.encode(melb, offs)
+            exact[name] = ctx.decode(toks, 0)[0]
+        for name, logits in exact.items():
+            assert np.isfinite(logits).all(), name
+            out["exact_%s_b%d" % (name, batch)] = digest(logits)
         ctx.close()
     hm.close()
     print("PROBE " + json.dumps(out, sort_keys=True))

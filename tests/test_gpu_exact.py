@@ -218,7 +218,8 @@ def test_audio_ctx_override(ref_lib_available, tmp_path):
     toks = np.array([_prompt(sp)] * 2, np.int32)
     ctx.encode(mels)
     full_logits, _ = ctx.decode(toks, 0)
-    for n_ctx in (700, 1):
+    # ascending first: the exact mode's encoder buffers are allocated by its first encode and must hold every audio_ctx that follows
+    for n_ctx in (1, 700, 1):
         w = ref.RefWhisper(path, n_threads=2, log_level=0)
         w.set_mel_any(mels[1].cpu().numpy())
         w.set_audio_ctx(n_ctx)
@@ -246,4 +247,54 @@ def test_audio_ctx_override(ref_lib_available, tmp_path):
     again, _ = ctx.decode(toks, 0)
     assert np.array_equal(again, full_logits)
     ctx.close()
+    m.close()
+
+
+def test_exact_decoder_scratch_is_freed_when_it_grows():
+    """The exact decoder's score scratch holds seqs * H * N * max(audio_ctx, n_past + N) floats, so with a small audio_ctx it grows while a host-stepped
+    decode advances. A buffer that is replaced is given back: with U = 4 * seqs * n_text_head bytes, the two-token prompt at n_past = 0 needs 4 U, the steps
+    at n_past = 4 .. 9 need 5 .. 10 U. Keeping every replaced buffer adds (5 + .. + 10) U = 4.5 S after the first step, S = 10 U being the final need; freeing on
+    growth adds at most (16 - 4) U = 1.2 S with doubling. The bound is 2 S. The row buffers are sized by the prompt step and do not grow afterwards.
+    Reallocation must not lose state: the last logits equal those of a context that decodes the same tokens after a step large enough to size every buffer
+    once, so that nothing is reallocated under it."""
+    model = gf.synth_model("test-d128", seed=1234, attn_sharpness=2.0)
+    hp = model.hparams
+    sp = gf.special_tokens(hp)
+    import bench
+    seqs = 2
+    m = binding.HipModel.from_ggml(model)
+    pcm_dev = torch.from_numpy(bench.synth_pcm(seqs, seed=100)).cuda()
+    prompt = np.array([_prompt(sp)[:2]] * seqs, np.int32)
+    steps = [np.full((seqs, 1), 1000 + 7 * k, np.int32) for k in range(8)]      # fed at n_past = 2 .. 9
+
+    def start(presize):
+        ctx = binding.HipContext(m, seqs)
+        mels = torch.stack([ctx.mel_spectrogram(pcm_dev[b]) for b in range(seqs)])
+        ctx.set_flags(binding.WH_FLAG_PARITY_EXACT, 2)
+        ctx.set_audio_ctx(1)
+        ctx.encode(mels)
+        if presize:
+            ctx.decode(np.zeros((seqs, 10), np.int32), 0)      # 10 x 10 scores per head, 20 rows: more than any call below; positions 0 .. 9 are rewritten
+        return ctx
+
+    ctx = start(False)
+    ctx.decode(prompt, 0)
+    v1 = ctx.vram_bytes()
+    for k, t in enumerate(steps):
+        logits, probs = ctx.decode(t, 2 + k)
+    v = ctx.vram_bytes()
+    S = 4 * seqs * hp.n_text_head * 10
+    print("exact decoder scratch: vram grew by %d bytes over the steps at n_past = 2 .. 9; S = %d, bound 2 S = %d" % (v - v1, S, 2 * S))
+    assert v - v1 <= 2 * S
+    ctx.close()
+
+    ref_ctx = start(True)
+    v0 = ref_ctx.vram_bytes()
+    ref_ctx.decode(prompt, 0)
+    for k, t in enumerate(steps):
+        ref_logits, ref_probs = ref_ctx.decode(t, 2 + k)
+    assert ref_ctx.vram_bytes() == v0, "the comparison context was meant not to reallocate"
+    assert np.isfinite(logits).all()
+    assert np.array_equal(logits, ref_logits) and np.array_equal(probs, ref_probs)
+    ref_ctx.close()
     m.close()

@@ -10,6 +10,7 @@ import os
 import subprocess
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -20,7 +21,9 @@ HIP_LIB = os.path.join(LIB_DIR, "libwhisper_hip.so")
 HOST_LIB = os.path.join(LIB_DIR, "libWhisper.so")
 CLI_BIN = os.path.join(LIB_DIR, "whisper-main")
 
-HIP_SOURCES = ["gemm.hip", "decode1.hip", "attn_enc.hip", "attn_dec.hip", "elementwise.hip", "mel.hip", "exact.hip", "runtime.hip"]
+# the runtime behind the C ABI, one unit per responsibility; runtime.h holds what they share (host code: the kernel units do not include it)
+RUNTIME_SOURCES = ["options.hip", "model.hip", "comm.hip", "context.hip", "encode.hip", "exact_graphs.hip", "decode.hip", "beam.hip", "ops_debug.hip"]
+HIP_SOURCES = ["gemm.hip", "decode1.hip", "attn_enc.hip", "attn_dec.hip", "elementwise.hip", "mel.hip", "exact.hip"] + RUNTIME_SOURCES
 # exact.hip restates the reference CPU path's summation order: a fused multiply-add only where the source says fma()
 EXTRA_FLAGS = {"exact.hip": ["-ffp-contract=off"]}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -49,15 +52,20 @@ def build_hip(force: bool = False) -> str:
     headers = [os.path.join(CSRC, h) for h in ("common.h", "kernels.h", "epilogue.h", "exact_ops.h")] + [os.path.join(ROOT, "include", "whisper_hip.h")]
     obj_dir = os.path.join(LIB_DIR, "obj")
     os.makedirs(obj_dir, exist_ok=True)
+    stale = []
     for s in HIP_SOURCES:
         src = os.path.join(CSRC, s)
         obj = os.path.join(obj_dir, s.replace(".hip", ".o"))
-        if force or _newer(obj, [src] + headers):
+        deps = [src] + headers + ([os.path.join(CSRC, "runtime.h")] if s in RUNTIME_SOURCES else [])
+        if force or _newer(obj, deps):
             # WH_PROBES=1: the tile-shape experiments and ablation instances of tools/*probe* (not in the shipped objects)
             probes = ["-DWH_PROBES"] if os.environ.get("WH_PROBES", "") not in ("", "0") else []
-            _run([HIPCC, "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wno-unused-result"] + probes + EXTRA_FLAGS.get(s, []) +
-                 ["-I" + os.path.join(ROOT, "include"), "-c", src, "-o", obj])
+            stale.append([HIPCC, "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wno-unused-result"] + probes + EXTRA_FLAGS.get(s, []) +
+                         ["-I" + os.path.join(ROOT, "include"), "-c", src, "-o", obj])
         objs.append(obj)
+    # the units are independent: a few compilers at a time (MAX_JOBS, at most 16), gemm.hip -- by far the longest -- first
+    with ThreadPoolExecutor(max_workers=max(1, min(16, int(os.environ.get("MAX_JOBS", "0") or 0) or os.cpu_count() or 1))) as pool:
+        list(pool.map(_run, stale))
     if force or _newer(HIP_LIB, objs):
         _run([HIPCC, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", HIP_LIB] + objs + ["-ldl"])
     return HIP_LIB

@@ -343,11 +343,11 @@ namespace wh
 	int launchExactFlashAttn( const float* q, const float* k, const float* v, float* out, int batch, int H, int T, const f16* expTab, hipStream_t stream )
 	{
 		const size_t lds = (size_t)FQ * T * 4 + (size_t)FQ * T * 2 + FQ * 64 * 2;
-		static bool attr = false;
-		if( !attr )
+		static PerDeviceOnce once;
+		if( const int onceDev = once.needed(); onceDev >= 0 )
 		{
 			WH_HIP( hipFuncSetAttribute( (const void*)exFlashAttn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096 ) );
-			attr = true;
+			once.mark( onceDev );
 		}
 		if( lds > 160 * 1024 - 4096 ) { setError( "exact attention: n_audio_ctx too large" ); return WH_E_INVALIDARG; }
 		hipLaunchKernelGGL( exFlashAttn, dim3( ( T + FQ - 1 ) / FQ, H, batch ), dim3( 256 ), lds, stream, q, k, v, out, T, H * 64, expTab );

@@ -1,0 +1,708 @@
+// Diagnostics and development aids: the profiler's switches, wh_debug_read, the op-level entry points (wh_op_*) and the micro-benchmarks of
+// wh_debug_probe with their kernels.
+#include "runtime.h"
+
+namespace
+{
+	__global__ void probeEmpty( int* p ) { if( p && threadIdx.x == 0xFFFF ) *p = 1; }
+
+	// Device memory of the op-level entry points, which have no context to own it: one buffer per (device, key), allocated and filled on first use,
+	// reused by every later call with that key and kept for the life of the process.
+	struct OpScratch
+	{
+		struct Key
+		{
+			int device;
+			const void* key;
+			bool operator<( const Key& o ) const { return device != o.device ? device < o.device : key < o.key; }
+		};
+		std::mutex mx;
+		std::map<Key, void*> bufs;
+		template<class F> int get( const void* key, size_t bytes, void** out, F&& fill )
+		{
+			int dev = 0;
+			WH_HIP( hipGetDevice( &dev ) );
+			std::lock_guard<std::mutex> lk( mx );
+			void*& p = bufs.emplace( Key{ dev, key }, nullptr ).first->second;
+			if( !p )
+			{
+				void* v = nullptr;
+				WH_HIP( hipMalloc( &v, bytes ) );
+				const int rc = fill( v );
+				if( rc != 0 ) { (void)hipFree( v ); return rc; }
+				p = v;
+			}
+			*out = p;
+			return 0;
+		}
+	};
+	OpScratch g_opSplitK, g_opExpTable;
+
+	// what a probe run holds: released when wh_debug_probe returns, on its error paths too
+	struct ProbeEvent
+	{
+		hipEvent_t ev = nullptr;
+		int create() { WH_HIP( hipEventCreate( &ev ) ); return 0; }
+		~ProbeEvent() { if( ev ) (void)hipEventDestroy( ev ); }
+		operator hipEvent_t() const { return ev; }
+	};
+	struct ProbeMemory
+	{
+		std::vector<void*> owned;
+		template<class T> int alloc( T** p, size_t bytes )
+		{
+			WH_HIP( hipMalloc( (void**)p, bytes ) );
+			owned.push_back( *p );
+			return 0;
+		}
+		~ProbeMemory()
+		{
+			for( void* p : owned ) (void)hipFree( p );
+		}
+	};
+}
+
+extern "C" {
+
+int wh_profile_enable( wh_context* c, int on )
+{
+	if( !c ) return WH_E_INVALIDARG;
+	WH_BIND( c->m );
+	c->prof.reset();
+	c->prof.on = on != 0;
+	if( c->prof.on )
+	{
+		// calibration: what an event pair around a launch measures when the kernel does nothing (the first launch of a
+		// kernel loads its code object: keep that out of the average)
+		for( int i = 0; i < 4; i++ ) hipLaunchKernelGGL( probeEmpty, dim3( 1 ), dim3( 64 ), 0, c->stream, (int*)nullptr );
+		WH_HIP( hipStreamSynchronize( c->stream ) );
+		for( int i = 0; i < 64; i++ )
+			WH_CHECK( profiled( c, KC_EVENT_PAIR, 0.0, 0.0, [ & ]() { hipLaunchKernelGGL( probeEmpty, dim3( 1 ), dim3( 64 ), 0, c->stream, (int*)nullptr ); return 0; } ) );
+	}
+	return 0;
+}
+
+int wh_profile_read( wh_context* c, wh_profile_entry* out, int cap, int* count )
+{
+	if( !c || !count ) return WH_E_INVALIDARG;
+	WH_BIND( c->m );
+	WH_HIP( hipStreamSynchronize( c->stream ) );
+	c->prof.resolve();
+	int n = 0;
+	for( int i = 0; i < KC_COUNT; i++ )
+	{
+		if( c->prof.calls[ i ] == 0 ) continue;
+		if( out && n < cap )
+		{
+			wh_profile_entry& e = out[ n ];
+			memset( &e, 0, sizeof( e ) );
+			snprintf( e.name, sizeof( e.name ), "%s", kernelClassNames[ i ] );
+			e.calls = c->prof.calls[ i ];
+			e.ms = c->prof.ms[ i ];
+			e.flops = c->prof.flops[ i ];
+			e.bytes = c->prof.bytes[ i ];
+		}
+		n++;
+	}
+	*count = n;
+	return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// debug reads
+// ------------------------------------------------------------------------------------------------------------------
+static int readHeadMajor( wh_context* c, const f16* src, int batch, int rows, int rowStride, float* dst )
+{
+	// [b][h][rowStride][64] FP16 -> [b][rows][H*64] FP32
+	const int H = c->m->hp.n_audio_head, d = H * HEAD_DIM;
+	std::vector<uint16_t> tmp( (size_t)batch * H * rowStride * HEAD_DIM );
+	WH_HIP( hipStreamSynchronize( c->stream ) );
+	WH_HIP( hipMemcpy( tmp.data(), src, tmp.size() * 2, hipMemcpyDeviceToHost ) );
+	for( int b = 0; b < batch; b++ )
+		for( int h = 0; h < H; h++ )
+			for( int t = 0; t < rows; t++ )
+				for( int j = 0; j < HEAD_DIM; j++ )
+					dst[ ( (size_t)b * rows + t ) * d + h * HEAD_DIM + j ] = f16BitsToF32( tmp[ ( ( (size_t)b * H + h ) * rowStride + t ) * HEAD_DIM + j ] );
+	return 0;
+}
+
+int wh_debug_read( wh_context* c, const char* what, int layer, int rows, float* dstHost, int64_t dstCapFloats )
+{
+	if( !c || !what || !dstHost ) return WH_E_INVALIDARG;
+	WH_BIND( c->m );
+	const wh_hparams& hp = c->m->hp;
+	const int d = hp.n_audio_state;
+	const int batch = c->lastEncBatch;
+	const int seqs = c->lastBatch;
+	const std::string w = what;
+	if( w == "exp-table" )
+	{
+		// the arena's copy of the reference's exponential table (non-positive arguments), as FP32 values
+		if( dstCapFloats < EXP_TABLE_ENTRIES ) return WH_E_BOUNDS;
+		std::vector<uint16_t> tmp( EXP_TABLE_ENTRIES );
+		WH_HIP( hipMemcpy( tmp.data(), c->m->at<f16>( c->m->L.expTab ), EXP_TABLE_ENTRIES * 2, hipMemcpyDeviceToHost ) );
+		for( int i = 0; i < EXP_TABLE_ENTRIES; i++ ) dstHost[ i ] = f16BitsToF32( tmp[ (size_t)i ] );
+		return 0;
+	}
+	if( w == "exact-gelu-table" || w == "exact-exp-table" )
+	{
+		// WH_FLAG_PARITY_EXACT's copies of ggml_init's tables, all 65536 entries, as FP32 values
+		if( dstCapFloats < 65536 ) return WH_E_BOUNDS;
+		WH_CHECK( exactTables( c ) );
+		std::vector<uint16_t> tmp( 65536 );
+		WH_HIP( hipMemcpy( tmp.data(), w == "exact-gelu-table" ? c->ex.gelu : c->ex.expt, 65536 * 2, hipMemcpyDeviceToHost ) );
+		for( int i = 0; i < 65536; i++ ) dstHost[ i ] = f16BitsToF32( tmp[ (size_t)i ] );
+		return 0;
+	}
+	if( w.compare( 0, 6, "exact:" ) == 0 )
+	{
+		// a buffer of the exact-order encoder as the last wh_encode left it (first chunk of windows): x, cur, q, k, v, kqv [windows][n_ctx][d], h [..][4 d], conv1 [..][2 n_ctx][d]
+		const std::string n = w.substr( 6 );
+		const wh_context::Exact& e = c->ex;
+		const float* src = n == "x" ? e.x : n == "cur" ? e.cur : n == "q" ? e.q : n == "k" ? e.k : n == "v" ? e.v : n == "kqv" ? e.kqv : n == "h" ? e.h : n == "conv1" ? e.conv1 : nullptr;
+		if( !src ) { setError( "debug_read: no such exact-mode buffer (or the mode has not run)" ); return WH_E_NOT_READY; }
+		const int64_t count = (int64_t)std::min( batch, e.encWindows ) * c->T * d * ( n == "h" ? 4 : n == "conv1" ? 2 : 1 );
+		if( dstCapFloats < count ) return WH_E_BOUNDS;
+		WH_HIP( hipStreamSynchronize( c->stream ) );
+		WH_HIP( hipMemcpy( dstHost, src, (size_t)count * 4, hipMemcpyDeviceToHost ) );
+		return 0;
+	}
+	if( w == "logits" || w == "probs" )
+	{
+		// what the LAST decode step left: logits (or, after wh_decode with probsHost / the sampler, probabilities) of every sequence, [seqs][n_vocab]
+		const int64_t n = (int64_t)seqs * hp.n_vocab;
+		if( n <= 0 || dstCapFloats < n ) return WH_E_BOUNDS;
+		WH_HIP( hipStreamSynchronize( c->stream ) );
+		WH_HIP( hipMemcpy( dstHost, w == "logits" ? c->logits : c->probs, (size_t)n * 4, hipMemcpyDeviceToHost ) );
+		return 0;
+	}
+	if( w == "cross-k1" || w == "cross-v1" )
+	{
+		// ONE window (index `rows`) of a layer's cross-attention cache: [n_ctx][d] -- contexts of hundreds of windows
+		if( layer < 0 || layer >= hp.n_text_layer || rows < 0 || rows >= batch || dstCapFloats < (int64_t)c->T * d ) return WH_E_BOUNDS;
+		const f16* base = ( w == "cross-k1" ? c->crossK : c->crossV ) + ( (int64_t)layer * c->maxBatch + rows ) * c->T * d;
+		return readHeadMajor( c, base, 1, c->T, c->T, dstHost );
+	}
+	if( w == "encode-out" )
+	{
+		// the FP16 LayerNorm output that feeds the cross-attention projection (of a batch the encoder took in one chunk)
+		if( batch > c->encChunk ) { setError( "debug_read: encode-out holds the last encoder chunk only" ); return WH_E_BOUNDS; }
+		const int64_t n = (int64_t)batch * c->T * d;
+		if( dstCapFloats < n ) return WH_E_BOUNDS;
+		std::vector<uint16_t> tmp( (size_t)n );
+		WH_HIP( hipStreamSynchronize( c->stream ) );
+		WH_HIP( hipMemcpy( tmp.data(), c->xn, (size_t)n * 2, hipMemcpyDeviceToHost ) );
+		for( int64_t i = 0; i < n; i++ ) dstHost[ i ] = f16BitsToF32( tmp[ (size_t)i ] );
+		return 0;
+	}
+	auto readF16 = [ & ]( const f16* src, int64_t n ) -> int
+	{
+		if( !src ) { setError( "debug_read: nothing captured (set WH_FLAG_DEBUG_CAPTURE before the call that produces it)" ); return WH_E_NOT_READY; }
+		if( dstCapFloats < n ) return WH_E_BOUNDS;
+		std::vector<uint16_t> tmp( (size_t)n );
+		WH_HIP( hipStreamSynchronize( c->stream ) );
+		WH_HIP( hipMemcpy( tmp.data(), src, (size_t)n * 2, hipMemcpyDeviceToHost ) );
+		for( int64_t i = 0; i < n; i++ ) dstHost[ i ] = f16BitsToF32( tmp[ (size_t)i ] );
+		return 0;
+	};
+	if( w == "enc.temp1" )
+	{
+		// conv1 + bias + GELU, time-major [batch][2*n_ctx][d] (the reference's tensor is [d][2*n_ctx]); padding rows dropped
+		if( !c->capTemp1 ) return readF16( nullptr, 0 );
+		const int64_t rowsT = 2ll * c->T;
+		if( dstCapFloats < batch * rowsT * d ) return WH_E_BOUNDS;
+		std::vector<uint16_t> tmp( (size_t)( batch * c->conv1Stride ) );
+		WH_HIP( hipStreamSynchronize( c->stream ) );
+		WH_HIP( hipMemcpy( tmp.data(), c->capTemp1, tmp.size() * 2, hipMemcpyDeviceToHost ) );
+		for( int b = 0; b < batch; b++ )
+			for( int64_t i = 0; i < rowsT * d; i++ ) dstHost[ b * rowsT * d + i ] = f16BitsToF32( tmp[ (size_t)( b * c->conv1Stride + d + i ) ] );
+		return 0;
+	}
+	if( w == "enc.layer0.in" )
+	{
+		const int64_t n = (int64_t)batch * c->T * d;
+		if( !c->capLayer0In ) return readF16( nullptr, 0 );
+		if( dstCapFloats < n ) return WH_E_BOUNDS;
+		WH_HIP( hipStreamSynchronize( c->stream ) );
+		WH_HIP( hipMemcpy( dstHost, c->capLayer0In, (size_t)n * 4, hipMemcpyDeviceToHost ) );
+		return 0;
+	}
+	if( w == "enc-KQV" ) return readF16( c->capEncKqv, (int64_t)batch * c->T * d );	   // layer 0, [batch][n_ctx][d] (heads side by side)
+	if( w == "dec-KQV" ) return readF16( c->capDecKqvSelf, (int64_t)c->capDecRows * d );   // layer 0 self-attention output, rows of the last wh_decode
+	if( w == "dec-KQV#2" ) return readF16( c->capDecKqvCross, (int64_t)c->capDecRows * d );
+	if( layer < 0 || layer >= hp.n_text_layer ) return WH_E_BOUNDS;
+	if( w == "cross-k" || w == "cross-v" )
+	{
+		if( dstCapFloats < (int64_t)batch * c->T * d ) return WH_E_BOUNDS;
+		const f16* base = ( w == "cross-k" ? c->crossK : c->crossV ) + (int64_t)layer * c->maxBatch * c->T * d;
+		return readHeadMajor( c, base, batch, c->T, c->T, dstHost );
+	}
+	if( w == "self-k" || w == "self-v" )
+	{
+		if( rows <= 0 || rows > hp.n_text_ctx || dstCapFloats < (int64_t)seqs * rows * d ) return WH_E_BOUNDS;
+		const f16* base = ( w == "self-k" ? c->selfK : c->selfV ) + (int64_t)layer * c->maxSeq * hp.n_text_ctx * d;
+		return readHeadMajor( c, base, seqs, rows, hp.n_text_ctx, dstHost );
+	}
+	setError( "debug_read: unknown item" );
+	return WH_E_INVALIDARG;
+}
+
+// ==================================================================================================================
+// op-level entry points
+// ==================================================================================================================
+int wh_op_mul_mat( void* stream, const void* aF16, const void* wF16, const float* bias, const float* residual, float* out, int M, int N, int K )
+{
+	GemmArgs g = plainGemm( (const f16*)aF16, (const f16*)wF16, M, N, K );
+	g.epi = EPI_F32; g.bias = bias; g.res = residual; g.out32 = out;
+	if( M > 32 && M <= GEMV_FUSED_MAX_ROWS && N <= 2048 && K >= 2048 )
+	{
+		// option dec_split needs room for its eight partial tiles: no context here, so the op-level entry keeps one buffer per (device, stream) -- calls on
+		// different streams never share partial tiles, calls on one stream are ordered (the decoder passes its context's buffer)
+		void* tiles = nullptr;
+		WH_CHECK( g_opSplitK.get( stream, 8ull * GEMV_FUSED_MAX_ROWS * 2048 * sizeof( float ), &tiles, []( void* ) { return 0; } ) );
+		g.splitScratch = (float*)tiles;
+	}
+	// the same choice the decoder makes: up to 32 rows go to the gemv when K allows it
+	if( M <= GEMV_MAX_ROWS && ( K % 128 ) == 0 ) return launchGemv( g, (hipStream_t)stream );	   // the op-level entry is the decode-step product: up to 512 rows on the weight-streaming kernels
+	return M <= 32 ? launchGemmSkinny( g, (hipStream_t)stream ) : launchGemm( g, (hipStream_t)stream );
+}
+
+int wh_op_mul_mat_gelu( void* stream, const void* aF16, const void* wF16, const float* bias, void* outF16, int M, int N, int K )
+{
+	if( !bias ) { setError( "mul_mat_gelu: bias is required" ); return WH_E_INVALIDARG; }
+	GemmArgs g = plainGemm( (const f16*)aF16, (const f16*)wF16, M, N, K );
+	g.epi = EPI_F16_GELU; g.bias = bias; g.out16 = (f16*)outF16;
+	if( M <= GEMV_MAX_ROWS && ( K % 128 ) == 0 ) return launchGemv( g, (hipStream_t)stream );	   // the op-level entry is the decode-step product: up to 512 rows on the weight-streaming kernels
+	return M <= 32 ? launchGemmSkinny( g, (hipStream_t)stream ) : launchGemm( g, (hipStream_t)stream );
+}
+
+int wh_op_layer_norm( void* stream, const float* x, const float* w, const float* b, void* outF16, int rows, int d )
+{
+	return launchLayerNorm( x, w, b, (f16*)outF16, rows, d, (hipStream_t)stream );
+}
+
+int wh_op_flash_attention( void* stream, const void* q, const void* k, const void* vT, void* out, int batch, int heads, int nCtx )
+{
+	// no model here: the op-level entry keeps its own copy of the exponential's table per device (built like wh_model_finalize builds the arena's)
+	const f16* expTab = nullptr;
+	if( g_tuning & TUNE_ATTN_ENC_TABLE )
+	{
+		void* tab = nullptr;
+		WH_CHECK( g_opExpTable.get( nullptr, EXP_TABLE_ENTRIES * 2, &tab, []( void* dst ) -> int
+		{
+			std::vector<_Float16> tab( EXP_TABLE_ENTRIES );
+			for( uint32_t i = 0; i < (uint32_t)EXP_TABLE_ENTRIES; i++ )
+			{
+				const uint16_t bits = (uint16_t)( i | 0x8000u );
+				_Float16 h;
+				memcpy( &h, &bits, 2 );
+				tab[ i ] = (_Float16)expf( (float)h );
+			}
+			WH_HIP( hipMemcpy( dst, tab.data(), EXP_TABLE_ENTRIES * 2, hipMemcpyHostToDevice ) );
+			return 0;
+		} ) );
+		expTab = (const f16*)tab;
+	}
+	return launchAttentionEnc( (const f16*)q, (const f16*)k, (const f16*)vT, (f16*)out, batch, heads, nCtx, roundUp( nCtx, 256 ), false, expTab, (hipStream_t)stream );
+}
+
+int wh_op_decoder_attention( void* stream, const void* qF16, const void* kCache, const void* vCache, void* outF16, int sequences, int heads,
+	int nTok, int nKeys, int keyStride, int causal, int nPast, int group, int parityThreads )
+{
+	DecAttnArgs a = {};
+	a.q = (const f16*)qF16; a.kc = (const f16*)kCache; a.vc = (const f16*)vCache; a.out = (f16*)outF16;
+	a.batch = sequences; a.H = heads; a.nTok = nTok; a.nKeys = nKeys; a.keyStride = keyStride;
+	a.causal = causal; a.nPast = nPast; a.group = group; a.parityThreads = parityThreads;
+	return launchAttentionDec( a, (hipStream_t)stream );
+}
+
+int wh_op_decoder_cross_attention( void* stream, const float* x, const float* lnW, const float* lnB, const void* qW, const float* qB, float qScale,
+	const void* kCache, const void* vCache, void* outF16, int sequences, int heads, int nKeys, int keyStride, int group )
+{
+	if( !x || !lnW || !lnB || !qW || !qB ) { setError( "decoder_cross_attention: null argument" ); return WH_E_INVALIDARG; }
+	DecAttnArgs a = {};
+	a.kc = (const f16*)kCache; a.vc = (const f16*)vCache; a.out = (f16*)outF16;
+	a.batch = sequences; a.H = heads; a.nTok = 1; a.nKeys = nKeys; a.keyStride = keyStride;
+	a.group = group;
+	a.lnX = x; a.lnW = lnW; a.lnB = lnB; a.qW = (const f16*)qW; a.qB = qB; a.qScale = qScale;
+	return launchAttentionDec( a, (hipStream_t)stream );
+}
+
+int wh_op_soft_max( void* stream, float* x, int rows, int cols )
+{
+	return launchSoftMaxRows( x, rows, cols, (hipStream_t)stream );
+}
+
+int wh_op_vocab_soft_max( void* stream, const float* logits, float* probs, int rows, int cols )
+{
+	if( !logits || !probs || rows < 1 || cols < 1 ) { setError( "vocab_soft_max: null pointer or empty shape" ); return WH_E_INVALIDARG; }
+	return launchVocabSoftMax( logits, probs, rows, cols, (hipStream_t)stream );
+}
+
+int wh_op_lang_probs( void* stream, const float* logits, int rows, int nVocab, int tokenSot, int nLang, float* langP, int32_t* best )
+{
+	if( !logits || !langP || !best || rows < 1 || nVocab < 1 || nVocab > 52224 || nLang < 1 || nLang > 1024 || tokenSot < 0 || (int64_t)tokenSot + 1 + nLang > nVocab )
+	{
+		setError( "lang_probs: bad pointer or size (at most 52224 columns), or the language block tokenSot + 1 .. tokenSot + nLang (1 .. 1024 tokens) leaves the row" );
+		return WH_E_INVALIDARG;
+	}
+	return launchLangProbs( logits, nVocab, rows, nVocab, tokenSot, nLang, langP, best, (hipStream_t)stream );
+}
+
+static bool tokenArgsOk( const float* probs, const wh_token_data* out, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot )
+{
+	return probs && out && rows >= 1 && nVocab >= 1 && tokenBeg >= 1 && tokenBeg < nVocab && tokenSot >= 0 && tokenSot < tokenBeg && tokenSolm >= 0 &&
+		tokenSolm < tokenBeg && tokenNot >= 0 && tokenNot < tokenBeg;
+}
+
+int wh_op_sample_best( void* stream, const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot,
+	int forceTimestamp, int isInitial, wh_token_data* out )
+{
+	static_assert( sizeof( wh_token_data ) == sizeof( TokenData ), "token data layout" );
+	if( !tokenArgsOk( probs, out, rows, nVocab, tokenBeg, tokenSot, tokenSolm, tokenNot ) ) { setError( "sample_best: bad pointer, size or token id" ); return WH_E_INVALIDARG; }
+	return launchSampleBest( probs, rows, nVocab, tokenBeg, tokenSot, tokenSolm, tokenNot, forceTimestamp ? 1 : 0, isInitial ? 1 : 0, (TokenData*)out,
+		(hipStream_t)stream );
+}
+
+int wh_op_beam_candidates( void* stream, const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot,
+	int forceTimestamp, int isInitial, int width, wh_token_data* out )
+{
+	if( !tokenArgsOk( probs, out, rows, nVocab, tokenBeg, tokenSot, tokenSolm, tokenNot ) || width < 1 || width > 8 )
+	{
+		setError( "beam_candidates: bad pointer, size, token id or width (1 .. 8)" );
+		return WH_E_INVALIDARG;
+	}
+	return launchBeamCandidates( probs, rows, nVocab, tokenBeg, tokenSot, tokenSolm, tokenNot, forceTimestamp ? 1 : 0, isInitial ? 1 : 0, width,
+		(TokenData*)out, (hipStream_t)stream );
+}
+
+int wh_op_reorder_self_cache( void* stream, void* cacheK, void* cacheV, void* scratchK, void* scratchV, const int32_t* parents,
+	const int32_t* rowsDev, int layers, int sequences, int maxSeq, int heads, int keyStride, int group )
+{
+	if( !cacheK || !cacheV || !scratchK || !scratchV || !parents || !rowsDev ) { setError( "reorder_self_cache: null pointer" ); return WH_E_INVALIDARG; }
+	if( layers < 1 || sequences < 1 || sequences > maxSeq || heads < 1 || keyStride < 1 || group < 1 || group > sequences )
+	{
+		setError( "reorder_self_cache: need layers, heads, keyStride >= 1, 1 <= group <= sequences <= maxSeq" );
+		return WH_E_INVALIDARG;
+	}
+	return launchReorderCacheDev( (f16*)cacheK, (f16*)cacheV, (f16*)scratchK, (f16*)scratchV, parents, rowsDev, layers, sequences, maxSeq, heads,
+		keyStride, group, (hipStream_t)stream );
+}
+
+
+// ------------------------------------------------------------------------------------------------------------------
+// micro-benchmarks used by tools/gemm_probe.py (development aid; not on the product path)
+// ------------------------------------------------------------------------------------------------------------------
+namespace
+{
+	// Grid-wide barrier cost probe: `n` rounds of { every workgroup publishes 64 bytes, barrier, reads another workgroup's
+	// line and checks it }. One monotonic counter, agent-scope release on arrival, acquire polling, bounded spin.
+	// mode 0: every workgroup polls the one counter; mode 1: arrivals are counted per XCD (workgroup id % 8) and the last
+	// arrival of an XCD bumps the global counter by its XCD's population, so only 8 RMWs hit the shared line.
+	__global__ void __launch_bounds__( 256 ) probeGridBarrier( unsigned* counters, float* buf, int n, int mode, int* err )
+	{
+		const unsigned G = gridDim.x, wg = blockIdx.x;
+		const int lane = threadIdx.x;
+		unsigned* const global = counters;
+		unsigned* const perXcd = counters + 64 + ( wg & 7 ) * 64;	// own 256-byte line per counter
+		const unsigned xcdPop = ( G + 7 - ( wg & 7 ) ) / 8;
+		__shared__ int dead;
+		if( lane == 0 ) dead = 0;
+		for( int it = 0; it < n; it++ )
+		{
+			float* const slot = buf + ( it & 1 ) * G * 16;
+			if( lane < 16 ) slot[ wg * 16 + lane ] = (float)( it * 7 + (int)wg + lane );
+			__syncthreads();
+			if( lane == 0 )
+			{
+				const unsigned target = (unsigned)( it + 1 ) * G;
+				if( mode == 0 )
+					__hip_atomic_fetch_add( global, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT );
+				else
+				{
+					const unsigned prev = __hip_atomic_fetch_add( perXcd, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT );
+					if( ( prev + 1 ) % xcdPop == 0 )
+						__hip_atomic_fetch_add( global, xcdPop, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT );
+				}
+				unsigned spins = 0;
+				while( __hip_atomic_load( global, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT ) < target )
+				{
+					if( ++spins > ( 1u << 21 ) )
+					{
+						*err = 2;
+						dead = 1;
+						break;
+					}
+				}
+			}
+			__syncthreads();
+			if( dead ) return;
+			const unsigned other = ( wg + 97 ) % G;
+			if( lane < 16 )
+			{
+				const float got = __builtin_nontemporal_load( slot + other * 16 + lane );
+				if( got != (float)( it * 7 + (int)other + lane ) ) *err = 1;
+			}
+		}
+	}
+	// max |a - b| over n floats (non-negative floats order like their bit patterns; NaN counts as +inf)
+	__global__ void probeMaxDiff( const float* a, const float* b, long long n, int* out )
+	{
+		float m = 0.0f;
+		for( long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x )
+		{
+			const float d = fabsf( a[ i ] - b[ i ] );
+			m = ( d != d ) ? INFINITY : fmaxf( m, d );
+		}
+		for( int off = 32; off > 0; off >>= 1 ) m = fmaxf( m, __shfl_xor( m, off ) );
+		if( ( threadIdx.x & 63 ) == 0 ) atomicMax( out, __float_as_int( m ) );
+	}
+	__global__ void probeFill( _Float16* p, long long n, unsigned seed )
+	{
+		for( long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x )
+		{
+			unsigned h = (unsigned)i * 2654435761u + seed;
+			h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
+			p[ i ] = (_Float16)( ( (float)( h & 0xFFFF ) / 32768.0f - 1.0f ) * 0.5f );
+		}
+	}
+}
+
+int wh_debug_probe( wh_context* c, int kind, int variant, int M, int N, int K, int iters, float* msPerIter )
+{
+	if( !c || !msPerIter || iters <= 0 ) return WH_E_INVALIDARG;
+	WH_BIND( c->m );
+	hipStream_t st = c->stream;
+	ProbeEvent e0, e1;
+	ProbeMemory mem;
+	WH_CHECK( e0.create() );
+	WH_CHECK( e1.create() );
+	int rc = 0;
+	float ms = 0;
+	if( kind == 0 || kind == 2 )
+	{
+		// chain of dependent empty kernels, `variant` workgroups of 256 threads each; kind 2 replays them from a graph
+		const int grid = variant > 0 ? variant : 1;
+		hipGraphExec_t exec = nullptr;
+		const int perGraph = 100;
+		if( kind == 2 )
+		{
+			hipGraph_t g = nullptr;
+			WH_HIP( hipStreamBeginCapture( st, hipStreamCaptureModeThreadLocal ) );
+			for( int i = 0; i < perGraph; i++ ) hipLaunchKernelGGL( probeEmpty, dim3( grid ), dim3( 256 ), 0, st, (int*)nullptr );
+			WH_HIP( hipStreamEndCapture( st, &g ) );
+			WH_HIP( hipGraphInstantiate( &exec, g, nullptr, nullptr, 0 ) );
+			(void)hipGraphDestroy( g );
+			WH_HIP( hipGraphLaunch( exec, st ) );
+		}
+		for( int i = 0; i < 20; i++ ) hipLaunchKernelGGL( probeEmpty, dim3( grid ), dim3( 256 ), 0, st, (int*)nullptr );
+		WH_HIP( hipStreamSynchronize( st ) );
+		WH_HIP( hipEventRecord( e0, st ) );
+		if( kind == 2 )
+			for( int i = 0; i < ( iters + perGraph - 1 ) / perGraph; i++ ) WH_HIP( hipGraphLaunch( exec, st ) );
+		else
+			for( int i = 0; i < iters; i++ ) hipLaunchKernelGGL( probeEmpty, dim3( grid ), dim3( 256 ), 0, st, (int*)nullptr );
+		WH_HIP( hipEventRecord( e1, st ) );
+		WH_HIP( hipEventSynchronize( e1 ) );
+		WH_HIP( hipEventElapsedTime( &ms, e0, e1 ) );
+		if( kind == 2 ) ms = ms * (float)iters / (float)( ( iters + perGraph - 1 ) / perGraph * perGraph );
+		if( exec ) (void)hipGraphExecDestroy( exec );
+	}
+	else if( kind == 1 )
+	{
+		void *A = nullptr, *W = nullptr, *out = nullptr;
+		WH_CHECK( mem.alloc( &A, (size_t)M * K * 2 ) );
+		WH_CHECK( mem.alloc( &W, (size_t)N * K * 2 ) );
+		WH_CHECK( mem.alloc( &out, (size_t)M * N * 4 ) );
+		hipLaunchKernelGGL( probeFill, dim3( 1024 ), dim3( 256 ), 0, st, (_Float16*)A, (long long)M * K, 1u );
+		hipLaunchKernelGGL( probeFill, dim3( 1024 ), dim3( 256 ), 0, st, (_Float16*)W, (long long)N * K, 2u );
+		GemmArgs g = plainGemm( (const f16*)A, (const f16*)W, M, N, K );
+		g.epi = EPI_F32; g.out32 = (float*)out;
+		g.groupM = variant / 100;	   // variant = tile variant + 100 * M tiles per band of the block walk (0 = default)
+		variant %= 100;
+		unsigned long long* stamps = nullptr;
+		if( variant == 35 || variant == 33 )
+		{
+			WH_CHECK( mem.alloc( &stamps, 32 ) );
+			WH_HIP( hipMemsetAsync( stamps, 0, 32, st ) );
+			g.pe = (const float*)stamps;
+		}
+		for( int i = 0; i < 2 && rc == 0; i++ ) rc = launchGemmVariant( g, variant, st );
+		if( rc == 0 )
+		{
+			WH_HIP( hipStreamSynchronize( st ) );
+			WH_HIP( hipEventRecord( e0, st ) );
+			for( int i = 0; i < iters && rc == 0; i++ ) rc = launchGemmVariant( g, variant, st );
+			WH_HIP( hipEventRecord( e1, st ) );
+			WH_HIP( hipEventSynchronize( e1 ) );
+			WH_HIP( hipEventElapsedTime( &ms, e0, e1 ) );
+		}
+		if( stamps && rc == 0 )
+		{
+			unsigned long long h[ 4 ] = {};
+			WH_HIP( hipMemcpy( h, stamps, 32, hipMemcpyDeviceToHost ) );
+			const double n = h[ 3 ] ? (double)h[ 3 ] : 1.0;
+			fprintf( stderr, "[gemm8 stamps] %dx%dx%d: per tile (wave 0, cycles) first-operand wait %.0f, K loop %.0f, epilogue %.0f; %.0f tiles\n", M, N, K,
+				h[ 0 ] / n, h[ 1 ] / n, h[ 2 ] / n, n );
+		}
+		// every variant is checked against the production path on the same operands: a pipeline that races is fast and wrong
+		// (variants 31 .. 39 are ablations, wrong by construction)
+		if( rc == 0 && ( variant == 34 || ( !( variant >= 31 && variant <= 39 ) && !( variant >= 41 && variant <= 49 ) && !( variant >= 60 && variant <= 69 ) ) ) )
+		{
+			void* ref = nullptr;
+			int* diff = nullptr;
+			WH_CHECK( mem.alloc( &ref, (size_t)M * N * 4 ) );
+			WH_CHECK( mem.alloc( &diff, 4 ) );
+			WH_HIP( hipMemsetAsync( diff, 0, 4, st ) );
+			GemmArgs g2 = plainGemm( (const f16*)A, (const f16*)W, M, N, K );
+			g2.epi = EPI_F32; g2.out32 = (float*)ref;
+			static const int refVariant = []() { const char* e = getenv( "WH_PROBE_REF" ); return e ? atoi( e ) : 2; }();
+			rc = launchGemmVariant( g2, refVariant, st );	   // 2 = the register-staged 128x128x32 kernel: shares no staging or scheduling code with the variants under test
+			if( rc == 0 )
+			{
+				hipLaunchKernelGGL( probeMaxDiff, dim3( 2048 ), dim3( 256 ), 0, st, (const float*)out, (const float*)ref, (long long)M * N, diff );
+				int bits = 0;
+				WH_HIP( hipMemcpyAsync( &bits, diff, 4, hipMemcpyDeviceToHost, st ) );
+				WH_HIP( hipStreamSynchronize( st ) );
+				float md;
+				memcpy( &md, &bits, 4 );
+				if( getenv( "WH_PROBE_REF" ) ) fprintf( stderr, "[gemm probe] variant %d against variant %d, %d x %d x %d: max |diff| = %g\n", variant, refVariant, M, N, K, (double)md );
+				if( !( md <= 1e-3f ) )
+				{
+					char buf[ 160 ];
+					snprintf( buf, sizeof( buf ), "gemm probe: variant %d differs from the production kernel by %g", variant, (double)md );
+					setError( buf );
+					rc = -1;
+				}
+			}
+		}
+	}
+	else if( kind == 3 )
+	{
+		// grid barrier: `variant` workgroups (must all be resident: <= number of CUs), M = mode, iters barriers per launch
+		const int grid = variant > 0 ? variant : 256;
+		unsigned* counters = nullptr;
+		float* buf = nullptr;
+		int* err = nullptr;
+		WH_CHECK( mem.alloc( &counters, 4096 ) );
+		WH_CHECK( mem.alloc( &buf, (size_t)grid * 16 * 2 * 4 ) );
+		WH_CHECK( mem.alloc( &err, 4 ) );
+		WH_HIP( hipMemsetAsync( err, 0, 4, st ) );
+		for( int rep = 0; rep < 2; rep++ )
+		{
+			WH_HIP( hipMemsetAsync( counters, 0, 4096, st ) );
+			WH_HIP( hipStreamSynchronize( st ) );
+			WH_HIP( hipEventRecord( e0, st ) );
+			hipLaunchKernelGGL( probeGridBarrier, dim3( grid ), dim3( 256 ), 0, st, counters, buf, iters, M, err );
+			WH_HIP( hipEventRecord( e1, st ) );
+			WH_HIP( hipEventSynchronize( e1 ) );
+			WH_HIP( hipEventElapsedTime( &ms, e0, e1 ) );
+		}
+		int herr = 0;
+		WH_HIP( hipMemcpy( &herr, err, 4, hipMemcpyDeviceToHost ) );
+		if( herr != 0 )
+		{
+			setError( herr == 1 ? "grid barrier probe: stale data after the barrier" : "grid barrier probe: spin limit reached" );
+			rc = -1;
+		}
+	}
+	else if( kind == 4 )
+	{
+		// MFMA-bound product NEXT TO the HBM-bound cross-attention, measured directly: the encoder product of M x N x K (the production
+		// launch: persistent gemmTiled8) `iters` times on stream A, attentionDecG<1,...> over `variant` windows x 16 heads x 1500 keys on stream B as often as fills
+		// the same time; each alone, then together -- for the persistent grid limited to 256 / 224 / 192 / 160 / 128 CUs, without CU masks (the attention's
+		// workgroups land where LDS and registers are free) and with complementary CU masks on the two streams. Results on stderr; ms = the unmasked 256-CU pair.
+		const int wins = variant > 0 ? variant : 224, H = 16, T = 1500, d = H * HEAD_DIM;
+		void *A = nullptr, *W = nullptr, *out = nullptr, *kc = nullptr, *vc = nullptr, *q = nullptr, *ao = nullptr;
+		WH_CHECK( mem.alloc( &A, (size_t)M * K * 2 ) );
+		WH_CHECK( mem.alloc( &W, (size_t)N * K * 2 ) );
+		WH_CHECK( mem.alloc( &out, (size_t)M * N * 4 ) );
+		const size_t kvBytes = (size_t)wins * H * T * HEAD_DIM * 2;
+		WH_CHECK( mem.alloc( &kc, kvBytes ) );
+		WH_CHECK( mem.alloc( &vc, kvBytes ) );
+		WH_CHECK( mem.alloc( &q, (size_t)wins * d * 2 ) );
+		WH_CHECK( mem.alloc( &ao, (size_t)wins * d * 2 ) );
+		hipLaunchKernelGGL( probeFill, dim3( 1024 ), dim3( 256 ), 0, st, (_Float16*)A, (long long)M * K, 1u );
+		hipLaunchKernelGGL( probeFill, dim3( 1024 ), dim3( 256 ), 0, st, (_Float16*)W, (long long)N * K, 2u );
+		hipLaunchKernelGGL( probeFill, dim3( 1024 ), dim3( 256 ), 0, st, (_Float16*)kc, (long long)( kvBytes / 2 ), 3u );
+		hipLaunchKernelGGL( probeFill, dim3( 1024 ), dim3( 256 ), 0, st, (_Float16*)vc, (long long)( kvBytes / 2 ), 4u );
+		hipLaunchKernelGGL( probeFill, dim3( 1024 ), dim3( 256 ), 0, st, (_Float16*)q, (long long)wins * d, 5u );
+		WH_HIP( hipStreamSynchronize( st ) );
+		GemmArgs g = plainGemm( (const f16*)A, (const f16*)W, M, N, K );
+		g.epi = EPI_F32; g.out32 = (float*)out;
+		DecAttnArgs a = {};
+		a.q = (const f16*)q; a.kc = (const f16*)kc; a.vc = (const f16*)vc; a.out = (f16*)ao;
+		a.batch = wins; a.H = H; a.nTok = 1; a.nKeys = T; a.keyStride = T; a.causal = 0; a.group = 1;
+		int cus = 0;
+		WH_HIP( hipDeviceGetAttribute( &cus, hipDeviceAttributeMultiprocessorCount, c->m->device ) );
+		auto wall = []() { return std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now().time_since_epoch() ).count(); };
+		auto timeIt = [ & ]( hipStream_t sa, hipStream_t sb, int nA, int nB, int cuLimit, double& msOut ) -> int
+		{
+			GemmArgs gl = g;
+			gl.cuLimit = cuLimit;
+			WH_HIP( hipDeviceSynchronize() );
+			const double t0 = wall();
+			// interleave the enqueues so that neither stream starts far ahead of the other
+			const int n = std::max( nA, nB );
+			for( int i = 0; i < n; i++ )
+			{
+				if( i < nA ) WH_CHECK( launchGemm( gl, sa ) );
+				if( i < nB ) WH_CHECK( launchAttentionDec( a, sb ) );
+			}
+			WH_HIP( hipDeviceSynchronize() );
+			msOut = wall() - t0;
+			return 0;
+		};
+		hipStream_t sa = nullptr, sb = nullptr;
+		WH_HIP( hipStreamCreateWithFlags( &sa, hipStreamNonBlocking ) );
+		WH_HIP( hipStreamCreateWithFlags( &sb, hipStreamNonBlocking ) );
+		double tA1 = 0, tB1 = 0, dummy = 0;
+		rc = timeIt( sa, sb, 3, 3, 0, dummy );	   // warm-up
+		if( rc == 0 ) rc = timeIt( sa, sb, iters, 0, 0, tA1 );
+		if( rc == 0 ) rc = timeIt( sa, sb, 0, iters, 0, tB1 );
+		const int nA = iters, nB = std::max( 1, (int)( iters * tA1 / std::max( tB1, 1e-6 ) + 0.5 ) );
+		double tA = 0, tB = 0;
+		if( rc == 0 ) rc = timeIt( sa, sb, nA, 0, 0, tA );
+		if( rc == 0 ) rc = timeIt( sa, sb, 0, nB, 0, tB );
+		if( rc == 0 )
+		{
+			fprintf( stderr, "[pair] product %d x %d x %d: %d launches %.2f ms alone (%.0f TFLOP/s); cross-attention %d windows: %d launches %.2f ms alone (%.2f TB/s)\n", M, N, K, nA, tA,
+				2.0 * M * N * K * nA / tA * 1e-9, wins, nB, tB, 2.0 * kvBytes * nB / tB * 1e-9 );
+			const int limits[] = { 0, 224, 192, 160, 128 };
+			for( int li = 0; li < 5 && rc == 0; li++ )
+			{
+				const int lim = limits[ li ];
+				double tAl = 0, tp = 0;
+				rc = timeIt( sa, sb, nA, 0, lim, tAl );
+				if( rc == 0 ) rc = timeIt( sa, sb, nA, nB, lim, tp );
+				if( rc == 0 ) fprintf( stderr, "[pair] no masks, product on %3d CUs: product alone %.2f ms, pair %.2f ms = %.3f of (A + B) = %.3f of (A at this limit + B)\n", lim ? lim : cus, tAl, tp,
+					tp / ( tA + tB ), tp / ( tAl + tB ) );
+				if( li == 0 ) ms = (float)tp * (float)iters;
+			}
+			// complementary CU masks: CU i of the mask belongs to XCD i % 8 (a multiple of 8 keeps the split even over the XCDs)
+			for( int li = 1; li < 5 && rc == 0; li++ )
+			{
+				const int lim = limits[ li ];
+				uint32_t mA[ 16 ] = {}, mB[ 16 ] = {};
+				const uint32_t words = (uint32_t)( ( cus + 31 ) / 32 );
+				for( int i = 0; i < cus && i < 512; i++ ) ( i < lim ? mA : mB )[ i >> 5 ] |= 1u << ( i & 31 );
+				hipStream_t ma = nullptr, mb = nullptr;
+				if( hipExtStreamCreateWithCUMask( &ma, words, mA ) != hipSuccess || hipExtStreamCreateWithCUMask( &mb, words, mB ) != hipSuccess ) { fprintf( stderr, "[pair] CU-masked streams unavailable\n" ); break; }
+				double tAl = 0, tBl = 0, tp = 0;
+				rc = timeIt( ma, mb, nA, 0, lim, tAl );
+				if( rc == 0 ) rc = timeIt( ma, mb, 0, nB, lim, tBl );
+				if( rc == 0 ) rc = timeIt( ma, mb, nA, nB, lim, tp );
+				if( rc == 0 ) fprintf( stderr, "[pair] masks %3d | %3d CUs: product alone %.2f ms, attention alone %.2f ms (%.2f TB/s), pair %.2f ms = %.3f of (A + B at 256 CUs)\n", lim, cus - lim, tAl, tBl,
+					2.0 * kvBytes * nB / tBl * 1e-9, tp, tp / ( tA + tB ) );
+				(void)hipStreamDestroy( ma ); (void)hipStreamDestroy( mb );
+			}
+		}
+		(void)hipStreamDestroy( sa ); (void)hipStreamDestroy( sb );
+	}
+	else
+		rc = WH_E_INVALIDARG;
+	*msPerIter = ms / (float)iters;
+	return rc;
+}
+
+}	// extern "C"
