@@ -36,11 +36,20 @@ int32_t whisperc_run_full_audio_ctx( void* ctx, const float* pcm, uint32_t nSamp
 	const int32_t* promptTokens, int nPrompt, int nMaxTextCtx, int audioCtx );
 int32_t whisperc_run_full_beam( void* ctx, const float* pcm, uint32_t nSamples, const char* language, uint32_t flags, int maxTokens,
 	const int32_t* promptTokens, int nPrompt, int nMaxTextCtx, int beamWidth );
-/* iMediaFoundation::loadAudioFileData( WAV bytes: 16 kHz, mono/stereo, PCM16/float32 ) + iContext::runStreamed( params,
+/* iMediaFoundation::loadAudioFileData( WAV bytes: PCM of 8 .. 32 bits or float32, 1 .. 8 channels, any rate from 1 to 384 kHz ) + iContext::runStreamed( params,
  * { progress callback }, reader ): the streaming entry the reference's CLI uses by default (Examples/main/main.cpp:305-311).
  * The values the progress sink received are copied to progressOut (first progressCap of them), their count to *progressCount. */
 int32_t whisperc_run_streamed( void* ctx, const void* wavBytes, uint64_t wavSize, const char* language, uint32_t flags, int maxTokens,
 	const int32_t* promptTokens, int nPrompt, int nMaxTextCtx, double* progressOut, int progressCap, int* progressCount );
+/* Audio of any rate -> 16 kHz FP32 on the GPU (wh_resample_host of whisper_hip.h, on the calling thread's current device): nFrames interleaved frames of
+ * `channels` samples in `format` (0 u8, 1 s16, 2 s24, 3 s32, 4 float32) at `rate` Hz; channel -1 = the mean of the channels, else that channel.
+ * *nOut = ceil( nFrames * 16000 / rate ); dst == NULL only counts, cap (floats of dst) < *nOut is E_INVALIDARG. rate 16000 converts without filtering. */
+int32_t whisperc_resample( const void* src, int32_t format, int32_t channels, int32_t channel, int32_t rate, int64_t nFrames, float* dst, int64_t cap,
+	int64_t* nOut );
+/* iMediaFoundation::loadAudioFile + iAudioBuffer::getPcmMono (stereo != 0: getPcmStereo, interleaved, 2 floats per frame): the WAV file as 16 kHz floats.
+ * *nFrames = its 16 kHz frames; dst == NULL reads the file and parses its chunks, converts nothing and returns the count (so a
+ * caller that asks for the count first reads the file twice); cap counts floats. */
+int32_t whisperc_load_audio( const char* pathUtf8, int32_t stereo, float* dst, int64_t cap, int64_t* nFrames );
 /* whisperc_run_full + the token-timestamp fields of sFullParams (set TokenTimestamps = 0x100 in flags): thold_pt, thold_ptsum, max_len */
 int32_t whisperc_run_full_tt( void* ctx, const float* pcm, uint32_t nSamples, const char* language, uint32_t flags, int maxTokens,
 	const int32_t* promptTokens, int nPrompt, int nMaxTextCtx, float tholdPt, float tholdPtsum, int maxLen );

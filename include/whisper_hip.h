@@ -194,6 +194,35 @@ WH_API int wh_mel_spectrogram_batch( wh_context* c, const float* pcmDev, int64_t
 WH_API int wh_mel_spectrogram_window( wh_context* c, const float* pcmDev, int64_t nSamples, int64_t frame0, int64_t nFrames, int64_t nChunks,
 	int reusePreviousMax, float* melDev );
 
+/* PCM of any rate -> 16 kHz mono FP32 on the GPU. Replaces what the reference leaves to the OS: its Media Foundation source reader is asked for 16 kHz
+ * float and resamples on the way (Whisper/MF/loadAudioFile.cpp, PcmReader.cpp). Rational polyphase resampling with a Kaiser-windowed sinc:
+ *   g = gcd( inRate, 16000 ), L = 16000 / g, M = inRate / g; w = 0.9475937167399596 * min( inRate, 16000 ) / inRate; half = ceil( 32 / w ), K = 2 half + 2;
+ *   h[p][k] = w sinc( w d ) I0( 14.769656459379492 sqrt( 1 - x^2 ) ) / I0( 14.769656459379492 ), d = k - half - p / L, x = d / ( half + 1 ), 0 where |x| >= 1,
+ *   evaluated in double and rounded once to float;  y[n] = sum_k h[p][k] x[base - half + k], base = ( n M ) div L, p = ( n M ) mod L, x zero outside the buffer.
+ * The sum runs in FP64 (one fma per tap, ascending k, one rounding to float): the correctly rounded value of the sum over the float taps up to ~1e-14.
+ * Samples become floats as u8 (v - 128) / 128, s16 v / 32768, s24 v / 8388608, s32 (float)( v * 2^-31 ), f32 as is; the mean of C channels is their FP32
+ * sum in channel order times 1.0f / C, taken before the filter. inRate == 16000 filters nothing: conversion and downmix only.
+ * inRate 1000 .. 384000, 1 .. 8 interleaved channels, nOut == wh_resample_out_len( inRate, nFrames ) = ceil( nFrames L / M ), or WH_E_INVALIDARG;
+ * nFrames == 0 is nOut == 0 and success. */
+typedef enum { WH_PCM_U8, WH_PCM_S16, WH_PCM_S24, WH_PCM_S32, WH_PCM_F32 } wh_pcm_format;
+/* Host only: works without a device. */
+WH_API int wh_resample_out_len( int inRate, int64_t nFrames, int64_t* nOut );
+/* device -> device, on `stream`; channel = -1: the mean of the channels, else that channel; dst[ n * dstStride ], dstStride 1 or 2 (interleaved stereo is
+ * two calls). srcDev aligned to its sample type (s24: any). The rate's tap table is built and uploaded by the first call with that rate on the device (the
+ * call waits for it) and kept for the life of the process: L * K floats -- 0.8 KB at 48 kHz, 119 KB at 44.1 kHz, 175 KB at 11.025 kHz, up to 104 MB for a rate
+ * coprime to 16000 (L = 16000).
+ * A workgroup owns min( 1024, ( ( 8191 - K ) L div M + 1 ) rounded down to a multiple of 64 ) consecutive outputs. */
+WH_API int wh_resample( void* stream, const void* srcDev, int format, int channels, int channel, int inRate, int64_t nFrames, float* dstDev, int64_t dstStride,
+	int64_t nOut );
+/* host -> host on the current device: upload of the file's own samples, kernel, download. */
+WH_API int wh_resample_host( const void* src, int format, int channels, int channel, int inRate, int64_t nFrames, float* dst, int64_t dstStride, int64_t nOut );
+/* The same for `count` results of ONE upload (a file's mono mix and its two stereo channels): result i is channel channelList[ i ] (-1 = the mean) written to
+ * dsts[ i ][ n * dstStrides[ i ] ]; the destinations may interleave in one buffer. */
+WH_API int wh_resample_host_multi( const void* src, int format, int channels, const int32_t* channelList, int count, int inRate, int64_t nFrames, float* const* dsts,
+	const int64_t* dstStrides, int64_t nOut );
+/* the table the kernel reads: L, M, half, K and the [L][K] taps (tapsHost may be NULL to query sizes; cap = floats it holds). Host only. */
+WH_API int wh_resample_taps( int inRate, int32_t* L, int32_t* M, int32_t* half, int32_t* K, float* tapsHost, int64_t cap );
+
 /* Encoder. Replaces WhisperContext::encode (WhisperContext.cpp:310-399) == whisper_encode (whisper.cpp:1084-1496).
  * melDev: FP32 device, `batch` spectrograms each [n_mel][melLen] (melStride floats apart); for each the window
  * [melOffset, melOffset + 2*n_audio_ctx) is taken and zero-padded (MelInputTensor.cpp:8-63).  Fills the
@@ -374,7 +403,7 @@ WH_API int wh_debug_read( wh_context* c, const char* what, int layer, int rows, 
  * afterwards (and their captured graphs) use the new setting. */
 WH_API int wh_debug_set_tuning( uint32_t mask );
 /* Integer knobs beyond the 32 switches (whisper_amd/csrc/kernels.h struct Options: "dec_tile", "dec_depth", "dec_wide_rows", "dec_deep_rows", "vocab_decrows",
- * "enc_chunk", "self_fuse_max_rows", "self_nq", "self_wave_min_rows", "enc_exp", "exact_enc_layers", "exact_alt_order", "gemm_mf16", "dec_lds", "dec_lds_ks", "dec_split", "cross_mfma", "vocab_lds", "beam_regs", "reorder_group", "gemm_big_min_rows"); also settable as WH_OPT_<NAME> in the environment at load.
+ * "enc_chunk", "self_fuse_max_rows", "self_nq", "self_wave_min_rows", "enc_exp", "exact_enc_layers", "exact_alt_order", "gemm_mf16", "dec_lds", "dec_lds_ks", "dec_split", "cross_mfma", "vocab_lds", "beam_regs", "reorder_group", "gemm_big_min_rows", "resample_lds_phases"); also settable as WH_OPT_<NAME> in the environment at load.
  * Unknown names and values outside [-1, 2^24]: WH_E_INVALIDARG (the environment form: ignored with a line on stderr). The options are process-global and read without
  * synchronisation by every launch: set them BEFORE contexts are created, never while another thread runs one. */
 WH_API int wh_debug_set_option( const char* name, int value );

@@ -73,6 +73,8 @@ def lib():
         L.whisperc_language_code.argtypes = [C.c_int32, C.c_char_p]
         L.whisperc_tr_language.argtypes = [vp, C.c_char_p, C.POINTER(C.c_float)]
         L.whisperc_debug_context_flags.argtypes = [vp, C.c_uint32, C.c_int32]
+        L.whisperc_resample.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64)]
+        L.whisperc_load_audio.argtypes = [C.c_char_p, C.c_int32, vp, C.c_int64, C.POINTER(C.c_int64)]
         _lib = L
     return _lib
 
@@ -113,6 +115,44 @@ def _check(hr: int, what: str) -> int:
     if hr < 0:
         raise WhisperError(hr, what)
     return hr
+
+
+PCM_U8, PCM_S16, PCM_S24, PCM_S32, PCM_F32 = range(5)          # wh_pcm_format
+_PCM_FORMATS = {"uint8": PCM_U8, "int16": PCM_S16, "int32": PCM_S32, "float32": PCM_F32}
+SAMPLE_RATE = 16000
+
+
+def resample(pcm: np.ndarray, rate: int, channel: int = -1) -> np.ndarray:
+    """PCM at `rate` Hz -> mono float32 at 16 kHz, on the GPU (wh_resample_host: Kaiser-windowed sinc, FP64 sums). pcm: uint8 / int16 / int32 / float32,
+    shape [n] or [n, C] with up to 8 channels; channel -1 = the mean of the channels, else that channel. rate 16000 converts and downmixes only."""
+    pcm = np.ascontiguousarray(pcm)
+    if pcm.dtype.name not in _PCM_FORMATS or pcm.ndim not in (1, 2):
+        raise ValueError("resample: uint8, int16, int32 or float32 of shape [n] or [n, channels], not %s %s" % (pcm.dtype, pcm.shape))
+    n, channels = pcm.shape[0], (pcm.shape[1] if pcm.ndim == 2 else 1)
+    fmt = _PCM_FORMATS[pcm.dtype.name]
+    n_out = C.c_int64()
+    _check(lib().whisperc_resample(pcm.ctypes.data_as(C.c_void_p), fmt, channels, channel, rate, n, None, 0, C.byref(n_out)), "resample")
+    out = np.empty(n_out.value, np.float32)
+    _check(lib().whisperc_resample(pcm.ctypes.data_as(C.c_void_p), fmt, channels, channel, rate, n, out.ctypes.data_as(C.c_void_p), out.size, C.byref(n_out)), "resample")
+    return out
+
+
+def load_audio(path: str, stereo: bool = False) -> np.ndarray:
+    """iMediaFoundation::loadAudioFile: a WAV file of any rate, bit depth and channel count as 16 kHz float32 -- mono [n], or with stereo=True the first two
+    channels [n, 2] (a mono file twice)."""
+    n = C.c_int64()
+    _check(lib().whisperc_load_audio(path.encode(), int(stereo), None, 0, C.byref(n)), "loadAudioFile")
+    out = np.empty((n.value, 2) if stereo else (n.value,), np.float32)
+    _check(lib().whisperc_load_audio(path.encode(), int(stereo), out.ctypes.data_as(C.c_void_p), out.size, C.byref(n)), "loadAudioFile")
+    return out
+
+
+def _at_16k(pcm: np.ndarray, sample_rate: int) -> np.ndarray:
+    """What the run entry points take: mono float32 at 16 kHz; another sample_rate is resampled on the GPU first."""
+    pcm = np.asarray(pcm)
+    if sample_rate == SAMPLE_RATE or pcm.dtype.name not in _PCM_FORMATS:
+        pcm = np.ascontiguousarray(pcm, np.float32)       # float64 and the like: cast as the 16 kHz path always did
+    return pcm if sample_rate == SAMPLE_RATE else resample(pcm, sample_rate)
 
 
 class Model:
@@ -178,11 +218,11 @@ class Context:
 
     def run_full(self, pcm: np.ndarray, language: str = "en", flags: int = 0, max_tokens: int = 0,
                  prompt: Optional[Sequence[int]] = None, n_max_text_ctx: int = -1, max_len: int = 0, thold_pt: float = 0.01,
-                 thold_ptsum: float = 0.01, beam_width: int = 0, audio_ctx: int = 0, offset_ms: int = 0, duration_ms: int = 0) -> int:
-        """runFull on mono float32 16 kHz PCM. Returns the HRESULT (0 = S_OK, 1 = S_FALSE: less than 1 s of audio). language "auto" (or ""): detected
+                 thold_ptsum: float = 0.01, beam_width: int = 0, audio_ctx: int = 0, offset_ms: int = 0, duration_ms: int = 0, sample_rate: int = 16000) -> int:
+        """runFull on mono float32 16 kHz PCM (another sample_rate: PCM of any dtype resample() takes, resampled on the GPU first). Returns the HRESULT (0 = S_OK, 1 = S_FALSE: less than 1 s of audio). language "auto" (or ""): detected
         on the window at frame 0, whatever the run's offset (detected_language tells which).
         With TOKEN_TIMESTAMPS in flags the tokens of results() carry t0 / t1 / vlen and max_len > 0 wraps the segments."""
-        pcm = np.ascontiguousarray(pcm, np.float32)
+        pcm = _at_16k(pcm, sample_rate)
         pt = np.ascontiguousarray(prompt if prompt is not None else [], np.int32)
         if offset_ms or duration_ms:            # sFullParams::offset_ms / duration_ms: the range that is transcribed
             return _check(lib().whisperc_run_full_range(self.h, pcm.ctypes.data_as(C.c_void_p), len(pcm), language.encode(), flags, max_tokens,
@@ -201,10 +241,10 @@ class Context:
                                               pt.ctypes.data_as(C.c_void_p) if len(pt) else None, len(pt), n_max_text_ctx), "runFull")
 
     def run_streamed(self, pcm: np.ndarray, language: str = "en", flags: int = 0, max_tokens: int = 0,
-                     prompt: Optional[Sequence[int]] = None, n_max_text_ctx: int = -1):
-        """iMediaFoundation::loadAudioFileData (the PCM wrapped as a float32 WAV image) + iContext::runStreamed.
-        Returns (HRESULT, [progress values the sink received])."""
-        wav = wav_bytes(pcm)
+                     prompt: Optional[Sequence[int]] = None, n_max_text_ctx: int = -1, sample_rate: int = 16000):
+        """iMediaFoundation::loadAudioFileData (the PCM wrapped as a float32 WAV image at sample_rate, which the loader resamples when it is not 16000) +
+        iContext::runStreamed. Returns (HRESULT, [progress values the sink received])."""
+        wav = wav_bytes(pcm, sample_rate)
         pt = np.ascontiguousarray(prompt if prompt is not None else [], np.int32)
         prog = (C.c_double * 4096)()
         n = C.c_int()
@@ -213,10 +253,11 @@ class Context:
                                                 prog, 4096, C.byref(n)), "runStreamed")
         return hr, list(prog[:min(n.value, 4096)])
 
-    def detect_language(self, pcm: np.ndarray, offset_ms: int = 0):
+    def detect_language(self, pcm: np.ndarray, offset_ms: int = 0, sample_rate: int = 16000):
         """whisper_lang_auto_detect on the 30 s window at offset_ms of mono float32 16 kHz PCM: (code, {code: p}). The p are the reference's
-        lang_probs: a SECOND softmax over the language tokens' probabilities, so a clear winner reads ~0.02, not ~0.9; their order is what counts."""
-        pcm = np.ascontiguousarray(pcm, np.float32)
+        lang_probs: a SECOND softmax over the language tokens' probabilities, so a clear winner reads ~0.02, not ~0.9; their order is what counts.
+        Another sample_rate is resampled on the GPU first."""
+        pcm = _at_16k(pcm, sample_rate)
         probs = np.zeros(N_LANGUAGES, np.float32)
         lang = C.c_int32(-1)
         _check(lib().whisperc_detect_language(self.h, pcm.ctypes.data_as(C.c_void_p), len(pcm), offset_ms, probs.ctypes.data_as(C.c_void_p), len(probs),
@@ -299,14 +340,20 @@ class BatchRunner:
             pass
 
     def run(self, streams, language: str = "en", flags: int = 0, max_tokens: int = 0, prompt: Optional[Sequence[int]] = None,
-            n_max_text_ctx: int = -1, want_results: bool = True):
-        """streams: list of float32 PCM arrays, or of (pcm, first_sample, count_samples) -- pieces of a recording share the array.
+            n_max_text_ctx: int = -1, want_results: bool = True, sample_rate: int = 16000):
+        """streams: list of float32 PCM arrays (at 16 kHz; another sample_rate: every array is resampled on the GPU first, first_sample / count_samples then count
+        16 kHz samples), or of (pcm, first_sample, count_samples) -- pieces of a recording share the array.
         Returns (HRESULT, [segments per stream or None], [per-stream HRESULT]). language "auto": every stream is detected on ITS OWN first window
         and transcribed in its own language; self.languages then holds (code, p) per stream (None where nothing was detected)."""
         n = len(streams)
         keep, ptrs, lens, first, cnt = [], (C.c_void_p * n)(), (C.c_uint32 * n)(), (C.c_int64 * n)(), (C.c_int64 * n)()
+        resampled = {}              # id of a caller's array -> its 16 kHz version: the pieces of one recording keep sharing one buffer
         for i, s in enumerate(streams):
             pcm, f, c = (s, 0, 0) if not isinstance(s, tuple) else s
+            if sample_rate != SAMPLE_RATE:
+                if id(pcm) not in resampled:
+                    resampled[id(pcm)] = resample(pcm, sample_rate)
+                pcm = resampled[id(pcm)]
             assert pcm.dtype == np.float32 and pcm.flags["C_CONTIGUOUS"]
             keep.append(pcm)
             ptrs[i], lens[i], first[i], cnt[i] = pcm.ctypes.data, len(pcm), f, c

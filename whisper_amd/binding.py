@@ -50,6 +50,7 @@ EXPORTS = [
     "wh_op_mul_mat", "wh_op_mul_mat_gelu", "wh_op_layer_norm", "wh_op_flash_attention", "wh_op_soft_max", "wh_op_decoder_attention", "wh_op_decoder_cross_attention",
     "wh_op_vocab_soft_max", "wh_op_sample_best", "wh_op_beam_candidates", "wh_op_reorder_self_cache",
     "wh_lang_detect", "wh_model_lang_count", "wh_op_lang_probs",
+    "wh_resample_out_len", "wh_resample", "wh_resample_host", "wh_resample_host_multi", "wh_resample_taps",
 ]
 
 
@@ -166,6 +167,11 @@ def lib():
         L.wh_lang_detect.argtypes = [vp, i32, vp, vp]
         L.wh_model_lang_count.argtypes = [vp]
         L.wh_op_lang_probs.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
+        L.wh_resample_out_len.argtypes = [i32, i64, C.POINTER(i64)]
+        L.wh_resample.argtypes = [vp, vp, i32, i32, i32, i32, i64, vp, i64, i64]
+        L.wh_resample_host.argtypes = [vp, i32, i32, i32, i32, i64, vp, i64, i64]
+        L.wh_resample_host_multi.argtypes = [vp, i32, i32, vp, i32, i32, i64, vp, vp, i64]
+        L.wh_resample_taps.argtypes = [i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, i64]
         _lib = L
     return _lib
 
@@ -181,7 +187,7 @@ def set_option(name: str, value: int):
 
 
 # the defaults of csrc/kernels.h struct Options (what a test restores an option to)
-OPTION_DEFAULTS = {"dec_tile": 0, "dec_depth": 0, "dec_wide_rows": 1, "dec_deep_rows": 0, "vocab_decrows": 0, "enc_chunk": 128, "self_fuse_max_rows": 32, "self_nq": 0, "self_wave_min_rows": 32, "enc_exp": 5, "exact_enc_layers": -1, "exact_alt_order": 0, "gemm_mf16": 1, "dec_lds": 1, "dec_lds_ks": 2, "dec_split": 1, "cross_mfma": 1, "vocab_lds": 1, "beam_regs": 1, "reorder_group": 1, "gemm_big_min_rows": 8192}
+OPTION_DEFAULTS = {"dec_tile": 0, "dec_depth": 0, "dec_wide_rows": 1, "dec_deep_rows": 0, "vocab_decrows": 0, "enc_chunk": 128, "self_fuse_max_rows": 32, "self_nq": 0, "self_wave_min_rows": 32, "enc_exp": 5, "exact_enc_layers": -1, "exact_alt_order": 0, "gemm_mf16": 1, "dec_lds": 1, "dec_lds_ks": 2, "dec_split": 1, "cross_mfma": 1, "vocab_lds": 1, "beam_regs": 1, "reorder_group": 1, "gemm_big_min_rows": 8192, "resample_lds_phases": 853}
 
 
 def get_option(name: str) -> int:

@@ -23,7 +23,9 @@ CLI_BIN = os.path.join(LIB_DIR, "whisper-main")
 
 # the runtime behind the C ABI, one unit per responsibility; runtime.h holds what they share (host code: the kernel units do not include it)
 RUNTIME_SOURCES = ["options.hip", "model.hip", "comm.hip", "context.hip", "encode.hip", "exact_graphs.hip", "decode.hip", "beam.hip", "ops_debug.hip"]
-HIP_SOURCES = ["gemm.hip", "decode1.hip", "attn_enc.hip", "attn_dec.hip", "elementwise.hip", "mel.hip", "exact.hip"] + RUNTIME_SOURCES
+# resample.hip keeps its kernels next to the entry points that own its tap tables: a kernel unit that does include runtime.h
+HIP_SOURCES = ["gemm.hip", "decode1.hip", "attn_enc.hip", "attn_dec.hip", "elementwise.hip", "mel.hip", "exact.hip", "resample.hip"] + RUNTIME_SOURCES
+RUNTIME_H_USERS = RUNTIME_SOURCES + ["resample.hip"]
 # exact.hip restates the reference CPU path's summation order: a fused multiply-add only where the source says fma()
 EXTRA_FLAGS = {"exact.hip": ["-ffp-contract=off"]}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -56,7 +58,7 @@ def build_hip(force: bool = False) -> str:
     for s in HIP_SOURCES:
         src = os.path.join(CSRC, s)
         obj = os.path.join(obj_dir, s.replace(".hip", ".o"))
-        deps = [src] + headers + ([os.path.join(CSRC, "runtime.h")] if s in RUNTIME_SOURCES else [])
+        deps = [src] + headers + ([os.path.join(CSRC, "runtime.h")] if s in RUNTIME_H_USERS else [])
         if force or _newer(obj, deps):
             # WH_PROBES=1: the tile-shape experiments and ablation instances of tools/*probe* (not in the shipped objects)
             probes = ["-DWH_PROBES"] if os.environ.get("WH_PROBES", "") not in ("", "0") else []

@@ -90,6 +90,8 @@ namespace wh
 									 // 8 windows = 12000 rows: beam5 1341 -> 1370 audio-s/s with 8192, the same ids)
 		int gemmMf16 = 1;			 // "gemm_mf16": 1 = gemmTiled8's K loop on v_mfma_f32_16x16x32_f16 (same bits as the 32x32x16 form, +9 % on the class in the model:
 									 // profiles/r06_evidence/gemm_vendor_gap.txt); 0 = v_mfma_f32_32x32x16_f16 (rounds 3-5)
+		int resampleLdsPhases = 853; // "resample_lds_phases": resampleKernel stages the taps of all L phases in LDS (K in chunks) up to this many phases and reads them from global memory
+									 // beyond; 0 = always from global memory (the same sums in the same order either way). 853 = the most phases of which 9 taps each fit the 30 KiB
 		int selfWaveMinRows = 32;	 // "self_wave_min_rows": single-token causal self-attention as its own launch: a wave per (sequence, head) beyond this many sequences
 	};
 	extern Options g_opt;
@@ -423,4 +425,8 @@ namespace wh
 		long long nLen, int nMel, float* maxScratch, hipStream_t stream );	 // 1 = shape not covered (loop over launchMel)
 	int launchMelWindow( const float* pcm, long long nSamples, const float* filters, const double* dftTable, float* mel, long long nLen,
 		long long nValidFrames, int nMel, int reusePreviousMax, float* maxScratch, hipStream_t stream );
+	// resample.hip: nFrames interleaved frames of `channels` samples (wh_pcm_format) at inRate -> nOut mono floats at 16 kHz, dst[ n * dstStride ]; channel -1 = the
+	// mean of the channels. 16 kHz in: conversion and downmix only. The arguments are the caller's to check (wh_resample); the rate's tap table is built on first use.
+	int launchResample( hipStream_t stream, const void* src, int format, int channels, int channel, int inRate, long long nFrames, float* dst,
+		long long dstStride, long long nOut );
 }

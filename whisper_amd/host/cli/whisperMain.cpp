@@ -1,6 +1,6 @@
 // Command-line transcription tool over the iModel / iContext API of libWhisper.so: the Linux counterpart of the
 // reference's Examples/main (main.cpp:174-330, params.cpp:24-56) with the same options, console output, exit codes and
-// .txt / .srt / .vtt writers. Audio comes from the WAV stand-in for Media Foundation (16 kHz PCM16 / float32).
+// .txt / .srt / .vtt writers. Audio comes from the WAV stand-in for Media Foundation (plain PCM of any rate).
 //
 //   whisper-main -m ggml-medium.bin -f clip.wav -osrt
 //

@@ -10,6 +10,7 @@
 #include "hostLoop.h"
 #include "languageDetect.h"
 #include "results.h"
+#include "wavFormat.h"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -897,7 +898,7 @@ namespace Whisper
 			HRESULT clone( iModel** rdi ) override { return createModelImpl( model, rdi ); }
 		};
 
-		// ---- iMediaFoundation stand-in: WAV (PCM16 / float32, 16 kHz) ------------------------------------------------
+		// ---- iMediaFoundation stand-in: WAV (plain PCM of any rate, wavFormat.h) ---------------------------------------
 		class WavLoader : public ComObject<iMediaFoundation>
 		{
 		public:
@@ -908,55 +909,48 @@ namespace Whisper
 			HRESULT openCaptureDevice( LPCTSTR, const sCaptureParams&, iAudioCapture** ) override { return E_NOTIMPL; }
 		};
 
-		// RIFF/WAVE, 16 kHz, mono or stereo, PCM16 or float32 -> mono (and interleaved stereo when asked for)
+		// RIFF/WAVE (wavFormat.h: PCM of 8 .. 32 bits or float32, 1 .. 8 channels, 1000 .. 384000 Hz) -> 16 kHz mono (and interleaved stereo when asked for: the
+		// first two channels, a mono file twice). The mean of the channels is their FP32 sum in channel order times 1.0f / C. A 16 kHz file is converted here;
+		// any other rate goes to the GPU in the file's own format (wh_resample_host on the calling thread's current device: conversion, downmix and the filter).
 		static HRESULT decodeWav( const char* bytes, size_t size, const std::string& what, bool wantStereo, std::vector<float>& mono, std::vector<float>& st )
 		{
-			if( size < 44 || memcmp( bytes, "RIFF", 4 ) || memcmp( bytes + 8, "WAVE", 4 ) )
+			wav::Info info;
+			std::string error;
+			if( !wav::parse( bytes, size, info, error ) )
 			{
-				logError( "'%s' is not a RIFF/WAVE file (only WAV is supported on this platform)", what.c_str() );
+				logError( "'%s': %s", what.c_str(), error.c_str() );
 				return E_INVALIDARG;
 			}
-			uint16_t fmt = 0, channels = 0, bits = 0;
-			uint32_t rate = 0;
-			const char* pcm = nullptr;
-			size_t pcmBytes = 0;
-			for( size_t o = 12; o + 8 <= size; )
-			{
-				uint32_t len;
-				memcpy( &len, bytes + o + 4, 4 );
-				const char* body = bytes + o + 8;
-				if( !memcmp( bytes + o, "fmt ", 4 ) && len >= 16 )
-				{
-					memcpy( &fmt, body, 2 ); memcpy( &channels, body + 2, 2 ); memcpy( &rate, body + 4, 4 ); memcpy( &bits, body + 14, 2 );
-				}
-				else if( !memcmp( bytes + o, "data", 4 ) )
-				{
-					pcm = body;
-					pcmBytes = std::min( (size_t)len, size - ( o + 8 ) );
-				}
-				o += 8 + (size_t)len + ( len & 1 );
-			}
-			const bool isFloat = fmt == 3 && bits == 32, isPcm16 = fmt == 1 && bits == 16;
-			if( !pcm || !( isFloat || isPcm16 ) || channels < 1 || channels > 2 || rate != 16000 )
-			{
-				logError( "'%s': need 16 kHz mono/stereo PCM16 or float32 WAV (got format %u, %u bit, %u ch, %u Hz)", what.c_str(), fmt, bits, channels, rate );
-				return E_INVALIDARG;
-			}
-			const size_t frames = pcmBytes / ( ( bits / 8 ) * channels );
-			mono.resize( frames );
+			const uint8_t* const pcm = (const uint8_t*)bytes + info.firstByte;
+			const int channels = info.channels, right = channels >= 2 ? 1 : 0;
 			st.clear();
-			if( wantStereo ) st.resize( frames * 2 );
-			auto sample = [ & ]( size_t i ) -> float
+			if( info.rate == 16000 )
 			{
-				if( isFloat ) { float v; memcpy( &v, pcm + i * 4, 4 ); return v; }
-				int16_t v; memcpy( &v, pcm + i * 2, 2 ); return (float)v / 32768.0f;
-			};
-			for( size_t i = 0; i < frames; i++ )
-			{
-				const float l = sample( i * channels ), r = channels == 2 ? sample( i * 2 + 1 ) : l;
-				mono[ i ] = channels == 2 ? 0.5f * ( l + r ) : l;
-				if( wantStereo ) { st[ 2 * i ] = l; st[ 2 * i + 1 ] = r; }
+				const size_t frames = info.frames, step = (size_t)wav::bytesPerSample( info.format );
+				mono.resize( frames );
+				if( wantStereo ) st.resize( frames * 2 );
+				const float inv = 1.0f / (float)channels;
+				for( size_t i = 0; i < frames; i++ )
+				{
+					const uint8_t* const f = pcm + i * channels * step;
+					const float l = wav::sample( f, info.format );
+					float sum = l;
+					for( int c = 1; c < channels; c++ ) sum += wav::sample( f + c * step, info.format );
+					mono[ i ] = channels == 1 ? l : sum * inv;
+					if( wantStereo ) { st[ 2 * i ] = l; st[ 2 * i + 1 ] = wav::sample( f + right * step, info.format ); }
+				}
+				return S_OK;
 			}
+			int64_t nOut = 0;
+			if( 0 != wh_resample_out_len( info.rate, (int64_t)info.frames, &nOut ) ) return E_INVALIDARG;
+			mono.resize( (size_t)nOut );
+			if( wantStereo ) st.resize( (size_t)nOut * 2 );
+			if( nOut == 0 ) return S_OK;
+			// one upload: the mono mix and, when asked for, the two stereo channels interleaved
+			const int32_t list[ 3 ] = { -1, 0, right };
+			float* const dsts[ 3 ] = { mono.data(), st.data(), st.data() + 1 };
+			const int64_t strides[ 3 ] = { 1, 2, 2 };
+			CHECK_WH( wh_resample_host_multi( pcm, info.format, channels, list, wantStereo ? 3 : 1, info.rate, (int64_t)info.frames, dsts, strides, nOut ) );
 			return S_OK;
 		}
 		static HRESULT readWavFile( LPCTSTR path, bool stereo, std::vector<float>& mono, std::vector<float>& st )
@@ -1285,6 +1279,47 @@ WHISPER_EXPORT int32_t whisperc_run_streamed( void* ctx, const void* wavBytes, u
 	reader->Release();
 	if( progressCount ) *progressCount = sink.n;
 	return hr;
+}
+// wh_resample_host behind an HRESULT: *nOut = the 16 kHz samples the input gives; dst == NULL only counts, cap < *nOut is E_INVALIDARG
+WHISPER_EXPORT int32_t whisperc_resample( const void* src, int32_t format, int32_t channels, int32_t channel, int32_t rate, int64_t nFrames, float* dst, int64_t cap,
+	int64_t* nOut )
+{
+	if( !nOut || ( !src && nFrames > 0 ) ) return E_POINTER;
+	if( format < 0 || format > 4 || channels < 1 || channels > 8 || channel < -1 || channel >= channels ) return E_INVALIDARG;
+	if( 0 != wh_resample_out_len( rate, nFrames, nOut ) ) return E_INVALIDARG;
+	if( !dst ) return S_OK;
+	if( cap < *nOut ) return E_INVALIDARG;
+	CHECK_WH( wh_resample_host( src, format, channels, channel, rate, nFrames, dst, 1, *nOut ) );
+	return S_OK;
+}
+// iMediaFoundation::loadAudioFile + iAudioBuffer::getPcmMono / getPcmStereo: *nFrames = the 16 kHz frames of the file; dst == NULL reads the file and parses its
+// chunks (the `data` chunk's clipped length needs the file's size) but converts nothing
+WHISPER_EXPORT int32_t whisperc_load_audio( const char* pathUtf8, int32_t stereo, float* dst, int64_t cap, int64_t* nFrames )
+{
+	if( !pathUtf8 || !nFrames ) return E_POINTER;
+	if( !dst )
+	{
+		std::ifstream f( pathUtf8, std::ios::binary );
+		if( !f ) { logError( "failed to open audio file '%s'", pathUtf8 ); return (HRESULT)0x80070002; }
+		std::vector<char> data( ( std::istreambuf_iterator<char>( f ) ), std::istreambuf_iterator<char>() );
+		wav::Info info;
+		std::string error;
+		if( !wav::parse( data.data(), data.size(), info, error ) ) { logError( "'%s': %s", pathUtf8, error.c_str() ); return E_INVALIDARG; }
+		return 0 == wh_resample_out_len( info.rate, (int64_t)info.frames, nFrames ) ? S_OK : E_INVALIDARG;
+	}
+	iMediaFoundation* mf = nullptr;
+	CHECK( initMediaFoundation( &mf ) );
+	iAudioBuffer* buf = nullptr;
+	const HRESULT hr = mf->loadAudioFile( pathUtf8, stereo != 0, &buf );
+	mf->Release();
+	if( FAILED( hr ) ) return hr;
+	const int64_t n = buf->countSamples(), floats = stereo ? 2 * n : n;
+	*nFrames = n;
+	HRESULT res = S_OK;
+	if( cap < floats ) res = E_INVALIDARG;
+	else if( n > 0 ) memcpy( dst, stereo ? buf->getPcmStereo() : buf->getPcmMono(), (size_t)floats * sizeof( float ) );
+	buf->Release();
+	return res;
 }
 // iContext::fullDefaultParams( BeamSearch ) + beam_search.beam_width = beamWidth (1 .. 8), then iContext::runFull
 WHISPER_EXPORT int32_t whisperc_run_full_beam( void* ctx, const float* pcm, uint32_t nSamples, const char* language, uint32_t flags, int maxTokens,
