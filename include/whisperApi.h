@@ -31,6 +31,7 @@ typedef int32_t HRESULT;
 #define E_OUTOFMEMORY ( (HRESULT)0x8007000E )
 #define E_INVALIDARG ( (HRESULT)0x80070057 )
 #define E_BOUNDS ( (HRESULT)0x8000000B )
+#define OLE_E_BLANK ( (HRESULT)0x80040007 )	   // iContext::detectSpeaker outside a run
 #define SUCCEEDED( hr ) ( ( (HRESULT)( hr ) ) >= 0 )
 #define FAILED( hr ) ( ( (HRESULT)( hr ) ) < 0 )
 #endif

@@ -46,7 +46,7 @@ int32_t whisperc_run_streamed( void* ctx, const void* wavBytes, uint64_t wavSize
  * *nOut = ceil( nFrames * 16000 / rate ); dst == NULL only counts, cap (floats of dst) < *nOut is E_INVALIDARG. rate 16000 converts without filtering. */
 int32_t whisperc_resample( const void* src, int32_t format, int32_t channels, int32_t channel, int32_t rate, int64_t nFrames, float* dst, int64_t cap,
 	int64_t* nOut );
-/* iMediaFoundation::loadAudioFile + iAudioBuffer::getPcmMono (stereo != 0: getPcmStereo, interleaved, 2 floats per frame): the WAV file as 16 kHz floats.
+/* iMediaFoundation::loadAudioFile + iAudioBuffer::getPcmMono (stereo != 0: getPcmStereo, interleaved, 2 floats per frame; a mono file, whose buffer has no stereo data, twice): the WAV file as 16 kHz floats.
  * *nFrames = its 16 kHz frames; dst == NULL reads the file and parses its chunks, converts nothing and returns the count (so a
  * caller that asks for the count first reads the file twice); cap counts floats. */
 int32_t whisperc_load_audio( const char* pathUtf8, int32_t stereo, float* dst, int64_t cap, int64_t* nFrames );
@@ -69,6 +69,26 @@ int32_t whisperc_batch_create( void* model, uint32_t maxSlots, uint32_t groups, 
 int32_t whisperc_batch_run( void* runner, uint32_t count, const float* const* pcm, const uint32_t* nSamples, const int64_t* firstSample,
 	const int64_t* countSamples, const char* language, uint32_t flags, int maxTokens, const int32_t* promptTokens, int nPrompt, int nMaxTextCtx,
 	void** resultsOut, int32_t* perStream );
+/* Stereo diarization (iContext::detectSpeaker; the reference's rule, Whisper/Whisper/ContextImpl.diarize.cpp: the sum of |sample| per channel over the
+ * segment, left if L > 1.1 R, right if R > 1.1 L, else unsure). `stereo` = nSamples interleaved frames (2 floats each, 16 kHz) of the recording whose mono
+ * mix is `pcm`, what iAudioBuffer::getPcmStereo returns; NULL = no stereo data.
+ * whisperc_run_full_stereo: whisperc_run_full_range over such a buffer.  whisperc_run_streamed_stereo: iContext::runStreamed over a reader of such PCM
+ *   (progress as in whisperc_run_streamed).  whisperc_batch_run_stereo: whisperc_batch_run with stereo[i] beside pcm[i] (entries and the array may be NULL).
+ * whisperc_detect_speaker: iContext::detectSpeaker( { t0, t1 } in 100 ns ticks ) -> *channel = eSpeakerChannel (0 unsure, 1 left, 2 right, 0xFF no stereo
+ *   data). Like the reference's it answers only from the callbacks of a run; anywhere else OLE_E_BLANK (0x80040007).
+ * whisperc_result_speakers / whisperc_tr_speakers: for callers without callbacks -- of a context's results / of a result object (a batch runner's
+ *   per-stream result), one eSpeakerChannel byte per segment: what detectSpeaker answered for the segment's times when the segment was appended;
+ *   0xFF = the run's audio had no stereo data. *count = the segments; out may be NULL (count only), cap < *count is E_INVALIDARG. */
+int32_t whisperc_run_full_stereo( void* ctx, const float* pcm, const float* stereo, uint32_t nSamples, const char* language, uint32_t flags, int maxTokens,
+	const int32_t* promptTokens, int nPrompt, int nMaxTextCtx, int offsetMs, int durationMs );
+int32_t whisperc_run_streamed_stereo( void* ctx, const float* pcm, const float* stereo, uint32_t nSamples, const char* language, uint32_t flags, int maxTokens,
+	const int32_t* promptTokens, int nPrompt, int nMaxTextCtx, double* progressOut, int progressCap, int* progressCount );
+int32_t whisperc_batch_run_stereo( void* runner, uint32_t count, const float* const* pcm, const float* const* stereo, const uint32_t* nSamples,
+	const int64_t* firstSample, const int64_t* countSamples, const char* language, uint32_t flags, int maxTokens, const int32_t* promptTokens, int nPrompt,
+	int nMaxTextCtx, void** resultsOut, int32_t* perStream );
+int32_t whisperc_detect_speaker( void* ctx, uint64_t t0, uint64_t t1, uint8_t* channel );
+int32_t whisperc_result_speakers( void* ctx, uint8_t* out, uint32_t cap, uint32_t* count );
+int32_t whisperc_tr_speakers( void* result, uint8_t* out, uint32_t cap, uint32_t* count );
 /* iTranscribeResult::getSize / getSegments / getTokens on a result object itself (times in 100 ns ticks) */
 int32_t whisperc_tr_counts( void* result, uint32_t* segments, uint32_t* tokens );
 int32_t whisperc_tr_segment( void* result, uint32_t index, uint64_t* t0, uint64_t* t1, uint32_t* firstToken, uint32_t* countTokens, char* text, uint32_t textCap );

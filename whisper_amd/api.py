@@ -75,6 +75,13 @@ def lib():
         L.whisperc_debug_context_flags.argtypes = [vp, C.c_uint32, C.c_int32]
         L.whisperc_resample.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64)]
         L.whisperc_load_audio.argtypes = [C.c_char_p, C.c_int32, vp, C.c_int64, C.POINTER(C.c_int64)]
+        L.whisperc_run_full_stereo.argtypes = [vp, vp, vp, C.c_uint32, C.c_char_p, C.c_uint32, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.whisperc_run_streamed_stereo.argtypes = [vp, vp, vp, C.c_uint32, C.c_char_p, C.c_uint32, C.c_int, vp, C.c_int, C.c_int,
+                                                   C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_int)]
+        L.whisperc_batch_run_stereo.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, C.c_char_p, C.c_uint32, C.c_int, vp, C.c_int, C.c_int, vp, vp]
+        L.whisperc_detect_speaker.argtypes = [vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint8)]
+        L.whisperc_result_speakers.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.whisperc_tr_speakers.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
         _lib = L
     return _lib
 
@@ -139,12 +146,42 @@ def resample(pcm: np.ndarray, rate: int, channel: int = -1) -> np.ndarray:
 
 def load_audio(path: str, stereo: bool = False) -> np.ndarray:
     """iMediaFoundation::loadAudioFile: a WAV file of any rate, bit depth and channel count as 16 kHz float32 -- mono [n], or with stereo=True the first two
-    channels [n, 2] (a mono file twice)."""
+    channels [n, 2] (a mono file twice -- the iAudioBuffer of a mono file has no stereo data; this function copies its one channel)."""
     n = C.c_int64()
     _check(lib().whisperc_load_audio(path.encode(), int(stereo), None, 0, C.byref(n)), "loadAudioFile")
     out = np.empty((n.value, 2) if stereo else (n.value,), np.float32)
     _check(lib().whisperc_load_audio(path.encode(), int(stereo), out.ctypes.data_as(C.c_void_p), out.size, C.byref(n)), "loadAudioFile")
     return out
+
+
+# eSpeakerChannel (iContext::detectSpeaker, Context.speakers): which channel of a stereo recording is louder during a segment
+SPEAKER_UNSURE, SPEAKER_LEFT, SPEAKER_RIGHT, NO_STEREO_DATA = 0, 1, 2, 0xFF
+
+
+def _stereo_at_16k(stereo, sample_rate: int, n_mono: int) -> np.ndarray:
+    """The stereo PCM beside a run's mono PCM: [n, 2] float32 at 16 kHz; at another sample_rate each channel is resampled on the GPU like the mono.
+    n must be the mono's length after resampling: the two are one recording."""
+    stereo = np.asarray(stereo)
+    if stereo.ndim != 2 or stereo.shape[1] != 2:
+        raise ValueError("stereo: an array of shape [n, 2], not %s" % (stereo.shape,))
+    if sample_rate == SAMPLE_RATE:
+        stereo = np.ascontiguousarray(stereo, np.float32)
+    else:
+        if stereo.dtype.name not in _PCM_FORMATS:
+            stereo = stereo.astype(np.float32)
+        stereo = np.ascontiguousarray(np.stack([resample(stereo, sample_rate, channel=c) for c in range(2)], 1))
+    if stereo.shape[0] != n_mono:
+        raise ValueError("stereo: %d frames beside %d mono samples at 16 kHz" % (stereo.shape[0], n_mono))
+    return stereo
+
+
+def _speakers_of(call, h) -> List[int]:
+    n = C.c_uint32()
+    _check(call(h, None, 0, C.byref(n)), "speakers")
+    out = np.zeros(n.value, np.uint8)
+    if n.value:
+        _check(call(h, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)), "speakers")
+    return [int(x) for x in out]
 
 
 def _at_16k(pcm: np.ndarray, sample_rate: int) -> np.ndarray:
@@ -218,12 +255,22 @@ class Context:
 
     def run_full(self, pcm: np.ndarray, language: str = "en", flags: int = 0, max_tokens: int = 0,
                  prompt: Optional[Sequence[int]] = None, n_max_text_ctx: int = -1, max_len: int = 0, thold_pt: float = 0.01,
-                 thold_ptsum: float = 0.01, beam_width: int = 0, audio_ctx: int = 0, offset_ms: int = 0, duration_ms: int = 0, sample_rate: int = 16000) -> int:
+                 thold_ptsum: float = 0.01, beam_width: int = 0, audio_ctx: int = 0, offset_ms: int = 0, duration_ms: int = 0, sample_rate: int = 16000,
+                 stereo: Optional[np.ndarray] = None) -> int:
         """runFull on mono float32 16 kHz PCM (another sample_rate: PCM of any dtype resample() takes, resampled on the GPU first). Returns the HRESULT (0 = S_OK, 1 = S_FALSE: less than 1 s of audio). language "auto" (or ""): detected
         on the window at frame 0, whatever the run's offset (detected_language tells which).
-        With TOKEN_TIMESTAMPS in flags the tokens of results() carry t0 / t1 / vlen and max_len > 0 wraps the segments."""
+        With TOKEN_TIMESTAMPS in flags the tokens of results() carry t0 / t1 / vlen and max_len > 0 wraps the segments.
+        stereo: the recording's two channels, [n, 2] at the same sample_rate (what iAudioBuffer::getPcmStereo returns): speakers() then tells which channel
+        is louder during each segment. Combines with offset_ms / duration_ms; not with beam_width, audio_ctx or TOKEN_TIMESTAMPS through this face."""
         pcm = _at_16k(pcm, sample_rate)
         pt = np.ascontiguousarray(prompt if prompt is not None else [], np.int32)
+        if stereo is not None:
+            if audio_ctx or beam_width > 0 or flags & TOKEN_TIMESTAMPS:
+                raise ValueError("run_full: stereo does not combine with beam_width, audio_ctx or TOKEN_TIMESTAMPS")
+            st = _stereo_at_16k(stereo, sample_rate, len(pcm))
+            return _check(lib().whisperc_run_full_stereo(self.h, pcm.ctypes.data_as(C.c_void_p), st.ctypes.data_as(C.c_void_p), len(pcm), language.encode(), flags,
+                                                         max_tokens, pt.ctypes.data_as(C.c_void_p) if len(pt) else None, len(pt), n_max_text_ctx, offset_ms,
+                                                         duration_ms), "runFull")
         if offset_ms or duration_ms:            # sFullParams::offset_ms / duration_ms: the range that is transcribed
             return _check(lib().whisperc_run_full_range(self.h, pcm.ctypes.data_as(C.c_void_p), len(pcm), language.encode(), flags, max_tokens,
                                                         pt.ctypes.data_as(C.c_void_p) if len(pt) else None, len(pt), n_max_text_ctx, offset_ms, duration_ms), "runFull")
@@ -241,13 +288,21 @@ class Context:
                                               pt.ctypes.data_as(C.c_void_p) if len(pt) else None, len(pt), n_max_text_ctx), "runFull")
 
     def run_streamed(self, pcm: np.ndarray, language: str = "en", flags: int = 0, max_tokens: int = 0,
-                     prompt: Optional[Sequence[int]] = None, n_max_text_ctx: int = -1, sample_rate: int = 16000):
+                     prompt: Optional[Sequence[int]] = None, n_max_text_ctx: int = -1, sample_rate: int = 16000, stereo: Optional[np.ndarray] = None):
         """iMediaFoundation::loadAudioFileData (the PCM wrapped as a float32 WAV image at sample_rate, which the loader resamples when it is not 16000) +
-        iContext::runStreamed. Returns (HRESULT, [progress values the sink received])."""
-        wav = wav_bytes(pcm, sample_rate)
+        iContext::runStreamed. Returns (HRESULT, [progress values the sink received]).
+        stereo: as in run_full; the reader then holds the 16 kHz mono and stereo PCM (both resampled here when sample_rate is not 16000)."""
         pt = np.ascontiguousarray(prompt if prompt is not None else [], np.int32)
         prog = (C.c_double * 4096)()
         n = C.c_int()
+        if stereo is not None:
+            mono = _at_16k(pcm, sample_rate)
+            st = _stereo_at_16k(stereo, sample_rate, len(mono))
+            hr = _check(lib().whisperc_run_streamed_stereo(self.h, mono.ctypes.data_as(C.c_void_p), st.ctypes.data_as(C.c_void_p), len(mono), language.encode(), flags,
+                                                           max_tokens, pt.ctypes.data_as(C.c_void_p) if len(pt) else None, len(pt), n_max_text_ctx,
+                                                           prog, 4096, C.byref(n)), "runStreamed")
+            return hr, list(prog[:min(n.value, 4096)])
+        wav = wav_bytes(pcm, sample_rate)
         hr = _check(lib().whisperc_run_streamed(self.h, wav, len(wav), language.encode(), flags, max_tokens,
                                                 pt.ctypes.data_as(C.c_void_p) if len(pt) else None, len(pt), n_max_text_ctx,
                                                 prog, 4096, C.byref(n)), "runStreamed")
@@ -296,6 +351,19 @@ class Context:
             out.append(dict(t0=t0.value, t1=t1.value, text=text.value, tokens=toks))
         return out
 
+    def speakers(self) -> List[int]:
+        """One eSpeakerChannel per segment of results(): what iContext::detectSpeaker answered for the segment's times when the segment was appended --
+        SPEAKER_LEFT / SPEAKER_RIGHT where that channel's sum of |sample| is more than 1.1 times the other's, SPEAKER_UNSURE otherwise; NO_STEREO_DATA (0xFF)
+        for every segment of a run without stereo data."""
+        return _speakers_of(lib().whisperc_result_speakers, self.h)
+
+    def detect_speaker(self, t0: int, t1: int) -> int:
+        """iContext::detectSpeaker on the interval [t0, t1] (100 ns ticks). Like the reference's it answers only from the callbacks of a run, which this face
+        does not have: here it raises WhisperError with OLE_E_BLANK (0x80040007). speakers() is how results carry the answer."""
+        ch = C.c_uint8(NO_STEREO_DATA)
+        _check(lib().whisperc_detect_speaker(self.h, t0, t1, C.byref(ch)), "detectSpeaker")
+        return ch.value
+
     def timings_print(self):
         _check(lib().whisperc_timings_print(self.h), "timingsPrint")
 
@@ -340,12 +408,17 @@ class BatchRunner:
             pass
 
     def run(self, streams, language: str = "en", flags: int = 0, max_tokens: int = 0, prompt: Optional[Sequence[int]] = None,
-            n_max_text_ctx: int = -1, want_results: bool = True, sample_rate: int = 16000):
+            n_max_text_ctx: int = -1, want_results: bool = True, sample_rate: int = 16000, stereo: Optional[Sequence] = None):
         """streams: list of float32 PCM arrays (at 16 kHz; another sample_rate: every array is resampled on the GPU first, first_sample / count_samples then count
         16 kHz samples), or of (pcm, first_sample, count_samples) -- pieces of a recording share the array.
         Returns (HRESULT, [segments per stream or None], [per-stream HRESULT]). language "auto": every stream is detected on ITS OWN first window
-        and transcribed in its own language; self.languages then holds (code, p) per stream (None where nothing was detected)."""
+        and transcribed in its own language; self.languages then holds (code, p) per stream (None where nothing was detected).
+        stereo: per stream None or the [n, 2] stereo PCM of the stream's WHOLE array (pieces of a recording share it like the mono); self.speakers then
+        holds one eSpeakerChannel per segment and stream (Context.speakers; NO_STEREO_DATA for a stream without stereo data, None without a result)."""
         n = len(streams)
+        if stereo is not None and len(stereo) != n:
+            raise ValueError("stereo: one entry (an array or None) per stream")
+        st_ptrs, st_keep = (C.c_void_p * n)(), {}
         keep, ptrs, lens, first, cnt = [], (C.c_void_p * n)(), (C.c_uint32 * n)(), (C.c_int64 * n)(), (C.c_int64 * n)()
         resampled = {}              # id of a caller's array -> its 16 kHz version: the pieces of one recording keep sharing one buffer
         for i, s in enumerate(streams):
@@ -357,18 +430,28 @@ class BatchRunner:
             assert pcm.dtype == np.float32 and pcm.flags["C_CONTIGUOUS"]
             keep.append(pcm)
             ptrs[i], lens[i], first[i], cnt[i] = pcm.ctypes.data, len(pcm), f, c
+            if stereo is not None and stereo[i] is not None:
+                if id(stereo[i]) not in st_keep:
+                    st_keep[id(stereo[i])] = _stereo_at_16k(stereo[i], sample_rate, len(pcm))
+                st_ptrs[i] = st_keep[id(stereo[i])].ctypes.data
         pt = np.ascontiguousarray(prompt if prompt is not None else [], np.int32)
         res = (C.c_void_p * n)()
         per = (C.c_int32 * n)()
         import time
         t0 = time.perf_counter()
-        hr = lib().whisperc_batch_run(self.h, n, ptrs, lens, first, cnt, language.encode(), flags, max_tokens,
-                                      pt.ctypes.data_as(C.c_void_p) if len(pt) else None, len(pt), n_max_text_ctx, res, per)
+        if stereo is None:
+            hr = lib().whisperc_batch_run(self.h, n, ptrs, lens, first, cnt, language.encode(), flags, max_tokens,
+                                          pt.ctypes.data_as(C.c_void_p) if len(pt) else None, len(pt), n_max_text_ctx, res, per)
+        else:
+            hr = lib().whisperc_batch_run_stereo(self.h, n, ptrs, st_ptrs, lens, first, cnt, language.encode(), flags, max_tokens,
+                                                 pt.ctypes.data_as(C.c_void_p) if len(pt) else None, len(pt), n_max_text_ctx, res, per)
         self.last_run_seconds = time.perf_counter() - t0          # the library call alone (bench.py)
         out = []
         self.languages = []
+        self.speakers = []
         for i in range(n):
             out.append(read_result(res[i]) if (res[i] and want_results) else None)
+            self.speakers.append(_speakers_of(lib().whisperc_tr_speakers, res[i]) if (res[i] and want_results) else None)
             code, p = C.create_string_buffer(8), C.c_float()
             detected = bool(res[i]) and lib().whisperc_tr_language(res[i], code, C.byref(p)) == 0
             self.languages.append((code.value.decode(), p.value) if detected else None)

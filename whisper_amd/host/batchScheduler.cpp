@@ -46,6 +46,12 @@ namespace Whisper
 		public:
 			std::vector<Segment> resultAll;
 			int64_t mediaTimeOffset = 0;
+			// detectSpeaker (diarize.h): the stream's piece of its buffer's stereo PCM -- getPcmStereo() advanced by 2 * firstSample, the stream's
+			// countSamples frames of it -- or nullptr. mediaTimeOffset already accounts for firstSample. The context exists only while its stream runs.
+			const float* stereoPcm = nullptr;
+			size_t stereoFrames = 0;
+			mutable std::vector<uint8_t> speakers;	   // per segment of resultAll
+			void labelNewSegments() const { appendSpeakers( resultAll, mediaTimeOffset, stereoPcm, stereoFrames, speakers ); }
 			StreamContext( iModel* m, const Vocabulary& v ) : owner( m ), vocab( v ) {}
 			HRESULT runFull( const sFullParams&, const iAudioBuffer* ) override { return E_NOTIMPL; }
 			HRESULT runStreamed( const sFullParams&, const sProgressSink&, const iAudioReader* ) override { return E_NOTIMPL; }
@@ -53,20 +59,26 @@ namespace Whisper
 			HRESULT getResults( eResultFlags flags, iTranscribeResult** pp ) const override
 			{
 				if( !pp ) return E_POINTER;
+				labelNewSegments();	   // a segment whose new_segment callback is running
 				if( flags & eResultFlags::NewObject )
 				{
 					TranscribeResult* r = new TranscribeResult();
+					r->speakers = speakers;
 					const HRESULT hr = fillResultData( resultAll, vocab, mediaTimeOffset, flags, *r );
 					if( FAILED( hr ) ) { r->Release(); return hr; }
 					*pp = r;
 					return S_OK;
 				}
 				// without NewObject the reference hands out an object that lives as long as the context (TranscribeResult.h:34-43)
+				live.speakers = speakers;
 				CHECK( fillResultData( resultAll, vocab, mediaTimeOffset, flags, live ) );
 				*pp = &live;
 				return S_OK;
 			}
-			HRESULT detectSpeaker( const sTimeInterval&, eSpeakerChannel& result ) const override { result = eSpeakerChannel::NoStereoData; return S_FALSE; }
+			HRESULT detectSpeaker( const sTimeInterval& time, eSpeakerChannel& result ) const override
+			{
+				return diarize::detectSpeaker( stereoPcm, stereoFrames, mediaTimeOffset, time, result );
+			}
 			HRESULT getModel( iModel** pp ) override
 			{
 				if( !pp ) return E_POINTER;
@@ -192,6 +204,8 @@ namespace Whisper
 				{
 					TranscribeResult* r = new TranscribeResult();
 					fillResultData( s->ctx->resultAll, model->vocab, s->ctx->mediaTimeOffset, eResultFlags::Tokens | eResultFlags::Timestamps, *r );
+					s->ctx->labelNewSegments();
+					r->speakers = s->ctx->speakers;
 					r->languageId = s->languageId;
 					r->languageP = s->languageP;
 					results[ s->index ] = r;
@@ -226,6 +240,11 @@ namespace Whisper
 					}
 					s->nSamples = d.countSamples ? d.countSamples : total - d.firstSample;
 					s->pcm = mono ? mono + d.firstSample : nullptr;
+					if( const float* const st = d.buffer->getPcmStereo() )
+					{
+						s->ctx->stereoPcm = st + 2 * d.firstSample;
+						s->ctx->stereoFrames = (size_t)s->nSamples;
+					}
 					int64_t bufferTime = 0;
 					d.buffer->getTime( bufferTime );
 					s->ctx->mediaTimeOffset = bufferTime + d.firstSample * 10000000ll / 16000;
@@ -460,6 +479,7 @@ namespace Whisper
 					if( !s ) continue;
 					if( !s->scan->over ) s->scan->failed = s->scan->over = true;	// see consume(): not reachable through the host loop's prompts
 					const HRESULT hr = s->run->finishWindow( *s->scan );
+					s->ctx->labelNewSegments();
 					s->scan.reset();
 					if( FAILED( hr ) )
 					{

@@ -6,8 +6,8 @@
 //
 // Like the reference's tool the audio goes through iMediaFoundation::openAudioFile + iContext::runStreamed (per-window
 // spectrogram normalisation) unless token timestamps are requested, which need the whole buffer (main.cpp:305-321).
-// Differences from the reference, all due to features this build does not have: -di and -su report
-// what the library reports for them; -owts turns token timestamps on but
+// Differences from the reference, all due to features this build does not have: -su reports
+// what the library reports for it; -owts turns token timestamps on but
 // writes no karaoke script (the reference's tool does not either: params.h declares the option, main.cpp never reads it).
 #include <stdio.h>
 #include <string.h>

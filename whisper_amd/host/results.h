@@ -3,6 +3,7 @@
 #pragma once
 #include "hostCommon.h"
 #include "hostLoop.h"
+#include "diarize.h"
 
 namespace Whisper
 {
@@ -11,6 +12,9 @@ namespace Whisper
 		std::vector<sSegment> segments;
 		std::vector<sToken> tokens;
 		std::vector<std::string> texts;
+		// eSpeakerChannel per segment of a run over stereo audio, what iContext::detectSpeaker answered for the segment's times when it was appended
+		// (whisperc_tr_speakers reads them); 0xFF = NoStereoData. Beside the segments, not in them: sSegment is the reference's POD.
+		std::vector<uint8_t> speakers;
 	};
 	class TranscribeResult : public ComObject<iTranscribeResult>, public ResultData
 	{
@@ -52,6 +56,26 @@ namespace Whisper
 		const sSegment* getSegments() const override { return segments.empty() ? nullptr : segments.data(); }
 		const sToken* getTokens() const override { return tokens.empty() ? nullptr : tokens.data(); }
 	};
+
+	// The speakers of the segments appended since the last call (speakers.size() .. resultAll.size()), at the moment new_segment fires for them: the
+	// reference's rule (diarize.h) on the times getResults reports. stereo == nullptr: the run's audio has no stereo data, every segment is 0xFF; so is a
+	// segment that starts past the end of the stereo data (E_BOUNDS: there is no data to judge it by).
+	inline void appendSpeakers( const std::vector<Segment>& resultAll, int64_t mediaTimeOffset, const float* stereo, size_t frames, std::vector<uint8_t>& speakers )
+	{
+		if( speakers.size() > resultAll.size() ) speakers.clear();
+		for( size_t i = speakers.size(); i < resultAll.size(); i++ )
+		{
+			eSpeakerChannel ch = eSpeakerChannel::NoStereoData;
+			if( stereo )
+			{
+				sTimeInterval time;
+				time.begin.ticks = (uint64_t)( resultAll[ i ].t0 * 100000 + mediaTimeOffset );
+				time.end.ticks = (uint64_t)( resultAll[ i ].t1 * 100000 + mediaTimeOffset );
+				if( FAILED( diarize::detectSpeaker( stereo, frames, mediaTimeOffset, time, ch ) ) ) ch = eSpeakerChannel::NoStereoData;
+			}
+			speakers.push_back( (uint8_t)ch );
+		}
+	}
 
 	// Segment times: 10 ms units -> 100 ns ticks, plus the media time of the first sample (ContextImpl.misc.cpp getResults)
 	inline HRESULT fillResultData( const std::vector<Segment>& resultAll, const Vocabulary& vocab, int64_t mediaTimeOffset, eResultFlags flags, ResultData& res )

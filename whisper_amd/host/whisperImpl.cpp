@@ -57,14 +57,16 @@ namespace Whisper
 		{
 			static constexpr ComLight::GUID iid() { return { 0x5d6b0c1e, 0x7f0a, 0x4f53, { 0x9f, 0x6e, 0x3c, 0x1d, 0x2a, 0x7b, 0x9e, 0x41 } }; }
 			virtual const std::vector<float>& pcmMono() const = 0;
+			// interleaved, 2 floats per frame of pcmMono; empty unless the reader was opened with stereo = true on a source of two channels or more
+			virtual const std::vector<float>& pcmStereo() const = 0;
 		};
 		class WavReader : public iAudioReader, public iPcmSource
 		{
 			std::atomic<uint32_t> rc{ 1 };
-			std::vector<float> mono;
+			std::vector<float> mono, stereoPcm;
 			bool stereo;
 		public:
-			WavReader( std::vector<float>&& m, bool wantStereo ) : mono( std::move( m ) ), stereo( wantStereo ) {}
+			WavReader( std::vector<float>&& m, std::vector<float>&& st, bool wantStereo ) : mono( std::move( m ) ), stereoPcm( std::move( st ) ), stereo( wantStereo ) {}
 			virtual ~WavReader() = default;
 			HRESULT QueryInterface( const ComLight::GUID& riid, void** ppv ) override
 			{
@@ -86,6 +88,7 @@ namespace Whisper
 			HRESULT getReader( IMFSourceReader** pp ) const override { if( pp ) *pp = nullptr; return E_NOTIMPL; }
 			HRESULT requestedStereo() const override { return stereo ? S_OK : S_FALSE; }
 			const std::vector<float>& pcmMono() const override { return mono; }
+			const std::vector<float>& pcmStereo() const override { return stereoPcm; }
 		};
 
 		// ---- iContext ---------------------------------------------------------------------------------------------
@@ -103,6 +106,13 @@ namespace Whisper
 			std::vector<Segment> resultAll;
 			std::vector<int> promptPast;
 			int64_t mediaTimeOffset = 0;
+			// detectSpeaker (diarize.h). The reference answers while a run's spectrogram is current (ContextImpl::currentSpectrogram, set and cleared by
+			// CurrentSpectrogramRaii around runFullImpl, ContextImpl.cpp:437-465); what it reads from the spectrogram is the stereo PCM, so here the
+			// run's stereo PCM is current instead: the caller's buffer (runFull) or the reader's (runStreamed), nullptr when it has none.
+			bool runCurrent = false;
+			const float* stereoPcm = nullptr;
+			size_t stereoFrames = 0;
+			mutable std::vector<uint8_t> speakers;	   // per segment of resultAll, see appendSpeakers
 			mutable TranscribeResultStatic results;
 			// timings, the blocks of ProfileCollection (Whisper/Utils/ProfileCollection.h)
 			double msSpectrogram = 0, msEncode = 0, msDecode = 0, msRun = 0;
@@ -185,10 +195,14 @@ namespace Whisper
 			HRESULT runStreamed( const sFullParams& params, const sProgressSink& progress, const iAudioReader* reader ) override;
 			HRESULT runCapture( const sFullParams&, const sCaptureCallbacks&, const iAudioCapture* ) override { return E_NOTIMPL; }
 			HRESULT getResults( eResultFlags flags, iTranscribeResult** pp ) const override;
-			HRESULT detectSpeaker( const sTimeInterval&, eSpeakerChannel& result ) const override
+			HRESULT detectSpeaker( const sTimeInterval& time, eSpeakerChannel& result ) const override
 			{
-				result = eSpeakerChannel::NoStereoData;
-				return S_FALSE;
+				if( !runCurrent )
+				{
+					logError( "Because the audio is streamed, iContext.detectSpeaker() method only works when called from the callbacks" );
+					return OLE_E_BLANK;
+				}
+				return diarize::detectSpeaker( stereoPcm, stereoFrames, mediaTimeOffset, time, result );
 			}
 			HRESULT getModel( iModel** pp ) override
 			{
@@ -283,6 +297,8 @@ namespace Whisper
 			const int64_t melLen = n / 160;
 			mel = MelSource{};
 			mel.length = melLen;
+			stereoPcm = buffer->getPcmStereo();	   // a foreign buffer without stereo data: nullptr, NoStereoData
+			stereoFrames = stereoPcm ? n : 0;
 			if( melLen > 0 )
 			{
 				const auto t = Clock::now();
@@ -330,6 +346,11 @@ namespace Whisper
 			mel.nSamples = (int64_t)pcm.size();
 			mel.length = mel.nSamples / 160;			   // PcmReader::getLength(): whole 10 ms chunks (PcmReader.h:50-55)
 			mel.nChunks = ( mel.nSamples + 159 ) / 160;	   // readChunk pads the last incomplete chunk with zeros (PcmReader.cpp:416-424)
+			// The reference's MelStreamer keeps the stereo chunks of the current window only and answers E_UNEXPECTED for times behind it
+			// (MelStreamer.cpp:495-534); the whole recording is resident here, so those times are answered too.
+			const std::vector<float>& st = src->pcmStereo();
+			stereoFrames = std::min( st.size() / 2, pcm.size() );
+			stereoPcm = stereoFrames ? st.data() : nullptr;
 			HRESULT hr = S_OK;
 			if( mel.nSamples > 0 )
 			{
@@ -775,6 +796,13 @@ namespace Whisper
 			bool firstWindowEncoded = false;
 			CHECK( resolveLanguage( params, firstWindowEncoded ) );
 			StreamRun run( params, vocab, hp, this, progress, resultAll, promptPast, &stamper );
+			// the run's audio is current until this function returns; the stereo PCM is the caller's and is not referred to afterwards
+			struct CurrentRun
+			{
+				ContextImpl& c;
+				explicit CurrentRun( ContextImpl& ctx ) : c( ctx ) { c.runCurrent = true; c.speakers.clear(); }
+				~CurrentRun() { c.runCurrent = false; c.stereoPcm = nullptr; c.stereoFrames = 0; }
+			} current( *this );
 			const HRESULT hrBegin = run.begin( mel.length );
 			if( hrBegin != S_OK ) return hrBegin;
 			// eSamplingStrategy::BeamSearch (declared by the reference, implemented only here: sFullParams.h:10-13): beam_width hypotheses per
@@ -829,13 +857,18 @@ namespace Whisper
 						msSince( tDec ), dec.steps, dec.msFetch, dec.msEnqueue );
 				nDecodeSteps += dec.steps;	   // tokens the loop consumed (the reference counts one DecodeStep per token)
 				nDecodeWindows++;
-				CHECK( run.finishWindow( scan ) );
+				const HRESULT hrWindow = run.finishWindow( scan );
+				appendSpeakers( resultAll, mediaTimeOffset, stereoPcm, stereoFrames, speakers );
+				CHECK( hrWindow );
 			}
 			return run.end();
 		}
 
 		HRESULT ContextImpl::fillResults( eResultFlags flags, ResultData& res ) const
 		{
+			// a segment whose new_segment callback is running has not been through runFullImpl's own call yet
+			if( runCurrent ) appendSpeakers( resultAll, mediaTimeOffset, stereoPcm, stereoFrames, speakers );
+			res.speakers.assign( speakers.begin(), speakers.begin() + std::min( speakers.size(), resultAll.size() ) );
 			return fillResultData( resultAll, model->vocab, mediaTimeOffset, flags, res );
 		}
 
@@ -910,7 +943,8 @@ namespace Whisper
 		};
 
 		// RIFF/WAVE (wavFormat.h: PCM of 8 .. 32 bits or float32, 1 .. 8 channels, 1000 .. 384000 Hz) -> 16 kHz mono (and interleaved stereo when asked for: the
-		// first two channels, a mono file twice). The mean of the channels is their FP32 sum in channel order times 1.0f / C. A 16 kHz file is converted here;
+		// first two channels; a mono file has no stereo data, like the reference's buffer of a mono source, Whisper/MF/loadAudioFile.cpp:61-63). The mean of the
+		// channels is their FP32 sum in channel order times 1.0f / C. A 16 kHz file is converted here;
 		// any other rate goes to the GPU in the file's own format (wh_resample_host on the calling thread's current device: conversion, downmix and the filter).
 		static HRESULT decodeWav( const char* bytes, size_t size, const std::string& what, bool wantStereo, std::vector<float>& mono, std::vector<float>& st )
 		{
@@ -921,6 +955,7 @@ namespace Whisper
 				logError( "'%s': %s", what.c_str(), error.c_str() );
 				return E_INVALIDARG;
 			}
+			if( info.channels < 2 ) wantStereo = false;
 			const uint8_t* const pcm = (const uint8_t*)bytes + info.firstByte;
 			const int channels = info.channels, right = channels >= 2 ? 1 : 0;
 			st.clear();
@@ -973,16 +1008,16 @@ namespace Whisper
 		{
 			if( !pp || !path ) return E_POINTER;
 			std::vector<float> mono, st;
-			CHECK( readWavFile( path, false, mono, st ) );
-			*pp = new WavReader( std::move( mono ), stereo );
+			CHECK( readWavFile( path, stereo, mono, st ) );
+			*pp = new WavReader( std::move( mono ), std::move( st ), stereo );
 			return S_OK;
 		}
 		HRESULT WavLoader::loadAudioFileData( const void* data, uint64_t size, bool stereo, iAudioReader** pp )
 		{
 			if( !pp || !data ) return E_POINTER;
 			std::vector<float> mono, st;
-			CHECK( decodeWav( (const char*)data, (size_t)size, "<memory>", false, mono, st ) );
-			*pp = new WavReader( std::move( mono ), stereo );
+			CHECK( decodeWav( (const char*)data, (size_t)size, "<memory>", stereo, mono, st ) );
+			*pp = new WavReader( std::move( mono ), std::move( st ), stereo );
 			return S_OK;
 		}
 	}	// namespace
@@ -999,6 +1034,14 @@ namespace Whisper
 	HRESULT contextSetDeviceFlags( void* ctx, uint32_t flags, int parityThreads )
 	{
 		return static_cast<ContextImpl*>( (iContext*)ctx )->setDeviceFlags( flags, parityThreads );
+	}
+	// a reader over PCM that is decoded already (whisperc_run_streamed_stereo): what loadAudioFileData makes of a WAV image, with the caller's stereo PCM
+	static HRESULT createPcmReader( std::vector<float>&& mono, std::vector<float>&& stereo, iAudioReader** pp )
+	{
+		if( !pp ) return E_POINTER;
+		const bool wantStereo = !stereo.empty();
+		*pp = new WavReader( std::move( mono ), std::move( stereo ), wantStereo );
+		return S_OK;
 	}
 	// the lock-step scheduler's way to the device half of language detection (languageDetect.h): installed when the library is loaded
 	static const bool g_detectorInstalled = ( g_batchLanguageDetector = &wh_lang_detect, true );
@@ -1280,6 +1323,96 @@ WHISPER_EXPORT int32_t whisperc_run_streamed( void* ctx, const void* wavBytes, u
 	if( progressCount ) *progressCount = sink.n;
 	return hr;
 }
+// whisperc_run_full_range over a buffer that has stereo data: `stereo` = nSamples interleaved frames (2 floats each) of the same recording, what
+// iAudioBuffer::getPcmStereo returns; NULL = whisperc_run_full_range. The segments' speakers: whisperc_result_speakers.
+WHISPER_EXPORT int32_t whisperc_run_full_stereo( void* ctx, const float* pcm, const float* stereo, uint32_t nSamples, const char* language, uint32_t flags, int maxTokens,
+	const int32_t* promptTokens, int nPrompt, int nMaxTextCtx, int offsetMs, int durationMs )
+{
+	if( !ctx || ( !pcm && nSamples ) ) return E_POINTER;
+	iContext* c = (iContext*)ctx;
+	sFullParams p;
+	CHECK( c->fullDefaultParams( eSamplingStrategy::Greedy, &p ) );
+	p.flags = (eFullParamsFlags)flags;
+	p.language = makeLanguageKey( language ? language : "en" );
+	p.max_tokens = maxTokens;
+	p.prompt_tokens = promptTokens;
+	p.prompt_n_tokens = nPrompt;
+	p.offset_ms = offsetMs;
+	p.duration_ms = durationMs;
+	if( nMaxTextCtx >= 0 ) p.n_max_text_ctx = nMaxTextCtx;
+	iAudioBuffer* buf = nullptr;
+	CHECK( createAudioBuffer( std::vector<float>( pcm, pcm + nSamples ), stereo ? std::vector<float>( stereo, stereo + 2 * (size_t)nSamples ) : std::vector<float>(), &buf ) );
+	const HRESULT hr = c->runFull( p, buf );
+	buf->Release();
+	return hr;
+}
+// iContext::runStreamed over a reader that has stereo data: mono FP32 16 kHz PCM and nSamples interleaved stereo frames of the same recording (NULL: none)
+WHISPER_EXPORT int32_t whisperc_run_streamed_stereo( void* ctx, const float* pcm, const float* stereo, uint32_t nSamples, const char* language, uint32_t flags,
+	int maxTokens, const int32_t* promptTokens, int nPrompt, int nMaxTextCtx, double* progressOut, int progressCap, int* progressCount )
+{
+	if( !ctx || ( !pcm && nSamples ) ) return E_POINTER;
+	iContext* c = (iContext*)ctx;
+	sFullParams p;
+	CHECK( c->fullDefaultParams( eSamplingStrategy::Greedy, &p ) );
+	p.flags = (eFullParamsFlags)flags;
+	p.language = makeLanguageKey( language ? language : "en" );
+	p.max_tokens = maxTokens;
+	p.prompt_tokens = promptTokens;
+	p.prompt_n_tokens = nPrompt;
+	if( nMaxTextCtx >= 0 ) p.n_max_text_ctx = nMaxTextCtx;
+	iAudioReader* reader = nullptr;
+	CHECK( createPcmReader( std::vector<float>( pcm, pcm + nSamples ), stereo ? std::vector<float>( stereo, stereo + 2 * (size_t)nSamples ) : std::vector<float>(), &reader ) );
+	struct Sink { double* out; int cap, n; } sink{ progressOut, progressCap, 0 };
+	sProgressSink ps;
+	ps.pfn = []( double v, iContext*, void* pv ) noexcept -> HRESULT
+	{
+		Sink* s = (Sink*)pv;
+		if( s->out && s->n < s->cap ) s->out[ s->n ] = v;
+		s->n++;
+		return S_OK;
+	};
+	ps.pv = &sink;
+	const HRESULT hr = c->runStreamed( p, ps, reader );
+	reader->Release();
+	if( progressCount ) *progressCount = sink.n;
+	return hr;
+}
+// iContext::detectSpeaker( { t0, t1 } in 100 ns ticks ): *channel = eSpeakerChannel (0 unsure, 1 left, 2 right, 0xFF no stereo data). Outside a run's
+// callbacks: OLE_E_BLANK, like the reference.
+WHISPER_EXPORT int32_t whisperc_detect_speaker( void* ctx, uint64_t t0, uint64_t t1, uint8_t* channel )
+{
+	if( !ctx || !channel ) return E_POINTER;
+	sTimeInterval time;
+	time.begin.ticks = t0;
+	time.end.ticks = t1;
+	eSpeakerChannel ch = eSpeakerChannel::NoStereoData;
+	const HRESULT hr = ( (iContext*)ctx )->detectSpeaker( time, ch );
+	*channel = (uint8_t)ch;
+	return hr;
+}
+// Of a transcribe result of this library (iContext::getResults, a batch runner's per-stream result): one eSpeakerChannel byte per segment, what
+// iContext::detectSpeaker answered for the segment when it was appended; 0xFF = the run's audio had no stereo data. *count = the segments;
+// out may be NULL (count only), cap < *count is E_INVALIDARG.
+WHISPER_EXPORT int32_t whisperc_tr_speakers( void* result, uint8_t* out, uint32_t cap, uint32_t* count )
+{
+	if( !result || !count ) return E_POINTER;
+	const ResultData* r = dynamic_cast<const ResultData*>( (iTranscribeResult*)result );
+	if( !r ) return E_INVALIDARG;
+	const size_t n = r->segments.size();
+	*count = (uint32_t)n;
+	if( !out ) return S_OK;
+	if( cap < n ) return E_INVALIDARG;
+	for( size_t i = 0; i < n; i++ ) out[ i ] = i < r->speakers.size() ? r->speakers[ i ] : (uint8_t)0xFF;
+	return S_OK;
+}
+// the same of a context's results (iContext::getResults)
+WHISPER_EXPORT int32_t whisperc_result_speakers( void* ctx, uint8_t* out, uint32_t cap, uint32_t* count )
+{
+	if( !ctx ) return E_POINTER;
+	iTranscribeResult* r = nullptr;
+	CHECK( ( (iContext*)ctx )->getResults( eResultFlags::Timestamps, &r ) );
+	return whisperc_tr_speakers( r, out, cap, count );
+}
 // wh_resample_host behind an HRESULT: *nOut = the 16 kHz samples the input gives; dst == NULL only counts, cap < *nOut is E_INVALIDARG
 WHISPER_EXPORT int32_t whisperc_resample( const void* src, int32_t format, int32_t channels, int32_t channel, int32_t rate, int64_t nFrames, float* dst, int64_t cap,
 	int64_t* nOut )
@@ -1317,6 +1450,12 @@ WHISPER_EXPORT int32_t whisperc_load_audio( const char* pathUtf8, int32_t stereo
 	*nFrames = n;
 	HRESULT res = S_OK;
 	if( cap < floats ) res = E_INVALIDARG;
+	else if( n > 0 && stereo && !buf->getPcmStereo() )
+	{
+		// a mono file: the buffer has no stereo data (iContext::detectSpeaker answers NoStereoData for it); this entry point hands out the one channel twice
+		const float* const m = buf->getPcmMono();
+		for( int64_t i = 0; i < n; i++ ) dst[ 2 * i ] = dst[ 2 * i + 1 ] = m[ i ];
+	}
 	else if( n > 0 ) memcpy( dst, stereo ? buf->getPcmStereo() : buf->getPcmMono(), (size_t)floats * sizeof( float ) );
 	buf->Release();
 	return res;
@@ -1430,12 +1569,13 @@ namespace
 	class PcmView : public Whisper::ComObject<Whisper::iAudioBuffer>
 	{
 		const float* const pcm;
+		const float* const stereo;	   // n interleaved frames, or nullptr
 		const uint32_t n;
 	public:
-		PcmView( const float* p, uint32_t count ) : pcm( p ), n( count ) {}
+		PcmView( const float* p, const float* st, uint32_t count ) : pcm( p ), stereo( st ), n( count ) {}
 		uint32_t countSamples() const override { return n; }
 		const float* getPcmMono() const override { return n ? pcm : nullptr; }
-		const float* getPcmStereo() const override { return nullptr; }
+		const float* getPcmStereo() const override { return n ? stereo : nullptr; }
 		HRESULT getTime( int64_t& rdi ) const override { rdi = 0; return S_OK; }
 	};
 }
@@ -1448,9 +1588,11 @@ WHISPER_EXPORT int32_t whisperc_batch_create( void* model, uint32_t maxSlots, ui
 	*runnerOut = r;
 	return hr;
 }
-WHISPER_EXPORT int32_t whisperc_batch_run( void* runner, uint32_t count, const float* const* pcm, const uint32_t* nSamples, const int64_t* firstSample,
-	const int64_t* countSamples, const char* language, uint32_t flags, int maxTokens, const int32_t* promptTokens, int nPrompt, int nMaxTextCtx,
-	void** resultsOut, int32_t* perStream )
+// whisperc_batch_run over buffers that have stereo data: stereo[i] = nSamples[i] interleaved frames of the recording pcm[i] is the mono of, or NULL
+// (stereo itself may be NULL: whisperc_batch_run). Every result carries its segments' speakers (whisperc_tr_speakers).
+WHISPER_EXPORT int32_t whisperc_batch_run_stereo( void* runner, uint32_t count, const float* const* pcm, const float* const* stereo, const uint32_t* nSamples,
+	const int64_t* firstSample, const int64_t* countSamples, const char* language, uint32_t flags, int maxTokens, const int32_t* promptTokens, int nPrompt,
+	int nMaxTextCtx, void** resultsOut, int32_t* perStream )
 {
 	if( !runner || !resultsOut || ( count && ( !pcm || !nSamples ) ) ) return E_POINTER;
 	sFullParams p;
@@ -1467,12 +1609,13 @@ WHISPER_EXPORT int32_t whisperc_batch_run( void* runner, uint32_t count, const f
 	p.prompt_n_tokens = nPrompt;
 	if( nMaxTextCtx >= 0 ) p.n_max_text_ctx = nMaxTextCtx;
 	// one view per distinct buffer: the chunks of a recording share it
-	std::map<std::pair<const float*, uint32_t>, PcmView*> views;
+	std::map<std::pair<std::pair<const float*, const float*>, uint32_t>, PcmView*> views;
 	std::vector<sBatchStream> streams( count );
 	for( uint32_t i = 0; i < count; i++ )
 	{
-		PcmView*& v = views[ { pcm[ i ], nSamples[ i ] } ];
-		if( !v ) v = new PcmView( pcm[ i ], nSamples[ i ] );
+		const float* const st = stereo ? stereo[ i ] : nullptr;
+		PcmView*& v = views[ { { pcm[ i ], st }, nSamples[ i ] } ];
+		if( !v ) v = new PcmView( pcm[ i ], st, nSamples[ i ] );
 		streams[ i ] = sBatchStream{ v, firstSample ? firstSample[ i ] : 0, countSamples ? countSamples[ i ] : 0, nullptr };
 	}
 	std::vector<iTranscribeResult*> res( count, nullptr );
@@ -1481,6 +1624,13 @@ WHISPER_EXPORT int32_t whisperc_batch_run( void* runner, uint32_t count, const f
 	for( uint32_t i = 0; i < count; i++ ) resultsOut[ i ] = res[ i ];
 	for( auto& kv : views ) kv.second->Release();
 	return hr;
+}
+WHISPER_EXPORT int32_t whisperc_batch_run( void* runner, uint32_t count, const float* const* pcm, const uint32_t* nSamples, const int64_t* firstSample,
+	const int64_t* countSamples, const char* language, uint32_t flags, int maxTokens, const int32_t* promptTokens, int nPrompt, int nMaxTextCtx,
+	void** resultsOut, int32_t* perStream )
+{
+	return whisperc_batch_run_stereo( runner, count, pcm, nullptr, nSamples, firstSample, countSamples, language, flags, maxTokens, promptTokens, nPrompt, nMaxTextCtx,
+		resultsOut, perStream );
 }
 WHISPER_EXPORT int32_t whisperc_tr_counts( void* result, uint32_t* segments, uint32_t* tokens )
 {
