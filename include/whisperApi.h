@@ -346,6 +346,21 @@ namespace Whisper
 	WHISPER_EXPORT HRESULT createBatchRunner( iModel* model, const sBatchSetup* setup, iBatchRunner** pp );
 	WHISPER_EXPORT HRESULT runFullBatch( iModel* model, const sFullParams& params, const sBatchStream* streams, uint32_t count, const sBatchSetup* setup,
 		iTranscribeResult** results, HRESULT* perStream );
+	// Extension (no counterpart in whisper.def): ONE long recording onto the batched path. The buffer is cut into pieces of at most maxLen samples at pauses,
+	// found with the reference's voice-activity detector (Whisper/Whisper/voiceActivityDetection.cpp, which its capture loop uses to fire a transcription when
+	// the speaker pauses): the per-frame features come from the device (wh_vad_features of whisper_hip.h, on the calling thread's current device), the decision
+	// and the plan are host code. A cut lies in the middle of a pause of at least pauseFrames frames of 256 samples, the last such pause that leaves the piece
+	// between minLen and maxLen samples; without one, where 21 frames hold the least energy. The plan is a partition of the buffer and a function of the samples
+	// alone. Run the pieces with NoContext: they are independent recordings.
+	struct sSplitParams
+	{
+		int64_t maxLen, minLen;		// samples; 0 = 480000 (30 s: a piece is one window) and 240000. 16000 <= minLen <= maxLen - 32000, maxLen <= 480000
+		uint32_t pauseFrames;		// 0 = 21 (0.336 s; the reference's pauseDuration is 0.333 s)
+		uint32_t reserved;
+	};
+	// receives the pieces as ready streams over the buffer (params nullptr = the call's common parameters), valid during the call; its result is splitAtPauses's
+	using pfnSplitChunks = HRESULT ( * )( const sBatchStream* streams, uint32_t count, void* pv );
+	WHISPER_EXPORT HRESULT splitAtPauses( const iAudioBuffer* buffer, const sSplitParams* params /* nullptr = defaults */, pfnSplitChunks pfnChunks, void* pv );
 	WHISPER_EXPORT HRESULT initMediaFoundation( iMediaFoundation** pp );
 	WHISPER_EXPORT uint32_t findLanguageKeyW( const wchar_t* lang );
 	WHISPER_EXPORT uint32_t findLanguageKeyA( const char* lang );

@@ -46,6 +46,19 @@ int32_t whisperc_run_streamed( void* ctx, const void* wavBytes, uint64_t wavSize
  * *nOut = ceil( nFrames * 16000 / rate ); dst == NULL only counts, cap (floats of dst) < *nOut is E_INVALIDARG. rate 16000 converts without filtering. */
 int32_t whisperc_resample( const void* src, int32_t format, int32_t channels, int32_t channel, int32_t rate, int64_t nFrames, float* dst, int64_t cap,
 	int64_t* nOut );
+/* Splitting a long recording at pauses (Whisper::splitAtPauses of whisperApi.h), on mono FP32 16 kHz PCM:
+ * whisperc_vad: voice-activity features on the calling thread's current device (wh_vad_features_host of whisper_hip.h), then the reference's decision loop
+ *   (Whisper/Whisper/voiceActivityDetection.cpp:121-205) on the host: speech[ f ] = 1 where frame f = samples [256 f, 256 f + 256) is speech, *lastSpeech =
+ *   ( f + 1 ) * 256 of the last speech frame (0 = none), *nFrames = nSamples / 256. speech == NULL only counts; cap < *nFrames is E_INVALIDARG.
+ * whisperc_plan_chunks: the chunks (first[ i ], count[ i ]) in samples that partition the recording into pieces of at most maxLen and -- but for the last --
+ *   at least minLen samples, cut in the middle of pauses of at least pauseFrames frames, or where 21 frames hold the least energy when there is no pause
+ *   (whisper_amd/host/chunkPlanner.h states the rule). 0 = the defaults 480000 / 240000 / 21; 16000 <= minLen <= maxLen - 32000, maxLen <= 480000, or
+ *   E_INVALIDARG. *nChunks = the chunks; first / count may be NULL (count only), cap < *nChunks is E_INVALIDARG.
+ * whisperc_debug_vad_decide: the host half on its own (no device): the decision loop over nFrames x ( energy, F, SFM ); speech may be NULL. */
+int32_t whisperc_vad( const float* pcm, int64_t nSamples, uint8_t* speech, int64_t cap, int64_t* nFrames, int64_t* lastSpeech );
+int32_t whisperc_plan_chunks( const float* pcm, int64_t nSamples, int64_t maxLen, int64_t minLen, int32_t pauseFrames, int64_t* first, int64_t* count,
+	int32_t cap, int32_t* nChunks );
+int32_t whisperc_debug_vad_decide( const float* feat, int64_t nFrames, uint8_t* speech, int64_t* lastSpeech );
 /* iMediaFoundation::loadAudioFile + iAudioBuffer::getPcmMono (stereo != 0: getPcmStereo, interleaved, 2 floats per frame; a mono file, whose buffer has no stereo data, twice): the WAV file as 16 kHz floats.
  * *nFrames = its 16 kHz frames; dst == NULL reads the file and parses its chunks, converts nothing and returns the count (so a
  * caller that asks for the count first reads the file twice); cap counts floats. */

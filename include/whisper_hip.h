@@ -223,6 +223,30 @@ WH_API int wh_resample_host_multi( const void* src, int format, int channels, co
 /* the table the kernel reads: L, M, half, K and the [L][K] taps (tapsHost may be NULL to query sizes; cap = floats it holds). Host only. */
 WH_API int wh_resample_taps( int inRate, int32_t* L, int32_t* M, int32_t* half, int32_t* K, float* tapsHost, int64_t cap );
 
+/* Voice-activity features of 16 kHz mono FP32 PCM on the GPU: the per-frame half of VAD::detect (Whisper/Whisper/voiceActivityDetection.cpp:65-113; Moattar &
+ * Homayounpour 2009), which the chunk planner of whisperApi.h (splitAtPauses) uses to cut a long recording at pauses. Frame f is samples [256 f, 256 f + 256),
+ * the last partial frame is ignored; with x[n] = pcm[n] * 32768.0f and X the 256-point DFT of x, featDev[ 3 f .. 3 f + 2 ] =
+ *   energy = sqrtf( (float)( sum_n (double)(float)( x[n] x[n] ) / 256 ) )                       the square is rounded to float, the sum is in double
+ *   F      = 62.5f * the first k in 0 .. 127 that maximises |X[k]|^2                            ties go to the lower bin, an all-zero frame gives 0
+ *   SFM    = -10 log10( (float)( exp( sum_{k<256} ln|X[k]| / 256 ) / ( sum_{k<256} |X[k]| / 256 ) ) )
+ * The reference evaluates X with a recursive single-precision FFT over approximate sines, so its own bits are no target: the features are those of the exact
+ * DFT, evaluated in FP64 (a GEMM against a host-built twiddle table on the FP64 matrix cores, fixed summation order) and rounded once to float; sqrtf and the
+ * final log10 are the correctly rounded float functions. A frame's numbers depend on its 256 samples only: not on the buffer's length, its address or the
+ * frame's place in a workgroup (16 frames each).
+ * Special values: an all-zero frame has energy 0, F 0 and SFM NaN (0 / 0). A frame with a bin that vanishes exactly has SFM +inf in exact arithmetic; the
+ * device returns +inf where its own sum for that bin is exactly zero (bins 0 and 128, whose twiddles are +-1: the alternating or the plain sum of
+ * integer-valued samples is exact) and otherwise a FINITE number: the bin's rounding noise, about 1e-16 of the frame's norm, stands in for the zero, and
+ * ln of it is about -37 instead of -inf, which lifts SFM by some 10 log10( e ) 2 * 37 / 256 = 1.3 dB over what the other bins give. A bin that cancels
+ * exactly against irrational twiddles takes samples constructed for it (a frame of two equal halves, say); recorded audio does not do that.
+ * nSamples < 256 gives zero frames and success; null or misaligned pointers with nFrames > 0, nSamples < 0 or > 2^40: WH_E_INVALIDARG.
+ * The twiddle table (4 KB) is built and uploaded by the first call on a device (the call waits for it) and kept for the life of the process. */
+/* Host only: *nFrames = nSamples / 256. */
+WH_API int wh_vad_frame_count( int64_t nSamples, int64_t* nFrames );
+/* device -> device, on `stream`; featDev: FP32 [nFrames][3] */
+WH_API int wh_vad_features( void* stream, const float* pcmDev, int64_t nSamples, float* featDev );
+/* host -> host on the current device: upload of the whole frames, kernel, download. */
+WH_API int wh_vad_features_host( const float* pcm, int64_t nSamples, float* feat );
+
 /* Encoder. Replaces WhisperContext::encode (WhisperContext.cpp:310-399) == whisper_encode (whisper.cpp:1084-1496).
  * melDev: FP32 device, `batch` spectrograms each [n_mel][melLen] (melStride floats apart); for each the window
  * [melOffset, melOffset + 2*n_audio_ctx) is taken and zero-padded (MelInputTensor.cpp:8-63).  Fills the

@@ -20,7 +20,7 @@ TOKEN_TIMESTAMPS = 0x100
 
 CPP_EXPORTS = ["setupLogger", "loadModel", "initMediaFoundation", "findLanguageKeyW", "findLanguageKeyA", "getSupportedLanguages", "listGPUs"]
 # extensions next to the seven names of whisper.def: one process per GPU, and K streams in lock step on one GPU
-CPP_EXTENSIONS = ["loadModelShared", "createBatchRunner", "runFullBatch"]
+CPP_EXTENSIONS = ["loadModelShared", "createBatchRunner", "runFullBatch", "splitAtPauses"]
 
 _lib = None
 
@@ -82,6 +82,9 @@ def lib():
         L.whisperc_detect_speaker.argtypes = [vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint8)]
         L.whisperc_result_speakers.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
         L.whisperc_tr_speakers.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.whisperc_vad.argtypes = [vp, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.whisperc_plan_chunks.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, vp, vp, C.c_int32, C.POINTER(C.c_int32)]
+        L.whisperc_debug_vad_decide.argtypes = [vp, C.c_int64, vp, C.POINTER(C.c_int64)]
         _lib = L
     return _lib
 
@@ -190,6 +193,42 @@ def _at_16k(pcm: np.ndarray, sample_rate: int) -> np.ndarray:
     if sample_rate == SAMPLE_RATE or pcm.dtype.name not in _PCM_FORMATS:
         pcm = np.ascontiguousarray(pcm, np.float32)       # float64 and the like: cast as the 16 kHz path always did
     return pcm if sample_rate == SAMPLE_RATE else resample(pcm, sample_rate)
+
+
+VAD_FRAME = 256             # samples per voice-activity frame: 16 ms at 16 kHz
+
+
+def vad(pcm: np.ndarray, sample_rate: int = 16000):
+    """Voice activity of a mono recording: (speech uint8 [n // 256], last_speech). speech[f] = 1 where frame f = samples [256 f, 256 f + 256) at 16 kHz is
+    speech; last_speech = the sample behind the last speech frame (0 = none). The features (energy, dominant frequency, spectral flatness: wh_vad_features)
+    are computed on the GPU, the reference's decision loop (Moattar & Homayounpour 2009) runs on the host. Another sample_rate is resampled on the GPU first."""
+    pcm = _at_16k(pcm, sample_rate)
+    n, last = C.c_int64(), C.c_int64()
+    _check(lib().whisperc_vad(pcm.ctypes.data_as(C.c_void_p), len(pcm), None, 0, C.byref(n), None), "vad")
+    speech = np.zeros(n.value, np.uint8)
+    _check(lib().whisperc_vad(pcm.ctypes.data_as(C.c_void_p), len(pcm), speech.ctypes.data_as(C.c_void_p), speech.size, C.byref(n), C.byref(last)), "vad")
+    return speech, last.value
+
+
+def vad_decide(features: np.ndarray):
+    """The host half of vad() on its own (no device): (speech, last_speech) from float32 [n, 3] features = energy, F, SFM per frame."""
+    feat = np.ascontiguousarray(features, np.float32).reshape(-1, 3)
+    speech, last = np.zeros(len(feat), np.uint8), C.c_int64()
+    _check(lib().whisperc_debug_vad_decide(feat.ctypes.data_as(C.c_void_p), len(feat), speech.ctypes.data_as(C.c_void_p), C.byref(last)), "vad_decide")
+    return speech, last.value
+
+
+def plan_chunks(pcm: np.ndarray, max_len: int = 480000, min_len: int = 240000, pause_frames: int = 21, sample_rate: int = 16000):
+    """Where to cut a long mono recording into independent pieces for BatchRunner.run: [(first_sample, count_samples)] at 16 kHz, a partition of the
+    recording into pieces of at most max_len and -- but for the last -- at least min_len samples, cut in the middle of pauses of at least pause_frames
+    frames of 256 samples (vad()), or where 21 frames hold the least energy when a piece holds no pause (Whisper::splitAtPauses)."""
+    pcm = _at_16k(pcm, sample_rate)
+    n = C.c_int32()
+    args = (pcm.ctypes.data_as(C.c_void_p), len(pcm), max_len, min_len, pause_frames)
+    _check(lib().whisperc_plan_chunks(*args, None, None, 0, C.byref(n)), "plan_chunks")
+    first, count = np.zeros(n.value, np.int64), np.zeros(n.value, np.int64)
+    _check(lib().whisperc_plan_chunks(*args, first.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p), n.value, C.byref(n)), "plan_chunks")
+    return [(int(f), int(c)) for f, c in zip(first, count)]
 
 
 class Model:
@@ -459,6 +498,16 @@ class BatchRunner:
                 lib().whisperc_release(res[i])
         _check(hr, "runFullBatch")
         return hr, out, [int(x) & 0xFFFFFFFF for x in per]
+
+
+    def run_split(self, pcm: np.ndarray, flags: int = 0, sample_rate: int = 16000, **run_kwargs):
+        """ONE long recording on the batched path: cut at pauses (plan_chunks), the pieces run as independent streams (NoContext is added to flags: a piece
+        carries nothing over). Returns what run returns plus the plan: (HRESULT, [segments per piece or None], [per-piece HRESULT], [(first, count)]);
+        segment times are relative to the recording. run_kwargs: run's language, max_tokens, prompt, n_max_text_ctx, want_results."""
+        pcm = _at_16k(pcm, sample_rate)
+        plan = plan_chunks(pcm)
+        hr, out, per = self.run([(pcm, f, c) for f, c in plan], flags=flags | NO_CONTEXT, **run_kwargs)
+        return hr, out, per, plan
 
 
 def wav_bytes(pcm: np.ndarray, rate: int = 16000) -> bytes:

@@ -51,6 +51,7 @@ EXPORTS = [
     "wh_op_vocab_soft_max", "wh_op_sample_best", "wh_op_beam_candidates", "wh_op_reorder_self_cache",
     "wh_lang_detect", "wh_model_lang_count", "wh_op_lang_probs",
     "wh_resample_out_len", "wh_resample", "wh_resample_host", "wh_resample_host_multi", "wh_resample_taps",
+    "wh_vad_frame_count", "wh_vad_features", "wh_vad_features_host",
 ]
 
 
@@ -172,6 +173,9 @@ def lib():
         L.wh_resample_host.argtypes = [vp, i32, i32, i32, i32, i64, vp, i64, i64]
         L.wh_resample_host_multi.argtypes = [vp, i32, i32, vp, i32, i32, i64, vp, vp, i64]
         L.wh_resample_taps.argtypes = [i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, i64]
+        L.wh_vad_frame_count.argtypes = [i64, C.POINTER(i64)]
+        L.wh_vad_features.argtypes = [vp, vp, i64, vp]
+        L.wh_vad_features_host.argtypes = [vp, i64, vp]
         _lib = L
     return _lib
 

@@ -2,6 +2,8 @@
 //
 //   whisper-mgpu -n 8 -m ggml-medium.bin -f recording.wav [-l en] [-o out.txt] [-timeout 300] [-job-timeout 0] [-slots 64] [-id file] [-job token]
 //   whisper-mgpu -n 8 -m ggml-medium.bin -per-recording -f a.wav -f b.wav ...   whole recordings, one stream each with the reference's sliding window (no words cut at 30 s)
+//   whisper-mgpu -n 8 -m ggml-medium.bin -split silence -f recording.wav        the chunks end at pauses instead of every 30 s (Whisper::splitAtPauses): no words cut either,
+//                                                                               and the chunks still run in lock step
 //
 // The parent forks N ranks (or, when RANK / WORLD_SIZE / LOCAL_RANK are set by an external launcher, runs as that rank).
 // Rank r binds GPU LOCAL_RANK % devices (sModelSetup.adapter); rank 0 creates the RCCL id and publishes it through a file;
@@ -43,6 +45,7 @@ namespace
 		double jobTimeout = 0.0;	// deadline of the whole job (forked mode: the parent ends the ranks); 0 = none
 		std::string model, wav, lang = "en", out = "transcript.txt", idFile;
 		std::vector<std::string> wavs;	// every -f
+		bool splitSilence = false;	// -split silence: the chunks of the recording end at pauses (splitAtPauses) instead of every 480000 samples (-split fixed, the default)
 		bool perRecording = false;	// -per-recording: whole recordings dealt round-robin to the ranks, each decoded with the reference's sliding window
 		std::string job;			// token of THIS job: stamped into the id file by rank 0, required by the ranks that read it
 	};
@@ -112,6 +115,15 @@ namespace
 		if( 0 == strcmp( colon + 1, "exit" ) ) _exit( 7 );
 		if( 0 == strcmp( colon + 1, "hang" ) )
 			while( true ) sleep( 1000 );
+	}
+
+	const char* const USAGE = "usage: whisper-mgpu -n ranks -m model.bin -f audio.wav [-l en] [-o out.txt] [-timeout seconds (rendezvous and collectives)] [-job-timeout seconds (whole job; default none)] [-slots n] [-id id-file] [-job token] [-split fixed|silence (where the chunks of the recording end: every 30 s, or at pauses)] [-per-recording -f more.wav ...]\n";
+
+	// splitAtPauses hands the plan out through a callback: keep the streams
+	HRESULT keepStreams( const sBatchStream* s, uint32_t n, void* pv )
+	{
+		( (std::vector<sBatchStream>*)pv )->assign( s, s + n );
+		return S_OK;
 	}
 
 	int runRank( const Args& a, int rank, int world, int localRank )
@@ -198,10 +210,23 @@ namespace
 			if( FAILED( hr ) ) { fprintf( stderr, "[rank %d] cannot load %s (0x%08x)\n", rank, a.wav.c_str(), (unsigned)hr ); return 5; }
 			audios.push_back( audio );
 			const int64_t nSamples = audio->countSamples();
-			windows = (int)( ( nSamples + chunk - 1 ) / chunk );
-			shardRange( windows, rank, world, wb, we );
-			for( int w = wb; w < we; w++ )
-				streams.push_back( sBatchStream{ audio, (int64_t)w * chunk, std::min( chunk, nSamples - (int64_t)w * chunk ), nullptr } );
+			if( a.splitSilence )
+			{
+				// every rank computes THE plan (a function of the samples alone) on its own GPU and takes its range of it
+				std::vector<sBatchStream> all;
+				hr = splitAtPauses( audio, nullptr, &keepStreams, &all );
+				if( FAILED( hr ) ) { fprintf( stderr, "[rank %d] splitAtPauses failed 0x%08x\n", rank, (unsigned)hr ); return 5; }
+				windows = (int)all.size();
+				shardRange( windows, rank, world, wb, we );
+				streams.assign( all.begin() + wb, all.begin() + we );
+			}
+			else
+			{
+				windows = (int)( ( nSamples + chunk - 1 ) / chunk );
+				shardRange( windows, rank, world, wb, we );
+				for( int w = wb; w < we; w++ )
+					streams.push_back( sBatchStream{ audio, (int64_t)w * chunk, std::min( chunk, nSamples - (int64_t)w * chunk ), nullptr } );
+			}
 		}
 
 		sFullParams p;
@@ -265,7 +290,11 @@ namespace
 			nSeg, tRun, tRun > 0 ? ( we - wb ) * 30.0 / tRun : 0.0, tAll );
 		if( rank == 0 )
 		{
-			printf( "{\"ranks\": %d, \"windows\": %d, \"seconds\": %.4f, \"audio_seconds_per_sec\": %.2f}\n", world, windows, tAll, windows * 30.0 / tAll );
+			if( a.splitSilence )
+				printf( "{\"ranks\": %d, \"windows\": %d, \"seconds\": %.4f, \"audio_seconds_per_sec\": %.2f, \"split\":\"silence\"}\n", world, windows, tAll,
+					audios[ 0 ]->countSamples() / 16000.0 / tAll );
+			else
+				printf( "{\"ranks\": %d, \"windows\": %d, \"seconds\": %.4f, \"audio_seconds_per_sec\": %.2f}\n", world, windows, tAll, windows * 30.0 / tAll );
 			fflush( stdout );	   // the rank leaves through _exit
 		}
 		if( runner ) runner->Release();
@@ -328,6 +357,13 @@ int main( int argc, char** argv )
 		else if( !strcmp( argv[ i ], "-m" ) ) a.model = val();
 		else if( !strcmp( argv[ i ], "-f" ) ) { a.wav = val(); a.wavs.push_back( a.wav ); }
 		else if( !strcmp( argv[ i ], "-per-recording" ) ) a.perRecording = true;
+		else if( !strcmp( argv[ i ], "-split" ) )
+		{
+			const char* const how = val();
+			if( !strcmp( how, "silence" ) ) a.splitSilence = true;
+			else if( !strcmp( how, "fixed" ) ) a.splitSilence = false;
+			else { fprintf( stderr, "whisper-mgpu: -split takes fixed or silence, not '%s'\n%s", how, USAGE ); return 1; }
+		}
 		else if( !strcmp( argv[ i ], "-l" ) ) a.lang = val();
 		else if( !strcmp( argv[ i ], "-o" ) ) a.out = val();
 		else if( !strcmp( argv[ i ], "-id" ) ) a.idFile = val();
@@ -364,8 +400,9 @@ int main( int argc, char** argv )
 				if( id[ k ] != (unsigned char)( k * 7 + 1 ) ) return 2;
 			return ok ? 0 : 1;
 		}
-		else { fprintf( stderr, "usage: whisper-mgpu -n ranks -m model.bin -f audio.wav [-l en] [-o out.txt] [-timeout seconds (rendezvous and collectives)] [-job-timeout seconds (whole job; default none)] [-slots n] [-id id-file] [-job token] [-per-recording -f more.wav ...]\n" ); return 1; }
+		else { fputs( USAGE, stderr ); return 1; }
 	}
+	if( a.splitSilence && a.perRecording ) { fprintf( stderr, "whisper-mgpu: -split silence cuts ONE recording into chunks; -per-recording keeps recordings whole\n%s", USAGE ); return 1; }
 	if( a.model.empty() || a.wav.empty() || a.ranks < 1 ) { fprintf( stderr, "whisper-mgpu: -m and -f are required\n" ); return 1; }
 	if( !a.perRecording && a.wavs.size() > 1 ) { fprintf( stderr, "whisper-mgpu: several -f recordings need -per-recording (the chunk mode shards ONE recording)\n" ); return 1; }
 	if( a.timeout <= 0 ) a.timeout = 300.0;
