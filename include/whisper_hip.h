@@ -60,9 +60,27 @@ WH_API int wh_model_create( const wh_hparams* hp, void* arenaDev, int alreadyFil
 WH_API void wh_model_destroy( wh_model* m );
 /* Upload one tensor of the ggml file by its file name ("encoder.blocks.3.attn.query.weight" ...;
  * name map Whisper/Whisper/WhisperModel.cpp:63-162).  ne[] in ggml order (ne[0] contiguous), nDims 1..3,
- * isF16 = the file's ftype != 0.  `data` is HOST memory, copied synchronously.  Unknown names, wrong shapes and
+ * type = the ggml type of the record: 0 f32, 1 f16 (what this argument meant while it was `isF16`), or a block-quantized type of wh_dequantize below --
+ * 2 q4_0, 3 q4_1, 6 q5_0, 7 q5_1, 8 q8_0 --, whose `data` is count / 32 packed blocks. A quantized matrix is loaded as the FP16 matrix of its dequantized
+ * values: the blocks go to a staging buffer of the model (grown on demand, freed by wh_model_finalize and wh_model_destroy) and are expanded on the device
+ * straight into the arena, which therefore holds the same bytes as after loading an f16 file with those values. Only the plain FP16 matrices -- the linear
+ * layers' weights and the token embedding, ne[0] a multiple of 32 -- may be quantized; on a convolution weight, a positional embedding or a vector, and for
+ * every other type number, the call fails with WH_E_INVALIDARG and names the tensor and the type.
+ * `data` is HOST memory, copied synchronously.  Unknown names, wrong shapes and
  * duplicates are errors, like the reference loader (WhisperModel.cpp:292-297, 331-335). */
-WH_API int wh_model_set_tensor( wh_model* m, const char* name, int nDims, const int32_t* ne, int isF16, const void* data );
+WH_API int wh_model_set_tensor( wh_model* m, const char* name, int nDims, const int32_t* ne, int type, const void* data );
+/* ggml's block-quantized types (quantization version 2) -> FP16, on `stream`: nBlocks packed blocks of 32 elements at srcDev -> 32 nBlocks FP16 values at
+ * dstDev, in order. Extends the reference, which predates quantization. Little endian, no padding between blocks; d, m FP16, qh a u32, q of element j < 16
+ * the low nibble of qs[ j ] and of element j + 16 the high nibble, each with bit j resp. j + 16 of qh as its fifth bit where the type has one:
+ *   type 2 q4_0  18 bytes  d, qs[16]             w = d ( q - 8 )          type 6 q5_0  22 bytes  d, qh, qs[16]       w = d ( q - 16 )
+ *   type 3 q4_1  20 bytes  d, m, qs[16]          w = d q + m              type 7 q5_1  24 bytes  d, m, qh, qs[16]    w = d q + m
+ *   type 8 q8_0  34 bytes  d, int8 qs[32]        w = d qs[ i ]
+ * evaluated as fp16( (float)d * (float)( q - off ) ) resp. fp16( (float)d * (float)q + (float)m ): the product is exact in FP32, the sum is rounded once to
+ * FP32, then to FP16 (round to nearest even). Overflow gives +-inf, a NaN d or m NaN, inf * 0 NaN; FP16 subnormals are read and written as such.
+ * srcDev and dstDev must be 16-byte aligned (a workgroup's 256 blocks are then a whole number of 16-byte loads for every type; nothing outside
+ * [srcDev, srcDev + nBlocks * blockBytes) is read, nothing outside the 64 nBlocks bytes at dstDev written). nBlocks == 0 is success and touches nothing.
+ * WH_E_INVALIDARG, and no launch: any other type, nBlocks < 0 or >= 2^31, a null or misaligned pointer with nBlocks > 0. */
+WH_API int wh_dequantize( void* stream, int type, const void* srcDev, int64_t nBlocks, void* dstDev );
 /* Mel filterbank from the file header, [n_mel][n_fft] FP32 (WhisperModel.cpp:456-470). */
 WH_API int wh_model_set_filters( wh_model* m, int nMel, int nFft, const float* data );
 /* Verifies every expected tensor arrived exactly once (WhisperModel.cpp:331-335) and builds derived data. */

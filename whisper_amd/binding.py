@@ -52,6 +52,7 @@ EXPORTS = [
     "wh_lang_detect", "wh_model_lang_count", "wh_op_lang_probs",
     "wh_resample_out_len", "wh_resample", "wh_resample_host", "wh_resample_host_multi", "wh_resample_taps",
     "wh_vad_frame_count", "wh_vad_features", "wh_vad_features_host",
+    "wh_dequantize",
 ]
 
 
@@ -176,6 +177,7 @@ def lib():
         L.wh_vad_frame_count.argtypes = [i64, C.POINTER(i64)]
         L.wh_vad_features.argtypes = [vp, vp, i64, vp]
         L.wh_vad_features_host.argtypes = [vp, i64, vp]
+        L.wh_dequantize.argtypes = [vp, i32, vp, i64, vp]
         _lib = L
     return _lib
 
@@ -245,6 +247,11 @@ class HipModel:
         filt = np.ascontiguousarray(model.filters, np.float32)
         check(L.wh_model_set_filters(m.handle, filt.shape[0], filt.shape[1], filt.ctypes.data_as(C.c_void_p)))
         for name, a in model.tensors.items():
+            if isinstance(a, gf.QTensor):          # the raw blocks, with their ggml type: dequantized on the device
+                blocks = np.ascontiguousarray(a.blocks, np.uint8)
+                ne = (C.c_int32 * len(a.shape))(*reversed(a.shape))
+                check(L.wh_model_set_tensor(m.handle, name.encode(), len(a.shape), ne, gf.GGML_TYPES[a.qtype], blocks.ctypes.data_as(C.c_void_p)))
+                continue
             a = np.ascontiguousarray(a)
             ne = (C.c_int32 * a.ndim)(*reversed(a.shape))
             check(L.wh_model_set_tensor(m.handle, name.encode(), a.ndim, ne, int(a.dtype == np.float16), a.ctypes.data_as(C.c_void_p)))

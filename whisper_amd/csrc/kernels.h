@@ -429,4 +429,8 @@ namespace wh
 	// mean of the channels. 16 kHz in: conversion and downmix only. The arguments are the caller's to check (wh_resample); the rate's tap table is built on first use.
 	int launchResample( hipStream_t stream, const void* src, int format, int channels, int channel, int inRate, long long nFrames, float* dst,
 		long long dstStride, long long nOut );
+	// dequant.hip: nBlocks 32-element blocks of a ggml quantized type (2 q4_0, 3 q4_1, 6 q5_0, 7 q5_1, 8 q8_0) -> 32 nBlocks FP16 values. src and dst 16-byte aligned;
+	// the arguments are the caller's to check (wh_dequantize, wh_model_set_tensor). dequantBlockBytes: bytes of one block, 0 for any other type.
+	int dequantBlockBytes( int type );
+	int launchDequantize( hipStream_t stream, int type, const void* src, long long nBlocks, void* dst );
 }

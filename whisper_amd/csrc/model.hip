@@ -70,6 +70,13 @@ namespace
 		}
 		return 0;
 	}
+
+	// the staging buffer of quantized tensors (uploadQuantized): nothing is in flight, every upload waits for its kernel
+	void freeStaging( wh_model* m )
+	{
+		if( m->staging.base ) (void)guardedFree( m->staging );
+		m->staging = Allocation{ nullptr, nullptr, 0, nullptr };
+	}
 }	// namespace
 
 int wh::bindDevice( const wh_model* m )
@@ -159,6 +166,7 @@ void wh_model_destroy( wh_model* m )
 {
 	if( !m ) return;
 	(void)bindDevice( m );
+	freeStaging( m );
 	if( m->ownsArena && m->arena ) (void)hipFree( m->arena );
 	delete m;
 }
@@ -167,6 +175,32 @@ static int upload( wh_model* m, int64_t off, const void* src, int64_t bytes )
 {
 	WH_BIND( m );
 	WH_HIP( hipMemcpy( m->arena + off, src, (size_t)bytes, hipMemcpyHostToDevice ) );
+	return 0;
+}
+
+// ggml tensor types a file may hold (the third int of a tensor record). 0 and 1 are what `isF16` used to say.
+enum { GGML_F32 = 0, GGML_F16 = 1 };
+static const char* ggmlTypeName( int type )
+{
+	static const char* const names[] = { "f32", "f16", "q4_0", "q4_1", "q4_2 (removed from ggml)", "q4_3 (removed from ggml)", "q5_0", "q5_1", "q8_0", "q8_1",
+		"q2_k", "q3_k", "q4_k", "q5_k", "q6_k", "q8_k" };
+	return type >= 0 && type < (int)( sizeof( names ) / sizeof( names[ 0 ] ) ) ? names[ type ] : "unknown";
+}
+
+// Quantized blocks of one matrix: host -> the model's staging buffer -> FP16 in the arena (dequant.hip). The staging buffer grows to the largest tensor seen
+// and lives until wh_model_finalize or wh_model_destroy; the call returns when the arena holds the values, like upload().
+static int uploadQuantized( wh_model* m, int64_t off, int type, const void* src, int64_t nBlocks )
+{
+	WH_BIND( m );
+	const int64_t bytes = nBlocks * dequantBlockBytes( type );
+	if( bytes > m->staging.bytes )
+	{
+		freeStaging( m );
+		WH_HIP( guardedAlloc( m->staging, bytes, -1, "quantized tensor staging", nullptr ) );
+	}
+	WH_HIP( hipMemcpy( m->staging.body, src, (size_t)bytes, hipMemcpyHostToDevice ) );
+	WH_CHECK( launchDequantize( nullptr, type, m->staging.body, nBlocks, m->arena + off ) );
+	WH_HIP( hipStreamSynchronize( nullptr ) );
 	return 0;
 }
 
@@ -270,10 +304,18 @@ static bool resolve( const wh_model* m, const std::string& name, Slot& s )
 }
 
 
-int wh_model_set_tensor( wh_model* m, const char* name, int nDims, const int32_t* ne, int isF16, const void* data )
+int wh_model_set_tensor( wh_model* m, const char* name, int nDims, const int32_t* ne, int type, const void* data )
 {
 	if( !m || !name || !ne || !data || nDims < 1 || nDims > 3 ) { setError( "set_tensor: bad argument" ); return WH_E_INVALIDARG; }
 	if( m->finalized ) { setError( "set_tensor: model already finalized" ); return WH_E_INVALIDARG; }
+	const bool quantized = dequantBlockBytes( type ) != 0;
+	if( type != GGML_F32 && type != GGML_F16 && !quantized )
+	{
+		setError( std::string( "tensor '" ) + name + "' has ggml type " + std::to_string( type ) + " (" + ggmlTypeName( type ) +
+			"): supported are f32, f16, q4_0, q4_1, q5_0, q5_1 and q8_0" );
+		return WH_E_INVALIDARG;
+	}
+	const bool isF16 = type == GGML_F16;
 	Slot s;
 	if( !resolve( m, name, s ) )
 	{
@@ -306,7 +348,22 @@ int wh_model_set_tensor( wh_model* m, const char* name, int nDims, const int32_t
 		return WH_E_INVALIDARG;
 	}
 
-	if( s.kind == 1 )
+	if( quantized )
+	{
+		// whisper.cpp's quantizer touches the 2-D *.weight matrices only: the linear layers and the token embedding -- here the plain FP16 matrices of the arena
+		if( s.kind != 0 || !s.f16 || s.rows <= 1 )
+		{
+			setError( std::string( "tensor '" ) + name + "' is stored as " + ggmlTypeName( type ) + ": only the linear layers' weight matrices and the token embedding may be quantized" );
+			return WH_E_INVALIDARG;
+		}
+		if( ( ne[ 0 ] % 32 ) != 0 )
+		{
+			setError( std::string( "tensor '" ) + name + "' is stored as " + ggmlTypeName( type ) + " but its rows of " + std::to_string( ne[ 0 ] ) + " elements are not whole blocks of 32" );
+			return WH_E_INVALIDARG;
+		}
+		WH_CHECK( uploadQuantized( m, s.off, type, data, count / 32 ) );
+	}
+	else if( s.kind == 1 )
 	{
 		// file: [out][in][3] (tap contiguous) -> ours: [out][tap * in + c], row padded with zeros (conv as an implicit GEMM)
 		const int64_t ic = s.convIc, oc = s.rows;
@@ -399,6 +456,7 @@ int wh_model_finalize( wh_model* m )
 		}
 		WH_CHECK( upload( m, m->L.expTab, tab.data(), EXP_TABLE_ENTRIES * 2 ) );
 	}
+	freeStaging( m );
 	m->finalized = true;
 	return 0;
 }

@@ -86,6 +86,7 @@ struct wh_model
 	bool finalized = false;
 	std::set<std::string> loaded;
 	bool filtersSet = false;
+	Allocation staging = { nullptr, nullptr, 0, nullptr };	   // raw blocks of the quantized tensor being loaded; freed by wh_model_finalize / wh_model_destroy
 	int device = 0;	   // the HIP device the arena lives on; every entry point binds the calling thread to it
 	template<class T> T* at( int64_t off ) const { return (T*)( arena + off ); }
 	size_t expectedTensors() const { return 11 + 15 * (size_t)hp.n_audio_layer + 24 * (size_t)hp.n_text_layer; }

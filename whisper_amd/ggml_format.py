@@ -7,7 +7,9 @@ File layout follows the two loaders of the reference, which both consume the sam
 
     u32 magic 0x67676d6c | 11 x i32 hparams | i32 n_mel, i32 n_fft, f32 filters[n_mel][n_fft]
     i32 n_words, n_words x { u32 len, bytes } | repeat { i32 n_dims, i32 name_len, i32 ftype, i32 ne[n_dims],
-    name, payload }  with ne[0] the contiguous dimension and ftype 0 = f32, otherwise f16.
+    name, payload }  with ne[0] the contiguous dimension and the third int of a record a ggml TYPE: 0 f32, 1 f16, or one of the
+    block-quantized types 2 q4_0, 3 q4_1, 6 q5_0, 7 q5_1, 8 q8_0 (32 elements of a row per block: QTensor below). The reference
+    predates quantization; the block layouts are ggml's "quantization version 2", and hparams.f16 of such a file is 2000 + ftype.
 
 numpy arrays are C-ordered, so a ggml tensor with ne = [ne0, ne1, ne2] is a numpy array of shape (ne2, ne1, ne0).
 No real weights exist on this machine (no network), so `synth_model` builds random-weight models of the exact
@@ -16,8 +18,8 @@ real shapes for perf work and small ones for parity tests.
 from __future__ import annotations
 
 import struct
-from dataclasses import dataclass, field, asdict
-from typing import Dict, List, Optional
+from dataclasses import dataclass, field, asdict, replace
+from typing import Dict, List, Optional, Tuple, Union
 
 import numpy as np
 
@@ -74,6 +76,161 @@ def hparams_for(kind: str, n_audio_ctx: int = 1500, n_text_ctx: int = 448) -> HP
     v, d, h, l = MODEL_SHAPES[kind]
     return HParams(n_vocab=v, n_audio_ctx=n_audio_ctx, n_audio_state=d, n_audio_head=h, n_audio_layer=l,
                    n_text_ctx=n_text_ctx, n_text_state=d, n_text_head=h, n_text_layer=l, n_mels=N_MELS.get(kind, 80), f16=1)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# block-quantized tensors (ggml quantization version 2). A block holds 32 consecutive elements of a row, little endian, unpadded:
+#   q4_0 18 bytes  d, qs[16]            w = d (q - 8)         q5_0 22 bytes  d, qh[4], qs[16]        w = d (q - 16)
+#   q4_1 20 bytes  d, m, qs[16]         w = d q + m           q5_1 24 bytes  d, m, qh[4], qs[16]     w = d q + m
+#   q8_0 34 bytes  d, int8 qs[32]       w = d qs[i]
+# d, m are FP16; q of element j < 16 is the low nibble of qs[j], of element j + 16 the high nibble, with bit j resp. j + 16 of the
+# u32 qh as fifth bit where the type has one. The loaders turn such a matrix into the FP16 matrix of its dequantized values.
+# ----------------------------------------------------------------------------------------------------------------------
+QK = 32
+GGML_TYPES = {"q4_0": 2, "q4_1": 3, "q5_0": 6, "q5_1": 7, "q8_0": 8}          # the type of a tensor record
+GGML_FTYPES = {"q4_0": 2, "q4_1": 3, "q8_0": 7, "q5_0": 8, "q5_1": 9}         # the ftype of the header: hparams.f16 = qntvr * 1000 + ftype
+GGML_TYPE_NAMES = {v: k for k, v in GGML_TYPES.items()}
+BLOCK_BYTES = {"q4_0": 18, "q4_1": 20, "q5_0": 22, "q5_1": 24, "q8_0": 34}
+QNT_VERSION = 2
+
+
+@dataclass
+class QTensor:
+    """A block-quantized tensor as the file holds it: `shape` is the numpy shape (last dimension contiguous, a multiple of 32),
+    `blocks` the uint8 payload, prod(shape) / 32 blocks of BLOCK_BYTES[qtype] in element order."""
+    qtype: str
+    shape: Tuple[int, ...]
+    blocks: np.ndarray
+
+    def __post_init__(self):
+        self.shape = tuple(int(v) for v in self.shape)
+        if self.qtype not in GGML_TYPES:
+            raise ValueError("unknown quantized type %r" % (self.qtype,))
+        if not self.shape or self.shape[-1] % QK:
+            raise ValueError("%s: rows of %s elements are not whole blocks of %d" % (self.qtype, self.shape[-1:] or "no", QK))
+        self.blocks = np.ascontiguousarray(self.blocks, dtype=np.uint8).reshape(-1)
+        if self.blocks.size != self.n_blocks * BLOCK_BYTES[self.qtype]:
+            raise ValueError("%s tensor of shape %s needs %d bytes, got %d" % (self.qtype, self.shape, self.n_blocks * BLOCK_BYTES[self.qtype], self.blocks.size))
+
+    @property
+    def n_blocks(self) -> int:
+        return int(np.prod(self.shape)) // QK
+
+
+def _block_fields(qt: QTensor):
+    """d, m (float32 [n] or None), q (int32 [n][32], the offset not yet taken)"""
+    b = qt.blocks.reshape(qt.n_blocks, BLOCK_BYTES[qt.qtype])
+    half = lambda col: np.ascontiguousarray(b[:, col:col + 2]).view("<f2").reshape(-1).astype(np.float32)
+    d = half(0)
+    t = qt.qtype
+    if t == "q8_0":
+        return d, None, b[:, 2:34].view(np.int8).astype(np.int32)
+    m = half(2) if t in ("q4_1", "q5_1") else None
+    pos = 2 + (2 if m is not None else 0)
+    fifth = 0
+    if t in ("q5_0", "q5_1"):
+        qh = b[:, pos:pos + 4].astype(np.uint32)
+        qh = qh[:, 0] | (qh[:, 1] << 8) | (qh[:, 2] << 16) | (qh[:, 3] << 24)
+        fifth = (((qh[:, None] >> np.arange(32, dtype=np.uint32)[None, :]) & 1) << 4).astype(np.int32)
+        pos += 4
+    qs = b[:, pos:pos + 16].astype(np.int32)
+    return d, m, np.concatenate([qs & 15, qs >> 4], axis=1) | fifth
+
+
+def dequantize(qt: QTensor) -> np.ndarray:
+    """float32 (float)d * (float)(q - off) resp. (float)d * (float)q + (float)m: the product is exact, the sum rounded once"""
+    d, m, q = _block_fields(qt)
+    off = {"q4_0": 8, "q5_0": 16}.get(qt.qtype, 0)
+    with np.errstate(invalid="ignore", over="ignore"):
+        w = d[:, None] * (q - off).astype(np.float32)
+        if m is not None:
+            w = w + m[:, None]
+    return w.astype(np.float32).reshape(qt.shape)
+
+
+def dequantize_f16(qt: QTensor) -> np.ndarray:
+    """What a loader puts in place of the tensor: dequantize() rounded to FP16 (nearest even; overflow gives inf)"""
+    with np.errstate(over="ignore"):
+        return dequantize(qt).astype(np.float16)
+
+
+def quantize(a: np.ndarray, qtype: str) -> QTensor:
+    """ggml's reference row quantizers, in float32 like theirs: d is stored as FP16, its inverse is taken from the float32 value.
+      q4_0 / q5_0   d = max / -8 resp. -16 with max the signed value of largest magnitude (the first of equals), q = min(15 resp. 31, int(x / d + 8.5 resp. 16.5))
+      q4_1 / q5_1   d = (max - min) / 15 resp. 31, m = min, q = int((x - m) / d + 0.5)
+      q8_0          d = amax / 127, q = round(x / d), halves away from zero"""
+    if qtype not in GGML_TYPES:
+        raise ValueError("unknown quantized type %r" % (qtype,))
+    a = np.asarray(a)
+    if a.ndim < 1 or a.shape[-1] % QK:
+        raise ValueError("%s: rows of %s elements are not whole blocks of %d" % (qtype, a.shape[-1:], QK))
+    x = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, QK)
+    n = x.shape[0]
+    one = np.float32(1.0)
+
+    def inverse(d):
+        with np.errstate(divide="ignore"):
+            return np.where(d != 0, one / d, np.float32(0)).astype(np.float32)
+
+    out = np.zeros((n, BLOCK_BYTES[qtype]), np.uint8)
+    f16 = lambda v: v.astype("<f2").view(np.uint8).reshape(n, 2)
+    with np.errstate(over="ignore", invalid="ignore"):
+        if qtype == "q8_0":
+            d = (np.abs(x).max(axis=1) / np.float32(127)).astype(np.float32)
+            v = x * inverse(d)[:, None]
+            q = np.where(v >= 0, np.floor(v + np.float32(0.5)), np.ceil(v - np.float32(0.5))).astype(np.int8)       # roundf
+            out[:, 0:2] = f16(d)
+            out[:, 2:34] = q.view(np.uint8)
+            return QTensor(qtype, a.shape, out)
+        levels = 15 if qtype in ("q4_0", "q4_1") else 31
+        if qtype in ("q4_0", "q5_0"):
+            big = x[np.arange(n), np.abs(x).argmax(axis=1)]
+            d = (big / np.float32(-(levels + 1) // 2)).astype(np.float32)
+            v = x * inverse(d)[:, None] + np.float32((levels + 1) // 2 + 0.5)
+            head = [f16(d)]
+        else:
+            lo, hi = x.min(axis=1), x.max(axis=1)
+            d = ((hi - lo) / np.float32(levels)).astype(np.float32)
+            v = (x - lo[:, None]) * inverse(d)[:, None] + np.float32(0.5)
+            head = [f16(d), f16(lo)]
+        q = np.minimum(levels, v.astype(np.int32)).astype(np.uint32)           # truncation, like the C cast
+    pos = 0
+    for h in head:
+        out[:, pos:pos + 2] = h
+        pos += 2
+    if levels == 31:
+        qh = (((q >> 4) & 1) << np.arange(32, dtype=np.uint32)[None, :]).sum(axis=1, dtype=np.uint32)
+        out[:, pos:pos + 4] = qh.astype("<u4").view(np.uint8).reshape(n, 4)
+        pos += 4
+    out[:, pos:pos + 16] = ((q[:, :16] & 15) | ((q[:, 16:] & 15) << 4)).astype(np.uint8)
+    return QTensor(qtype, a.shape, out)
+
+
+def is_quantizable(name: str, a) -> bool:
+    """What whisper.cpp's quantizer touches: the 2-D `*.weight` matrices, i.e. the linear layers and the token embedding (the
+    convolution weights are 3-D; positional embeddings, biases and LayerNorm vectors stay as they are)."""
+    return name.endswith(".weight") and len(a.shape) == 2 and a.shape[0] > 1 and a.shape[-1] % QK == 0
+
+
+def quantize_model(model: "GgmlModel", qtype: str) -> "GgmlModel":
+    """The model with exactly those matrices quantized and hparams.f16 = 2000 + ftype; everything else is shared with `model`."""
+    tensors = {}
+    for name, a in model.tensors.items():
+        if isinstance(a, QTensor):
+            raise ValueError("tensor '%s' is quantized already" % name)
+        tensors[name] = quantize(a.astype(np.float32), qtype) if is_quantizable(name, a) else a
+    return GgmlModel(replace(model.hparams, f16=QNT_VERSION * 1000 + GGML_FTYPES[qtype]), model.filters, model.vocab, tensors)
+
+
+def dequantized_twin(model: "GgmlModel") -> "GgmlModel":
+    """The F16 model that loads to the same arena, byte for byte: every quantized matrix replaced by its dequantize_f16()"""
+    tensors = {name: dequantize_f16(a) if isinstance(a, QTensor) else a for name, a in model.tensors.items()}
+    return GgmlModel(replace(model.hparams, f16=1), model.filters, model.vocab, tensors)
+
+
+def split_ftype(f16: int) -> Tuple[int, int]:
+    """hparams.f16 of the header -> (quantization version, ftype)"""
+    return int(f16) // 1000, int(f16) % 1000
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -166,7 +323,7 @@ class GgmlModel:
     hparams: HParams
     filters: np.ndarray                     # [n_mel][n_fft] float32
     vocab: List[bytes]                      # the n_words strings stored in the file
-    tensors: Dict[str, np.ndarray] = field(default_factory=dict)
+    tensors: Dict[str, Union[np.ndarray, "QTensor"]] = field(default_factory=dict)
 
 
 def default_vocab_words(hp: HParams) -> List[bytes]:
@@ -225,6 +382,14 @@ def write_model(path: str, model: GgmlModel) -> int:
         for name, shape, is_f16 in tensor_specs(hp):
             a = model.tensors[name]
             assert tuple(a.shape) == tuple(shape), (name, a.shape, shape)
+            if isinstance(a, QTensor):
+                ne = list(reversed(a.shape))
+                nm = name.encode()
+                f.write(struct.pack("<3i", len(ne), len(nm), GGML_TYPES[a.qtype]))
+                f.write(struct.pack("<%di" % len(ne), *ne))
+                f.write(nm)
+                f.write(a.blocks.tobytes())
+                continue
             a = np.ascontiguousarray(a, dtype=np.float16 if is_f16 else np.float32)
             ne = list(reversed(a.shape))
             nm = name.encode()
@@ -261,15 +426,31 @@ def read_model(path: str, load_tensors: bool = True) -> GgmlModel:
         off += ln
     tensors: Dict[str, np.ndarray] = {}
     while off < len(data):
-        n_dims, name_len, ftype = take("<3i")
+        n_dims, name_len, ttype = take("<3i")
         ne = take("<%di" % n_dims)
         name = bytes(data[off:off + name_len]).decode()
         off += name_len
-        count = int(np.prod(ne))
-        dt = "<f4" if ftype == 0 else "<f2"
+        count = int(np.prod(ne, dtype=np.int64))
+        if ttype in GGML_TYPE_NAMES:
+            qtype = GGML_TYPE_NAMES[ttype]
+            if split_ftype(hp.f16)[0] != QNT_VERSION:
+                raise ValueError("tensor '%s' is %s but the file's quantization version is %d: only version %d block layouts are read" %
+                                 (name, qtype, split_ftype(hp.f16)[0], QNT_VERSION))
+            if ne[0] % QK:
+                raise ValueError("tensor '%s' is %s but its rows of %d elements are not whole blocks of %d" % (name, qtype, ne[0], QK))
+            size = count // QK * BLOCK_BYTES[qtype]
+            if off + size > len(data):
+                raise ValueError("file is truncated inside tensor '%s'" % name)
+            if load_tensors:
+                tensors[name] = QTensor(qtype, tuple(reversed(ne)), np.frombuffer(data, dtype=np.uint8, count=size, offset=off).copy())
+            off += size
+            continue
+        if ttype not in (0, 1):
+            raise ValueError("tensor '%s' has ggml type %d: supported are 0 f32, 1 f16, 2 q4_0, 3 q4_1, 6 q5_0, 7 q5_1, 8 q8_0" % (name, ttype))
+        dt = "<f4" if ttype == 0 else "<f2"
         if load_tensors:
             tensors[name] = np.frombuffer(data, dtype=dt, count=count, offset=off).reshape(tuple(reversed(ne))).copy()
-        off += count * (4 if ftype == 0 else 2)
+        off += count * (4 if ttype == 0 else 2)
     return GgmlModel(hp, filt, vocab, tensors)
 
 

@@ -1,5 +1,6 @@
 // Logger, language table, vocabulary and the ggml file loader of libWhisper.so.
 #include "hostCommon.h"
+#include "ggmlTensor.h"
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -366,20 +367,39 @@ namespace Whisper
 			std::vector<char> payload;
 			while( true )
 			{
-				int32_t nDims = 0, nameLen = 0, ftype = 0;
+				int32_t nDims = 0, nameLen = 0, type = 0;
 				if( !rd( f, nDims ) ) break;	// clean end of file
-				if( !rd( f, nameLen ) || !rd( f, ftype ) || nDims < 1 || nDims > 3 || nameLen <= 0 || nameLen > 256 ) return E_INVALIDARG;
-				int32_t ne[ 3 ] = { 1, 1, 1 };
-				int64_t count = 1;
-				for( int i = 0; i < nDims; i++ )
+				if( !rd( f, nameLen ) || !rd( f, type ) || nDims < 1 || nDims > 3 || nameLen <= 0 || nameLen > 256 )
 				{
-					if( !rd( f, ne[ i ] ) || ne[ i ] <= 0 ) return E_INVALIDARG;
-					count *= ne[ i ];
+					logError( "model file '%s': a tensor record with %d dimensions and a name of %d bytes (truncated, or not a ggml model)", path.c_str(), nDims, nameLen );
+					return E_INVALIDARG;
 				}
+				int32_t ne[ 3 ] = { 1, 1, 1 };
+				for( int i = 0; i < nDims; i++ )
+					if( !rd( f, ne[ i ] ) )
+					{
+						logError( "model file '%s' is truncated inside a tensor record", path.c_str() );
+						return E_INVALIDARG;
+					}
 				std::string name( (size_t)nameLen, '\0' );
 				f.read( &name[ 0 ], nameLen );
-				const int64_t bytes = count * ( ftype == 0 ? 4 : 2 );
-				if( !f || bytes > fileSize ) return E_INVALIDARG;
+				if( !f )
+				{
+					logError( "model file '%s' is truncated inside a tensor's name", path.c_str() );
+					return E_INVALIDARG;
+				}
+				int64_t count = 0, bytes = 0;
+				std::string why;
+				if( !ggml::payloadBytes( type, nDims, ne, lm->hp.f16, count, bytes, why ) )
+				{
+					logError( "model file '%s', tensor '%s': %s", path.c_str(), name.c_str(), why.c_str() );
+					return E_INVALIDARG;
+				}
+				if( bytes > fileSize - (int64_t)f.tellg() )
+				{
+					logError( "model file '%s' is truncated inside tensor '%s' (%s, %lld bytes)", path.c_str(), name.c_str(), ggml::typeName( type ), (long long)bytes );
+					return E_INVALIDARG;
+				}
 				payload.resize( (size_t)bytes );
 				f.read( payload.data(), bytes );
 				if( !f )
@@ -387,7 +407,7 @@ namespace Whisper
 					logError( "model file '%s' is truncated inside tensor '%s'", path.c_str(), name.c_str() );
 					return E_INVALIDARG;
 				}
-				CHECK_WH( wh_model_set_tensor( lm->gpu, name.c_str(), nDims, ne, ftype != 0, payload.data() ) );
+				CHECK_WH( wh_model_set_tensor( lm->gpu, name.c_str(), nDims, ne, type, payload.data() ) );
 				if( callbacks )
 				{
 					if( callbacks->cancel && S_OK != callbacks->cancel( callbacks->pv ) ) return (HRESULT)0x800704C7;	 // ERROR_CANCELLED
@@ -426,6 +446,7 @@ namespace Whisper
 		}
 		else if( FAILED( hrRead ) )
 			return hrRead;
+		logInfo( "loaded model '%s': %s", path.c_str(), ggml::describeFileType( lm->hp.f16 ).c_str() );
 		out = lm;
 		return S_OK;
 	}
