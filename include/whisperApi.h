@@ -174,6 +174,12 @@ namespace Whisper
 	{
 		Translate = 1, NoContext = 2, SingleSegment = 4, PrintSpecial = 8, PrintProgress = 0x10, PrintRealtime = 0x20,
 		PrintTimestamps = 0x40, TokenTimestamps = 0x100, SpeedupAudio = 0x200,
+		// Extension (the bit is free in the reference's enum): token times from the decoder's cross-attention by dynamic time warping instead of the
+		// TokenTimestamps heuristic (DESIGN.md "Token alignment"). Text tokens get t0 / t1 from the window's warping path, timestamp tokens their own time,
+		// other special tokens the end of the token before them; vlen is what TokenTimestamps puts there, max_len wraps as under TokenTimestamps, and with
+		// both flags set these times win. Needs no PCM: runStreamed takes it too. Greedy decoding of one stream only: beam search and iBatchRunner::run
+		// answer E_NOTIMPL.
+		AlignTokens = 0x1000,
 	};
 	inline eFullParamsFlags operator|( eFullParamsFlags a, eFullParamsFlags b ) { return (eFullParamsFlags)( (uint32_t)a | (uint32_t)b ); }
 
@@ -346,6 +352,10 @@ namespace Whisper
 	WHISPER_EXPORT HRESULT createBatchRunner( iModel* model, const sBatchSetup* setup, iBatchRunner** pp );
 	WHISPER_EXPORT HRESULT runFullBatch( iModel* model, const sFullParams& params, const sBatchStream* streams, uint32_t count, const sBatchSetup* setup,
 		iTranscribeResult** results, HRESULT* perStream );
+	// The decoder heads whose cross-attention weights the AlignTokens flag averages, for every context of the model: `count` (layer, head) pairs, used in
+	// ascending (layer, head) order. count == 0 restores the default, every head of the upper half of the decoder's layers (what openai-whisper takes for a
+	// model that names none). A free function: iModel's vtable is the reference's. E_INVALIDARG for a pair outside the model or a model of another library.
+	WHISPER_EXPORT HRESULT setAlignmentHeads( iModel* model, const int32_t* layerHeadPairs, uint32_t count );
 	// Extension (no counterpart in whisper.def): ONE long recording onto the batched path. The buffer is cut into pieces of at most maxLen samples at pauses,
 	// found with the reference's voice-activity detector (Whisper/Whisper/voiceActivityDetection.cpp, which its capture loop uses to fire a transcription when
 	// the speaker pauses): the per-frame features come from the device (wh_vad_features of whisper_hip.h, on the calling thread's current device), the decision

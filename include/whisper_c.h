@@ -66,6 +66,9 @@ int32_t whisperc_load_audio( const char* pathUtf8, int32_t stereo, float* dst, i
 /* whisperc_run_full + the token-timestamp fields of sFullParams (set TokenTimestamps = 0x100 in flags): thold_pt, thold_ptsum, max_len */
 int32_t whisperc_run_full_tt( void* ctx, const float* pcm, uint32_t nSamples, const char* language, uint32_t flags, int maxTokens,
 	const int32_t* promptTokens, int nPrompt, int nMaxTextCtx, float tholdPt, float tholdPtsum, int maxLen );
+/* Whisper::setAlignmentHeads: the (layer, head) pairs whose cross-attention weights the AlignTokens flag (0x1000 in flags: token times by dynamic time
+ * warping; through whisperc_run_full, _range, _audio_ctx, _tt for max_len, and whisperc_run_streamed) averages; count 0 restores the default heads */
+int32_t whisperc_model_set_alignment_heads( void* model, const int32_t* layerHeadPairs, int32_t count );
 /* iContext::getResults( Tokens | Timestamps ) + iTranscribeResult::getSize / getSegments / getTokens; times in 100 ns ticks */
 int32_t whisperc_result_counts( void* ctx, uint32_t* segments, uint32_t* tokens );
 int32_t whisperc_result_segment( void* ctx, uint32_t index, uint64_t* t0, uint64_t* t1, uint32_t* firstToken, uint32_t* countTokens,

@@ -302,6 +302,27 @@ WH_API int wh_lang_detect( wh_context* c, int batch, float* langP, int32_t* best
 /* Language tokens of the model's vocabulary: n_vocab - 51766 (99 at 51865, 100 at the large-v3 shape), 0 for .en models. */
 WH_API int wh_model_lang_count( const wh_model* m );
 
+/* Token alignment: word-level timestamps from the decoder's cross-attention by dynamic time warping, as openai-whisper's word_timestamps and
+ * whisper.cpp's --dtw do it (an extension: the reference has the TokenTimestamps heuristic only). The definition is DESIGN.md "Token alignment",
+ * restated in numpy by tests/align_ref.py.
+ *   wh_model_set_alignment_heads: the heads whose weights are averaged, `count` (layer, head) pairs; they are used in ascending (layer, head) order and a
+ *     pair named twice counts once. count == 0 restores the default: every head of decoder layers n_text_layer / 2 .. n_text_layer - 1.
+ *   wh_align_tokens: after wh_encode / wh_encode_windows of at least `batch` windows and after their decoding is over (the call overwrites the sequences' self-
+ *     attention caches, decoder activations, logits and probabilities). tokens: HOST [batch][nMax], row b = the lens[ b ] tokens
+ *     [sot sequence, no-timestamps token, text ..., eot] followed by padding (ignored); the text begins behind the row's first no-timestamps token, at least one
+ *     text token, 3 <= lens[ b ] <= nMax <= min( 256, n_text_ctx ). nKeys: HOST [batch], the keys (audio positions of 20 ms) of window b that take part,
+ *     1 .. the context's audio context. One teacher-forced pass of the multi-token decoder graph at position 0, ended behind the cross-attention query of the
+ *     last selected layer (the debug captures of WH_FLAG_DEBUG_CAPTURE are left as the last wh_decode made them); the matrix and the DTW run on the device and only the frames come back:
+ *     framesHost: HOST [batch][nMax], row b = for each text token and then the eot row the smallest key index of the warping path inside its row
+ *     (lens[ b ] - 1 - p numbers, p = the index of the no-timestamps token), then -1. Frames of a row never decrease.
+ *     The matrix and DTW kernels give a window the same bits whatever the batch, its place in it and nMax; the pass before them is the decoder's own, which
+ *     picks its product kernels by the total number of rows, so a window's FP16 query rows may move in their last bits with the batch. Greedy contexts only: WH_E_INVALIDARG on a
+ *     hypothesis-group context and under WH_FLAG_PARITY_EXACT. Buffers are allocated by the first call; contexts that never call it pay nothing.
+ * wh_debug_read: "align-matrix" = the last call's M, [batch][nMax][audio context] (zero outside a window's rows and keys); "align-q" = the FP16 cross-attention
+ *     query rows of `layer` (one of the selected heads' layers) as that pass formed them, [batch * nMax][d]. */
+WH_API int wh_model_set_alignment_heads( wh_model* m, const int32_t* layerHeadPairs, int count );
+WH_API int wh_align_tokens( wh_context* c, int batch, const int32_t* tokens, const int32_t* lens, const int32_t* nKeys, int nMax, int32_t* framesHost );
+
 /* sTokenData of the reference (Whisper/Whisper/sTokenData.h): the result of ContextImpl::sampleBest. */
 typedef struct wh_token_data
 {
@@ -509,6 +530,25 @@ WH_API int wh_op_beam_candidates( void* stream, const float* probs, int rows, in
  * Every parents[ j ] MUST lie in [0, sequences): the device reads them as they are. Bad sizes: WH_E_INVALIDARG. */
 WH_API int wh_op_reorder_self_cache( void* stream, void* cacheK, void* cacheV, void* scratchK, void* scratchV, const int32_t* parents,
 	const int32_t* rowsDev, int layers, int sequences, int maxSeq, int heads, int keyStride, int group );
+
+
+/* ---- op-level entry points of token alignment (the kernels of wh_align_tokens). Device pointers. ---- */
+
+/* The alignment matrix of `windows` windows. q: FP16 [layer - qLayer0][window][nMax][heads*64] (layers qLayerStride elements apart), the cross-attention query
+ * rows, already scaled; kCache: FP16 [layer][window][heads][keyStride][64] (layers kLayerStride elements apart). headPairsDev: DEVICE int32 [nHeads][2] =
+ * (layer, head), layer in [qLayer0, nLayers), in the order the heads are summed; rowsDev / keysDev: DEVICE int32 [windows], the rows (<= nMax <= 256) and keys
+ * (<= min( keyMax, keyStride )) of each window. Per head: S = q k^T in FP32 on the matrix cores, softmax over the keys with FP32 exp, (P - mean) / std over the
+ * window's rows per key column (FP64 sums in row order; std == 0 gives 0), median of 7 along the keys with reflect padding (none at 3 keys or fewer);
+ * mDev: FP32 [windows][nMax][keyMax] = the mean over the heads, 0 outside a window's rows and keys. statsDev: scratch, FP32 [windows][nHeads][nMax][2].
+ * No atomics and fixed summation orders: a window's bits do not depend on windows, its index or nMax. Indices read from device memory are clamped into the buffers. */
+WH_API int wh_op_align_matrix( void* stream, const void* qF16, int64_t qLayerStride, int qLayer0, const void* kCache, int64_t kLayerStride, int nLayers, int heads,
+	int keyStride, const int32_t* headPairsDev, int nHeads, const int32_t* rowsDev, const int32_t* keysDev, int windows, int nMax, int keyMax, float* statsDev, float* mDev );
+/* Dynamic time warping in FP32, one workgroup per window. xDev: FP32 [windows][rowMax][keyMax] costs; rowsDev / keysDev: DEVICE int32 [windows], R <= rowMax <= 256 and
+ * nKeys <= keyMax of each window, rowMax * ceil( keyMax / 16 ) * 4 <= 150 KB (the packed trace lives in LDS). cost[0][0] = 0, +inf elsewhere on the border;
+ * cost[i][j] = x[i-1][j-1] + min( c0 = cost[i-1][j-1], c1 = cost[i-1][j], c2 = cost[i][j-1] ); trace 0 when c0 < c1 && c0 < c2, else 1 when c1 < c0 && c1 < c2, else 2;
+ * row 0 of the trace is 2, column 0 is 1; walked back from ( R, nKeys ). framesDev: int32 [windows][rowMax], the smallest key index of the path inside each row
+ * (a path cell in column 0 of the table counts as key 0), -1 for rows >= R; a window with R == 0 or nKeys == 0 is all -1. */
+WH_API int wh_op_dtw( void* stream, const float* xDev, int windows, int rowMax, int keyMax, const int32_t* rowsDev, const int32_t* keysDev, int32_t* framesDev );
 
 #ifdef __cplusplus
 }

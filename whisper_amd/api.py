@@ -17,10 +17,11 @@ HOST_LIB_PATH = os.path.join(_HERE, "lib", "libWhisper.so")
 # eFullParamsFlags (Whisper/API/sFullParams.h:21-35)
 TRANSLATE, NO_CONTEXT, SINGLE_SEGMENT, PRINT_SPECIAL = 1, 2, 4, 8
 TOKEN_TIMESTAMPS = 0x100
+ALIGN_TOKENS = 0x1000      # extension: token times from the decoder's cross-attention by dynamic time warping (greedy runs of one stream)
 
 CPP_EXPORTS = ["setupLogger", "loadModel", "initMediaFoundation", "findLanguageKeyW", "findLanguageKeyA", "getSupportedLanguages", "listGPUs"]
 # extensions next to the seven names of whisper.def: one process per GPU, and K streams in lock step on one GPU
-CPP_EXTENSIONS = ["loadModelShared", "createBatchRunner", "runFullBatch", "splitAtPauses"]
+CPP_EXTENSIONS = ["loadModelShared", "createBatchRunner", "runFullBatch", "splitAtPauses", "setAlignmentHeads"]
 
 _lib = None
 
@@ -73,6 +74,7 @@ def lib():
         L.whisperc_language_code.argtypes = [C.c_int32, C.c_char_p]
         L.whisperc_tr_language.argtypes = [vp, C.c_char_p, C.POINTER(C.c_float)]
         L.whisperc_debug_context_flags.argtypes = [vp, C.c_uint32, C.c_int32]
+        L.whisperc_model_set_alignment_heads.argtypes = [vp, vp, C.c_int32]
         L.whisperc_resample.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64)]
         L.whisperc_load_audio.argtypes = [C.c_char_p, C.c_int32, vp, C.c_int64, C.POINTER(C.c_int64)]
         L.whisperc_run_full_stereo.argtypes = [vp, vp, vp, C.c_uint32, C.c_char_p, C.c_uint32, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]
@@ -267,6 +269,12 @@ class Model:
     def is_multilingual(self) -> bool:
         return lib().whisperc_is_multilingual(self.h) == 0
 
+    def set_alignment_heads(self, pairs: Sequence[Sequence[int]]):
+        """Whisper::setAlignmentHeads: the (layer, head) pairs whose cross-attention weights ALIGN_TOKENS averages; [] restores the default (every head of
+        the upper half of the decoder's layers)."""
+        a = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        _check(lib().whisperc_model_set_alignment_heads(self.h, a.ctypes.data_as(C.c_void_p) if len(a) else None, len(a)), "setAlignmentHeads")
+
     def tokenize(self, text: str) -> List[int]:
         buf = (C.c_int32 * 4096)()
         n = _check(lib().whisperc_tokenize(self.h, text.encode(), buf, 4096), "tokenize")
@@ -299,6 +307,8 @@ class Context:
         """runFull on mono float32 16 kHz PCM (another sample_rate: PCM of any dtype resample() takes, resampled on the GPU first). Returns the HRESULT (0 = S_OK, 1 = S_FALSE: less than 1 s of audio). language "auto" (or ""): detected
         on the window at frame 0, whatever the run's offset (detected_language tells which).
         With TOKEN_TIMESTAMPS in flags the tokens of results() carry t0 / t1 / vlen and max_len > 0 wraps the segments.
+        With ALIGN_TOKENS the token times come from the decoder's cross-attention by dynamic time warping instead (Model.set_alignment_heads chooses the heads);
+        with both flags those times win. Not with beam_width (E_NOTIMPL).
         stereo: the recording's two channels, [n, 2] at the same sample_rate (what iAudioBuffer::getPcmStereo returns): speakers() then tells which channel
         is louder during each segment. Combines with offset_ms / duration_ms; not with beam_width, audio_ctx or TOKEN_TIMESTAMPS through this face."""
         pcm = _at_16k(pcm, sample_rate)
@@ -319,7 +329,7 @@ class Context:
         if beam_width > 0:          # eSamplingStrategy::BeamSearch with this beam_width (extension: the reference only declares it)
             return _check(lib().whisperc_run_full_beam(self.h, pcm.ctypes.data_as(C.c_void_p), len(pcm), language.encode(), flags, max_tokens,
                                                        pt.ctypes.data_as(C.c_void_p) if len(pt) else None, len(pt), n_max_text_ctx, beam_width), "runFull")
-        if flags & TOKEN_TIMESTAMPS:
+        if flags & (TOKEN_TIMESTAMPS | ALIGN_TOKENS):
             return _check(lib().whisperc_run_full_tt(self.h, pcm.ctypes.data_as(C.c_void_p), len(pcm), language.encode(), flags, max_tokens,
                                                      pt.ctypes.data_as(C.c_void_p) if len(pt) else None, len(pt), n_max_text_ctx,
                                                      thold_pt, thold_ptsum, max_len), "runFull")

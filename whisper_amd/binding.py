@@ -53,6 +53,7 @@ EXPORTS = [
     "wh_resample_out_len", "wh_resample", "wh_resample_host", "wh_resample_host_multi", "wh_resample_taps",
     "wh_vad_frame_count", "wh_vad_features", "wh_vad_features_host",
     "wh_dequantize",
+    "wh_model_set_alignment_heads", "wh_align_tokens", "wh_op_align_matrix", "wh_op_dtw",
 ]
 
 
@@ -178,6 +179,10 @@ def lib():
         L.wh_vad_features.argtypes = [vp, vp, i64, vp]
         L.wh_vad_features_host.argtypes = [vp, i64, vp]
         L.wh_dequantize.argtypes = [vp, i32, vp, i64, vp]
+        L.wh_model_set_alignment_heads.argtypes = [vp, vp, i32]
+        L.wh_align_tokens.argtypes = [vp, i32, vp, vp, vp, i32, vp]
+        L.wh_op_align_matrix.argtypes = [vp, vp, i64, i32, vp, i64, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, vp, vp]
+        L.wh_op_dtw.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -268,6 +273,11 @@ class HipModel:
         if n < 0:
             check(n)
         return n
+
+    def set_alignment_heads(self, pairs):
+        """The (layer, head) pairs whose cross-attention weights wh_align_tokens averages; an empty list restores the default (the upper half of the decoder)."""
+        a = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        check(lib().wh_model_set_alignment_heads(self.handle, a.ctypes.data_as(C.c_void_p) if len(a) else None, len(a)))
 
     def arena(self):
         p = C.c_void_p()
@@ -415,6 +425,21 @@ class HipContext:
         check(lib().wh_lang_detect(self.handle, b, p.ctypes.data_as(C.c_void_p), best.ctypes.data_as(C.c_void_p)))
         return p, best
 
+    def align_tokens(self, rows, n_keys, n_max: Optional[int] = None):
+        """rows: per window the tokens [sot sequence, no-timestamps, text..., eot] of a decoded window; n_keys: per window the audio positions that take part.
+        Returns frames [batch][n_max] int32: per text token and the eot row the smallest key index of the DTW path, then -1."""
+        lens = np.asarray([len(r) for r in rows], np.int32)
+        n_max = int(lens.max()) if n_max is None else n_max
+        t = np.zeros((len(rows), n_max), np.int32)
+        for b, r in enumerate(rows):
+            t[b, :len(r)] = r
+        keys = np.ascontiguousarray(n_keys, np.int32)
+        frames = np.empty((len(rows), n_max), np.int32)
+        check(lib().wh_align_tokens(self.handle, len(rows), t.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), keys.ctypes.data_as(C.c_void_p), n_max,
+                                    frames.ctypes.data_as(C.c_void_p)))
+        self._align = (len(rows), n_max)
+        return frames
+
     def sample_best(self, batch: int, force_timestamp: bool = False, is_initial: bool = False):
         out = (TokenDataC * batch)()
         check(lib().wh_sample_best(self.handle, batch, int(force_timestamp), int(is_initial), out))
@@ -560,6 +585,7 @@ class HipContext:
     def set_audio_ctx(self, audio_ctx: int):
         """sFullParams::audio_ctx: encoder positions / cross-attention keys per window (0 = the model's n_audio_ctx)."""
         check(lib().wh_context_set_audio_ctx(self.handle, audio_ctx))
+        self._audio_ctx = audio_ctx
 
     def set_flags(self, flags: int, parity_threads: int = 1):
         check(lib().wh_context_set_flags(self.handle, flags, parity_threads))
@@ -596,6 +622,13 @@ class HipContext:
             shape = (b, 2 * self.hp.n_audio_ctx, d) if what == "exact:conv1" else (b, self.hp.n_audio_ctx, d * mult)
             out = np.empty(shape, np.float32)
             check(lib().wh_debug_read(self.handle, what.encode(), 0, 0, out.ctypes.data_as(C.c_void_p), out.size))
+            return out
+        if what in ("align-matrix", "align-q"):
+            ab, an = getattr(self, "_align", (0, 0))          # the last align_tokens call; none yet: the library answers WH_E_NOT_READY
+            keys = getattr(self, "_audio_ctx", 0) or self.hp.n_audio_ctx          # the matrix is as wide as the context's audio context
+            shape = (ab, an, keys) if what == "align-matrix" else (ab, an, d)
+            out = np.empty(shape, np.float32)
+            check(lib().wh_debug_read(self.handle, what.encode(), layer, 0, out.ctypes.data_as(C.c_void_p), out.size))
             return out
         if what in ("logits", "probs"):
             shape = (rows, self.hp.n_vocab)         # rows = sequences of the last decode step

@@ -129,7 +129,7 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 				a.causal = 1; a.nPast = nPast; a.parityThreads = 0; a.nPastDev = nPastDev;
 				if( devState ) a.nKeys = hp.n_text_ctx;
 				WH_CHECK( attnDecP( c, a, devState ? c->profKeysHint : -1 ) );
-				if( il == 0 && !devState )
+				if( il == 0 && !devState && !c->alignHook )
 				{
 					WH_CHECK( capture( c, c->capDecKqvSelf, c->dattn, (int64_t)M * d, (int64_t)c->maxRows * d ) );	 // "dec-KQV" (self)
 					c->capDecRows = M;
@@ -215,7 +215,7 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 			const double bytes = 2.0 * 3.0 * d * d + 4.0 * M * d + 2.0 * 2.0 * M * ( keys - 1 ) * d + 2.0 * 2.0 * M * d + 2.0 * M * d;
 			const double flops = 2.0 * M * 3.0 * d * d + 4.0 * M * keys * d;
 			WH_CHECK( profiled( c, KC_SELF_BLOCK, flops, bytes, [ & ]() { return launchSelfBlockDec( a, st ); } ) );
-			if( il == 0 && !devState )
+			if( il == 0 && !devState && !c->alignHook )
 			{
 				WH_CHECK( capture( c, c->capDecKqvSelf, c->dattn, (int64_t)M * d, (int64_t)c->maxRows * d ) );	 // "dec-KQV" (self)
 				c->capDecRows = M;
@@ -240,7 +240,7 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 			a.causal = 1; a.nPast = nPast; a.parityThreads = parity; a.nPastDev = nPastDev;
 			if( devState ) a.nKeys = hp.n_text_ctx;	  // upper bound for the argument check; the kernel reads the real value
 			WH_CHECK( attnDecP( c, a, devState ? c->profKeysHint : -1 ) );
-			if( il == 0 && !devState )
+			if( il == 0 && !devState && !c->alignHook )
 			{
 				WH_CHECK( capture( c, c->capDecKqvSelf, c->dattn, (int64_t)M * d, (int64_t)c->maxRows * d ) );	 // "dec-KQV" (self)
 				c->capDecRows = M;
@@ -259,6 +259,13 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 			GemmArgs g = plainGemm( c->dxn, m->at<f16>( e.wcq ), M, d, d );
 			g.epi = EPI_Q_DEC; g.bias = m->at<float>( e.bcq ); g.scale = kqScale; g.q = c->dq;
 			WH_CHECK( product( g, m->at<float>( e.lncw ), m->at<float>( e.lncb ) ) );
+		}
+		if( const AlignHook* const hook = c->alignHook; hook && il >= hook->layer0 )
+		{
+			// wh_align_tokens: this layer's query rows, and the end of the pass behind the last selected layer
+			if( fuseCrossQ ) { setError( "align_tokens: the query rows of a single-token step are never formed" ); return WH_E_INVALIDARG; }
+			WH_HIP( hipMemcpyAsync( hook->q + (int64_t)( il - hook->layer0 ) * hook->layerStride, c->dq, sizeof( f16 ) * (size_t)M * d, hipMemcpyDeviceToDevice, st ) );
+			if( il >= hook->layer1 ) return 0;
 		}
 		{
 			DecAttnArgs a = {};
@@ -283,7 +290,7 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 				a.qW = m->at<f16>( e.wcq ); a.qB = m->at<float>( e.bcq ); a.qScale = kqScale;
 			}
 			WH_CHECK( attnDecP( c, a ) );
-			if( il == 0 && !devState ) WH_CHECK( capture( c, c->capDecKqvCross, c->dattn, (int64_t)M * d, (int64_t)c->maxRows * d ) );	  // "dec-KQV" (cross)
+			if( il == 0 && !devState && !c->alignHook ) WH_CHECK( capture( c, c->capDecKqvCross, c->dattn, (int64_t)M * d, (int64_t)c->maxRows * d ) );	  // "dec-KQV" (cross)
 		}
 		{
 			GemmArgs g = plainGemm( c->dattn, m->at<f16>( e.wco ), M, d, d );

@@ -230,6 +230,7 @@ int wh_debug_read( wh_context* c, const char* what, int layer, int rows, float* 
 	if( w == "enc-KQV" ) return readF16( c->capEncKqv, (int64_t)batch * c->T * d );	   // layer 0, [batch][n_ctx][d] (heads side by side)
 	if( w == "dec-KQV" ) return readF16( c->capDecKqvSelf, (int64_t)c->capDecRows * d );   // layer 0 self-attention output, rows of the last wh_decode
 	if( w == "dec-KQV#2" ) return readF16( c->capDecKqvCross, (int64_t)c->capDecRows * d );
+	if( const int rcAlign = alignDebugRead( c, w, layer, dstHost, dstCapFloats ); rcAlign != 1 ) return rcAlign;
 	if( layer < 0 || layer >= hp.n_text_layer ) return WH_E_BOUNDS;
 	if( w == "cross-k" || w == "cross-v" )
 	{

@@ -88,6 +88,7 @@ struct wh_model
 	bool filtersSet = false;
 	Allocation staging = { nullptr, nullptr, 0, nullptr };	   // raw blocks of the quantized tensor being loaded; freed by wh_model_finalize / wh_model_destroy
 	int device = 0;	   // the HIP device the arena lives on; every entry point binds the calling thread to it
+	std::vector<int32_t> alignHeads;	   // wh_model_set_alignment_heads: (layer, head) pairs, ascending; empty = every head of the upper half of the decoder
 	template<class T> T* at( int64_t off ) const { return (T*)( arena + off ); }
 	size_t expectedTensors() const { return 11 + 15 * (size_t)hp.n_audio_layer + 24 * (size_t)hp.n_text_layer; }
 };
@@ -152,6 +153,10 @@ struct Profiler
 	}
 };
 
+// The per-layer hook of wh_align_tokens in the multi-token decoder graph: behind the cross-attention query of layers layer0 .. layer1 the rows are copied
+// to q + ( layer - layer0 ) * layerStride, and the pass ends behind layer1's query (nothing later is read: no MLP, no vocabulary product).
+struct AlignHook { int layer0, layer1; wh::f16* q; int64_t layerStride; };
+
 struct wh_context
 {
 	wh_model* m = nullptr;
@@ -188,6 +193,13 @@ struct wh_context
 	uint8_t* sampleScratch = nullptr;		   // TUNE_SAMPLE_SPREAD: slice records of the spread sampler (allocated on first use, before any capture)
 	float* langP = nullptr;					   // wh_lang_detect: [maxBatch][n_lang] probabilities and [maxBatch] winners (allocated on first use)
 	int* langBest = nullptr;
+	// wh_align_tokens (align.hip; all allocated on first use, outside every captured graph): the query rows of the selected layers, the last call's matrix,
+	// the softmax maxima and sums of sweep 1, the frames, and the call's head list and per-window sizes
+	f16* alignQ = nullptr;
+	float *alignM = nullptr, *alignStats = nullptr;
+	int *alignFrames = nullptr, *alignMeta = nullptr;
+	int alignBatch = 0, alignNMax = 0, alignLayer0 = 0, alignLayer1 = 0;	   // what the last call left for wh_debug_read
+	const struct AlignHook* alignHook = nullptr;   // set around the pass of wh_align_tokens only
 	TokenData* beamCand = nullptr;			   // beam search: [maxSeq][8] candidates (allocated on first use)
 	f16 *selfKScratch = nullptr, *selfVScratch = nullptr;	   // beam search: the copy a cache reorder goes through (allocated on first use)
 	// beam search on the device (wh_beam_window_*): per-window rules and state, the records of every step, the parents a step's reorder reads
@@ -376,6 +388,7 @@ namespace wh
 	int decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devState );
 	int checkTokens( const wh_hparams& hp, const int32_t* tokens, int64_t count, const char* who );
 	int uploadDecodeState( wh_context* c, int batch, const DecodeState& s, const int32_t* positions, int uniform );
+	int alignDebugRead( wh_context* c, const std::string& w, int layer, float* dstHost, int64_t dstCapFloats );
 }
 
 static inline uint16_t f32ToF16Bits( float f )

@@ -608,6 +608,14 @@ namespace Whisper
 					logError( "runFullBatch: eSamplingStrategy::BeamSearch is not available in a lock-step batch; use iContext::runFull" );
 					return E_NOTIMPL;
 				}
+				// AlignTokens: the scheduler keeps two batches in flight and a group's caches may be gone when a window is scanned (a follow-up)
+				bool align = params.flag( eFullParamsFlags::AlignTokens );
+				for( uint32_t i = 0; i < count; i++ ) align = align || ( streams[ i ].params && streams[ i ].params->flag( eFullParamsFlags::AlignTokens ) );
+				if( align )
+				{
+					logError( "runFullBatch: eFullParamsFlags::AlignTokens is not available in a lock-step batch; use iContext::runFull" );
+					return E_NOTIMPL;
+				}
 				// streams dealt evenly: no more groups than hold two streams each, every group the same number of slots
 				const uint32_t useGroups = std::max<uint32_t>( 1, std::min<uint32_t>( nGroups, count / 2 ) );
 				const uint32_t slots = std::max<uint32_t>( 1, std::min<uint32_t>( maxSlots, ( count + useGroups - 1 ) / useGroups ) );

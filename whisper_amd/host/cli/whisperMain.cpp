@@ -381,6 +381,18 @@ int main( int argc, char** argv )
 	o.threads = std::min( 4u, std::max( 1u, std::thread::hardware_concurrency() ) );
 	const bool dump = argc > 1 && !strcmp( argv[ 1 ], "--dump-options" );
 	if( dump ) { argv[ 1 ] = argv[ 0 ]; argv++; argc--; }
+	// --align (anywhere; an extension, so neither in the reference's usage text nor among its parameters): token times from the decoder's cross-attention by
+	// dynamic time warping (eFullParamsFlags::AlignTokens) instead of the TokenTimestamps heuristic, for -ml / -owts and the tokens of the results
+	bool align = false;
+	{
+		int kept = 1;
+		for( int i = 1; i < argc; i++ )
+		{
+			if( !strcmp( argv[ i ], "--align" ) ) align = true;
+			else argv[ kept++ ] = argv[ i ];
+		}
+		argc = kept;
+	}
 	if( const int stop = parse( argc, argv, o ) ) return stop - 1;
 	if( dump ) { dumpOptions( o ); return 0; }
 	if( o.colors && !isatty( STDOUT_FILENO ) ) o.colors = false;
@@ -446,7 +458,8 @@ int main( int argc, char** argv )
 		if( o.maxContext != std::numeric_limits<uint32_t>::max() ) p.n_max_text_ctx = (int)o.maxContext;
 		p.offset_ms = (int)o.offsetMs;
 		p.duration_ms = (int)o.durationMs;
-		p.setFlag( eFullParamsFlags::TokenTimestamps, o.outputWords || o.maxLen > 0 );
+		p.setFlag( eFullParamsFlags::TokenTimestamps, !align && ( o.outputWords || o.maxLen > 0 ) );
+		p.setFlag( eFullParamsFlags::AlignTokens, align );
 		p.thold_pt = o.wordThreshold;
 		p.max_len = ( o.outputWords && o.maxLen == 0 ) ? 60 : (int)o.maxLen;
 		p.setFlag( eFullParamsFlags::SpeedupAudio, o.speedUp );

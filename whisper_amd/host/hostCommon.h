@@ -117,6 +117,17 @@ namespace Whisper
 		// Splits the LAST segment into pieces of at most maxLen characters at token boundaries; returns the number of
 		// segments it became (>= 1).
 		static int wrapLast( std::vector<Segment>& all, const Vocabulary& vocab, int maxLen );
+		// the heuristic cost of pronouncing a token's text: what compute() stores in vlen
+		static float voiceLength( const char* text );
+	};
+
+	// ---- token alignment (AlignTokens flag): the device work of one window, supplied by the caller of StreamRun like the decoding itself ----
+	struct iTokenAligner
+	{
+		virtual ~iTokenAligner() = default;
+		// The window at `seek` (10 ms units; the stream ends at seekEnd) was decoded from [sotSequence, ...] and kept the text tokens `text` (ids below eot, at
+		// least one). frames: text.size() + 1 numbers, for each text token and then the end of the text the first 20 ms audio position of the window it aligns to.
+		virtual HRESULT alignWindow( int seek, int seekEnd, const std::vector<int>& sotSequence, const std::vector<int>& text, std::vector<int>& frames ) = 0;
 	};
 
 	// ---- languages (Whisper/Whisper/Languages.cpp, languageCodez.inl; whisper.cpp:31-133) ----

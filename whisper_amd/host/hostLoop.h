@@ -103,6 +103,7 @@ namespace Whisper
 		std::vector<Segment>& resultAll;
 		std::vector<int>& promptPast;
 		TokenTimestamper* const stamper;   // TokenTimestamps flag, or nullptr
+		iTokenAligner* aligner = nullptr;  // AlignTokens flag, or nullptr
 		std::vector<int> promptInit;
 		int seekStart = 0, seekEndV = 0;
 		bool stoppedPrematurely = false;
@@ -111,6 +112,8 @@ namespace Whisper
 		StreamRun( const sFullParams& p, const Vocabulary& v, const wh_hparams& h, iContext* ctx, const sProgressSink& sink, std::vector<Segment>& results,
 			std::vector<int>& past, TokenTimestamper* ts ) : params( p ), vocab( v ), hp( h ), self( ctx ), progress( sink ), resultAll( results ), promptPast( past ), stamper( ts ) {}
 		const sFullParams& fullParams() const { return params; }
+		// AlignTokens: who aligns a finished window's text against its audio (called once per window from finishWindow, never without the flag)
+		void setAligner( iTokenAligner* a ) { aligner = a; }
 		int seekEnd() const { return seekEndV; }
 		int maxTokens() const { return hp.n_text_ctx / 2 - 4; }
 
@@ -213,6 +216,24 @@ namespace Whisper
 			tokensCur.resize( std::min( (size_t)scan.resultLen, tokensCur.size() ) );
 			for( const TokenData& t : tokensCur ) promptPast.push_back( t.id );
 
+			// AlignTokens: the window's text against its cross-attention, once per window; the times are written as each segment is emitted
+			std::vector<int> alignFrames;
+			if( params.flag( eFullParamsFlags::AlignTokens ) && aligner )
+			{
+				std::vector<int> text;
+				for( const TokenData& t : tokensCur )
+					if( t.id < vocab.token_eot ) text.push_back( t.id );
+				if( !text.empty() )
+				{
+					CHECK( aligner->alignWindow( seek, seekEndV, promptInit, text, alignFrames ) );
+					if( alignFrames.size() != text.size() + 1 )
+					{
+						logError( "runFull: the aligner returned %d frames for %d text tokens", (int)alignFrames.size(), (int)text.size() );
+						return E_UNEXPECTED;
+					}
+				}
+			}
+
 			// cut the window's tokens into segments at the timestamp tokens (ContextImpl.cpp:689-784)
 			if( !tokensCur.empty() )
 			{
@@ -229,7 +250,9 @@ namespace Whisper
 					if( params.flag( eFullParamsFlags::PrintRealtime ) ) logDebug( "[%d --> %d]  %s", t0, t1, text.c_str() );
 					resultAll.push_back( std::move( s ) );
 					uint32_t nNew = 1;
-					if( params.flag( eFullParamsFlags::TokenTimestamps ) && stamper && stamper->ready() )
+					const bool aligned = params.flag( eFullParamsFlags::AlignTokens ) && aligner;	  // a window without text tokens has no frames and needs none
+					const bool stamped = params.flag( eFullParamsFlags::TokenTimestamps ) && stamper && stamper->ready();
+					if( stamped )
 					{
 						// whisper.cpp:3063-3069 / ContextImpl.cpp:741-749. The GPU model's sampler starts a token's times at 0
 						// (`sTokenData result = { 0 }`, ContextImpl.cpp:77) where whisper.cpp starts them at -1 = unknown
@@ -238,8 +261,35 @@ namespace Whisper
 						if( g_hostLoopRules == eHostLoopRules::ContextImpl )
 							for( TokenData& t : resultAll.back().tokens ) t.t0 = t.t1 = 0;
 						stamper->compute( resultAll.back(), vocab, params.thold_pt, params.thold_ptsum );
-						if( params.max_len > 0 ) nNew = (uint32_t)TokenTimestamper::wrapLast( resultAll, vocab, params.max_len );
 					}
+					if( aligned )
+					{
+						// text tokens from the warping path, timestamp tokens their own time, other specials the end of the token before them; with both
+						// flags set these times replace the heuristic's (its vlen stays: it is the same number)
+						Segment& seg = resultAll.back();
+						int64_t prev = seg.t0;
+						// the segment's first text token is the window's alignNext-th: counted from the window's start, so that a range that was not
+						// emitted (its text came out empty) cannot shift the frames of what follows
+						size_t alignNext = 0;
+						for( int j = 0; j < i0; j++ )
+							if( tokensCur[ (size_t)j ].id < vocab.token_eot ) alignNext++;
+						for( TokenData& t : seg.tokens )
+						{
+							if( t.id >= vocab.token_beg )
+								t.t0 = t.t1 = seek + 2 * ( t.id - vocab.token_beg );
+							else if( t.id >= vocab.token_eot )
+								t.t0 = t.t1 = prev;
+							else
+							{
+								t.t0 = seek + 2 * alignFrames[ alignNext ];
+								t.t1 = seek + 2 * alignFrames[ alignNext + 1 ];
+								alignNext++;
+							}
+							if( !stamped ) t.vlen = TokenTimestamper::voiceLength( vocab.string( t.id ) );
+							prev = t.t1;
+						}
+					}
+					if( ( stamped || aligned ) && params.max_len > 0 ) nNew = (uint32_t)TokenTimestamper::wrapLast( resultAll, vocab, params.max_len );
 					if( params.new_segment_callback )
 					{
 						const HRESULT hr = params.new_segment_callback( self, nNew, params.new_segment_callback_user_data );

@@ -39,6 +39,8 @@ namespace Whisper
 		}
 	}
 
+	float TokenTimestamper::voiceLength( const char* text ) { return ::Whisper::voiceLength( text ); }
+
 	void TokenTimestamper::begin( const float* pcm, size_t samples )
 	{
 		tBeg = tLast = 0;

@@ -795,6 +795,12 @@ namespace Whisper
 			sFullParams params = paramsIn;
 			bool firstWindowEncoded = false;
 			CHECK( resolveLanguage( params, firstWindowEncoded ) );
+			// AlignTokens: one stream, decoded greedily (beam search is a follow-up: the compute entry point is batched for it already)
+			if( params.flag( eFullParamsFlags::AlignTokens ) && params.strategy == eSamplingStrategy::BeamSearch && params.beam_search.beam_width >= 1 )
+			{
+				logError( "runFull: eFullParamsFlags::AlignTokens is not available with eSamplingStrategy::BeamSearch" );
+				return E_NOTIMPL;
+			}
 			StreamRun run( params, vocab, hp, this, progress, resultAll, promptPast, &stamper );
 			// the run's audio is current until this function returns; the stereo PCM is the caller's and is not referred to afterwards
 			struct CurrentRun
@@ -815,6 +821,30 @@ namespace Whisper
 			// overwrite audio_ctx (ContextImpl.cpp:488-489): encoder positions and cross-attention keys of every window of this run
 			audioCtx = params.audio_ctx;
 			CHECK_WH( wh_context_set_audio_ctx( active, audioCtx ) );
+			// AlignTokens: a finished window's text against its cross-attention caches, which are still the window's when StreamRun::finishWindow asks
+			struct DeviceAligner : iTokenAligner
+			{
+				wh_context* ctx;
+				const Vocabulary& vocab;
+				int64_t melLen;
+				int keysMax;
+				DeviceAligner( wh_context* c, const Vocabulary& v, int64_t len, int keys ) : ctx( c ), vocab( v ), melLen( len ), keysMax( keys ) {}
+				HRESULT alignWindow( int seek, int seekEnd, const std::vector<int>& sotSequence, const std::vector<int>& text, std::vector<int>& frames ) override
+				{
+					std::vector<int32_t> tokens( sotSequence.begin(), sotSequence.end() );
+					tokens.push_back( vocab.token_not );
+					tokens.insert( tokens.end(), text.begin(), text.end() );
+					tokens.push_back( vocab.token_eot );
+					const int32_t len = (int32_t)tokens.size();
+					const int64_t audioEnd = std::min<int64_t>( seekEnd, melLen );
+					const int32_t nKeys = (int32_t)std::max<int64_t>( 1, std::min<int64_t>( keysMax, ( audioEnd - seek ) / 2 ) );
+					std::vector<int32_t> all( tokens.size() );
+					CHECK_WH( wh_align_tokens( ctx, 1, tokens.data(), &len, &nKeys, len, all.data() ) );
+					frames.assign( all.begin(), all.begin() + (ptrdiff_t)text.size() + 1 );
+					return S_OK;
+				}
+			} aligner( active, vocab, mel.length, audioCtx > 0 ? audioCtx : hp.n_audio_ctx );
+			if( params.flag( eFullParamsFlags::AlignTokens ) ) run.setAligner( &aligner );
 			std::vector<int> prompt;
 			while( true )
 			{
@@ -1055,6 +1085,20 @@ namespace Whisper
 		*pp = c;
 		return S_OK;
 	}
+	HRESULT setAlignmentHeads( iModel* model, const int32_t* layerHeadPairs, uint32_t count )
+	{
+		if( !model || ( count && !layerHeadPairs ) ) return E_POINTER;
+		iModelInternals* in = nullptr;
+		if( FAILED( model->QueryInterface( iModelInternals::iid(), (void**)&in ) ) || !in )
+		{
+			logError( "setAlignmentHeads: the model was not created by this library" );
+			return E_INVALIDARG;
+		}
+		const int rc = wh_model_set_alignment_heads( in->loaded()->gpu, layerHeadPairs, (int)count );
+		model->Release();	  // QueryInterface's reference
+		CHECK_WH( rc );
+		return S_OK;
+	}
 	HRESULT createModelImpl( const std::shared_ptr<LoadedModel>& model, iModel** pp )
 	{
 		if( !pp ) return E_POINTER;
@@ -1211,6 +1255,13 @@ WHISPER_EXPORT int32_t whisperc_debug_context_flags( void* ctx, uint32_t flags, 
 {
 	if( !ctx ) return E_POINTER;
 	return contextSetDeviceFlags( ctx, flags, parityThreads );
+}
+// Whisper::setAlignmentHeads: count (layer, head) pairs, 0 = the default heads
+WHISPER_EXPORT int32_t whisperc_model_set_alignment_heads( void* model, const int32_t* layerHeadPairs, int32_t count )
+{
+	if( !model ) return E_POINTER;
+	if( count < 0 ) return E_INVALIDARG;
+	return setAlignmentHeads( (iModel*)model, layerHeadPairs, (uint32_t)count );
 }
 // the code of language `id` (0 .. 98; the language token is sot + 1 + id): S_FALSE beyond the table
 WHISPER_EXPORT int32_t whisperc_language_code( int32_t id, char* code5 )
