@@ -819,7 +819,13 @@ namespace wh
 		constexpr int W_NBUF = 4;
 		constexpr int W_LDS_BYTES = 2 * W_NBUF * F_TILE * 2;
 		constexpr float W_LAZY = 4.0f;
-		template<int NG, bool ONLINE, bool NOARG = false>
+		// SCHED ("enc_sched" 1, one-sweep form only): the same arithmetic in the same order per wave, with the LDS latencies taken off the dependency chain --
+		//   * the four V fragments of sub-tile s and the four K fragments of sub-tile s + 1 are requested before the maximum / exponential section of sub-tile s, into
+		//     registers of their own (K double-buffered), and waited for at their first consumer only;
+		//   * the row maximum of the two half-waves is joined by v_permlane32_swap (no LDS crossbar round trip in front of the rescale branch);
+		//   * the rare rescale multiplies O in place, so the loop-carried accumulator stays in one register block (no copy at the tile boundary);
+		//   * the last tile stops after its last sub-tile with a key < T (the others have e == 0 exactly and V's padding is zero: O and the row sum keep their values).
+		template<int NG, bool ONLINE, bool NOARG = false, int SCHED = 0>
 		__global__ void __launch_bounds__( 1024 / NG, NG == 1 ? 4 : 2 ) attentionEncW( const f16* __restrict__ q, const f16* __restrict__ k,
 			const f16* __restrict__ vT, f16* __restrict__ out, int heads, int T, int Tpad, int nQ, int xcdRemap )
 		{
@@ -1021,6 +1027,125 @@ namespace wh
 	#pragma unroll
 			for( int i = 0; i < W_NBUF - 1; i++ )
 				if( i < nTiles ) { issueK( i, i ); issueV( i, i ); }
+			if constexpr( SCHED == 1 )
+			{
+				static_assert( ONLINE && NG == 2, "the scheduled loop is the one-sweep form of two query groups per wave" );
+				const int swK = ( c >> 1 ) & 7;		// ( ( st * 32 + c ) >> 1 ) & 7: the same for every sub-tile
+				// the last tile is peeled out of the loop (not a second body inside it): the loop-carried O then has one definition per iteration
+				auto tile = [ & ]( int t, auto last )
+				{
+					waitTile( t, std::integral_constant<int, 2 * NG>{} );
+					__syncthreads();
+					if( t + W_NBUF - 1 < nTiles )
+					{
+						issueK( t + W_NBUF - 1, ( t + W_NBUF - 1 ) % W_NBUF );
+						issueV( t + W_NBUF - 1, ( t + W_NBUF - 1 ) % W_NBUF );
+					}
+					const f16* const kt = ldsK + ( t % W_NBUF ) * F_TILE;
+					const f16* const vt = ldsV + ( t % W_NBUF ) * F_TILE;
+					auto readK = [ & ]( int st, f16x8 ( &kf )[ 4 ] )
+					{
+		#pragma unroll
+						for( int kk = 0; kk < 4; kk++ ) kf[ kk ] = *(const f16x8*)( kt + ( st * 32 + c ) * HEAD_DIM + ( ( ( kk * 2 + hi ) ^ swK ) << 3 ) );
+					};
+					// one 32-key sub-tile: scores from kcur; V of this sub-tile and K of the next one requested before the softmax section
+					auto subTile = [ & ]( int st, auto last, const f16x8 ( &kcur )[ 4 ], f16x8 ( &knext )[ 4 ] )
+					{
+						f32x16 S[ NG ];
+		#pragma unroll
+						for( int kk = 0; kk < 4; kk++ )
+		#pragma unroll
+							for( int g = 0; g < NG; g++ ) S[ g ] = __builtin_amdgcn_mfma_f32_32x32x16_f16( kcur[ kk ], qf[ g ][ kk ], kk == 0 ? zero16 : S[ g ], 0, 0, 0 );
+						f16x8 vf[ 4 ];
+		#pragma unroll
+						for( int i = 0; i < 4; i++ ) vf[ i ] = *(const f16x8*)( vt + ( ( st * 4 + i ) * 64 + lane ) * 8 );	  // i = half * 2 + ddt
+						if( st + 1 < 4 ) readK( st + 1, knext );
+						__builtin_amdgcn_sched_barrier( 0 );	   // the requests stay above the maximum / exponential section
+						if constexpr( decltype( last )::value )
+						{
+							const int limit = T - ( t * FK + st * 32 + 4 * hi );
+		#pragma unroll
+							for( int r = 0; r < 16; r++ )
+							{
+								const bool in = ( r & 3 ) + 8 * ( r >> 2 ) < limit;
+		#pragma unroll
+								for( int g = 0; g < NG; g++ ) S[ g ][ r ] = in ? S[ g ][ r ] : -3.0e38f;
+							}
+						}
+						float tm[ NG ];
+						bool raise = false;
+		#pragma unroll
+						for( int g = 0; g < NG; g++ )
+						{
+							tm[ g ] = S[ g ][ 0 ];
+		#pragma unroll
+							for( int r = 1; r < 16; r++ ) tm[ g ] = fmaxf( tm[ g ], S[ g ][ r ] );
+							// the other half-wave's maximum without LDS: v_permlane32_swap exchanges the upper half of its first operand with the lower half of its
+							// second, so the lower lanes find their partner's value in the second result and the upper lanes in the first (what __shfl_xor( tm, 32 ) returns)
+							const unsigned tb = __builtin_bit_cast( unsigned, tm[ g ] );
+							const auto sw2 = __builtin_amdgcn_permlane32_swap( tb, tb, false, false );
+							tm[ g ] = fmaxf( tm[ g ], __builtin_bit_cast( float, hi ? sw2[ 0 ] : sw2[ 1 ] ) );
+							raise = raise || tm[ g ] > mx[ g ] + W_LAZY;
+						}
+						if( __any( raise ) )
+						{
+		#pragma unroll
+							for( int g = 0; g < NG; g++ )
+							{
+								const float mNew = tm[ g ] > mx[ g ] + W_LAZY ? tm[ g ] : mx[ g ];
+								float f = __builtin_amdgcn_exp2f( ( mx[ g ] - mNew ) * L2E );
+								mx[ g ] = mNew;
+								sumF[ g ] *= f;
+								// O *= f in place (the allocator otherwise keeps the scaled accumulator apart from the loop-carried one and copies all 64 registers at the
+								// tile boundary). The waits of the string: v_exp_f32's result into a VALU read; O's last MFMAs were issued before this sub-tile's score
+								// MFMAs, whose results the decision above has read, so they have retired.
+								// The compiler's hazard recogniser does not see these reads of MFMA results. What must stay true if the sub-tile is ever reordered: every
+								// MFMA that writes O is issued BEFORE the score MFMAs whose results decide this branch (the matrix pipe retires in order), and no MFMA
+								// into O is issued between that decision and the multiplies -- the two sched_barriers keep the compiler from moving one in.
+								__builtin_amdgcn_sched_barrier( 0 );
+								asm volatile( "s_nop 7" : "+v"( f ) );
+		#pragma unroll
+								for( int a = 0; a < 2; a++ )
+		#pragma unroll
+									for( int r = 0; r < 16; r++ )
+									{
+										float x = O[ g ][ a ][ r ];
+										asm volatile( "v_mul_f32 %0, %0, %1" : "+v"( x ) : "v"( f ) );
+										O[ g ][ a ][ r ] = x;
+									}
+							}
+							__builtin_amdgcn_sched_barrier( 0 );
+						}
+						f16x8 P[ NG ][ 2 ];
+		#pragma unroll
+						for( int g = 0; g < NG; g++ )
+						{
+							expTile( S[ g ], mx[ g ], P[ g ] );
+							sumF[ g ] += sumP( P[ g ] );
+						}
+		#pragma unroll
+						for( int half = 0; half < 2; half++ )
+		#pragma unroll
+							for( int ddt = 0; ddt < 2; ddt++ )
+		#pragma unroll
+								for( int g = 0; g < NG; g++ ) O[ g ][ ddt ] = __builtin_amdgcn_mfma_f32_32x32x16_f16( vf[ half * 2 + ddt ], P[ g ][ half ], O[ g ][ ddt ], 0, 0, 0 );
+					};
+					// sub-tiles of the last tile that lie wholly beyond T are not computed: wave-uniform, and no barrier inside a tile
+					const int nValid = decltype( last )::value ? ( T - t * FK + 31 ) >> 5 : 4;
+					f16x8 kA[ 4 ], kB[ 4 ];
+					readK( 0, kA );
+					subTile( 0, last, kA, kB );
+					if( nValid < 2 ) return;
+					subTile( 1, last, kB, kA );
+					if( nValid < 3 ) return;
+					subTile( 2, last, kA, kB );
+					if( nValid < 4 ) return;
+					subTile( 3, last, kB, kA );
+				};
+				for( int t = 0; t < nTiles - 1; t++ ) tile( t, std::false_type{} );
+				tile( nTiles - 1, std::true_type{} );
+			}
+			else
 			for( int t = 0; t < nTiles; t++ )
 			{
 				waitTile( t, std::integral_constant<int, 2 * NG>{} );
@@ -1116,24 +1241,35 @@ namespace wh
 			}
 		}
 
-		template<int NG, bool ONLINE, bool NOARG = false>
+		template<int NG, bool ONLINE, bool NOARG = false, int SCHED = 0>
 		int launchEncWideT( const f16* q, const f16* k, const f16* vT, f16* out, int batch, int heads, int T, int Tpad, hipStream_t stream )
 		{
 			static PerDeviceOnce once;
 			if( const int onceDev = once.needed(); onceDev >= 0 )
 			{
-				WH_HIP( hipFuncSetAttribute( (const void*)attentionEncW<NG, ONLINE, NOARG>, hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS_BYTES ) );
+				WH_HIP( hipFuncSetAttribute( (const void*)attentionEncW<NG, ONLINE, NOARG, SCHED>, hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS_BYTES ) );
 				once.mark( onceDev );
 			}
 			const int nQ = ( T + TQ - 1 ) / TQ, BH = batch * heads;
 			const int xcdRemap = ( BH % 8 ) == 0 && ( g_tuning & TUNE_ATTN_XCD ) ? 1 : 0;
-			hipLaunchKernelGGL( ( attentionEncW<NG, ONLINE, NOARG> ), dim3( nQ * BH ), dim3( 1024 / NG ), W_LDS_BYTES, stream, q, k, vT, out, heads, T, Tpad, nQ, xcdRemap );
+			hipLaunchKernelGGL( ( attentionEncW<NG, ONLINE, NOARG, SCHED> ), dim3( nQ * BH ), dim3( 1024 / NG ), W_LDS_BYTES, stream, q, k, vT, out, heads, T, Tpad, nQ, xcdRemap );
 			WH_HIP( hipGetLastError() );
 			return 0;
 		}
-		// mode (the "enc_exp" option): 2 = two sweeps, 3 = one sweep
+		// mode (the "enc_exp" option): 2 = two sweeps, 3 = one sweep, 5 = one sweep without the FP16 rounding of the argument; the one-sweep forms run the
+		// scheduled tile loop under "enc_sched" 1
 		int launchEncWide( const f16* q, const f16* k, const f16* vT, f16* out, int batch, int heads, int T, int Tpad, int mode, hipStream_t stream )
 		{
+			if( g_opt.encSched != 0 && g_opt.encSched != 1 )
+			{
+				setError( "attentionEnc: option enc_sched must be 0 or 1" );
+				return -1;
+			}
+			if( g_opt.encSched == 1 )
+			{
+				if( mode == 5 ) return launchEncWideT<2, true, true, 1>( q, k, vT, out, batch, heads, T, Tpad, stream );
+				if( mode == 3 ) return launchEncWideT<2, true, false, 1>( q, k, vT, out, batch, heads, T, Tpad, stream );
+			}
 			if( mode == 5 ) return launchEncWideT<2, true, true>( q, k, vT, out, batch, heads, T, Tpad, stream );
 			if( mode == 3 ) return launchEncWideT<2, true>( q, k, vT, out, batch, heads, T, Tpad, stream );
 			return launchEncWideT<2, false>( q, k, vT, out, batch, heads, T, Tpad, stream );

@@ -69,6 +69,8 @@ namespace wh
 		int selfNq = 0;				 // "self_nq": sequences per selfBlockDec workgroup (0 = by grid size; 1, 2, 4, 8)
 		int exactEncLayers = -1;	 // "exact_enc_layers": WH_FLAG_PARITY_EXACT, debugging: encode only this many layers and stop (buffers readable as "exact:<name>"); -1 = all
 		int encExp = 5;				 // "enc_exp": encoder attention on the timed path: 5 = attentionEncW<2, true, true> (one sweep, lazily raised running maximum, e = fp16( 2^( s log2 e - m log2 e ) ) with NO FP16 rounding of the argument: 1.46-1.49 ms per 112 windows isolated), 3 = the same with the reference's fp16( s - m ) argument (1.59-1.65), 2 = its two-sweep form (1.85), 1 = attentionEncT<1> (two sweeps, v_exp_f32; 1.83), 0 = attentionEncT<0> (the reference's table in LDS, bit-exact e; 1.91-2.14: round 5's kernel)
+		int encSched = 1;			 // "enc_sched": the tile loop of the one-sweep encoder attention ("enc_exp" 3 and 5): 1 = K / V fragments requested ahead of the exponentials, the half-waves'
+									 // maxima joined by v_permlane32_swap, O rescaled in place, sub-tiles beyond T skipped (the same bits); 0 = the loop of round 6
 		int encAblate = 0;			 // "enc_ablate": attentionEncW, measurement only (results wrong): 1 = no exponentials, 2 = no P.V MFMAs, 4 = a quarter of the Q.K MFMAs
 		int exactAltOrder = 0;		 // "exact_alt_order": WH_FLAG_PARITY_EXACT, measurement only: the weight products add their 32 chains left to right instead of in ggml's tree
 		int decLds = 1;				 // "dec_lds": decode products of 129 .. 512 rows: 1 = gemmDecTile where its 64 x 64 / 64 x 32 tiles fill the chip (operands staged through LDS in
