@@ -31,7 +31,7 @@ def ptr(t):
 
 
 def v_operand(v, T):
-    """V in the kernel's operand order (gemm.hip vFragIndex), zero beyond T."""
+    """V in the kernel's operand order (epilogue.h vFragIndex), zero beyond T."""
     BH = v.shape[0]
     Tpad = (T + 255) // 256 * 256
     key, dd = np.meshgrid(np.arange(T), np.arange(D), indexing="ij")

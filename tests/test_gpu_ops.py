@@ -154,7 +154,7 @@ def test_flash_attention(batch, heads, T):
     k = (rng.standard_normal((batch * heads, T, D)) * 1.5).astype(np.float16)
     v = rng.standard_normal((batch * heads, T, D)).astype(np.float16)
     Tpad = (T + 255) // 256 * 256
-    # V in the kernel's operand order (whisper_hip.h, gemm.hip vFragIndex): blocks of 16 keys x 32 dims, lane-major 8-half fragments
+    # V in the kernel's operand order (whisper_hip.h, epilogue.h vFragIndex): blocks of 16 keys x 32 dims, lane-major 8-half fragments
     key, dd = np.meshgrid(np.arange(T), np.arange(D), indexing="ij")
     idx = (((key >> 4) * 2 + (dd >> 5)) * 64 + ((key >> 2) & 1) * 32 + (dd & 31)) * 8 + ((key >> 3) & 1) * 4 + (key & 3)
     vT = np.zeros((batch * heads, D * Tpad), np.float16)
@@ -277,7 +277,7 @@ def _torch_ref_mul_mat(a16, w16, bias=None, res=None):
 @pytest.mark.parametrize("M,N,K", [(16500, 4608, 1024), (16400, 4096, 1024), (17000, 5120, 192), (16384 + 77, 4672, 256)])
 def test_mul_mat_big_tiles(M, N, K):
     """M >= 16384 rows and >= 300 256x256 tiles: the 256x256x64 direct-to-LDS instance with the banded block walk
-    (gemm.hip CfgGlBig, launchGemm) that the encoder of a 28-window batch runs -- plain FP32 epilogue with bias + residual,
+    (gemm_tiled.hip CfgGlBig, launchGemm) that the encoder of a 28-window batch runs -- plain FP32 epilogue with bias + residual,
     ragged M and N (clamped edge tiles) included."""
     g = torch.Generator(device="cuda").manual_seed(M + N)
     a = torch.randn((M, K), generator=g, device="cuda").half()

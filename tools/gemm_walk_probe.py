@@ -1,4 +1,4 @@
-"""Tiled-GEMM block walk on the GPU box: rows of tiles vs bands of groupM M tiles (gemm.hip), per shape of the 28-window encoder.
+"""Tiled-GEMM block walk on the GPU box: rows of tiles vs bands of groupM M tiles (gemm_tiled.hip, gemm_persistent.hip), per shape of the 28-window encoder.
     python tools/gemm_walk_probe.py > gpurun_out/gemm_walk.txt      (variant = tile variant + 100 * groupM, wh_debug_probe kind 1)"""
 import os
 import sys

@@ -24,7 +24,8 @@ CLI_BIN = os.path.join(LIB_DIR, "whisper-main")
 # the runtime behind the C ABI, one unit per responsibility; runtime.h holds what they share (host code: the kernel units do not include it)
 RUNTIME_SOURCES = ["options.hip", "model.hip", "comm.hip", "context.hip", "encode.hip", "exact_graphs.hip", "decode.hip", "beam.hip", "ops_debug.hip"]
 # resample.hip and vad.hip keep their kernels next to the entry points that own their tables, dequant.hip next to wh_dequantize, align.hip next to wh_align_tokens: kernel units that do include runtime.h
-HIP_SOURCES = ["gemm.hip", "decode1.hip", "attn_enc.hip", "attn_dec.hip", "elementwise.hip", "mel.hip", "exact.hip", "resample.hip", "vad.hip", "dequant.hip", "align.hip"] + RUNTIME_SOURCES
+HIP_SOURCES = ["gemm_persistent.hip", "gemm_decode.hip", "gemm_tiled.hip", "attn_dec.hip", "decode1.hip", "attn_enc.hip", "gemm.hip", "elementwise.hip", "mel.hip", "exact.hip", "resample.hip", "vad.hip", "dequant.hip",
+               "align.hip"] + RUNTIME_SOURCES
 RUNTIME_H_USERS = RUNTIME_SOURCES + ["resample.hip", "vad.hip", "dequant.hip", "align.hip"]
 # exact.hip restates the reference CPU path's summation order: a fused multiply-add only where the source says fma()
 EXTRA_FLAGS = {"exact.hip": ["-ffp-contract=off"]}
@@ -51,7 +52,8 @@ def _run(cmd):
 def build_hip(force: bool = False) -> str:
     os.makedirs(LIB_DIR, exist_ok=True)
     objs = []
-    headers = [os.path.join(CSRC, h) for h in ("common.h", "kernels.h", "epilogue.h", "exact_ops.h")] + [os.path.join(ROOT, "include", "whisper_hip.h")]
+    # every unit depends on every header of csrc/ (an edit of any rebuilds all), except runtime.h, whose users are listed
+    headers = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h") and h != "runtime.h") + [os.path.join(ROOT, "include", "whisper_hip.h")]
     obj_dir = os.path.join(LIB_DIR, "obj")
     os.makedirs(obj_dir, exist_ok=True)
     stale = []
@@ -65,7 +67,8 @@ def build_hip(force: bool = False) -> str:
             stale.append([HIPCC, "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wno-unused-result"] + probes + EXTRA_FLAGS.get(s, []) +
                          ["-I" + os.path.join(ROOT, "include"), "-c", src, "-o", obj])
         objs.append(obj)
-    # the units are independent: a few compilers at a time (MAX_JOBS, at most 16), gemm.hip -- by far the longest -- first
+    # the units are independent: a few compilers at a time (MAX_JOBS, at most 16), in the order of HIP_SOURCES -- the longest first (alone: gemm_persistent.hip 60 s,
+    # gemm_decode.hip 50 s, gemm_tiled.hip 29 s, attn_dec.hip 24 s), so that the build ends when the longest unit does
     with ThreadPoolExecutor(max_workers=max(1, min(16, int(os.environ.get("MAX_JOBS", "0") or 0) or os.cpu_count() or 1))) as pool:
         list(pool.map(_run, stale))
     if force or _newer(HIP_LIB, objs):

@@ -379,15 +379,7 @@ namespace wh
 				setError( "dtw: bad argument (1 .. 256 rows, the packed trace of rows x keys within 150 KB of LDS)" );
 				return WH_E_INVALIDARG;
 			}
-			static PerDeviceOnce once;
-			if( const int onceDev = once.needed(); onceDev >= 0 )
-			{
-				WH_HIP( hipFuncSetAttribute( (const void*)dtw, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024 ) );
-				once.mark( onceDev );
-			}
-			hipLaunchKernelGGL( dtw, dim3( windows ), dim3( 256 ), lds, stream, a );
-			WH_HIP( hipGetLastError() );
-			return 0;
+			return launchLds<dtw, 150 * 1024>( dim3( windows ), dim3( 256 ), lds, stream, a );
 		}
 	}	// namespace
 

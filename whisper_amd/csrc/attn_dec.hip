@@ -1130,18 +1130,7 @@ namespace wh
 		{
 			constexpr int lds = (int)sizeof( std::conditional_t<MF, SelfBlockLdsMf<NQ>, SelfBlockLds<NQ>> );
 			static_assert( lds <= 160 * 1024, "selfBlockDec LDS" );
-			if( lds > 48 * 1024 )
-			{
-				static PerDeviceOnce once;
-				if( const int onceDev = once.needed(); onceDev >= 0 )
-				{
-					WH_HIP( hipFuncSetAttribute( (const void*)selfBlockDec<NQ, MF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds ) );
-					once.mark( onceDev );
-				}
-			}
-			hipLaunchKernelGGL( ( selfBlockDec<NQ, MF> ), dim3( a.H, ( a.batch + NQ - 1 ) / NQ ), dim3( NT ), lds, stream, a );
-			WH_HIP( hipGetLastError() );
-			return 0;
+			return launchLds<selfBlockDec<NQ, MF>>( dim3( a.H, ( a.batch + NQ - 1 ) / NQ ), dim3( NT ), lds, stream, a );
 		}
 
 		// ---------------------------------------------------------------------------------------------------------------
@@ -1388,33 +1377,14 @@ namespace wh
 		{
 			constexpr int lds = (int)sizeof( DecMLds<NQ> );
 			static_assert( lds <= 160 * 1024, "attentionDecM LDS" );
-			static PerDeviceOnce once;
-			if( const int onceDev = once.needed(); onceDev >= 0 )
-			{
-				WH_HIP( hipFuncSetAttribute( (const void*)attentionDecM<NQ>, hipFuncAttributeMaxDynamicSharedMemorySize, lds ) );
-				once.mark( onceDev );
-			}
-			hipLaunchKernelGGL( ( attentionDecM<NQ> ), dim3( a.H, a.batch / NQ ), dim3( NT ), lds, stream, a );
-			WH_HIP( hipGetLastError() );
-			return 0;
+			return launchLds<attentionDecM<NQ>>( dim3( a.H, a.batch / NQ ), dim3( NT ), lds, stream, a );
 		}
 
 		template<int NQ, bool FUSEQ, bool NT_LOADS = false>
 		int launchDecG( const DecAttnArgs& a, hipStream_t stream )
 		{
 			constexpr int lds = (int)sizeof( DecGLds<NQ> );
-			if( lds > 64 * 1024 )
-			{
-				static PerDeviceOnce once;
-				if( const int onceDev = once.needed(); onceDev >= 0 )
-				{
-					WH_HIP( hipFuncSetAttribute( (const void*)attentionDecG<NQ, FUSEQ, NT_LOADS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds ) );
-					once.mark( onceDev );
-				}
-			}
-			hipLaunchKernelGGL( ( attentionDecG<NQ, FUSEQ, NT_LOADS> ), dim3( a.H, a.batch / NQ, a.nTok ), dim3( NT ), lds, stream, a );
-			WH_HIP( hipGetLastError() );
-			return 0;
+			return launchLds<attentionDecG<NQ, FUSEQ, NT_LOADS>>( dim3( a.H, a.batch / NQ, a.nTok ), dim3( NT ), lds, stream, a );
 		}
 	}	// namespace
 

@@ -15,7 +15,7 @@
 //     in-lane loops + one xor-32 shuffle + an 8-entry LDS exchange between waves.
 //   * P is packed to FP16 in registers directly in the B-operand layout of the P.V MFMA: the accumulator's key order
 //     (r&3) + 8*(r>>2) + 4*(lane>>5) is matched by permuting the K-slots of the V operand, which the QKV GEMM epilogue
-//     stores fragment-major (gemm.hip vFragIndex) so that each operand is one coalesced 16-byte load per lane; no
+//     stores fragment-major (epilogue.h vFragIndex) so that each operand is one coalesced 16-byte load per lane; no
 //     cross-lane movement is needed.
 //   * the 8 partial O^T tiles are tree-reduced through LDS in a fixed order (deterministic).
 #include "kernels.h"
@@ -221,7 +221,7 @@ namespace wh
 #pragma unroll
 				for( int st = 0; st < 2; st++ )
 				{
-					// fragment-major V (gemm.hip vFragIndex): one coalesced 16-byte load per lane and operand
+					// fragment-major V (epilogue.h vFragIndex): one coalesced 16-byte load per lane and operand
 					const int kb = ( keyBase + kt * 32 + 16 * st ) >> 4;
 					f16x8 vf[ 2 ];
 #pragma unroll
@@ -1244,17 +1244,9 @@ namespace wh
 		template<int NG, bool ONLINE, bool NOARG = false, int SCHED = 0>
 		int launchEncWideT( const f16* q, const f16* k, const f16* vT, f16* out, int batch, int heads, int T, int Tpad, hipStream_t stream )
 		{
-			static PerDeviceOnce once;
-			if( const int onceDev = once.needed(); onceDev >= 0 )
-			{
-				WH_HIP( hipFuncSetAttribute( (const void*)attentionEncW<NG, ONLINE, NOARG, SCHED>, hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS_BYTES ) );
-				once.mark( onceDev );
-			}
 			const int nQ = ( T + TQ - 1 ) / TQ, BH = batch * heads;
 			const int xcdRemap = ( BH % 8 ) == 0 && ( g_tuning & TUNE_ATTN_XCD ) ? 1 : 0;
-			hipLaunchKernelGGL( ( attentionEncW<NG, ONLINE, NOARG, SCHED> ), dim3( nQ * BH ), dim3( 1024 / NG ), W_LDS_BYTES, stream, q, k, vT, out, heads, T, Tpad, nQ, xcdRemap );
-			WH_HIP( hipGetLastError() );
-			return 0;
+			return launchLds<attentionEncW<NG, ONLINE, NOARG, SCHED>>( dim3( nQ * BH ), dim3( 1024 / NG ), W_LDS_BYTES, stream, q, k, vT, out, heads, T, Tpad, nQ, xcdRemap );
 		}
 		// mode (the "enc_exp" option): 2 = two sweeps, 3 = one sweep, 5 = one sweep without the FP16 rounding of the argument; the one-sweep forms run the
 		// scheduled tile loop under "enc_sched" 1
@@ -1277,58 +1269,29 @@ namespace wh
 
 		int launchEncTable( const f16* q, const f16* k, const f16* vT, f16* out, int batch, int heads, int T, int Tpad, const f16* expTab, hipStream_t stream )
 		{
-			static PerDeviceOnce once;
-			if( const int onceDev = once.needed(); onceDev >= 0 )
-			{
-				WH_HIP( hipFuncSetAttribute( (const void*)attentionEncT<0>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS_BYTES ) );
-				WH_HIP( hipFuncSetAttribute( (const void*)attentionEncT<1>, hipFuncAttributeMaxDynamicSharedMemorySize, T_LDS_BYTES - T_TABLE_HALFS * 2 ) );
-				once.mark( onceDev );
-			}
 			const int nQ = ( T + TQ - 1 ) / TQ, BH = batch * heads;
 			const int xcdRemap = ( BH % 8 ) == 0 && ( g_tuning & TUNE_ATTN_XCD ) ? 1 : 0;
 			if( g_opt.encExp == 2 || g_opt.encExp == 3 || g_opt.encExp == 5 ) return launchEncWide( q, k, vT, out, batch, heads, T, Tpad, g_opt.encExp, stream );
 			if( g_opt.encExp == 1 )
-				hipLaunchKernelGGL( attentionEncT<1>, dim3( nQ * BH ), dim3( 1024 ), T_LDS_BYTES - T_TABLE_HALFS * 2, stream, q, k, vT, out, expTab, heads, T, Tpad, nQ, xcdRemap );
-			else
-			hipLaunchKernelGGL( attentionEncT<0>, dim3( nQ * BH ), dim3( 1024 ), T_LDS_BYTES, stream, q, k, vT, out, expTab, heads, T, Tpad, nQ, xcdRemap );
-			WH_HIP( hipGetLastError() );
-			return 0;
+				return launchLds<attentionEncT<1>>( dim3( nQ * BH ), dim3( 1024 ), T_LDS_BYTES - T_TABLE_HALFS * 2, stream, q, k, vT, out, expTab, heads, T, Tpad, nQ, xcdRemap );
+			return launchLds<attentionEncT<0>>( dim3( nQ * BH ), dim3( 1024 ), T_LDS_BYTES, stream, q, k, vT, out, expTab, heads, T, Tpad, nQ, xcdRemap );
 		}
 
 		int launchEncF( const f16* q, const f16* k, const f16* vT, f16* out, int batch, int heads, int T, int Tpad, bool exactP, hipStream_t stream )
 		{
-			static PerDeviceOnce once;
-			if( const int onceDev = once.needed(); onceDev >= 0 )
-			{
-				WH_HIP( hipFuncSetAttribute( (const void*)attentionEncF<false>, hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS_BYTES ) );
-				WH_HIP( hipFuncSetAttribute( (const void*)attentionEncF<true>, hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS_BYTES ) );
-				once.mark( onceDev );
-			}
 			const int nQ = ( T + FQ - 1 ) / FQ, BH = batch * heads;
 			const int xcdRemap = ( BH % 8 ) == 0 && ( g_tuning & TUNE_ATTN_XCD ) ? 1 : 0;
 			const bool two = !exactP && ( g_tuning & TUNE_ATTN_ENC_2SWEEP );
-			if( two )
-				hipLaunchKernelGGL( attentionEncF<true>, dim3( nQ * BH ), dim3( 512 ), F_LDS_BYTES, stream, q, k, vT, out, heads, T, Tpad, nQ, xcdRemap );
-			else
-				hipLaunchKernelGGL( attentionEncF<false>, dim3( nQ * BH ), dim3( 512 ), F_LDS_BYTES, stream, q, k, vT, out, heads, T, Tpad, nQ, xcdRemap );
-			WH_HIP( hipGetLastError() );
-			return 0;
+			if( two ) return launchLds<attentionEncF<true>>( dim3( nQ * BH ), dim3( 512 ), F_LDS_BYTES, stream, q, k, vT, out, heads, T, Tpad, nQ, xcdRemap );
+			return launchLds<attentionEncF<false>>( dim3( nQ * BH ), dim3( 512 ), F_LDS_BYTES, stream, q, k, vT, out, heads, T, Tpad, nQ, xcdRemap );
 		}
 
 		template<int KT>
 		int launchEncT( const f16* q, const f16* k, const f16* vT, f16* out, int batch, int heads, int T, int Tpad, hipStream_t stream )
 		{
-			static PerDeviceOnce once;
-			if( const int onceDev = once.needed(); onceDev >= 0 )
-			{
-				WH_HIP( hipFuncSetAttribute( (const void*)attentionEnc<KT>, hipFuncAttributeMaxDynamicSharedMemorySize, ATT_LDS_BYTES ) );
-				once.mark( onceDev );
-			}
 			const int nQ = ( T + AQ - 1 ) / AQ, BH = batch * heads;
 			const int xcdRemap = ( BH % 8 ) == 0 && ( g_tuning & TUNE_ATTN_XCD ) ? 1 : 0;
-			hipLaunchKernelGGL( attentionEnc<KT>, dim3( nQ * BH ), dim3( 512 ), ATT_LDS_BYTES, stream, q, k, vT, out, heads, T, Tpad, nQ, xcdRemap );
-			WH_HIP( hipGetLastError() );
-			return 0;
+			return launchLds<attentionEnc<KT>>( dim3( nQ * BH ), dim3( 512 ), ATT_LDS_BYTES, stream, q, k, vT, out, heads, T, Tpad, nQ, xcdRemap );
 		}
 	}	// namespace
 

@@ -206,3 +206,27 @@ namespace wh
 		const int s__ = ( st );      \
 		if( s__ != 0 ) return s__;   \
 	} while( 0 )
+
+namespace wh
+{
+	// The launch of a kernel with dynamic LDS (down here because it uses WH_HIP): the first launch on a device that asks for more than the 48 KiB a kernel
+	// gets without it raises hipFuncAttributeMaxDynamicSharedMemorySize there (one PerDeviceOnce per kernel instance), then the kernel is launched and a launch
+	// error reported. LIMIT = what the attribute is raised to, for a kernel whose size varies from launch to launch; 0 = this launch's size, for a kernel that
+	// always asks for the same. Up to 48 KiB the attribute changes nothing, so no site sets it there -- whatever threshold (none, or 64 KiB) it once had.
+	template<auto Kernel, int LIMIT = 0, class... Args>
+	int launchLds( dim3 grid, dim3 block, size_t ldsBytes, hipStream_t stream, const Args&... args )
+	{
+		if( ldsBytes > 48 * 1024 )
+		{
+			static PerDeviceOnce once;
+			if( const int onceDev = once.needed(); onceDev >= 0 )
+			{
+				WH_HIP( hipFuncSetAttribute( (const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LIMIT > 0 ? LIMIT : (int)ldsBytes ) );
+				once.mark( onceDev );
+			}
+		}
+		hipLaunchKernelGGL( Kernel, grid, block, ldsBytes, stream, args... );
+		WH_HIP( hipGetLastError() );
+		return 0;
+	}
+}

@@ -584,20 +584,9 @@ namespace wh
 		{
 			const int kPad = ( ( a.g.K + 511 ) >> 9 ) << 9;
 			const size_t lds = (size_t)MR * kPad * 2;
-			if( lds > 48 * 1024 )
-			{
-				static PerDeviceOnce once;
-				if( const int onceDev = once.needed(); onceDev >= 0 )
-				{
-					WH_HIP( hipFuncSetAttribute( (const void*)gemvSmall<EPI, PRO, MR>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024 ) );
-					once.mark( onceDev );
-				}
-			}
 			const int grid = ( a.g.N + rowsPerWg - 1 ) / rowsPerWg;
 			const int extra = ( a.pf[ 0 ].ptr || a.pf[ 1 ].ptr ) ? PF_WGS : 0;
-			hipLaunchKernelGGL( ( gemvSmall<EPI, PRO, MR> ), dim3( grid + extra ), dim3( GS_NT ), lds, stream, a, rowsPerWg, grid );
-			WH_HIP( hipGetLastError() );
-			return 0;
+			return launchLds<gemvSmall<EPI, PRO, MR>, 64 * 1024>( dim3( grid + extra ), dim3( GS_NT ), lds, stream, a, rowsPerWg, grid );
 		}
 
 		template<int EPI, int PRO>

@@ -1,4 +1,4 @@
-// Output addressing and the per-element epilogues of the matrix products (shared by gemm.hip and decode1.hip).
+// Output addressing and the per-element epilogues of the matrix products (shared by the gemm_*.hip units and decode1.hip).
 #pragma once
 #include "kernels.h"
 

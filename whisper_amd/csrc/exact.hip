@@ -7,7 +7,7 @@
 // P.V product (Whisper/source/ggml.c:4689-4735), and it is an argument here.
 //
 // NEVER timed: one thread per output element and FP32 FMAs on the VALU (no MFMA: the matrix cores sum in their own order). This is what the
-// timed kernels (gemm.hip, attn_enc.hip, attn_dec.hip, decode1.hip) are measured against on the device, at any shape and batch size, without
+// timed kernels (gemm*.hip, attn_enc.hip, attn_dec.hip, decode1.hip) are measured against on the device, at any shape and batch size, without
 // the reference's own thread-count band in the way. Compiled with -ffp-contract=off: a fused multiply-add happens exactly where fmaf / fma is written.
 #include "whisper_hip.h"
 #include "kernels.h"
@@ -343,16 +343,8 @@ namespace wh
 	int launchExactFlashAttn( const float* q, const float* k, const float* v, float* out, int batch, int H, int T, const f16* expTab, hipStream_t stream )
 	{
 		const size_t lds = (size_t)FQ * T * 4 + (size_t)FQ * T * 2 + FQ * 64 * 2;
-		static PerDeviceOnce once;
-		if( const int onceDev = once.needed(); onceDev >= 0 )
-		{
-			WH_HIP( hipFuncSetAttribute( (const void*)exFlashAttn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096 ) );
-			once.mark( onceDev );
-		}
 		if( lds > 160 * 1024 - 4096 ) { setError( "exact attention: n_audio_ctx too large" ); return WH_E_INVALIDARG; }
-		hipLaunchKernelGGL( exFlashAttn, dim3( ( T + FQ - 1 ) / FQ, H, batch ), dim3( 256 ), lds, stream, q, k, v, out, T, H * 64, expTab );
-		WH_HIP( hipGetLastError() );
-		return 0;
+		return launchLds<exFlashAttn, 160 * 1024 - 4096>( dim3( ( T + FQ - 1 ) / FQ, H, batch ), dim3( 256 ), lds, stream, q, k, v, out, T, H * 64, expTab );
 	}
 
 	int launchExactPackHeads( const float* src, f16* dst, int batch, int rowsPer, int rowCap, int r0, int H, hipStream_t stream )

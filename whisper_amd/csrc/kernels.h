@@ -158,7 +158,6 @@ namespace wh
 	constexpr int GEMV_FUSED_MAX_ROWS = 128;	 // gemvFused / gemmAllRows: 16 (32) columns x up to 128 rows per workgroup
 	constexpr int GEMV_MAX_ROWS = 512;		 // beyond that, up to here: gemmDecRows (64 x 64 output tiles, the lock-step batches of 129 .. 512 sequences)
 	int launchGemmVariant( const GemmArgs& a, int variant, hipStream_t stream );	// tile-shape experiments, EPI_F32 only
-	int gemmInit();													// one-time function attributes
 
 	// ---------------------------------------------------------------------------------------------------------------
 	// elementwise / normalisation
