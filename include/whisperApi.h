@@ -356,6 +356,37 @@ namespace Whisper
 	// ascending (layer, head) order. count == 0 restores the default, every head of the upper half of the decoder's layers (what openai-whisper takes for a
 	// model that names none). A free function: iModel's vtable is the reference's. E_INVALIDARG for a pair outside the model or a model of another library.
 	WHISPER_EXPORT HRESULT setAlignmentHeads( iModel* model, const int32_t* layerHeadPairs, uint32_t count );
+	// Extension (the reference has no temperature and no quality gate anywhere in Whisper/API): decoding fallback, as openai-whisper and whisper.cpp do it, for one
+	// stream through iContext::runFull / runStreamed with the Greedy strategy. A window's greedy attempt is scored over its resultLen tokens -- avgLogprob = the
+	// mean of ln max( p, FLT_MIN ), entropy = that of the token ids among the last 32 -- and fails when the stop rules call it failed, when it is empty, when
+	// avgLogprob < logprobThold, or when it is longer than 32 tokens and entropy < entropyThold. A failed attempt is decoded again (no second encode) by sampling at
+	// temperature k * temperatureInc, k = 1, 2, ... up to 1.0; the last attempt stands whatever its scores. An attempt the stop rules did not fail whose window has
+	// P( <|nospeech|> ) > noSpeechThold and avgLogprob < logprobThold is skipped instead: no segments, no prompt carry-over, the stream moves on. The rules are
+	// DESIGN.md section 7; whisper_amd/host/decodeFallback.h holds them. A free function: iContext's vtable is the reference's. nullptr = off, the state of every
+	// new context: the transcript of a run with the feature off is what it always was. With it on, eSamplingStrategy::BeamSearch answers E_NOTIMPL; the batch
+	// runner has no such setting. E_INVALIDARG for a context of another library, a NaN threshold, or 0 < temperatureInc < 0.01.
+	struct sDecodingFallback
+	{
+		float temperatureInc = 0.2f;	// <= 0: one greedy attempt, gates only
+		float logprobThold = -1.0f;
+		float entropyThold = 2.4f;
+		float noSpeechThold = 0.6f;
+		uint64_t seed = 0;				// the draws of a run are a function of ( seed, window, attempt, position )
+	};
+	WHISPER_EXPORT HRESULT setDecodingFallback( iContext* context, const sDecodingFallback* params );
+	// What the fallback did with each window of the context's last run, in order (a window the stop rules made the stream retry appears once per visit)
+	struct sWindowStats
+	{
+		int32_t seek;			// the window's first frame, 10 ms units
+		int32_t attempts;
+		float temperature;		// of the last attempt
+		float noSpeech;
+		double avgLogprob, entropy;	  // of the last attempt
+		uint32_t skipped;		// 1: the silence rule dropped the window
+		uint32_t reserved;
+	};
+	// count in: the capacity of `stats`; out: the number of windows (stats may be nullptr to ask for it). Empty when the run had the feature off.
+	WHISPER_EXPORT HRESULT getWindowStats( const iContext* context, sWindowStats* stats, uint32_t* count );
 	// Extension (no counterpart in whisper.def): ONE long recording onto the batched path. The buffer is cut into pieces of at most maxLen samples at pauses,
 	// found with the reference's voice-activity detector (Whisper/Whisper/voiceActivityDetection.cpp, which its capture loop uses to fire a transcription when
 	// the speaker pauses): the per-frame features come from the device (wh_vad_features of whisper_hip.h, on the calling thread's current device), the decision

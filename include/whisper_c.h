@@ -69,6 +69,13 @@ int32_t whisperc_run_full_tt( void* ctx, const float* pcm, uint32_t nSamples, co
 /* Whisper::setAlignmentHeads: the (layer, head) pairs whose cross-attention weights the AlignTokens flag (0x1000 in flags: token times by dynamic time
  * warping; through whisperc_run_full, _range, _audio_ctx, _tt for max_len, and whisperc_run_streamed) averages; count 0 restores the default heads */
 int32_t whisperc_model_set_alignment_heads( void* model, const int32_t* layerHeadPairs, int32_t count );
+/* Whisper::setDecodingFallback on an iContext: on != 0 turns the temperature fallback and the quality gates on with these sDecodingFallback values (the
+ * defaults are 0.2, -1, 2.4, 0.6 and seed 0), on == 0 turns them off, the state of every new context; then a run's transcript is what it always was.
+ * whisperc_window_stats: Whisper::getWindowStats, what the fallback did with each window of the context's last run. out = sWindowStats [cap] of whisperApi.h
+ * { int32 seek, attempts; float temperature, noSpeech; double avgLogprob, entropy; uint32 skipped, reserved } or NULL, *count = the number of windows;
+ * cap smaller than that with a non-NULL out is E_BOUNDS. */
+int32_t whisperc_set_fallback( void* ctx, int32_t on, float temperatureInc, float logprobThold, float entropyThold, float noSpeechThold, uint64_t seed );
+int32_t whisperc_window_stats( void* ctx, void* out, uint32_t cap, uint32_t* count );
 /* iContext::getResults( Tokens | Timestamps ) + iTranscribeResult::getSize / getSegments / getTokens; times in 100 ns ticks */
 int32_t whisperc_result_counts( void* ctx, uint32_t* segments, uint32_t* tokens );
 int32_t whisperc_result_segment( void* ctx, uint32_t index, uint64_t* t0, uint64_t* t1, uint32_t* firstToken, uint32_t* countTokens,

@@ -434,6 +434,21 @@ WH_API int wh_decode_window_fetch( wh_context* c, int first, int count, wh_token
  * yet, negative on error. Lets ONE host thread serve several contexts (a scheduler that keeps two lock-step batches in flight). */
 WH_API int wh_decode_window_ready( wh_context* c, int first, int count );
 
+/* Temperature sampling in the device-side loop (wh_decode_greedy, wh_decode_window_*). temperature == 0 -- the state of every new context -- is the greedy
+ * sampler. With temperature > 0 every sample, the prompt step's first one under its forceTimestamp / isInitial flags included, is
+ * wh_op_vocab_soft_max_scaled( invT = 1.0f / temperature ) followed by wh_op_sample_draw with the sequence's decoder position (the position of the token that
+ * was just fed: prompt length - 1 for the first sample) and this seed and nonce. The values are stored in device memory behind what the stream holds (the call
+ * waits for the stream), and the captured step graph is keyed on the mode, not on the values: an attempt at another temperature or nonce replays the same graph,
+ * going back to 0 replays a greedy graph. WH_E_INVALIDARG for a temperature that is negative, NaN or above 4, and, above 0, on a hypothesis-group context or
+ * under WH_FLAG_PARITY_EXACT. A context that never calls it launches, allocates and captures what it always did. */
+WH_API int wh_context_set_sampling( wh_context* c, float temperature, uint64_t seed, uint32_t nonce );
+/* The model's own "no speech" probability of a window: when on, wh_decode_window_start / _start_ragged queue one small gather behind the prompt step's sample,
+ * p[ token_solm ] of every sequence's row of probabilities as that step formed it (the id the reference calls token_solm, 50361 + 1 when multilingual, is
+ * <|nospeech|> in OpenAI's vocabulary). wh_decode_window_no_speech: HOST float [batch] of the window in progress; waits for the first sample only. The buffer
+ * is allocated by the first call that turns it on. */
+WH_API int wh_context_set_no_speech( wh_context* c, int on );
+WH_API int wh_decode_window_no_speech( wh_context* c, float* out );
+
 /* Per-kernel-class GPU timings, the counterpart of the reference's GpuProfiler / iContext::timingsPrint
  * (Whisper/Utils/GpuProfiler.h:21-188, Whisper/Whisper/ContextImpl.misc.cpp:170-182). hipEvent pairs around every launch
  * on the context's stream while enabled; flops / bytes are the algorithmic work of the launches. */
@@ -520,6 +535,23 @@ WH_API int wh_op_lang_probs( void* stream, const float* logits, int rows, int nV
 /* wh_sample_best on probabilities [rows][nVocab]: out [rows]. tokenBeg .. nVocab - 1 are the timestamps; the specials are < tokenBeg. */
 WH_API int wh_op_sample_best( void* stream, const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot,
 	int forceTimestamp, int isInitial, wh_token_data* out );
+/* ---- temperature sampling (an extension: the reference has no temperature; the rules are DESIGN.md section 7 "Decoding fallback", restated in float64 by
+ * tests/fallback_ref.py) ----
+ * wh_op_vocab_soft_max_scaled: wh_op_vocab_soft_max of the FP32 array logits[ i ] * invT, each product rounded once to FP32 -- the bits of scaling on the host and
+ *   calling wh_op_vocab_soft_max; the same choice of kernel (the row in registers up to 52224 columns, three passes beyond).
+ * wh_op_sample_draw: one categorical draw per row of probs [rows][nVocab] under wh_op_sample_best's rules. tsEnd, sumTs, the best text token and onlyTs are that
+ *   kernel's, on the probs given. The allowed set A: with onlyTs the columns [tokenBeg, tsEnd); otherwise every column < tokenBeg except sot / solm / not, plus
+ *   [tokenBeg, tsEnd). u = ( ( (u64)x0 << 21 ) | ( x1 >> 11 ) ) * 2^-53, x = Philox4x32-10 with key ( seed & 0xffffffff, seed >> 32 ) at counter
+ *   ( positionsDev[ row ], row, nonce, 0 ). W = the FP64 sum of p over A; the token is the first c in A whose FP64 prefix sum over A exceeds u W; if rounding
+ *   leaves none, the last c in A with p[ c ] > 0; if W == 0, wh_op_sample_best's pick. out[ row ]: id, p = probs[ id ], and tid / pt / ptsum with the bits
+ *   wh_op_sample_best gives on the row. The sums are formed tile by tile (64 columns) and scanned: an FP64 sum of at most 52 k non-negative terms moves by less
+ *   than 5.8e-12 relative with its order, so a draw can differ from another summation order's only where u W lies that close to a prefix boundary.
+ *   nVocab <= 65536; positionsDev: DEVICE int32 [rows]. No atomics, no scratch memory.
+ * wh_op_philox_u: the u of each row, uOut DEVICE double [rows]. */
+WH_API int wh_op_vocab_soft_max_scaled( void* stream, const float* logits, float invT, float* probs, int rows, int cols );
+WH_API int wh_op_sample_draw( void* stream, const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot,
+	int forceTimestamp, int isInitial, uint64_t seed, uint32_t nonce, const int32_t* positionsDev, wh_token_data* out );
+WH_API int wh_op_philox_u( void* stream, uint64_t seed, uint32_t nonce, int rows, const int32_t* positionsDev, double* uOut );
 /* wh_beam_candidates on probabilities [rows][nVocab]: out [rows][width], width 1 .. 8. */
 WH_API int wh_op_beam_candidates( void* stream, const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot,
 	int forceTimestamp, int isInitial, int width, wh_token_data* out );

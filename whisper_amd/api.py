@@ -75,6 +75,8 @@ def lib():
         L.whisperc_tr_language.argtypes = [vp, C.c_char_p, C.POINTER(C.c_float)]
         L.whisperc_debug_context_flags.argtypes = [vp, C.c_uint32, C.c_int32]
         L.whisperc_model_set_alignment_heads.argtypes = [vp, vp, C.c_int32]
+        L.whisperc_set_fallback.argtypes = [vp, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint64]
+        L.whisperc_window_stats.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
         L.whisperc_resample.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64)]
         L.whisperc_load_audio.argtypes = [C.c_char_p, C.c_int32, vp, C.c_int64, C.POINTER(C.c_int64)]
         L.whisperc_run_full_stereo.argtypes = [vp, vp, vp, C.c_uint32, C.c_char_p, C.c_uint32, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]
@@ -281,6 +283,12 @@ class Model:
         return list(buf[:n])
 
 
+class WindowStatsC(C.Structure):
+    """sWindowStats of whisperApi.h"""
+    _fields_ = [("seek", C.c_int32), ("attempts", C.c_int32), ("temperature", C.c_float), ("noSpeech", C.c_float), ("avgLogprob", C.c_double),
+                ("entropy", C.c_double), ("skipped", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class Context:
     """iContext."""
 
@@ -372,6 +380,29 @@ class Context:
     def set_device_flags(self, flags: int, parity_threads: int = 1):
         """wh_context_set_flags on the device context behind this iContext (parity tests: binding.WH_FLAG_PARITY_EXACT)."""
         _check(lib().whisperc_debug_context_flags(self.h, flags, parity_threads), "setDeviceFlags")
+
+    def set_fallback(self, temperature_inc: Optional[float] = 0.2, logprob_thold: float = -1.0, entropy_thold: float = 2.4, no_speech_thold: float = 0.6, seed: int = 0):
+        """Whisper::setDecodingFallback. set_fallback() or set_fallback(temperature_inc=0.2, ...) turns the feature on for this context's later runs: a greedy
+        window whose scores look bad (mean log-probability below logprob_thold, or more than 32 tokens whose ids have an entropy below entropy_thold, or no
+        timestamp) is decoded again by sampling at temperature_inc, 2 temperature_inc ... 1.0, and a window the model calls silent
+        (P(<|nospeech|>) > no_speech_thold and a mean log-probability below logprob_thold) is dropped. set_fallback(None) turns it off, the state of a new
+        context: the transcript is then what it always was. Greedy decoding of one stream only (beam_width: E_NOTIMPL)."""
+        if temperature_inc is None:
+            _check(lib().whisperc_set_fallback(self.h, 0, 0.0, 0.0, 0.0, 0.0, 0), "setDecodingFallback")
+            return
+        _check(lib().whisperc_set_fallback(self.h, 1, float(temperature_inc), logprob_thold, entropy_thold, no_speech_thold, seed), "setDecodingFallback")
+
+    def window_stats(self):
+        """What the fallback did with each window of the last run: [{seek, attempts, temperature, no_speech, avg_logprob, entropy, skipped}], empty when
+        the feature was off."""
+        n = C.c_uint32()
+        _check(lib().whisperc_window_stats(self.h, None, 0, C.byref(n)), "getWindowStats")
+        if n.value == 0:
+            return []
+        arr = (WindowStatsC * n.value)()
+        _check(lib().whisperc_window_stats(self.h, arr, n.value, C.byref(n)), "getWindowStats")
+        return [dict(seek=w.seek, attempts=w.attempts, temperature=w.temperature, no_speech=w.noSpeech, avg_logprob=w.avgLogprob, entropy=w.entropy,
+                     skipped=bool(w.skipped)) for w in arr]
 
     @property
     def detected_language(self):

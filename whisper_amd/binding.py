@@ -54,6 +54,7 @@ EXPORTS = [
     "wh_vad_frame_count", "wh_vad_features", "wh_vad_features_host",
     "wh_dequantize",
     "wh_model_set_alignment_heads", "wh_align_tokens", "wh_op_align_matrix", "wh_op_dtw",
+    "wh_op_vocab_soft_max_scaled", "wh_op_sample_draw", "wh_op_philox_u", "wh_context_set_sampling", "wh_context_set_no_speech", "wh_decode_window_no_speech",
 ]
 
 
@@ -183,6 +184,12 @@ def lib():
         L.wh_align_tokens.argtypes = [vp, i32, vp, vp, vp, i32, vp]
         L.wh_op_align_matrix.argtypes = [vp, vp, i64, i32, vp, i64, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, vp, vp]
         L.wh_op_dtw.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
+        L.wh_op_vocab_soft_max_scaled.argtypes = [vp, vp, C.c_float, vp, i32, i32]
+        L.wh_op_sample_draw.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, C.c_uint64, C.c_uint32, vp, vp]
+        L.wh_op_philox_u.argtypes = [vp, C.c_uint64, C.c_uint32, i32, vp, vp]
+        L.wh_context_set_sampling.argtypes = [vp, C.c_float, C.c_uint64, C.c_uint32]
+        L.wh_context_set_no_speech.argtypes = [vp, i32]
+        L.wh_decode_window_no_speech.argtypes = [vp, vp]
         _lib = L
     return _lib
 
@@ -325,6 +332,21 @@ class HipContext:
     def set_parity(self, n_threads: int):
         """n_threads > 0: emulate the CPU reference's FP16 thread-partitioned P.V accumulation; 0: FP32 fast path."""
         check(lib().wh_context_set_flags(self.handle, WH_FLAG_PARITY_PV if n_threads > 0 else 0, max(n_threads, 1)))
+
+    def set_sampling(self, temperature: float, seed: int = 0, nonce: int = 0):
+        """temperature > 0: the device-side loop samples from softmax( logits / temperature ) (Philox draws keyed by seed, nonce, position and row);
+        0 restores the greedy sampler."""
+        check(lib().wh_context_set_sampling(self.handle, temperature, seed, nonce))
+
+    def set_no_speech(self, on: bool):
+        """on: every window start also gathers P( <|nospeech|> ) of the prompt step (window_no_speech)."""
+        check(lib().wh_context_set_no_speech(self.handle, 1 if on else 0))
+
+    def window_no_speech(self, batch: int):
+        """P( <|nospeech|> ) of the `batch` sequences of the window in progress; waits for its first sample only."""
+        out = np.empty(batch, np.float32)
+        check(lib().wh_decode_window_no_speech(self.handle, out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def upload_async(self, dst_dev, src_host_pinned):
         """Enqueue a host -> device copy on the context's stream (torch tensors; the host one should be pinned)."""

@@ -240,6 +240,7 @@ void wh_context_destroy( wh_context* c )
 			if( gate.owner == c ) gate = EncGate{};
 	}
 	if( c->encGateEv ) (void)hipEventDestroy( c->encGateEv );
+	if( c->noSpeechEv ) (void)hipEventDestroy( c->noSpeechEv );
 	int bad = 0;
 	for( const Allocation& a : c->allocations ) bad += guardedFree( a ) > 0;
 	if( bad != 0 ) fprintf( stderr, "WH_GUARD_VIOLATION: context %p wrote outside its buffers\n", (void*)c );

@@ -450,6 +450,12 @@ int wh::uploadDecodeState( wh_context* c, int batch, const DecodeState& s, const
 
 extern "C" {
 
+// What a captured step graph depends on besides the batch: the parity mode and the sampler (greedy or temperature: other kernels, the same graph for every temperature)
+static uint32_t stepGraphKey( const wh_context* c )
+{
+	return ( ( c->flags & WH_FLAG_PARITY_PV ) ? ( 0x10000u | (uint32_t)c->parityThreads ) : 0u ) | ( c->temperature > 0.0f ? 0x20000u : 0u );
+}
+
 // logits -> table softmax -> sampleBest -> token data + next token: one workgroup per row, or -- for the few rows of one stream -- every row cut
 // into 64 slices over the chip (three small launches, ~12 us instead of 41 on one CU)
 static int sampleStep( wh_context* c, int batch, hipStream_t st )
@@ -457,6 +463,14 @@ static int sampleStep( wh_context* c, int batch, hipStream_t st )
 	const wh_hparams& hp = c->m->hp;
 	const SpecialIds sp = specialIds( hp );
 	const int sot = sp.sot, solm = sp.solm, tnot = sp.tnot, beg = sp.beg;
+	if( c->temperature > 0.0f )
+	{
+		// wh_context_set_sampling: the table softmax of logits / T, then one draw per row under sampleBest's masks (sample.hip), which also does the loop's bookkeeping
+		WH_CHECK( profiled( c, KC_SOFTMAX, 11.0 * batch * hp.n_vocab, 8.0 * batch * hp.n_vocab,
+			[ & ]() { return launchVocabSoftMaxScaled( c->logits, 1.0f, &c->sampleParams->invT, c->probs, batch, hp.n_vocab, st ); } ) );
+		return profiled( c, KC_SAMPLE, 4.0 * batch * hp.n_vocab, 8.0 * batch * hp.n_vocab,
+			[ & ]() { return launchSampleDrawStep( c->probs, batch, hp.n_vocab, beg, sot, solm, tnot, c->state, c->sampleParams, c->seqPos, c->greedyOut, c->tokensDev, c->mailDev, st ); } );
+	}
 	if( batch <= SMALL_MAX_ROWS && ( g_tuning & TUNE_SAMPLE_SPREAD ) )
 	{
 		if( !c->sampleScratch ) WH_CHECK( c->alloc( c->sampleScratch, (int64_t)sampleSpreadScratchBytes( SMALL_MAX_ROWS ), wh_context::DONT_CARE, "sampleScratch" ) );
@@ -497,7 +511,7 @@ int wh_decode_greedy( wh_context* c, int batch, const int32_t* firstTokens, int 
 	const bool useGraph = !c->prof.on && !( c->flags & WH_FLAG_NO_GRAPH ) && !debugSync();
 	if( useGraph )
 	{
-		const uint32_t key = ( c->flags & WH_FLAG_PARITY_PV ) ? ( 0x10000u | (uint32_t)c->parityThreads ) : 0u;
+		const uint32_t key = stepGraphKey( c );
 		if( c->graphExec && ( c->graphBatch != batch || c->graphKey != key ) )
 		{
 			(void)hipGraphExecDestroy( c->graphExec );
@@ -584,7 +598,7 @@ static int windowStart( wh_context* c, int batch, const int32_t* promptTokens, c
 	for( auto& mk : c->marks ) c->markPool.push_back( mk.ev );
 	c->marks.clear();
 	const bool useGraph = !c->prof.on && !( c->flags & WH_FLAG_NO_GRAPH ) && nSteps > 0 && !debugSync();
-	const uint32_t key = ( c->flags & WH_FLAG_PARITY_PV ) ? ( 0x10000u | (uint32_t)c->parityThreads ) : 0u;
+	const uint32_t key = stepGraphKey( c );
 	if( useGraph && c->graphExec && ( c->graphBatch != batch || c->graphKey != key ) )
 	{
 		WH_HIP( hipStreamSynchronize( st ) );
@@ -641,6 +655,16 @@ static int windowStart( wh_context* c, int batch, const int32_t* promptTokens, c
 		const int sot = sp.sot, solm = sp.solm, tnot = sp.tnot, beg = sp.beg;
 		WH_CHECK( sampleStep( c, batch, st ) );
 		WH_CHECK( launchAdvanceState( c->state, c->seqPos, batch, st ) );
+		c->noSpeechRows = 0;
+		if( c->noSpeech )
+		{
+			// p[ solm ] of the rows the first sample just left in c->probs (the spread sampler leaves unnormalised e and its slice sums), and an event behind it:
+			// wh_decode_window_no_speech waits for the first sample only
+			const bool spread = !( c->temperature > 0.0f ) && batch <= SMALL_MAX_ROWS && ( g_tuning & TUNE_SAMPLE_SPREAD );
+			WH_CHECK( launchNoSpeechGather( c->probs, spread ? c->sampleScratch : nullptr, batch, hp.n_vocab, solm, c->noSpeechDev, st ) );
+			WH_HIP( hipEventRecord( c->noSpeechEv, st ) );
+			c->noSpeechRows = batch;
+		}
 	}
 	if( useGraph )
 		for( int s = 0; s < nSteps; s++ ) WH_HIP( hipGraphLaunch( c->graphExec, st ) );
@@ -679,7 +703,7 @@ int wh_decode_window_continue( wh_context* c, int nSteps )
 	if( c->windowPos + nSteps > hp.n_text_ctx ) { setError( "decode_window_continue: n_text_ctx exceeded" ); return WH_E_BOUNDS; }
 	const int batch = c->lastBatch;
 	const bool useGraph = !c->prof.on && !( c->flags & WH_FLAG_NO_GRAPH ) && !debugSync();
-	const uint32_t key = ( c->flags & WH_FLAG_PARITY_PV ) ? ( 0x10000u | (uint32_t)c->parityThreads ) : 0u;
+	const uint32_t key = stepGraphKey( c );
 	if( useGraph && ( !c->graphExec || c->graphBatch != batch || c->graphKey != key ) )
 	{
 		// the window was started with nSteps == 0 (no graph yet): capture now. The eager warm-up step must not disturb
@@ -806,6 +830,49 @@ int wh_decode_window_finish( wh_context* c, wh_token_data* out )
 	WH_HIP( hipMemcpyAsync( out, c->greedyOut, sizeof( TokenData ) * (size_t)c->lastBatch * c->windowSamples, hipMemcpyDeviceToHost, c->stream ) );
 	WH_HIP( hipStreamSynchronize( c->stream ) );
 	c->windowSamples = 0;
+	return 0;
+}
+
+// Temperature sampling for the device-side loop. The factor 1 / T, the seed and the nonce go to device memory, stream-ordered behind what
+// is queued; the captured step graph is keyed on the mode only.
+int wh_context_set_sampling( wh_context* c, float temperature, uint64_t seed, uint32_t nonce )
+{
+	if( !c ) { setError( "context_set_sampling: null context" ); return WH_E_INVALIDARG; }
+	if( !( temperature >= 0.0f ) || temperature > 4.0f ) { setError( "context_set_sampling: the temperature must lie in [0, 4]" ); return WH_E_INVALIDARG; }
+	if( temperature == 0.0f ) { c->temperature = 0.0f; return 0; }
+	if( c->hyp != 1 ) { setError( "context_set_sampling: not available on a hypothesis-group context" ); return WH_E_INVALIDARG; }
+	if( c->flags & WH_FLAG_PARITY_EXACT ) { setError( "context_set_sampling: not available under WH_FLAG_PARITY_EXACT" ); return WH_E_INVALIDARG; }
+	WH_BIND( c->m );
+	if( c->m->hp.n_vocab > SAMPLE_DRAW_MAX_VOCAB ) { setError( "context_set_sampling: vocabulary larger than 65536" ); return WH_E_INVALIDARG; }
+	if( !c->sampleParams ) WH_CHECK( c->alloc( c->sampleParams, 1, wh_context::DONT_CARE, "sampleParams" ) );
+	const SampleParams p = { 1.0f / temperature, (unsigned)( seed & 0xffffffffull ), (unsigned)( seed >> 32 ), nonce };
+	WH_HIP( hipMemcpyAsync( c->sampleParams, &p, sizeof( p ), hipMemcpyHostToDevice, c->stream ) );
+	WH_HIP( hipStreamSynchronize( c->stream ) );	 // `p` is on this stack
+	c->temperature = temperature;
+	return 0;
+}
+
+int wh_context_set_no_speech( wh_context* c, int on )
+{
+	if( !c ) { setError( "context_set_no_speech: null context" ); return WH_E_INVALIDARG; }
+	if( on && !c->noSpeechDev )
+	{
+		WH_BIND( c->m );
+		WH_CHECK( c->alloc( c->noSpeechDev, (int64_t)c->maxSeq, wh_context::DONT_CARE, "noSpeech" ) );
+		WH_HIP( hipEventCreateWithFlags( &c->noSpeechEv, hipEventDisableTiming ) );
+	}
+	c->noSpeech = on != 0;
+	return 0;
+}
+
+int wh_decode_window_no_speech( wh_context* c, float* out )
+{
+	if( !c || !out || c->noSpeechRows <= 0 ) { setError( "decode_window_no_speech: no window was started with wh_context_set_no_speech on" ); return WH_E_INVALIDARG; }
+	WH_BIND( c->m );
+	if( !c->copyStream ) WH_HIP( hipStreamCreateWithFlags( &c->copyStream, hipStreamNonBlocking ) );
+	WH_HIP( hipStreamWaitEvent( c->copyStream, c->noSpeechEv, 0 ) );
+	WH_HIP( hipMemcpyAsync( out, c->noSpeechDev, sizeof( float ) * (size_t)c->noSpeechRows, hipMemcpyDeviceToHost, c->copyStream ) );
+	WH_HIP( hipStreamSynchronize( c->copyStream ) );
 	return 0;
 }
 

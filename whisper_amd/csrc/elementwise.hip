@@ -1,5 +1,6 @@
 // Normalisation, embedding, layout and softmax/sampling kernels (HBM-bound; one wave per row, shuffle reductions).
 #include "kernels.h"
+#include "block_reduce.h"
 
 namespace wh
 {
@@ -86,49 +87,33 @@ namespace wh
 				x[ (long long)row * d + c ] = (float)te[ (long long)tok * d + c ] + pe[ (long long)pos * d + c ];
 		}
 
-		// ---- block reductions ------------------------------------------------------------------------------------
-		template<int NW>
-		__device__ __forceinline__ float blockMax( float v, float* sh )
-		{
-			v = waveReduceMax( v );
-			const int w = threadIdx.x >> 6;
-			if( ( threadIdx.x & 63 ) == 0 ) sh[ w ] = v;
-			__syncthreads();
-			float r = sh[ 0 ];
-#pragma unroll
-			for( int i = 1; i < NW; i++ ) r = fmaxf( r, sh[ i ] );
-			__syncthreads();
-			return r;
-		}
-		template<int NW>
-		__device__ __forceinline__ double blockSumD( double v, double* sh )
-		{
-			v = waveReduceSumD( v );
-			const int w = threadIdx.x >> 6;
-			if( ( threadIdx.x & 63 ) == 0 ) sh[ w ] = v;
-			__syncthreads();
-			double r = sh[ 0 ];
-#pragma unroll
-			for( int i = 1; i < NW; i++ ) r += sh[ i ];
-			__syncthreads();
-			return r;
-		}
-
 		// ---- table softmax over rows (softMax.hlsl / softMaxLong.hlsl; ggml.c:5030-5090) ---------------------------
 		// p = exp16( x - max ) / sum, sum in double like the reference, -inf -> 0. One 1024-thread block per row.
-		__global__ void __launch_bounds__( 1024 ) softMaxRows( const float* in, float* out, int cols )
+		// SCALED (temperature sampling, wh_op_vocab_soft_max_scaled): the row is x * invT, each product rounded once to FP32 (__fmul_rn: never contracted into the
+		// subtraction of the maximum), invT by value or, when invTDev is non-null, read from device memory (a captured step graph outlives a change of temperature).
+		// The unscaled instances ignore both and compile to the code they had before the parameter existed.
+		template<bool SCALED>
+		__device__ __forceinline__ float softMaxInput( float x, float invT )
+		{
+			if constexpr( SCALED ) return __fmul_rn( x, invT );
+			else return x;
+		}
+		template<bool SCALED>
+		__global__ void __launch_bounds__( 1024 ) softMaxRows( const float* in, float* out, int cols, float invT, const float* invTDev )
 		{
 			__shared__ float shf[ 16 ];
 			__shared__ double shd[ 16 ];
 			const float* x = in + (long long)blockIdx.x * cols;
 			float* y = out + (long long)blockIdx.x * cols;
+			if constexpr( SCALED )
+				if( invTDev ) invT = *invTDev;
 			float m = -INFINITY;
-			for( int c = threadIdx.x; c < cols; c += 1024 ) m = fmaxf( m, x[ c ] );
+			for( int c = threadIdx.x; c < cols; c += 1024 ) m = fmaxf( m, softMaxInput<SCALED>( x[ c ], invT ) );
 			m = blockMax<16>( m, shf );
 			double s = 0.0;
 			for( int c = threadIdx.x; c < cols; c += 1024 )
 			{
-				const float v = x[ c ];
+				const float v = softMaxInput<SCALED>( x[ c ], invT );
 				const float e = ( v == -INFINITY ) ? 0.0f : exp16( v - m );
 				y[ c ] = e;
 				s += (double)e;
@@ -139,36 +124,6 @@ namespace wh
 		}
 
 		// ---- ContextImpl::sampleBest on the device (Whisper/Whisper/ContextImpl.cpp:71-157) -------------------------
-		struct ArgMax
-		{
-			float v;
-			int i;
-		};
-		__device__ __forceinline__ ArgMax better( ArgMax a, ArgMax b )
-		{
-			// larger value wins; equal values resolve to the lower index (the reference's partial_sort leaves ties unspecified)
-			if( b.v > a.v || ( b.v == a.v && b.i < a.i ) ) return b;
-			return a;
-		}
-		__device__ __forceinline__ ArgMax blockArgMax( ArgMax a, ArgMax* sh )
-		{
-#pragma unroll
-			for( int o = 32; o > 0; o >>= 1 )
-			{
-				ArgMax b;
-				b.v = __shfl_xor( a.v, o, 64 );
-				b.i = __shfl_xor( a.i, o, 64 );
-				a = better( a, b );
-			}
-			const int w = threadIdx.x >> 6;
-			if( ( threadIdx.x & 63 ) == 0 ) sh[ w ] = a;
-			__syncthreads();
-			ArgMax r = sh[ 0 ];
-			for( int i = 1; i < 16; i++ ) r = better( r, sh[ i ] );
-			__syncthreads();
-			return r;
-		}
-
 		__global__ void __launch_bounds__( 1024 ) sampleBestKernel( const float* __restrict__ probs, int nVocab, int tokenBeg,
 			int tokenSot, int tokenSolm, int tokenNot, int forceTimestamp, int isInitial, TokenData* __restrict__ out )
 		{
@@ -307,19 +262,22 @@ namespace wh
 		// thread where beamCandidatesKernel re-reads the row: 57.6 against 26 us, VALU-bound, a third of the row spilled), and both in one launch (124 us: 288 spill
 		// instructions under the 128-register cap of a 1024-thread workgroup).
 		constexpr int SC_PER = 51;
-		__global__ void __launch_bounds__( 1024 ) softMaxRowsReg( const float* __restrict__ in, float* __restrict__ out, int cols )
+		template<bool SCALED>
+		__global__ void __launch_bounds__( 1024 ) softMaxRowsReg( const float* __restrict__ in, float* __restrict__ out, int cols, float invT, const float* __restrict__ invTDev )
 		{
 			__shared__ float shf[ 16 ];
 			__shared__ double shd[ 16 ];
 			const float* const x = in + (long long)blockIdx.x * cols;
 			float* const y = out + (long long)blockIdx.x * cols;
+			if constexpr( SCALED )
+				if( invTDev ) invT = *invTDev;
 			float v[ SC_PER ];
 			float m = -INFINITY;
 	#pragma unroll
 			for( int i = 0; i < SC_PER; i++ )
 			{
 				const int c = threadIdx.x + 1024 * i;
-				const float t = x[ c < cols ? c : cols - 1 ];	  // (clamped address + select: a branch per element would serialise the loads)
+				const float t = softMaxInput<SCALED>( x[ c < cols ? c : cols - 1 ], invT );	  // (clamped address + select: a branch per element would serialise the loads)
 				v[ i ] = c < cols ? t : -INFINITY;
 				m = fmaxf( m, v[ i ] );
 			}
@@ -970,6 +928,23 @@ namespace wh
 			}
 		}
 
+		// ---- no-speech probability of the prompt step (wh_decode_window_no_speech): out[ row ] = p[ tokenSolm ] of the row the sampler just left in `probs` ----
+		// parts == nullptr: the row holds probabilities (softMaxSampleKernel, the scaled softmax). Otherwise it holds the spread sampler's unnormalised e, and
+		// p = e * float( 1 / sum ) with the sum sampleSpreadFinal forms from the same slice records in the same order. One wave per row.
+		__global__ void __launch_bounds__( 64 ) noSpeechGatherKernel( const float* __restrict__ probs, const SamplePart* __restrict__ parts, int nVocab, int tokenSolm,
+			float* __restrict__ out )
+		{
+			static_assert( SP_G == 64, "one lane per slice" );
+			const int row = blockIdx.x, lane = threadIdx.x;
+			float v = probs[ (long long)row * nVocab + tokenSolm ];
+			if( parts )
+			{
+				const double sum = waveReduceSumD( parts[ row * SP_G + lane ].sumE );
+				v = v * (float)( 1.0 / sum );
+			}
+			if( lane == 0 ) out[ row ] = v;
+		}
+
 		__global__ void advanceStateKernel( DecodeState* state, int* seqPos, int rows )
 		{
 			const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1026,7 +1001,7 @@ namespace wh
 
 	int launchSoftMaxRows( float* x, int rows, int cols, hipStream_t stream )
 	{
-		hipLaunchKernelGGL( softMaxRows, dim3( rows ), dim3( 1024 ), 0, stream, x, x, cols );
+		hipLaunchKernelGGL( softMaxRows<false>, dim3( rows ), dim3( 1024 ), 0, stream, x, x, cols, 1.0f, (const float*)nullptr );
 		WH_HIP( hipGetLastError() );
 		return 0;
 	}
@@ -1035,9 +1010,28 @@ namespace wh
 	{
 		// option beam_regs: the row in registers (one read and one write instead of three reads and two writes), the same probabilities
 		if( g_opt.beamRegs && nVocab <= SC_PER * 1024 )
-			hipLaunchKernelGGL( softMaxRowsReg, dim3( rows ), dim3( 1024 ), 0, stream, logits, probs, nVocab );
+			hipLaunchKernelGGL( softMaxRowsReg<false>, dim3( rows ), dim3( 1024 ), 0, stream, logits, probs, nVocab, 1.0f, (const float*)nullptr );
 		else
-			hipLaunchKernelGGL( softMaxRows, dim3( rows ), dim3( 1024 ), 0, stream, logits, probs, nVocab );
+			hipLaunchKernelGGL( softMaxRows<false>, dim3( rows ), dim3( 1024 ), 0, stream, logits, probs, nVocab, 1.0f, (const float*)nullptr );
+		WH_HIP( hipGetLastError() );
+		return 0;
+	}
+
+	int launchVocabSoftMaxScaled( const float* logits, float invT, const float* invTDev, float* probs, int rows, int nVocab, hipStream_t stream )
+	{
+		// the same choice of kernel as launchVocabSoftMax, so that the scaled row has the bits the unscaled kernels give on a host-scaled row
+		if( g_opt.beamRegs && nVocab <= SC_PER * 1024 )
+			hipLaunchKernelGGL( softMaxRowsReg<true>, dim3( rows ), dim3( 1024 ), 0, stream, logits, probs, nVocab, invT, invTDev );
+		else
+			hipLaunchKernelGGL( softMaxRows<true>, dim3( rows ), dim3( 1024 ), 0, stream, logits, probs, nVocab, invT, invTDev );
+		WH_HIP( hipGetLastError() );
+		return 0;
+	}
+
+	int launchNoSpeechGather( const float* probs, const void* spreadScratch, int rows, int nVocab, int tokenSolm, float* out, hipStream_t stream )
+	{
+		if( rows < 1 || tokenSolm < 0 || tokenSolm >= nVocab || !probs || !out ) { setError( "noSpeechGather: bad argument" ); return -1; }
+		hipLaunchKernelGGL( noSpeechGatherKernel, dim3( rows ), dim3( 64 ), 0, stream, probs, (const SamplePart*)spreadScratch, nVocab, tokenSolm, out );
 		WH_HIP( hipGetLastError() );
 		return 0;
 	}

@@ -411,6 +411,31 @@ namespace wh
 		const DecodeState* state, TokenData* out, int* nextTokens, SampleMailbox mail, void* scratch, hipStream_t stream );
 	// step += 1, the sampler flags cleared, seqPos[0 .. rows) += 1
 	int launchAdvanceState( DecodeState* state, int* seqPos, int rows, hipStream_t stream );
+
+	// ---- temperature sampling (sample.hip; DESIGN.md section 7 "Decoding fallback") ----
+	// What a sampling context keeps in device memory, so that ONE captured step graph serves every temperature, seed and attempt
+	struct SampleParams
+	{
+		float invT;
+		unsigned seedLo, seedHi, nonce;
+	};
+	constexpr int SAMPLE_DRAW_MAX_VOCAB = 65536;   // 1024 tiles of 64 columns, one per thread of the draw's scan
+	// launchVocabSoftMax on logits * invT (each product rounded once to FP32): the bits launchVocabSoftMax gives on a row scaled by the host. invTDev non-null: the
+	// factor is read from device memory instead
+	int launchVocabSoftMaxScaled( const float* logits, float invT, const float* invTDev, float* probs, int rows, int nVocab, hipStream_t stream );
+	// One categorical draw per row of probs [rows][nVocab] under sampleBest's masks, u from Philox4x32-10 keyed by the seed at counter ( positions[row], row, nonce, 0 );
+	// out [rows]. positions: device. nVocab <= SAMPLE_DRAW_MAX_VOCAB.
+	int launchSampleDraw( const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot, int forceTimestamp, int isInitial,
+		unsigned long long seed, unsigned nonce, const int* positions, TokenData* out, hipStream_t stream );
+	// The same as a step of the device-side loop: flags, output slot and mailbox generation from `state`, seed and nonce from `params` (device), and
+	// softMaxSampleKernel's bookkeeping (out[ state->step * rows + row ], nextTokens[ row ], the mailbox stamp)
+	int launchSampleDrawStep( const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot, const DecodeState* state,
+		const SampleParams* params, const int* positions, TokenData* out, int* nextTokens, SampleMailbox mail, hipStream_t stream );
+	// the uniform number of each row's draw: uOut [rows] (device)
+	int launchPhiloxU( unsigned long long seed, unsigned nonce, int rows, const int* positions, double* uOut, hipStream_t stream );
+	// out[ row ] = p[ tokenSolm ] of the row the sampler left in `probs`; spreadScratch non-null: the row holds the spread sampler's unnormalised e and is
+	// normalised by the sum of its slice records (what sampleSpreadFinal multiplies by)
+	int launchNoSpeechGather( const float* probs, const void* spreadScratch, int rows, int nVocab, int tokenSolm, float* out, hipStream_t stream );
 	// Prompt steps whose sequences differ in length (rows right-padded to nTok tokens): the normalised row of sequence b's LAST real
 	// token, lastPos[b] (device), is copied over its row nTok - 1, where the vocabulary product of a prompt step reads. In place, f16 rows.
 	int launchGatherLastRows( f16* xn, const int* lastPos, int batch, int nTok, int d, hipStream_t stream );

@@ -365,6 +365,30 @@ int wh_op_sample_best( void* stream, const float* probs, int rows, int nVocab, i
 		(hipStream_t)stream );
 }
 
+int wh_op_vocab_soft_max_scaled( void* stream, const float* logits, float invT, float* probs, int rows, int cols )
+{
+	if( !logits || !probs || rows < 1 || cols < 1 ) { setError( "vocab_soft_max_scaled: null pointer or empty shape" ); return WH_E_INVALIDARG; }
+	return launchVocabSoftMaxScaled( logits, invT, nullptr, probs, rows, cols, (hipStream_t)stream );
+}
+
+int wh_op_sample_draw( void* stream, const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot,
+	int forceTimestamp, int isInitial, uint64_t seed, uint32_t nonce, const int32_t* positionsDev, wh_token_data* out )
+{
+	if( !tokenArgsOk( probs, out, rows, nVocab, tokenBeg, tokenSot, tokenSolm, tokenNot ) || !positionsDev || nVocab > SAMPLE_DRAW_MAX_VOCAB )
+	{
+		setError( "sample_draw: bad pointer, size (at most 65536 columns) or token id" );
+		return WH_E_INVALIDARG;
+	}
+	return launchSampleDraw( probs, rows, nVocab, tokenBeg, tokenSot, tokenSolm, tokenNot, forceTimestamp ? 1 : 0, isInitial ? 1 : 0, seed, nonce, positionsDev,
+		(TokenData*)out, (hipStream_t)stream );
+}
+
+int wh_op_philox_u( void* stream, uint64_t seed, uint32_t nonce, int rows, const int32_t* positionsDev, double* uOut )
+{
+	if( rows < 1 || !positionsDev || !uOut ) { setError( "philox_u: null pointer or no rows" ); return WH_E_INVALIDARG; }
+	return launchPhiloxU( seed, nonce, rows, positionsDev, uOut, (hipStream_t)stream );
+}
+
 int wh_op_beam_candidates( void* stream, const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot,
 	int forceTimestamp, int isInitial, int width, wh_token_data* out )
 {

@@ -193,6 +193,15 @@ struct wh_context
 	uint8_t* sampleScratch = nullptr;		   // TUNE_SAMPLE_SPREAD: slice records of the spread sampler (allocated on first use, before any capture)
 	float* langP = nullptr;					   // wh_lang_detect: [maxBatch][n_lang] probabilities and [maxBatch] winners (allocated on first use)
 	int* langBest = nullptr;
+	// temperature sampling (wh_context_set_sampling): 0 = the greedy sampler. The factor, seed and nonce live in device memory (allocated by the first call with a
+	// temperature above 0, before any capture), so one captured step graph per mode serves every attempt
+	float temperature = 0.0f;
+	SampleParams* sampleParams = nullptr;
+	// wh_context_set_no_speech: p[ solm ] of the prompt step's rows, gathered behind the first sample of every window (allocated by the first call that turns it on)
+	bool noSpeech = false;
+	float* noSpeechDev = nullptr;
+	hipEvent_t noSpeechEv = nullptr;
+	int noSpeechRows = 0;	   // rows the window in progress gathered (0 = none)
 	// wh_align_tokens (align.hip; all allocated on first use, outside every captured graph): the query rows of the selected layers, the last call's matrix,
 	// the softmax maxima and sums of sweep 1, the frames, and the call's head list and per-window sizes
 	f16* alignQ = nullptr;

@@ -383,13 +383,27 @@ int main( int argc, char** argv )
 	if( dump ) { argv[ 1 ] = argv[ 0 ]; argv++; argc--; }
 	// --align (anywhere; an extension, so neither in the reference's usage text nor among its parameters): token times from the decoder's cross-attention by
 	// dynamic time warping (eFullParamsFlags::AlignTokens) instead of the TokenTimestamps heuristic, for -ml / -owts and the tokens of the results
-	bool align = false;
+	// --fallback (the same way): Whisper::setDecodingFallback with its defaults, a greedy window that scores badly is decoded again at rising temperatures and a
+	// window the model calls silent is dropped; -tpi / -lpt / -et / -nth N (whisper.cpp's names) set temperatureInc, logprobThold, entropyThold, noSpeechThold
+	bool align = false, useFallback = false;
+	sDecodingFallback fallbackParams;
 	{
 		int kept = 1;
 		for( int i = 1; i < argc; i++ )
 		{
+			float* value = nullptr;
 			if( !strcmp( argv[ i ], "--align" ) ) align = true;
+			else if( !strcmp( argv[ i ], "--fallback" ) ) useFallback = true;
+			else if( !strcmp( argv[ i ], "-tpi" ) ) value = &fallbackParams.temperatureInc;
+			else if( !strcmp( argv[ i ], "-lpt" ) ) value = &fallbackParams.logprobThold;
+			else if( !strcmp( argv[ i ], "-et" ) ) value = &fallbackParams.entropyThold;
+			else if( !strcmp( argv[ i ], "-nth" ) ) value = &fallbackParams.noSpeechThold;
 			else argv[ kept++ ] = argv[ i ];
+			if( value )
+			{
+				if( i + 1 >= argc ) { fprintf( stderr, "error: %s needs a number\n", argv[ i ] ); return 2; }
+				*value = strtof( argv[ ++i ], nullptr );
+			}
 		}
 		argc = kept;
 	}
@@ -431,6 +445,11 @@ int main( int argc, char** argv )
 	ComLight::CComPtr<iContext> context;
 	hr = model->createContext( &context );
 	if( FAILED( hr ) ) { printFailure( "failed to initialize whisper context", hr ); return 6; }
+	if( useFallback )
+	{
+		hr = setDecodingFallback( context, &fallbackParams );
+		if( FAILED( hr ) ) { printFailure( "failed to set the decoding fallback", hr ); return 6; }
+	}
 
 	ComLight::CComPtr<iMediaFoundation> media;
 	hr = initMediaFoundation( &media );

@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include "hostCommon.h"
 #include "hostLoop.h"
+#include "decodeFallback.h"
 #include "languageDetect.h"
 #include "results.h"
 #include "wavFormat.h"
@@ -119,6 +120,10 @@ namespace Whisper
 			int nEncode = 0, nDecodeSteps = 0, nRuns = 0, nSpectrogram = 0, nDecodeWindows = 0;
 			TokenTimestamper stamper;	  // TokenTimestamps flag: token-level times + max_len wrapping (host-only post-processing)
 			bool gpuProfile = false;	  // WHISPER_PROFILE=1: per-kernel hipEvent timing, printed as the "Compute Shaders" table
+			// Whisper::setDecodingFallback (decodeFallback.h): off unless set; what it did with the windows of the last run
+			bool fallbackOn = false;
+			sDecodingFallback fallbackParams;
+			std::vector<sWindowStats> windowStats;
 
 			using Clock = std::chrono::steady_clock;
 			static double msSince( Clock::time_point t ) { return std::chrono::duration<double, std::milli>( Clock::now() - t ).count(); }
@@ -191,6 +196,20 @@ namespace Whisper
 				CHECK_WH( wh_context_set_flags( gpu, flags, parityThreads ) );
 				return S_OK;
 			}
+			HRESULT setFallback( const sDecodingFallback* p )
+			{
+				if( !p ) { fallbackOn = false; return S_OK; }
+				const bool nan = std::isnan( p->temperatureInc ) || std::isnan( p->logprobThold ) || std::isnan( p->entropyThold ) || std::isnan( p->noSpeechThold );
+				if( nan || ( p->temperatureInc > 0.0f && p->temperatureInc < 0.01f ) )
+				{
+					logError( "setDecodingFallback: a threshold is NaN, or temperatureInc lies in ( 0, 0.01 )" );
+					return E_INVALIDARG;
+				}
+				fallbackParams = *p;
+				fallbackOn = true;
+				return S_OK;
+			}
+			const std::vector<sWindowStats>& lastWindowStats() const { return windowStats; }
 			HRESULT runFull( const sFullParams& params, const iAudioBuffer* buffer ) override;
 			HRESULT runStreamed( const sFullParams& params, const sProgressSink& progress, const iAudioReader* reader ) override;
 			HRESULT runCapture( const sFullParams&, const sCaptureCallbacks&, const iAudioCapture* ) override { return E_NOTIMPL; }
@@ -801,6 +820,13 @@ namespace Whisper
 				logError( "runFull: eFullParamsFlags::AlignTokens is not available with eSamplingStrategy::BeamSearch" );
 				return E_NOTIMPL;
 			}
+			// decoding fallback: one stream, the Greedy strategy (the batch runner and beam search are follow-ups)
+			windowStats.clear();
+			if( fallbackOn && params.strategy == eSamplingStrategy::BeamSearch && params.beam_search.beam_width >= 1 )
+			{
+				logError( "runFull: decoding fallback (setDecodingFallback) is not available with eSamplingStrategy::BeamSearch" );
+				return E_NOTIMPL;
+			}
 			StreamRun run( params, vocab, hp, this, progress, resultAll, promptPast, &stamper );
 			// the run's audio is current until this function returns; the stereo PCM is the caller's and is not referred to afterwards
 			struct CurrentRun
@@ -845,7 +871,32 @@ namespace Whisper
 				}
 			} aligner( active, vocab, mel.length, audioCtx > 0 ? audioCtx : hp.n_audio_ctx );
 			if( params.flag( eFullParamsFlags::AlignTokens ) ) run.setAligner( &aligner );
+			// decoding fallback: whatever path leaves this function, the context is back at the greedy sampler and gathers nothing
+			struct SamplingGuard
+			{
+				wh_context* const ctx;
+				~SamplingGuard()
+				{
+					if( !ctx ) return;
+					wh_context_set_sampling( ctx, 0.0f, 0, 0 );
+					wh_context_set_no_speech( ctx, 0 );
+				}
+			} samplingGuard{ fallbackOn ? active : nullptr };
 			std::vector<int> prompt;
+			// one greedy-loop pass over the window the encoder just filled: at the context's temperature when it has one
+			auto decodeAttempt = [ & ]( WindowDecoder& dec, WindowScan& scan ) -> HRESULT
+			{
+				for( bool first = true; !scan.over; first = false )
+				{
+					TokenData token;
+					if( first )
+						CHECK( dec.start( prompt, token ) );
+					else
+						CHECK( dec.next( token ) );
+					scan.feed( token );
+				}
+				return S_OK;
+			};
 			while( true )
 			{
 				const HRESULT hrNext = run.nextWindow( prompt );
@@ -871,15 +922,52 @@ namespace Whisper
 				WindowScan scan( run.fullParams(), vocab, run.seek, run.seekEnd(), run.maxTokens() );
 				if( beamWidth >= 1 )
 					CHECK( g_beamRankingOnHost ? decodeWindowBeam( prompt, beamWidth, scan, dec.steps ) : decodeWindowBeamDevice( prompt, beamWidth, scan, dec.steps ) );
+				else if( !fallbackOn )
+					CHECK( decodeAttempt( dec, scan ) );
 				else
-				for( bool first = true; !scan.over; first = false )
 				{
-					TokenData token;
-					if( first )
-						CHECK( dec.start( prompt, token ) );
-					else
-						CHECK( dec.next( token ) );
-					scan.feed( token );
+					// the plan of decodeFallback.h around the greedy loop: the encoder output and the cross-attention caches stay the window's, a further
+					// attempt is one more decode from position 0. The no-speech probability is the greedy attempt's (temperature 0: the model's own
+					// distribution, as openai-whisper takes it); later attempts do not gather it again.
+					fallback::FallbackPlan plan( fallbackParams, run.seek );
+					sWindowStats ws = {};
+					ws.seek = run.seek;
+					int steps = 0;
+					while( true )
+					{
+						const float temperature = plan.temperature();
+						CHECK_WH( wh_context_set_sampling( active, temperature, plan.seed(), plan.nonce() ) );
+						CHECK_WH( wh_context_set_no_speech( active, plan.attemptIndex() == 0 ? 1 : 0 ) );
+						WindowDecoder attemptDec( active, hp.n_text_ctx );
+						WindowScan attemptScan( run.fullParams(), vocab, run.seek, run.seekEnd(), run.maxTokens() );
+						CHECK( decodeAttempt( attemptDec, attemptScan ) );
+						if( plan.attemptIndex() == 0 ) CHECK_WH( wh_decode_window_no_speech( active, &ws.noSpeech ) );
+						steps += attemptDec.steps;
+						dec.msFetch += attemptDec.msFetch;
+						dec.msEnqueue += attemptDec.msEnqueue;
+						fallback::Attempt a;
+						a.scanFailed = attemptScan.failed;
+						a.resultLen = std::min( attemptScan.resultLen, (int)attemptScan.tokens.size() );
+						a.scores = fallback::score( attemptScan.tokens.data(), a.resultLen );
+						a.noSpeech = ws.noSpeech;
+						ws.attempts = plan.attempts();
+						ws.temperature = temperature;
+						ws.avgLogprob = a.scores.avgLogprob;
+						ws.entropy = a.scores.entropy;
+						const fallback::eVerdict verdict = plan.judge( a );
+						if( verdict == fallback::eVerdict::Retry ) continue;
+						scan.adopt( attemptScan );
+						if( verdict == fallback::eVerdict::Skip )
+						{
+							// silence: no segments, nothing for the next window's prompt, the stream moves on by the scan's seekDelta
+							scan.tokens.clear();
+							scan.resultLen = 0;
+							ws.skipped = 1;
+						}
+						break;
+					}
+					dec.steps = steps;
+					windowStats.push_back( ws );
 				}
 				msDecode += msSince( tDec );
 				if( getenv( "WHISPER_HOSTPROF" ) )
@@ -1099,6 +1187,30 @@ namespace Whisper
 		CHECK_WH( rc );
 		return S_OK;
 	}
+	HRESULT setDecodingFallback( iContext* context, const sDecodingFallback* params )
+	{
+		if( !context ) return E_POINTER;
+		ContextImpl* const c = dynamic_cast<ContextImpl*>( context );
+		if( !c )
+		{
+			logError( "setDecodingFallback: not a context of this library's createContext (the batch runner has no such setting)" );
+			return E_INVALIDARG;
+		}
+		return c->setFallback( params );
+	}
+	HRESULT getWindowStats( const iContext* context, sWindowStats* stats, uint32_t* count )
+	{
+		if( !context || !count ) return E_POINTER;
+		const ContextImpl* const c = dynamic_cast<const ContextImpl*>( context );
+		if( !c ) return E_INVALIDARG;
+		const std::vector<sWindowStats>& all = c->lastWindowStats();
+		const uint32_t cap = *count;
+		*count = (uint32_t)all.size();
+		if( !stats ) return S_OK;
+		if( cap < all.size() ) return E_BOUNDS;
+		std::copy( all.begin(), all.end(), stats );
+		return S_OK;
+	}
 	HRESULT createModelImpl( const std::shared_ptr<LoadedModel>& model, iModel** pp )
 	{
 		if( !pp ) return E_POINTER;
@@ -1255,6 +1367,22 @@ WHISPER_EXPORT int32_t whisperc_debug_context_flags( void* ctx, uint32_t flags, 
 {
 	if( !ctx ) return E_POINTER;
 	return contextSetDeviceFlags( ctx, flags, parityThreads );
+}
+// Whisper::setDecodingFallback: on != 0 turns the feature on with these parameters, 0 turns it off (the others are ignored)
+WHISPER_EXPORT int32_t whisperc_set_fallback( void* ctx, int32_t on, float temperatureInc, float logprobThold, float entropyThold, float noSpeechThold, uint64_t seed )
+{
+	if( !ctx ) return E_POINTER;
+	if( !on ) return setDecodingFallback( (iContext*)ctx, nullptr );
+	sDecodingFallback p;
+	p.temperatureInc = temperatureInc; p.logprobThold = logprobThold; p.entropyThold = entropyThold; p.noSpeechThold = noSpeechThold; p.seed = seed;
+	return setDecodingFallback( (iContext*)ctx, &p );
+}
+// Whisper::getWindowStats: out = sWindowStats [cap] (may be NULL), *count = the windows of the last run
+WHISPER_EXPORT int32_t whisperc_window_stats( void* ctx, void* out, uint32_t cap, uint32_t* count )
+{
+	if( !ctx || !count ) return E_POINTER;
+	*count = cap;
+	return getWindowStats( (const iContext*)ctx, (sWindowStats*)out, count );
 }
 // Whisper::setAlignmentHeads: count (layer, head) pairs, 0 = the default heads
 WHISPER_EXPORT int32_t whisperc_model_set_alignment_heads( void* model, const int32_t* layerHeadPairs, int32_t count )
