@@ -765,12 +765,6 @@ int wh_decode_window_fetch( wh_context* c, int first, int count, wh_token_data* 
 		const TokenData* const data = c->mailData + (size_t)first * rows;
 		const size_t slot0 = (size_t)first * rows, nRec = rows * (size_t)count;
 		const auto t0 = std::chrono::steady_clock::now();
-		auto checksum = [ & ]( const TokenData& r ) -> int
-		{
-			int p, pt, ps;
-			memcpy( &p, &r.p, 4 ); memcpy( &pt, &r.pt, 4 ); memcpy( &ps, &r.ptsum, 4 );
-			return (int)( (unsigned)c->mailGen ^ (unsigned)r.id ^ ( (unsigned)r.tid * 0x9E3779B1u ) ^ (unsigned)p ^ ( (unsigned)pt * 3u ) ^ ( (unsigned)ps * 5u ) );
-		};
 		bool ready = false;
 		for( long spins = 0; !ready; spins++ )
 		{
@@ -785,7 +779,7 @@ int wh_decode_window_fetch( wh_context* c, int first, int count, wh_token_data* 
 				{
 					TokenData td;
 					memcpy( &td, (const char*)out + r * sizeof( TokenData ), sizeof( td ) );
-					ready = flag[ 2 * ( slot0 + r ) + 1 ] == checksum( td );
+					ready = flag[ 2 * ( slot0 + r ) + 1 ] == sampleChecksum( c->mailGen, td );
 				}
 				if( ready ) return 0;
 			}

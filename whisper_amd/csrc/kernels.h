@@ -160,7 +160,7 @@ namespace wh
 	int launchGemmVariant( const GemmArgs& a, int variant, hipStream_t stream );	// tile-shape experiments, EPI_F32 only
 
 	// ---------------------------------------------------------------------------------------------------------------
-	// elementwise / normalisation
+	// elementwise / normalisation (elementwise.hip)
 	// ---------------------------------------------------------------------------------------------------------------
 	// out16[row] = fp16( norm(x[row]) * w + b ); rows of length d (multiple of 4, <= 2048). norm.hlsl + fmaRepeat1.hlsl
 	int launchLayerNorm( const float* x, const float* w, const float* b, f16* out, int rows, int d, hipStream_t stream );
@@ -178,7 +178,7 @@ namespace wh
 	// token ids are clamped to [0, nVocab), positions to [0, nTextCtx): no input can index outside the two tables
 	int launchEmbed( const int* tokens, const f16* te, const float* pe, float* x, int rows, int nTok, int nPast, const int* nPastDev, int d,
 		int nVocab, int nTextCtx, hipStream_t stream );
-	// in-place table softmax of FP32 rows (softMax*.hlsl with the CPU path's FP16 exp table semantics)
+	// in-place table softmax of FP32 rows (softMax*.hlsl with the CPU path's FP16 exp table semantics); sample.hip
 	int launchSoftMaxRows( float* x, int rows, int cols, hipStream_t stream );
 
 	// ---------------------------------------------------------------------------------------------------------------
@@ -307,7 +307,7 @@ namespace wh
 	int launchCrossSoftmaxPV( const CrossSplitArgs& a, hipStream_t stream );
 
 	// ---------------------------------------------------------------------------------------------------------------
-	// logits -> probabilities -> greedy token, on the device
+	// logits -> probabilities -> greedy token, on the device (sample.hip; what its kernels share: sampler_device.h)
 	// ---------------------------------------------------------------------------------------------------------------
 	struct TokenData
 	{
@@ -333,7 +333,7 @@ namespace wh
 	int launchReorderCache( f16* cacheK, f16* cacheV, f16* scratchK, f16* scratchV, const int* parents, int layers, int sequences, int maxSeq,
 		int heads, int keyStride, int rows, hipStream_t stream );
 
-	// ---- beam search WITHOUT the host in the loop (round 5) ------------------------------------------------------------------
+	// ---- beam search WITHOUT the host in the loop (round 5; the ranking and the cache reorder: beam.hip) ---------------------
 	// One window = `slots` decoder sequences sharing its cross-attention K/V. After every decode step beamRankKernel does, per window, what
 	// ContextImpl::decodeWindowBeam (host/whisperImpl.cpp) does on the host: pool = live hypotheses x their `width` candidates ranked by
 	// parent score + log p (stable: ties keep parent order, then candidate order), the best `width` accepted, each fed through the
@@ -392,7 +392,7 @@ namespace wh
 		int gen;			 // window generation: stamped into the host mailbox with every sample (0 = no mailbox writes)
 	};
 	// Pinned, host-coherent mirror of the greedy loop's samples: the sampler writes sample `step` of row r to data[step * rows + r]
-	// and then (system-scope fence in between) stamps flag[step * rows + r] = gen. A host thread that polls the flag gets the
+	// and then (the data stores drained in between: publishSample, sampler_device.h) stamps flag[step * rows + r] = gen. A host thread that polls the flag gets the
 	// token without an event, a copy or a stream synchronisation on the decode stream.
 	// flag holds two ints per record: [2 * slot] = the stamp, [2 * slot + 1] = a checksum of the record and the generation.
 	struct SampleMailbox
@@ -400,6 +400,12 @@ namespace wh
 		TokenData* data;	 // device-visible address of the pinned array
 		int* flag;
 	};
+	// the checksum word: depends on every field of the record and on the generation (the sampler writes it, wh_decode_window_fetch holds the record against it)
+	__host__ __device__ inline int sampleChecksum( int gen, const TokenData& r )
+	{
+		const unsigned p = __builtin_bit_cast( unsigned, r.p ), pt = __builtin_bit_cast( unsigned, r.pt ), ps = __builtin_bit_cast( unsigned, r.ptsum );
+		return (int)( (unsigned)gen ^ (unsigned)r.id ^ ( (unsigned)r.tid * 0x9E3779B1u ) ^ p ^ ( pt * 3u ) ^ ( ps * 5u ) );
+	}
 	// logits row -> table softmax -> ContextImpl::sampleBest, one kernel; writes TokenData to out[state->step * rows + row],
 	// the chosen id to nextTokens[row]; probsOut optional.
 	int launchSoftMaxSample( const float* logits, float* probsOut, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm,

@@ -4,7 +4,8 @@
 // The runtime is the MI355X counterpart of the reference's DirectCompute::WhisperContext
 // (Whisper/Whisper/WhisperContext.cpp: encode :310-399, encodeLayer :158-289, decode :578-639, decodeLayer :407-576),
 // ModelBuffers (Whisper/Whisper/ModelBuffers.h:8-112) and KeyValueBuffers (KeyValueBuffers.h:7-53). It is host code
-// only: every arithmetic step is a kernel from gemm*.hip / attn_enc.hip / attn_dec.hip / elementwise.hip / mel.hip.
+// only: every arithmetic step is a kernel from gemm*.hip / attn_enc.hip / attn_dec.hip / elementwise.hip / sample.hip / mel.hip
+// (beam.hip keeps the beam ranking and the cache reorder next to its entry points).
 //
 // Memory model (sized for 288 GB of HBM3E, no allocation in steady state):
 //   * ONE packed weight arena per model, layout a pure function of the hparams, so a rank that did not read the file

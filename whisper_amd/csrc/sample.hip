@@ -1,12 +1,399 @@
-// Temperature sampling: one categorical draw per row of probabilities under ContextImpl::sampleBest's own masks ("Decoding fallback").
-// The reference has no temperature anywhere; the rules are this project's and are restated in float64 by tests/fallback_ref.py.
+// The vocabulary-row kernels: table softmax, ContextImpl::sampleBest on the device (alone, fused behind the softmax, spread over the chip, as beam candidates),
+// language detection, and temperature sampling -- one categorical draw per row under sampleBest's own masks ("Decoding fallback"; the
+// reference has no temperature anywhere: those rules are this project's and are restated in float64 by tests/fallback_ref.py). One 1024-thread workgroup per row
+// unless a kernel says otherwise. What the kernels share -- sampleBest's rules, the record, the host mailbox -- is sampler_device.h's.
 #include "kernels.h"
-#include "block_reduce.h"
+#include "sampler_device.h"
 
 namespace wh
 {
 	namespace
 	{
+		// ---- table softmax over rows (softMax.hlsl / softMaxLong.hlsl; ggml.c:5030-5090) ---------------------------
+		// p = exp16( x - max ) / sum, sum in double like the reference, -inf -> 0. One 1024-thread block per row.
+		// SCALED: the row is softMaxInput's x * invT, invT by value or, when invTDev is non-null, read from device memory (a captured step graph outlives a change
+		// of temperature).
+		template<bool SCALED>
+		__global__ void __launch_bounds__( 1024 ) softMaxRows( const float* in, float* out, int cols, float invT, const float* invTDev )
+		{
+			__shared__ float shf[ 16 ];
+			__shared__ double shd[ 16 ];
+			const float* x = in + (long long)blockIdx.x * cols;
+			float* y = out + (long long)blockIdx.x * cols;
+			if constexpr( SCALED )
+				if( invTDev ) invT = *invTDev;
+			float m = -INFINITY;
+			for( int c = threadIdx.x; c < cols; c += 1024 ) m = fmaxf( m, softMaxInput<SCALED>( x[ c ], invT ) );
+			m = blockMax<16>( m, shf );
+			double s = 0.0;
+			for( int c = threadIdx.x; c < cols; c += 1024 )
+			{
+				const float v = softMaxInput<SCALED>( x[ c ], invT );
+				const float e = ( v == -INFINITY ) ? 0.0f : exp16( v - m );
+				y[ c ] = e;
+				s += (double)e;
+			}
+			s = blockSumD<16>( s, shd );
+			const float inv = (float)( 1.0 / s );
+			for( int c = threadIdx.x; c < cols; c += 1024 ) y[ c ] = y[ c ] * inv;
+		}
+
+		// ---- ContextImpl::sampleBest on the device (Whisper/Whisper/ContextImpl.cpp:71-157) -------------------------
+		__global__ void __launch_bounds__( 1024 ) sampleBestKernel( const float* __restrict__ probs, int nVocab, int tokenBeg,
+			int tokenSot, int tokenSolm, int tokenNot, int forceTimestamp, int isInitial, TokenData* __restrict__ out )
+		{
+			__shared__ ArgMax sha[ 16 ];
+			__shared__ double shd[ 16 ];
+			const float* p = probs + (long long)blockIdx.x * nVocab;
+			const int tsEnd = timestampEnd( isInitial, tokenBeg, nVocab );
+			RowStats st;
+			for( int c = threadIdx.x; c < nVocab; c += 1024 ) st.feed( p[ c ], c, tokenBeg, tsEnd );
+			const bool onlyTs = st.reduce( forceTimestamp, sha, shd );
+			const ArgMax pick = sampleBestPick( p, nVocab, tokenBeg, tsEnd, onlyTs, tokenSot, tokenSolm, tokenNot, sha );
+			if( threadIdx.x == 0 ) out[ blockIdx.x ] = sampleRecord( pick, st.ts, st.sumTs, nVocab );
+		}
+		// ---- the `width` best continuations of a sequence under sampleBest's own rules (beam search on hypothesis groups) ----
+		// Candidate 0 IS ContextImpl::sampleBest's pick (timestamp-vs-text sum rule, initial-timestamp cap, the top tokens that are
+		// sot / solm / not skipped); candidates 1 .. width-1 are the next best tokens under the same mask, specials skipped as well.
+		// So a beam of width 1 is the greedy decoder. out: [sequences][width] TokenData (tid / pt / ptsum repeated).
+		__global__ void __launch_bounds__( 1024 ) beamCandidatesKernel( const float* __restrict__ probs, int nVocab, int tokenBeg,
+			int tokenSot, int tokenSolm, int tokenNot, int forceTimestamp, int isInitial, int width, TokenData* __restrict__ out )
+		{
+			__shared__ ArgMax sha[ 16 ];
+			__shared__ double shd[ 16 ];
+			const float* p = probs + (long long)blockIdx.x * nVocab;
+			const int tsEnd = timestampEnd( isInitial, tokenBeg, nVocab );
+			RowStats st;
+			for( int c = threadIdx.x; c < nVocab; c += 1024 ) st.feed( p[ c ], c, tokenBeg, tsEnd );
+			const bool onlyTs = st.reduce( forceTimestamp, sha, shd );
+			const int lo = onlyTs ? tokenBeg : 0;
+			constexpr int MAXW = 8;
+			int taken[ MAXW + 3 ];
+			int nTaken = 0, found = 0;
+			// at most width + 3 rounds: the three specials may each cost one
+			for( int round = 0; round < width + 3 && found < width; round++ )
+			{
+				const ArgMax best = bestUntaken( p, lo, nVocab, tokenBeg, tsEnd, taken, nTaken, sha );
+				// no token left under the mask (fewer than `width` survive): the rest repeats the last candidate with probability 0 below, not the
+				// sentinel's token 0 at -inf (candidate 0 of an empty row keeps sampleBest's own answer)
+				if( found > 0 && ( best.i < 0 || best.i >= nVocab ) ) break;
+				taken[ nTaken++ ] = best.i;
+				// sampleBest gives up after four rounds and takes the fourth token whatever it is: only candidate 0 can meet that rule
+				if( specialToken( best.i, tokenSot, tokenSolm, tokenNot ) && !( found == 0 && round == 3 ) ) continue;
+				if( threadIdx.x == 0 ) out[ (long long)blockIdx.x * width + found ] = sampleRecord( best, st.ts, st.sumTs, nVocab );
+				found++;
+			}
+			// fewer than `width` tokens under the mask (cannot happen with a real vocabulary): repeat the last one with probability 0
+			for( ; found < width; found++ )
+				if( threadIdx.x == 0 )
+				{
+					TokenData r = out[ (long long)blockIdx.x * width + ( found > 0 ? found - 1 : 0 ) ];
+					r.p = 0.0f;
+					out[ (long long)blockIdx.x * width + found ] = r;
+				}
+		}
+
+		// softMaxRows with the ROW IN REGISTERS (round 6, option beam_regs): one read and one write of the row instead of three reads and two writes (a workgroup per row:
+		// 40 CUs at 40 rows) -- 37.8 -> 18.3 us at 40 x 51865. The same arithmetic in the same order (e = exp16( x - max ), the double sum thread by thread in column
+		// order, p = e * float( 1 / sum )): the same bits. cols <= SC_PER * 1024. Built, measured and NOT kept: the candidate search the same way (51 selects per round and
+		// thread where beamCandidatesKernel re-reads the row: 57.6 against 26 us, VALU-bound, a third of the row spilled), and both in one launch (124 us: 288 spill
+		// instructions under the 128-register cap of a 1024-thread workgroup).
+		constexpr int SC_PER = 51;
+		template<bool SCALED>
+		__global__ void __launch_bounds__( 1024 ) softMaxRowsReg( const float* __restrict__ in, float* __restrict__ out, int cols, float invT, const float* __restrict__ invTDev )
+		{
+			__shared__ float shf[ 16 ];
+			__shared__ double shd[ 16 ];
+			const float* const x = in + (long long)blockIdx.x * cols;
+			float* const y = out + (long long)blockIdx.x * cols;
+			if constexpr( SCALED )
+				if( invTDev ) invT = *invTDev;
+			float v[ SC_PER ];
+			const float m = loadRowReg<SC_PER, SCALED>( x, cols, invT, v );
+			const float inv = softMaxRowReg( v, m, shf, shd ).inv;
+	#pragma unroll
+			for( int i = 0; i < SC_PER; i++ )
+			{
+				const int c = threadIdx.x + 1024 * i;
+				if( c < cols ) y[ c ] = v[ i ] * inv;
+			}
+		}
+		// ---- language detection: the vocabulary softmax's statistics, only the language columns written (whisper.cpp:2428-2495) ----
+		// Row r of the logits stands rowStride floats behind row r - 1 (the first sequence of every hypothesis group). The row maximum, e = exp16( x - max ) and the
+		// double sum thread by thread in column order are softMaxRows' / softMaxRowsReg's, so p = e * float( 1 / sum ) at columns tokenSot + 1 .. tokenSot + nLang has
+		// the same bits as what those kernels write there; the 51865-float row of probabilities is never written. best = the language with the largest p, exact
+		// ties to the lower id. The row stays in registers between the two sweeps like softMaxRowsReg's (cols <= SC_PER * 1024; 124 VGPRs, no scratch). Reading it
+		// twice instead (46 VGPRs) was built and measured: 30.9 / 53.2 us at 64 / 448 rows x 51865 against 18.0 / 36.8 us for this one -- not kept. nLang <= 1024.
+		__global__ void __launch_bounds__( 1024 ) langProbsKernel( const float* __restrict__ in, long long rowStride, int cols, int tokenSot, int nLang,
+			float* __restrict__ langP, int* __restrict__ best )
+		{
+			__shared__ float shf[ 16 ];
+			__shared__ double shd[ 16 ];
+			__shared__ ArgMax sha[ 16 ];
+			const float* const x = in + (long long)blockIdx.x * rowStride;
+			float v[ SC_PER ];
+			const float m = loadRowReg<SC_PER, false>( x, cols, 1.0f, v );
+			const RowNorm n = softMaxRowReg( v, m, shf, shd );
+			// the language block is at most 1024 columns: thread t owns language t (the few logits are read once more, from the cache)
+			ArgMax a = { -1.0f, 0x7fffffff };
+			if( (int)threadIdx.x < nLang )
+			{
+				const float x1 = x[ tokenSot + 1 + threadIdx.x ];
+				const float e = ( x1 == -INFINITY ) ? 0.0f : exp16( x1 - n.max );
+				a.v = e * n.inv;
+				a.i = threadIdx.x;
+				langP[ (long long)blockIdx.x * nLang + threadIdx.x ] = a.v;
+			}
+			a = blockArgMax<16>( a, sha );
+			if( threadIdx.x == 0 ) best[ blockIdx.x ] = ( a.i < 0 || a.i >= nLang ) ? 0 : a.i;	  // (NaN compares false everywhere and leaves the sentinel)
+		}
+
+		// The same two outputs from probabilities that exist already (WH_FLAG_PARITY_EXACT: the reference's own bits, exact.hip): a gather and an argmax.
+		__global__ void __launch_bounds__( 1024 ) langGatherKernel( const float* __restrict__ probs, long long rowStride, int tokenSot, int nLang,
+			float* __restrict__ langP, int* __restrict__ best )
+		{
+			__shared__ ArgMax sha[ 16 ];
+			const float* const p = probs + (long long)blockIdx.x * rowStride;
+			ArgMax a = { -1.0f, 0x7fffffff };
+			if( (int)threadIdx.x < nLang )
+			{
+				a.v = p[ tokenSot + 1 + threadIdx.x ];
+				a.i = threadIdx.x;
+				langP[ (long long)blockIdx.x * nLang + threadIdx.x ] = a.v;
+			}
+			a = blockArgMax<16>( a, sha );
+			if( threadIdx.x == 0 ) best[ blockIdx.x ] = ( a.i < 0 || a.i >= nLang ) ? 0 : a.i;
+		}
+
+		// ---- logits row -> table softmax -> sampleBest in ONE kernel, the row held in registers -----------------------
+		// Used by the captured decode step: no host round trip between the logits product and the next token. Same
+		// arithmetic as softMaxRows followed by sampleBestKernel (p = exp16(x - max) * float(1 / double sum)).
+		__global__ void __launch_bounds__( 1024 ) softMaxSampleKernel( const float* __restrict__ logits, float* __restrict__ probsOut,
+			int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot, const DecodeState* __restrict__ state,
+			TokenData* __restrict__ out, int* __restrict__ nextTokens, const SampleMailbox mail )
+		{
+			__shared__ float shf[ 16 ];
+			__shared__ double shd[ 16 ];
+			__shared__ ArgMax sha[ 16 ];
+			const float* x = logits + (long long)blockIdx.x * nVocab;
+			const int forceTimestamp = state->forceTimestamp, isInitial = state->isInitial;
+			const int tsEnd = timestampEnd( isInitial, tokenBeg, nVocab );
+			float v[ SC_PER ];
+			// (a branch per element, not loadRowReg's clamped address: under this kernel's register pressure the compiler then waits for each load of the clamped
+			// form before it issues the next -- 51 round trips, +9 us per token at the one row of a single stream, measured)
+			float m = -INFINITY;
+#pragma unroll
+			for( int j = 0; j < SC_PER; j++ )
+			{
+				const int c = threadIdx.x + j * 1024;
+				v[ j ] = c < nVocab ? x[ c ] : -INFINITY;
+				m = fmaxf( m, v[ j ] );
+			}
+			const float inv = softMaxRowReg( v, m, shf, shd ).inv;
+			RowStats st;
+#pragma unroll
+			for( int j = 0; j < SC_PER; j++ )
+			{
+				const int c = threadIdx.x + j * 1024;
+				const float p = v[ j ] * inv;
+				v[ j ] = p;
+				if( c < nVocab )
+				{
+					if( probsOut ) probsOut[ (long long)blockIdx.x * nVocab + c ] = p;
+					st.feed( p, c, tokenBeg, tsEnd );
+				}
+			}
+			const bool onlyTs = st.reduce( forceTimestamp, sha, shd );
+			const int lo = onlyTs ? tokenBeg : 0;
+			ArgMax pick = { -INFINITY, 0 };
+			for( int round = 0; round < 4; round++ )
+			{
+				ArgMax best = { -INFINITY, 0x7fffffff };
+#pragma unroll
+				for( int j = 0; j < SC_PER; j++ )
+				{
+					const int c = threadIdx.x + j * 1024;
+					const bool ok = c < nVocab && c >= lo && !( c >= tsEnd && c >= tokenBeg );
+					if( ok ) best = better( best, ArgMax{ v[ j ], c } );
+				}
+				best = blockArgMax<16>( best, sha );
+				pick = best;
+				// remove the winner from its owner's registers for the next round
+#pragma unroll
+				for( int j = 0; j < SC_PER; j++ )
+					if( (int)threadIdx.x + j * 1024 == best.i ) v[ j ] = -INFINITY;
+				if( !specialToken( best.i, tokenSot, tokenSolm, tokenNot ) ) break;
+			}
+			if( threadIdx.x == 0 ) publishSample( state, mail, out, nextTokens, sampleRecord( pick, st.ts, st.sumTs, nVocab ), blockIdx.x, gridDim.x );
+		}
+
+		// ---- the same sampler for the few rows of ONE stream, spread over the chip -------------------------------------
+		// softMaxSampleKernel gives a row to one workgroup: 207 KB of logits and 52 k exponentials on ONE CU = 41 us of the ~1.1 ms a
+		// single-stream token takes. Here a row is cut into SP_G slices: (1) slice maxima, (2) e = exp16( x - global max ), slice sums,
+		// slice argmaxima and top-4 lists, (3) one wave per row merges the SP_G records and applies sampleBest's rules. Same values:
+		// p = e * float( 1 / double sum ) for every number that leaves the sampler; the timestamp sum adds the same products in another order
+		// (double). e (unnormalised) is left in `eOut`.
+		constexpr int SP_G = 64;
+		struct SamplePart
+		{
+			double sumE;
+			ArgMax tx, ts;
+			ArgMax topAll[ 4 ], topTs[ 4 ];
+		};
+		__global__ void __launch_bounds__( 256 ) sampleSpreadMax( const float* __restrict__ logits, int nVocab, float* __restrict__ partMax )
+		{
+			__shared__ float sh[ 4 ];
+			const int row = blockIdx.y, g = blockIdx.x;
+			const int per = ( nVocab + SP_G - 1 ) / SP_G;
+			const int c0 = g * per, c1 = min( c0 + per, nVocab );
+			const float* x = logits + (long long)row * nVocab;
+			float m = -INFINITY;
+			for( int c = c0 + threadIdx.x; c < c1; c += 256 ) m = fmaxf( m, x[ c ] );
+			m = waveReduceMax( m );
+			if( ( threadIdx.x & 63 ) == 0 ) sh[ threadIdx.x >> 6 ] = m;
+			__syncthreads();
+			if( threadIdx.x == 0 ) partMax[ row * SP_G + g ] = fmaxf( fmaxf( sh[ 0 ], sh[ 1 ] ), fmaxf( sh[ 2 ], sh[ 3 ] ) );
+		}
+		__global__ void __launch_bounds__( 256 ) sampleSpreadExp( const float* __restrict__ logits, int nVocab, int tokenBeg, const float* __restrict__ partMax,
+			const DecodeState* __restrict__ state, float* __restrict__ eOut, SamplePart* __restrict__ parts )
+		{
+			__shared__ ArgMax sha[ 4 ];
+			__shared__ double shd[ 4 ];
+			const int row = blockIdx.y, g = blockIdx.x;
+			const int per = ( nVocab + SP_G - 1 ) / SP_G;
+			const int c0 = g * per, c1 = min( c0 + per, nVocab );
+			const float* x = logits + (long long)row * nVocab;
+			const int tsEnd = timestampEnd( state->isInitial, tokenBeg, nVocab );
+			float m = partMax[ row * SP_G + ( threadIdx.x & ( SP_G - 1 ) ) ];
+			m = waveReduceMax( m );
+			constexpr int PER_T = 4;	   // ceil( 51866 / 64 / 256 )
+			float v[ PER_T ];
+			double s = 0.0;
+			ArgMax tx = { -1.0f, 0x7fffffff }, ts = { -1.0f, 0x7fffffff };
+#pragma unroll
+			for( int j = 0; j < PER_T; j++ )
+			{
+				const int c = c0 + threadIdx.x + j * 256;
+				float e = -1.0f;	   // below every real e: never wins an argmax
+				if( c < c1 )
+				{
+					const float xv = x[ c ];
+					e = ( xv == -INFINITY ) ? 0.0f : exp16( xv - m );
+					eOut[ (long long)row * nVocab + c ] = e;
+					s += (double)e;
+					if( c < tokenBeg ) tx = better( tx, ArgMax{ e, c } );
+					else if( c < tsEnd ) ts = better( ts, ArgMax{ e, c } );
+				}
+				v[ j ] = e;
+			}
+			s = waveReduceSumD( s );
+			if( ( threadIdx.x & 63 ) == 0 ) shd[ threadIdx.x >> 6 ] = s;
+			tx = blockArgMax<4>( tx, sha );	   // (its barriers also publish shd)
+			ts = blockArgMax<4>( ts, sha );
+			SamplePart p;
+			p.sumE = ( shd[ 0 ] + shd[ 1 ] ) + ( shd[ 2 ] + shd[ 3 ] );
+			p.tx = tx; p.ts = ts;
+			// the slice's four best tokens among all that may be sampled, and among its timestamps: whichever list the row needs is merged later
+			for( int list = 0; list < 2; list++ )
+			{
+				float w[ PER_T ];
+#pragma unroll
+				for( int j = 0; j < PER_T; j++ )
+				{
+					const int c = c0 + threadIdx.x + j * 256;
+					const bool ok = c < c1 && !( c >= tsEnd && c >= tokenBeg ) && ( list == 0 || c >= tokenBeg );
+					w[ j ] = ok ? v[ j ] : -2.0f;
+				}
+				for( int round = 0; round < 4; round++ )
+				{
+					ArgMax best = { -2.0f, 0x7fffffff };
+#pragma unroll
+					for( int j = 0; j < PER_T; j++ ) best = better( best, ArgMax{ w[ j ], c0 + (int)threadIdx.x + j * 256 } );
+					best = blockArgMax<4>( best, sha );
+					if( best.v < 0.0f ) best.i = 0x7fffffff;	   // the slice has fewer than `round + 1` such tokens
+					( list == 0 ? p.topAll : p.topTs )[ round ] = best;
+#pragma unroll
+					for( int j = 0; j < PER_T; j++ )
+						if( c0 + (int)threadIdx.x + j * 256 == best.i ) w[ j ] = -2.0f;
+				}
+			}
+			if( threadIdx.x == 0 ) parts[ row * SP_G + g ] = p;
+		}
+		__global__ void __launch_bounds__( 64 ) sampleSpreadFinal( const SamplePart* __restrict__ parts, const float* __restrict__ e, int nVocab, int tokenBeg,
+			int tokenSot, int tokenSolm, int tokenNot, const DecodeState* __restrict__ state, TokenData* __restrict__ out, int* __restrict__ nextTokens,
+			const SampleMailbox mail )
+		{
+			static_assert( SP_G == 64, "one lane per slice" );
+			const int row = blockIdx.x, lane = threadIdx.x;
+			const SamplePart p = parts[ row * SP_G + lane ];
+			const int forceTimestamp = state->forceTimestamp;
+			const int tsEnd = timestampEnd( state->isInitial, tokenBeg, nVocab );
+			const double sum = waveReduceSumD( p.sumE );
+			const float inv = (float)( 1.0 / sum );
+			ArgMax tx = waveArgMax( p.tx ), ts = waveArgMax( p.ts );
+			tx.v = tx.v < 0.0f ? -1.0f : tx.v * inv;
+			ts.v = ts.v < 0.0f ? -1.0f : ts.v * inv;
+			// the timestamp probabilities once more, as the products the one-workgroup sampler adds
+			double sumTs = 0.0;
+			for( int c = tokenBeg + lane; c < tsEnd; c += 64 ) sumTs += (double)( e[ (long long)row * nVocab + c ] * inv );
+			sumTs = waveReduceSumD( sumTs );
+			const bool onlyTs = ( sumTs > (double)fmaxf( tx.v, -1.0f ) ) || forceTimestamp;
+			// merge the slices' lists: every round the best head wins and its lane moves on
+			ArgMax mine[ 4 ];
+#pragma unroll
+			for( int k = 0; k < 4; k++ ) mine[ k ] = onlyTs ? p.topTs[ k ] : p.topAll[ k ];
+			int cursor = 0;
+			ArgMax pick = { -INFINITY, 0 };
+			for( int round = 0; round < 4; round++ )
+			{
+				ArgMax head = { -2.0f, 0x7fffffff };
+#pragma unroll
+				for( int k = 0; k < 4; k++ )
+					if( k == cursor ) head = mine[ k ];
+				if( head.i == 0x7fffffff ) head.v = -2.0f;
+				const ArgMax best = waveArgMax( head );
+				if( best.i == head.i && head.i != 0x7fffffff ) cursor++;
+				pick = best;
+				if( !specialToken( best.i, tokenSot, tokenSolm, tokenNot ) ) break;
+			}
+			if( lane == 0 )
+			{
+				if( pick.i < 0 || pick.i >= nVocab ) { pick.i = 0; pick.v = 0.0f; }
+				pick.v = pick.v * inv;
+				publishSample( state, mail, out, nextTokens, sampleRecord( pick, ts, sumTs, nVocab ), row, gridDim.x );
+			}
+		}
+
+		// ---- no-speech probability of the prompt step (wh_decode_window_no_speech): out[ row ] = p[ tokenSolm ] of the row the sampler just left in `probs` ----
+		// parts == nullptr: the row holds probabilities (softMaxSampleKernel, the scaled softmax). Otherwise it holds the spread sampler's unnormalised e, and
+		// p = e * float( 1 / sum ) with the sum sampleSpreadFinal forms from the same slice records in the same order. One wave per row.
+		__global__ void __launch_bounds__( 64 ) noSpeechGatherKernel( const float* __restrict__ probs, const SamplePart* __restrict__ parts, int nVocab, int tokenSolm,
+			float* __restrict__ out )
+		{
+			static_assert( SP_G == 64, "one lane per slice" );
+			const int row = blockIdx.x, lane = threadIdx.x;
+			float v = probs[ (long long)row * nVocab + tokenSolm ];
+			if( parts )
+			{
+				const double sum = waveReduceSumD( parts[ row * SP_G + lane ].sumE );
+				v = v * (float)( 1.0 / sum );
+			}
+			if( lane == 0 ) out[ row ] = v;
+		}
+
+		__global__ void advanceStateKernel( DecodeState* state, int* seqPos, int rows )
+		{
+			const int i = blockIdx.x * blockDim.x + threadIdx.x;
+			if( i < rows ) seqPos[ i ] += 1;
+			if( i == 0 )
+			{
+				state->step += 1;
+				state->forceTimestamp = 0;
+				state->isInitial = 0;
+			}
+		}
+
+		// ---- temperature sampling -----------------------------------------------------------------------------------
 		// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11), the counter-based generator of curand and torch:
 		// the draw of a row depends on (seed, position, row, nonce) only -- not on the launch, the batch or what ran before
 		struct Philox4 { unsigned x0, x1, x2, x3; };
@@ -74,26 +461,12 @@ namespace wh
 			const float* const p = a.probs + (long long)row * nVocab;
 			const int forceTimestamp = a.state ? a.state->forceTimestamp : a.forceTimestamp;
 			const int isInitial = a.state ? a.state->isInitial : a.isInitial;
-			const int tsEnd = isInitial ? min( tokenBeg + 101, nVocab ) : nVocab;
+			const int tsEnd = timestampEnd( isInitial, tokenBeg, nVocab );
 
-			// ---- 1: best text token and the timestamp statistics, exactly as sampleBestKernel forms them ----
-			ArgMax tx = { -1.0f, 0x7fffffff }, ts = { -1.0f, 0x7fffffff };
-			double sumTs = 0.0;
-			for( int c = tid; c < nVocab; c += 1024 )
-			{
-				const float v = p[ c ];
-				if( c < tokenBeg )
-					tx = better( tx, ArgMax{ v, c } );
-				else if( c < tsEnd )
-				{
-					ts = better( ts, ArgMax{ v, c } );
-					sumTs += (double)v;
-				}
-			}
-			tx = blockArgMax( tx, sha );
-			ts = blockArgMax( ts, sha );
-			sumTs = blockSumD<16>( sumTs, shd );
-			const bool onlyTs = ( sumTs > (double)fmaxf( tx.v, -1.0f ) ) || forceTimestamp;
+			// ---- 1: best text token and the timestamp statistics ----
+			RowStats st;
+			for( int c = tid; c < nVocab; c += 1024 ) st.feed( p[ c ], c, tokenBeg, tsEnd );
+			const bool onlyTs = st.reduce( forceTimestamp, sha, shd );
 			auto allowed = [ & ]( int c ) -> bool
 			{
 				if( c >= tokenBeg ) return c < tsEnd;
@@ -157,25 +530,8 @@ namespace wh
 			ArgMax pick = { 0.0f, 0 };
 			if( !( W > 0.0 ) )
 			{
-				// nothing to draw from: sampleBestKernel's pick -- the top 4 under the mask, the first that is not sot / solm / not
-				const int lo = onlyTs ? tokenBeg : 0;
-				int taken[ 4 ];
-				for( int round = 0; round < 4; round++ )
-				{
-					ArgMax best = { -INFINITY, 0x7fffffff };
-					for( int c = lo + tid; c < nVocab; c += 1024 )
-					{
-						bool skip = c >= tsEnd && c >= tokenBeg;
-						for( int k = 0; k < round; k++ ) skip = skip || ( taken[ k ] == c );
-						if( !skip ) best = better( best, ArgMax{ p[ c ], c } );
-					}
-					best = blockArgMax( best, sha );
-					taken[ round ] = best.i;
-					pick = best;
-					const bool special = best.i == tokenSot || best.i == tokenSolm || best.i == tokenNot;
-					if( !special ) break;
-				}
-				if( pick.i < 0 || pick.i >= nVocab ) pick.i = 0;
+				// nothing to draw from: sampleBestKernel's pick
+				pick = sampleBestPick( p, nVocab, tokenBeg, tsEnd, onlyTs, tokenSot, tokenSolm, tokenNot, sha );
 			}
 			else
 			{
@@ -210,37 +566,12 @@ namespace wh
 
 			if( tid == 0 )
 			{
-				TokenData r;
-				r.id = pick.i;
-				r.tid = ts.v > -1.0f ? ts.i : 0;
-				r.p = pick.v;
-				r.pt = (float)( (double)ts.v / ( sumTs + 1e-10 ) );
-				r.ptsum = (float)sumTs;
-				if( !a.state )
+				const TokenData r = sampleRecord( pick, st.ts, st.sumTs, nVocab );
+				if( a.state ) publishSample( a.state, a.mail, a.out, a.nextTokens, r, row, gridDim.x );
+				else
 				{
 					a.out[ row ] = r;
 					if( a.nextTokens ) a.nextTokens[ row ] = r.id;
-					return;
-				}
-				// the greedy loop's bookkeeping, as softMaxSampleKernel does it: the sample's slot, the token the next step embeds, the host mailbox
-				const long long slot = (long long)a.state->step * gridDim.x + row;
-				a.out[ slot ] = r;
-				a.nextTokens[ row ] = r.id;
-				const int gen = a.state->gen;
-				if( a.mail.data && gen != 0 )
-				{
-					// the record as write-through stores, drained, then the stamp the host polls; the checksum lets a host that saw the stamp early reject a torn record
-					int* const md = (int*)( a.mail.data + slot );
-					__hip_atomic_store( md + 0, r.id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM );
-					__hip_atomic_store( md + 1, r.tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM );
-					__hip_atomic_store( md + 2, __float_as_int( r.p ), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM );
-					__hip_atomic_store( md + 3, __float_as_int( r.pt ), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM );
-					__hip_atomic_store( md + 4, __float_as_int( r.ptsum ), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM );
-					const int check = (int)( (unsigned)gen ^ (unsigned)r.id ^ ( (unsigned)r.tid * 0x9E3779B1u ) ^ (unsigned)__float_as_int( r.p ) ^
-						( (unsigned)__float_as_int( r.pt ) * 3u ) ^ ( (unsigned)__float_as_int( r.ptsum ) * 5u ) );
-					__hip_atomic_store( a.mail.flag + 2 * slot + 1, check, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM );
-					asm volatile( "s_waitcnt vmcnt(0)" ::: "memory" );
-					__hip_atomic_store( a.mail.flag + 2 * slot, gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM );
 				}
 			}
 		}
@@ -252,6 +583,121 @@ namespace wh
 		}
 	}	// namespace
 
+	int launchSoftMaxRows( float* x, int rows, int cols, hipStream_t stream )
+	{
+		hipLaunchKernelGGL( softMaxRows<false>, dim3( rows ), dim3( 1024 ), 0, stream, x, x, cols, 1.0f, (const float*)nullptr );
+		WH_HIP( hipGetLastError() );
+		return 0;
+	}
+
+	int launchVocabSoftMax( const float* logits, float* probs, int rows, int nVocab, hipStream_t stream )
+	{
+		// option beam_regs: the row in registers (one read and one write instead of three reads and two writes), the same probabilities
+		if( g_opt.beamRegs && nVocab <= SC_PER * 1024 )
+			hipLaunchKernelGGL( softMaxRowsReg<false>, dim3( rows ), dim3( 1024 ), 0, stream, logits, probs, nVocab, 1.0f, (const float*)nullptr );
+		else
+			hipLaunchKernelGGL( softMaxRows<false>, dim3( rows ), dim3( 1024 ), 0, stream, logits, probs, nVocab, 1.0f, (const float*)nullptr );
+		WH_HIP( hipGetLastError() );
+		return 0;
+	}
+
+	int launchVocabSoftMaxScaled( const float* logits, float invT, const float* invTDev, float* probs, int rows, int nVocab, hipStream_t stream )
+	{
+		// the same choice of kernel as launchVocabSoftMax, so that the scaled row has the bits the unscaled kernels give on a host-scaled row
+		if( g_opt.beamRegs && nVocab <= SC_PER * 1024 )
+			hipLaunchKernelGGL( softMaxRowsReg<true>, dim3( rows ), dim3( 1024 ), 0, stream, logits, probs, nVocab, invT, invTDev );
+		else
+			hipLaunchKernelGGL( softMaxRows<true>, dim3( rows ), dim3( 1024 ), 0, stream, logits, probs, nVocab, invT, invTDev );
+		WH_HIP( hipGetLastError() );
+		return 0;
+	}
+
+	int launchNoSpeechGather( const float* probs, const void* spreadScratch, int rows, int nVocab, int tokenSolm, float* out, hipStream_t stream )
+	{
+		if( rows < 1 || tokenSolm < 0 || tokenSolm >= nVocab || !probs || !out ) { setError( "noSpeechGather: bad argument" ); return -1; }
+		hipLaunchKernelGGL( noSpeechGatherKernel, dim3( rows ), dim3( 64 ), 0, stream, probs, (const SamplePart*)spreadScratch, nVocab, tokenSolm, out );
+		WH_HIP( hipGetLastError() );
+		return 0;
+	}
+
+	int launchLangProbs( const float* logits, long long rowStride, int rows, int nVocab, int tokenSot, int nLang, float* langP, int* best, hipStream_t stream )
+	{
+		if( rows < 1 || nLang < 1 || nLang > 1024 || tokenSot < 0 || (long long)tokenSot + 1 + nLang > nVocab || rowStride < nVocab || nVocab > SC_PER * 1024 )
+		{
+			setError( "langProbs: the language block must lie inside the row and hold 1 .. 1024 tokens, the vocabulary at most 52224" );
+			return -1;
+		}
+		hipLaunchKernelGGL( langProbsKernel, dim3( rows ), dim3( 1024 ), 0, stream, logits, rowStride, nVocab, tokenSot, nLang, langP, best );
+		WH_HIP( hipGetLastError() );
+		return 0;
+	}
+
+	int launchLangGather( const float* probs, long long rowStride, int rows, int nVocab, int tokenSot, int nLang, float* langP, int* best, hipStream_t stream )
+	{
+		if( rows < 1 || nLang < 1 || nLang > 1024 || tokenSot < 0 || (long long)tokenSot + 1 + nLang > nVocab || rowStride < nVocab )
+		{
+			setError( "langGather: the language block must lie inside the row and hold 1 .. 1024 tokens" );
+			return -1;
+		}
+		hipLaunchKernelGGL( langGatherKernel, dim3( rows ), dim3( 1024 ), 0, stream, probs, rowStride, tokenSot, nLang, langP, best );
+		WH_HIP( hipGetLastError() );
+		return 0;
+	}
+
+	int launchSampleBest( const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot,
+		int forceTimestamp, int isInitial, TokenData* out, hipStream_t stream )
+	{
+		hipLaunchKernelGGL( sampleBestKernel, dim3( rows ), dim3( 1024 ), 0, stream, probs, nVocab, tokenBeg, tokenSot, tokenSolm,
+			tokenNot, forceTimestamp, isInitial, out );
+		WH_HIP( hipGetLastError() );
+		return 0;
+	}
+
+	int launchBeamCandidates( const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot,
+		int forceTimestamp, int isInitial, int width, TokenData* out, hipStream_t stream )
+	{
+		if( width < 1 || width > 8 ) { setError( "beamCandidates: width must be 1 .. 8" ); return -1; }
+		hipLaunchKernelGGL( beamCandidatesKernel, dim3( rows ), dim3( 1024 ), 0, stream, probs, nVocab, tokenBeg, tokenSot, tokenSolm,
+			tokenNot, forceTimestamp, isInitial, width, out );
+		WH_HIP( hipGetLastError() );
+		return 0;
+	}
+
+	int launchSoftMaxSample( const float* logits, float* probsOut, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm,
+		int tokenNot, const DecodeState* state, TokenData* out, int* nextTokens, SampleMailbox mail, hipStream_t stream )
+	{
+		if( nVocab > SC_PER * 1024 )
+		{
+			setError( "softMaxSample: vocabulary larger than 52224" );
+			return -1;
+		}
+		hipLaunchKernelGGL( softMaxSampleKernel, dim3( rows ), dim3( 1024 ), 0, stream, logits, probsOut, nVocab, tokenBeg, tokenSot, tokenSolm,
+			tokenNot, state, out, nextTokens, mail );
+		WH_HIP( hipGetLastError() );
+		return 0;
+	}
+
+	size_t sampleSpreadScratchBytes( int rows ) { return (size_t)rows * SP_G * ( sizeof( SamplePart ) + sizeof( float ) ); }
+	int launchSoftMaxSampleSpread( const float* logits, float* eOut, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot,
+		const DecodeState* state, TokenData* out, int* nextTokens, SampleMailbox mail, void* scratch, hipStream_t stream )
+	{
+		if( nVocab > SP_G * 256 * 4 || rows < 1 || !scratch || !eOut ) { setError( "softMaxSampleSpread: bad argument" ); return -1; }
+		SamplePart* const parts = (SamplePart*)scratch;
+		float* const partMax = (float*)( parts + (size_t)rows * SP_G );
+		hipLaunchKernelGGL( sampleSpreadMax, dim3( SP_G, rows ), dim3( 256 ), 0, stream, logits, nVocab, partMax );
+		hipLaunchKernelGGL( sampleSpreadExp, dim3( SP_G, rows ), dim3( 256 ), 0, stream, logits, nVocab, tokenBeg, partMax, state, eOut, parts );
+		hipLaunchKernelGGL( sampleSpreadFinal, dim3( rows ), dim3( 64 ), 0, stream, parts, eOut, nVocab, tokenBeg, tokenSot, tokenSolm, tokenNot, state, out,
+			nextTokens, mail );
+		WH_HIP( hipGetLastError() );
+		return 0;
+	}
+
+	int launchAdvanceState( DecodeState* state, int* seqPos, int rows, hipStream_t stream )
+	{
+		hipLaunchKernelGGL( advanceStateKernel, dim3( ( rows + 127 ) / 128 ), dim3( 128 ), 0, stream, state, seqPos, rows );
+		WH_HIP( hipGetLastError() );
+		return 0;
+	}
 	int launchSampleDraw( const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot, int forceTimestamp, int isInitial,
 		unsigned long long seed, unsigned nonce, const int* positions, TokenData* out, hipStream_t stream )
 	{
