@@ -364,7 +364,7 @@ namespace Whisper
 	// P( <|nospeech|> ) > noSpeechThold and avgLogprob < logprobThold is skipped instead: no segments, no prompt carry-over, the stream moves on. The rules are
 	// DESIGN.md section 7; whisper_amd/host/decodeFallback.h holds them. A free function: iContext's vtable is the reference's. nullptr = off, the state of every
 	// new context: the transcript of a run with the feature off is what it always was. With it on, eSamplingStrategy::BeamSearch answers E_NOTIMPL; the batch
-	// runner has no such setting. E_INVALIDARG for a context of another library, a NaN threshold, or 0 < temperatureInc < 0.01.
+	// runner has its own switch, setBatchDecodingFallback below. E_INVALIDARG for a context of another library, a NaN threshold, or 0 < temperatureInc < 0.01.
 	struct sDecodingFallback
 	{
 		float temperatureInc = 0.2f;	// <= 0: one greedy attempt, gates only
@@ -387,6 +387,19 @@ namespace Whisper
 	};
 	// count in: the capacity of `stats`; out: the number of windows (stats may be nullptr to ask for it). Empty when the run had the feature off.
 	WHISPER_EXPORT HRESULT getWindowStats( const iContext* context, sWindowStats* stats, uint32_t* count );
+	// The same feature for the lock-step batch runner: every later run of the runner scores each stream's windows with the rules above. A window whose attempt
+	// fails STAYS in its slot -- same seek, same prompt -- and is decoded again in its group's next round at the next temperature while its neighbours move on
+	// to new windows: a retried window costs one slot-round (a round encodes and decodes every slot whatever it holds), and the rows of one decode step sample
+	// each under its own temperature, key and nonce (wh_context_set_sampling_rows). The draws of stream i use the key seed + i: the chunks of one recording all
+	// stand at seek 0 and must not share draws. A stream's transcript does not depend on its neighbours' retries; with gates that never fire it is the transcript
+	// of the runner with the feature off. With maxSlots <= 4 a greedy row of a round in which a neighbour retries is sampled by another kernel than in an
+	// all-greedy round (the spread sampler has no per-row form): its ptsum may then differ in the last bits of a double sum. A stream whose every window was skipped as silence ends
+	// with S_FALSE in perStream and an empty result, like a recording too short to transcribe. nullptr = off, the state of every
+	// new runner. E_INVALIDARG as setDecodingFallback; E_NOTIMPL where the scheduler was built without the device's per-row sampler. BeamSearch and AlignTokens
+	// in a batch stay E_NOTIMPL.
+	WHISPER_EXPORT HRESULT setBatchDecodingFallback( iBatchRunner* runner, const sDecodingFallback* params );
+	// What the fallback did with each window of the stream a batch runner's result object belongs to, in order; count as getWindowStats. Empty with the feature off.
+	WHISPER_EXPORT HRESULT getResultWindowStats( const iTranscribeResult* result, sWindowStats* stats, uint32_t* count );
 	// Extension (no counterpart in whisper.def): ONE long recording onto the batched path. The buffer is cut into pieces of at most maxLen samples at pauses,
 	// found with the reference's voice-activity detector (Whisper/Whisper/voiceActivityDetection.cpp, which its capture loop uses to fire a transcription when
 	// the speaker pauses): the per-frame features come from the device (wh_vad_features of whisper_hip.h, on the calling thread's current device), the decision

@@ -76,6 +76,11 @@ int32_t whisperc_model_set_alignment_heads( void* model, const int32_t* layerHea
  * cap smaller than that with a non-NULL out is E_BOUNDS. */
 int32_t whisperc_set_fallback( void* ctx, int32_t on, float temperatureInc, float logprobThold, float entropyThold, float noSpeechThold, uint64_t seed );
 int32_t whisperc_window_stats( void* ctx, void* out, uint32_t cap, uint32_t* count );
+/* The same for a batch runner (Whisper::setBatchDecodingFallback): every later run of the runner; a window whose attempt fails is decoded again in its slot in
+ * the group's next round (one slot-round per retry), stream i draws under the key seed + i. whisperc_tr_window_stats: Whisper::getResultWindowStats, the
+ * windows of the stream a result object of whisperc_batch_run belongs to; out / cap / count as whisperc_window_stats. */
+int32_t whisperc_batch_set_fallback( void* runner, int32_t on, float temperatureInc, float logprobThold, float entropyThold, float noSpeechThold, uint64_t seed );
+int32_t whisperc_tr_window_stats( void* result, void* out, uint32_t cap, uint32_t* count );
 /* iContext::getResults( Tokens | Timestamps ) + iTranscribeResult::getSize / getSegments / getTokens; times in 100 ns ticks */
 int32_t whisperc_result_counts( void* ctx, uint32_t* segments, uint32_t* tokens );
 int32_t whisperc_result_segment( void* ctx, uint32_t index, uint64_t* t0, uint64_t* t1, uint32_t* firstToken, uint32_t* countTokens,

@@ -442,6 +442,19 @@ WH_API int wh_decode_window_ready( wh_context* c, int first, int count );
  * going back to 0 replays a greedy graph. WH_E_INVALIDARG for a temperature that is negative, NaN or above 4, and, above 0, on a hypothesis-group context or
  * under WH_FLAG_PARITY_EXACT. A context that never calls it launches, allocates and captures what it always did. */
 WH_API int wh_context_set_sampling( wh_context* c, float temperature, uint64_t seed, uint32_t nonce );
+/* Per-row sampling for a lock-step batch (wh_decode_window_start_ragged and its chunks) whose sequences stand at different attempts: sequence r of every
+ * following step is greedy where temperature[ r ] == 0 and otherwise samples at temperature[ r ] in (0, 4] under its own Philox key seed[ r ] and nonce[ r ];
+ * sequences beyond `rows` are greedy. HOST arrays [rows], 1 <= rows <= the context's sequences. Every step is then two one-workgroup-per-row kernels, whatever
+ * the batch: the table softmax of logits * ( 1 / T ) with the factor read per row (1.0f for a greedy row: x * 1.0f is x, the greedy probabilities bit for bit),
+ * and a draw kernel that gives a greedy row wh_op_sample_best's record and a sampled row wh_op_sample_draw's record for that row ALONE -- the Philox counter is
+ * ( position, 0, nonce[ r ], 0 ), so a stream's draws do not depend on the slot it sits in. The records are uploaded through pinned staging behind what the
+ * stream holds (work queued earlier still reads the old ones; the call does not wait for the stream). The mode has a captured step graph of its own, which
+ * lives next to the greedy one: entering and leaving the mode recaptures nothing. rows == 0, or every temperature 0, turns the mode off: the greedy sampler
+ * and graph, exactly what a context that never made the call launches (at <= 4 sequences that is the spread sampler, whose ptsum may differ from a greedy row
+ * of a per-row step in the last bits of a double sum). wh_context_set_no_speech gathers probabilities in this mode as in the others.
+ * WH_E_INVALIDARG on a hypothesis-group context, under WH_FLAG_PARITY_EXACT, for a vocabulary above 65536, for a temperature that is NaN or outside [0, 4],
+ * and while wh_context_set_sampling has a temperature set (which in turn refuses a temperature while this mode is on). */
+WH_API int wh_context_set_sampling_rows( wh_context* c, int rows, const float* temperature, const uint64_t* seed, const uint32_t* nonce );
 /* The model's own "no speech" probability of a window: when on, wh_decode_window_start / _start_ragged queue one small gather behind the prompt step's sample,
  * p[ token_solm ] of every sequence's row of probabilities as that step formed it (the id the reference calls token_solm, 50361 + 1 when multilingual, is
  * <|nospeech|> in OpenAI's vocabulary). wh_decode_window_no_speech: HOST float [batch] of the window in progress; waits for the first sample only. The buffer
@@ -551,6 +564,17 @@ WH_API int wh_op_sample_best( void* stream, const float* probs, int rows, int nV
 WH_API int wh_op_vocab_soft_max_scaled( void* stream, const float* logits, float invT, float* probs, int rows, int cols );
 WH_API int wh_op_sample_draw( void* stream, const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot,
 	int forceTimestamp, int isInitial, uint64_t seed, uint32_t nonce, const int32_t* positionsDev, wh_token_data* out );
+/* The per-row step of wh_context_set_sampling_rows outside a context: probsOut [rows][nVocab] (device) = the table softmax of logits * ( 1 / T_row ) (factor 1
+ * for a greedy row), out[ row ] (device) = wh_op_sample_best's record of a greedy row, wh_op_sample_draw's record of a sampled row run on that row alone with
+ * its seed and nonce. rowParams: HOST [rows]. The call waits for the stream. */
+typedef struct wh_sample_row
+{
+	float temperature;	/* 0 = greedy, else (0, 4] */
+	uint32_t nonce;
+	uint64_t seed;
+} wh_sample_row;
+WH_API int wh_op_sample_rows( void* stream, const float* logits, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot,
+	int forceTimestamp, int isInitial, const wh_sample_row* rowParams, const int32_t* positionsDev, float* probsOut, wh_token_data* out );
 WH_API int wh_op_philox_u( void* stream, uint64_t seed, uint32_t nonce, int rows, const int32_t* positionsDev, double* uOut );
 /* wh_beam_candidates on probabilities [rows][nVocab]: out [rows][width], width 1 .. 8. */
 WH_API int wh_op_beam_candidates( void* stream, const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot,

@@ -77,6 +77,8 @@ def lib():
         L.whisperc_model_set_alignment_heads.argtypes = [vp, vp, C.c_int32]
         L.whisperc_set_fallback.argtypes = [vp, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint64]
         L.whisperc_window_stats.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.whisperc_batch_set_fallback.argtypes = [vp, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint64]
+        L.whisperc_tr_window_stats.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
         L.whisperc_resample.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64)]
         L.whisperc_load_audio.argtypes = [C.c_char_p, C.c_int32, vp, C.c_int64, C.POINTER(C.c_int64)]
         L.whisperc_run_full_stereo.argtypes = [vp, vp, vp, C.c_uint32, C.c_char_p, C.c_uint32, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]
@@ -395,14 +397,7 @@ class Context:
     def window_stats(self):
         """What the fallback did with each window of the last run: [{seek, attempts, temperature, no_speech, avg_logprob, entropy, skipped}], empty when
         the feature was off."""
-        n = C.c_uint32()
-        _check(lib().whisperc_window_stats(self.h, None, 0, C.byref(n)), "getWindowStats")
-        if n.value == 0:
-            return []
-        arr = (WindowStatsC * n.value)()
-        _check(lib().whisperc_window_stats(self.h, arr, n.value, C.byref(n)), "getWindowStats")
-        return [dict(seek=w.seek, attempts=w.attempts, temperature=w.temperature, no_speech=w.noSpeech, avg_logprob=w.avgLogprob, entropy=w.entropy,
-                     skipped=bool(w.skipped)) for w in arr]
+        return _window_stats_of(lib().whisperc_window_stats, self.h, "getWindowStats")
 
     @property
     def detected_language(self):
@@ -448,6 +443,18 @@ class Context:
         _check(lib().whisperc_timings_print(self.h), "timingsPrint")
 
 
+def _window_stats_of(fn, h, what) -> list:
+    """whisperc_window_stats / whisperc_tr_window_stats -> [{seek, attempts, temperature, no_speech, avg_logprob, entropy, skipped}]"""
+    n = C.c_uint32()
+    _check(fn(h, None, 0, C.byref(n)), what)
+    if n.value == 0:
+        return []
+    arr = (WindowStatsC * n.value)()
+    _check(fn(h, arr, n.value, C.byref(n)), what)
+    return [dict(seek=w.seek, attempts=w.attempts, temperature=w.temperature, no_speech=w.noSpeech, avg_logprob=w.avgLogprob, entropy=w.entropy,
+                 skipped=bool(w.skipped)) for w in arr]
+
+
 def read_result(h) -> list:
     """iTranscribeResult -> list of segments {t0, t1 (100 ns ticks), text, tokens[{id, p, pt, ptsum, t0, t1, vlen}]}."""
     L = lib()
@@ -486,6 +493,16 @@ class BatchRunner:
             self.close()
         except Exception:
             pass
+
+    def set_fallback(self, temperature_inc: Optional[float] = 0.2, logprob_thold: float = -1.0, entropy_thold: float = 2.4, no_speech_thold: float = 0.6, seed: int = 0):
+        """Whisper::setBatchDecodingFallback: Context.set_fallback's gates and temperature retries for every stream of this runner's later runs
+        (set_fallback(None) turns them off, the state of a new runner). A window whose attempt fails stays in its slot and is decoded again in the next
+        round at the next temperature -- one slot-round per retry -- while its neighbours move on; stream i draws under the key seed + i. After run /
+        run_split, window_stats holds one list per stream (Context.window_stats' records; None for a stream without a result)."""
+        if temperature_inc is None:
+            _check(lib().whisperc_batch_set_fallback(self.h, 0, 0.0, 0.0, 0.0, 0.0, 0), "setBatchDecodingFallback")
+            return
+        _check(lib().whisperc_batch_set_fallback(self.h, 1, float(temperature_inc), logprob_thold, entropy_thold, no_speech_thold, seed), "setBatchDecodingFallback")
 
     def run(self, streams, language: str = "en", flags: int = 0, max_tokens: int = 0, prompt: Optional[Sequence[int]] = None,
             n_max_text_ctx: int = -1, want_results: bool = True, sample_rate: int = 16000, stereo: Optional[Sequence] = None):
@@ -529,8 +546,10 @@ class BatchRunner:
         out = []
         self.languages = []
         self.speakers = []
+        self.window_stats = []
         for i in range(n):
             out.append(read_result(res[i]) if (res[i] and want_results) else None)
+            self.window_stats.append(_window_stats_of(lib().whisperc_tr_window_stats, res[i], "getResultWindowStats") if res[i] else None)
             self.speakers.append(_speakers_of(lib().whisperc_tr_speakers, res[i]) if (res[i] and want_results) else None)
             code, p = C.create_string_buffer(8), C.c_float()
             detected = bool(res[i]) and lib().whisperc_tr_language(res[i], code, C.byref(p)) == 0

@@ -55,6 +55,7 @@ EXPORTS = [
     "wh_dequantize",
     "wh_model_set_alignment_heads", "wh_align_tokens", "wh_op_align_matrix", "wh_op_dtw",
     "wh_op_vocab_soft_max_scaled", "wh_op_sample_draw", "wh_op_philox_u", "wh_context_set_sampling", "wh_context_set_no_speech", "wh_decode_window_no_speech",
+    "wh_context_set_sampling_rows", "wh_op_sample_rows",
 ]
 
 
@@ -64,6 +65,10 @@ class HParamsC(C.Structure):
 
 class TokenDataC(C.Structure):
     _fields_ = [("id", C.c_int32), ("tid", C.c_int32), ("p", C.c_float), ("pt", C.c_float), ("ptsum", C.c_float)]
+
+
+class SampleRowC(C.Structure):
+    _fields_ = [("temperature", C.c_float), ("nonce", C.c_uint32), ("seed", C.c_uint64)]
 
 
 class BeamRulesC(C.Structure):
@@ -189,6 +194,8 @@ def lib():
         L.wh_op_philox_u.argtypes = [vp, C.c_uint64, C.c_uint32, i32, vp, vp]
         L.wh_context_set_sampling.argtypes = [vp, C.c_float, C.c_uint64, C.c_uint32]
         L.wh_context_set_no_speech.argtypes = [vp, i32]
+        L.wh_context_set_sampling_rows.argtypes = [vp, i32, vp, vp, vp]
+        L.wh_op_sample_rows.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]
         L.wh_decode_window_no_speech.argtypes = [vp, vp]
         _lib = L
     return _lib
@@ -337,6 +344,18 @@ class HipContext:
         """temperature > 0: the device-side loop samples from softmax( logits / temperature ) (Philox draws keyed by seed, nonce, position and row);
         0 restores the greedy sampler."""
         check(lib().wh_context_set_sampling(self.handle, temperature, seed, nonce))
+
+    def set_sampling_rows(self, temperatures=None, seeds=None, nonces=None):
+        """Per-row sampling: sequence r of every following step is greedy where temperatures[r] == 0, else samples at that temperature under its own
+        seed and nonce. None (or no rows) turns the mode off."""
+        if temperatures is None or len(temperatures) == 0:
+            check(lib().wh_context_set_sampling_rows(self.handle, 0, None, None, None))
+            return
+        t = np.ascontiguousarray(temperatures, np.float32)
+        s = np.ascontiguousarray(seeds if seeds is not None else np.zeros(len(t)), np.uint64)
+        n = np.ascontiguousarray(nonces if nonces is not None else np.zeros(len(t)), np.uint32)
+        assert len(s) == len(t) and len(n) == len(t)
+        check(lib().wh_context_set_sampling_rows(self.handle, len(t), t.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p), n.ctypes.data_as(C.c_void_p)))
 
     def set_no_speech(self, on: bool):
         """on: every window start also gathers P( <|nospeech|> ) of the prompt step (window_no_speech)."""

@@ -226,7 +226,7 @@ void wh_context_destroy( wh_context* c )
 	liveContexts( c->m ).fetch_sub( 1 );
 	(void)bindDevice( c->m );
 	if( c->stream ) (void)hipStreamSynchronize( c->stream );
-	if( c->graphExec ) (void)hipGraphExecDestroy( c->graphExec );
+	c->destroyStepGraphs();
 	if( c->beamGraphExec ) (void)hipGraphExecDestroy( c->beamGraphExec );
 	for( auto& mk : c->marks ) (void)hipEventDestroy( mk.ev );
 	for( hipEvent_t e : c->markPool ) (void)hipEventDestroy( e );
@@ -241,6 +241,8 @@ void wh_context_destroy( wh_context* c )
 	}
 	if( c->encGateEv ) (void)hipEventDestroy( c->encGateEv );
 	if( c->noSpeechEv ) (void)hipEventDestroy( c->noSpeechEv );
+	if( c->sampleRowsEv ) (void)hipEventDestroy( c->sampleRowsEv );
+	if( c->sampleRowsPin ) (void)hipHostFree( c->sampleRowsPin );
 	int bad = 0;
 	for( const Allocation& a : c->allocations ) bad += guardedFree( a ) > 0;
 	if( bad != 0 ) fprintf( stderr, "WH_GUARD_VIOLATION: context %p wrote outside its buffers\n", (void*)c );
@@ -269,7 +271,7 @@ int wh_context_set_audio_ctx( wh_context* c, int audioCtx )
 	WH_HIP( hipStreamSynchronize( c->stream ) );
 	// every launch reads the key count from the context (row strides of the caches included), so the override is the context's T; what was captured or
 	// encoded with another T is void
-	if( c->graphExec ) { (void)hipGraphExecDestroy( c->graphExec ); c->graphExec = nullptr; c->graphBatch = 0; }
+	c->destroyStepGraphs();
 	if( c->beamGraphExec ) { (void)hipGraphExecDestroy( c->beamGraphExec ); c->beamGraphExec = nullptr; c->beamGraphBatch = 0; }
 	c->T = T;
 	c->Tpad = roundUp( T, 256 );

@@ -451,9 +451,45 @@ int wh::uploadDecodeState( wh_context* c, int batch, const DecodeState& s, const
 extern "C" {
 
 // What a captured step graph depends on besides the batch: the parity mode and the sampler (greedy or temperature: other kernels, the same graph for every temperature)
+constexpr uint32_t STEP_KEY_ROWS = 0x40000u;	  // per-row sampling (wh_context_set_sampling_rows)
 static uint32_t stepGraphKey( const wh_context* c )
 {
-	return ( ( c->flags & WH_FLAG_PARITY_PV ) ? ( 0x10000u | (uint32_t)c->parityThreads ) : 0u ) | ( c->temperature > 0.0f ? 0x20000u : 0u );
+	return ( ( c->flags & WH_FLAG_PARITY_PV ) ? ( 0x10000u | (uint32_t)c->parityThreads ) : 0u ) | ( c->temperature > 0.0f ? 0x20000u : 0u ) |
+		( c->sampleRowsOn ? STEP_KEY_ROWS : 0u );
+}
+// Captured steps that cannot serve ( batch, key ) or its sibling in the other per-row mode go (see wh_context::stepGraphs); true when one went
+static bool dropStaleStepGraphs( wh_context* c, int batch, uint32_t key )
+{
+	bool dropped = false;
+	for( size_t i = 0; i < c->stepGraphs.size(); )
+	{
+		const wh_context::StepGraph& g = c->stepGraphs[ i ];
+		if( g.batch != batch || ( ( g.key ^ key ) & ~STEP_KEY_ROWS ) != 0 )
+		{
+			(void)hipGraphExecDestroy( g.exec );
+			c->stepGraphs.erase( c->stepGraphs.begin() + (ptrdiff_t)i );
+			dropped = true;
+		}
+		else i++;
+	}
+	return dropped;
+}
+// One greedyStep of `batch` rows in the context's present mode, captured on its stream and kept under ( batch, key )
+static int greedyStep( wh_context* c, int batch );
+static int captureStepGraph( wh_context* c, int batch, uint32_t key, hipGraphExec_t& exec )
+{
+	hipGraph_t graph = nullptr;
+	WH_HIP( hipStreamBeginCapture( c->stream, hipStreamCaptureModeThreadLocal ) );
+	const int rc = greedyStep( c, batch );
+	const hipError_t e = hipStreamEndCapture( c->stream, &graph );
+	if( rc != 0 ) { if( graph ) (void)hipGraphDestroy( graph ); return rc; }
+	if( e != hipSuccess ) return hipFail( e, "hipStreamEndCapture", __FILE__, __LINE__ );
+	exec = nullptr;
+	const hipError_t e2 = hipGraphInstantiate( &exec, graph, nullptr, nullptr, 0 );
+	(void)hipGraphDestroy( graph );
+	if( e2 != hipSuccess ) { exec = nullptr; return hipFail( e2, "hipGraphInstantiate", __FILE__, __LINE__ ); }
+	c->stepGraphs.push_back( wh_context::StepGraph{ batch, key, exec } );
+	return 0;
 }
 
 // logits -> table softmax -> sampleBest -> token data + next token: one workgroup per row, or -- for the few rows of one stream -- every row cut
@@ -463,6 +499,14 @@ static int sampleStep( wh_context* c, int batch, hipStream_t st )
 	const wh_hparams& hp = c->m->hp;
 	const SpecialIds sp = specialIds( hp );
 	const int sot = sp.sot, solm = sp.solm, tnot = sp.tnot, beg = sp.beg;
+	if( c->sampleRowsOn )
+	{
+		// wh_context_set_sampling_rows: the same two one-workgroup kernels with a record per row -- a greedy row's factor is 1 and its draw ends behind sampleBest's pick
+		WH_CHECK( profiled( c, KC_SOFTMAX, 11.0 * batch * hp.n_vocab, 8.0 * batch * hp.n_vocab,
+			[ & ]() { return launchVocabSoftMaxRows( c->logits, c->sampleRows, c->probs, batch, hp.n_vocab, st ); } ) );
+		return profiled( c, KC_SAMPLE, 4.0 * batch * hp.n_vocab, 8.0 * batch * hp.n_vocab,
+			[ & ]() { return launchSampleRows( c->probs, batch, hp.n_vocab, beg, sot, solm, tnot, 0, 0, c->state, c->sampleRows, c->seqPos, c->greedyOut, c->tokensDev, c->mailDev, st ); } );
+	}
 	if( c->temperature > 0.0f )
 	{
 		// wh_context_set_sampling: the table softmax of logits / T, then one draw per row under sampleBest's masks (sample.hip), which also does the loop's bookkeeping
@@ -512,32 +556,19 @@ int wh_decode_greedy( wh_context* c, int batch, const int32_t* firstTokens, int 
 	if( useGraph )
 	{
 		const uint32_t key = stepGraphKey( c );
-		if( c->graphExec && ( c->graphBatch != batch || c->graphKey != key ) )
+		hipGraphExec_t exec = c->stepGraph( batch, key );
+		if( !exec )
 		{
-			(void)hipGraphExecDestroy( c->graphExec );
-			c->graphExec = nullptr;
-		}
-		if( !c->graphExec )
-		{
+			dropStaleStepGraphs( c, batch, key );	   // (the stream is idle here)
 			// one eager step first: it sets the per-kernel function attributes, which capture does not allow
 			WH_CHECK( greedyStep( c, batch ) );
 			WH_HIP( hipStreamSynchronize( st ) );
 			WH_CHECK( uploadDecodeState( c, batch, init, nullptr, nPast ) );
 			WH_HIP( hipMemcpyAsync( c->tokensDev, firstTokens, sizeof( int32_t ) * batch, hipMemcpyHostToDevice, st ) );
 			WH_HIP( hipStreamSynchronize( st ) );
-			hipGraph_t graph = nullptr;
-			WH_HIP( hipStreamBeginCapture( st, hipStreamCaptureModeThreadLocal ) );
-			const int rc = greedyStep( c, batch );
-			const hipError_t e = hipStreamEndCapture( st, &graph );
-			if( rc != 0 ) { if( graph ) (void)hipGraphDestroy( graph ); return rc; }
-			if( e != hipSuccess ) return hipFail( e, "hipStreamEndCapture", __FILE__, __LINE__ );
-			const hipError_t e2 = hipGraphInstantiate( &c->graphExec, graph, nullptr, nullptr, 0 );
-			(void)hipGraphDestroy( graph );
-			if( e2 != hipSuccess ) { c->graphExec = nullptr; return hipFail( e2, "hipGraphInstantiate", __FILE__, __LINE__ ); }
-			c->graphBatch = batch;
-			c->graphKey = key;
+			WH_CHECK( captureStepGraph( c, batch, key, exec ) );
 		}
-		for( int s = 0; s < nSteps; s++ ) WH_HIP( hipGraphLaunch( c->graphExec, st ) );
+		for( int s = 0; s < nSteps; s++ ) WH_HIP( hipGraphLaunch( exec, st ) );
 	}
 	else
 	{
@@ -599,14 +630,12 @@ static int windowStart( wh_context* c, int batch, const int32_t* promptTokens, c
 	c->marks.clear();
 	const bool useGraph = !c->prof.on && !( c->flags & WH_FLAG_NO_GRAPH ) && nSteps > 0 && !debugSync();
 	const uint32_t key = stepGraphKey( c );
-	if( useGraph && c->graphExec && ( c->graphBatch != batch || c->graphKey != key ) )
+	hipGraphExec_t exec = useGraph ? c->stepGraph( batch, key ) : nullptr;
+	if( useGraph && !exec )
 	{
+		// a graph that can no longer be replayed may still be queued: wait before it goes
 		WH_HIP( hipStreamSynchronize( st ) );
-		(void)hipGraphExecDestroy( c->graphExec );
-		c->graphExec = nullptr;
-	}
-	if( useGraph && !c->graphExec )
-	{
+		dropStaleStepGraphs( c, batch, key );
 		// first use for this batch size: one eager step (sets the per-kernel function attributes), then capture. Blocking,
 		// once per context; the state it leaves behind is overwritten below.
 		const DecodeState warm = { 0, 0, 0, 0 };
@@ -621,17 +650,7 @@ static int windowStart( wh_context* c, int batch, const int32_t* promptTokens, c
 		WH_HIP( hipStreamSynchronize( st ) );
 		WH_CHECK( greedyStep( c, batch ) );
 		WH_HIP( hipStreamSynchronize( st ) );
-		hipGraph_t graph = nullptr;
-		WH_HIP( hipStreamBeginCapture( st, hipStreamCaptureModeThreadLocal ) );
-		const int rc = greedyStep( c, batch );
-		const hipError_t e = hipStreamEndCapture( st, &graph );
-		if( rc != 0 ) { if( graph ) (void)hipGraphDestroy( graph ); return rc; }
-		if( e != hipSuccess ) return hipFail( e, "hipStreamEndCapture", __FILE__, __LINE__ );
-		const hipError_t e2 = hipGraphInstantiate( &c->graphExec, graph, nullptr, nullptr, 0 );
-		(void)hipGraphDestroy( graph );
-		if( e2 != hipSuccess ) { c->graphExec = nullptr; return hipFail( e2, "hipGraphInstantiate", __FILE__, __LINE__ ); }
-		c->graphBatch = batch;
-		c->graphKey = key;
+		WH_CHECK( captureStepGraph( c, batch, key, exec ) );
 	}
 	// a new generation per window: stamps of earlier windows in the mailbox can never be taken for this one's
 	// (only for the few sequences of a stream whose host loop reads every sample; a lock-step batch is read chunk by chunk through events)
@@ -660,14 +679,14 @@ static int windowStart( wh_context* c, int batch, const int32_t* promptTokens, c
 		{
 			// p[ solm ] of the rows the first sample just left in c->probs (the spread sampler leaves unnormalised e and its slice sums), and an event behind it:
 			// wh_decode_window_no_speech waits for the first sample only
-			const bool spread = !( c->temperature > 0.0f ) && batch <= SMALL_MAX_ROWS && ( g_tuning & TUNE_SAMPLE_SPREAD );
+			const bool spread = !( c->temperature > 0.0f ) && !c->sampleRowsOn && batch <= SMALL_MAX_ROWS && ( g_tuning & TUNE_SAMPLE_SPREAD );
 			WH_CHECK( launchNoSpeechGather( c->probs, spread ? c->sampleScratch : nullptr, batch, hp.n_vocab, solm, c->noSpeechDev, st ) );
 			WH_HIP( hipEventRecord( c->noSpeechEv, st ) );
 			c->noSpeechRows = batch;
 		}
 	}
 	if( useGraph )
-		for( int s = 0; s < nSteps; s++ ) WH_HIP( hipGraphLaunch( c->graphExec, st ) );
+		for( int s = 0; s < nSteps; s++ ) WH_HIP( hipGraphLaunch( exec, st ) );
 	else
 		for( int s = 0; s < nSteps; s++ )
 		{
@@ -704,7 +723,8 @@ int wh_decode_window_continue( wh_context* c, int nSteps )
 	const int batch = c->lastBatch;
 	const bool useGraph = !c->prof.on && !( c->flags & WH_FLAG_NO_GRAPH ) && !debugSync();
 	const uint32_t key = stepGraphKey( c );
-	if( useGraph && ( !c->graphExec || c->graphBatch != batch || c->graphKey != key ) )
+	hipGraphExec_t exec = useGraph ? c->stepGraph( batch, key ) : nullptr;
+	if( useGraph && !exec )
 	{
 		// the window was started with nSteps == 0 (no graph yet): capture now. The eager warm-up step must not disturb
 		// the window's device state, so the state and the pending token are saved around it.
@@ -714,26 +734,16 @@ int wh_decode_window_continue( wh_context* c, int nSteps )
 		WH_HIP( hipMemcpy( &saved, c->state, sizeof( saved ), hipMemcpyDeviceToHost ) );
 		WH_HIP( hipMemcpy( savedPos.data(), c->seqPos, sizeof( int32_t ) * batch, hipMemcpyDeviceToHost ) );
 		WH_HIP( hipMemcpy( tok.data(), c->tokensDev, sizeof( int32_t ) * batch, hipMemcpyDeviceToHost ) );
-		if( c->graphExec ) { (void)hipGraphExecDestroy( c->graphExec ); c->graphExec = nullptr; }
+		dropStaleStepGraphs( c, batch, key );
 		WH_CHECK( greedyStep( c, batch ) );
 		WH_HIP( hipStreamSynchronize( c->stream ) );
-		hipGraph_t graph = nullptr;
-		WH_HIP( hipStreamBeginCapture( c->stream, hipStreamCaptureModeThreadLocal ) );
-		const int rc = greedyStep( c, batch );
-		const hipError_t e = hipStreamEndCapture( c->stream, &graph );
-		if( rc != 0 ) { if( graph ) (void)hipGraphDestroy( graph ); return rc; }
-		if( e != hipSuccess ) return hipFail( e, "hipStreamEndCapture", __FILE__, __LINE__ );
-		const hipError_t e2 = hipGraphInstantiate( &c->graphExec, graph, nullptr, nullptr, 0 );
-		(void)hipGraphDestroy( graph );
-		if( e2 != hipSuccess ) { c->graphExec = nullptr; return hipFail( e2, "hipGraphInstantiate", __FILE__, __LINE__ ); }
-		c->graphBatch = batch;
-		c->graphKey = key;
+		WH_CHECK( captureStepGraph( c, batch, key, exec ) );
 		WH_HIP( hipMemcpy( c->state, &saved, sizeof( saved ), hipMemcpyHostToDevice ) );
 		WH_HIP( hipMemcpy( c->seqPos, savedPos.data(), sizeof( int32_t ) * batch, hipMemcpyHostToDevice ) );
 		WH_HIP( hipMemcpy( c->tokensDev, tok.data(), sizeof( int32_t ) * batch, hipMemcpyHostToDevice ) );
 	}
 	if( useGraph )
-		for( int s = 0; s < nSteps; s++ ) WH_HIP( hipGraphLaunch( c->graphExec, c->stream ) );
+		for( int s = 0; s < nSteps; s++ ) WH_HIP( hipGraphLaunch( exec, c->stream ) );
 	else
 		for( int s = 0; s < nSteps; s++ )
 		{
@@ -836,6 +846,7 @@ int wh_context_set_sampling( wh_context* c, float temperature, uint64_t seed, ui
 	if( temperature == 0.0f ) { c->temperature = 0.0f; return 0; }
 	if( c->hyp != 1 ) { setError( "context_set_sampling: not available on a hypothesis-group context" ); return WH_E_INVALIDARG; }
 	if( c->flags & WH_FLAG_PARITY_EXACT ) { setError( "context_set_sampling: not available under WH_FLAG_PARITY_EXACT" ); return WH_E_INVALIDARG; }
+	if( c->sampleRowsOn ) { setError( "context_set_sampling: per-row sampling (wh_context_set_sampling_rows) is on" ); return WH_E_INVALIDARG; }
 	WH_BIND( c->m );
 	if( c->m->hp.n_vocab > SAMPLE_DRAW_MAX_VOCAB ) { setError( "context_set_sampling: vocabulary larger than 65536" ); return WH_E_INVALIDARG; }
 	if( !c->sampleParams ) WH_CHECK( c->alloc( c->sampleParams, 1, wh_context::DONT_CARE, "sampleParams" ) );
@@ -843,6 +854,42 @@ int wh_context_set_sampling( wh_context* c, float temperature, uint64_t seed, ui
 	WH_HIP( hipMemcpyAsync( c->sampleParams, &p, sizeof( p ), hipMemcpyHostToDevice, c->stream ) );
 	WH_HIP( hipStreamSynchronize( c->stream ) );	 // `p` is on this stack
 	c->temperature = temperature;
+	return 0;
+}
+
+// Per-row sampling for a lock-step batch whose sequences stand at different attempts ("The batch runner"). The records go through pinned
+// staging behind what the stream holds -- a chunk queued earlier still reads the old ones -- and the call waits only for the staging's previous upload.
+int wh_context_set_sampling_rows( wh_context* c, int rows, const float* temperature, const uint64_t* seed, const uint32_t* nonce )
+{
+	if( !c || rows < 0 ) { setError( "context_set_sampling_rows: null context or a negative row count" ); return WH_E_INVALIDARG; }
+	if( rows == 0 ) { c->sampleRowsOn = 0; return 0; }
+	if( !temperature || !seed || !nonce || rows > c->maxSeq ) { setError( "context_set_sampling_rows: null array, or more rows than the context has sequences" ); return WH_E_INVALIDARG; }
+	if( c->hyp != 1 ) { setError( "context_set_sampling_rows: not available on a hypothesis-group context" ); return WH_E_INVALIDARG; }
+	if( c->flags & WH_FLAG_PARITY_EXACT ) { setError( "context_set_sampling_rows: not available under WH_FLAG_PARITY_EXACT" ); return WH_E_INVALIDARG; }
+	if( c->m->hp.n_vocab > SAMPLE_DRAW_MAX_VOCAB ) { setError( "context_set_sampling_rows: vocabulary larger than 65536" ); return WH_E_INVALIDARG; }
+	if( c->temperature > 0.0f ) { setError( "context_set_sampling_rows: wh_context_set_sampling has a temperature set" ); return WH_E_INVALIDARG; }
+	bool any = false;
+	for( int r = 0; r < rows; r++ )
+	{
+		if( !( temperature[ r ] >= 0.0f ) || temperature[ r ] > 4.0f ) { setError( "context_set_sampling_rows: a temperature lies outside [0, 4]" ); return WH_E_INVALIDARG; }
+		any = any || temperature[ r ] > 0.0f;
+	}
+	// every row greedy: the greedy sampler and its own captured graph, exactly what a context without this call launches
+	if( !any ) { c->sampleRowsOn = 0; return 0; }
+	WH_BIND( c->m );
+	if( !c->sampleRows )
+	{
+		WH_CHECK( c->alloc( c->sampleRows, (int64_t)c->maxSeq, wh_context::MUST_BE_ZERO, "sampleRows" ) );
+		WH_HIP( hipHostMalloc( (void**)&c->sampleRowsPin, sizeof( SampleRowParams ) * (size_t)c->maxSeq, hipHostMallocDefault ) );
+		WH_HIP( hipEventCreateWithFlags( &c->sampleRowsEv, hipEventDisableTiming ) );
+	}
+	else
+		WH_HIP( hipEventSynchronize( c->sampleRowsEv ) );	 // the staging's previous upload (long done in a scheduler's round; never the stream's queued work)
+	// sequences beyond `rows` are greedy: no record is ever read that was not written
+	for( int r = 0; r < c->maxSeq; r++ ) c->sampleRowsPin[ r ] = r < rows ? makeSampleRow( temperature[ r ], seed[ r ], nonce[ r ] ) : makeSampleRow( 0.0f, 0, 0 );
+	WH_HIP( hipMemcpyAsync( c->sampleRows, c->sampleRowsPin, sizeof( SampleRowParams ) * (size_t)c->maxSeq, hipMemcpyHostToDevice, c->stream ) );
+	WH_HIP( hipEventRecord( c->sampleRowsEv, c->stream ) );
+	c->sampleRowsOn = rows;
 	return 0;
 }
 

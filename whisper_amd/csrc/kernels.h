@@ -437,6 +437,27 @@ namespace wh
 	// softMaxSampleKernel's bookkeeping (out[ state->step * rows + row ], nextTokens[ row ], the mailbox stamp)
 	int launchSampleDrawStep( const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot, const DecodeState* state,
 		const SampleParams* params, const int* positions, TokenData* out, int* nextTokens, SampleMailbox mail, hipStream_t stream );
+	// Per-row sampling (wh_context_set_sampling_rows): what a lock-step batch keeps per sequence in device memory, so that the rows of ONE step may be greedy
+	// or sample at temperatures, keys and nonces of their own. A greedy row: sampled == 0 and invT == 1.0f ( __fmul_rn( x, 1.0f ) is x: launchVocabSoftMax's bits ).
+	struct SampleRowParams
+	{
+		float invT;
+		unsigned seedLo, seedHi, nonce;
+		unsigned sampled;
+		unsigned reserved[ 3 ];
+	};
+	inline SampleRowParams makeSampleRow( float temperature, unsigned long long seed, unsigned nonce )
+	{
+		const bool on = temperature > 0.0f;
+		return SampleRowParams{ on ? 1.0f / temperature : 1.0f, (unsigned)( seed & 0xffffffffull ), (unsigned)( seed >> 32 ), nonce, on ? 1u : 0u, { 0, 0, 0 } };
+	}
+	// launchVocabSoftMaxScaled with row r's factor rowParams[ r ].invT (device)
+	int launchVocabSoftMaxRows( const float* logits, const SampleRowParams* rowParams, float* probs, int rows, int nVocab, hipStream_t stream );
+	// The sample of every row under its own record: a greedy row gets launchSampleBest's record, a sampled row launchSampleDraw's for that row ALONE (the Philox
+	// counter is ( positions[ row ], 0, nonce, 0 ) under the row's key). state non-null: a step of the device-side loop (flags, output slot, mailbox and
+	// nextTokens as launchSampleDrawStep); null: the flags of the call, out [rows].
+	int launchSampleRows( const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot, int forceTimestamp, int isInitial,
+		const DecodeState* state, const SampleRowParams* rowParams, const int* positions, TokenData* out, int* nextTokens, SampleMailbox mail, hipStream_t stream );
 	// the uniform number of each row's draw: uOut [rows] (device)
 	int launchPhiloxU( unsigned long long seed, unsigned nonce, int rows, const int* positions, double* uOut, hipStream_t stream );
 	// out[ row ] = p[ tokenSolm ] of the row the sampler left in `probs`; spreadScratch non-null: the row holds the spread sampler's unnormalised e and is

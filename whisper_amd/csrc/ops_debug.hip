@@ -383,6 +383,41 @@ int wh_op_sample_draw( void* stream, const float* probs, int rows, int nVocab, i
 		(TokenData*)out, (hipStream_t)stream );
 }
 
+// The per-row step outside a context: the records go to a temporary device array (the call waits for the stream at both ends: a test entry point)
+int wh_op_sample_rows( void* stream, const float* logits, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot, int forceTimestamp,
+	int isInitial, const wh_sample_row* rowParams, const int32_t* positionsDev, float* probsOut, wh_token_data* out )
+{
+	if( !tokenArgsOk( logits, out, rows, nVocab, tokenBeg, tokenSot, tokenSolm, tokenNot ) || !rowParams || !positionsDev || !probsOut || nVocab > SAMPLE_DRAW_MAX_VOCAB )
+	{
+		setError( "sample_rows: bad pointer, size (at most 65536 columns) or token id" );
+		return WH_E_INVALIDARG;
+	}
+	std::vector<SampleRowParams> host( (size_t)rows );
+	for( int r = 0; r < rows; r++ )
+	{
+		const float t = rowParams[ r ].temperature;
+		if( !( t >= 0.0f ) || t > 4.0f ) { setError( "sample_rows: a temperature lies outside [0, 4]" ); return WH_E_INVALIDARG; }
+		host[ (size_t)r ] = makeSampleRow( t, rowParams[ r ].seed, rowParams[ r ].nonce );
+	}
+	hipStream_t st = (hipStream_t)stream;
+	SampleRowParams* dev = nullptr;
+	WH_HIP( hipMalloc( (void**)&dev, sizeof( SampleRowParams ) * (size_t)rows ) );
+	const auto body = [ & ]() -> int
+	{
+		WH_HIP( hipMemcpyAsync( dev, host.data(), sizeof( SampleRowParams ) * (size_t)rows, hipMemcpyHostToDevice, st ) );
+		WH_HIP( hipStreamSynchronize( st ) );
+		WH_CHECK( launchVocabSoftMaxRows( logits, dev, probsOut, rows, nVocab, st ) );
+		WH_CHECK( launchSampleRows( probsOut, rows, nVocab, tokenBeg, tokenSot, tokenSolm, tokenNot, forceTimestamp ? 1 : 0, isInitial ? 1 : 0, nullptr, dev, positionsDev,
+			(TokenData*)out, nullptr, SampleMailbox{ nullptr, nullptr }, st ) );
+		WH_HIP( hipStreamSynchronize( st ) );
+		return 0;
+	};
+	const int rc = body();
+	if( rc != 0 ) (void)hipStreamSynchronize( st );	   // whatever was launched has finished before the records go
+	(void)hipFree( dev );
+	return rc;
+}
+
 int wh_op_philox_u( void* stream, uint64_t seed, uint32_t nonce, int rows, const int32_t* positionsDev, double* uOut )
 {
 	if( rows < 1 || !positionsDev || !uOut ) { setError( "philox_u: null pointer or no rows" ); return WH_E_INVALIDARG; }
@@ -481,6 +516,16 @@ namespace
 		}
 		for( int off = 32; off > 0; off >>= 1 ) m = fmaxf( m, __shfl_xor( m, off ) );
 		if( ( threadIdx.x & 63 ) == 0 ) atomicMax( out, __float_as_int( m ) );
+	}
+	// logits-like FP32 values in [-6, 6)
+	__global__ void probeFillF32( float* p, long long n, unsigned seed )
+	{
+		for( long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x )
+		{
+			unsigned h = (unsigned)i * 2654435761u + seed;
+			h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
+			p[ i ] = ( (float)( h & 0xFFFF ) / 32768.0f - 1.0f ) * 6.0f;
+		}
 	}
 	__global__ void probeFill( _Float16* p, long long n, unsigned seed )
 	{
@@ -723,6 +768,58 @@ int wh_debug_probe( wh_context* c, int kind, int variant, int M, int N, int K, i
 			}
 		}
 		(void)hipStreamDestroy( sa ); (void)hipStreamDestroy( sb );
+	}
+	else if( kind == 5 )
+	{
+		// The sampler of a decode step on M rows of N columns: variant 0 = the fused greedy sampler (launchSoftMaxSample), 1 = the per-row step with every row
+		// greedy (launchVocabSoftMaxRows + launchSampleRows) -- what a round with one retrying row costs its greedy neighbours. The logits rotate through
+		// buffers that together exceed the last-level cache (512 MB); 5 warm-up launches, then the MEDIAN of `iters` launches, each between its own events.
+		const int rows = M, nVocab = N;
+		if( rows < 1 || rows > 4096 || nVocab < 2048 || nVocab > 52224 || variant < 0 || variant > 1 ) return WH_E_INVALIDARG;
+		const size_t rowBytes = (size_t)rows * nVocab * 4;
+		const int nBuf = (int)std::min<size_t>( 64, ( (size_t)512 << 20 ) / rowBytes + 2 );
+		std::vector<float*> logits( (size_t)nBuf, nullptr );
+		float* probs = nullptr;
+		DecodeState* state = nullptr;
+		TokenData* out = nullptr;
+		int *next = nullptr, *pos = nullptr;
+		SampleRowParams* rowParams = nullptr;
+		for( int b = 0; b < nBuf; b++ ) WH_CHECK( mem.alloc( &logits[ b ], rowBytes ) );
+		WH_CHECK( mem.alloc( &probs, rowBytes ) );
+		WH_CHECK( mem.alloc( &state, sizeof( DecodeState ) ) );
+		WH_CHECK( mem.alloc( &out, sizeof( TokenData ) * (size_t)rows ) );
+		WH_CHECK( mem.alloc( &next, sizeof( int ) * (size_t)rows ) );
+		WH_CHECK( mem.alloc( &pos, sizeof( int ) * (size_t)rows ) );
+		WH_CHECK( mem.alloc( &rowParams, sizeof( SampleRowParams ) * (size_t)rows ) );
+		for( int b = 0; b < nBuf; b++ ) hipLaunchKernelGGL( probeFillF32, dim3( 1024 ), dim3( 256 ), 0, st, logits[ b ], (long long)rows * nVocab, 11u + (unsigned)b );
+		WH_HIP( hipMemsetAsync( state, 0, sizeof( DecodeState ), st ) );	 // step 0, no flags, no mailbox: every launch writes slot 0
+		WH_HIP( hipMemsetAsync( pos, 0, sizeof( int ) * (size_t)rows, st ) );
+		const std::vector<SampleRowParams> greedy( (size_t)rows, makeSampleRow( 0.0f, 0, 0 ) );
+		WH_HIP( hipMemcpyAsync( rowParams, greedy.data(), sizeof( SampleRowParams ) * (size_t)rows, hipMemcpyHostToDevice, st ) );
+		WH_HIP( hipStreamSynchronize( st ) );
+		const int beg = nVocab - 1501, sot = beg - 105, solm = beg - 2, tnot = beg - 1;
+		const SampleMailbox noMail = { nullptr, nullptr };
+		const auto launch = [ & ]( const float* x ) -> int
+		{
+			if( variant == 0 ) return launchSoftMaxSample( x, probs, rows, nVocab, beg, sot, solm, tnot, state, out, next, noMail, st );
+			WH_CHECK( launchVocabSoftMaxRows( x, rowParams, probs, rows, nVocab, st ) );
+			return launchSampleRows( probs, rows, nVocab, beg, sot, solm, tnot, 0, 0, state, rowParams, pos, out, next, noMail, st );
+		};
+		for( int i = 0; i < 5; i++ ) WH_CHECK( launch( logits[ (size_t)( i % nBuf ) ] ) );
+		WH_HIP( hipStreamSynchronize( st ) );
+		std::vector<float> each;
+		for( int i = 0; i < iters; i++ )
+		{
+			WH_HIP( hipEventRecord( e0, st ) );
+			WH_CHECK( launch( logits[ (size_t)( ( 5 + i ) % nBuf ) ] ) );
+			WH_HIP( hipEventRecord( e1, st ) );
+			WH_HIP( hipEventSynchronize( e1 ) );
+			float t = 0;
+			WH_HIP( hipEventElapsedTime( &t, e0, e1 ) );
+			each.push_back( t );
+		}
+		std::sort( each.begin(), each.end() );
+		ms = each[ each.size() / 2 ] * (float)iters;	  // (the caller gets ms / iters)
 	}
 	else
 		rc = WH_E_INVALIDARG;

@@ -198,6 +198,11 @@ struct wh_context
 	// temperature above 0, before any capture), so one captured step graph per mode serves every attempt
 	float temperature = 0.0f;
 	SampleParams* sampleParams = nullptr;
+	// per-row sampling (wh_context_set_sampling_rows): sampleRowsOn != 0 = every sequence samples under its own record of sampleRows [maxSeq] (device; allocated,
+	// like its pinned staging and the event behind the staging's last upload, by the first call that turns the mode on, before any capture)
+	int sampleRowsOn = 0;
+	SampleRowParams *sampleRows = nullptr, *sampleRowsPin = nullptr;
+	hipEvent_t sampleRowsEv = nullptr;
 	// wh_context_set_no_speech: p[ solm ] of the prompt step's rows, gathered behind the first sample of every window (allocated by the first call that turns it on)
 	bool noSpeech = false;
 	float* noSpeechDev = nullptr;
@@ -231,9 +236,22 @@ struct wh_context
 	int mailGen = 0;		   // generation of the window in progress (0 = its samples are not mirrored)
 	int mailCounter = 0;	   // last generation handed out
 	TokenData* greedyOut = nullptr;	   // [n_text_ctx][maxBatch]
-	hipGraphExec_t graphExec = nullptr;
-	int graphBatch = 0;
-	uint32_t graphKey = 0;
+	// the captured steps of the device-side loop, by ( batch, stepGraphKey ). Entries that differ from the one asked for in the batch or in anything but the key's
+	// per-row bit are destroyed when it is captured: at most the greedy graph and the per-row graph of one batch live side by side, so a lock-step batch whose
+	// rounds enter and leave the per-row mode never recaptures
+	struct StepGraph { int batch; uint32_t key; hipGraphExec_t exec; };
+	std::vector<StepGraph> stepGraphs;
+	hipGraphExec_t stepGraph( int batch, uint32_t key ) const
+	{
+		for( const StepGraph& g : stepGraphs )
+			if( g.batch == batch && g.key == key ) return g.exec;
+		return nullptr;
+	}
+	void destroyStepGraphs()
+	{
+		for( const StepGraph& g : stepGraphs ) (void)hipGraphExecDestroy( g.exec );
+		stepGraphs.clear();
+	}
 	const int* raggedLastPos = nullptr;	   // set around the prompt step of a window whose prompts differ in length: device [batch], position of each sequence's last prompt token
 	int windowSamples = 0;
 	int windowPos = 0;		   // position the next greedy step feeds (prompt length + steps enqueued so far)

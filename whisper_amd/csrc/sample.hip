@@ -12,15 +12,18 @@ namespace wh
 		// ---- table softmax over rows (softMax.hlsl / softMaxLong.hlsl; ggml.c:5030-5090) ---------------------------
 		// p = exp16( x - max ) / sum, sum in double like the reference, -inf -> 0. One 1024-thread block per row.
 		// SCALED: the row is softMaxInput's x * invT, invT by value or, when invTDev is non-null, read from device memory (a captured step graph outlives a change
-		// of temperature).
-		template<bool SCALED>
+		// of temperature). PER_ROW: invTDev is the head of an array of SampleRowParams records and row r takes its own record's factor.
+		constexpr int ROW_PARAMS_STRIDE = (int)( sizeof( SampleRowParams ) / sizeof( float ) );
+		static_assert( sizeof( SampleRowParams ) % sizeof( float ) == 0 && offsetof( SampleRowParams, invT ) == 0, "the softmax reads the factor at the head of each record" );
+		template<bool SCALED, bool PER_ROW = false>
 		__global__ void __launch_bounds__( 1024 ) softMaxRows( const float* in, float* out, int cols, float invT, const float* invTDev )
 		{
 			__shared__ float shf[ 16 ];
 			__shared__ double shd[ 16 ];
 			const float* x = in + (long long)blockIdx.x * cols;
 			float* y = out + (long long)blockIdx.x * cols;
-			if constexpr( SCALED )
+			if constexpr( PER_ROW ) invT = invTDev[ blockIdx.x * ROW_PARAMS_STRIDE ];
+			else if constexpr( SCALED )
 				if( invTDev ) invT = *invTDev;
 			float m = -INFINITY;
 			for( int c = threadIdx.x; c < cols; c += 1024 ) m = fmaxf( m, softMaxInput<SCALED>( x[ c ], invT ) );
@@ -99,14 +102,15 @@ namespace wh
 		// thread where beamCandidatesKernel re-reads the row: 57.6 against 26 us, VALU-bound, a third of the row spilled), and both in one launch (124 us: 288 spill
 		// instructions under the 128-register cap of a 1024-thread workgroup).
 		constexpr int SC_PER = 51;
-		template<bool SCALED>
+		template<bool SCALED, bool PER_ROW = false>
 		__global__ void __launch_bounds__( 1024 ) softMaxRowsReg( const float* __restrict__ in, float* __restrict__ out, int cols, float invT, const float* __restrict__ invTDev )
 		{
 			__shared__ float shf[ 16 ];
 			__shared__ double shd[ 16 ];
 			const float* const x = in + (long long)blockIdx.x * cols;
 			float* const y = out + (long long)blockIdx.x * cols;
-			if constexpr( SCALED )
+			if constexpr( PER_ROW ) invT = invTDev[ blockIdx.x * ROW_PARAMS_STRIDE ];
+			else if constexpr( SCALED )
 				if( invTDev ) invT = *invTDev;
 			float v[ SC_PER ];
 			const float m = loadRowReg<SC_PER, SCALED>( x, cols, invT, v );
@@ -434,6 +438,7 @@ namespace wh
 			const DecodeState* state;		   // the greedy loop's device state: flags, output slot, mailbox generation
 			unsigned seedLo, seedHi, nonce;	   // params == nullptr: the generator's key and nonce of the call
 			const SampleParams* params;		   // device memory: a captured step graph outlives a change of seed or nonce
+			const SampleRowParams* rowParams;  // device [rows] or nullptr: every row its own mode, key and nonce (wh_context_set_sampling_rows)
 			const int* positions;			   // [rows]
 			TokenData* out;					   // state ? [step][rows] : [rows]
 			int* nextTokens;				   // [rows] or nullptr
@@ -448,6 +453,9 @@ namespace wh
 		//   3. wave 0 scans that one tile and takes the first column whose prefix passes u W.
 		// Rounding may leave no column (u W rounds up to W, or the tile's scan falls an ulp short of its sum): then the last allowed column with p > 0 -- of the
 		// tile, else of the row. W == 0 (or NaN): sampleBestKernel's pick. No atomics, no scratch; 8.4 KB of LDS.
+		// With rowParams every row has its own record: a greedy row ends behind pass 1 with sampleBestKernel's pick (the branch is uniform over the workgroup, so
+		// the barriers of passes 2 and 3 stay legal); a sampled row draws under its own key and nonce with the row word of the Philox counter 0 -- the draws of a
+		// stream do not depend on the slot it sits in, and the row equals this kernel run on that row alone.
 		__global__ void __launch_bounds__( 1024 ) sampleDrawKernel( const DrawArgs a )
 		{
 			__shared__ ArgMax sha[ 16 ];
@@ -467,6 +475,31 @@ namespace wh
 			RowStats st;
 			for( int c = tid; c < nVocab; c += 1024 ) st.feed( p[ c ], c, tokenBeg, tsEnd );
 			const bool onlyTs = st.reduce( forceTimestamp, sha, shd );
+			auto publish = [ & ]( ArgMax pick )
+			{
+				const TokenData r = sampleRecord( pick, st.ts, st.sumTs, nVocab );
+				if( a.state ) publishSample( a.state, a.mail, a.out, a.nextTokens, r, row, gridDim.x );
+				else
+				{
+					a.out[ row ] = r;
+					if( a.nextTokens ) a.nextTokens[ row ] = r.id;
+				}
+			};
+			SampleParams prm = { 1.0f, a.seedLo, a.seedHi, a.nonce };
+			int philoxRow = row;
+			if( a.rowParams )
+			{
+				const SampleRowParams rp = a.rowParams[ row ];
+				if( !rp.sampled )
+				{
+					const ArgMax pick = sampleBestPick( p, nVocab, tokenBeg, tsEnd, onlyTs, tokenSot, tokenSolm, tokenNot, sha );
+					if( tid == 0 ) publish( pick );
+					return;
+				}
+				prm = SampleParams{ rp.invT, rp.seedLo, rp.seedHi, rp.nonce };
+				philoxRow = 0;
+			}
+			else if( a.params ) prm = *a.params;
 			auto allowed = [ & ]( int c ) -> bool
 			{
 				if( c >= tokenBeg ) return c < tsEnd;
@@ -515,8 +548,7 @@ namespace wh
 			int rowLast = shLast[ 0 ];
 			for( int i = 1; i < 16; i++ ) rowLast = max( rowLast, shLast[ i ] );
 
-			const SampleParams prm = a.params ? *a.params : SampleParams{ 1.0f, a.seedLo, a.seedHi, a.nonce };
-			const double u = philoxUniform( prm.seedLo, prm.seedHi, prm.nonce, a.positions[ row ], row );
+			const double u = philoxUniform( prm.seedLo, prm.seedHi, prm.nonce, a.positions[ row ], philoxRow );
 			const double target = u * W;
 			const bool hit = tid < nTiles && incl > target;
 			const unsigned long long hits = __ballot( hit );
@@ -564,16 +596,7 @@ namespace wh
 				pick.v = p[ pick.i ];
 			}
 
-			if( tid == 0 )
-			{
-				const TokenData r = sampleRecord( pick, st.ts, st.sumTs, nVocab );
-				if( a.state ) publishSample( a.state, a.mail, a.out, a.nextTokens, r, row, gridDim.x );
-				else
-				{
-					a.out[ row ] = r;
-					if( a.nextTokens ) a.nextTokens[ row ] = r.id;
-				}
-			}
+			if( tid == 0 ) publish( pick );
 		}
 
 		bool drawShapeOk( int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot )
@@ -727,6 +750,35 @@ namespace wh
 		DrawArgs a = {};
 		a.probs = probs; a.nVocab = nVocab; a.tokenBeg = tokenBeg; a.tokenSot = tokenSot; a.tokenSolm = tokenSolm; a.tokenNot = tokenNot;
 		a.state = state; a.params = params; a.positions = positions; a.out = out; a.nextTokens = nextTokens; a.mail = mail;
+		hipLaunchKernelGGL( sampleDrawKernel, dim3( rows ), dim3( 1024 ), 0, stream, a );
+		WH_HIP( hipGetLastError() );
+		return 0;
+	}
+
+	int launchVocabSoftMaxRows( const float* logits, const SampleRowParams* rowParams, float* probs, int rows, int nVocab, hipStream_t stream )
+	{
+		if( !logits || !rowParams || !probs || rows < 1 || nVocab < 1 ) { setError( "vocabSoftMaxRows: bad argument" ); return -1; }
+		// the same choice of kernel as launchVocabSoftMax, so that a greedy row (factor 1) has its bits
+		if( g_opt.beamRegs && nVocab <= SC_PER * 1024 )
+			hipLaunchKernelGGL( ( softMaxRowsReg<true, true> ), dim3( rows ), dim3( 1024 ), 0, stream, logits, probs, nVocab, 1.0f, &rowParams->invT );
+		else
+			hipLaunchKernelGGL( ( softMaxRows<true, true> ), dim3( rows ), dim3( 1024 ), 0, stream, logits, probs, nVocab, 1.0f, &rowParams->invT );
+		WH_HIP( hipGetLastError() );
+		return 0;
+	}
+
+	int launchSampleRows( const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot, int forceTimestamp, int isInitial,
+		const DecodeState* state, const SampleRowParams* rowParams, const int* positions, TokenData* out, int* nextTokens, SampleMailbox mail, hipStream_t stream )
+	{
+		if( !probs || !positions || !out || !rowParams || ( state && !nextTokens ) || !drawShapeOk( rows, nVocab, tokenBeg, tokenSot, tokenSolm, tokenNot ) )
+		{
+			setError( "sampleRows: bad pointer, token id or size (at most 65536 columns)" );
+			return -1;
+		}
+		DrawArgs a = {};
+		a.probs = probs; a.nVocab = nVocab; a.tokenBeg = tokenBeg; a.tokenSot = tokenSot; a.tokenSolm = tokenSolm; a.tokenNot = tokenNot;
+		a.forceTimestamp = forceTimestamp; a.isInitial = isInitial;
+		a.state = state; a.rowParams = rowParams; a.positions = positions; a.out = out; a.nextTokens = nextTokens; a.mail = mail;
 		hipLaunchKernelGGL( sampleDrawKernel, dim3( rows ), dim3( 1024 ), 0, stream, a );
 		WH_HIP( hipGetLastError() );
 		return 0;

@@ -12,6 +12,9 @@
 //             text) -> wh_encode_windows (each slot its own spectrogram and seek) -> wh_decode_window_start_ragged (prompts of
 //             different lengths, a position per sequence) -> greedy chunks, scanned chunk by chunk with WindowScan until every slot's
 //             window is over -> StreamRun::finishWindow per slot (segments, callbacks, seek += the stream's own delta)
+//   retry   = with Whisper::setBatchDecodingFallback on, a window whose attempt fails its gates STAYS in its slot -- same seek, same prompt, no nextWindow
+//             and no finishWindow -- and is decoded again in the next round at the plan's next temperature while its neighbours move on: a retried window
+//             costs one slot-round (the round encodes every slot anyway). The rows of a round sample each under its own temperature, key and nonce.
 //
 // Rounds of different groups overlap on the GPU (the MFMA-bound encoder of one under the latency-bound decode chain of the other);
 // ONE host thread -- the caller's, so callbacks arrive on the calling thread like runFull's -- serves all groups through
@@ -19,6 +22,8 @@
 // is the transcript of runFull on the same samples (tests/test_batch_api.py).
 #include "hostCommon.h"
 #include "hostLoop.h"
+#include "batchSampling.h"
+#include "decodeFallback.h"
 #include "languageDetect.h"
 #include "results.h"
 #include <algorithm>
@@ -32,6 +37,8 @@ namespace Whisper
 {
 	// The device half of language detection, injected (languageDetect.h): this file names no entry point of the compute layer for it
 	pfnBatchLanguageDetector g_batchLanguageDetector = nullptr;
+	// ... and for per-row sampling and the no-speech gather (batchSampling.h)
+	const BatchSamplingHooks* g_batchSamplingHooks = nullptr;
 
 	namespace
 	{
@@ -111,6 +118,12 @@ namespace Whisper
 			bool needsLanguage = false;
 			int languageId = -1;
 			float languageP = 0;
+			// decoding fallback: the plan of the window in the slot, the greedy attempt's no-speech probability, what became of the windows so far.
+			// retry: the window failed its last attempt and is decoded again next round -- it keeps prompt and seek and gets a fresh scan
+			std::unique_ptr<fallback::FallbackPlan> plan;
+			bool retry = false;
+			sWindowStats window{};
+			std::vector<sWindowStats> stats;
 		};
 
 		// Device buffers of the streams (PCM, spectrograms), recycled: hipFree waits for the whole device, i.e. for the OTHER group's
@@ -168,6 +181,11 @@ namespace Whisper
 			std::vector<wh_mel_window> windows;
 			std::vector<float> langP;
 			std::vector<int32_t> langBest;
+			// decoding fallback: the rows' sampling parameters of the round, and whether its prompt step gathers the no-speech probabilities
+			std::vector<float> temperature, noSpeech;
+			std::vector<uint64_t> seed;
+			std::vector<uint32_t> nonce;
+			bool gathers = false;
 		};
 
 		// One call of iBatchRunner::run over the runner's groups (their wh_contexts outlive the call: KV caches, captured graphs)
@@ -183,6 +201,7 @@ namespace Whisper
 			std::vector<Group>& groups;
 			Shared& shared;
 			const int chunk, lookahead;
+			const sDecodingFallback* const fallbackParams;	   // nullptr: the feature is off
 			bool loaderBusy = false;
 			std::deque<uint32_t> pending;
 			HRESULT firstFailure = S_OK;
@@ -208,6 +227,7 @@ namespace Whisper
 					r->speakers = s->ctx->speakers;
 					r->languageId = s->languageId;
 					r->languageP = s->languageP;
+					r->windowStats = std::move( s->stats );
 					results[ s->index ] = r;
 				}
 				s->run.reset();
@@ -364,10 +384,24 @@ namespace Whisper
 						Stream& s = *g.slot[ b ];
 						if( s.needsLanguage ) { detect = true; break; }
 						if( s.scan ) break;
+						if( s.retry )
+						{
+							// this slot has its window: the same prompt at the same seek, scanned afresh
+							s.retry = false;
+							s.scan.reset( new WindowScan( s.run->fullParams(), model->vocab, s.run->seek, s.run->seekEnd(), s.run->maxTokens() ) );
+							any = true;
+							break;
+						}
 						const HRESULT hr = s.run->nextWindow( s.prompt );
 						if( hr == S_OK )
 						{
 							s.scan.reset( new WindowScan( s.run->fullParams(), model->vocab, s.run->seek, s.run->seekEnd(), s.run->maxTokens() ) );
+							if( fallbackParams )
+							{
+								s.plan.reset( new fallback::FallbackPlan( *fallbackParams, s.run->seek ) );
+								s.window = sWindowStats{};
+								s.window.seek = s.run->seek;
+							}
 							any = true;
 							break;
 						}
@@ -376,6 +410,8 @@ namespace Whisper
 						{
 							const HRESULT hrEnd = s.run->end();
 							if( FAILED( hrEnd ) ) fail( s, hrEnd );
+							// every window dropped as silence: an empty transcript, reported the way a recording too short to transcribe is
+							else if( !s.stats.empty() && std::all_of( s.stats.begin(), s.stats.end(), []( const sWindowStats& w ) { return w.skipped != 0; } ) ) s.status = S_FALSE;
 						}
 						retire( g, b );
 					}
@@ -416,6 +452,27 @@ namespace Whisper
 					g.windows[ b ] = wh_mel_window{ (const float*)s->melDev, s->melLen, (int32_t)s->run->seek, 0 };
 				}
 				CHECK_WH( wh_encode_windows( g.gpu, g.windows.data(), g.slots ) );
+				if( fallbackParams )
+				{
+					// every row at its own attempt: its plan's temperature and nonce, the seed moved by the stream's index (the chunks of one recording all sit at
+					// seek 0 and must not share draws); an idle slot is greedy. The no-speech probability is the greedy attempt's: gathered when a slot is at its first.
+					// Uploaded behind what the stream holds: a chunk of the last round decoded in vain still reads the old values.
+					g.temperature.assign( (size_t)g.slots, 0.0f );
+					g.seed.assign( (size_t)g.slots, 0 );
+					g.nonce.assign( (size_t)g.slots, 0 );
+					g.gathers = false;
+					for( int b = 0; b < g.slots; b++ )
+					{
+						const Stream* s = g.slot[ b ];
+						if( !s ) continue;
+						g.temperature[ b ] = s->plan->temperature();
+						g.seed[ b ] = s->plan->seed() + s->index;
+						g.nonce[ b ] = s->plan->nonce();
+						g.gathers = g.gathers || s->plan->attemptIndex() == 0;
+					}
+					CHECK_WH( g_batchSamplingHooks->setRowSampling( g.gpu, g.slots, g.temperature.data(), g.seed.data(), g.nonce.data() ) );
+					CHECK_WH( g_batchSamplingHooks->setNoSpeech( g.gpu, g.gathers ? 1 : 0 ) );
+				}
 				const int room = model->hp.n_text_ctx - g.promptMax;
 				const int n0 = std::max( 0, std::min( chunk, room ) );
 				CHECK_WH( wh_decode_window_start_ragged( g.gpu, g.slots, g.tokens.data(), g.lens.data(), g.promptMax, n0, 1, 1 ) );
@@ -473,11 +530,48 @@ namespace Whisper
 			}
 			HRESULT finishRound( Group& g )
 			{
+				if( fallbackParams && g.gathers )
+				{
+					g.noSpeech.assign( (size_t)g.slots, 0.0f );
+					CHECK_WH( g_batchSamplingHooks->readNoSpeech( g.gpu, g.noSpeech.data() ) );
+				}
 				for( int b = 0; b < g.slots; b++ )
 				{
 					Stream* s = g.slot[ b ];
 					if( !s ) continue;
 					if( !s->scan->over ) s->scan->failed = s->scan->over = true;	// see consume(): not reachable through the host loop's prompts
+					if( fallbackParams )
+					{
+						// scored exactly as iContext::runFull scores an attempt; the plan says what becomes of the window
+						WindowScan& scan = *s->scan;
+						sWindowStats& ws = s->window;
+						if( s->plan->attemptIndex() == 0 ) ws.noSpeech = g.noSpeech[ b ];
+						fallback::Attempt a;
+						a.scanFailed = scan.failed;
+						a.resultLen = std::min( scan.resultLen, (int)scan.tokens.size() );
+						a.scores = fallback::score( scan.tokens.data(), a.resultLen );
+						a.noSpeech = ws.noSpeech;
+						ws.attempts = s->plan->attempts();
+						ws.temperature = s->plan->temperature();
+						ws.avgLogprob = a.scores.avgLogprob;
+						ws.entropy = a.scores.entropy;
+						const fallback::eVerdict verdict = s->plan->judge( a );
+						if( verdict == fallback::eVerdict::Retry )
+						{
+							// the window stays in its slot: the next round decodes it again at the plan's next temperature
+							s->scan.reset();
+							s->retry = true;
+							continue;
+						}
+						if( verdict == fallback::eVerdict::Skip )
+						{
+							// silence: no segments, nothing for the next window's prompt, the stream moves on by the scan's seekDelta
+							scan.tokens.clear();
+							scan.resultLen = 0;
+							ws.skipped = 1;
+						}
+						s->stats.push_back( ws );
+					}
 					const HRESULT hr = s->run->finishWindow( *s->scan );
 					s->ctx->labelNewSegments();
 					s->scan.reset();
@@ -493,8 +587,9 @@ namespace Whisper
 
 		public:
 			Scheduler( const std::shared_ptr<LoadedModel>& m, iModel* o, const sFullParams& p, const sBatchStream* d, uint32_t n, iTranscribeResult** r, HRESULT* per,
-				std::vector<Group>& grp, Shared& sh, int chunk_, int lookahead_ )
-				: model( m ), owner( o ), common( p ), descs( d ), count( n ), results( r ), perStream( per ), groups( grp ), shared( sh ), chunk( chunk_ ), lookahead( lookahead_ ) {}
+				std::vector<Group>& grp, Shared& sh, int chunk_, int lookahead_, const sDecodingFallback* fallback_ )
+				: model( m ), owner( o ), common( p ), descs( d ), count( n ), results( r ), perStream( per ), groups( grp ), shared( sh ), chunk( chunk_ ), lookahead( lookahead_ ),
+				fallbackParams( fallback_ ) {}
 			~Scheduler()
 			{
 				// a failure left streams in their slots: their buffers go, the device work they queued is awaited
@@ -566,7 +661,28 @@ namespace Whisper
 			int chunk = 4, lookahead = 0;
 			std::vector<Group> groups;
 			Shared shared;
+			// Whisper::setBatchDecodingFallback: off unless set. modesDirty: a run with the feature on left the groups' contexts in its modes
+			bool fallbackOn = false, modesDirty = false;
+			sDecodingFallback fallbackParams;
 		public:
+			HRESULT setFallback( const sDecodingFallback* p )
+			{
+				if( !p ) { fallbackOn = false; return S_OK; }
+				const bool nan = std::isnan( p->temperatureInc ) || std::isnan( p->logprobThold ) || std::isnan( p->entropyThold ) || std::isnan( p->noSpeechThold );
+				if( nan || ( p->temperatureInc > 0.0f && p->temperatureInc < 0.01f ) )
+				{
+					logError( "setBatchDecodingFallback: a threshold is NaN, or temperatureInc lies in ( 0, 0.01 )" );
+					return E_INVALIDARG;
+				}
+				if( !g_batchSamplingHooks )
+				{
+					logError( "setBatchDecodingFallback: this build of the scheduler was not given the device's per-row sampler" );
+					return E_NOTIMPL;
+				}
+				fallbackParams = *p;
+				fallbackOn = true;
+				return S_OK;
+			}
 			BatchRunner( const std::shared_ptr<LoadedModel>& m, iModel* o, const sBatchSetup* setup ) : model( m ), owner( o )
 			{
 				owner->AddRef();
@@ -629,7 +745,18 @@ namespace Whisper
 				// one sFullParams for every stream of the batch: its audio_ctx is the groups' (ContextImpl.cpp:488-489)
 				if( params.audio_ctx < 0 || params.audio_ctx > model->hp.n_audio_ctx ) return E_INVALIDARG;
 				for( Group& g : groups ) CHECK_WH( wh_context_set_audio_ctx( g.gpu, params.audio_ctx ) );
-				Scheduler s( model, owner, params, streams, count, results, perStream, groups, shared, chunk, lookahead );
+				if( modesDirty && !fallbackOn )
+				{
+					// the feature was turned off: the contexts go back to the greedy sampler and gather nothing
+					for( Group& g : groups )
+					{
+						CHECK_WH( g_batchSamplingHooks->setRowSampling( g.gpu, 0, nullptr, nullptr, nullptr ) );
+						CHECK_WH( g_batchSamplingHooks->setNoSpeech( g.gpu, 0 ) );
+					}
+					modesDirty = false;
+				}
+				modesDirty = modesDirty || fallbackOn;
+				Scheduler s( model, owner, params, streams, count, results, perStream, groups, shared, chunk, lookahead, fallbackOn ? &fallbackParams : nullptr );
 				const HRESULT hr = s.run( (int)slots, (int)useGroups );
 				if( FAILED( hr ) ) logError( "runFullBatch: failed, HRESULT 0x%08x", (unsigned)hr );
 				return hr;
@@ -649,6 +776,30 @@ namespace Whisper
 		const std::shared_ptr<LoadedModel> lm = mi->loaded();
 		mi->Release();
 		*pp = new BatchRunner( lm, model, setup );
+		return S_OK;
+	}
+
+	HRESULT setBatchDecodingFallback( iBatchRunner* runner, const sDecodingFallback* params )
+	{
+		if( !runner ) return E_POINTER;
+		BatchRunner* const r = dynamic_cast<BatchRunner*>( runner );
+		if( !r )
+		{
+			logError( "setBatchDecodingFallback: not a runner of this library's createBatchRunner" );
+			return E_INVALIDARG;
+		}
+		return r->setFallback( params );
+	}
+	HRESULT getResultWindowStats( const iTranscribeResult* result, sWindowStats* stats, uint32_t* count )
+	{
+		if( !result || !count ) return E_POINTER;
+		const TranscribeResult* const r = dynamic_cast<const TranscribeResult*>( result );
+		if( !r ) return E_INVALIDARG;
+		const uint32_t cap = *count;
+		*count = (uint32_t)r->windowStats.size();
+		if( !stats ) return S_OK;
+		if( cap < r->windowStats.size() ) return E_BOUNDS;
+		std::copy( r->windowStats.begin(), r->windowStats.end(), stats );
 		return S_OK;
 	}
 

@@ -48,6 +48,10 @@ namespace
 		bool splitSilence = false;	// -split silence: the chunks of the recording end at pauses (splitAtPauses) instead of every 480000 samples (-split fixed, the default)
 		bool perRecording = false;	// -per-recording: whole recordings dealt round-robin to the ranks, each decoded with the reference's sliding window
 		std::string job;			// token of THIS job: stamped into the id file by rank 0, required by the ranks that read it
+		// -fallback: Whisper::setBatchDecodingFallback on every rank's runner; -tpi / -lpt / -et / -nth N (whisper-main's names) set temperatureInc, logprobThold,
+		// entropyThold, noSpeechThold
+		bool useFallback = false;
+		sDecodingFallback fallback;
 	};
 	std::wstring widen( const std::string& s )
 	{
@@ -117,7 +121,7 @@ namespace
 			while( true ) sleep( 1000 );
 	}
 
-	const char* const USAGE = "usage: whisper-mgpu -n ranks -m model.bin -f audio.wav [-l en] [-o out.txt] [-timeout seconds (rendezvous and collectives)] [-job-timeout seconds (whole job; default none)] [-slots n] [-id id-file] [-job token] [-split fixed|silence (where the chunks of the recording end: every 30 s, or at pauses)] [-per-recording -f more.wav ...]\n";
+	const char* const USAGE = "usage: whisper-mgpu -n ranks -m model.bin -f audio.wav [-l en] [-o out.txt] [-timeout seconds (rendezvous and collectives)] [-job-timeout seconds (whole job; default none)] [-slots n] [-id id-file] [-job token] [-split fixed|silence (where the chunks of the recording end: every 30 s, or at pauses)] [-per-recording -f more.wav ...] [-fallback (quality gates and temperature retries per window) [-tpi N] [-lpt N] [-et N] [-nth N]]\n";
 
 	// splitAtPauses hands the plan out through a callback: keep the streams
 	HRESULT keepStreams( const sBatchStream* s, uint32_t n, void* pv )
@@ -241,11 +245,16 @@ namespace
 		iBatchRunner* runner = nullptr;
 		const sBatchSetup bs{ (uint32_t)std::max( 1, std::min( a.slots, 512 ) ), 0, 0, 0 };
 		if( !streams.empty() && FAILED( createBatchRunner( model, &bs, &runner ) ) ) return 6;
+		if( runner && a.useFallback )
+		{
+			hr = setBatchDecodingFallback( runner, &a.fallback );
+			if( FAILED( hr ) ) { fprintf( stderr, "[rank %d] setBatchDecodingFallback failed 0x%08x\n", rank, (unsigned)hr ); return 6; }
+		}
 
 		if( 0 != wh_comm_barrier( comm ) ) { fprintf( stderr, "[rank %d] %s\n", rank, wh_last_error() ); return 8; }
 		const double tStart = since();
 		std::string textAll;
-		int nSeg = 0;
+		int nSeg = 0, nAttempts = 0, nRetried = 0, nSkipped = 0, nWindows = 0;
 		if( !streams.empty() )
 		{
 			std::vector<iTranscribeResult*> results( streams.size(), nullptr );
@@ -269,6 +278,20 @@ namespace
 					text += "\n";
 				}
 				nSeg += (int)len.countSegments;
+				if( a.useFallback )
+				{
+					uint32_t n = 0;
+					getResultWindowStats( res, nullptr, &n );
+					std::vector<sWindowStats> ws( n );
+					if( n > 0 && SUCCEEDED( getResultWindowStats( res, ws.data(), &n ) ) )
+						for( const sWindowStats& w : ws )
+						{
+							nWindows++;
+							nAttempts += w.attempts;
+							nRetried += w.attempts > 1;
+							nSkipped += (int)w.skipped;
+						}
+				}
 				res->Release();
 				if( a.perRecording )
 				{
@@ -288,6 +311,8 @@ namespace
 		}
 		fprintf( stderr, "[rank %d] chunks %d..%d of %d: %d segments in %.3f s (%.1f audio-s/s on this rank); all ranks done after %.3f s\n", rank, wb, we, windows,
 			nSeg, tRun, tRun > 0 ? ( we - wb ) * 30.0 / tRun : 0.0, tAll );
+		if( a.useFallback )
+			fprintf( stderr, "[rank %d] fallback: %d windows, %d attempts, %d retried, %d skipped as silence\n", rank, nWindows, nAttempts, nRetried, nSkipped );
 		if( rank == 0 )
 		{
 			if( a.splitSilence )
@@ -371,6 +396,11 @@ int main( int argc, char** argv )
 		else if( !strcmp( argv[ i ], "-job-timeout" ) ) a.jobTimeout = atof( val() );
 		else if( !strcmp( argv[ i ], "-job" ) ) a.job = val();
 		else if( !strcmp( argv[ i ], "-slots" ) ) a.slots = atoi( val() );
+		else if( !strcmp( argv[ i ], "-fallback" ) || !strcmp( argv[ i ], "--fallback" ) ) a.useFallback = true;
+		else if( !strcmp( argv[ i ], "-tpi" ) ) a.fallback.temperatureInc = (float)atof( val() );
+		else if( !strcmp( argv[ i ], "-lpt" ) ) a.fallback.logprobThold = (float)atof( val() );
+		else if( !strcmp( argv[ i ], "-et" ) ) a.fallback.entropyThold = (float)atof( val() );
+		else if( !strcmp( argv[ i ], "-nth" ) ) a.fallback.noSpeechThold = (float)atof( val() );
 		else if( !strcmp( argv[ i ], "--shard-range" ) )
 		{
 			// test hook (no GPU): the chunk range rank r of w gets out of n chunks, "begin end" -- must equal whisper_amd/distributed.py shard_range

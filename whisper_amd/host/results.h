@@ -23,6 +23,8 @@ namespace Whisper
 		// Plain members behind the interface's methods: the vtable is the reference's (whisperc_tr_language reads them).
 		int languageId = -1;
 		float languageP = 0;
+		// a batch runner's stream with Whisper::setBatchDecodingFallback on: what the fallback did with each of its windows (getResultWindowStats reads them)
+		std::vector<sWindowStats> windowStats;
 		HRESULT getSize( sTranscribeLength& rdi ) const override
 		{
 			rdi.countSegments = (uint32_t)segments.size();

@@ -9,6 +9,7 @@
 #include "hostCommon.h"
 #include "hostLoop.h"
 #include "decodeFallback.h"
+#include "batchSampling.h"
 #include "languageDetect.h"
 #include "results.h"
 #include "wavFormat.h"
@@ -1163,6 +1164,9 @@ namespace Whisper
 	}
 	// the lock-step scheduler's way to the device half of language detection (languageDetect.h): installed when the library is loaded
 	static const bool g_detectorInstalled = ( g_batchLanguageDetector = &wh_lang_detect, true );
+	// ... and to per-row sampling and the no-speech gather (batchSampling.h)
+	static const BatchSamplingHooks g_samplingHooks = { &wh_context_set_sampling_rows, &wh_context_set_no_speech, &wh_decode_window_no_speech };
+	static const bool g_samplingInstalled = ( g_batchSamplingHooks = &g_samplingHooks, true );
 
 	HRESULT createContextImpl( const std::shared_ptr<LoadedModel>& model, iModel* owner, iContext** pp )
 	{
@@ -1193,7 +1197,7 @@ namespace Whisper
 		ContextImpl* const c = dynamic_cast<ContextImpl*>( context );
 		if( !c )
 		{
-			logError( "setDecodingFallback: not a context of this library's createContext (the batch runner has no such setting)" );
+			logError( "setDecodingFallback: not a context of this library's createContext (a batch runner takes setBatchDecodingFallback)" );
 			return E_INVALIDARG;
 		}
 		return c->setFallback( params );
@@ -1383,6 +1387,22 @@ WHISPER_EXPORT int32_t whisperc_window_stats( void* ctx, void* out, uint32_t cap
 	if( !ctx || !count ) return E_POINTER;
 	*count = cap;
 	return getWindowStats( (const iContext*)ctx, (sWindowStats*)out, count );
+}
+// Whisper::setBatchDecodingFallback on a runner of whisperc_batch_create: the arguments of whisperc_set_fallback
+WHISPER_EXPORT int32_t whisperc_batch_set_fallback( void* runner, int32_t on, float temperatureInc, float logprobThold, float entropyThold, float noSpeechThold, uint64_t seed )
+{
+	if( !runner ) return E_POINTER;
+	if( !on ) return setBatchDecodingFallback( (iBatchRunner*)runner, nullptr );
+	sDecodingFallback p;
+	p.temperatureInc = temperatureInc; p.logprobThold = logprobThold; p.entropyThold = entropyThold; p.noSpeechThold = noSpeechThold; p.seed = seed;
+	return setBatchDecodingFallback( (iBatchRunner*)runner, &p );
+}
+// Whisper::getResultWindowStats: out = sWindowStats [cap] (may be NULL), *count = the windows of the result's stream
+WHISPER_EXPORT int32_t whisperc_tr_window_stats( void* result, void* out, uint32_t cap, uint32_t* count )
+{
+	if( !result || !count ) return E_POINTER;
+	*count = cap;
+	return getResultWindowStats( (const iTranscribeResult*)result, (sWindowStats*)out, count );
 }
 // Whisper::setAlignmentHeads: count (layer, head) pairs, 0 = the default heads
 WHISPER_EXPORT int32_t whisperc_model_set_alignment_heads( void* model, const int32_t* layerHeadPairs, int32_t count )
