@@ -400,6 +400,21 @@ namespace Whisper
 	WHISPER_EXPORT HRESULT setBatchDecodingFallback( iBatchRunner* runner, const sDecodingFallback* params );
 	// What the fallback did with each window of the stream a batch runner's result object belongs to, in order; count as getWindowStats. Empty with the feature off.
 	WHISPER_EXPORT HRESULT getResultWindowStats( const iTranscribeResult* result, sWindowStats* stats, uint32_t* count );
+	// Extension: suppressed tokens, openai-whisper's definition -- the logits of the given token ids are replaced by -inf before the softmax, so the decoder can
+	// never emit them, whatever the strategy: greedy runs, the sampled attempts of the decoding fallback, eSamplingStrategy::BeamSearch. Free functions: the
+	// vtables are the reference's. The ids are text tokens, each in [ 0, eot ): eot, the task and language tokens and the timestamps cannot be suppressed.
+	// getNonSpeechTokens: the set openai-whisper suppresses by default (suppress_tokens = "-1") and whisper.cpp under --suppress-nst -- brackets, quotes that open a
+	// word, note symbols, "((", "[[", "♪♪" and the like -- found by exact match in the model's own vocabulary (whisper_amd/host/nonSpeechTokens.h), ascending.
+	// count in: the capacity of `ids`; out: the size of the set (ids may be nullptr to ask for it); E_BOUNDS when the capacity is too small.
+	WHISPER_EXPORT HRESULT getNonSpeechTokens( iModel* model, int32_t* ids, uint32_t* count );
+	// The set holds for every later runFull / runStreamed of the context and reaches every device context it owns or creates later. count == 0 = off, the state of
+	// every new context: such a run is what it always was. Language "auto" detects on the unfiltered distribution as before; prompt tokens are fed, not sampled,
+	// so a suppressed id in prompt_tokens is legal. With a set held the no-speech probability of the decoding fallback is that of the filtered distribution.
+	// E_INVALIDARG for an id outside [ 0, eot ) or a context of another library.
+	WHISPER_EXPORT HRESULT setSuppressedTokens( iContext* context, const int32_t* ids, uint32_t count );
+	// One set for all streams of every later run of the runner. E_INVALIDARG as above; E_NOTIMPL for a non-empty set where the scheduler was built without the
+	// device's logit filter.
+	WHISPER_EXPORT HRESULT setBatchSuppressedTokens( iBatchRunner* runner, const int32_t* ids, uint32_t count );
 	// Extension (no counterpart in whisper.def): ONE long recording onto the batched path. The buffer is cut into pieces of at most maxLen samples at pauses,
 	// found with the reference's voice-activity detector (Whisper/Whisper/voiceActivityDetection.cpp, which its capture loop uses to fire a transcription when
 	// the speaker pauses): the per-frame features come from the device (wh_vad_features of whisper_hip.h, on the calling thread's current device), the decision

@@ -81,6 +81,13 @@ int32_t whisperc_window_stats( void* ctx, void* out, uint32_t cap, uint32_t* cou
  * windows of the stream a result object of whisperc_batch_run belongs to; out / cap / count as whisperc_window_stats. */
 int32_t whisperc_batch_set_fallback( void* runner, int32_t on, float temperatureInc, float logprobThold, float entropyThold, float noSpeechThold, uint64_t seed );
 int32_t whisperc_tr_window_stats( void* result, void* out, uint32_t cap, uint32_t* count );
+/* Suppressed tokens (Whisper::getNonSpeechTokens / setSuppressedTokens / setBatchSuppressedTokens of whisperApi.h): the logits of the given text-token ids
+ * (each in [0, eot)) are -inf before the softmax in every later run. whisperc_non_speech_tokens: the model's non-speech set, ascending; out = int32 [cap] or
+ * NULL, *count = its size; cap smaller than that with a non-NULL out is E_BOUNDS. count == 0 (ids may be NULL) turns suppression off, the state of every new
+ * context and runner. */
+int32_t whisperc_non_speech_tokens( void* model, int32_t* out, uint32_t cap, uint32_t* count );
+int32_t whisperc_set_suppress_tokens( void* ctx, const int32_t* ids, uint32_t count );
+int32_t whisperc_batch_set_suppress_tokens( void* runner, const int32_t* ids, uint32_t count );
 /* iContext::getResults( Tokens | Timestamps ) + iTranscribeResult::getSize / getSegments / getTokens; times in 100 ns ticks */
 int32_t whisperc_result_counts( void* ctx, uint32_t* segments, uint32_t* tokens );
 int32_t whisperc_result_segment( void* ctx, uint32_t index, uint64_t* t0, uint64_t* t1, uint32_t* firstToken, uint32_t* countTokens,

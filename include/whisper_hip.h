@@ -459,6 +459,17 @@ WH_API int wh_context_set_sampling_rows( wh_context* c, int rows, const float* t
  * p[ token_solm ] of every sequence's row of probabilities as that step formed it (the id the reference calls token_solm, 50361 + 1 when multilingual, is
  * <|nospeech|> in OpenAI's vocabulary). wh_decode_window_no_speech: HOST float [batch] of the window in progress; waits for the first sample only. The buffer
  * is allocated by the first call that turns it on. */
+/* Suppressed tokens, openai-whisper's definition: the logits of these ids are replaced by -inf before the softmax, for every row of every later decoder pass of
+ * the context -- wh_decode (the logits and probabilities it returns included), the greedy, tempered and per-row steps of the device-side loop, the prompt step's
+ * first sample, the beam step -- by ONE small launch behind the vocabulary product; no sampler changes, each reads -inf as probability 0. Two passes stay
+ * unfiltered: wh_lang_detect (the model's own distribution at [sot], the same bits whatever set is held) and wh_align_tokens (which forms no logits). The
+ * no-speech gather reads the row the sampler saw: with a set held it is the filtered distribution's probability.
+ * ids: HOST [count], each in [0, eot) -- text tokens only, so every row keeps mass; duplicates allowed, the sorted unique set is stored. count == 0 (ids may be
+ * NULL) is the state of every new context. The set goes to device memory behind what the stream holds (the call waits for the stream); the buffer, eot + 1 int32,
+ * is allocated by the first non-empty call and never again, and the captured step graphs are keyed on "a set is held" only: another set replays the same graph.
+ * WH_E_INVALIDARG for an id outside the range and for a non-empty set under WH_FLAG_PARITY_EXACT (wh_context_set_flags in turn refuses that flag while a set is
+ * held). Hypothesis-group contexts take the call like greedy ones. A context that never calls it launches, allocates and captures what it always did. */
+WH_API int wh_context_set_suppress( wh_context* c, const int32_t* ids, int count );
 WH_API int wh_context_set_no_speech( wh_context* c, int on );
 WH_API int wh_decode_window_no_speech( wh_context* c, float* out );
 
@@ -541,6 +552,9 @@ WH_API int wh_op_soft_max( void* stream, float* x, int rows, int cols );
 /* The decoder's vocabulary softmax (same semantics as wh_op_soft_max), out of place: probs [rows][cols] = softmax( logits [rows][cols] ).
  * Takes the kernel the option "beam_regs" selects (the row in registers up to 52224 columns, the three-pass kernel beyond). */
 WH_API int wh_op_vocab_soft_max( void* stream, const float* logits, float* probs, int rows, int cols );
+/* The kernel of wh_context_set_suppress outside a context: logits[ row ][ ids[ i ] ] = -inf for every row and i < count, in place; every other float keeps its
+ * bits. ids: DEVICE int32 [count]; an id outside [0, nVocab) is skipped. count == 0 launches nothing (ids may be NULL). Plain stores: no atomics, no LDS. */
+WH_API int wh_op_suppress_logits( void* stream, float* logits, int rows, int nVocab, const int32_t* ids, int count );
 /* The language-detection kernel of wh_lang_detect on logits [rows][nVocab]: langP [rows][nLang] = the probabilities wh_op_vocab_soft_max gives at columns
  * tokenSot + 1 .. tokenSot + nLang, bit for bit, without writing the other columns; best [rows] = the index (0 .. nLang - 1) of the largest, exact ties
  * to the lower index. The row stays in registers: nVocab <= 52224; 1 <= nLang <= 1024 and the block inside the row, or WH_E_INVALIDARG. */

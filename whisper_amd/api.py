@@ -79,6 +79,9 @@ def lib():
         L.whisperc_window_stats.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
         L.whisperc_batch_set_fallback.argtypes = [vp, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint64]
         L.whisperc_tr_window_stats.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.whisperc_non_speech_tokens.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.whisperc_set_suppress_tokens.argtypes = [vp, vp, C.c_uint32]
+        L.whisperc_batch_set_suppress_tokens.argtypes = [vp, vp, C.c_uint32]
         L.whisperc_resample.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64)]
         L.whisperc_load_audio.argtypes = [C.c_char_p, C.c_int32, vp, C.c_int64, C.POINTER(C.c_int64)]
         L.whisperc_run_full_stereo.argtypes = [vp, vp, vp, C.c_uint32, C.c_char_p, C.c_uint32, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]
@@ -279,10 +282,30 @@ class Model:
         a = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
         _check(lib().whisperc_model_set_alignment_heads(self.h, a.ctypes.data_as(C.c_void_p) if len(a) else None, len(a)), "setAlignmentHeads")
 
+    def non_speech_tokens(self) -> List[int]:
+        """Whisper::getNonSpeechTokens: the ids openai-whisper suppresses by default (brackets, quotes that open a word, note symbols ...), found by exact match
+        in this model's vocabulary; ascending."""
+        n = C.c_uint32(0)
+        _check(lib().whisperc_non_speech_tokens(self.h, None, 0, C.byref(n)), "getNonSpeechTokens")
+        ids = np.zeros(max(n.value, 1), np.int32)
+        _check(lib().whisperc_non_speech_tokens(self.h, ids.ctypes.data_as(C.c_void_p), n.value, C.byref(n)), "getNonSpeechTokens")
+        return [int(i) for i in ids[:n.value]]
+
     def tokenize(self, text: str) -> List[int]:
         buf = (C.c_int32 * 4096)()
         n = _check(lib().whisperc_tokenize(self.h, text.encode(), buf, 4096), "tokenize")
         return list(buf[:n])
+
+
+def _suppress_ids(model: Model, ids) -> np.ndarray:
+    """ids | "non_speech" | None -> int32 array"""
+    if ids is None:
+        return np.zeros(0, np.int32)
+    if isinstance(ids, str):
+        if ids != "non_speech":
+            raise ValueError('set_suppress_tokens: the only named set is "non_speech"')
+        ids = model.non_speech_tokens()
+    return np.ascontiguousarray(ids, np.int32).reshape(-1)
 
 
 class WindowStatsC(C.Structure):
@@ -394,6 +417,13 @@ class Context:
             return
         _check(lib().whisperc_set_fallback(self.h, 1, float(temperature_inc), logprob_thold, entropy_thold, no_speech_thold, seed), "setDecodingFallback")
 
+    def set_suppress_tokens(self, ids=None):
+        """Whisper::setSuppressedTokens: the logits of these token ids (text tokens, each below eot) are -inf before the softmax in every later run of this
+        context -- greedy, the fallback's sampled attempts, beam search -- so they are never emitted. "non_speech": Model.non_speech_tokens(). None or []
+        turns it off, the state of a new context: the transcript is then what it always was."""
+        a = _suppress_ids(self.model, ids)
+        _check(lib().whisperc_set_suppress_tokens(self.h, a.ctypes.data_as(C.c_void_p) if len(a) else None, len(a)), "setSuppressedTokens")
+
     def window_stats(self):
         """What the fallback did with each window of the last run: [{seek, attempts, temperature, no_speech, avg_logprob, entropy, skipped}], empty when
         the feature was off."""
@@ -503,6 +533,11 @@ class BatchRunner:
             _check(lib().whisperc_batch_set_fallback(self.h, 0, 0.0, 0.0, 0.0, 0.0, 0), "setBatchDecodingFallback")
             return
         _check(lib().whisperc_batch_set_fallback(self.h, 1, float(temperature_inc), logprob_thold, entropy_thold, no_speech_thold, seed), "setBatchDecodingFallback")
+
+    def set_suppress_tokens(self, ids=None):
+        """Whisper::setBatchSuppressedTokens: Context.set_suppress_tokens for every stream of this runner's later runs (one set for all of them)."""
+        a = _suppress_ids(self.model, ids)
+        _check(lib().whisperc_batch_set_suppress_tokens(self.h, a.ctypes.data_as(C.c_void_p) if len(a) else None, len(a)), "setBatchSuppressedTokens")
 
     def run(self, streams, language: str = "en", flags: int = 0, max_tokens: int = 0, prompt: Optional[Sequence[int]] = None,
             n_max_text_ctx: int = -1, want_results: bool = True, sample_rate: int = 16000, stereo: Optional[Sequence] = None):

@@ -56,6 +56,7 @@ EXPORTS = [
     "wh_model_set_alignment_heads", "wh_align_tokens", "wh_op_align_matrix", "wh_op_dtw",
     "wh_op_vocab_soft_max_scaled", "wh_op_sample_draw", "wh_op_philox_u", "wh_context_set_sampling", "wh_context_set_no_speech", "wh_decode_window_no_speech",
     "wh_context_set_sampling_rows", "wh_op_sample_rows",
+    "wh_context_set_suppress", "wh_op_suppress_logits",
 ]
 
 
@@ -197,6 +198,8 @@ def lib():
         L.wh_context_set_sampling_rows.argtypes = [vp, i32, vp, vp, vp]
         L.wh_op_sample_rows.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]
         L.wh_decode_window_no_speech.argtypes = [vp, vp]
+        L.wh_context_set_suppress.argtypes = [vp, vp, i32]
+        L.wh_op_suppress_logits.argtypes = [vp, vp, i32, i32, vp, i32]
         _lib = L
     return _lib
 
@@ -356,6 +359,11 @@ class HipContext:
         n = np.ascontiguousarray(nonces if nonces is not None else np.zeros(len(t)), np.uint32)
         assert len(s) == len(t) and len(n) == len(t)
         check(lib().wh_context_set_sampling_rows(self.handle, len(t), t.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p), n.ctypes.data_as(C.c_void_p)))
+
+    def set_suppress(self, ids=None):
+        """The logits of these token ids (each < eot) are -inf before the softmax in every later decoder pass of the context; None or an empty list turns it off."""
+        a = np.ascontiguousarray(ids if ids is not None else [], np.int32).reshape(-1)
+        check(lib().wh_context_set_suppress(self.handle, a.ctypes.data_as(C.c_void_p) if len(a) else None, len(a)))
 
     def set_no_speech(self, on: bool):
         """on: every window start also gathers P( <|nospeech|> ) of the prompt step (window_no_speech)."""

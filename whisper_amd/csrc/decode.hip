@@ -1,5 +1,6 @@
 // The decoder graph, host-stepped decoding (wh_decode), language detection, the sampler step, the greedy loop and its window.
 #include "runtime.h"
+#include <algorithm>
 
 static int attnDecP( wh_context* c, const DecAttnArgs& a, int keysHint = -1 )
 {
@@ -17,6 +18,17 @@ static int attnDecP( wh_context* c, const DecAttnArgs& a, int keysHint = -1 )
 		flops += 2.0 * a.batch * a.nTok * d * d;
 	}
 	return profiled( c, a.causal ? KC_ATTN_DEC : KC_ATTN_DEC_CROSS, flops, bytes, [ & ]() { return launchAttentionDec( a, c->stream ); } );
+}
+
+// The ONE place suppressed tokens take effect (wh_context_set_suppress): behind the launch that finishes c->logits, -inf over the set's columns of every row. Every
+// consumer -- wh_decode's softmax, the greedy, tempered and per-row samplers, the beam step, the no-speech gather -- reads the filtered row and none of them changes.
+// Accounted under the sampler's class: timingsPrint's sections are the reference's.
+static int suppressLogits( wh_context* c, int batch )
+{
+	if( c->suppressCount <= 0 || c->suppressBypass ) return 0;
+	const int nVocab = c->m->hp.n_vocab, cap = specialIds( c->m->hp ).sot - 1;
+	return profiled( c, KC_SAMPLE, 0.0, 4.0 * batch * c->suppressCount,
+		[ & ]() { return launchSuppressLogits( c->logits, batch, nVocab, c->suppress + 1, c->suppress, 0, cap, c->stream ); } );
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -194,7 +206,7 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 			a.pro = 1; a.g.lnX = c->dx; a.g.lnW = m->at<float>( L.decLnW ); a.g.lnB = m->at<float>( L.decLnB );
 			WH_CHECK( smallGemv( a ) );
 		}
-		return 0;
+		return suppressLogits( c, batch );
 	}
 
 	for( int il = 0; il < hp.n_text_layer; il++ )
@@ -332,7 +344,7 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 		else
 			WH_CHECK( product( g, nullptr, nullptr ) );
 	}
-	return 0;
+	return suppressLogits( c, batch );
 }
 
 // Token ids index the embedding table: anything outside [0, n_vocab) is rejected at the boundary (the reference's addRows
@@ -421,7 +433,11 @@ int wh_lang_detect( wh_context* c, int batch, float* langP, int32_t* best )
 	}
 	else
 	{
-		WH_CHECK( decodeGraph( c, seqs, 1, 0, false ) );
+		// detection is the model's own distribution at [sot]: the pass runs unfiltered whatever set the context holds (set around the call like AlignHook)
+		c->suppressBypass = true;
+		const int rcGraph = decodeGraph( c, seqs, 1, 0, false );
+		c->suppressBypass = false;
+		WH_CHECK( rcGraph );
 		WH_CHECK( profiled( c, KC_SOFTMAX, 10.0 * batch * hp.n_vocab, 4.0 * batch * hp.n_vocab,
 			[ & ]() { return launchLangProbs( c->logits, rowStride, batch, hp.n_vocab, sot, nLang, c->langP, c->langBest, st ); } ) );
 	}
@@ -452,10 +468,11 @@ extern "C" {
 
 // What a captured step graph depends on besides the batch: the parity mode and the sampler (greedy or temperature: other kernels, the same graph for every temperature)
 constexpr uint32_t STEP_KEY_ROWS = 0x40000u;	  // per-row sampling (wh_context_set_sampling_rows)
+constexpr uint32_t STEP_KEY_SUPPRESS = 0x80000u;   // a suppressed set is held (wh_context_set_suppress): the graph has one more node, the same for every set
 static uint32_t stepGraphKey( const wh_context* c )
 {
 	return ( ( c->flags & WH_FLAG_PARITY_PV ) ? ( 0x10000u | (uint32_t)c->parityThreads ) : 0u ) | ( c->temperature > 0.0f ? 0x20000u : 0u ) |
-		( c->sampleRowsOn ? STEP_KEY_ROWS : 0u );
+		( c->sampleRowsOn ? STEP_KEY_ROWS : 0u ) | ( c->suppressCount > 0 ? STEP_KEY_SUPPRESS : 0u );
 }
 // Captured steps that cannot serve ( batch, key ) or its sibling in the other per-row mode go (see wh_context::stepGraphs); true when one went
 static bool dropStaleStepGraphs( wh_context* c, int batch, uint32_t key )
@@ -890,6 +907,41 @@ int wh_context_set_sampling_rows( wh_context* c, int rows, const float* temperat
 	WH_HIP( hipMemcpyAsync( c->sampleRows, c->sampleRowsPin, sizeof( SampleRowParams ) * (size_t)c->maxSeq, hipMemcpyHostToDevice, c->stream ) );
 	WH_HIP( hipEventRecord( c->sampleRowsEv, c->stream ) );
 	c->sampleRowsOn = rows;
+	return 0;
+}
+
+// Suppressed tokens. The sorted unique set and its count go to device memory behind what the stream holds; the captured graphs are keyed on
+// "a set is held" only, and the beam step's graph, which has no key, goes when that state flips.
+int wh_context_set_suppress( wh_context* c, const int32_t* ids, int count )
+{
+	if( !c || count < 0 || ( count > 0 && !ids ) ) { setError( "context_set_suppress: null context, a negative count or null ids" ); return WH_E_INVALIDARG; }
+	const int eot = specialIds( c->m->hp ).sot - 1;
+	for( int i = 0; i < count; i++ )
+		if( ids[ i ] < 0 || ids[ i ] >= eot )
+		{
+			char buf[ 160 ];
+			snprintf( buf, sizeof( buf ), "context_set_suppress: id %d at index %d is outside [0, %d): only text tokens can be suppressed", (int)ids[ i ], i, eot );
+			setError( buf );
+			return WH_E_INVALIDARG;
+		}
+	if( count > 0 && ( c->flags & WH_FLAG_PARITY_EXACT ) ) { setError( "context_set_suppress: not available under WH_FLAG_PARITY_EXACT" ); return WH_E_INVALIDARG; }
+	if( count == 0 && !c->suppress ) return 0;
+	WH_BIND( c->m );
+	std::vector<int32_t> up( 1 );
+	up.insert( up.end(), ids, ids + count );
+	std::sort( up.begin() + 1, up.end() );
+	up.erase( std::unique( up.begin() + 1, up.end() ), up.end() );
+	up[ 0 ] = (int32_t)up.size() - 1;
+	if( !c->suppress ) WH_CHECK( c->alloc( c->suppress, (int64_t)eot + 1, wh_context::MUST_BE_ZERO, "suppress" ) );
+	WH_HIP( hipMemcpyAsync( c->suppress, up.data(), sizeof( int32_t ) * up.size(), hipMemcpyHostToDevice, c->stream ) );
+	WH_HIP( hipStreamSynchronize( c->stream ) );	 // `up` is this call's; the stream is idle below
+	if( ( up[ 0 ] > 0 ) != ( c->suppressCount > 0 ) && c->beamGraphExec )
+	{
+		(void)hipGraphExecDestroy( c->beamGraphExec );
+		c->beamGraphExec = nullptr;
+		c->beamGraphBatch = 0;
+	}
+	c->suppressCount = up[ 0 ];
 	return 0;
 }
 

@@ -462,6 +462,9 @@ namespace wh
 	int launchPhiloxU( unsigned long long seed, unsigned nonce, int rows, const int* positions, double* uOut, hipStream_t stream );
 	// out[ row ] = p[ tokenSolm ] of the row the sampler left in `probs`; spreadScratch non-null: the row holds the spread sampler's unnormalised e and is
 	// normalised by the sum of its slice records (what sampleSpreadFinal multiplies by)
+	// Suppressed tokens: logits [rows][nVocab] get -inf at columns ids[ 0 .. count ) (device, ascending), count = *countDev when countDev is non-null, at most cap;
+	// the grid depends on the rows alone
+	int launchSuppressLogits( float* logits, int rows, int nVocab, const int* ids, const int* countDev, int count, int cap, hipStream_t stream );
 	int launchNoSpeechGather( const float* probs, const void* spreadScratch, int rows, int nVocab, int tokenSolm, float* out, hipStream_t stream );
 	// Prompt steps whose sequences differ in length (rows right-padded to nTok tokens): the normalised row of sequence b's LAST real
 	// token, lastPos[b] (device), is copied over its row nTok - 1, where the vocabulary product of a prompt step reads. In place, f16 rows.

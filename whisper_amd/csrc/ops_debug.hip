@@ -340,6 +340,13 @@ int wh_op_vocab_soft_max( void* stream, const float* logits, float* probs, int r
 	return launchVocabSoftMax( logits, probs, rows, cols, (hipStream_t)stream );
 }
 
+int wh_op_suppress_logits( void* stream, float* logits, int rows, int nVocab, const int32_t* ids, int count )
+{
+	if( !logits || rows < 1 || nVocab < 1 || count < 0 || ( count > 0 && !ids ) ) { setError( "suppress_logits: null pointer, empty shape or negative count" ); return WH_E_INVALIDARG; }
+	if( count == 0 ) return 0;
+	return launchSuppressLogits( logits, rows, nVocab, ids, nullptr, count, count, (hipStream_t)stream );
+}
+
 int wh_op_lang_probs( void* stream, const float* logits, int rows, int nVocab, int tokenSot, int nLang, float* langP, int32_t* best )
 {
 	if( !logits || !langP || !best || rows < 1 || nVocab < 1 || nVocab > 52224 || nLang < 1 || nLang > 1024 || tokenSot < 0 || (int64_t)tokenSot + 1 + nLang > nVocab )
@@ -773,9 +780,12 @@ int wh_debug_probe( wh_context* c, int kind, int variant, int M, int N, int K, i
 	{
 		// The sampler of a decode step on M rows of N columns: variant 0 = the fused greedy sampler (launchSoftMaxSample), 1 = the per-row step with every row
 		// greedy (launchVocabSoftMaxRows + launchSampleRows) -- what a round with one retrying row costs its greedy neighbours. The logits rotate through
-		// buffers that together exceed the last-level cache (512 MB); 5 warm-up launches, then the MEDIAN of `iters` launches, each between its own events.
+		// buffers that together exceed the last-level cache (512 MB; at most 64 buffers); 5 warm-up launches, then the MEDIAN of `iters` launches, each between its
+		// own events. Variant 2 = the logit filter of wh_context_set_suppress with K ids in front of the fused greedy sampler, 3 = the filter alone (tools/suppress_probe.py).
 		const int rows = M, nVocab = N;
-		if( rows < 1 || rows > 4096 || nVocab < 2048 || nVocab > 52224 || variant < 0 || variant > 1 ) return WH_E_INVALIDARG;
+		if( rows < 1 || rows > 4096 || nVocab < 2048 || nVocab > 52224 || variant < 0 || variant > 3 ) return WH_E_INVALIDARG;
+		const int nIds = variant >= 2 ? K : 0;
+		if( variant >= 2 && ( nIds < 1 || nIds > nVocab - 1607 ) ) return WH_E_INVALIDARG;
 		const size_t rowBytes = (size_t)rows * nVocab * 4;
 		const int nBuf = (int)std::min<size_t>( 64, ( (size_t)512 << 20 ) / rowBytes + 2 );
 		std::vector<float*> logits( (size_t)nBuf, nullptr );
@@ -791,6 +801,15 @@ int wh_debug_probe( wh_context* c, int kind, int variant, int M, int N, int K, i
 		WH_CHECK( mem.alloc( &next, sizeof( int ) * (size_t)rows ) );
 		WH_CHECK( mem.alloc( &pos, sizeof( int ) * (size_t)rows ) );
 		WH_CHECK( mem.alloc( &rowParams, sizeof( SampleRowParams ) * (size_t)rows ) );
+		int* ids = nullptr;
+		std::vector<int> idsHost( (size_t)nIds );
+		// ascending ids spread over the text tokens, as a sorted set is
+		for( int i = 0; i < nIds; i++ ) idsHost[ (size_t)i ] = (int)( (long long)i * ( nVocab - 1607 ) / nIds );
+		if( nIds > 0 )
+		{
+			WH_CHECK( mem.alloc( &ids, sizeof( int ) * (size_t)nIds ) );
+			WH_HIP( hipMemcpyAsync( ids, idsHost.data(), sizeof( int ) * (size_t)nIds, hipMemcpyHostToDevice, st ) );
+		}
 		for( int b = 0; b < nBuf; b++ ) hipLaunchKernelGGL( probeFillF32, dim3( 1024 ), dim3( 256 ), 0, st, logits[ b ], (long long)rows * nVocab, 11u + (unsigned)b );
 		WH_HIP( hipMemsetAsync( state, 0, sizeof( DecodeState ), st ) );	 // step 0, no flags, no mailbox: every launch writes slot 0
 		WH_HIP( hipMemsetAsync( pos, 0, sizeof( int ) * (size_t)rows, st ) );
@@ -799,9 +818,11 @@ int wh_debug_probe( wh_context* c, int kind, int variant, int M, int N, int K, i
 		WH_HIP( hipStreamSynchronize( st ) );
 		const int beg = nVocab - 1501, sot = beg - 105, solm = beg - 2, tnot = beg - 1;
 		const SampleMailbox noMail = { nullptr, nullptr };
-		const auto launch = [ & ]( const float* x ) -> int
+		const auto launch = [ & ]( float* x ) -> int
 		{
-			if( variant == 0 ) return launchSoftMaxSample( x, probs, rows, nVocab, beg, sot, solm, tnot, state, out, next, noMail, st );
+			if( variant >= 2 ) WH_CHECK( launchSuppressLogits( x, rows, nVocab, ids, nullptr, nIds, nIds, st ) );
+			if( variant == 3 ) return 0;
+			if( variant == 0 || variant == 2 ) return launchSoftMaxSample( x, probs, rows, nVocab, beg, sot, solm, tnot, state, out, next, noMail, st );
 			WH_CHECK( launchVocabSoftMaxRows( x, rowParams, probs, rows, nVocab, st ) );
 			return launchSampleRows( probs, rows, nVocab, beg, sot, solm, tnot, 0, 0, state, rowParams, pos, out, next, noMail, st );
 		};

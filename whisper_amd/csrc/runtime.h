@@ -203,6 +203,12 @@ struct wh_context
 	int sampleRowsOn = 0;
 	SampleRowParams *sampleRows = nullptr, *sampleRowsPin = nullptr;
 	hipEvent_t sampleRowsEv = nullptr;
+	// suppressed tokens (wh_context_set_suppress): suppressCount != 0 = decodeGraph ends with one launch that writes -inf over those columns of c->logits. suppress =
+	// [ count ][ ids: eot ] int32 in device memory, allocated by the first call with a non-empty set (before any capture) and never again: a captured step reads the
+	// count and the ids from it, so a change of the set recaptures nothing. suppressBypass is set around the one pass that must see the model's own row (wh_lang_detect).
+	int suppressCount = 0;
+	int* suppress = nullptr;
+	bool suppressBypass = false;
 	// wh_context_set_no_speech: p[ solm ] of the prompt step's rows, gathered behind the first sample of every window (allocated by the first call that turns it on)
 	bool noSpeech = false;
 	float* noSpeechDev = nullptr;

@@ -599,6 +599,23 @@ namespace wh
 			if( tid == 0 ) publish( pick );
 		}
 
+		// ---- suppressed tokens (wh_context_set_suppress; DESIGN.md section 7 "Suppressed tokens") ----------------------
+		// logits[ row ][ ids[ i ] ] = -inf for i < count, one workgroup per row: every kernel above reads -inf as probability 0, so nothing downstream changes. The
+		// count comes from device memory when countDev is non-null (a captured step graph outlives a change of the set) and is held to `cap`, the ids' allocation;
+		// an id outside the row is skipped. The ids are ascending, so neighbouring lanes store to ascending addresses of a row the vocabulary product just wrote.
+		__global__ void __launch_bounds__( 256 ) suppressLogitsKernel( float* __restrict__ logits, int nVocab, const int* __restrict__ ids, const int* __restrict__ countDev,
+			int count, int cap )
+		{
+			float* const x = logits + (long long)blockIdx.x * nVocab;
+			if( countDev ) count = *countDev;
+			count = min( count, cap );
+			for( int i = threadIdx.x; i < count; i += 256 )
+			{
+				const int id = ids[ i ];
+				if( (unsigned)id < (unsigned)nVocab ) x[ id ] = -INFINITY;
+			}
+		}
+
 		bool drawShapeOk( int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot )
 		{
 			return rows >= 1 && nVocab >= 1 && nVocab <= SAMPLE_DRAW_MAX_VOCAB && tokenBeg >= 1 && tokenBeg < nVocab && tokenSot >= 0 && tokenSot < tokenBeg &&
@@ -631,6 +648,14 @@ namespace wh
 			hipLaunchKernelGGL( softMaxRowsReg<true>, dim3( rows ), dim3( 1024 ), 0, stream, logits, probs, nVocab, invT, invTDev );
 		else
 			hipLaunchKernelGGL( softMaxRows<true>, dim3( rows ), dim3( 1024 ), 0, stream, logits, probs, nVocab, invT, invTDev );
+		WH_HIP( hipGetLastError() );
+		return 0;
+	}
+
+	int launchSuppressLogits( float* logits, int rows, int nVocab, const int* ids, const int* countDev, int count, int cap, hipStream_t stream )
+	{
+		if( !logits || !ids || rows < 1 || nVocab < 1 || count < 0 || cap < 0 ) { setError( "suppressLogits: bad argument" ); return -1; }
+		hipLaunchKernelGGL( suppressLogitsKernel, dim3( rows ), dim3( 256 ), 0, stream, logits, nVocab, ids, countDev, count, cap );
 		WH_HIP( hipGetLastError() );
 		return 0;
 	}

@@ -23,6 +23,7 @@
 #include "hostCommon.h"
 #include "hostLoop.h"
 #include "batchSampling.h"
+#include "batchSuppress.h"
 #include "decodeFallback.h"
 #include "languageDetect.h"
 #include "results.h"
@@ -39,6 +40,8 @@ namespace Whisper
 	pfnBatchLanguageDetector g_batchLanguageDetector = nullptr;
 	// ... and for per-row sampling and the no-speech gather (batchSampling.h)
 	const BatchSamplingHooks* g_batchSamplingHooks = nullptr;
+	// ... and for suppressed tokens (batchSuppress.h)
+	pfnBatchSuppress g_batchSuppress = nullptr;
 
 	namespace
 	{
@@ -186,6 +189,8 @@ namespace Whisper
 			std::vector<uint64_t> seed;
 			std::vector<uint32_t> nonce;
 			bool gathers = false;
+			// suppressed tokens: the version of the runner's set this group's context holds (0 = never told: a new context holds none)
+			uint32_t suppressVersion = 0;
 		};
 
 		// One call of iBatchRunner::run over the runner's groups (their wh_contexts outlive the call: KV caches, captured graphs)
@@ -664,7 +669,29 @@ namespace Whisper
 			// Whisper::setBatchDecodingFallback: off unless set. modesDirty: a run with the feature on left the groups' contexts in its modes
 			bool fallbackOn = false, modesDirty = false;
 			sDecodingFallback fallbackParams;
+			// Whisper::setBatchSuppressedTokens: one set for every stream; each group's context is told once, before the first round that follows a change
+			std::vector<int32_t> suppressIds;
+			uint32_t suppressVersion = 0;
 		public:
+			HRESULT setSuppressed( const int32_t* ids, uint32_t count )
+			{
+				if( count && !ids ) return E_POINTER;
+				for( uint32_t i = 0; i < count; i++ )
+					if( ids[ i ] < 0 || ids[ i ] >= model->vocab.token_eot )
+					{
+						logError( "setBatchSuppressedTokens: id %i is outside [ 0, %i ): only text tokens can be suppressed", (int)ids[ i ], model->vocab.token_eot );
+						return E_INVALIDARG;
+					}
+				if( count && !g_batchSuppress )
+				{
+					logError( "setBatchSuppressedTokens: this build of the scheduler was not given the device's logit filter" );
+					return E_NOTIMPL;
+				}
+				if( count == 0 && suppressIds.empty() ) return S_OK;
+				suppressIds.assign( ids, ids + count );
+				suppressVersion++;
+				return S_OK;
+			}
 			HRESULT setFallback( const sDecodingFallback* p )
 			{
 				if( !p ) { fallbackOn = false; return S_OK; }
@@ -745,6 +772,12 @@ namespace Whisper
 				// one sFullParams for every stream of the batch: its audio_ctx is the groups' (ContextImpl.cpp:488-489)
 				if( params.audio_ctx < 0 || params.audio_ctx > model->hp.n_audio_ctx ) return E_INVALIDARG;
 				for( Group& g : groups ) CHECK_WH( wh_context_set_audio_ctx( g.gpu, params.audio_ctx ) );
+				for( Group& g : groups )
+					if( g.suppressVersion != suppressVersion && g_batchSuppress )
+					{
+						CHECK_WH( g_batchSuppress( g.gpu, suppressIds.data(), (int)suppressIds.size() ) );
+						g.suppressVersion = suppressVersion;
+					}
 				if( modesDirty && !fallbackOn )
 				{
 					// the feature was turned off: the contexts go back to the greedy sampler and gather nothing
@@ -789,6 +822,17 @@ namespace Whisper
 			return E_INVALIDARG;
 		}
 		return r->setFallback( params );
+	}
+	HRESULT setBatchSuppressedTokens( iBatchRunner* runner, const int32_t* ids, uint32_t count )
+	{
+		if( !runner ) return E_POINTER;
+		BatchRunner* const r = dynamic_cast<BatchRunner*>( runner );
+		if( !r )
+		{
+			logError( "setBatchSuppressedTokens: not a runner of this library's createBatchRunner" );
+			return E_INVALIDARG;
+		}
+		return r->setSuppressed( ids, count );
 	}
 	HRESULT getResultWindowStats( const iTranscribeResult* result, sWindowStats* stats, uint32_t* count )
 	{

@@ -385,7 +385,8 @@ int main( int argc, char** argv )
 	// dynamic time warping (eFullParamsFlags::AlignTokens) instead of the TokenTimestamps heuristic, for -ml / -owts and the tokens of the results
 	// --fallback (the same way): Whisper::setDecodingFallback with its defaults, a greedy window that scores badly is decoded again at rising temperatures and a
 	// window the model calls silent is dropped; -tpi / -lpt / -et / -nth N (whisper.cpp's names) set temperatureInc, logprobThold, entropyThold, noSpeechThold
-	bool align = false, useFallback = false;
+	// -sns / --suppress-nst (the same way; whisper.cpp's names): Whisper::setSuppressedTokens with the model's non-speech set (getNonSpeechTokens)
+	bool align = false, useFallback = false, suppressNst = false;
 	sDecodingFallback fallbackParams;
 	{
 		int kept = 1;
@@ -394,6 +395,7 @@ int main( int argc, char** argv )
 			float* value = nullptr;
 			if( !strcmp( argv[ i ], "--align" ) ) align = true;
 			else if( !strcmp( argv[ i ], "--fallback" ) ) useFallback = true;
+			else if( !strcmp( argv[ i ], "-sns" ) || !strcmp( argv[ i ], "--suppress-nst" ) ) suppressNst = true;
 			else if( !strcmp( argv[ i ], "-tpi" ) ) value = &fallbackParams.temperatureInc;
 			else if( !strcmp( argv[ i ], "-lpt" ) ) value = &fallbackParams.logprobThold;
 			else if( !strcmp( argv[ i ], "-et" ) ) value = &fallbackParams.entropyThold;
@@ -449,6 +451,15 @@ int main( int argc, char** argv )
 	{
 		hr = setDecodingFallback( context, &fallbackParams );
 		if( FAILED( hr ) ) { printFailure( "failed to set the decoding fallback", hr ); return 6; }
+	}
+	if( suppressNst )
+	{
+		uint32_t n = 0;
+		hr = getNonSpeechTokens( model, nullptr, &n );
+		std::vector<int32_t> ids( n );
+		if( SUCCEEDED( hr ) ) hr = getNonSpeechTokens( model, ids.data(), &n );
+		if( SUCCEEDED( hr ) ) hr = setSuppressedTokens( context, ids.data(), n );
+		if( FAILED( hr ) ) { printFailure( "failed to suppress the non-speech tokens", hr ); return 6; }
 	}
 
 	ComLight::CComPtr<iMediaFoundation> media;

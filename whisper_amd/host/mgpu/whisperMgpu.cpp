@@ -52,6 +52,9 @@ namespace
 		// entropyThold, noSpeechThold
 		bool useFallback = false;
 		sDecodingFallback fallback;
+		// -sns / --suppress-nst: Whisper::setBatchSuppressedTokens on every rank's runner with the model's non-speech set (getNonSpeechTokens: every rank computes
+		// the same set from the same vocabulary)
+		bool suppressNst = false;
 	};
 	std::wstring widen( const std::string& s )
 	{
@@ -121,7 +124,7 @@ namespace
 			while( true ) sleep( 1000 );
 	}
 
-	const char* const USAGE = "usage: whisper-mgpu -n ranks -m model.bin -f audio.wav [-l en] [-o out.txt] [-timeout seconds (rendezvous and collectives)] [-job-timeout seconds (whole job; default none)] [-slots n] [-id id-file] [-job token] [-split fixed|silence (where the chunks of the recording end: every 30 s, or at pauses)] [-per-recording -f more.wav ...] [-fallback (quality gates and temperature retries per window) [-tpi N] [-lpt N] [-et N] [-nth N]]\n";
+	const char* const USAGE = "usage: whisper-mgpu -n ranks -m model.bin -f audio.wav [-l en] [-o out.txt] [-timeout seconds (rendezvous and collectives)] [-job-timeout seconds (whole job; default none)] [-slots n] [-id id-file] [-job token] [-split fixed|silence (where the chunks of the recording end: every 30 s, or at pauses)] [-per-recording -f more.wav ...] [-fallback (quality gates and temperature retries per window) [-tpi N] [-lpt N] [-et N] [-nth N]] [-sns (suppress the non-speech tokens)]\n";
 
 	// splitAtPauses hands the plan out through a callback: keep the streams
 	HRESULT keepStreams( const sBatchStream* s, uint32_t n, void* pv )
@@ -249,6 +252,15 @@ namespace
 		{
 			hr = setBatchDecodingFallback( runner, &a.fallback );
 			if( FAILED( hr ) ) { fprintf( stderr, "[rank %d] setBatchDecodingFallback failed 0x%08x\n", rank, (unsigned)hr ); return 6; }
+		}
+		if( runner && a.suppressNst )
+		{
+			uint32_t n = 0;
+			hr = getNonSpeechTokens( model, nullptr, &n );
+			std::vector<int32_t> ids( n );
+			if( SUCCEEDED( hr ) ) hr = getNonSpeechTokens( model, ids.data(), &n );
+			if( SUCCEEDED( hr ) ) hr = setBatchSuppressedTokens( runner, ids.data(), n );
+			if( FAILED( hr ) ) { fprintf( stderr, "[rank %d] setBatchSuppressedTokens failed 0x%08x\n", rank, (unsigned)hr ); return 6; }
 		}
 
 		if( 0 != wh_comm_barrier( comm ) ) { fprintf( stderr, "[rank %d] %s\n", rank, wh_last_error() ); return 8; }
@@ -397,6 +409,7 @@ int main( int argc, char** argv )
 		else if( !strcmp( argv[ i ], "-job" ) ) a.job = val();
 		else if( !strcmp( argv[ i ], "-slots" ) ) a.slots = atoi( val() );
 		else if( !strcmp( argv[ i ], "-fallback" ) || !strcmp( argv[ i ], "--fallback" ) ) a.useFallback = true;
+		else if( !strcmp( argv[ i ], "-sns" ) || !strcmp( argv[ i ], "--suppress-nst" ) ) a.suppressNst = true;
 		else if( !strcmp( argv[ i ], "-tpi" ) ) a.fallback.temperatureInc = (float)atof( val() );
 		else if( !strcmp( argv[ i ], "-lpt" ) ) a.fallback.logprobThold = (float)atof( val() );
 		else if( !strcmp( argv[ i ], "-et" ) ) a.fallback.entropyThold = (float)atof( val() );

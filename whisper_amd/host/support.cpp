@@ -1,6 +1,7 @@
 // Logger, language table, vocabulary and the ggml file loader of libWhisper.so.
 #include "hostCommon.h"
 #include "ggmlTensor.h"
+#include "nonSpeechTokens.h"
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -467,6 +468,27 @@ namespace Whisper
 			for( const char* p = full; *p; p++ ) w += (wchar_t)(unsigned char)*p;
 			pfn( w.c_str(), pv );
 		}
+		return S_OK;
+	}
+
+	// The non-speech tokens of the model's own vocabulary (nonSpeechTokens.h), through the boundary: host only, no device call
+	HRESULT getNonSpeechTokens( iModel* model, int32_t* ids, uint32_t* count )
+	{
+		if( !model || !count ) return E_POINTER;
+		iModelInternals* in = nullptr;
+		if( FAILED( model->QueryInterface( iModelInternals::iid(), (void**)&in ) ) || !in )
+		{
+			logError( "getNonSpeechTokens: the model was not created by this library" );
+			return E_INVALIDARG;
+		}
+		const Vocabulary& vocab = in->loaded()->vocab;
+		const std::vector<int32_t> all = nonSpeechTokens( vocab.idToToken, vocab.token_eot );
+		model->Release();	  // QueryInterface's reference
+		const uint32_t cap = *count;
+		*count = (uint32_t)all.size();
+		if( !ids ) return S_OK;
+		if( cap < all.size() ) return E_BOUNDS;
+		std::copy( all.begin(), all.end(), ids );
 		return S_OK;
 	}
 }

@@ -10,6 +10,7 @@
 #include "hostLoop.h"
 #include "decodeFallback.h"
 #include "batchSampling.h"
+#include "batchSuppress.h"
 #include "languageDetect.h"
 #include "results.h"
 #include "wavFormat.h"
@@ -125,6 +126,8 @@ namespace Whisper
 			bool fallbackOn = false;
 			sDecodingFallback fallbackParams;
 			std::vector<sWindowStats> windowStats;
+			// Whisper::setSuppressedTokens: empty unless set; every device context this object owns holds it (beamContext tells the ones created later)
+			std::vector<int32_t> suppressIds;
 
 			using Clock = std::chrono::steady_clock;
 			static double msSince( Clock::time_point t ) { return std::chrono::duration<double, std::milli>( Clock::now() - t ).count(); }
@@ -208,6 +211,20 @@ namespace Whisper
 				}
 				fallbackParams = *p;
 				fallbackOn = true;
+				return S_OK;
+			}
+			HRESULT setSuppressed( const int32_t* ids, uint32_t count )
+			{
+				if( count && !ids ) return E_POINTER;
+				for( uint32_t i = 0; i < count; i++ )
+					if( ids[ i ] < 0 || ids[ i ] >= model->vocab.token_eot )
+					{
+						logError( "setSuppressedTokens: id %i is outside [ 0, %i ): only text tokens can be suppressed", (int)ids[ i ], model->vocab.token_eot );
+						return E_INVALIDARG;
+					}
+				CHECK_WH( wh_context_set_suppress( gpu, ids, (int)count ) );
+				if( gpuBeam ) CHECK_WH( wh_context_set_suppress( gpuBeam, ids, (int)count ) );
+				suppressIds.assign( ids, ids + count );
 				return S_OK;
 			}
 			const std::vector<sWindowStats>& lastWindowStats() const { return windowStats; }
@@ -485,6 +502,7 @@ namespace Whisper
 			if( gpuBeam ) { wh_context_destroy( gpuBeam ); gpuBeam = nullptr; }
 			CHECK_WH( wh_context_create_hyp( model->gpu, 1, slots, nullptr, &gpuBeam ) );
 			beamSlots = slots;
+			if( !suppressIds.empty() ) CHECK_WH( wh_context_set_suppress( gpuBeam, suppressIds.data(), (int)suppressIds.size() ) );
 			return S_OK;
 		}
 
@@ -1167,6 +1185,8 @@ namespace Whisper
 	// ... and to per-row sampling and the no-speech gather (batchSampling.h)
 	static const BatchSamplingHooks g_samplingHooks = { &wh_context_set_sampling_rows, &wh_context_set_no_speech, &wh_decode_window_no_speech };
 	static const bool g_samplingInstalled = ( g_batchSamplingHooks = &g_samplingHooks, true );
+	// ... and to the logit filter of suppressed tokens (batchSuppress.h)
+	static const bool g_suppressInstalled = ( g_batchSuppress = &wh_context_set_suppress, true );
 
 	HRESULT createContextImpl( const std::shared_ptr<LoadedModel>& model, iModel* owner, iContext** pp )
 	{
@@ -1201,6 +1221,17 @@ namespace Whisper
 			return E_INVALIDARG;
 		}
 		return c->setFallback( params );
+	}
+	HRESULT setSuppressedTokens( iContext* context, const int32_t* ids, uint32_t count )
+	{
+		if( !context ) return E_POINTER;
+		ContextImpl* const c = dynamic_cast<ContextImpl*>( context );
+		if( !c )
+		{
+			logError( "setSuppressedTokens: not a context of this library's createContext (a batch runner takes setBatchSuppressedTokens)" );
+			return E_INVALIDARG;
+		}
+		return c->setSuppressed( ids, count );
 	}
 	HRESULT getWindowStats( const iContext* context, sWindowStats* stats, uint32_t* count )
 	{
@@ -1396,6 +1427,24 @@ WHISPER_EXPORT int32_t whisperc_batch_set_fallback( void* runner, int32_t on, fl
 	sDecodingFallback p;
 	p.temperatureInc = temperatureInc; p.logprobThold = logprobThold; p.entropyThold = entropyThold; p.noSpeechThold = noSpeechThold; p.seed = seed;
 	return setBatchDecodingFallback( (iBatchRunner*)runner, &p );
+}
+// Whisper::getNonSpeechTokens: out = int32 [cap] (may be NULL), *count = the size of the model's non-speech set
+WHISPER_EXPORT int32_t whisperc_non_speech_tokens( void* model, int32_t* out, uint32_t cap, uint32_t* count )
+{
+	if( !model || !count ) return E_POINTER;
+	*count = cap;
+	return getNonSpeechTokens( (iModel*)model, out, count );
+}
+// Whisper::setSuppressedTokens / setBatchSuppressedTokens: count == 0 turns suppression off (ids may be NULL)
+WHISPER_EXPORT int32_t whisperc_set_suppress_tokens( void* ctx, const int32_t* ids, uint32_t count )
+{
+	if( !ctx ) return E_POINTER;
+	return setSuppressedTokens( (iContext*)ctx, ids, count );
+}
+WHISPER_EXPORT int32_t whisperc_batch_set_suppress_tokens( void* runner, const int32_t* ids, uint32_t count )
+{
+	if( !runner ) return E_POINTER;
+	return setBatchSuppressedTokens( (iBatchRunner*)runner, ids, count );
 }
 // Whisper::getResultWindowStats: out = sWindowStats [cap] (may be NULL), *count = the windows of the result's stream
 WHISPER_EXPORT int32_t whisperc_tr_window_stats( void* result, void* out, uint32_t cap, uint32_t* count )
