@@ -547,6 +547,35 @@ WH_API int wh_op_decoder_cross_attention( void* stream, const float* x, const fl
 /* softMax over rows with the reference's FP16 exp table semantics (softMax.hlsl / ggml.c:5030-5090): in place, FP32 */
 WH_API int wh_op_soft_max( void* stream, float* x, int rows, int cols );
 
+/* ---- op-level entry points of the single-token step's own kernels (what wh_decode launches for 1 .. 4 sequences, and the fused self-attention half of a
+ * lock-step batch of 9 .. 32): WhisperContext.cpp:412-520. Device pointers; no prefetch hints; restated in float64 by tests/decode_step_ref.py. ---- */
+
+/* gemvSmall: out[m][n] = epilogue( sum_k w[n][k] * x[m][k] ), w FP16 [N][K], 1 <= M <= 4 rows, K a multiple of 8 and at most 8192, FP32 accumulation.
+ * pro: 0  x = aF16, FP16 [M][K];
+ *      1  x = fp16( LayerNorm( lnX[m] ) * lnW + lnB ), lnX FP32 [M][K], K <= 2048;
+ *      3  x[m][h*64 + j] = fp16( ( sum over the 8 splits, in order, of part[m][h][s][j] ) * float( 1 / sum over the splits of the double at part[m][h][s][64] ) ),
+ *         part FP32 [M][K/64][8][68] as wh_op_cross_split leaves it, K a multiple of 64.
+ * epi: 0  out32 FP32 [M][N] = acc (+ bias[n]) (+ residual[m][n]);
+ *      1  out16 FP16 [M][N] = gelu16( acc + bias[n] );
+ *      2  the decoder's Q/K/V product (N = 3 K, K = 64 heads): qF16 FP16 [M][K] = fp16( ( acc + bias ) * scale ); row pos of sequence m of kCache / vCache,
+ *         FP16 [M][heads][textCtx][64], = fp16( acc * scale ) / fp16( acc + bias ), pos = nPastDev ? nPastDev[ m ] : nPast. Nothing else in the caches is written.
+ * Operands a combination does not use may be NULL. Bad shapes or missing operands: an error, nothing is launched. */
+WH_API int wh_op_gemv_small( void* stream, int M, int N, int K, int epi, int pro, const void* wF16, const void* aF16, const float* lnX, const float* lnW,
+	const float* lnB, const float* part, const float* bias, const float* residual, float* out32, void* out16, void* qF16, void* kCache, void* vCache, int heads,
+	int textCtx, int nPast, const int32_t* nPastDev, float scale );
+/* crossScores then crossSoftmaxPV: the cross-attention of up to 4 sequences over 8 key ranges per head, range length ( ( nKeys + 7 ) / 8 + 3 ) & ~3. The query is
+ * wh_op_decoder_cross_attention's. scores FP32 [sequences][heads][keyStride] = K . q for key < nKeys; splitMax FP32 [sequences][heads][8] = the maximum of each
+ * range (-inf for an empty one); part FP32 [sequences][heads][8][68]: 64 sums of exp16( score - max over ALL ranges ) * V, the double sum of the exponentials at
+ * floats 64 .. 65, two floats never written. nKeys <= 1536, heads * 64 <= 1280. wh_op_gemv_small( pro 3 ) combines the ranges. */
+WH_API int wh_op_cross_split( void* stream, const float* x, const float* lnW, const float* lnB, const void* qW, const float* qB, float qScale,
+	const void* kCache, const void* vCache, float* scores, float* splitMax, float* part, int sequences, int heads, int nKeys, int keyStride );
+/* selfBlockDec: LayerNorm -> this head's rows of the fused FP16 [3d][d] weight (query, key, value; bqkv FP32 [3d]) -> q = fp16( ( . + b ) * scale ),
+ * k = fp16( . * scale ), v = fp16( . + b ) -> k, v stored at row pos of the sequence's caches, FP16 [sequences][heads][keyStride][64] -> causal attention over
+ * rows 0 .. pos -> outF16 FP16 [sequences][d]. pos = nPastDev ? nPastDev[ sequence ] : nPast, in [0, keyStride); keyStride <= 512, d <= 1280. The sequences per
+ * workgroup follow the option "self_nq", the projection unit the tuning bit TUNE_SELF_MFMA. */
+WH_API int wh_op_self_block_dec( void* stream, const float* x, const float* lnW, const float* lnB, const void* wqkv, const float* bqkv, float scale,
+	void* kCache, void* vCache, void* outF16, int sequences, int heads, int keyStride, int nPast, const int32_t* nPastDev );
+
 /* ---- op-level entry points of the beam step's kernels (the routes wh_decode and wh_beam_window_* take). Device pointers. ---- */
 
 /* The decoder's vocabulary softmax (same semantics as wh_op_soft_max), out of place: probs [rows][cols] = softmax( logits [rows][cols] ).

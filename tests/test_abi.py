@@ -82,6 +82,45 @@ def test_product_never_touches_the_oracle():
         assert head.rfind("def cpu_baseline") > head.rfind("def main") and head.rfind("def cpu_baseline") > head.rfind("def run_passes")
 
 
+def test_decode_step_entry_points_reject_bad_arguments_before_any_launch():
+    """wh_op_gemv_small / wh_op_cross_split / wh_op_self_block_dec: a null operand, or a shape their launchers do not take, is an error with a message and
+    nothing is launched -- checked on the host alone (the pointers below are never dereferenced: every call is turned away first)."""
+    import ctypes as C
+    L = binding.lib()
+    p = C.c_void_p(0x1000)
+    one = C.c_float(1.0)
+
+    def rejected(rc, word):
+        msg = L.wh_last_error().decode()
+        assert rc != 0 and word in msg, (rc, msg)
+
+    # gemvSmall: no weight; an unknown prologue / epilogue; an operand its combination needs; shapes of the launcher
+    rejected(L.wh_op_gemv_small(None, 1, 64, 64, 0, 0, None, p, None, None, None, None, None, None, p, None, None, None, None, 0, 0, 0, None, one), "gemv_small")
+    rejected(L.wh_op_gemv_small(None, 1, 64, 64, 0, 2, p, p, None, None, None, None, None, None, p, None, None, None, None, 0, 0, 0, None, one), "gemv_small")
+    rejected(L.wh_op_gemv_small(None, 1, 64, 64, 5, 0, p, p, None, None, None, None, None, None, p, None, None, None, None, 0, 0, 0, None, one), "gemv_small")
+    rejected(L.wh_op_gemv_small(None, 1, 64, 64, 0, 1, p, None, p, p, None, None, None, None, p, None, None, None, None, 0, 0, 0, None, one), "gemv_small")
+    rejected(L.wh_op_gemv_small(None, 1, 64, 64, 1, 0, p, p, None, None, None, None, None, None, None, p, None, None, None, 0, 0, 0, None, one), "GELU")
+    rejected(L.wh_op_gemv_small(None, 1, 192, 64, 2, 1, p, None, p, p, p, None, p, None, None, None, p, p, p, 1, 448, 448, None, one), "nPast")
+    rejected(L.wh_op_gemv_small(None, 5, 64, 64, 0, 0, p, p, None, None, None, None, None, None, p, None, None, None, None, 0, 0, 0, None, one), "gemvSmall")
+    rejected(L.wh_op_gemv_small(None, 1, 64, 12, 0, 0, p, p, None, None, None, None, None, None, p, None, None, None, None, 0, 0, 0, None, one), "gemvSmall")
+    rejected(L.wh_op_gemv_small(None, 1, 64, 8256, 0, 0, p, p, None, None, None, None, None, None, p, None, None, None, None, 0, 0, 0, None, one), "gemvSmall")
+    rejected(L.wh_op_gemv_small(None, 1, 64, 4096, 0, 1, p, None, p, p, p, None, None, None, p, None, None, None, None, 0, 0, 0, None, one), "gemvSmall")
+    rejected(L.wh_op_gemv_small(None, 1, 64, 72, 0, 3, p, None, None, None, None, p, None, None, p, None, None, None, None, 0, 0, 0, None, one), "gemvSmall")
+    # the split cross-attention: a null scratch buffer; five sequences; more keys than rows; too many keys; too wide
+    rejected(L.wh_op_cross_split(None, p, p, p, p, p, one, p, p, p, None, p, 1, 6, 1500, 1500), "cross_split")
+    rejected(L.wh_op_cross_split(None, p, p, p, p, p, one, p, p, p, p, p, 5, 6, 1500, 1500), "crossSplit")
+    rejected(L.wh_op_cross_split(None, p, p, p, p, p, one, p, p, p, p, p, 1, 6, 1500, 1499), "crossSplit")
+    rejected(L.wh_op_cross_split(None, p, p, p, p, p, one, p, p, p, p, p, 1, 6, 1537, 1600), "crossSplit")
+    rejected(L.wh_op_cross_split(None, p, p, p, p, p, one, p, p, p, p, p, 1, 21, 1500, 1500), "crossSplit")
+    # selfBlockDec: a null cache; a position outside the cache; a cache deeper than its LDS score rows; too wide
+    rejected(L.wh_op_self_block_dec(None, p, p, p, p, p, one, None, p, p, 1, 2, 448, 0, None), "self_block_dec")
+    rejected(L.wh_op_self_block_dec(None, p, p, p, p, p, one, p, p, p, 1, 2, 448, 448, None), "self_block_dec")
+    rejected(L.wh_op_self_block_dec(None, p, p, p, p, p, one, p, p, p, 1, 2, 448, -1, None), "self_block_dec")
+    rejected(L.wh_op_self_block_dec(None, p, p, p, p, p, one, p, p, p, 1, 2, 513, 0, None), "selfBlockDec")
+    rejected(L.wh_op_self_block_dec(None, p, p, p, p, p, one, p, p, p, 1, 21, 448, 0, None), "selfBlockDec")
+    rejected(L.wh_op_self_block_dec(None, p, p, p, p, p, one, p, p, p, 0, 2, 448, 0, None), "selfBlockDec")
+
+
 def test_tuning_bits_of_the_binding_match_the_library_header():
     """whisper_amd/binding.py mirrors csrc/kernels.h eTuning by hand; tests restore binding.TUNE_DEFAULT after an A/B, so a bit that is in one default
     and not in the other would silently change what the rest of a test session measures."""

@@ -196,6 +196,79 @@ def test_timed_path_against_the_exact_mode(kind, n_win, n_steps):
     assert np.array_equal(T.argmax(-1), E0.argmax(-1)) and np.array_equal(T.argmax(-1), E16.argmax(-1))
 
 
+_DEPTH_MODELS = {}
+
+
+@pytest.fixture(scope="module")
+def depth_model():
+    """Two-layer synthetic models at the widths of large and tiny, built once per width for the cases below."""
+    def get(d, heads):
+        if d not in _DEPTH_MODELS:
+            hp = gf.HParams(n_vocab=51865, n_audio_ctx=1500, n_audio_state=d, n_audio_head=heads, n_audio_layer=1,
+                            n_text_ctx=448, n_text_state=d, n_text_head=heads, n_text_layer=2, n_mels=80, f16=1)
+            _DEPTH_MODELS[d] = binding.HipModel.from_ggml(gf.synth_model(hp=hp, seed=21, attn_sharpness=2.0))
+        return _DEPTH_MODELS[d]
+    yield get
+    for m in _DEPTH_MODELS.values():
+        m.close()
+    _DEPTH_MODELS.clear()
+
+
+@pytest.mark.parametrize("d,heads,n_seq", [(1280, 20, 1), (1280, 20, 4), (1280, 20, 12), (1280, 20, 40), (384, 6, 1), (384, 6, 4), (384, 6, 12), (384, 6, 40)])
+def test_single_token_steps_at_depth_against_the_exact_mode(depth_model, d, heads, n_seq):
+    """The single-token kernels as wh_decode wires them, deep in the context: 1 and 4 sequences take decode1.hip (gemvSmall, the split cross-attention), 12 take
+    selfBlockDec, 40 the separate self-attention launch. Every sequence has its own audio and its own prompt of P = 61, 125 and 443 tokens fed at n_past 0, then
+    four single-token steps: they cross positions 64 and 128 (the ends of the score loops' 64-row passes) and end with 447 cached keys.
+    Three runs of one context, teacher-forced with the timed run's tokens, as in test_timed_path_against_the_exact_mode: T the timed path, E0 the exact mode with
+    P.V rounded once per output, E0alt the same with the smallest re-ordering of the reference's own FP32 sums. On the single-token steps max and mean |T - E0| stay
+    within 1.5 x |E0alt - E0| measured in the same run, and the top token agrees wherever E0's margin over its runner-up exceeds twice that measured maximum."""
+    import bench
+    m = depth_model(d, heads)
+    sp = gf.special_tokens(m.hp)
+    ctx = binding.HipContext(m, n_seq)
+    pcm_dev = torch.from_numpy(bench.synth_pcm(n_seq, seed=100 + n_seq)).cuda()
+    mels = torch.stack([ctx.mel_spectrogram(pcm_dev[b]) for b in range(n_seq)])
+    rng = np.random.default_rng(d + n_seq)
+    lengths = (61, 125, 443)
+    prompts = {P: rng.integers(0, sp["eot"], (n_seq, P)).astype(np.int32) for P in lengths}
+    X = binding.WH_FLAG_PARITY_EXACT
+
+    def run(flags, fed=None):
+        ctx.set_flags(*flags)
+        ctx.encode(mels)
+        logits, tokens = {}, {}
+        for P in lengths:
+            toks, n_past = prompts[P], 0
+            logits[P], tokens[P] = [], []
+            for st in range(5):
+                gl, _ = ctx.decode(toks, n_past)
+                n_past += toks.shape[1]
+                toks = fed[P][st] if fed is not None else np.argmax(gl, axis=1).astype(np.int32).reshape(-1, 1)
+                tokens[P].append(toks)
+                if st > 0:
+                    logits[P].append(gl.copy())          # the four single-token steps
+        ctx.set_flags(0, 1)
+        return {P: np.stack(v) for P, v in logits.items()}, tokens
+
+    T, fed = run((0, 1))
+    E0, _ = run((X, 0), fed)
+    binding.set_option("exact_alt_order", 1)
+    try:
+        E0alt, _ = run((X, 0), fed)
+    finally:
+        binding.set_option("exact_alt_order", 0)
+    ctx.close()
+    for P in lengths:
+        floor, dist = np.abs(E0alt[P] - E0[P]), np.abs(T[P] - E0[P])
+        print("d=%d, %d sequence(s), prompt %d: timed vs E0 max %.2e mean %.2e; re-ordered reference vs E0 max %.2e mean %.2e (bound 1.5 x)"
+              % (d, n_seq, P, dist.max(), dist.mean(), floor.max(), floor.mean()))
+        assert np.isfinite(T[P]).all()
+        assert dist.max() <= 1.5 * floor.max() and dist.mean() <= 1.5 * floor.mean()
+        top2 = np.sort(E0[P], axis=-1)[..., -2:]
+        clear = (top2[..., 1] - top2[..., 0]) > 2.0 * floor.max()
+        assert np.array_equal(T[P].argmax(-1)[clear], E0[P].argmax(-1)[clear])
+
+
 def test_audio_ctx_override(ref_lib_available, tmp_path):
     """sFullParams::audio_ctx (Whisper/Whisper/ContextImpl.cpp:24, 55, 488-489 == whisper.cpp's exp_n_audio_ctx): the encoder runs on the first audio_ctx
     positions of a window, the decoder's cross-attention sees that many keys. wh_context_set_audio_ctx against the reference with the same override:

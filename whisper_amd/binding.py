@@ -57,6 +57,7 @@ EXPORTS = [
     "wh_op_vocab_soft_max_scaled", "wh_op_sample_draw", "wh_op_philox_u", "wh_context_set_sampling", "wh_context_set_no_speech", "wh_decode_window_no_speech",
     "wh_context_set_sampling_rows", "wh_op_sample_rows",
     "wh_context_set_suppress", "wh_op_suppress_logits",
+    "wh_op_gemv_small", "wh_op_cross_split", "wh_op_self_block_dec",
 ]
 
 
@@ -200,6 +201,9 @@ def lib():
         L.wh_decode_window_no_speech.argtypes = [vp, vp]
         L.wh_context_set_suppress.argtypes = [vp, vp, i32]
         L.wh_op_suppress_logits.argtypes = [vp, vp, i32, i32, vp, i32]
+        L.wh_op_gemv_small.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, C.c_float]
+        L.wh_op_cross_split.argtypes = [vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, i32, i32, i32, i32]
+        L.wh_op_self_block_dec.argtypes = [vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, i32, i32, i32, i32, vp]
         _lib = L
     return _lib
 

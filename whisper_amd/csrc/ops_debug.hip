@@ -334,6 +334,86 @@ int wh_op_soft_max( void* stream, float* x, int rows, int cols )
 	return launchSoftMaxRows( x, rows, cols, (hipStream_t)stream );
 }
 
+// ---- the kernels of a single-token step: the products and the split cross-attention of one stream (decode1.hip), the fused self-attention half of a
+// lock-step batch (attn_dec.hip). Thin: the launchers check the shapes; what they cannot see (null pointers, a position outside the cache) is checked here.
+int wh_op_gemv_small( void* stream, int M, int N, int K, int epi, int pro, const void* wF16, const void* aF16, const float* lnX, const float* lnW, const float* lnB,
+	const float* part, const float* bias, const float* residual, float* out32, void* out16, void* qF16, void* kCache, void* vCache, int heads, int textCtx,
+	int nPast, const int32_t* nPastDev, float scale )
+{
+	if( !wF16 || ( pro != 0 && pro != 1 && pro != 3 ) || ( pro == 0 && !aF16 ) || ( pro == 1 && ( !lnX || !lnW || !lnB ) ) || ( pro == 3 && !part ) )
+	{
+		setError( "gemv_small: null operand, or a prologue other than 0 (FP16 rows), 1 (LayerNorm) or 3 (cross-attention partials)" );
+		return WH_E_INVALIDARG;
+	}
+	SmallGemvArgs a = {};
+	a.g = plainGemm( (const f16*)aF16, (const f16*)wF16, M, N, K );
+	a.pro = pro; a.part = part;
+	a.g.lnX = lnX; a.g.lnW = lnW; a.g.lnB = lnB;
+	a.g.bias = bias;
+	if( epi == 0 )
+	{
+		if( !out32 ) { setError( "gemv_small: the FP32 epilogue needs out32" ); return WH_E_INVALIDARG; }
+		a.g.epi = EPI_F32; a.g.res = residual; a.g.out32 = out32;
+	}
+	else if( epi == 1 )
+	{
+		if( !out16 || !bias ) { setError( "gemv_small: the GELU epilogue needs out16 and a bias" ); return WH_E_INVALIDARG; }
+		a.g.epi = EPI_F16_GELU; a.g.out16 = (f16*)out16;
+	}
+	else if( epi == 2 )
+	{
+		// every position written must lie inside the cache: a scalar is checked here, a device array is the caller's to keep in [0, textCtx)
+		if( !qF16 || !kCache || !vCache || !bias || heads < 1 || N != 3 * heads * HEAD_DIM || K != heads * HEAD_DIM || textCtx < 1 ||
+			( !nPastDev && ( nPast < 0 || nPast >= textCtx ) ) )
+		{
+			setError( "gemv_small: the QKV epilogue needs q, both caches and a bias, N = 3 K = 3 * 64 * heads and 0 <= nPast < textCtx" );
+			return WH_E_INVALIDARG;
+		}
+		a.g.epi = EPI_QKV_DEC; a.g.scale = scale;
+		a.g.q = (f16*)qF16; a.g.k = (f16*)kCache; a.g.v = (f16*)vCache;
+		a.g.H = heads; a.g.nTok = 1; a.g.nPast = nPast; a.g.nPastDev = nPastDev; a.g.textCtx = textCtx;
+	}
+	else
+	{
+		setError( "gemv_small: epilogue 0 (FP32, bias, residual), 1 (FP16 GELU) or 2 (decoder Q/K/V)" );
+		return WH_E_INVALIDARG;
+	}
+	return launchGemvSmall( a, (hipStream_t)stream );
+}
+
+int wh_op_cross_split( void* stream, const float* x, const float* lnW, const float* lnB, const void* qW, const float* qB, float qScale, const void* kCache,
+	const void* vCache, float* scores, float* splitMax, float* part, int sequences, int heads, int nKeys, int keyStride )
+{
+	if( !x || !lnW || !lnB || !qW || !qB || !kCache || !vCache || !scores || !splitMax || !part || heads < 1 )
+	{
+		setError( "cross_split: null argument" );
+		return WH_E_INVALIDARG;
+	}
+	CrossSplitArgs a = {};
+	a.lnX = x; a.lnW = lnW; a.lnB = lnB; a.qW = (const f16*)qW; a.qB = qB; a.qScale = qScale;
+	a.kc = (const f16*)kCache; a.vc = (const f16*)vCache;
+	a.scores = scores; a.splitMax = splitMax; a.part = part;
+	a.batch = sequences; a.H = heads; a.nKeys = nKeys; a.keyStride = keyStride;
+	WH_CHECK( launchCrossScores( a, (hipStream_t)stream ) );
+	return launchCrossSoftmaxPV( a, (hipStream_t)stream );
+}
+
+int wh_op_self_block_dec( void* stream, const float* x, const float* lnW, const float* lnB, const void* wqkv, const float* bqkv, float scale, void* kCache,
+	void* vCache, void* outF16, int sequences, int heads, int keyStride, int nPast, const int32_t* nPastDev )
+{
+	// a scalar position is checked here; positions in device memory are the caller's to keep in [0, keyStride)
+	if( !x || !lnW || !lnB || !wqkv || !bqkv || !kCache || !vCache || !outF16 || heads < 1 || ( !nPastDev && ( nPast < 0 || nPast >= keyStride ) ) )
+	{
+		setError( "self_block_dec: null argument, or nPast outside [0, keyStride)" );
+		return WH_E_INVALIDARG;
+	}
+	DecSelfArgs a = {};
+	a.x = x; a.lnW = lnW; a.lnB = lnB; a.wqkv = (const f16*)wqkv; a.bqkv = bqkv; a.scale = scale;
+	a.kc = (f16*)kCache; a.vc = (f16*)vCache; a.out = (f16*)outF16;
+	a.batch = sequences; a.H = heads; a.keyStride = keyStride; a.nPast = nPast; a.nPastDev = nPastDev;
+	return launchSelfBlockDec( a, (hipStream_t)stream );
+}
+
 int wh_op_vocab_soft_max( void* stream, const float* logits, float* probs, int rows, int cols )
 {
 	if( !logits || !probs || rows < 1 || cols < 1 ) { setError( "vocab_soft_max: null pointer or empty shape" ); return WH_E_INVALIDARG; }
