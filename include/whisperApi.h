@@ -415,6 +415,16 @@ namespace Whisper
 	// One set for all streams of every later run of the runner. E_INVALIDARG as above; E_NOTIMPL for a non-empty set where the scheduler was built without the
 	// device's logit filter.
 	WHISPER_EXPORT HRESULT setBatchSuppressedTokens( iBatchRunner* runner, const int32_t* ids, uint32_t count );
+	// Extension: timestamp rules, the three clauses of openai-whisper's ApplyTimestampRules (whisper.cpp: whisper_process_logits) the sampler does not hold, applied
+	// to the logits on the device in every step of the decoding loop: after `text, <|t|>` a timestamp or eot follows, after `<|t|>, <|t|>` no timestamp; no timestamp
+	// lies below the last one of its window; a segment has non-zero length. With them on, the host loop no longer meets a timestamp that goes back in time, which it
+	// answers by cutting the window there. They hold for greedy runs and for the sampled attempts of the decoding fallback. Off unless set: such a run is what it
+	// always was. Free functions: the vtables are the reference's. With the rules on, a run with eSamplingStrategy::BeamSearch answers E_NOTIMPL (the per-sequence
+	// history would have to follow the beam's reorder); language detection and eFullParamsFlags::AlignTokens read unfiltered passes as before.
+	// E_INVALIDARG for a context of another library.
+	WHISPER_EXPORT HRESULT setTimestampRules( iContext* context, bool on );
+	// One switch for all streams of every later run of the runner. E_NOTIMPL to turn it on where the scheduler was built without the device's filter.
+	WHISPER_EXPORT HRESULT setBatchTimestampRules( iBatchRunner* runner, bool on );
 	// Extension (no counterpart in whisper.def): ONE long recording onto the batched path. The buffer is cut into pieces of at most maxLen samples at pauses,
 	// found with the reference's voice-activity detector (Whisper/Whisper/voiceActivityDetection.cpp, which its capture loop uses to fire a transcription when
 	// the speaker pauses): the per-frame features come from the device (wh_vad_features of whisper_hip.h, on the calling thread's current device), the decision

@@ -88,6 +88,10 @@ int32_t whisperc_tr_window_stats( void* result, void* out, uint32_t cap, uint32_
 int32_t whisperc_non_speech_tokens( void* model, int32_t* out, uint32_t cap, uint32_t* count );
 int32_t whisperc_set_suppress_tokens( void* ctx, const int32_t* ids, uint32_t count );
 int32_t whisperc_batch_set_suppress_tokens( void* runner, const int32_t* ids, uint32_t count );
+/* Timestamp rules (Whisper::setTimestampRules / setBatchTimestampRules of whisperApi.h): on != 0 = every later run masks the logits so that timestamps come in
+ * pairs, never go back in time and close segments of non-zero length. Off is the state of every new context and runner. */
+int32_t whisperc_set_timestamp_rules( void* ctx, int32_t on );
+int32_t whisperc_batch_set_timestamp_rules( void* runner, int32_t on );
 /* iContext::getResults( Tokens | Timestamps ) + iTranscribeResult::getSize / getSegments / getTokens; times in 100 ns ticks */
 int32_t whisperc_result_counts( void* ctx, uint32_t* segments, uint32_t* tokens );
 int32_t whisperc_result_segment( void* ctx, uint32_t index, uint64_t* t0, uint64_t* t1, uint32_t* firstToken, uint32_t* countTokens,

@@ -470,6 +470,23 @@ WH_API int wh_context_set_sampling_rows( wh_context* c, int rows, const float* t
  * WH_E_INVALIDARG for an id outside the range and for a non-empty set under WH_FLAG_PARITY_EXACT (wh_context_set_flags in turn refuses that flag while a set is
  * held). Hypothesis-group contexts take the call like greedy ones. A context that never calls it launches, allocates and captures what it always did. */
 WH_API int wh_context_set_suppress( wh_context* c, const int32_t* ids, int count );
+/* Timestamp rules: the three clauses of openai-whisper's ApplyTimestampRules that the sampler does not hold, as -inf over ranges of the logits, for every row of
+ * every later step of the device-side loop. A token is a timestamp when its id is >= beg (<|0.00|>). (1) Pairs: after `text, <|t|>` the next token is a timestamp
+ * or eot ([0, eot) is masked; eot and the special ids stay, so a row always keeps mass); after `<|t|>, <|t|>` it is no timestamp ([beg, nVocab) is masked; "the
+ * one before" also counts as a timestamp while fewer than two tokens have been sampled). (2) No timestamp below the last one sampled in this window and (3) none
+ * equal to it either, unless it closes a pair: [beg, last) is masked in the text-then-timestamp case, [beg, last + 1) otherwise. The sampler's own two clauses (the
+ * timestamp mass against the best text token, the first timestamp's cap) are unchanged and see the filtered row.
+ * The mask depends on what the row has sampled, so the context keeps one record of four int32 per sequence in device memory (last token a timestamp, the one
+ * before it, the last timestamp id, tokens sampled). ONE small launch behind the vocabulary product folds the token just fed -- the previous step's sample -- into
+ * the record and masks the row; the prompt step of a window resets the records and masks nothing, so the window's first sample is what it always was and no
+ * record survives into the next window. It applies to wh_decode_greedy (the history starts at the call's first sample: firstTokens are not counted),
+ * wh_decode_window_start, _start_ragged and _continue, whatever the sampler: greedy, wh_context_set_sampling, wh_context_set_sampling_rows. Unfiltered: wh_decode
+ * (the host feeds the tokens, there is no device history), wh_lang_detect, wh_align_tokens and the beam step.
+ * The records, maxSeq of them, are allocated by the first call that turns the mode on and never again; the captured step graphs are keyed on the mode. The call
+ * waits for the stream: what was queued runs under the mode it was queued in. WH_E_INVALIDARG to turn it on on a hypothesis-group context (the records would have
+ * to follow the beam's reorder) or under WH_FLAG_PARITY_EXACT (wh_context_set_flags in turn refuses that flag while the mode is on). A context that never turns
+ * it on launches, allocates and captures what it always did. */
+WH_API int wh_context_set_timestamp_rules( wh_context* c, int on );
 WH_API int wh_context_set_no_speech( wh_context* c, int on );
 WH_API int wh_decode_window_no_speech( wh_context* c, float* out );
 
@@ -584,6 +601,12 @@ WH_API int wh_op_vocab_soft_max( void* stream, const float* logits, float* probs
 /* The kernel of wh_context_set_suppress outside a context: logits[ row ][ ids[ i ] ] = -inf for every row and i < count, in place; every other float keeps its
  * bits. ids: DEVICE int32 [count]; an id outside [0, nVocab) is skipped. count == 0 launches nothing (ids may be NULL). Plain stores: no atomics, no LDS. */
 WH_API int wh_op_suppress_logits( void* stream, float* logits, int rows, int nVocab, const int32_t* ids, int count );
+/* One step of the kernel of wh_context_set_timestamp_rules outside a context, on logits [rows][nVocab] in place. recordsDev: DEVICE int32 [rows][4] = { last token
+ * was a timestamp, the one before it was, the last timestamp id (0 = none), tokens sampled (negative = armed) }. reset 0: fedTokensDev [rows] (DEVICE; the token
+ * each row sampled last) is folded into the row's record -- an armed record folds nothing and becomes the empty history -- and the ranges the rules give become
+ * -inf; every other float keeps its bits. reset 1: every record becomes the empty history; 2: armed; neither touches the logits, fedTokensDev may be NULL.
+ * 0 <= tokenEot < tokenBeg < nVocab and tokenBeg >= 1, or WH_E_INVALIDARG. Plain stores: no atomics, no LDS. */
+WH_API int wh_op_timestamp_rules( void* stream, float* logits, int rows, int nVocab, int tokenEot, int tokenBeg, const int32_t* fedTokensDev, int reset, int32_t* recordsDev );
 /* The language-detection kernel of wh_lang_detect on logits [rows][nVocab]: langP [rows][nLang] = the probabilities wh_op_vocab_soft_max gives at columns
  * tokenSot + 1 .. tokenSot + nLang, bit for bit, without writing the other columns; best [rows] = the index (0 .. nLang - 1) of the largest, exact ties
  * to the lower index. The row stays in registers: nVocab <= 52224; 1 <= nLang <= 1024 and the block inside the row, or WH_E_INVALIDARG. */

@@ -82,6 +82,8 @@ def lib():
         L.whisperc_non_speech_tokens.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
         L.whisperc_set_suppress_tokens.argtypes = [vp, vp, C.c_uint32]
         L.whisperc_batch_set_suppress_tokens.argtypes = [vp, vp, C.c_uint32]
+        L.whisperc_set_timestamp_rules.argtypes = [vp, C.c_int32]
+        L.whisperc_batch_set_timestamp_rules.argtypes = [vp, C.c_int32]
         L.whisperc_resample.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64)]
         L.whisperc_load_audio.argtypes = [C.c_char_p, C.c_int32, vp, C.c_int64, C.POINTER(C.c_int64)]
         L.whisperc_run_full_stereo.argtypes = [vp, vp, vp, C.c_uint32, C.c_char_p, C.c_uint32, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int]
@@ -424,6 +426,12 @@ class Context:
         a = _suppress_ids(self.model, ids)
         _check(lib().whisperc_set_suppress_tokens(self.h, a.ctypes.data_as(C.c_void_p) if len(a) else None, len(a)), "setSuppressedTokens")
 
+    def set_timestamp_rules(self, on: bool = True):
+        """Whisper::setTimestampRules: every later run masks the logits on the device so that timestamps come in pairs, never go back in time within a window
+        and close segments of non-zero length (openai-whisper's ApplyTimestampRules) -- greedy runs and the fallback's sampled attempts alike. Off, the state
+        of a new context, the transcript is what it always was. With the rules on, beam search raises (E_NOTIMPL)."""
+        _check(lib().whisperc_set_timestamp_rules(self.h, 1 if on else 0), "setTimestampRules")
+
     def window_stats(self):
         """What the fallback did with each window of the last run: [{seek, attempts, temperature, no_speech, avg_logprob, entropy, skipped}], empty when
         the feature was off."""
@@ -538,6 +546,10 @@ class BatchRunner:
         """Whisper::setBatchSuppressedTokens: Context.set_suppress_tokens for every stream of this runner's later runs (one set for all of them)."""
         a = _suppress_ids(self.model, ids)
         _check(lib().whisperc_batch_set_suppress_tokens(self.h, a.ctypes.data_as(C.c_void_p) if len(a) else None, len(a)), "setBatchSuppressedTokens")
+
+    def set_timestamp_rules(self, on: bool = True):
+        """Whisper::setBatchTimestampRules: Context.set_timestamp_rules for every stream of this runner's later runs (one switch for all of them)."""
+        _check(lib().whisperc_batch_set_timestamp_rules(self.h, 1 if on else 0), "setBatchTimestampRules")
 
     def run(self, streams, language: str = "en", flags: int = 0, max_tokens: int = 0, prompt: Optional[Sequence[int]] = None,
             n_max_text_ctx: int = -1, want_results: bool = True, sample_rate: int = 16000, stereo: Optional[Sequence] = None):

@@ -57,6 +57,7 @@ EXPORTS = [
     "wh_op_vocab_soft_max_scaled", "wh_op_sample_draw", "wh_op_philox_u", "wh_context_set_sampling", "wh_context_set_no_speech", "wh_decode_window_no_speech",
     "wh_context_set_sampling_rows", "wh_op_sample_rows",
     "wh_context_set_suppress", "wh_op_suppress_logits",
+    "wh_context_set_timestamp_rules", "wh_op_timestamp_rules",
     "wh_op_gemv_small", "wh_op_cross_split", "wh_op_self_block_dec",
 ]
 
@@ -201,6 +202,8 @@ def lib():
         L.wh_decode_window_no_speech.argtypes = [vp, vp]
         L.wh_context_set_suppress.argtypes = [vp, vp, i32]
         L.wh_op_suppress_logits.argtypes = [vp, vp, i32, i32, vp, i32]
+        L.wh_context_set_timestamp_rules.argtypes = [vp, i32]
+        L.wh_op_timestamp_rules.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp]
         L.wh_op_gemv_small.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, C.c_float]
         L.wh_op_cross_split.argtypes = [vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, i32, i32, i32, i32]
         L.wh_op_self_block_dec.argtypes = [vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, i32, i32, i32, i32, vp]
@@ -368,6 +371,10 @@ class HipContext:
         """The logits of these token ids (each < eot) are -inf before the softmax in every later decoder pass of the context; None or an empty list turns it off."""
         a = np.ascontiguousarray(ids if ids is not None else [], np.int32).reshape(-1)
         check(lib().wh_context_set_suppress(self.handle, a.ctypes.data_as(C.c_void_p) if len(a) else None, len(a)))
+
+    def set_timestamp_rules(self, on: bool):
+        """on: every later step of the device-side loop masks the logits by openai-whisper's timestamp rules (pairs, non-decreasing, non-zero segments)."""
+        check(lib().wh_context_set_timestamp_rules(self.handle, 1 if on else 0))
 
     def set_no_speech(self, on: bool):
         """on: every window start also gathers P( <|nospeech|> ) of the prompt step (window_no_speech)."""

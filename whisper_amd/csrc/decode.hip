@@ -31,6 +31,18 @@ static int suppressLogits( wh_context* c, int batch )
 		[ & ]() { return launchSuppressLogits( c->logits, batch, nVocab, c->suppress + 1, c->suppress, 0, cap, c->stream ); } );
 }
 
+// Timestamp rules (wh_context_set_timestamp_rules): the filter whose mask depends on what each row has sampled. Only the device-side loop calls it, right behind
+// decodeGraph -- so behind the suppress launch -- and in front of the sampler: reset 1 behind a window's prompt step (the records become empty, nothing is masked),
+// 0 in every step (the fed token c->tokensDev[ row ], the previous step's sample, is folded in and the row masked). The replayed step reads device memory only.
+static int timestampRules( wh_context* c, int batch, int reset )
+{
+	if( !c->tsRules ) return 0;
+	const wh_hparams& hp = c->m->hp;
+	const SpecialIds sp = specialIds( hp );
+	return profiled( c, KC_SAMPLE, 0.0, 4.0 * batch * hp.n_vocab,
+		[ & ]() { return launchTimestampRules( c->logits, batch, hp.n_vocab, sp.sot - 1, sp.beg, c->tokensDev, reset, c->tsRecords, c->stream ); } );
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // decoder
 // ------------------------------------------------------------------------------------------------------------------
@@ -469,10 +481,12 @@ extern "C" {
 // What a captured step graph depends on besides the batch: the parity mode and the sampler (greedy or temperature: other kernels, the same graph for every temperature)
 constexpr uint32_t STEP_KEY_ROWS = 0x40000u;	  // per-row sampling (wh_context_set_sampling_rows)
 constexpr uint32_t STEP_KEY_SUPPRESS = 0x80000u;   // a suppressed set is held (wh_context_set_suppress): the graph has one more node, the same for every set
+constexpr uint32_t STEP_KEY_TS_RULES = 0x100000u;  // the timestamp rules are on (wh_context_set_timestamp_rules): one more node, the same for every window
 static uint32_t stepGraphKey( const wh_context* c )
 {
 	return ( ( c->flags & WH_FLAG_PARITY_PV ) ? ( 0x10000u | (uint32_t)c->parityThreads ) : 0u ) | ( c->temperature > 0.0f ? 0x20000u : 0u ) |
-		( c->sampleRowsOn ? STEP_KEY_ROWS : 0u ) | ( c->suppressCount > 0 ? STEP_KEY_SUPPRESS : 0u );
+		( c->sampleRowsOn ? STEP_KEY_ROWS : 0u ) | ( c->suppressCount > 0 ? STEP_KEY_SUPPRESS : 0u ) |
+		( c->tsRules ? STEP_KEY_TS_RULES : 0u );
 }
 // Captured steps that cannot serve ( batch, key ) or its sibling in the other per-row mode go (see wh_context::stepGraphs); true when one went
 static bool dropStaleStepGraphs( wh_context* c, int batch, uint32_t key )
@@ -549,6 +563,7 @@ static int greedyStep( wh_context* c, int batch )
 	const SpecialIds sp = specialIds( hp );
 	const int sot = sp.sot, solm = sp.solm, tnot = sp.tnot, beg = sp.beg;
 	WH_CHECK( decodeGraph( c, batch, 1, 0, true ) );
+	WH_CHECK( timestampRules( c, batch, 0 ) );
 	WH_CHECK( sampleStep( c, batch, c->stream ) );
 	return launchAdvanceState( c->state, c->seqPos, batch, c->stream );
 }
@@ -585,10 +600,13 @@ int wh_decode_greedy( wh_context* c, int batch, const int32_t* firstTokens, int 
 			WH_HIP( hipStreamSynchronize( st ) );
 			WH_CHECK( captureStepGraph( c, batch, key, exec ) );
 		}
+		// the first token is the caller's, not a sample: the records are armed, the history starts at this call's first sample
+		WH_CHECK( timestampRules( c, batch, 2 ) );
 		for( int s = 0; s < nSteps; s++ ) WH_HIP( hipGraphLaunch( exec, st ) );
 	}
 	else
 	{
+		WH_CHECK( timestampRules( c, batch, 2 ) );
 		for( int s = 0; s < nSteps; s++ )
 		{
 			c->profKeysHint = nPast + s + 1;
@@ -689,6 +707,7 @@ static int windowStart( wh_context* c, int batch, const int32_t* promptTokens, c
 	{
 		const SpecialIds sp = specialIds( hp );
 		const int sot = sp.sot, solm = sp.solm, tnot = sp.tnot, beg = sp.beg;
+		WH_CHECK( timestampRules( c, batch, 1 ) );	 // a new window: no record survives into it, and the first sample is unfiltered
 		WH_CHECK( sampleStep( c, batch, st ) );
 		WH_CHECK( launchAdvanceState( c->state, c->seqPos, batch, st ) );
 		c->noSpeechRows = 0;
@@ -751,6 +770,8 @@ int wh_decode_window_continue( wh_context* c, int nSteps )
 		WH_HIP( hipMemcpy( &saved, c->state, sizeof( saved ), hipMemcpyDeviceToHost ) );
 		WH_HIP( hipMemcpy( savedPos.data(), c->seqPos, sizeof( int32_t ) * batch, hipMemcpyDeviceToHost ) );
 		WH_HIP( hipMemcpy( tok.data(), c->tokensDev, sizeof( int32_t ) * batch, hipMemcpyDeviceToHost ) );
+		std::vector<TimestampRecord> savedRec( c->tsRules ? (size_t)batch : 0 );
+		if( c->tsRules ) WH_HIP( hipMemcpy( savedRec.data(), c->tsRecords, sizeof( TimestampRecord ) * batch, hipMemcpyDeviceToHost ) );
 		dropStaleStepGraphs( c, batch, key );
 		WH_CHECK( greedyStep( c, batch ) );
 		WH_HIP( hipStreamSynchronize( c->stream ) );
@@ -758,6 +779,7 @@ int wh_decode_window_continue( wh_context* c, int nSteps )
 		WH_HIP( hipMemcpy( c->state, &saved, sizeof( saved ), hipMemcpyHostToDevice ) );
 		WH_HIP( hipMemcpy( c->seqPos, savedPos.data(), sizeof( int32_t ) * batch, hipMemcpyHostToDevice ) );
 		WH_HIP( hipMemcpy( c->tokensDev, tok.data(), sizeof( int32_t ) * batch, hipMemcpyHostToDevice ) );
+		if( c->tsRules ) WH_HIP( hipMemcpy( c->tsRecords, savedRec.data(), sizeof( TimestampRecord ) * batch, hipMemcpyHostToDevice ) );
 	}
 	if( useGraph )
 		for( int s = 0; s < nSteps; s++ ) WH_HIP( hipGraphLaunch( exec, c->stream ) );
@@ -942,6 +964,26 @@ int wh_context_set_suppress( wh_context* c, const int32_t* ids, int count )
 		c->beamGraphBatch = 0;
 	}
 	c->suppressCount = up[ 0 ];
+	return 0;
+}
+
+// Timestamp rules. The records are allocated once, before any capture; the captured graphs are keyed on the mode. The call waits for the
+// stream, so a chunk queued earlier has run under the mode it was enqueued in before the flag changes.
+int wh_context_set_timestamp_rules( wh_context* c, int on )
+{
+	if( !c ) { setError( "context_set_timestamp_rules: null context" ); return WH_E_INVALIDARG; }
+	if( !on )
+	{
+		if( c->tsRules ) { WH_BIND( c->m ); WH_HIP( hipStreamSynchronize( c->stream ) ); }
+		c->tsRules = false;
+		return 0;
+	}
+	if( c->hyp != 1 ) { setError( "context_set_timestamp_rules: not available on a hypothesis-group context (the records do not follow the beam's reorder)" ); return WH_E_INVALIDARG; }
+	if( c->flags & WH_FLAG_PARITY_EXACT ) { setError( "context_set_timestamp_rules: not available under WH_FLAG_PARITY_EXACT" ); return WH_E_INVALIDARG; }
+	WH_BIND( c->m );
+	if( !c->tsRecords ) WH_CHECK( c->alloc( c->tsRecords, (int64_t)c->maxSeq, wh_context::MUST_BE_ZERO, "tsRecords" ) );
+	WH_HIP( hipStreamSynchronize( c->stream ) );
+	c->tsRules = true;
 	return 0;
 }
 

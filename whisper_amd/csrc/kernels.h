@@ -465,6 +465,14 @@ namespace wh
 	// Suppressed tokens: logits [rows][nVocab] get -inf at columns ids[ 0 .. count ) (device, ascending), count = *countDev when countDev is non-null, at most cap;
 	// the grid depends on the rows alone
 	int launchSuppressLogits( float* logits, int rows, int nVocab, const int* ids, const int* countDev, int count, int cap, hipStream_t stream );
+	// Timestamp rules (wh_context_set_timestamp_rules): what one row of the device-side loop has sampled in this window, as far as the rules need it. lastTs / prevTs:
+	// was the last sampled token, and the one before it, a timestamp (id >= beg); lastId: the last timestamp's id, 0 = none yet; count: the tokens sampled so far,
+	// negative = armed (the next fed token is no sample and is not folded). All zero is the empty history.
+	struct TimestampRecord { int lastTs, prevTs, lastId, count; };
+	constexpr int TSR_THREADS = 1024;
+	// One step of the filter on logits [rows][nVocab], in place: reset 0 folds fed[ row ] (device) into records[ row ] and writes -inf over the ranges the rules give,
+	// 1 makes every record the empty history and 2 arms it, both without touching the logits. The grid depends on the rows alone.
+	int launchTimestampRules( float* logits, int rows, int nVocab, int tokenEot, int tokenBeg, const int* fed, int reset, TimestampRecord* records, hipStream_t stream );
 	int launchNoSpeechGather( const float* probs, const void* spreadScratch, int rows, int nVocab, int tokenSolm, float* out, hipStream_t stream );
 	// Prompt steps whose sequences differ in length (rows right-padded to nTok tokens): the normalised row of sequence b's LAST real
 	// token, lastPos[b] (device), is copied over its row nTok - 1, where the vocabulary product of a prompt step reads. In place, f16 rows.

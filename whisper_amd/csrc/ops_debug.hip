@@ -427,6 +427,18 @@ int wh_op_suppress_logits( void* stream, float* logits, int rows, int nVocab, co
 	return launchSuppressLogits( logits, rows, nVocab, ids, nullptr, count, count, (hipStream_t)stream );
 }
 
+int wh_op_timestamp_rules( void* stream, float* logits, int rows, int nVocab, int tokenEot, int tokenBeg, const int32_t* fedTokensDev, int reset, int32_t* recordsDev )
+{
+	static_assert( sizeof( TimestampRecord ) == 4 * sizeof( int32_t ), "wh_op_timestamp_rules documents the record as four int32" );
+	if( !logits || !recordsDev || ( !reset && !fedTokensDev ) || rows < 1 || nVocab < 2 || tokenBeg < 1 || tokenBeg >= nVocab || tokenEot < 0 || tokenEot >= tokenBeg ||
+		reset < 0 || reset > 2 )
+	{
+		setError( "timestamp_rules: null pointer, empty shape, ids that are not 0 <= eot < beg < nVocab, or a reset outside 0 .. 2" );
+		return WH_E_INVALIDARG;
+	}
+	return launchTimestampRules( logits, rows, nVocab, tokenEot, tokenBeg, fedTokensDev, reset, (TimestampRecord*)recordsDev, (hipStream_t)stream );
+}
+
 int wh_op_lang_probs( void* stream, const float* logits, int rows, int nVocab, int tokenSot, int nLang, float* langP, int32_t* best )
 {
 	if( !logits || !langP || !best || rows < 1 || nVocab < 1 || nVocab > 52224 || nLang < 1 || nLang > 1024 || tokenSot < 0 || (int64_t)tokenSot + 1 + nLang > nVocab )
@@ -862,10 +874,15 @@ int wh_debug_probe( wh_context* c, int kind, int variant, int M, int N, int K, i
 		// greedy (launchVocabSoftMaxRows + launchSampleRows) -- what a round with one retrying row costs its greedy neighbours. The logits rotate through
 		// buffers that together exceed the last-level cache (512 MB; at most 64 buffers); 5 warm-up launches, then the MEDIAN of `iters` launches, each between its
 		// own events. Variant 2 = the logit filter of wh_context_set_suppress with K ids in front of the fused greedy sampler, 3 = the filter alone (tools/suppress_probe.py).
+		// Variant 4 = the filter of wh_context_set_timestamp_rules in front of the fused greedy sampler, 5 = that filter alone (tools/timestamp_rules_probe.py); K is
+		// the history the timed launch meets: 0 = text only, nothing masked; 1 = a closed pair, the timestamps masked (1501 columns); 2 = text then a timestamp, the
+		// text tokens and the earlier timestamps masked (the widest mask; an untimed launch that feeds a text token goes in front of every timed one).
 		const int rows = M, nVocab = N;
-		if( rows < 1 || rows > 4096 || nVocab < 2048 || nVocab > 52224 || variant < 0 || variant > 3 ) return WH_E_INVALIDARG;
-		const int nIds = variant >= 2 ? K : 0;
-		if( variant >= 2 && ( nIds < 1 || nIds > nVocab - 1607 ) ) return WH_E_INVALIDARG;
+		if( rows < 1 || rows > 4096 || nVocab < 2048 || nVocab > 52224 || variant < 0 || variant > 5 ) return WH_E_INVALIDARG;
+		const bool tsr = variant >= 4;
+		if( tsr && ( K < 0 || K > 2 ) ) return WH_E_INVALIDARG;
+		const int nIds = ( variant == 2 || variant == 3 ) ? K : 0;
+		if( ( variant == 2 || variant == 3 ) && ( nIds < 1 || nIds > nVocab - 1607 ) ) return WH_E_INVALIDARG;
 		const size_t rowBytes = (size_t)rows * nVocab * 4;
 		const int nBuf = (int)std::min<size_t>( 64, ( (size_t)512 << 20 ) / rowBytes + 2 );
 		std::vector<float*> logits( (size_t)nBuf, nullptr );
@@ -898,8 +915,27 @@ int wh_debug_probe( wh_context* c, int kind, int variant, int M, int N, int K, i
 		WH_HIP( hipStreamSynchronize( st ) );
 		const int beg = nVocab - 1501, sot = beg - 105, solm = beg - 2, tnot = beg - 1;
 		const SampleMailbox noMail = { nullptr, nullptr };
+		int *fedText = nullptr, *fedTs = nullptr;
+		TimestampRecord* records = nullptr;
+		if( tsr )
+		{
+			WH_CHECK( mem.alloc( &fedText, sizeof( int ) * (size_t)rows ) );
+			WH_CHECK( mem.alloc( &fedTs, sizeof( int ) * (size_t)rows ) );
+			WH_CHECK( mem.alloc( &records, sizeof( TimestampRecord ) * (size_t)rows ) );
+			const std::vector<int> text( (size_t)rows, 100 ), stamp( (size_t)rows, beg + 750 );
+			WH_HIP( hipMemcpy( fedText, text.data(), sizeof( int ) * (size_t)rows, hipMemcpyHostToDevice ) );
+			WH_HIP( hipMemcpy( fedTs, stamp.data(), sizeof( int ) * (size_t)rows, hipMemcpyHostToDevice ) );
+			WH_CHECK( launchTimestampRules( probs, rows, nVocab, sot - 1, beg, nullptr, 1, records, st ) );
+		}
 		const auto launch = [ & ]( float* x ) -> int
 		{
+			if( tsr )
+			{
+				// K == 2: the untimed fold of a text token goes to the scratch row `probs`
+				WH_CHECK( launchTimestampRules( x, rows, nVocab, sot - 1, beg, K == 0 ? fedText : fedTs, 0, records, st ) );
+				if( variant == 5 ) return 0;
+				return launchSoftMaxSample( x, probs, rows, nVocab, beg, sot, solm, tnot, state, out, next, noMail, st );
+			}
 			if( variant >= 2 ) WH_CHECK( launchSuppressLogits( x, rows, nVocab, ids, nullptr, nIds, nIds, st ) );
 			if( variant == 3 ) return 0;
 			if( variant == 0 || variant == 2 ) return launchSoftMaxSample( x, probs, rows, nVocab, beg, sot, solm, tnot, state, out, next, noMail, st );
@@ -911,6 +947,7 @@ int wh_debug_probe( wh_context* c, int kind, int variant, int M, int N, int K, i
 		std::vector<float> each;
 		for( int i = 0; i < iters; i++ )
 		{
+			if( tsr && K == 2 ) WH_CHECK( launchTimestampRules( probs, rows, nVocab, sot - 1, beg, fedText, 0, records, st ) );
 			WH_HIP( hipEventRecord( e0, st ) );
 			WH_CHECK( launch( logits[ (size_t)( ( 5 + i ) % nBuf ) ] ) );
 			WH_HIP( hipEventRecord( e1, st ) );

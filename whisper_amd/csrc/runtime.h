@@ -209,6 +209,11 @@ struct wh_context
 	int suppressCount = 0;
 	int* suppress = nullptr;
 	bool suppressBypass = false;
+	// timestamp rules (wh_context_set_timestamp_rules): on = the prompt step of a window resets tsRecords and every step of the device-side loop runs one launch that
+	// folds the fed token into its row's record and masks c->logits. tsRecords [maxSeq] is allocated by the first call that turns the mode on (before any capture)
+	// and never again. Only the device-side loop launches it: wh_decode, wh_lang_detect, wh_align_tokens and the beam step do not.
+	bool tsRules = false;
+	TimestampRecord* tsRecords = nullptr;
 	// wh_context_set_no_speech: p[ solm ] of the prompt step's rows, gathered behind the first sample of every window (allocated by the first call that turns it on)
 	bool noSpeech = false;
 	float* noSpeechDev = nullptr;

@@ -616,6 +616,52 @@ namespace wh
 			}
 		}
 
+		// ---- timestamp rules (wh_context_set_timestamp_rules; DESIGN.md section 7 "Timestamp rules") ----------------------
+		// The three clauses of openai-whisper's ApplyTimestampRules that sampleBest does not hold -- pairs, non-decreasing timestamps, segments of non-zero length --
+		// as -inf over ranges of the row, one workgroup per row. The mask depends on what the row has sampled so far: one TimestampRecord per row in device memory.
+		// reset 0 (a step of the device-side loop): fold fed[ row ], the previous step's sample, into the record, then mask what the record gives. A record whose
+		// count is negative is armed: the fed token is no sample (wh_decode_greedy's first token), nothing is folded and the history starts empty.
+		// reset 1 (the prompt step): the record becomes the empty history and nothing is masked -- the first sample is sampleTimestamp( true )'s business. reset 2: armed.
+		// Every thread reads the record and the fed token, the barrier follows, and only then thread 0 writes the record back: no lane can see the new one.
+		// Plain stores, consecutive lanes to consecutive floats of the row; ranges are held to [0, nVocab).
+		__device__ __forceinline__ void fillNegInf( float* __restrict__ x, int lo, int hi )
+		{
+			for( int i = lo + (int)threadIdx.x; i < hi; i += TSR_THREADS ) x[ i ] = -INFINITY;
+		}
+		__global__ void __launch_bounds__( TSR_THREADS ) timestampRulesKernel( float* __restrict__ logits, int nVocab, int tokenEot, int tokenBeg, const int* __restrict__ fed,
+			int reset, TimestampRecord* __restrict__ records )
+		{
+			const int row = blockIdx.x;
+			if( reset )
+			{
+				if( threadIdx.x == 0 ) records[ row ] = TimestampRecord{ 0, 0, 0, reset == 2 ? -1 : 0 };
+				return;
+			}
+			TimestampRecord r = records[ row ];
+			const int tok = fed[ row ];
+			__syncthreads();
+			if( r.count < 0 ) r = TimestampRecord{ 0, 0, 0, 0 };
+			else
+			{
+				const int isTs = tok >= tokenBeg ? 1 : 0;
+				r.prevTs = r.lastTs;
+				r.lastTs = isTs;
+				if( isTs ) r.lastId = min( tok, nVocab - 1 );
+				r.count = min( r.count + 1, 0x7ffffffe );
+			}
+			if( threadIdx.x == 0 ) records[ row ] = r;
+			float* const x = logits + (long long)row * nVocab;
+			// "the one before it" counts as a timestamp while fewer than two tokens have been sampled
+			const bool open = r.lastTs && !( r.count < 2 || r.prevTs );	  // text, <|t|>: the pair must close
+			if( r.lastTs )
+			{
+				if( open ) fillNegInf( x, 0, min( tokenEot, nVocab ) );
+				else fillNegInf( x, tokenBeg, nVocab );
+			}
+			// lastId: 0 = no timestamp yet (tokenBeg >= 1). A pair may close at the time it opened; everything else must move on
+			if( r.lastId > 0 ) fillNegInf( x, tokenBeg, min( open ? r.lastId : r.lastId + 1, nVocab ) );
+		}
+
 		bool drawShapeOk( int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot )
 		{
 			return rows >= 1 && nVocab >= 1 && nVocab <= SAMPLE_DRAW_MAX_VOCAB && tokenBeg >= 1 && tokenBeg < nVocab && tokenSot >= 0 && tokenSot < tokenBeg &&
@@ -656,6 +702,18 @@ namespace wh
 	{
 		if( !logits || !ids || rows < 1 || nVocab < 1 || count < 0 || cap < 0 ) { setError( "suppressLogits: bad argument" ); return -1; }
 		hipLaunchKernelGGL( suppressLogitsKernel, dim3( rows ), dim3( 256 ), 0, stream, logits, nVocab, ids, countDev, count, cap );
+		WH_HIP( hipGetLastError() );
+		return 0;
+	}
+
+	int launchTimestampRules( float* logits, int rows, int nVocab, int tokenEot, int tokenBeg, const int* fed, int reset, TimestampRecord* records, hipStream_t stream )
+	{
+		if( !logits || !records || ( !reset && !fed ) || rows < 1 || nVocab < 2 || tokenBeg < 1 || tokenBeg >= nVocab || tokenEot < 0 || tokenEot >= tokenBeg || reset < 0 || reset > 2 )
+		{
+			setError( "timestampRules: bad argument" );
+			return -1;
+		}
+		hipLaunchKernelGGL( timestampRulesKernel, dim3( rows ), dim3( TSR_THREADS ), 0, stream, logits, nVocab, tokenEot, tokenBeg, fed, reset, records );
 		WH_HIP( hipGetLastError() );
 		return 0;
 	}

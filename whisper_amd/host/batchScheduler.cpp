@@ -24,6 +24,7 @@
 #include "hostLoop.h"
 #include "batchSampling.h"
 #include "batchSuppress.h"
+#include "batchTimestampRules.h"
 #include "decodeFallback.h"
 #include "languageDetect.h"
 #include "results.h"
@@ -42,6 +43,8 @@ namespace Whisper
 	const BatchSamplingHooks* g_batchSamplingHooks = nullptr;
 	// ... and for suppressed tokens (batchSuppress.h)
 	pfnBatchSuppress g_batchSuppress = nullptr;
+	// ... and for the timestamp rules (batchTimestampRules.h)
+	pfnBatchTimestampRules g_batchTimestampRules = nullptr;
 
 	namespace
 	{
@@ -191,6 +194,8 @@ namespace Whisper
 			bool gathers = false;
 			// suppressed tokens: the version of the runner's set this group's context holds (0 = never told: a new context holds none)
 			uint32_t suppressVersion = 0;
+			// timestamp rules: the version of the runner's switch this group's context holds (0 = never told: a new context has them off)
+			uint32_t timestampRulesVersion = 0;
 		};
 
 		// One call of iBatchRunner::run over the runner's groups (their wh_contexts outlive the call: KV caches, captured graphs)
@@ -672,7 +677,22 @@ namespace Whisper
 			// Whisper::setBatchSuppressedTokens: one set for every stream; each group's context is told once, before the first round that follows a change
 			std::vector<int32_t> suppressIds;
 			uint32_t suppressVersion = 0;
+			// Whisper::setBatchTimestampRules: one switch for every stream; each group's context is told once, before the first round that follows a change
+			bool timestampRulesOn = false;
+			uint32_t timestampRulesVersion = 0;
 		public:
+			HRESULT setTimestampRulesMode( bool on )
+			{
+				if( on && !g_batchTimestampRules )
+				{
+					logError( "setBatchTimestampRules: this build of the scheduler was not given the device's timestamp filter" );
+					return E_NOTIMPL;
+				}
+				if( on == timestampRulesOn ) return S_OK;
+				timestampRulesOn = on;
+				timestampRulesVersion++;
+				return S_OK;
+			}
 			HRESULT setSuppressed( const int32_t* ids, uint32_t count )
 			{
 				if( count && !ids ) return E_POINTER;
@@ -778,6 +798,12 @@ namespace Whisper
 						CHECK_WH( g_batchSuppress( g.gpu, suppressIds.data(), (int)suppressIds.size() ) );
 						g.suppressVersion = suppressVersion;
 					}
+				for( Group& g : groups )
+					if( g.timestampRulesVersion != timestampRulesVersion && g_batchTimestampRules )
+					{
+						CHECK_WH( g_batchTimestampRules( g.gpu, timestampRulesOn ? 1 : 0 ) );
+						g.timestampRulesVersion = timestampRulesVersion;
+					}
 				if( modesDirty && !fallbackOn )
 				{
 					// the feature was turned off: the contexts go back to the greedy sampler and gather nothing
@@ -833,6 +859,17 @@ namespace Whisper
 			return E_INVALIDARG;
 		}
 		return r->setSuppressed( ids, count );
+	}
+	HRESULT setBatchTimestampRules( iBatchRunner* runner, bool on )
+	{
+		if( !runner ) return E_POINTER;
+		BatchRunner* const r = dynamic_cast<BatchRunner*>( runner );
+		if( !r )
+		{
+			logError( "setBatchTimestampRules: not a runner of this library's createBatchRunner" );
+			return E_INVALIDARG;
+		}
+		return r->setTimestampRulesMode( on );
 	}
 	HRESULT getResultWindowStats( const iTranscribeResult* result, sWindowStats* stats, uint32_t* count )
 	{

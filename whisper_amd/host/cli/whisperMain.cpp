@@ -386,7 +386,8 @@ int main( int argc, char** argv )
 	// --fallback (the same way): Whisper::setDecodingFallback with its defaults, a greedy window that scores badly is decoded again at rising temperatures and a
 	// window the model calls silent is dropped; -tpi / -lpt / -et / -nth N (whisper.cpp's names) set temperatureInc, logprobThold, entropyThold, noSpeechThold
 	// -sns / --suppress-nst (the same way; whisper.cpp's names): Whisper::setSuppressedTokens with the model's non-speech set (getNonSpeechTokens)
-	bool align = false, useFallback = false, suppressNst = false;
+	// -tsr / --timestamp-rules (the same way): Whisper::setTimestampRules, openai-whisper's ApplyTimestampRules on the device
+	bool align = false, useFallback = false, suppressNst = false, timestampRules = false;
 	sDecodingFallback fallbackParams;
 	{
 		int kept = 1;
@@ -396,6 +397,7 @@ int main( int argc, char** argv )
 			if( !strcmp( argv[ i ], "--align" ) ) align = true;
 			else if( !strcmp( argv[ i ], "--fallback" ) ) useFallback = true;
 			else if( !strcmp( argv[ i ], "-sns" ) || !strcmp( argv[ i ], "--suppress-nst" ) ) suppressNst = true;
+			else if( !strcmp( argv[ i ], "-tsr" ) || !strcmp( argv[ i ], "--timestamp-rules" ) ) timestampRules = true;
 			else if( !strcmp( argv[ i ], "-tpi" ) ) value = &fallbackParams.temperatureInc;
 			else if( !strcmp( argv[ i ], "-lpt" ) ) value = &fallbackParams.logprobThold;
 			else if( !strcmp( argv[ i ], "-et" ) ) value = &fallbackParams.entropyThold;
@@ -460,6 +462,11 @@ int main( int argc, char** argv )
 		if( SUCCEEDED( hr ) ) hr = getNonSpeechTokens( model, ids.data(), &n );
 		if( SUCCEEDED( hr ) ) hr = setSuppressedTokens( context, ids.data(), n );
 		if( FAILED( hr ) ) { printFailure( "failed to suppress the non-speech tokens", hr ); return 6; }
+	}
+	if( timestampRules )
+	{
+		hr = setTimestampRules( context, true );
+		if( FAILED( hr ) ) { printFailure( "failed to turn the timestamp rules on", hr ); return 6; }
 	}
 
 	ComLight::CComPtr<iMediaFoundation> media;

@@ -55,6 +55,8 @@ namespace
 		// -sns / --suppress-nst: Whisper::setBatchSuppressedTokens on every rank's runner with the model's non-speech set (getNonSpeechTokens: every rank computes
 		// the same set from the same vocabulary)
 		bool suppressNst = false;
+		// -tsr / --timestamp-rules: Whisper::setBatchTimestampRules on every rank's runner
+		bool timestampRules = false;
 	};
 	std::wstring widen( const std::string& s )
 	{
@@ -262,6 +264,11 @@ namespace
 			if( SUCCEEDED( hr ) ) hr = setBatchSuppressedTokens( runner, ids.data(), n );
 			if( FAILED( hr ) ) { fprintf( stderr, "[rank %d] setBatchSuppressedTokens failed 0x%08x\n", rank, (unsigned)hr ); return 6; }
 		}
+		if( runner && a.timestampRules )
+		{
+			hr = setBatchTimestampRules( runner, true );
+			if( FAILED( hr ) ) { fprintf( stderr, "[rank %d] setBatchTimestampRules failed 0x%08x\n", rank, (unsigned)hr ); return 6; }
+		}
 
 		if( 0 != wh_comm_barrier( comm ) ) { fprintf( stderr, "[rank %d] %s\n", rank, wh_last_error() ); return 8; }
 		const double tStart = since();
@@ -410,6 +417,7 @@ int main( int argc, char** argv )
 		else if( !strcmp( argv[ i ], "-slots" ) ) a.slots = atoi( val() );
 		else if( !strcmp( argv[ i ], "-fallback" ) || !strcmp( argv[ i ], "--fallback" ) ) a.useFallback = true;
 		else if( !strcmp( argv[ i ], "-sns" ) || !strcmp( argv[ i ], "--suppress-nst" ) ) a.suppressNst = true;
+		else if( !strcmp( argv[ i ], "-tsr" ) || !strcmp( argv[ i ], "--timestamp-rules" ) ) a.timestampRules = true;
 		else if( !strcmp( argv[ i ], "-tpi" ) ) a.fallback.temperatureInc = (float)atof( val() );
 		else if( !strcmp( argv[ i ], "-lpt" ) ) a.fallback.logprobThold = (float)atof( val() );
 		else if( !strcmp( argv[ i ], "-et" ) ) a.fallback.entropyThold = (float)atof( val() );

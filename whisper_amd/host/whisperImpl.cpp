@@ -11,6 +11,7 @@
 #include "decodeFallback.h"
 #include "batchSampling.h"
 #include "batchSuppress.h"
+#include "batchTimestampRules.h"
 #include "languageDetect.h"
 #include "results.h"
 #include "wavFormat.h"
@@ -128,6 +129,8 @@ namespace Whisper
 			std::vector<sWindowStats> windowStats;
 			// Whisper::setSuppressedTokens: empty unless set; every device context this object owns holds it (beamContext tells the ones created later)
 			std::vector<int32_t> suppressIds;
+			// Whisper::setTimestampRules: off unless set. The stream's device context holds the mode; the hypothesis-group context of beam search cannot (runFull refuses)
+			bool timestampRulesOn = false;
 
 			using Clock = std::chrono::steady_clock;
 			static double msSince( Clock::time_point t ) { return std::chrono::duration<double, std::milli>( Clock::now() - t ).count(); }
@@ -225,6 +228,12 @@ namespace Whisper
 				CHECK_WH( wh_context_set_suppress( gpu, ids, (int)count ) );
 				if( gpuBeam ) CHECK_WH( wh_context_set_suppress( gpuBeam, ids, (int)count ) );
 				suppressIds.assign( ids, ids + count );
+				return S_OK;
+			}
+			HRESULT setTimestampRulesMode( bool on )
+			{
+				CHECK_WH( wh_context_set_timestamp_rules( gpu, on ? 1 : 0 ) );
+				timestampRulesOn = on;
 				return S_OK;
 			}
 			const std::vector<sWindowStats>& lastWindowStats() const { return windowStats; }
@@ -846,6 +855,12 @@ namespace Whisper
 				logError( "runFull: decoding fallback (setDecodingFallback) is not available with eSamplingStrategy::BeamSearch" );
 				return E_NOTIMPL;
 			}
+			// timestamp rules: the device-side loop only (the records would have to follow the beam's parent reorder: a follow-up)
+			if( timestampRulesOn && params.strategy == eSamplingStrategy::BeamSearch && params.beam_search.beam_width >= 1 )
+			{
+				logError( "runFull: the timestamp rules (setTimestampRules) are not available with eSamplingStrategy::BeamSearch" );
+				return E_NOTIMPL;
+			}
 			StreamRun run( params, vocab, hp, this, progress, resultAll, promptPast, &stamper );
 			// the run's audio is current until this function returns; the stereo PCM is the caller's and is not referred to afterwards
 			struct CurrentRun
@@ -1187,6 +1202,8 @@ namespace Whisper
 	static const bool g_samplingInstalled = ( g_batchSamplingHooks = &g_samplingHooks, true );
 	// ... and to the logit filter of suppressed tokens (batchSuppress.h)
 	static const bool g_suppressInstalled = ( g_batchSuppress = &wh_context_set_suppress, true );
+	// ... and to the timestamp rules (batchTimestampRules.h)
+	static const bool g_timestampRulesInstalled = ( g_batchTimestampRules = &wh_context_set_timestamp_rules, true );
 
 	HRESULT createContextImpl( const std::shared_ptr<LoadedModel>& model, iModel* owner, iContext** pp )
 	{
@@ -1232,6 +1249,17 @@ namespace Whisper
 			return E_INVALIDARG;
 		}
 		return c->setSuppressed( ids, count );
+	}
+	HRESULT setTimestampRules( iContext* context, bool on )
+	{
+		if( !context ) return E_POINTER;
+		ContextImpl* const c = dynamic_cast<ContextImpl*>( context );
+		if( !c )
+		{
+			logError( "setTimestampRules: not a context of this library's createContext (a batch runner takes setBatchTimestampRules)" );
+			return E_INVALIDARG;
+		}
+		return c->setTimestampRulesMode( on );
 	}
 	HRESULT getWindowStats( const iContext* context, sWindowStats* stats, uint32_t* count )
 	{
@@ -1445,6 +1473,17 @@ WHISPER_EXPORT int32_t whisperc_batch_set_suppress_tokens( void* runner, const i
 {
 	if( !runner ) return E_POINTER;
 	return setBatchSuppressedTokens( (iBatchRunner*)runner, ids, count );
+}
+// Whisper::setTimestampRules / setBatchTimestampRules
+WHISPER_EXPORT int32_t whisperc_set_timestamp_rules( void* ctx, int32_t on )
+{
+	if( !ctx ) return E_POINTER;
+	return setTimestampRules( (iContext*)ctx, on != 0 );
+}
+WHISPER_EXPORT int32_t whisperc_batch_set_timestamp_rules( void* runner, int32_t on )
+{
+	if( !runner ) return E_POINTER;
+	return setBatchTimestampRules( (iBatchRunner*)runner, on != 0 );
 }
 // Whisper::getResultWindowStats: out = sWindowStats [cap] (may be NULL), *count = the windows of the result's stream
 WHISPER_EXPORT int32_t whisperc_tr_window_stats( void* result, void* out, uint32_t cap, uint32_t* count )
