@@ -425,6 +425,42 @@ namespace Whisper
 	WHISPER_EXPORT HRESULT setTimestampRules( iContext* context, bool on );
 	// One switch for all streams of every later run of the runner. E_NOTIMPL to turn it on where the scheduler was built without the device's filter.
 	WHISPER_EXPORT HRESULT setBatchTimestampRules( iBatchRunner* runner, bool on );
+	// Extension: scoring a GIVEN transcript -- "how probable is this text for this audio?" -- and, with flag 1, forced alignment of a known text. The tokens are
+	// fed to the decoder (teacher forcing) and every scored token receives its log-probability under the model's OWN distribution: neither suppressed tokens nor
+	// the timestamp rules nor the sampler's clauses apply, and a context's decoding settings do not matter. True logarithms (an unlikely token scores a large
+	// negative number, not -inf); the definition is wh_token_score's in whisper_hip.h. Free functions: the vtables are the reference's.
+	struct sScoreRequest
+	{
+		// samples [firstSample, firstSample + countSamples) of the buffer's mono PCM (16 kHz); countSamples 0 = to the end. A clip of 1 to 30 s: its spectrogram is
+		// the one runFull makes of those samples, normalised on its own maximum, scored as ONE window at seek 0 with the model's full audio context. Anything
+		// shorter or longer is E_INVALIDARG: long-form scoring (walking the windows of a recording) is out of scope.
+		const iAudioBuffer* buffer;
+		int64_t firstSample, countSamples;
+		const whisper_token* prompt;	// fed, not scored: [prev + past text,] sot, language, task[, no-timestamps] (makeSotSequence)
+		uint32_t promptCount;
+		const whisper_token* tokens;	// scored; eot is appended and scored too: count + 1 records
+		uint32_t count;
+		uint32_t flags;					// 1 = also align (forced alignment): the prompt must hold the no-timestamps token exactly once and as its last entry, the
+										// scored tokens must all lie below eot; promptCount + count + 1 <= min( 256, n_text_ctx ) in any case
+	};
+	struct sTokenScore
+	{
+		float logprob, bestLogprob;		// of the token, and of the arg-max of its row
+		int32_t best, rank;				// the arg-max (ties to the lower id); how many ids the model prefers to the token (0 = it is what greedy decoding takes)
+		sTimeInterval time;				// flag 1: from the warping path, by the frame-to-time rule of eFullParamsFlags::AlignTokens (eot: the end of the text),
+										// relative to the buffer plus its media time; zero without the flag (timestamp tokens among the scored tokens are then legal)
+	};
+	// scores: request.count + 1 records. Uses the context's own device context: its self-attention caches are overwritten, its results and settings stay.
+	// E_INVALIDARG for a context of another library, an empty prompt or token list, an id outside the vocabulary, a row that is too long, a clip outside 1 .. 30 s.
+	WHISPER_EXPORT HRESULT scoreTokens( iContext* context, const sScoreRequest& request, sTokenScore* scores );
+	// `count` requests on the runner's first group, up to maxSlots per pass in request order; one pass = one encoder batch and one scoring call. scores[ i ]:
+	// requests[ i ].count + 1 records. perRequest, when non-null, receives every request's own HRESULT; returns the first failure, S_OK otherwise: a request that
+	// fails its checks does not keep its neighbours from being scored. Flag 1 is E_NOTIMPL here (token alignment in a batch runner is). E_NOTIMPL where the
+	// scheduler was built without the device's scorer.
+	WHISPER_EXPORT HRESULT scoreBatch( iBatchRunner* runner, const sScoreRequest* requests, uint32_t count, sTokenScore* const* scores, HRESULT* perRequest );
+	// The tokens that select the task, as runFull builds them: sot[, language, transcribe | translate] for a multilingual model, then the no-timestamps token unless
+	// `timestamps`. language: makeLanguageKey( "en" ). count in: the capacity of `out`; out: the number of tokens (E_BOUNDS when the capacity is too small).
+	WHISPER_EXPORT HRESULT makeSotSequence( iModel* model, uint32_t language, bool translate, bool timestamps, whisper_token* out, uint32_t* count );
 	// Extension (no counterpart in whisper.def): ONE long recording onto the batched path. The buffer is cut into pieces of at most maxLen samples at pauses,
 	// found with the reference's voice-activity detector (Whisper/Whisper/voiceActivityDetection.cpp, which its capture loop uses to fire a transcription when
 	// the speaker pauses): the per-frame features come from the device (wh_vad_features of whisper_hip.h, on the calling thread's current device), the decision

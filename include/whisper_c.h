@@ -152,6 +152,21 @@ int32_t whisperc_tr_language( void* result, char* code5, float* p );
 int32_t whisperc_debug_context_flags( void* ctx, uint32_t flags, int32_t parityThreads );
 /* The code of language id (0 .. 98; the language token is sot + 1 + id) -> code5; S_FALSE beyond the table */
 int32_t whisperc_language_code( int32_t id, char* code5 );
+/* Scoring a given transcript (Whisper::scoreTokens / scoreBatch / makeSotSequence of whisperApi.h): teacher-forced token log-probabilities.
+ * whisperc_sot_sequence: the tokens that select the task -- sot[, language, transcribe | translate], then the no-timestamps token unless `timestamps` -- into
+ *   out[ cap ]; *count = their number (out may be NULL to ask for it; E_BOUNDS when cap is too small).
+ * whisperc_score_tokens: the whole mono FP32 16 kHz buffer is the clip (1 to 30 s, one window); `prompt` is fed, `tokens` are scored and eot behind them:
+ *   scoresOut receives count + 1 records of 32 bytes = { float logprob, bestLogprob; int32 best, rank; uint64 t0, t1 } (100 ns ticks; zero unless flags & 1 =
+ *   forced alignment, which needs the no-timestamps token as the prompt's last entry and text tokens only).
+ * whisperc_batch_score: `count` requests on a batch runner, up to its maxSlots per pass in request order; request i = samples [firstSample[i], firstSample[i] +
+ *   countSamples[i]) (0 = to the end; the arrays may be NULL) of pcm[i], prompts[i] / tokens[i] with promptCounts[i] / counts[i] entries; scoresOut[i] receives
+ *   counts[i] + 1 records, perRequest[i] (may be NULL) the request's own HRESULT. Returns the first failure. flags & 1 is E_NOTIMPL here. */
+int32_t whisperc_sot_sequence( void* model, const char* language, int32_t translate, int32_t timestamps, int32_t* out, uint32_t cap, uint32_t* count );
+int32_t whisperc_score_tokens( void* ctx, const float* pcm, uint32_t nSamples, const int32_t* prompt, uint32_t promptCount, const int32_t* tokens, uint32_t count,
+	uint32_t flags, void* scoresOut );
+int32_t whisperc_batch_score( void* runner, uint32_t count, const float* const* pcm, const uint32_t* nSamples, const int64_t* firstSample, const int64_t* countSamples,
+	const int32_t* const* prompts, const uint32_t* promptCounts, const int32_t* const* tokens, const uint32_t* counts, uint32_t flags, void* const* scoresOut,
+	int32_t* perRequest );
 /* iContext::timingsPrint */
 int32_t whisperc_timings_print( void* ctx );
 /* One line of the profiler output, formatted like ProfileCollection::Measure::print (Whisper/Utils/ProfileCollection.cpp:113-170):

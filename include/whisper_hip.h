@@ -323,6 +323,35 @@ WH_API int wh_model_lang_count( const wh_model* m );
 WH_API int wh_model_set_alignment_heads( wh_model* m, const int32_t* layerHeadPairs, int count );
 WH_API int wh_align_tokens( wh_context* c, int batch, const int32_t* tokens, const int32_t* lens, const int32_t* nKeys, int nMax, int32_t* framesHost );
 
+/* Scoring a GIVEN transcript: teacher-forced token log-probabilities (an extension: the reference only scores what it samples). The definition is DESIGN.md
+ * section 7 "Scoring", restated in float64 by tests/token_score_ref.py. A row of FP32 logits x[ 0 .. V ) and a target id t give one record:
+ *   logprob     = x[ t ] - m - ln sum_j exp( x[ j ] - m ), m = max_j x[ j ];
+ *   bestLogprob = -ln sum_j exp( x[ j ] - m ), the log-probability of the arg-max;
+ *   best        = the lowest id j with x[ j ] == m;
+ *   rank        = #{ j : x[ j ] > x[ t ] } + #{ j < t : x[ j ] == x[ t ] }: 0 means t is what an arg-max would take under wh_sample_best's tie rule (exact ties
+ *                 resolve to the lower token id).
+ * These are TRUE logarithms, not ln of the table softmax's probabilities (whose FP16 exponential is 0 for an unlikely token): FP32 expf per term, the sum in
+ * double, the two logarithms formed in double and rounded once. An entry of -inf adds 0 to the sum; a target at -inf scores -inf with a finite bestLogprob.
+ * The pass scores the model's OWN distribution: neither the suppressed set (wh_context_set_suppress) nor the timestamp rules nor any clause of wh_sample_best
+ * applies, as in wh_lang_detect.
+ *   wh_score_tokens: after wh_encode / wh_encode_windows of at least `batch` windows and after their decoding is over (the call overwrites the sequences' self-
+ *     attention caches and the decoder activations like wh_align_tokens; logits and probabilities of the last wh_decode stay as they were, the product writes into a
+ *     buffer of its own). tokens: HOST [batch][nMax], row b = lens[ b ] tokens followed by padding (ignored). Entry i of row b is scored for
+ *     firstScored[ b ] <= i < lens[ b ], 1 <= firstScored[ b ] < lens[ b ] <= nMax <= min( 256, n_text_ctx ): the probability of token i given tokens 0 .. i - 1,
+ *     that is, decoder row i - 1. One teacher-forced pass of the multi-token decoder graph at position 0 through every layer and the final LayerNorm; the needed
+ *     rows are gathered compactly and go through the vocabulary product at most "score_chunk_rows" rows at a time, each chunk reduced by the kernel of
+ *     wh_op_token_scores, so the [rows][n_vocab] logits are never downloaded. The product is the M-tiled kernel whatever the row count, so the records do not
+ *     depend on the chunk size, bit for bit. The pass before it is the decoder's own, which picks its kernels by the total number of rows: a window's records
+ *     may move in their last bits with the batch. outHost: HOST [batch][nMax], the scored entries filled, every other one zero.
+ *     Greedy contexts only: WH_E_INVALIDARG on a hypothesis-group context and under WH_FLAG_PARITY_EXACT. Buffers are allocated by the first call; contexts that
+ *     never call it pay nothing, and no captured graph changes. */
+typedef struct wh_token_score
+{
+	float logprob, bestLogprob;
+	int32_t best, rank;
+} wh_token_score;
+WH_API int wh_score_tokens( wh_context* c, int batch, const int32_t* tokens, const int32_t* lens, const int32_t* firstScored, int nMax, wh_token_score* outHost );
+
 /* sTokenData of the reference (Whisper/Whisper/sTokenData.h): the result of ContextImpl::sampleBest. */
 typedef struct wh_token_data
 {
@@ -522,7 +551,7 @@ WH_API int wh_debug_read( wh_context* c, const char* what, int layer, int rows, 
  * afterwards (and their captured graphs) use the new setting. */
 WH_API int wh_debug_set_tuning( uint32_t mask );
 /* Integer knobs beyond the 32 switches (whisper_amd/csrc/kernels.h struct Options: "dec_tile", "dec_depth", "dec_wide_rows", "dec_deep_rows", "vocab_decrows",
- * "enc_chunk", "self_fuse_max_rows", "self_nq", "self_wave_min_rows", "enc_exp", "enc_sched", "exact_enc_layers", "exact_alt_order", "gemm_mf16", "dec_lds", "dec_lds_ks", "dec_split", "cross_mfma", "vocab_lds", "beam_regs", "reorder_group", "gemm_big_min_rows", "resample_lds_phases"); also settable as WH_OPT_<NAME> in the environment at load.
+ * "enc_chunk", "self_fuse_max_rows", "self_nq", "self_wave_min_rows", "enc_exp", "enc_sched", "exact_enc_layers", "exact_alt_order", "gemm_mf16", "dec_lds", "dec_lds_ks", "dec_split", "cross_mfma", "vocab_lds", "beam_regs", "reorder_group", "gemm_big_min_rows", "resample_lds_phases", "score_chunk_rows", "score_regs"); also settable as WH_OPT_<NAME> in the environment at load.
  * Unknown names and values outside [-1, 2^24]: WH_E_INVALIDARG (the environment form: ignored with a line on stderr). The options are process-global and read without
  * synchronisation by every launch: set them BEFORE contexts are created, never while another thread runs one. */
 WH_API int wh_debug_set_option( const char* name, int value );
@@ -611,6 +640,11 @@ WH_API int wh_op_timestamp_rules( void* stream, float* logits, int rows, int nVo
  * tokenSot + 1 .. tokenSot + nLang, bit for bit, without writing the other columns; best [rows] = the index (0 .. nLang - 1) of the largest, exact ties
  * to the lower index. The row stays in registers: nVocab <= 52224; 1 <= nLang <= 1024 and the block inside the row, or WH_E_INVALIDARG. */
 WH_API int wh_op_lang_probs( void* stream, const float* logits, int rows, int nVocab, int tokenSot, int nLang, float* langP, int32_t* best );
+/* The kernel of wh_score_tokens outside a context: outDev[ r ] = the record (see wh_token_score) of row r of logits, rowStride >= nVocab floats apart, against
+ * targetsDev[ r ]. One 1024-thread workgroup per row; the row is read once and kept in registers up to 52224 columns, read twice beyond (and everywhere with the
+ * option "score_regs" 0): the same bits. The targets are downloaded and checked first, so the call waits for the stream: a target outside [0, nVocab),
+ * rowStride < nVocab, a null pointer or rows < 1 is WH_E_INVALIDARG and nothing is launched. No atomics, no scratch memory. */
+WH_API int wh_op_token_scores( void* stream, const float* logits, int64_t rowStride, int rows, int nVocab, const int32_t* targetsDev, wh_token_score* outDev );
 /* wh_sample_best on probabilities [rows][nVocab]: out [rows]. tokenBeg .. nVocab - 1 are the timestamps; the specials are < tokenBeg. */
 WH_API int wh_op_sample_best( void* stream, const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot,
 	int forceTimestamp, int isInitial, wh_token_data* out );

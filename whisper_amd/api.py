@@ -93,6 +93,9 @@ def lib():
         L.whisperc_detect_speaker.argtypes = [vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint8)]
         L.whisperc_result_speakers.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
         L.whisperc_tr_speakers.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.whisperc_sot_sequence.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32, vp, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.whisperc_score_tokens.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp]
+        L.whisperc_batch_score.argtypes = [vp, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp]
         L.whisperc_vad.argtypes = [vp, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.whisperc_plan_chunks.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, vp, vp, C.c_int32, C.POINTER(C.c_int32)]
         L.whisperc_debug_vad_decide.argtypes = [vp, C.c_int64, vp, C.POINTER(C.c_int64)]
@@ -278,6 +281,13 @@ class Model:
     def is_multilingual(self) -> bool:
         return lib().whisperc_is_multilingual(self.h) == 0
 
+    def sot_sequence(self, language: str = "en", translate: bool = False, timestamps: bool = False) -> List[int]:
+        """Whisper::makeSotSequence: the tokens that select the task, as runFull builds them -- sot[, language, transcribe | translate], then the
+        no-timestamps token unless `timestamps`."""
+        out, n = (C.c_int32 * 8)(), C.c_uint32(0)
+        _check(lib().whisperc_sot_sequence(self.h, language.encode(), int(translate), int(timestamps), out, 8, C.byref(n)), "makeSotSequence")
+        return [int(out[i]) for i in range(n.value)]
+
     def set_alignment_heads(self, pairs: Sequence[Sequence[int]]):
         """Whisper::setAlignmentHeads: the (layer, head) pairs whose cross-attention weights ALIGN_TOKENS averages; [] restores the default (every head of
         the upper half of the decoder's layers)."""
@@ -308,6 +318,32 @@ def _suppress_ids(model: Model, ids) -> np.ndarray:
             raise ValueError('set_suppress_tokens: the only named set is "non_speech"')
         ids = model.non_speech_tokens()
     return np.ascontiguousarray(ids, np.int32).reshape(-1)
+
+
+# sTokenScore of whisperApi.h: the record of Whisper::scoreTokens / scoreBatch (times in 100 ns ticks, zero unless aligned)
+TOKEN_SCORE_DT = np.dtype([("logprob", "<f4"), ("best_logprob", "<f4"), ("best", "<i4"), ("rank", "<i4"), ("t0", "<u8"), ("t1", "<u8")])
+SCORE_ALIGN = 1
+
+
+def _score_request(model, tokens_or_text, language, translate, timestamps, prompt, align):
+    """(prompt tokens, scored tokens) of a scoring request: text goes through the model's tokenize, the prompt is [prev + past text,] + the sot sequence"""
+    tokens = model.tokenize(tokens_or_text) if isinstance(tokens_or_text, str) else [int(t) for t in tokens_or_text]
+    seq = model.sot_sequence(language, translate, timestamps and not align)
+    past = ([model.special_tokens()["prev"]] + [int(t) for t in prompt]) if prompt is not None and len(prompt) else []
+    return np.ascontiguousarray(past + seq, np.int32), np.ascontiguousarray(tokens, np.int32)
+
+
+def _score_dicts(model, tokens, recs, align):
+    """The per-token dicts of Context.score / BatchRunner.score: the scored tokens and eot behind them"""
+    ids = [int(t) for t in tokens] + [model.special_tokens()["eot"]]
+    out = []
+    for t, r in zip(ids, recs):
+        d = dict(id=t, text=model.token_string(t), logprob=float(r["logprob"]), best=int(r["best"]), best_logprob=float(r["best_logprob"]), rank=int(r["rank"]))
+        if align:
+            d["t0"], d["t1"] = int(r["t0"]), int(r["t1"])
+        out.append(d)
+    total = float(np.sum(recs["logprob"].astype(np.float64)))
+    return dict(tokens=out, sum_logprob=total, avg_logprob=total / len(out))
 
 
 class WindowStatsC(C.Structure):
@@ -370,6 +406,20 @@ class Context:
                                                      thold_pt, thold_ptsum, max_len), "runFull")
         return _check(lib().whisperc_run_full(self.h, pcm.ctypes.data_as(C.c_void_p), len(pcm), language.encode(), flags, max_tokens,
                                               pt.ctypes.data_as(C.c_void_p) if len(pt) else None, len(pt), n_max_text_ctx), "runFull")
+
+    def score(self, pcm: np.ndarray, tokens_or_text, language: str = "en", translate: bool = False, timestamps: bool = False,
+              prompt: Optional[Sequence[int]] = None, align: bool = False, sample_rate: int = 16000):
+        """Whisper::scoreTokens: how probable is this transcript for this clip (1 to 30 s of mono PCM; one window)? The tokens -- or the text, through the model's
+        tokenize -- are fed to the decoder behind [prev + prompt,] sot, language, task[, no-timestamps], and each of them and the eot behind them is scored under
+        the model's own distribution. Returns dict(tokens=[dict(id, text, logprob, best, best_logprob, rank[, t0, t1])], sum_logprob, avg_logprob).
+        align: forced alignment of the known text -- t0 / t1 (100 ns ticks) from the decoder's cross-attention, as ALIGN_TOKENS gives a transcript of its own;
+        text tokens only, and the prompt ends on the no-timestamps token whatever `timestamps` says."""
+        pcm = _at_16k(pcm, sample_rate)
+        pt, tk = _score_request(self.model, tokens_or_text, language, translate, timestamps, prompt, align)
+        recs = np.zeros(len(tk) + 1, TOKEN_SCORE_DT)
+        _check(lib().whisperc_score_tokens(self.h, pcm.ctypes.data_as(C.c_void_p), len(pcm), pt.ctypes.data_as(C.c_void_p), len(pt),
+                                           tk.ctypes.data_as(C.c_void_p), len(tk), SCORE_ALIGN if align else 0, recs.ctypes.data_as(C.c_void_p)), "scoreTokens")
+        return _score_dicts(self.model, tk, recs, align)
 
     def run_streamed(self, pcm: np.ndarray, language: str = "en", flags: int = 0, max_tokens: int = 0,
                      prompt: Optional[Sequence[int]] = None, n_max_text_ctx: int = -1, sample_rate: int = 16000, stereo: Optional[np.ndarray] = None):
@@ -606,6 +656,27 @@ class BatchRunner:
         _check(hr, "runFullBatch")
         return hr, out, [int(x) & 0xFFFFFFFF for x in per]
 
+
+    def score(self, items, language: str = "en", translate: bool = False, timestamps: bool = False, prompt: Optional[Sequence[int]] = None):
+        """Whisper::scoreBatch: Context.score for many (clip, transcript) pairs, up to the runner's max_slots per pass in the order given. items: a list of
+        (pcm, tokens_or_text) or (pcm, first_sample, count_samples, tokens_or_text) -- float32 PCM at 16 kHz, pieces of a recording share the array.
+        Returns (HRESULT of the first failure or 0, [Context.score's dict per item, None where the item failed], [per-item HRESULT]): an item that fails its
+        checks does not keep its neighbours from being scored. Forced alignment is Context.score's."""
+        n = len(items)
+        keep, ptrs, lens, first, cnt = [], (C.c_void_p * n)(), (C.c_uint32 * n)(), (C.c_int64 * n)(), (C.c_int64 * n)()
+        pps, pcs, tps, tcs, outs = (C.c_void_p * n)(), (C.c_uint32 * n)(), (C.c_void_p * n)(), (C.c_uint32 * n)(), (C.c_void_p * n)()
+        for i, it in enumerate(items):
+            pcm, f, c, what = (it[0], 0, 0, it[1]) if len(it) == 2 else it
+            assert pcm.dtype == np.float32 and pcm.flags["C_CONTIGUOUS"]
+            pt, tk = _score_request(self.model, what, language, translate, timestamps, prompt, False)
+            recs = np.zeros(len(tk) + 1, TOKEN_SCORE_DT)
+            keep.append((pcm, pt, tk, recs))
+            ptrs[i], lens[i], first[i], cnt[i] = pcm.ctypes.data, len(pcm), f, c
+            pps[i], pcs[i], tps[i], tcs[i], outs[i] = pt.ctypes.data, len(pt), tk.ctypes.data, len(tk), recs.ctypes.data
+        per = (C.c_int32 * n)()
+        hr = lib().whisperc_batch_score(self.h, n, ptrs, lens, first, cnt, pps, pcs, tps, tcs, 0, outs, per) & 0xFFFFFFFF
+        res = [_score_dicts(self.model, k[2], k[3], False) if per[i] >= 0 else None for i, k in enumerate(keep)]
+        return hr, res, [int(x) & 0xFFFFFFFF for x in per]
 
     def run_split(self, pcm: np.ndarray, flags: int = 0, sample_rate: int = 16000, **run_kwargs):
         """ONE long recording on the batched path: cut at pauses (plan_chunks), the pieces run as independent streams (NoContext is added to flags: a piece

@@ -59,6 +59,7 @@ EXPORTS = [
     "wh_context_set_suppress", "wh_op_suppress_logits",
     "wh_context_set_timestamp_rules", "wh_op_timestamp_rules",
     "wh_op_gemv_small", "wh_op_cross_split", "wh_op_self_block_dec",
+    "wh_score_tokens", "wh_op_token_scores",
 ]
 
 
@@ -68,6 +69,14 @@ class HParamsC(C.Structure):
 
 class TokenDataC(C.Structure):
     _fields_ = [("id", C.c_int32), ("tid", C.c_int32), ("p", C.c_float), ("pt", C.c_float), ("ptsum", C.c_float)]
+
+
+class TokenScoreC(C.Structure):
+    """wh_token_score: the score of a given token under a row of logits (include/whisper_hip.h)."""
+    _fields_ = [("logprob", C.c_float), ("bestLogprob", C.c_float), ("best", C.c_int32), ("rank", C.c_int32)]
+
+
+TOKEN_SCORE_DTYPE = np.dtype([("logprob", "<f4"), ("bestLogprob", "<f4"), ("best", "<i4"), ("rank", "<i4")])
 
 
 class SampleRowC(C.Structure):
@@ -207,6 +216,8 @@ def lib():
         L.wh_op_gemv_small.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, C.c_float]
         L.wh_op_cross_split.argtypes = [vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, i32, i32, i32, i32]
         L.wh_op_self_block_dec.argtypes = [vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, i32, i32, i32, i32, vp]
+        L.wh_score_tokens.argtypes = [vp, i32, vp, vp, vp, i32, vp]
+        L.wh_op_token_scores.argtypes = [vp, vp, i64, i32, i32, vp, vp]
         _lib = L
     return _lib
 
@@ -222,7 +233,14 @@ def set_option(name: str, value: int):
 
 
 # the defaults of csrc/kernels.h struct Options (what a test restores an option to)
-OPTION_DEFAULTS = {"dec_tile": 0, "dec_depth": 0, "dec_wide_rows": 1, "dec_deep_rows": 0, "vocab_decrows": 0, "enc_chunk": 128, "self_fuse_max_rows": 32, "self_nq": 0, "self_wave_min_rows": 32, "enc_exp": 5, "enc_sched": 1, "exact_enc_layers": -1, "exact_alt_order": 0, "gemm_mf16": 1, "dec_lds": 1, "dec_lds_ks": 2, "dec_split": 1, "cross_mfma": 1, "vocab_lds": 1, "beam_regs": 1, "reorder_group": 1, "gemm_big_min_rows": 8192, "resample_lds_phases": 853}
+OPTION_DEFAULTS = {"dec_tile": 0, "dec_depth": 0, "dec_wide_rows": 1, "dec_deep_rows": 0, "vocab_decrows": 0, "enc_chunk": 128, "self_fuse_max_rows": 32, "self_nq": 0, "self_wave_min_rows": 32, "enc_exp": 5, "enc_sched": 1, "exact_enc_layers": -1, "exact_alt_order": 0, "gemm_mf16": 1, "dec_lds": 1, "dec_lds_ks": 2, "dec_split": 1, "cross_mfma": 1, "vocab_lds": 1, "beam_regs": 1, "reorder_group": 1, "gemm_big_min_rows": 8192, "resample_lds_phases": 853,
+                   "score_chunk_rows": 320, "score_regs": 1}
+
+
+def op_token_scores(logits_ptr, row_stride: int, rows: int, n_vocab: int, targets_ptr, out_ptr, stream=None):
+    """wh_op_token_scores on device memory: out[r] (16 bytes, TOKEN_SCORE_DTYPE) = the record of row r of the FP32 logits, row_stride floats apart, against the
+    int32 target r. The arguments are device addresses (ctypes.c_void_p or int). Waits for the stream: the targets are checked on the host before the launch."""
+    check(lib().wh_op_token_scores(stream, logits_ptr, int(row_stride), int(rows), int(n_vocab), targets_ptr, out_ptr))
 
 
 def get_option(name: str) -> int:
@@ -499,6 +517,24 @@ class HipContext:
                                     frames.ctypes.data_as(C.c_void_p)))
         self._align = (len(rows), n_max)
         return frames
+
+    def score_tokens(self, tokens, lens, first_scored, n_max: Optional[int] = None):
+        """Teacher-forced scores of given rows for the windows of the last encode. tokens: per window its row (row b holds lens[b] tokens; what follows is
+        padding); entry i of row b is scored for first_scored[b] <= i < lens[b]: the probability of token i given tokens 0 .. i - 1. Returns a structured array
+        [batch][n_max] with the fields logprob, bestLogprob, best, rank (TOKEN_SCORE_DTYPE); entries that are not scored are zero. Overwrites the sequences'
+        self-attention caches and the decoder activations like align_tokens."""
+        lens = np.ascontiguousarray(lens, np.int32)
+        first = np.ascontiguousarray(first_scored, np.int32)
+        assert len(tokens) == len(lens) == len(first)
+        n_max = max(len(r) for r in tokens) if n_max is None else int(n_max)
+        t = np.zeros((len(lens), max(n_max, 1)), np.int32)
+        for b, r in enumerate(tokens):
+            r = np.asarray(r, np.int32)[:n_max]
+            t[b, :len(r)] = r
+        out = np.zeros((len(lens), max(n_max, 1)), TOKEN_SCORE_DTYPE)
+        check(lib().wh_score_tokens(self.handle, len(lens), t.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), first.ctypes.data_as(C.c_void_p), n_max,
+                                    out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def sample_best(self, batch: int, force_timestamp: bool = False, is_initial: bool = False):
         out = (TokenDataC * batch)()

@@ -541,4 +541,92 @@ int wh_align_tokens( wh_context* c, int batch, const int32_t* tokens, const int3
 	return 0;
 }
 
+// Teacher-forced scores of given rows (include/whisper_hip.h; DESIGN.md section 7 "Scoring"): the pass of wh_align_tokens carried through every layer and the
+// final LayerNorm, then the vocabulary product of the rows that predict a scored token only, chunk by chunk, each chunk reduced to 16 bytes per row.
+int wh_score_tokens( wh_context* c, int batch, const int32_t* tokens, const int32_t* lens, const int32_t* firstScored, int nMax, wh_token_score* outHost )
+{
+	if( !c || !tokens || !lens || !firstScored || !outHost || batch <= 0 || nMax <= 0 ) { setError( "score_tokens: bad argument" ); return WH_E_INVALIDARG; }
+	if( c->hyp != 1 ) { setError( "score_tokens: greedy contexts only (one hypothesis per window)" ); return WH_E_INVALIDARG; }
+	if( c->flags & WH_FLAG_PARITY_EXACT ) { setError( "score_tokens: not under WH_FLAG_PARITY_EXACT" ); return WH_E_INVALIDARG; }
+	if( !c->encoded ) { setError( "score_tokens: wh_encode has not run" ); return WH_E_NOT_READY; }
+	if( batch > c->lastEncBatch ) { setError( "score_tokens: more windows than the last wh_encode filled" ); return WH_E_INVALIDARG; }
+	WH_BIND( c->m );
+	const wh_model* m = c->m;
+	const wh_hparams& hp = m->hp;
+	const int d = hp.n_text_state;
+	if( nMax > AL_MAX_ROWS || nMax > hp.n_text_ctx || (int64_t)batch * nMax > c->pinTokenCap() ) { setError( "score_tokens: too many tokens per window" ); return WH_E_BOUNDS; }
+	if( 3ll * batch > wh_context::PIN_WINDOWS ) { setError( "score_tokens: too many windows for one call" ); return WH_E_BOUNDS; }
+	// per window: where its rows begin among the gathered ones
+	std::vector<int32_t> off( (size_t)batch );
+	int64_t rowsScored = 0;
+	for( int b = 0; b < batch; b++ )
+	{
+		const int len = lens[ b ], first = firstScored[ b ];
+		if( len < 2 || len > nMax ) { setError( "score_tokens: a window's length is outside [2, nMax]" ); return WH_E_INVALIDARG; }
+		if( first < 1 || first >= len ) { setError( "score_tokens: a window's first scored entry is outside [1, its length)" ); return WH_E_INVALIDARG; }
+		WH_CHECK( checkTokens( hp, tokens + (size_t)b * nMax, len, "score_tokens" ) );
+		off[ (size_t)b ] = (int32_t)rowsScored;
+		rowsScored += len - first;
+	}
+	hipStream_t st = c->stream;
+	// buffers of the feature: first use, grown to the largest call (never part of a captured graph). The logits hold one chunk of rows.
+	const int64_t rowsAll = (int64_t)batch * nMax;
+	// (the logits are sized for a whole chunk at once: grown call by call, the doubling of grow() would pass the cap the option sets)
+	const int chunk = std::max( 1, std::min( g_opt.scoreChunkRows, 4096 ) );
+	WH_CHECK( c->grow( c->scoreRows, rowsScored * d, wh_context::DONT_CARE, "scoreRows" ) );
+	WH_CHECK( c->grow( c->scoreLogits, (int64_t)chunk * hp.n_vocab, wh_context::DONT_CARE, "scoreLogits" ) );
+	WH_CHECK( c->grow( c->scoreOut, rowsScored, wh_context::DONT_CARE, "scoreOut" ) );
+	WH_CHECK( c->grow( c->scoreTargets, rowsScored, wh_context::DONT_CARE, "scoreTargets" ) );
+	WH_CHECK( c->grow( c->scoreMeta, 3ll * batch, wh_context::DONT_CARE, "scoreMeta" ) );
+
+	// the tokens and the per-window sizes travel through the pinned staging like wh_align_tokens': nothing the copies read dies with an early return
+	int32_t* const stTok = c->pinTokens();
+	WH_HIP( hipStreamSynchronize( st ) );	  // the staging may still be read by an earlier enqueue
+	for( int b = 0; b < batch; b++ )
+		for( int i = 0; i < nMax; i++ ) stTok[ (size_t)b * nMax + i ] = i < lens[ b ] ? tokens[ (size_t)b * nMax + i ] : 0;
+	WH_HIP( hipMemcpyAsync( c->tokensDev, stTok, sizeof( int32_t ) * rowsAll, hipMemcpyHostToDevice, st ) );
+	{
+		int32_t* const stMeta = c->pinned;
+		for( int b = 0; b < batch; b++ )
+		{
+			stMeta[ b ] = firstScored[ b ];
+			stMeta[ batch + b ] = lens[ b ];
+			stMeta[ 2 * batch + b ] = off[ (size_t)b ];
+		}
+		WH_HIP( hipMemcpyAsync( c->scoreMeta, stMeta, sizeof( int32_t ) * 3 * (size_t)batch, hipMemcpyHostToDevice, st ) );
+	}
+
+	// one teacher-forced pass of the multi-token decoder graph; the hook ends it behind the final LayerNorm of all rows
+	c->scoreHook = true;
+	const int rcGraph = decodeGraph( c, batch, nMax, 0, false );
+	c->scoreHook = false;
+	WH_CHECK( rcGraph );
+
+	WH_CHECK( profiled( c, KC_SAMPLE, 0.0, 4.0 * rowsScored * d,
+		[ & ]() { return launchGatherScoreRows( c->dxn, c->tokensDev, c->scoreMeta, batch, nMax, d, c->scoreRows, c->scoreTargets, st ); } ) );
+	// The vocabulary product in chunks of rows, each followed by its reduction. Always the M-tiled kernel (the choice decodeGraph makes beyond 128 sequences): its
+	// sums do not depend on how many rows a launch has, so the records are the same bits whatever the chunk size -- the decode products pick a kernel by row count.
+	for( int64_t r0 = 0; r0 < rowsScored; r0 += chunk )
+	{
+		const int rows = (int)std::min<int64_t>( chunk, rowsScored - r0 );
+		GemmArgs g = plainGemm( c->scoreRows + r0 * d, m->at<f16>( m->L.te ), rows, hp.n_vocab, d );
+		g.epi = EPI_F32; g.out32 = c->scoreLogits; g.ldc = hp.n_vocab;
+		WH_CHECK( gemmP( c, g, false, false ) );	  // (accounted under the tiled products' class, which nothing else of a decoder pass uses: wh_profile_read splits the call)
+		WH_CHECK( profiled( c, KC_SAMPLE, 20.0 * rows * hp.n_vocab, 4.0 * rows * hp.n_vocab,
+			[ & ]() { return launchTokenScores( c->scoreLogits, hp.n_vocab, rows, hp.n_vocab, c->scoreTargets + r0, c->scoreOut + r0, st ); } ) );
+	}
+
+	std::vector<TokenScore> got( (size_t)rowsScored );
+	WH_HIP( hipMemcpyAsync( got.data(), c->scoreOut, sizeof( TokenScore ) * (size_t)rowsScored, hipMemcpyDeviceToHost, st ) );
+	WH_HIP( hipStreamSynchronize( st ) );
+	memset( outHost, 0, sizeof( wh_token_score ) * (size_t)rowsAll );
+	for( int b = 0; b < batch; b++ )
+		for( int i = firstScored[ b ]; i < lens[ b ]; i++ )
+		{
+			const TokenScore& s = got[ (size_t)off[ (size_t)b ] + (size_t)( i - firstScored[ b ] ) ];
+			outHost[ (size_t)b * nMax + i ] = wh_token_score{ s.logprob, s.bestLogprob, s.best, s.rank };
+		}
+	return 0;
+}
+
 }	// extern "C"

@@ -239,7 +239,7 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 			const double bytes = 2.0 * 3.0 * d * d + 4.0 * M * d + 2.0 * 2.0 * M * ( keys - 1 ) * d + 2.0 * 2.0 * M * d + 2.0 * M * d;
 			const double flops = 2.0 * M * 3.0 * d * d + 4.0 * M * keys * d;
 			WH_CHECK( profiled( c, KC_SELF_BLOCK, flops, bytes, [ & ]() { return launchSelfBlockDec( a, st ); } ) );
-			if( il == 0 && !devState && !c->alignHook )
+			if( il == 0 && !devState && !c->alignHook && !c->scoreHook )
 			{
 				WH_CHECK( capture( c, c->capDecKqvSelf, c->dattn, (int64_t)M * d, (int64_t)c->maxRows * d ) );	 // "dec-KQV" (self)
 				c->capDecRows = M;
@@ -264,7 +264,7 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 			a.causal = 1; a.nPast = nPast; a.parityThreads = parity; a.nPastDev = nPastDev;
 			if( devState ) a.nKeys = hp.n_text_ctx;	  // upper bound for the argument check; the kernel reads the real value
 			WH_CHECK( attnDecP( c, a, devState ? c->profKeysHint : -1 ) );
-			if( il == 0 && !devState && !c->alignHook )
+			if( il == 0 && !devState && !c->alignHook && !c->scoreHook )
 			{
 				WH_CHECK( capture( c, c->capDecKqvSelf, c->dattn, (int64_t)M * d, (int64_t)c->maxRows * d ) );	 // "dec-KQV" (self)
 				c->capDecRows = M;
@@ -314,7 +314,7 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 				a.qW = m->at<f16>( e.wcq ); a.qB = m->at<float>( e.bcq ); a.qScale = kqScale;
 			}
 			WH_CHECK( attnDecP( c, a ) );
-			if( il == 0 && !devState && !c->alignHook ) WH_CHECK( capture( c, c->capDecKqvCross, c->dattn, (int64_t)M * d, (int64_t)c->maxRows * d ) );	  // "dec-KQV" (cross)
+			if( il == 0 && !devState && !c->alignHook && !c->scoreHook ) WH_CHECK( capture( c, c->capDecKqvCross, c->dattn, (int64_t)M * d, (int64_t)c->maxRows * d ) );	  // "dec-KQV" (cross)
 		}
 		{
 			GemmArgs g = plainGemm( c->dattn, m->at<f16>( e.wco ), M, d, d );
@@ -338,6 +338,8 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 	// and then consumes just the last one, ContextImpl.cpp:159-169). The norm stays a separate launch here: fusing it
 	// into the 3242 workgroups of the vocabulary product would re-read the rows 3242 times.
 	WH_CHECK( lnP( c, c->dx, m->at<float>( L.decLnW ), m->at<float>( L.decLnB ), c->dxn, M, d, true ) );
+	// wh_score_tokens: all M normalised rows are the result; the caller gathers the ones it scores and runs the vocabulary product on them
+	if( c->scoreHook ) return 0;
 	// prompts of different lengths (rows right-padded to nTokens): the row of every sequence's own last token moves to where the
 	// product below reads, row nTokens - 1 of the sequence
 	if( c->raggedLastPos && nTokens > 1 ) WH_CHECK( launchGatherLastRows( c->dxn, c->raggedLastPos, batch, nTokens, d, st ) );

@@ -95,6 +95,10 @@ namespace wh
 		int resampleLdsPhases = 853; // "resample_lds_phases": resampleKernel stages the taps of all L phases in LDS (K in chunks) up to this many phases and reads them from global memory
 									 // beyond; 0 = always from global memory (the same sums in the same order either way). 853 = the most phases of which 9 taps each fit the 30 KiB
 		int selfWaveMinRows = 32;	 // "self_wave_min_rows": single-token causal self-attention as its own launch: a wave per (sequence, head) beyond this many sequences
+		int scoreChunkRows = 320;	 // "score_chunk_rows": wh_score_tokens: the most rows of logits one vocabulary product forms before tokenScoreKernel reduces them (the feature's
+									 // logits buffer: 320 x 51866 floats = 63.3 MiB); the records do not depend on it
+		int scoreRegs = 1;			 // "score_regs": tokenScoreKernel: 1 = the row in registers up to SC_PER * 1024 = 52224 columns (one read), the two-read form beyond;
+									 // 0 = the two-read form always (the same bits)
 	};
 	extern Options g_opt;
 
@@ -321,6 +325,17 @@ namespace wh
 	// largest, ties to the lower. launchLangGather: the same from probabilities that exist already (the exact mode's).
 	int launchLangProbs( const float* logits, long long rowStride, int rows, int nVocab, int tokenSot, int nLang, float* langP, int* best, hipStream_t stream );
 	int launchLangGather( const float* probs, long long rowStride, int rows, int nVocab, int tokenSot, int nLang, float* langP, int* best, hipStream_t stream );
+	// the score of a given token under a row of logits (wh_score_tokens, wh_op_token_scores): out[ row ] from row `row` of logits (rowStride floats apart) and
+	// targets[ row ] (DEVICE, inside [0, nVocab): the callers check on the host). The layout is wh_token_score's.
+	struct TokenScore
+	{
+		float logprob, bestLogprob;
+		int best, rank;
+	};
+	int launchTokenScores( const float* logits, long long rowStride, int rows, int nVocab, const int* targets, TokenScore* out, hipStream_t stream );
+	// wh_score_tokens: rows first[ b ] - 1 .. len[ b ] - 2 of window b of x [windows][nMax][d] -> rows off[ b ] .. of dst, targets[ row ] = the token that row predicts
+	// (tokens [windows][nMax]); meta = [ first | len | off ] x windows, DEVICE, checked by the caller
+	int launchGatherScoreRows( const f16* x, const int* tokens, const int* meta, int windows, int nMax, int d, f16* dst, int* targets, hipStream_t stream );
 	// ContextImpl::sampleBest on the device
 	int launchSampleBest( const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot,
 		int forceTimestamp, int isInitial, TokenData* out, hipStream_t stream );

@@ -449,7 +449,28 @@ int wh_op_lang_probs( void* stream, const float* logits, int rows, int nVocab, i
 	return launchLangProbs( logits, nVocab, rows, nVocab, tokenSot, nLang, langP, best, (hipStream_t)stream );
 }
 
-static bool tokenArgsOk( const float* probs, const wh_token_data* out, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot )
+int wh_op_token_scores( void* stream, const float* logits, int64_t rowStride, int rows, int nVocab, const int32_t* targetsDev, wh_token_score* outDev )
+{
+	static_assert( sizeof( wh_token_score ) == sizeof( TokenScore ) && sizeof( wh_token_score ) == 16, "token score layout" );
+	if( !logits || !targetsDev || !outDev || rows < 1 || nVocab < 1 || rowStride < nVocab )
+	{
+		setError( "token_scores: null pointer, rows < 1, empty vocabulary or rowStride < nVocab" );
+		return WH_E_INVALIDARG;
+	}
+	// the targets index the row on the device: checked here, before any launch
+	std::vector<int32_t> t( (size_t)rows );
+	WH_HIP( hipMemcpyAsync( t.data(), targetsDev, sizeof( int32_t ) * (size_t)rows, hipMemcpyDeviceToHost, (hipStream_t)stream ) );
+	WH_HIP( hipStreamSynchronize( (hipStream_t)stream ) );
+	for( int r = 0; r < rows; r++ )
+		if( t[ (size_t)r ] < 0 || t[ (size_t)r ] >= nVocab )
+		{
+			setError( "token_scores: target " + std::to_string( t[ (size_t)r ] ) + " of row " + std::to_string( r ) + " is outside [0, " + std::to_string( nVocab ) + ")" );
+			return WH_E_INVALIDARG;
+		}
+	return launchTokenScores( logits, rowStride, rows, nVocab, targetsDev, (TokenScore*)outDev, (hipStream_t)stream );
+}
+
+static bool tokenArgsOk(const float* probs, const wh_token_data* out, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot )
 {
 	return probs && out && rows >= 1 && nVocab >= 1 && tokenBeg >= 1 && tokenBeg < nVocab && tokenSot >= 0 && tokenSot < tokenBeg && tokenSolm >= 0 &&
 		tokenSolm < tokenBeg && tokenNot >= 0 && tokenNot < tokenBeg;

@@ -226,6 +226,13 @@ struct wh_context
 	int *alignFrames = nullptr, *alignMeta = nullptr;
 	int alignBatch = 0, alignNMax = 0, alignLayer0 = 0, alignLayer1 = 0;	   // what the last call left for wh_debug_read
 	const struct AlignHook* alignHook = nullptr;   // set around the pass of wh_align_tokens only
+	// wh_score_tokens (align.hip; all allocated on first use, outside every captured graph): the gathered rows of the normalised activations, the logits of one
+	// chunk of them, the targets and records of all of them, the call's per-window sizes
+	f16* scoreRows = nullptr;
+	float* scoreLogits = nullptr;
+	TokenScore* scoreOut = nullptr;
+	int *scoreTargets = nullptr, *scoreMeta = nullptr;
+	bool scoreHook = false;	   // set around the pass of wh_score_tokens only: the multi-token decoder graph ends behind the final LayerNorm of all its rows
 	TokenData* beamCand = nullptr;			   // beam search: [maxSeq][8] candidates (allocated on first use)
 	f16 *selfKScratch = nullptr, *selfVScratch = nullptr;	   // beam search: the copy a cache reorder goes through (allocated on first use)
 	// beam search on the device (wh_beam_window_*): per-window rules and state, the records of every step, the parents a step's reorder reads

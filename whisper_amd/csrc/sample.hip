@@ -169,6 +169,100 @@ namespace wh
 			if( threadIdx.x == 0 ) best[ blockIdx.x ] = ( a.i < 0 || a.i >= nLang ) ? 0 : a.i;
 		}
 
+		// ---- the score of a GIVEN token under a row of logits (wh_score_tokens; DESIGN.md section 7 "Scoring", restated in float64 by tests/token_score_ref.py) ----
+		// Per row and target t: the row maximum m and the lowest id that has it, s = sum exp( x - m ) in double (FP32 expf per term, -inf adds 0), and
+		// rank = #{ x[ j ] > x[ t ] } + #{ j < t : x[ j ] == x[ t ] }; logprob = x[ t ] - m - ln s and bestLogprob = -ln s in double, rounded once. True logarithms:
+		// nothing of the FP16 exp table, whose e is 0 for an unlikely token. REG: the row in registers between the two sweeps like langProbsKernel's (one read with
+		// consecutive lanes on consecutive floats, cols <= SC_PER * 1024); otherwise the row is read twice. Either way thread t visits columns t, t + 1024, ... in
+		// that order and the three reductions are the same code, so the two forms give the same bits. 16 bytes written per row.
+		struct ScoreAcc
+		{
+			double s = 0.0;
+			int rank = 0, best = 0x7fffffff;
+			__device__ __forceinline__ void feed( float v, int c, float m, float xt, int t )
+			{
+				s += ( v == -INFINITY ) ? 0.0 : (double)expf( v - m );
+				rank += ( v > xt || ( v == xt && c < t ) ) ? 1 : 0;
+				best = ( v == m && c < best ) ? c : best;
+			}
+		};
+		template<bool REG>
+		__global__ void __launch_bounds__( 1024 ) tokenScoreKernel( const float* __restrict__ in, long long rowStride, int cols, const int* __restrict__ targets,
+			TokenScore* __restrict__ out )
+		{
+			__shared__ float shf[ 16 ];
+			__shared__ double shd[ 16 ];
+			__shared__ int shRank[ 16 ], shBest[ 16 ];
+			const float* const x = in + (long long)blockIdx.x * rowStride;
+			// (the entry points have checked the targets on the host; an id read from device memory is clamped into the row all the same)
+			const int t = min( max( targets[ blockIdx.x ], 0 ), cols - 1 );
+			const float xt = x[ t ];	 // a broadcast load
+			ScoreAcc a;
+			float m;
+			if constexpr( REG )
+			{
+				float v[ SC_PER ];
+				m = blockMax<16>( loadRowReg<SC_PER, false>( x, cols, 1.0f, v ), shf );
+	#pragma unroll
+				for( int i = 0; i < SC_PER; i++ ) a.feed( v[ i ], threadIdx.x + 1024 * i, m, xt, t );	  // (-inf beyond the row's end: adds 0, outranks nothing, never the maximum)
+			}
+			else
+			{
+				m = -INFINITY;
+				for( int c = threadIdx.x; c < cols; c += 1024 ) m = fmaxf( m, x[ c ] );
+				m = blockMax<16>( m, shf );
+				for( int c = threadIdx.x; c < cols; c += 1024 ) a.feed( x[ c ], c, m, xt, t );
+			}
+			// the three reductions behind one barrier; the sum wave by wave in blockSumD's order
+			a.s = waveReduceSumD( a.s );
+	#pragma unroll
+			for( int o = 32; o > 0; o >>= 1 )
+			{
+				a.rank += __shfl_xor( a.rank, o, 64 );
+				a.best = min( a.best, __shfl_xor( a.best, o, 64 ) );
+			}
+			if( ( threadIdx.x & 63 ) == 0 )
+			{
+				const int w = threadIdx.x >> 6;
+				shd[ w ] = a.s; shRank[ w ] = a.rank; shBest[ w ] = a.best;
+			}
+			__syncthreads();
+			if( threadIdx.x == 0 )
+			{
+				double s = shd[ 0 ];
+				int rank = shRank[ 0 ], best = shBest[ 0 ];
+				for( int i = 1; i < 16; i++ )
+				{
+					s += shd[ i ];
+					rank += shRank[ i ];
+					best = min( best, shBest[ i ] );
+				}
+				const double lnS = log( s );
+				TokenScore r;
+				r.logprob = (float)( ( (double)xt - (double)m ) - lnS );
+				r.bestLogprob = (float)( -lnS );
+				r.best = ( best < 0 || best >= cols ) ? 0 : best;	  // (NaN compares false everywhere and leaves the sentinel)
+				r.rank = rank;
+				out[ blockIdx.x ] = r;
+			}
+		}
+
+		// wh_score_tokens: the rows of the normalised decoder activations that predict a scored token, gathered compactly, and the tokens they are scored against.
+		// Window b's rows first[ b ] - 1 .. len[ b ] - 2 of x [windows][nMax][d] go to rows off[ b ] .. of dst; targets[ that row ] = tokens[ b ][ i + 1 ].
+		// meta: [ first | len | off ] x windows. One workgroup per (row i, window b), 16 bytes per thread and trip; d % 8 == 0.
+		__global__ void __launch_bounds__( 128 ) gatherScoreRowsKernel( const f16* __restrict__ x, const int* __restrict__ tokens, const int* __restrict__ meta, int windows,
+			int nMax, int d, f16* __restrict__ dst, int* __restrict__ targets )
+		{
+			const int b = blockIdx.y, i = blockIdx.x;
+			const int first = meta[ b ], len = meta[ windows + b ], off = meta[ 2 * windows + b ];
+			if( i < first - 1 || i > len - 2 ) return;
+			const long long src = (long long)b * nMax + i, row = (long long)off + ( i - ( first - 1 ) );
+			const uint4* const s = (const uint4*)( x + src * d );
+			uint4* const o = (uint4*)( dst + row * d );
+			for( int k = threadIdx.x; k < d / 8; k += 128 ) o[ k ] = s[ k ];
+			if( threadIdx.x == 0 ) targets[ row ] = tokens[ src + 1 ];
+		}
+
 		// ---- logits row -> table softmax -> sampleBest in ONE kernel, the row held in registers -----------------------
 		// Used by the captured decode step: no host round trip between the logits product and the next token. Same
 		// arithmetic as softMaxRows followed by sampleBestKernel (p = exp16(x - max) * float(1 / double sum)).
@@ -734,6 +828,26 @@ namespace wh
 			return -1;
 		}
 		hipLaunchKernelGGL( langProbsKernel, dim3( rows ), dim3( 1024 ), 0, stream, logits, rowStride, nVocab, tokenSot, nLang, langP, best );
+		WH_HIP( hipGetLastError() );
+		return 0;
+	}
+
+	int launchTokenScores( const float* logits, long long rowStride, int rows, int nVocab, const int* targets, TokenScore* out, hipStream_t stream )
+	{
+		if( !logits || !targets || !out || rows < 1 || nVocab < 1 || rowStride < nVocab ) { setError( "tokenScores: bad argument" ); return -1; }
+		// option score_regs: the row in registers where it fits (one read), two reads beyond and with the option off; the same bits
+		if( g_opt.scoreRegs && nVocab <= SC_PER * 1024 )
+			hipLaunchKernelGGL( tokenScoreKernel<true>, dim3( rows ), dim3( 1024 ), 0, stream, logits, rowStride, nVocab, targets, out );
+		else
+			hipLaunchKernelGGL( tokenScoreKernel<false>, dim3( rows ), dim3( 1024 ), 0, stream, logits, rowStride, nVocab, targets, out );
+		WH_HIP( hipGetLastError() );
+		return 0;
+	}
+
+	int launchGatherScoreRows( const f16* x, const int* tokens, const int* meta, int windows, int nMax, int d, f16* dst, int* targets, hipStream_t stream )
+	{
+		if( !x || !tokens || !meta || !dst || !targets || windows < 1 || windows > 65535 || nMax < 2 || d < 8 || ( d % 8 ) != 0 ) { setError( "gatherScoreRows: bad argument" ); return -1; }
+		hipLaunchKernelGGL( gatherScoreRowsKernel, dim3( nMax - 1, windows ), dim3( 128 ), 0, stream, x, tokens, meta, windows, nMax, d, dst, targets );
 		WH_HIP( hipGetLastError() );
 		return 0;
 	}

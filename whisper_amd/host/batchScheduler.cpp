@@ -27,6 +27,7 @@
 #include "batchTimestampRules.h"
 #include "decodeFallback.h"
 #include "languageDetect.h"
+#include "scoreRequest.h"
 #include "results.h"
 #include <algorithm>
 #include <chrono>
@@ -45,6 +46,8 @@ namespace Whisper
 	pfnBatchSuppress g_batchSuppress = nullptr;
 	// ... and for the timestamp rules (batchTimestampRules.h)
 	pfnBatchTimestampRules g_batchTimestampRules = nullptr;
+	// ... and to the scorer of given transcripts (scoreRequest.h)
+	pfnBatchScorer g_batchScorer = nullptr;
 
 	namespace
 	{
@@ -759,6 +762,86 @@ namespace Whisper
 					if( g.gpu ) wh_context_destroy( g.gpu );
 				owner->Release();
 			}
+			// Whisper::scoreBatch: the requests that pass their checks (scoreRequest.h), up to maxSlots per pass in request order, on the first group's context.
+			// One pass = the clips' spectrograms on the loader's stream, one encoder batch at seek 0 with the full audio context, one call of the scorer.
+			HRESULT score( const sScoreRequest* requests, uint32_t count, sTokenScore* const* scores, HRESULT* perRequest )
+			{
+				if( count && ( !requests || !scores ) ) return E_POINTER;
+				if( !g_batchScorer )
+				{
+					logError( "scoreBatch: this build of the scheduler was not given the device's scorer" );
+					return E_NOTIMPL;
+				}
+				const score::Limits lim{ model->hp.n_vocab, model->vocab.token_eot, model->vocab.token_not, model->hp.n_text_ctx };
+				std::vector<HRESULT> status( count, S_OK );
+				std::vector<score::Row> rows( count );
+				std::vector<int64_t> samples( count, 0 );
+				for( uint32_t i = 0; i < count; i++ )
+				{
+					const sScoreRequest& r = requests[ i ];
+					HRESULT& hr = status[ i ];
+					if( !r.buffer || !r.buffer->getPcmMono() || !scores[ i ] ) hr = E_POINTER;
+					if( SUCCEEDED( hr ) ) hr = score::clipRange( r.buffer->countSamples(), r.firstSample, r.countSamples, samples[ i ] );
+					if( SUCCEEDED( hr ) ) hr = score::buildRow( lim, r.prompt, r.promptCount, r.tokens, r.count, r.flags, rows[ i ] );
+					if( SUCCEEDED( hr ) && rows[ i ].align )
+					{
+						logError( "scoreBatch: forced alignment (flag 1) is not available in a batch runner; use scoreTokens" );
+						hr = E_NOTIMPL;
+					}
+				}
+				HRESULT first = S_OK;
+				auto fail = [ & ]( uint32_t i, HRESULT hr ) { status[ i ] = hr; };
+				const std::vector<std::vector<uint32_t>> passes = score::packPasses( status, maxSlots );
+				if( !passes.empty() )
+				{
+					if( groups.empty() )
+					{
+						Group g;
+						CHECK_WH( wh_context_create( model->gpu, (int)maxSlots, nullptr, &g.gpu ) );
+						groups.push_back( std::move( g ) );
+					}
+					if( !shared.loader ) CHECK_WH( wh_context_create( model->gpu, 1, nullptr, &shared.loader ) );
+					CHECK_WH( wh_context_set_audio_ctx( groups[ 0 ].gpu, 0 ) );
+				}
+				for( const std::vector<uint32_t>& pass : passes )
+				{
+					wh_context* const gpu = groups[ 0 ].gpu;
+					std::vector<void*> held;
+					std::vector<wh_mel_window> windows( pass.size() );
+					HRESULT hr = S_OK;
+					for( size_t s = 0; s < pass.size() && SUCCEEDED( hr ); s++ )
+					{
+						const sScoreRequest& r = requests[ pass[ s ] ];
+						const int64_t n = samples[ pass[ s ] ], melLen = n / 160;
+						void *pcmDev = nullptr, *melDev = nullptr;
+						hr = shared.pool.acquire( n * 4, pcmDev );
+						if( SUCCEEDED( hr ) ) held.push_back( pcmDev );
+						if( SUCCEEDED( hr ) ) hr = shared.pool.acquire( melLen * model->hp.n_mels * 4, melDev );
+						if( SUCCEEDED( hr ) ) held.push_back( melDev );
+						int64_t got = 0;
+						if( SUCCEEDED( hr ) && ( 0 != wh_buffer_upload_async( shared.loader, pcmDev, r.buffer->getPcmMono() + r.firstSample, n * 4 ) ||
+							0 != wh_mel_spectrogram( shared.loader, (const float*)pcmDev, n, (float*)melDev, &got ) ) )
+							hr = hrFromStatus( -1, "scoreBatch: spectrogram" );
+						windows[ s ] = wh_mel_window{ (const float*)melDev, melLen, 0, 0 };
+					}
+					const score::PassArgs a = score::packTokens( pass, rows );
+					std::vector<wh_token_score> recs( pass.size() * (size_t)a.nMax );
+					if( SUCCEEDED( hr ) && 0 != wh_context_synchronize( shared.loader ) ) hr = hrFromStatus( -1, "scoreBatch: wh_context_synchronize" );
+					if( SUCCEEDED( hr ) ) { const int rc = wh_encode_windows( gpu, windows.data(), (int)pass.size() ); if( rc ) hr = hrFromStatus( rc, "scoreBatch: wh_encode_windows" ); }
+					if( SUCCEEDED( hr ) ) { const int rc = g_batchScorer( gpu, (int)pass.size(), a.tokens.data(), a.lens.data(), a.first.data(), a.nMax, recs.data() ); if( rc ) hr = hrFromStatus( rc, "scoreBatch: the scorer" ); }
+					wh_context_synchronize( gpu );	  // the encoder has read the spectrograms before their buffers go back to the pool
+					for( void* p : held ) shared.pool.release( p );
+					if( SUCCEEDED( hr ) ) score::unpackRecords( pass, rows, a, recs.data(), scores );
+					else
+						for( uint32_t r : pass ) fail( r, hr );
+				}
+				for( uint32_t i = 0; i < count; i++ )
+				{
+					if( perRequest ) perRequest[ i ] = status[ i ];
+					if( FAILED( status[ i ] ) && SUCCEEDED( first ) ) first = status[ i ];
+				}
+				return first;
+			}
 			HRESULT run( const sFullParams& params, const sBatchStream* streams, uint32_t count, iTranscribeResult** results, HRESULT* perStream ) override
 			{
 				if( !results || ( count && !streams ) ) return E_POINTER;
@@ -823,6 +906,17 @@ namespace Whisper
 		};
 	}	// namespace
 
+	HRESULT runnerScore( iBatchRunner* runner, const sScoreRequest* requests, uint32_t count, sTokenScore* const* scores, HRESULT* perRequest )
+	{
+		if( !runner ) return E_POINTER;
+		BatchRunner* const r = dynamic_cast<BatchRunner*>( runner );
+		if( !r )
+		{
+			logError( "scoreBatch: not a runner of this library's createBatchRunner" );
+			return E_INVALIDARG;
+		}
+		return r->score( requests, count, scores, perRequest );
+	}
 	HRESULT createBatchRunner( iModel* model, const sBatchSetup* setup, iBatchRunner** pp )
 	{
 		if( !model || !pp ) return E_POINTER;

@@ -15,6 +15,8 @@
 #include <atomic>
 #include <limits>
 #include <string>
+#include <fstream>
+#include <iterator>
 #include <thread>
 #include <vector>
 #include "subtitles.h"
@@ -367,6 +369,44 @@ static int formatFile( const char* segFile, const std::string& prefix )
 	return 0;
 }
 
+// --score: the transcript of one input, read from a text file, scored against it (Whisper::scoreTokens); with --align also aligned
+static int scoreInput( iModel* model, iContext* context, iMediaFoundation* media, const std::string& input, const std::string& textFile, const std::string& language,
+	bool translate, bool align )
+{
+	std::string text;
+	{
+		std::ifstream f( textFile, std::ios::binary );
+		if( !f ) { fprintf( stderr, "error: cannot read '%s'\n", textFile.c_str() ); return 11; }
+		text.assign( std::istreambuf_iterator<char>( f ), std::istreambuf_iterator<char>() );
+		while( !text.empty() && ( text.back() == '\n' || text.back() == '\r' ) ) text.pop_back();
+	}
+	std::vector<int> tokens;
+	HRESULT hr = model->tokenize( text.c_str(), []( const int* p, int n, void* pv ) { if( n > 0 ) ( (std::vector<int>*)pv )->assign( p, p + n ); }, &tokens );
+	if( FAILED( hr ) || tokens.empty() ) { printFailure( "failed to tokenize the transcript", FAILED( hr ) ? hr : E_INVALIDARG ); return 11; }
+	whisper_token prompt[ 8 ];
+	uint32_t nPrompt = 8;
+	hr = makeSotSequence( model, makeLanguageKey( language.c_str() ), translate, false, prompt, &nPrompt );
+	if( FAILED( hr ) ) { printFailure( "failed to build the prompt", hr ); return 11; }
+	ComLight::CComPtr<iAudioBuffer> buffer;
+	hr = media->loadAudioFile( input.c_str(), false, &buffer );
+	if( FAILED( hr ) ) { printFailure( "Unable to load audio", hr ); return 10; }
+	std::vector<sTokenScore> scores( tokens.size() + 1 );
+	const sScoreRequest request{ buffer, 0, 0, prompt, nPrompt, tokens.data(), (uint32_t)tokens.size(), align ? 1u : 0u };
+	hr = scoreTokens( context, request, scores.data() );
+	if( FAILED( hr ) ) { printFailure( "Unable to score the transcript", hr ); return 10; }
+	double sum = 0;
+	for( size_t i = 0; i < scores.size(); i++ )
+	{
+		const sTokenScore& s = scores[ i ];
+		const char* const str = i < tokens.size() ? model->stringFromToken( tokens[ i ] ) : "[_EOT_]";
+		if( align ) printf( "[%8.2f --> %8.2f]  ", (double)s.time.begin.ticks * 1e-7, (double)s.time.end.ticks * 1e-7 );
+		printf( "%10.4f  %6d  %s\n", s.logprob, (int)s.rank, str ? str : "" );
+		sum += s.logprob;
+	}
+	printf( "%s: %zu tokens, sum_logprob %.4f, avg_logprob %.4f\n", input.c_str(), scores.size(), sum, sum / (double)scores.size() );
+	return 0;
+}
+
 int main( int argc, char** argv )
 {
 	if( argc == 3 && !strcmp( argv[ 1 ], "--format-sample" ) ) return formatSample( argv[ 2 ] );
@@ -387,7 +427,10 @@ int main( int argc, char** argv )
 	// window the model calls silent is dropped; -tpi / -lpt / -et / -nth N (whisper.cpp's names) set temperatureInc, logprobThold, entropyThold, noSpeechThold
 	// -sns / --suppress-nst (the same way; whisper.cpp's names): Whisper::setSuppressedTokens with the model's non-speech set (getNonSpeechTokens)
 	// -tsr / --timestamp-rules (the same way): Whisper::setTimestampRules, openai-whisper's ApplyTimestampRules on the device
+	// --score FILE (the same way): instead of transcribing, Whisper::scoreTokens of the text in FILE against every input (a clip of 1 to 30 s): one line per
+	// token -- its time with --align (forced alignment), log-probability, rank, text -- and a summary line
 	bool align = false, useFallback = false, suppressNst = false, timestampRules = false;
+	std::string scoreFile;
 	sDecodingFallback fallbackParams;
 	{
 		int kept = 1;
@@ -398,6 +441,11 @@ int main( int argc, char** argv )
 			else if( !strcmp( argv[ i ], "--fallback" ) ) useFallback = true;
 			else if( !strcmp( argv[ i ], "-sns" ) || !strcmp( argv[ i ], "--suppress-nst" ) ) suppressNst = true;
 			else if( !strcmp( argv[ i ], "-tsr" ) || !strcmp( argv[ i ], "--timestamp-rules" ) ) timestampRules = true;
+			else if( !strcmp( argv[ i ], "--score" ) )
+			{
+				if( i + 1 >= argc ) { fprintf( stderr, "error: --score needs a file\n" ); return 2; }
+				scoreFile = argv[ ++i ];
+			}
 			else if( !strcmp( argv[ i ], "-tpi" ) ) value = &fallbackParams.temperatureInc;
 			else if( !strcmp( argv[ i ], "-lpt" ) ) value = &fallbackParams.logprobThold;
 			else if( !strcmp( argv[ i ], "-et" ) ) value = &fallbackParams.entropyThold;
@@ -480,6 +528,12 @@ int main( int argc, char** argv )
 			o.language = "en";
 			o.translate = false;
 			fprintf( stderr, "main: WARNING: model is not multilingual, ignoring language and translation options\n" );
+		}
+
+		if( !scoreFile.empty() )
+		{
+			if( const int rc = scoreInput( model, context, media, input, scoreFile, o.language, o.translate, align ) ) return rc;
+			continue;
 		}
 
 		sFullParams p;

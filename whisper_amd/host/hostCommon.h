@@ -157,6 +157,11 @@ namespace Whisper
 		virtual const std::shared_ptr<LoadedModel>& loaded() const = 0;
 	};
 
+	// Whisper::scoreTokens / scoreBatch (scoreTranscripts.cpp) on the objects that own the device contexts. contextScoreClip: the clip's spectrogram as runFull makes
+	// it, one window at seek 0 with the full audio context, wh_score_tokens on the row (recs: len records) and, with frames != nullptr, wh_align_tokens on the same
+	// row (frames: len numbers). E_INVALIDARG for a context of another library. runnerScore: the checks, the passes and the device work of scoreBatch.
+	HRESULT contextScoreClip( iContext* context, const float* pcm, int64_t nSamples, const int32_t* tokens, int32_t len, int32_t firstScored, wh_token_score* recs, int32_t* frames );
+	HRESULT runnerScore( iBatchRunner* runner, const sScoreRequest* requests, uint32_t count, sTokenScore* const* scores, HRESULT* perRequest );
 	HRESULT createContextImpl( const std::shared_ptr<LoadedModel>& model, iModel* owner, iContext** pp );
 	HRESULT createModelImpl( const std::shared_ptr<LoadedModel>& model, iModel** pp );
 	HRESULT createAudioBuffer( std::vector<float>&& mono, std::vector<float>&& stereo, iAudioBuffer** pp );

@@ -13,6 +13,7 @@
 #include "batchSuppress.h"
 #include "batchTimestampRules.h"
 #include "languageDetect.h"
+#include "scoreRequest.h"
 #include "results.h"
 #include "wavFormat.h"
 #include <algorithm>
@@ -228,6 +229,31 @@ namespace Whisper
 				CHECK_WH( wh_context_set_suppress( gpu, ids, (int)count ) );
 				if( gpuBeam ) CHECK_WH( wh_context_set_suppress( gpuBeam, ids, (int)count ) );
 				suppressIds.assign( ids, ids + count );
+				return S_OK;
+			}
+			// Whisper::scoreTokens: the clip's spectrogram (normalised on its own maximum, like runFull's of those samples), one window at seek 0 with the model's
+			// full audio context, then the teacher-forced pass; frames != nullptr: the same row through wh_align_tokens with the keys runFull's aligner takes
+			HRESULT scoreClip( const float* pcm, int64_t n, const int32_t* tokens, int32_t len, int32_t firstScored, wh_token_score* recs, int32_t* frames )
+			{
+				const wh_hparams& hp = model->hp;
+				const int64_t melLen = n / 160;
+				mel = MelSource{};
+				mel.length = melLen;
+				CHECK( ensureBuffer( pcmDev, pcmCapacity, n * 4 ) );
+				CHECK( ensureBuffer( melDev, melCapacity, melLen * hp.n_mels * 4 ) );
+				CHECK_WH( wh_buffer_upload( gpu, pcmDev, pcm, n * 4 ) );
+				int64_t got = 0;
+				CHECK_WH( wh_mel_spectrogram( gpu, (const float*)pcmDev, n, (float*)melDev, &got ) );
+				audioCtx = 0;
+				CHECK_WH( wh_context_set_audio_ctx( gpu, 0 ) );
+				const int32_t off = 0;
+				CHECK_WH( wh_encode( gpu, (const float*)melDev, 1, melLen, melLen * hp.n_mels, &off ) );
+				CHECK_WH( wh_score_tokens( gpu, 1, tokens, &len, &firstScored, len, recs ) );
+				if( frames )
+				{
+					const int32_t nKeys = (int32_t)std::max<int64_t>( 1, std::min<int64_t>( hp.n_audio_ctx, melLen / 2 ) );
+					CHECK_WH( wh_align_tokens( gpu, 1, tokens, &len, &nKeys, len, frames ) );
+				}
 				return S_OK;
 			}
 			HRESULT setTimestampRulesMode( bool on )
@@ -1204,6 +1230,8 @@ namespace Whisper
 	static const bool g_suppressInstalled = ( g_batchSuppress = &wh_context_set_suppress, true );
 	// ... and to the timestamp rules (batchTimestampRules.h)
 	static const bool g_timestampRulesInstalled = ( g_batchTimestampRules = &wh_context_set_timestamp_rules, true );
+	// ... and to the scorer of given transcripts (scoreRequest.h)
+	static const bool g_scorerInstalled = ( g_batchScorer = &wh_score_tokens, true );
 
 	HRESULT createContextImpl( const std::shared_ptr<LoadedModel>& model, iModel* owner, iContext** pp )
 	{
@@ -1260,6 +1288,17 @@ namespace Whisper
 			return E_INVALIDARG;
 		}
 		return c->setTimestampRulesMode( on );
+	}
+	HRESULT contextScoreClip( iContext* context, const float* pcm, int64_t nSamples, const int32_t* tokens, int32_t len, int32_t firstScored, wh_token_score* recs, int32_t* frames )
+	{
+		if( !context || !pcm || !tokens || !recs ) return E_POINTER;
+		ContextImpl* const c = dynamic_cast<ContextImpl*>( context );
+		if( !c )
+		{
+			logError( "scoreTokens: not a context of this library's createContext (a batch runner takes scoreBatch)" );
+			return E_INVALIDARG;
+		}
+		return c->scoreClip( pcm, nSamples, tokens, len, firstScored, recs, frames );
 	}
 	HRESULT getWindowStats( const iContext* context, sWindowStats* stats, uint32_t* count )
 	{
