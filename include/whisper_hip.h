@@ -387,7 +387,7 @@ WH_API int wh_reorder_self_cache( wh_context* c, int batch, const int32_t* paren
  *                           it); rules HOST [windows]; the prompt step, the first ranking (sampleTimestamp( true ) rules) and nSteps ranked steps are
  *                           enqueued. The call WAITS for what the stream holds first (the window's rules and initial state are copied synchronously, and the step
  *                           graph is captured on first use): one host round trip per window, the encoder included; the steps themselves never block. The
- *                           captured graph is keyed on (sequences, width): kernel options set with wh_debug_set_option / _tuning afterwards do not reach it.
+ *                           captured graph is keyed on (sequences, width) and on what the greedy step's is (the parity mode, "a suppressed set is held"): kernel options set with wh_debug_set_option / _tuning afterwards do not reach it.
  *                           forced != 0 in a window's rules: no stop rules, every hypothesis lives (random-weight workloads).
  *   wh_beam_window_continue nSteps more (bounded by n_text_ctx like wh_decode_window_continue). Steps enqueued after a window is done change nothing.
  *   wh_beam_window_status   blocks until everything enqueued has run; the search state of every window: HOST [windows].
@@ -544,6 +544,9 @@ WH_API int wh_profile_read( wh_context* c, wh_profile_entry* out, int cap, int* 
  *          "dec-KQV" / "dec-KQV#2"   decoder layer 0 self / cross attention output of the last wh_decode, [rows][d]
  */
 WH_API int wh_debug_read( wh_context* c, const char* what, int layer, int rows, float* dstHost, int64_t dstCapFloats );
+/* Decode-step graphs the context has captured (instantiated) since it was created, of every kind of step. A recapture costs a blocking +2 to +7 ms and changes
+ * no result, so only this count shows a retention rule that regressed. Host only. */
+WH_API int wh_debug_step_captures( wh_context* c, int* count );
 
 /* Development micro-benchmarks (tools/gemm_probe.py): kind 0 = chain of empty kernels (variant = workgroups), 2 = the same
  * replayed from a hipGraph, 1 = tiled GEMM tile-shape variant on an M x N x K problem. Returns milliseconds per iteration. */

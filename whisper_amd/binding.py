@@ -46,7 +46,7 @@ EXPORTS = [
     "wh_comm_runtime_check", "wh_comm_unique_id", "wh_comm_create", "wh_comm_destroy", "wh_comm_info", "wh_comm_barrier", "wh_comm_create_timeout", "wh_comm_set_timeout", "wh_comm_broadcast_i32", "wh_model_broadcast",
     "wh_context_create", "wh_context_create_hyp", "wh_context_destroy", "wh_context_bind", "wh_context_set_flags", "wh_context_set_audio_ctx", "wh_context_synchronize", "wh_context_memory",
     "wh_buffer_alloc", "wh_buffer_free", "wh_buffer_upload", "wh_buffer_upload_async", "wh_buffer_download",
-    "wh_mel_spectrogram", "wh_encode", "wh_encode_windows", "wh_decode", "wh_sample_best", "wh_beam_candidates", "wh_reorder_self_cache", "wh_beam_window_start", "wh_beam_window_continue", "wh_beam_window_status", "wh_beam_window_records", "wh_decode_greedy", "wh_decode_window_start", "wh_decode_window_finish", "wh_decode_window_continue", "wh_decode_window_fetch", "wh_decode_window_start_ragged", "wh_decode_window_ready", "wh_mel_spectrogram_window", "wh_mel_spectrogram_batch", "wh_profile_enable", "wh_profile_read", "wh_debug_read", "wh_debug_probe", "wh_debug_set_tuning", "wh_debug_set_option", "wh_debug_get_option",
+    "wh_mel_spectrogram", "wh_encode", "wh_encode_windows", "wh_decode", "wh_sample_best", "wh_beam_candidates", "wh_reorder_self_cache", "wh_beam_window_start", "wh_beam_window_continue", "wh_beam_window_status", "wh_beam_window_records", "wh_decode_greedy", "wh_decode_window_start", "wh_decode_window_finish", "wh_decode_window_continue", "wh_decode_window_fetch", "wh_decode_window_start_ragged", "wh_decode_window_ready", "wh_mel_spectrogram_window", "wh_mel_spectrogram_batch", "wh_profile_enable", "wh_profile_read", "wh_debug_read", "wh_debug_step_captures", "wh_debug_probe", "wh_debug_set_tuning", "wh_debug_set_option", "wh_debug_get_option",
     "wh_op_mul_mat", "wh_op_mul_mat_gelu", "wh_op_layer_norm", "wh_op_flash_attention", "wh_op_soft_max", "wh_op_decoder_attention", "wh_op_decoder_cross_attention",
     "wh_op_vocab_soft_max", "wh_op_sample_best", "wh_op_beam_candidates", "wh_op_reorder_self_cache",
     "wh_lang_detect", "wh_model_lang_count", "wh_op_lang_probs",
@@ -162,6 +162,7 @@ def lib():
         L.wh_beam_candidates.argtypes = [vp, i32, i32, i32, i32, C.POINTER(TokenDataC)]
         L.wh_reorder_self_cache.argtypes = [vp, i32, vp, i32]
         L.wh_debug_read.argtypes = [vp, C.c_char_p, i32, i32, vp, i64]
+        L.wh_debug_step_captures.argtypes = [vp, C.POINTER(C.c_int)]
         L.wh_decode_greedy.argtypes = [vp, i32, vp, i32, i32, i32, i32, C.POINTER(TokenDataC)]
         L.wh_decode_window_start.argtypes = [vp, i32, vp, i32, i32, i32, i32]
         L.wh_decode_window_finish.argtypes = [vp, C.POINTER(TokenDataC)]
@@ -685,6 +686,12 @@ class HipContext:
 
     def set_flags(self, flags: int, parity_threads: int = 1):
         check(lib().wh_context_set_flags(self.handle, flags, parity_threads))
+
+    def step_captures(self) -> int:
+        """Decode-step graphs this context has captured since it was created (wh_debug_step_captures)."""
+        n = C.c_int()
+        check(lib().wh_debug_step_captures(self.handle, C.byref(n)))
+        return n.value
 
     def probe(self, kind: int, variant: int, M: int = 0, N: int = 0, K: int = 0, iters: int = 100) -> float:
         ms = C.c_float()

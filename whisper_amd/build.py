@@ -22,7 +22,7 @@ HOST_LIB = os.path.join(LIB_DIR, "libWhisper.so")
 CLI_BIN = os.path.join(LIB_DIR, "whisper-main")
 
 # the runtime behind the C ABI, one unit per responsibility; runtime.h holds what they share (host code: the kernel units do not include it)
-RUNTIME_SOURCES = ["options.hip", "model.hip", "comm.hip", "context.hip", "encode.hip", "exact_graphs.hip", "decode.hip", "beam.hip", "ops_debug.hip"]
+RUNTIME_SOURCES = ["options.hip", "model.hip", "comm.hip", "context.hip", "encode.hip", "exact_graphs.hip", "step_graph.hip", "decode.hip", "beam.hip", "ops_debug.hip"]
 # resample.hip and vad.hip keep their kernels next to the entry points that own their tables, dequant.hip next to wh_dequantize, align.hip next to wh_align_tokens: kernel units that do include runtime.h
 HIP_SOURCES = ["gemm_persistent.hip", "gemm_decode.hip", "gemm_tiled.hip", "attn_dec.hip", "decode1.hip", "attn_enc.hip", "gemm.hip", "elementwise.hip", "sample.hip", "mel.hip", "exact.hip", "resample.hip", "vad.hip", "dequant.hip",
                "align.hip"] + RUNTIME_SOURCES

@@ -410,20 +410,11 @@ static int beamStep( wh_context* c, int batch, int width )
 	return launchAdvanceState( c->state, c->seqPos, batch, st );
 }
 
-static int beamEnqueue( wh_context* c, int nSteps )
+// nSteps steps of the window in progress: replays of `exec`, eager launches when there is none
+static int beamEnqueue( wh_context* c, hipGraphExec_t exec, int nSteps )
 {
 	const int batch = c->beamWindows * c->hyp, width = c->beamWidth;
-	// the graph wh_beam_window_start captured for this shape; eager launches when there is none (profiler on, WH_FLAG_NO_GRAPH, WH_DEBUG_SYNC)
-	const bool useGraph = !c->prof.on && !( c->flags & WH_FLAG_NO_GRAPH ) && !debugSync() && c->beamGraphExec && c->beamGraphBatch == batch && c->beamGraphWidth == width;
-	for( int s = 0; s < nSteps; s++ )
-	{
-		if( useGraph ) WH_HIP( hipGraphLaunch( c->beamGraphExec, c->stream ) );
-		else
-		{
-			c->profKeysHint = c->windowPos + s + 1;
-			WH_CHECK( beamStep( c, batch, width ) );
-		}
-	}
+	WH_CHECK( enqueueSteps( c, exec, nSteps, c->windowPos + 1, [ c, batch, width ]() { return beamStep( c, batch, width ); } ) );
 	c->beamSteps += nSteps;
 	c->windowPos += nSteps;
 	return 0;
@@ -450,40 +441,25 @@ int wh_beam_window_start( wh_context* c, int windows, const int32_t* promptToken
 	c->beamWindows = windows;
 	c->beamWidth = width;
 	c->beamSteps = 0;
-	const bool useGraph = !c->prof.on && !( c->flags & WH_FLAG_NO_GRAPH ) && !debugSync();
-	if( useGraph && ( !c->beamGraphExec || c->beamGraphBatch != batch || c->beamGraphWidth != width ) )
+	hipGraphExec_t exec = nullptr;
+	if( stepsReplayable( c ) )
 	{
-		// first use for this shape: one eager step with a finished search (the ranking returns at once, parents = identity) sets the per-kernel function
-		// attributes, then the capture. Blocking, once per context and shape; what it leaves behind is overwritten below.
-		std::vector<BeamWindow> idle( (size_t)windows );
-		memset( idle.data(), 0, idle.size() * sizeof( BeamWindow ) );
-		for( BeamWindow& w : idle ) w.done = 1;
-		std::vector<int32_t> zeros( (size_t)batch, 0 ), ident( (size_t)batch );
-		for( int b = 0; b < batch; b++ ) ident[ (size_t)b ] = b;
-		const DecodeState warm = { 0, 0, 0, 0 };
-		WH_HIP( hipMemcpy( c->beamState, idle.data(), idle.size() * sizeof( BeamWindow ), hipMemcpyHostToDevice ) );
-		WH_HIP( hipMemcpy( c->beamRules, rules, sizeof( BeamRules ) * windows, hipMemcpyHostToDevice ) );
-		WH_HIP( hipMemcpy( c->beamParents, ident.data(), sizeof( int32_t ) * batch, hipMemcpyHostToDevice ) );
-		WH_HIP( hipMemcpy( c->state, &warm, sizeof( warm ), hipMemcpyHostToDevice ) );
-		WH_HIP( hipMemcpy( c->seqPos, zeros.data(), sizeof( int32_t ) * batch, hipMemcpyHostToDevice ) );
-		WH_HIP( hipMemcpy( c->tokensDev, zeros.data(), sizeof( int32_t ) * batch, hipMemcpyHostToDevice ) );
-		WH_CHECK( beamStep( c, batch, width ) );
-		WH_HIP( hipStreamSynchronize( st ) );
-		if( c->beamGraphExec ) { (void)hipGraphExecDestroy( c->beamGraphExec ); c->beamGraphExec = nullptr; }
-		// the launch sequence of a step is the same for every token: positions, parents, tokens and the search state live in device memory
+		// no window state exists yet. The idle state of a beam step: idleLoopState, a finished search (the ranking returns at once), parents = identity and the
+		// rules; what it and the warm-up leave behind is overwritten below. The launch sequence of a step is the same for every token: positions, parents,
+		// tokens and the search state live in device memory.
+		const StepFn idle = [ c, windows, batch, rules ]()
 		{
-			hipGraph_t graph = nullptr;
-			WH_HIP( hipStreamBeginCapture( st, hipStreamCaptureModeThreadLocal ) );
-			const int rc = beamStep( c, batch, width );
-			const hipError_t e = hipStreamEndCapture( st, &graph );
-			if( rc != 0 ) { if( graph ) (void)hipGraphDestroy( graph ); return rc; }
-			if( e != hipSuccess ) return hipFail( e, "hipStreamEndCapture", __FILE__, __LINE__ );
-			const hipError_t e2 = hipGraphInstantiate( &c->beamGraphExec, graph, nullptr, nullptr, 0 );
-			(void)hipGraphDestroy( graph );
-			if( e2 != hipSuccess ) { c->beamGraphExec = nullptr; return hipFail( e2, "hipGraphInstantiate", __FILE__, __LINE__ ); }
-			c->beamGraphBatch = batch;
-			c->beamGraphWidth = width;
-		}
+			std::vector<BeamWindow> idleSearch( (size_t)windows );
+			memset( idleSearch.data(), 0, idleSearch.size() * sizeof( BeamWindow ) );
+			for( BeamWindow& w : idleSearch ) w.done = 1;
+			std::vector<int32_t> ident( (size_t)batch );
+			for( int b = 0; b < batch; b++ ) ident[ (size_t)b ] = b;
+			WH_HIP( hipMemcpy( c->beamState, idleSearch.data(), idleSearch.size() * sizeof( BeamWindow ), hipMemcpyHostToDevice ) );
+			WH_HIP( hipMemcpy( c->beamRules, rules, sizeof( BeamRules ) * windows, hipMemcpyHostToDevice ) );
+			WH_HIP( hipMemcpy( c->beamParents, ident.data(), sizeof( int32_t ) * batch, hipMemcpyHostToDevice ) );
+			return idleLoopState( c, batch );
+		};
+		WH_CHECK( obtainStepGraph( c, batch, stepKey( c, width ), WARM_FRESH, idle, [ c, batch, width ]() { return beamStep( c, batch, width ); }, exec ) );
 	}
 	// the window's own state: rules, an empty search, the prompt of every slot, positions
 	{
@@ -514,7 +490,7 @@ int wh_beam_window_start( wh_context* c, int windows, const int32_t* promptToken
 	c->beamSteps = 1;
 	c->windowPos = nPrompt;
 	c->lastBatch = batch;
-	return beamEnqueue( c, nSteps );
+	return beamEnqueue( c, exec, nSteps );
 }
 
 int wh_beam_window_continue( wh_context* c, int nSteps )
@@ -522,7 +498,8 @@ int wh_beam_window_continue( wh_context* c, int nSteps )
 	if( !c || nSteps <= 0 || c->beamSteps <= 0 ) { setError( "beam_window_continue: no window in progress" ); return WH_E_INVALIDARG; }
 	WH_BIND( c->m );
 	if( c->windowPos + nSteps > c->m->hp.n_text_ctx ) { setError( "beam_window_continue: n_text_ctx exceeded" ); return WH_E_BOUNDS; }
-	return beamEnqueue( c, nSteps );
+	// the graph wh_beam_window_start captured for this shape and mode, when a replay is allowed and it is still there
+	return beamEnqueue( c, stepsReplayable( c ) ? c->stepGraph( c->beamWindows * c->hyp, stepKey( c, c->beamWidth ) ) : nullptr, nSteps );
 }
 
 int wh_beam_window_status( wh_context* c, wh_beam_window* out )

@@ -227,7 +227,6 @@ void wh_context_destroy( wh_context* c )
 	(void)bindDevice( c->m );
 	if( c->stream ) (void)hipStreamSynchronize( c->stream );
 	c->destroyStepGraphs();
-	if( c->beamGraphExec ) (void)hipGraphExecDestroy( c->beamGraphExec );
 	for( auto& mk : c->marks ) (void)hipEventDestroy( mk.ev );
 	for( hipEvent_t e : c->markPool ) (void)hipEventDestroy( e );
 	if( c->copyStream ) (void)hipStreamDestroy( c->copyStream );
@@ -272,7 +271,6 @@ int wh_context_set_audio_ctx( wh_context* c, int audioCtx )
 	// every launch reads the key count from the context (row strides of the caches included), so the override is the context's T; what was captured or
 	// encoded with another T is void
 	c->destroyStepGraphs();
-	if( c->beamGraphExec ) { (void)hipGraphExecDestroy( c->beamGraphExec ); c->beamGraphExec = nullptr; c->beamGraphBatch = 0; }
 	c->T = T;
 	c->Tpad = roundUp( T, 256 );
 	c->encoded = false;

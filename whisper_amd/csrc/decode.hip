@@ -478,51 +478,11 @@ int wh::uploadDecodeState( wh_context* c, int batch, const DecodeState& s, const
 	return 0;
 }
 
-extern "C" {
-
-// What a captured step graph depends on besides the batch: the parity mode and the sampler (greedy or temperature: other kernels, the same graph for every temperature)
-constexpr uint32_t STEP_KEY_ROWS = 0x40000u;	  // per-row sampling (wh_context_set_sampling_rows)
-constexpr uint32_t STEP_KEY_SUPPRESS = 0x80000u;   // a suppressed set is held (wh_context_set_suppress): the graph has one more node, the same for every set
-constexpr uint32_t STEP_KEY_TS_RULES = 0x100000u;  // the timestamp rules are on (wh_context_set_timestamp_rules): one more node, the same for every window
-static uint32_t stepGraphKey( const wh_context* c )
+// Does the spread sampler serve `batch` rows in the context's present mode? It leaves unnormalised e and its slice sums where the others leave probabilities,
+// so whoever reads c->probs behind a sample asks here
+static bool spreadSampler( const wh_context* c, int batch )
 {
-	return ( ( c->flags & WH_FLAG_PARITY_PV ) ? ( 0x10000u | (uint32_t)c->parityThreads ) : 0u ) | ( c->temperature > 0.0f ? 0x20000u : 0u ) |
-		( c->sampleRowsOn ? STEP_KEY_ROWS : 0u ) | ( c->suppressCount > 0 ? STEP_KEY_SUPPRESS : 0u ) |
-		( c->tsRules ? STEP_KEY_TS_RULES : 0u );
-}
-// Captured steps that cannot serve ( batch, key ) or its sibling in the other per-row mode go (see wh_context::stepGraphs); true when one went
-static bool dropStaleStepGraphs( wh_context* c, int batch, uint32_t key )
-{
-	bool dropped = false;
-	for( size_t i = 0; i < c->stepGraphs.size(); )
-	{
-		const wh_context::StepGraph& g = c->stepGraphs[ i ];
-		if( g.batch != batch || ( ( g.key ^ key ) & ~STEP_KEY_ROWS ) != 0 )
-		{
-			(void)hipGraphExecDestroy( g.exec );
-			c->stepGraphs.erase( c->stepGraphs.begin() + (ptrdiff_t)i );
-			dropped = true;
-		}
-		else i++;
-	}
-	return dropped;
-}
-// One greedyStep of `batch` rows in the context's present mode, captured on its stream and kept under ( batch, key )
-static int greedyStep( wh_context* c, int batch );
-static int captureStepGraph( wh_context* c, int batch, uint32_t key, hipGraphExec_t& exec )
-{
-	hipGraph_t graph = nullptr;
-	WH_HIP( hipStreamBeginCapture( c->stream, hipStreamCaptureModeThreadLocal ) );
-	const int rc = greedyStep( c, batch );
-	const hipError_t e = hipStreamEndCapture( c->stream, &graph );
-	if( rc != 0 ) { if( graph ) (void)hipGraphDestroy( graph ); return rc; }
-	if( e != hipSuccess ) return hipFail( e, "hipStreamEndCapture", __FILE__, __LINE__ );
-	exec = nullptr;
-	const hipError_t e2 = hipGraphInstantiate( &exec, graph, nullptr, nullptr, 0 );
-	(void)hipGraphDestroy( graph );
-	if( e2 != hipSuccess ) { exec = nullptr; return hipFail( e2, "hipGraphInstantiate", __FILE__, __LINE__ ); }
-	c->stepGraphs.push_back( wh_context::StepGraph{ batch, key, exec } );
-	return 0;
+	return !c->sampleRowsOn && !( c->temperature > 0.0f ) && batch <= SMALL_MAX_ROWS && ( g_tuning & TUNE_SAMPLE_SPREAD );
 }
 
 // logits -> table softmax -> sampleBest -> token data + next token: one workgroup per row, or -- for the few rows of one stream -- every row cut
@@ -548,7 +508,7 @@ static int sampleStep( wh_context* c, int batch, hipStream_t st )
 		return profiled( c, KC_SAMPLE, 4.0 * batch * hp.n_vocab, 8.0 * batch * hp.n_vocab,
 			[ & ]() { return launchSampleDrawStep( c->probs, batch, hp.n_vocab, beg, sot, solm, tnot, c->state, c->sampleParams, c->seqPos, c->greedyOut, c->tokensDev, c->mailDev, st ); } );
 	}
-	if( batch <= SMALL_MAX_ROWS && ( g_tuning & TUNE_SAMPLE_SPREAD ) )
+	if( spreadSampler( c, batch ) )
 	{
 		if( !c->sampleScratch ) WH_CHECK( c->alloc( c->sampleScratch, (int64_t)sampleSpreadScratchBytes( SMALL_MAX_ROWS ), wh_context::DONT_CARE, "sampleScratch" ) );
 		return profiled( c, KC_SAMPLE, 12.0 * batch * hp.n_vocab, 8.0 * batch * hp.n_vocab,
@@ -561,14 +521,35 @@ static int sampleStep( wh_context* c, int batch, hipStream_t st )
 // One greedy token on the device: decoder graph -> softmax + sampleBest -> advance the device-resident state.
 static int greedyStep( wh_context* c, int batch )
 {
-	const wh_hparams& hp = c->m->hp;
-	const SpecialIds sp = specialIds( hp );
-	const int sot = sp.sot, solm = sp.solm, tnot = sp.tnot, beg = sp.beg;
 	WH_CHECK( decodeGraph( c, batch, 1, 0, true ) );
 	WH_CHECK( timestampRules( c, batch, 0 ) );
 	WH_CHECK( sampleStep( c, batch, c->stream ) );
 	return launchAdvanceState( c->state, c->seqPos, batch, c->stream );
 }
+// Everything in device memory that a greedyStep mutates and a window in progress still needs (obtainStepGraph's WARM_PRESERVE; the stream is idle): the sampler
+// state, the positions, the fed tokens and -- when the rules are on -- the timestamp records. Per-row device state a later feature adds to the step joins HERE.
+// (The cache row and the sample the warm-up writes are rewritten by the first real step.)
+int wh::saveLoopState( wh_context* c, int batch, LoopState& s )
+{
+	s.pos.resize( (size_t)batch );
+	s.tok.resize( (size_t)batch );
+	s.rec.resize( c->tsRules ? (size_t)batch : 0 );
+	WH_HIP( hipMemcpy( &s.state, c->state, sizeof( DecodeState ), hipMemcpyDeviceToHost ) );
+	WH_HIP( hipMemcpy( s.pos.data(), c->seqPos, sizeof( int32_t ) * batch, hipMemcpyDeviceToHost ) );
+	WH_HIP( hipMemcpy( s.tok.data(), c->tokensDev, sizeof( int32_t ) * batch, hipMemcpyDeviceToHost ) );
+	if( c->tsRules ) WH_HIP( hipMemcpy( s.rec.data(), c->tsRecords, sizeof( TimestampRecord ) * batch, hipMemcpyDeviceToHost ) );
+	return 0;
+}
+int wh::restoreLoopState( wh_context* c, int batch, const LoopState& s )
+{
+	WH_HIP( hipMemcpy( c->state, &s.state, sizeof( DecodeState ), hipMemcpyHostToDevice ) );
+	WH_HIP( hipMemcpy( c->seqPos, s.pos.data(), sizeof( int32_t ) * batch, hipMemcpyHostToDevice ) );
+	WH_HIP( hipMemcpy( c->tokensDev, s.tok.data(), sizeof( int32_t ) * batch, hipMemcpyHostToDevice ) );
+	if( c->tsRules ) WH_HIP( hipMemcpy( c->tsRecords, s.rec.data(), sizeof( TimestampRecord ) * batch, hipMemcpyHostToDevice ) );
+	return 0;
+}
+
+extern "C" {
 
 int wh_decode_greedy( wh_context* c, int batch, const int32_t* firstTokens, int nPast, int nSteps, int forceFirstTimestamp, int firstIsInitial,
 	wh_token_data* out )
@@ -586,35 +567,13 @@ int wh_decode_greedy( wh_context* c, int batch, const int32_t* firstTokens, int 
 	WH_HIP( hipMemcpyAsync( c->tokensDev, firstTokens, sizeof( int32_t ) * batch, hipMemcpyHostToDevice, st ) );
 	WH_HIP( hipStreamSynchronize( st ) );
 
-	const bool useGraph = !c->prof.on && !( c->flags & WH_FLAG_NO_GRAPH ) && !debugSync();
-	if( useGraph )
-	{
-		const uint32_t key = stepGraphKey( c );
-		hipGraphExec_t exec = c->stepGraph( batch, key );
-		if( !exec )
-		{
-			dropStaleStepGraphs( c, batch, key );	   // (the stream is idle here)
-			// one eager step first: it sets the per-kernel function attributes, which capture does not allow
-			WH_CHECK( greedyStep( c, batch ) );
-			WH_HIP( hipStreamSynchronize( st ) );
-			WH_CHECK( uploadDecodeState( c, batch, init, nullptr, nPast ) );
-			WH_HIP( hipMemcpyAsync( c->tokensDev, firstTokens, sizeof( int32_t ) * batch, hipMemcpyHostToDevice, st ) );
-			WH_HIP( hipStreamSynchronize( st ) );
-			WH_CHECK( captureStepGraph( c, batch, key, exec ) );
-		}
-		// the first token is the caller's, not a sample: the records are armed, the history starts at this call's first sample
-		WH_CHECK( timestampRules( c, batch, 2 ) );
-		for( int s = 0; s < nSteps; s++ ) WH_HIP( hipGraphLaunch( exec, st ) );
-	}
-	else
-	{
-		WH_CHECK( timestampRules( c, batch, 2 ) );
-		for( int s = 0; s < nSteps; s++ )
-		{
-			c->profKeysHint = nPast + s + 1;
-			WH_CHECK( greedyStep( c, batch ) );
-		}
-	}
+	const StepFn step = [ c, batch ]() { return greedyStep( c, batch ); };
+	hipGraphExec_t exec = nullptr;
+	// nPast may be above 0 over the cache rows of an earlier wh_decode, and the state is uploaded: the warm-up must preserve both
+	if( stepsReplayable( c ) ) WH_CHECK( obtainStepGraph( c, batch, stepKey( c, 0 ), WARM_PRESERVE, nullptr, step, exec ) );
+	// the first token is the caller's, not a sample: the records are armed, the history starts at this call's first sample
+	WH_CHECK( timestampRules( c, batch, 2 ) );
+	WH_CHECK( enqueueSteps( c, exec, nSteps, nPast + 1, step ) );
 	c->lastBatch = batch;
 	static_assert( sizeof( wh_token_data ) == sizeof( TokenData ), "token data layout" );
 	WH_HIP( hipMemcpyAsync( out, c->greedyOut, sizeof( TokenData ) * (size_t)batch * nSteps, hipMemcpyDeviceToHost, st ) );
@@ -665,30 +624,11 @@ static int windowStart( wh_context* c, int batch, const int32_t* promptTokens, c
 	hipStream_t st = c->stream;
 	for( auto& mk : c->marks ) c->markPool.push_back( mk.ev );
 	c->marks.clear();
-	const bool useGraph = !c->prof.on && !( c->flags & WH_FLAG_NO_GRAPH ) && nSteps > 0 && !debugSync();
-	const uint32_t key = stepGraphKey( c );
-	hipGraphExec_t exec = useGraph ? c->stepGraph( batch, key ) : nullptr;
-	if( useGraph && !exec )
-	{
-		// a graph that can no longer be replayed may still be queued: wait before it goes
-		WH_HIP( hipStreamSynchronize( st ) );
-		dropStaleStepGraphs( c, batch, key );
-		// first use for this batch size: one eager step (sets the per-kernel function attributes), then capture. Blocking,
-		// once per context; the state it leaves behind is overwritten below.
-		const DecodeState warm = { 0, 0, 0, 0 };
-		WH_HIP( hipStreamSynchronize( st ) );
-		{
-			// not through the staging: it already holds this window's tokens
-			std::vector<int32_t> zeros( (size_t)batch, 0 );
-			WH_HIP( hipMemcpy( c->state, &warm, sizeof( warm ), hipMemcpyHostToDevice ) );
-			WH_HIP( hipMemcpy( c->seqPos, zeros.data(), sizeof( int32_t ) * batch, hipMemcpyHostToDevice ) );
-		}
-		WH_HIP( hipMemsetAsync( c->tokensDev, 0, sizeof( int32_t ) * batch, st ) );
-		WH_HIP( hipStreamSynchronize( st ) );
-		WH_CHECK( greedyStep( c, batch ) );
-		WH_HIP( hipStreamSynchronize( st ) );
-		WH_CHECK( captureStepGraph( c, batch, key, exec ) );
-	}
+	const StepFn step = [ c, batch ]() { return greedyStep( c, batch ); };
+	hipGraphExec_t exec = nullptr;
+	// no window state exists yet: what the warm-up leaves behind is overwritten below
+	if( stepsReplayable( c ) && nSteps > 0 )
+		WH_CHECK( obtainStepGraph( c, batch, stepKey( c, 0 ), WARM_FRESH, [ c, batch ]() { return idleLoopState( c, batch ); }, step, exec ) );
 	// a new generation per window: stamps of earlier windows in the mailbox can never be taken for this one's
 	// (only for the few sequences of a stream whose host loop reads every sample; a lock-step batch is read chunk by chunk through events)
 	const bool mailbox = c->mailData && batch <= SMALL_MAX_ROWS;
@@ -707,8 +647,6 @@ static int windowStart( wh_context* c, int batch, const int32_t* promptTokens, c
 	c->raggedLastPos = nullptr;
 	WH_CHECK( rcGraph );
 	{
-		const SpecialIds sp = specialIds( hp );
-		const int sot = sp.sot, solm = sp.solm, tnot = sp.tnot, beg = sp.beg;
 		WH_CHECK( timestampRules( c, batch, 1 ) );	 // a new window: no record survives into it, and the first sample is unfiltered
 		WH_CHECK( sampleStep( c, batch, st ) );
 		WH_CHECK( launchAdvanceState( c->state, c->seqPos, batch, st ) );
@@ -717,20 +655,12 @@ static int windowStart( wh_context* c, int batch, const int32_t* promptTokens, c
 		{
 			// p[ solm ] of the rows the first sample just left in c->probs (the spread sampler leaves unnormalised e and its slice sums), and an event behind it:
 			// wh_decode_window_no_speech waits for the first sample only
-			const bool spread = !( c->temperature > 0.0f ) && !c->sampleRowsOn && batch <= SMALL_MAX_ROWS && ( g_tuning & TUNE_SAMPLE_SPREAD );
-			WH_CHECK( launchNoSpeechGather( c->probs, spread ? c->sampleScratch : nullptr, batch, hp.n_vocab, solm, c->noSpeechDev, st ) );
+			WH_CHECK( launchNoSpeechGather( c->probs, spreadSampler( c, batch ) ? c->sampleScratch : nullptr, batch, hp.n_vocab, specialIds( hp ).solm, c->noSpeechDev, st ) );
 			WH_HIP( hipEventRecord( c->noSpeechEv, st ) );
 			c->noSpeechRows = batch;
 		}
 	}
-	if( useGraph )
-		for( int s = 0; s < nSteps; s++ ) WH_HIP( hipGraphLaunch( exec, st ) );
-	else
-		for( int s = 0; s < nSteps; s++ )
-		{
-			c->profKeysHint = nPrompt + s + 1;
-			WH_CHECK( greedyStep( c, batch ) );
-		}
+	WH_CHECK( enqueueSteps( c, exec, nSteps, nPrompt + 1, step ) );
 	c->lastBatch = batch;
 	c->windowSamples = 1 + nSteps;
 	c->windowPos = nPrompt + nSteps;
@@ -759,38 +689,11 @@ int wh_decode_window_continue( wh_context* c, int nSteps )
 	const wh_hparams& hp = c->m->hp;
 	if( c->windowPos + nSteps > hp.n_text_ctx ) { setError( "decode_window_continue: n_text_ctx exceeded" ); return WH_E_BOUNDS; }
 	const int batch = c->lastBatch;
-	const bool useGraph = !c->prof.on && !( c->flags & WH_FLAG_NO_GRAPH ) && !debugSync();
-	const uint32_t key = stepGraphKey( c );
-	hipGraphExec_t exec = useGraph ? c->stepGraph( batch, key ) : nullptr;
-	if( useGraph && !exec )
-	{
-		// the window was started with nSteps == 0 (no graph yet): capture now. The eager warm-up step must not disturb
-		// the window's device state, so the state and the pending token are saved around it.
-		WH_HIP( hipStreamSynchronize( c->stream ) );
-		DecodeState saved;
-		std::vector<int32_t> tok( (size_t)batch ), savedPos( (size_t)batch );
-		WH_HIP( hipMemcpy( &saved, c->state, sizeof( saved ), hipMemcpyDeviceToHost ) );
-		WH_HIP( hipMemcpy( savedPos.data(), c->seqPos, sizeof( int32_t ) * batch, hipMemcpyDeviceToHost ) );
-		WH_HIP( hipMemcpy( tok.data(), c->tokensDev, sizeof( int32_t ) * batch, hipMemcpyDeviceToHost ) );
-		std::vector<TimestampRecord> savedRec( c->tsRules ? (size_t)batch : 0 );
-		if( c->tsRules ) WH_HIP( hipMemcpy( savedRec.data(), c->tsRecords, sizeof( TimestampRecord ) * batch, hipMemcpyDeviceToHost ) );
-		dropStaleStepGraphs( c, batch, key );
-		WH_CHECK( greedyStep( c, batch ) );
-		WH_HIP( hipStreamSynchronize( c->stream ) );
-		WH_CHECK( captureStepGraph( c, batch, key, exec ) );
-		WH_HIP( hipMemcpy( c->state, &saved, sizeof( saved ), hipMemcpyHostToDevice ) );
-		WH_HIP( hipMemcpy( c->seqPos, savedPos.data(), sizeof( int32_t ) * batch, hipMemcpyHostToDevice ) );
-		WH_HIP( hipMemcpy( c->tokensDev, tok.data(), sizeof( int32_t ) * batch, hipMemcpyHostToDevice ) );
-		if( c->tsRules ) WH_HIP( hipMemcpy( c->tsRecords, savedRec.data(), sizeof( TimestampRecord ) * batch, hipMemcpyHostToDevice ) );
-	}
-	if( useGraph )
-		for( int s = 0; s < nSteps; s++ ) WH_HIP( hipGraphLaunch( exec, c->stream ) );
-	else
-		for( int s = 0; s < nSteps; s++ )
-		{
-			c->profKeysHint = c->windowPos + s + 1;
-			WH_CHECK( greedyStep( c, batch ) );
-		}
+	const StepFn step = [ c, batch ]() { return greedyStep( c, batch ); };
+	hipGraphExec_t exec = nullptr;
+	// a window started with nSteps == 0 captured nothing: the first capture then happens here, over the window's device state
+	if( stepsReplayable( c ) ) WH_CHECK( obtainStepGraph( c, batch, stepKey( c, 0 ), WARM_PRESERVE, nullptr, step, exec ) );
+	WH_CHECK( enqueueSteps( c, exec, nSteps, c->windowPos + 1, step ) );
 	c->windowSamples += nSteps;
 	c->windowPos += nSteps;
 	return markWindow( c );
@@ -934,8 +837,8 @@ int wh_context_set_sampling_rows( wh_context* c, int rows, const float* temperat
 	return 0;
 }
 
-// Suppressed tokens. The sorted unique set and its count go to device memory behind what the stream holds; the captured graphs are keyed on
-// "a set is held" only, and the beam step's graph, which has no key, goes when that state flips.
+// Suppressed tokens. The sorted unique set and its count go to device memory behind what the stream holds; the captured steps of every kind are
+// keyed on "a set is held" only.
 int wh_context_set_suppress( wh_context* c, const int32_t* ids, int count )
 {
 	if( !c || count < 0 || ( count > 0 && !ids ) ) { setError( "context_set_suppress: null context, a negative count or null ids" ); return WH_E_INVALIDARG; }
@@ -958,13 +861,7 @@ int wh_context_set_suppress( wh_context* c, const int32_t* ids, int count )
 	up[ 0 ] = (int32_t)up.size() - 1;
 	if( !c->suppress ) WH_CHECK( c->alloc( c->suppress, (int64_t)eot + 1, wh_context::MUST_BE_ZERO, "suppress" ) );
 	WH_HIP( hipMemcpyAsync( c->suppress, up.data(), sizeof( int32_t ) * up.size(), hipMemcpyHostToDevice, c->stream ) );
-	WH_HIP( hipStreamSynchronize( c->stream ) );	 // `up` is this call's; the stream is idle below
-	if( ( up[ 0 ] > 0 ) != ( c->suppressCount > 0 ) && c->beamGraphExec )
-	{
-		(void)hipGraphExecDestroy( c->beamGraphExec );
-		c->beamGraphExec = nullptr;
-		c->beamGraphBatch = 0;
-	}
+	WH_HIP( hipStreamSynchronize( c->stream ) );	 // `up` is this call's
 	c->suppressCount = up[ 0 ];
 	return 0;
 }

@@ -1,5 +1,5 @@
 // Private declarations of the runtime behind the C ABI of include/whisper_hip.h: the model arena, the context and what the units
-// options / model / comm / context / encode / exact_graphs / decode / beam / ops_debug (.hip) share.
+// options / model / comm / context / encode / exact_graphs / step_graph / decode / beam / ops_debug (.hip) share.
 //
 // The runtime is the MI355X counterpart of the reference's DirectCompute::WhisperContext
 // (Whisper/Whisper/WhisperContext.cpp: encode :310-399, encodeLayer :158-289, decode :578-639, decodeLayer :407-576),
@@ -24,6 +24,7 @@
 #include <condition_variable>
 #include <memory>
 #include <cstdlib>
+#include <functional>
 #include <set>
 #include <string>
 #include <vector>
@@ -240,8 +241,6 @@ struct wh_context
 	BeamWindow* beamState = nullptr;
 	BeamRecord* beamRecords = nullptr;
 	int* beamParents = nullptr;
-	hipGraphExec_t beamGraphExec = nullptr;
-	int beamGraphBatch = 0, beamGraphWidth = 0;
 	int beamWindows = 0, beamWidth = 0, beamSteps = 0;	   // the window in progress: windows, width, ranking steps enqueued so far
 	float* melScratch = nullptr;
 	// device-side greedy loop: the sampler's state and one position per sequence (the sequences of a lock-step batch may differ)
@@ -254,11 +253,11 @@ struct wh_context
 	int mailGen = 0;		   // generation of the window in progress (0 = its samples are not mirrored)
 	int mailCounter = 0;	   // last generation handed out
 	TokenData* greedyOut = nullptr;	   // [n_text_ctx][maxBatch]
-	// the captured steps of the device-side loop, by ( batch, stepGraphKey ). Entries that differ from the one asked for in the batch or in anything but the key's
-	// per-row bit are destroyed when it is captured: at most the greedy graph and the per-row graph of one batch live side by side, so a lock-step batch whose
-	// rounds enter and leave the per-row mode never recaptures
+	// the captured decode steps of every kind, by ( batch, stepKey ): owned by step_graph.hip, which states the key and the retention rule. stepCaptures counts the
+	// graphs instantiated over the context's life (wh_debug_step_captures)
 	struct StepGraph { int batch; uint32_t key; hipGraphExec_t exec; };
 	std::vector<StepGraph> stepGraphs;
+	int stepCaptures = 0;
 	hipGraphExec_t stepGraph( int batch, uint32_t key ) const
 	{
 		for( const StepGraph& g : stepGraphs )
@@ -435,6 +434,20 @@ namespace wh
 	int checkTokens( const wh_hparams& hp, const int32_t* tokens, int64_t count, const char* who );
 	int uploadDecodeState( wh_context* c, int batch, const DecodeState& s, const int32_t* positions, int uniform );
 	int alignDebugRead( wh_context* c, const std::string& w, int layer, float* dstHost, int64_t dstCapFloats );
+
+	// captured decode steps (step_graph.hip, where each of these is explained)
+	constexpr uint32_t STEP_KEY_ROWS = 0x40000u, STEP_KEY_SUPPRESS = 0x80000u, STEP_KEY_TS_RULES = 0x100000u, STEP_KEY_BEAM = 0x200000u;
+	using StepFn = std::function<int()>;
+	enum eWarmUp { WARM_FRESH, WARM_PRESERVE };
+	bool stepsReplayable( const wh_context* c );
+	uint32_t stepKey( const wh_context* c, int beamWidth );	   // beamWidth 0: a step of the greedy loop
+	int obtainStepGraph( wh_context* c, int batch, uint32_t key, eWarmUp warm, const StepFn& idle, const StepFn& step, hipGraphExec_t& exec );
+	int idleLoopState( wh_context* c, int batch );
+	int enqueueSteps( wh_context* c, hipGraphExec_t exec, int nSteps, int firstKeys, const StepFn& step );
+	// what WARM_PRESERVE carries over the warm-up step: the list is stated next to the step that mutates it (decode.hip)
+	struct LoopState { DecodeState state; std::vector<int32_t> pos, tok; std::vector<TimestampRecord> rec; };
+	int saveLoopState( wh_context* c, int batch, LoopState& s );
+	int restoreLoopState( wh_context* c, int batch, const LoopState& s );
 }
 
 static inline uint16_t f32ToF16Bits( float f )
