@@ -425,6 +425,33 @@ namespace Whisper
 	WHISPER_EXPORT HRESULT setTimestampRules( iContext* context, bool on );
 	// One switch for all streams of every later run of the runner. E_NOTIMPL to turn it on where the scheduler was built without the device's filter.
 	WHISPER_EXPORT HRESULT setBatchTimestampRules( iBatchRunner* runner, bool on );
+	// Extension: phrase boosting ("hotwords", contextual biasing) -- the caller names phrases, as rows of text-token ids, and one boost; in every step of the
+	// decoding loop the boost is added on the device to the logit of every token that continues a phrase after what the stream has just emitted (the text tokens
+	// since its last timestamp; the start of a phrase is always offered), before the softmax. DESIGN.md section 7 "Phrase boosting" holds the definition. It
+	// applies to greedy runs and to the sampled attempts of the decoding fallback, each attempt from an empty history. Suppressed tokens and the timestamp rules
+	// win (-inf stays -inf). The probabilities a run reports, and what the fallback's gates see, are the boosted distribution's. A partial match keeps its bonus.
+	// There is NO default boost: a useful value on a real checkpoint has not been measured, and neither has recognition accuracy with boosting on.
+	// Off unless set: such a run is what it always was. Free functions: the vtables are the reference's.
+	struct sBoostedPhrases
+	{
+		const int32_t* tokens;	   // [ count ][ maxLength ]: row p holds lengths[ p ] ids, each in [ 0, eot )
+		const int32_t* lengths;	   // [ count ], each 1 .. 16 and <= maxLength
+		uint32_t count;			   // at most 1024; 0 = off
+		uint32_t maxLength;
+		float boost;			   // finite, > 0: added to the logits
+	};
+	// The set holds for every later runFull / runStreamed of the context. nullptr or count == 0 = off, the state of every new context. With a set held, a run
+	// with eSamplingStrategy::BeamSearch answers E_NOTIMPL (the per-sequence state would have to follow the beam's reorder); language detection,
+	// eFullParamsFlags::AlignTokens and scoreTokens read unboosted passes. E_INVALIDARG for an id outside [ 0, eot ), a boost that is NaN, infinite or not
+	// positive, more than 1024 phrases, a phrase of 0 or more than 16 tokens, tables beyond the device's cap, or a context of another library.
+	WHISPER_EXPORT HRESULT setBoostedPhrases( iContext* context, const sBoostedPhrases* phrases );
+	// One set for all streams of every later run of the runner. E_INVALIDARG as above; E_NOTIMPL for a non-empty set where the scheduler was built without the
+	// device's filter.
+	WHISPER_EXPORT HRESULT setBatchBoostedPhrases( iBatchRunner* runner, const sBoostedPhrases* phrases );
+	// One text phrase as rows for sBoostedPhrases: the text as written and, when it does not begin with a space, also the text behind one space, which is how a
+	// word is spelled in mid-sentence; rows that come out equal collapse. tokens [ cap ][ 16 ], lengths [ cap ]; count in: cap, out: the rows written (1 or 2);
+	// E_BOUNDS when cap is too small. E_INVALIDARG, the log naming the phrase, when a spelling is empty or longer than 16 tokens.
+	WHISPER_EXPORT HRESULT phraseSpellings( iModel* model, const char* text, int32_t* tokens, int32_t* lengths, uint32_t* count );
 	// Extension: scoring a GIVEN transcript -- "how probable is this text for this audio?" -- and, with flag 1, forced alignment of a known text. The tokens are
 	// fed to the decoder (teacher forcing) and every scored token receives its log-probability under the model's OWN distribution: neither suppressed tokens nor
 	// the timestamp rules nor the sampler's clauses apply, and a context's decoding settings do not matter. True logarithms (an unlikely token scores a large

@@ -88,6 +88,12 @@ int32_t whisperc_tr_window_stats( void* result, void* out, uint32_t cap, uint32_
 int32_t whisperc_non_speech_tokens( void* model, int32_t* out, uint32_t cap, uint32_t* count );
 int32_t whisperc_set_suppress_tokens( void* ctx, const int32_t* ids, uint32_t count );
 int32_t whisperc_batch_set_suppress_tokens( void* runner, const int32_t* ids, uint32_t count );
+/* Phrase boosting (Whisper::setBoostedPhrases / setBatchBoostedPhrases / phraseSpellings of whisperApi.h): tokens = int32 [count][nMax], row p holds lens[ p ]
+ * text-token ids; boost is added to the logits of the tokens that continue a phrase. count == 0 turns it off (the pointers may be NULL), the state of every new
+ * context and runner. whisperc_phrase_spellings: tokens = int32 [cap][16], lens = int32 [cap], *count = the rows written (1 or 2). */
+int32_t whisperc_set_boost_phrases( void* ctx, const int32_t* tokens, const int32_t* lens, uint32_t count, uint32_t nMax, float boost );
+int32_t whisperc_batch_set_boost_phrases( void* runner, const int32_t* tokens, const int32_t* lens, uint32_t count, uint32_t nMax, float boost );
+int32_t whisperc_phrase_spellings( void* model, const char* text, int32_t* tokens, int32_t* lens, uint32_t cap, uint32_t* count );
 /* Timestamp rules (Whisper::setTimestampRules / setBatchTimestampRules of whisperApi.h): on != 0 = every later run masks the logits so that timestamps come in
  * pairs, never go back in time and close segments of non-zero length. Off is the state of every new context and runner. */
 int32_t whisperc_set_timestamp_rules( void* ctx, int32_t on );

@@ -516,6 +516,29 @@ WH_API int wh_context_set_suppress( wh_context* c, const int32_t* ids, int count
  * to follow the beam's reorder) or under WH_FLAG_PARITY_EXACT (wh_context_set_flags in turn refuses that flag while the mode is on). A context that never turns
  * it on launches, allocates and captures what it always did. */
 WH_API int wh_context_set_timestamp_rules( wh_context* c, int on );
+/* Phrase boosting ("hotwords"; DESIGN.md section 7 "Phrase boosting" holds the definition). A context holds a set of phrases -- each 1 .. 16 text-token ids in
+ * [0, eot) -- and one boost, finite and > 0. For a row of the device-side loop, h = the text tokens the row has sampled in this window since its last non-text
+ * token (any sampled id >= eot empties it, so does the prompt step; wh_decode_greedy starts with it empty and does not count firstTokens). Before the softmax of each
+ * step, logits[ row ][ t ] += boost, once, for every t such that u . t is a prefix of a phrase for some suffix u of h, the empty one included. -inf stays -inf:
+ * suppressed tokens and the timestamp rules win. The order is vocabulary product -> suppress -> timestamp rules -> boost -> sampler, whatever the sampler; the
+ * window's first sample is boosted too. Probabilities a run reports are the boosted distribution's. Not boosted: wh_decode, wh_lang_detect, wh_score_tokens,
+ * wh_align_tokens, the beam step.
+ * tokens: HOST [count][nMax], row p holds lens[ p ] ids; duplicates collapse. count == 0 turns it off (the state of every new context). Limits: 1024 phrases, 16
+ * tokens each, 262144 table entries, a vocabulary of at most 65536 -- WH_E_INVALIDARG names the one violated, as for an id outside [0, eot), a boost that is not
+ * finite or not > 0, a hypothesis-group context and WH_FLAG_PARITY_EXACT (wh_context_set_flags in turn refuses that flag while a set is held).
+ * The tables (2.1 MB, sized for the limits) and maxSeq int32 states are allocated by the first non-empty call and never again; the tables and the boost live in
+ * device memory and the captured step graphs are keyed on "a set is held" only. The call waits for the stream. */
+WH_API int wh_context_set_boost( wh_context* c, const int32_t* tokens, const int32_t* lens, int count, int nMax, float boost );
+/* Host only, no device needed: the automaton's tables for a set (the arguments and limits of wh_context_set_boost; nVocab <= 65536), as int32:
+ * [0] nodes, [1] entries, [2] the boost's bits, [3] 0, off [nodes + 1], tok [entries], next [entries]. Node 0 is the root; node n owns entries off[ n ] ..
+ * off[ n + 1 ), ascending in tok. The root's entries are its children; a deeper node's are the children along its failure chain without the root's, the deeper node
+ * winning. delta( n, t ) = n's entry, else the root's, else the root; the tokens offered at n are n's and the root's. *nInts = the ints the tables take (0 for
+ * count == 0); tables may be NULL to ask for it, cap = the ints it holds. */
+WH_API int wh_boost_compile( const int32_t* tokens, const int32_t* lens, int count, int nMax, int tokenEot, int nVocab, float boost, int32_t* tables, int64_t cap,
+	int64_t* nInts );
+/* Host only: the twin of one step of the kernel on one row. state: a node or -1 (armed); reset as in wh_op_boost_logits. *newState and row [nVocab] in place.
+ * Every call validates the whole of `tables` first, O( entries ): a twin for tests and tools, not a hot path. */
+WH_API int wh_boost_step_host( const int32_t* tables, int64_t nInts, int32_t state, int32_t fed, int reset, float* row, int nVocab, int tokenEot, int32_t* newState );
 WH_API int wh_context_set_no_speech( wh_context* c, int on );
 WH_API int wh_decode_window_no_speech( wh_context* c, float* out );
 
@@ -639,6 +662,13 @@ WH_API int wh_op_suppress_logits( void* stream, float* logits, int rows, int nVo
  * -inf; every other float keeps its bits. reset 1: every record becomes the empty history; 2: armed; neither touches the logits, fedTokensDev may be NULL.
  * 0 <= tokenEot < tokenBeg < nVocab and tokenBeg >= 1, or WH_E_INVALIDARG. Plain stores: no atomics, no LDS. */
 WH_API int wh_op_timestamp_rules( void* stream, float* logits, int rows, int nVocab, int tokenEot, int tokenBeg, const int32_t* fedTokensDev, int reset, int32_t* recordsDev );
+/* One step of the kernel of wh_context_set_boost outside a context, on logits [rows][nVocab] in place. tablesDev: DEVICE int32 [tableInts], what wh_boost_compile
+ * wrote. statesDev: DEVICE int32 [rows], the node each row's history stands on (0 = the root, -1 = armed). reset 0: statesDev[ row ] moves over fedTokensDev[ row ]
+ * (DEVICE; the token each row sampled last) -- an armed state, or a fed id outside [0, tokenEot), gives the root; reset 1: every state becomes the root; 2: armed,
+ * fedTokensDev may be NULL. Then, in all three, the boost is added once to every token the new state offers (an armed state offers what the root does); every other
+ * float keeps its bits. Plain loads and stores: no atomics, no LDS; every index read from device memory is held inside its buffer. */
+WH_API int wh_op_boost_logits( void* stream, float* logits, int rows, int nVocab, int tokenEot, const int32_t* tablesDev, int64_t tableInts, const int32_t* fedTokensDev,
+	int reset, int32_t* statesDev );
 /* The language-detection kernel of wh_lang_detect on logits [rows][nVocab]: langP [rows][nLang] = the probabilities wh_op_vocab_soft_max gives at columns
  * tokenSot + 1 .. tokenSot + nLang, bit for bit, without writing the other columns; best [rows] = the index (0 .. nLang - 1) of the largest, exact ties
  * to the lower index. The row stays in registers: nVocab <= 52224; 1 <= nLang <= 1024 and the block inside the row, or WH_E_INVALIDARG. */

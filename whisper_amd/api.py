@@ -82,6 +82,10 @@ def lib():
         L.whisperc_non_speech_tokens.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
         L.whisperc_set_suppress_tokens.argtypes = [vp, vp, C.c_uint32]
         L.whisperc_batch_set_suppress_tokens.argtypes = [vp, vp, C.c_uint32]
+        L.whisperc_set_boost_phrases.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_float]
+        L.whisperc_batch_set_boost_phrases.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_float]
+        L.whisperc_phrase_spellings.argtypes = [vp, C.c_char_p, vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.whisperc_debug_phrase_spellings.argtypes = [C.c_char_p, C.c_char_p, vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
         L.whisperc_set_timestamp_rules.argtypes = [vp, C.c_int32]
         L.whisperc_batch_set_timestamp_rules.argtypes = [vp, C.c_int32]
         L.whisperc_resample.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64)]
@@ -303,10 +307,39 @@ class Model:
         _check(lib().whisperc_non_speech_tokens(self.h, ids.ctypes.data_as(C.c_void_p), n.value, C.byref(n)), "getNonSpeechTokens")
         return [int(i) for i in ids[:n.value]]
 
+    def phrase_spellings(self, text: str) -> List[List[int]]:
+        """Whisper::phraseSpellings: one text phrase as token rows for set_boost_phrases -- the text as written and, when it does not begin with a space, the
+        text behind one space (a word in mid-sentence); equal rows collapse. A spelling that is empty or longer than 16 tokens is an error naming the phrase."""
+        tokens, lens, n = np.zeros((2, 16), np.int32), np.zeros(2, np.int32), C.c_uint32(0)
+        _check(lib().whisperc_phrase_spellings(self.h, text.encode("utf-8"), tokens.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), 2, C.byref(n)), "phraseSpellings")
+        return [[int(t) for t in tokens[r, :lens[r]]] for r in range(n.value)]
+
     def tokenize(self, text: str) -> List[int]:
         buf = (C.c_int32 * 4096)()
         n = _check(lib().whisperc_tokenize(self.h, text.encode(), buf, 4096), "tokenize")
         return list(buf[:n])
+
+
+def _boost_rows(model: Model, phrases):
+    """strings (each gives its spellings) or id lists | None -> ( int32 [count][nMax], int32 [count] ) for whisperc_set_boost_phrases"""
+    rows: List[List[int]] = []
+    for p in (phrases if phrases is not None else []):
+        rows += model.phrase_spellings(p) if isinstance(p, str) else [[int(t) for t in p]]
+    lens = np.array([len(r) for r in rows], np.int32)
+    tokens = np.zeros((len(rows), max([1] + [len(r) for r in rows])), np.int32)
+    for i, r in enumerate(rows):
+        tokens[i, :len(r)] = r
+    return tokens, lens
+
+
+def _set_boost(fn, who: str, h, model: Model, phrases, boost):
+    tokens, lens = _boost_rows(model, phrases)
+    if len(lens) == 0:
+        _check(fn(h, None, None, 0, 0, 0.0), who)
+        return
+    if boost is None:
+        raise ValueError(who + ": a boost is required with phrases (there is no default)")
+    _check(fn(h, tokens.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), len(lens), tokens.shape[1], float(boost)), who)
 
 
 def _suppress_ids(model: Model, ids) -> np.ndarray:
@@ -476,6 +509,13 @@ class Context:
         a = _suppress_ids(self.model, ids)
         _check(lib().whisperc_set_suppress_tokens(self.h, a.ctypes.data_as(C.c_void_p) if len(a) else None, len(a)), "setSuppressedTokens")
 
+    def set_boost_phrases(self, phrases=None, boost: Optional[float] = None):
+        """Whisper::setBoostedPhrases ("hotwords"): in every later run of this context -- greedy, and each sampled attempt of the fallback -- `boost` is added to
+        the logit of every token that continues one of `phrases` after what was just emitted. phrases: strings (Model.phrase_spellings gives each its two
+        spellings) or lists of text-token ids. None or [] turns it off, the state of a new context. There is no default boost: none has been measured on a
+        real checkpoint. Beam search with a set held is E_NOTIMPL."""
+        _set_boost(lib().whisperc_set_boost_phrases, "setBoostedPhrases", self.h, self.model, phrases, boost)
+
     def set_timestamp_rules(self, on: bool = True):
         """Whisper::setTimestampRules: every later run masks the logits on the device so that timestamps come in pairs, never go back in time within a window
         and close segments of non-zero length (openai-whisper's ApplyTimestampRules) -- greedy runs and the fallback's sampled attempts alike. Off, the state
@@ -596,6 +636,10 @@ class BatchRunner:
         """Whisper::setBatchSuppressedTokens: Context.set_suppress_tokens for every stream of this runner's later runs (one set for all of them)."""
         a = _suppress_ids(self.model, ids)
         _check(lib().whisperc_batch_set_suppress_tokens(self.h, a.ctypes.data_as(C.c_void_p) if len(a) else None, len(a)), "setBatchSuppressedTokens")
+
+    def set_boost_phrases(self, phrases=None, boost: Optional[float] = None):
+        """Whisper::setBatchBoostedPhrases: Context.set_boost_phrases for every stream of this runner's later runs (one set and one boost for all of them)."""
+        _set_boost(lib().whisperc_batch_set_boost_phrases, "setBatchBoostedPhrases", self.h, self.model, phrases, boost)
 
     def set_timestamp_rules(self, on: bool = True):
         """Whisper::setBatchTimestampRules: Context.set_timestamp_rules for every stream of this runner's later runs (one switch for all of them)."""

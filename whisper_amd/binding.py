@@ -58,9 +58,42 @@ EXPORTS = [
     "wh_context_set_sampling_rows", "wh_op_sample_rows",
     "wh_context_set_suppress", "wh_op_suppress_logits",
     "wh_context_set_timestamp_rules", "wh_op_timestamp_rules",
+    "wh_context_set_boost", "wh_boost_compile", "wh_boost_step_host", "wh_op_boost_logits",
     "wh_op_gemv_small", "wh_op_cross_split", "wh_op_self_block_dec",
     "wh_score_tokens", "wh_op_token_scores",
 ]
+
+
+def pack_phrases(phrases):
+    """Lists of token ids -> ( int32 [count][nMax] padded with 0, int32 [count] lengths ), the layout of wh_context_set_boost and wh_boost_compile."""
+    rows = [np.asarray(p, np.int64).reshape(-1) for p in (phrases if phrases is not None else [])]
+    lens = np.array([len(r) for r in rows], np.int32)
+    tokens = np.zeros((len(rows), max(1, int(lens.max()) if len(rows) else 1)), np.int32)
+    for i, r in enumerate(rows):
+        tokens[i, :len(r)] = r
+    return tokens, lens
+
+
+def boost_compile(phrases, token_eot: int, n_vocab: int, boost: float):
+    """wh_boost_compile (host only): the automaton's tables of a set, int32."""
+    tokens, lens = pack_phrases(phrases)
+    tp = tokens.ctypes.data_as(C.c_void_p) if len(lens) else None
+    lp = lens.ctypes.data_as(C.c_void_p) if len(lens) else None
+    n = C.c_int64(0)
+    check(lib().wh_boost_compile(tp, lp, len(lens), tokens.shape[1], token_eot, n_vocab, boost, None, 0, C.byref(n)))
+    out = np.zeros(n.value, np.int32)
+    if n.value:
+        check(lib().wh_boost_compile(tp, lp, len(lens), tokens.shape[1], token_eot, n_vocab, boost, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+    return out
+
+
+def boost_step_host(tables, state: int, fed: int, reset: int, row, token_eot: int):
+    """wh_boost_step_host: ( new state, the row after the step ); `row` is not changed."""
+    tables = np.ascontiguousarray(tables, np.int32)
+    out = np.array(row, np.float32, copy=True)
+    new = C.c_int32(0)
+    check(lib().wh_boost_step_host(tables.ctypes.data_as(C.c_void_p), len(tables), state, fed, reset, out.ctypes.data_as(C.c_void_p), len(out), token_eot, C.byref(new)))
+    return new.value, out
 
 
 class HParamsC(C.Structure):
@@ -214,6 +247,10 @@ def lib():
         L.wh_op_suppress_logits.argtypes = [vp, vp, i32, i32, vp, i32]
         L.wh_context_set_timestamp_rules.argtypes = [vp, i32]
         L.wh_op_timestamp_rules.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp]
+        L.wh_context_set_boost.argtypes = [vp, vp, vp, i32, i32, C.c_float]
+        L.wh_boost_compile.argtypes = [vp, vp, i32, i32, i32, i32, C.c_float, vp, i64, C.POINTER(i64)]
+        L.wh_boost_step_host.argtypes = [vp, i64, i32, i32, i32, vp, i32, i32, C.POINTER(C.c_int32)]
+        L.wh_op_boost_logits.argtypes = [vp, vp, i32, i32, i32, vp, i64, vp, i32, vp]
         L.wh_op_gemv_small.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, C.c_float]
         L.wh_op_cross_split.argtypes = [vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, i32, i32, i32, i32]
         L.wh_op_self_block_dec.argtypes = [vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, i32, i32, i32, i32, vp]
@@ -394,6 +431,13 @@ class HipContext:
     def set_timestamp_rules(self, on: bool):
         """on: every later step of the device-side loop masks the logits by openai-whisper's timestamp rules (pairs, non-decreasing, non-zero segments)."""
         check(lib().wh_context_set_timestamp_rules(self.handle, 1 if on else 0))
+
+    def set_boost(self, phrases=None, boost: float = 0.0):
+        """Phrase boosting: `boost` is added to the logits of every token that continues one of `phrases` (lists of 1 .. 16 text-token ids) after what the row
+        has sampled, in every later step of the device-side loop. None or an empty list turns it off."""
+        tokens, lens = pack_phrases(phrases)
+        check(lib().wh_context_set_boost(self.handle, tokens.ctypes.data_as(C.c_void_p) if len(lens) else None, lens.ctypes.data_as(C.c_void_p) if len(lens) else None,
+                                         len(lens), tokens.shape[1] if len(lens) else 0, boost))
 
     def set_no_speech(self, on: bool):
         """on: every window start also gathers P( <|nospeech|> ) of the prompt step (window_no_speech)."""

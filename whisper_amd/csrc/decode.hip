@@ -43,6 +43,17 @@ static int timestampRules( wh_context* c, int batch, int reset )
 		[ & ]() { return launchTimestampRules( c->logits, batch, hp.n_vocab, sp.sot - 1, sp.beg, c->tokensDev, reset, c->tsRecords, c->stream ); } );
 }
 
+// Phrase boosting (wh_context_set_boost): the filter whose bonus depends on a string-matching state per row. Only the device-side loop calls it, behind the
+// timestamp rules -- so what they and the suppress launch made -inf stays -inf -- and in front of the sampler: reset 1 behind a window's prompt step (every state
+// becomes the root and the root's offers are boosted: the first sample counts), 0 in every step (the state moves over c->tokensDev[ row ], the previous step's sample).
+static int boostLogits( wh_context* c, int batch, int reset )
+{
+	if( !c->boostOn ) return 0;
+	const wh_hparams& hp = c->m->hp;
+	return profiled( c, KC_SAMPLE, 0.0, 8.0 * batch * BOOST_MAX_PHRASES,
+		[ & ]() { return launchBoostLogits( c->logits, batch, hp.n_vocab, specialIds( hp ).sot - 1, c->boostTables, BOOST_TABLE_INTS, c->tokensDev, reset, c->boostStates, c->stream ); } );
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // decoder
 // ------------------------------------------------------------------------------------------------------------------
@@ -523,11 +534,12 @@ static int greedyStep( wh_context* c, int batch )
 {
 	WH_CHECK( decodeGraph( c, batch, 1, 0, true ) );
 	WH_CHECK( timestampRules( c, batch, 0 ) );
+	WH_CHECK( boostLogits( c, batch, 0 ) );
 	WH_CHECK( sampleStep( c, batch, c->stream ) );
 	return launchAdvanceState( c->state, c->seqPos, batch, c->stream );
 }
 // Everything in device memory that a greedyStep mutates and a window in progress still needs (obtainStepGraph's WARM_PRESERVE; the stream is idle): the sampler
-// state, the positions, the fed tokens and -- when the rules are on -- the timestamp records. Per-row device state a later feature adds to the step joins HERE.
+// state, the positions, the fed tokens, -- when the rules are on -- the timestamp records and -- when a set of phrases is held -- the boost states. Per-row device state a later feature adds to the step joins HERE.
 // (The cache row and the sample the warm-up writes are rewritten by the first real step.)
 int wh::saveLoopState( wh_context* c, int batch, LoopState& s )
 {
@@ -538,6 +550,8 @@ int wh::saveLoopState( wh_context* c, int batch, LoopState& s )
 	WH_HIP( hipMemcpy( s.pos.data(), c->seqPos, sizeof( int32_t ) * batch, hipMemcpyDeviceToHost ) );
 	WH_HIP( hipMemcpy( s.tok.data(), c->tokensDev, sizeof( int32_t ) * batch, hipMemcpyDeviceToHost ) );
 	if( c->tsRules ) WH_HIP( hipMemcpy( s.rec.data(), c->tsRecords, sizeof( TimestampRecord ) * batch, hipMemcpyDeviceToHost ) );
+	s.boost.resize( c->boostOn ? (size_t)batch : 0 );
+	if( c->boostOn ) WH_HIP( hipMemcpy( s.boost.data(), c->boostStates, sizeof( int32_t ) * batch, hipMemcpyDeviceToHost ) );
 	return 0;
 }
 int wh::restoreLoopState( wh_context* c, int batch, const LoopState& s )
@@ -546,6 +560,7 @@ int wh::restoreLoopState( wh_context* c, int batch, const LoopState& s )
 	WH_HIP( hipMemcpy( c->seqPos, s.pos.data(), sizeof( int32_t ) * batch, hipMemcpyHostToDevice ) );
 	WH_HIP( hipMemcpy( c->tokensDev, s.tok.data(), sizeof( int32_t ) * batch, hipMemcpyHostToDevice ) );
 	if( c->tsRules ) WH_HIP( hipMemcpy( c->tsRecords, s.rec.data(), sizeof( TimestampRecord ) * batch, hipMemcpyHostToDevice ) );
+	if( c->boostOn ) WH_HIP( hipMemcpy( c->boostStates, s.boost.data(), sizeof( int32_t ) * batch, hipMemcpyHostToDevice ) );
 	return 0;
 }
 
@@ -573,6 +588,8 @@ int wh_decode_greedy( wh_context* c, int batch, const int32_t* firstTokens, int 
 	if( stepsReplayable( c ) ) WH_CHECK( obtainStepGraph( c, batch, stepKey( c, 0 ), WARM_PRESERVE, nullptr, step, exec ) );
 	// the first token is the caller's, not a sample: the records are armed, the history starts at this call's first sample
 	WH_CHECK( timestampRules( c, batch, 2 ) );
+	// the same for the phrases' history: every state becomes -1, armed. No launch: there is no row to boost yet, the first step boosts its own
+	if( c->boostOn ) WH_HIP( hipMemsetAsync( c->boostStates, 0xFF, sizeof( int32_t ) * (size_t)batch, st ) );
 	WH_CHECK( enqueueSteps( c, exec, nSteps, nPast + 1, step ) );
 	c->lastBatch = batch;
 	static_assert( sizeof( wh_token_data ) == sizeof( TokenData ), "token data layout" );
@@ -648,6 +665,7 @@ static int windowStart( wh_context* c, int batch, const int32_t* promptTokens, c
 	WH_CHECK( rcGraph );
 	{
 		WH_CHECK( timestampRules( c, batch, 1 ) );	 // a new window: no record survives into it, and the first sample is unfiltered
+		WH_CHECK( boostLogits( c, batch, 1 ) );		 // ... but boosted: the history is empty and the root's offers count for the first sample
 		WH_CHECK( sampleStep( c, batch, st ) );
 		WH_CHECK( launchAdvanceState( c->state, c->seqPos, batch, st ) );
 		c->noSpeechRows = 0;
@@ -883,6 +901,34 @@ int wh_context_set_timestamp_rules( wh_context* c, int on )
 	if( !c->tsRecords ) WH_CHECK( c->alloc( c->tsRecords, (int64_t)c->maxSeq, wh_context::MUST_BE_ZERO, "tsRecords" ) );
 	WH_HIP( hipStreamSynchronize( c->stream ) );
 	c->tsRules = true;
+	return 0;
+}
+
+// Phrase boosting. The set is compiled on the host (boost.hip) and uploaded behind what the stream holds; the tables and the states are
+// allocated once, before any capture, and the captured graphs are keyed on "a set is held". The call waits for the stream, so a chunk queued earlier has run
+// under the set it was enqueued with.
+int wh_context_set_boost( wh_context* c, const int32_t* tokens, const int32_t* lens, int count, int nMax, float boost )
+{
+	if( !c || count < 0 ) { setError( "context_set_boost: null context or a negative count" ); return WH_E_INVALIDARG; }
+	if( count == 0 )
+	{
+		if( c->boostOn ) { WH_BIND( c->m ); WH_HIP( hipStreamSynchronize( c->stream ) ); }
+		c->boostOn = false;
+		return 0;
+	}
+	if( c->hyp != 1 ) { setError( "context_set_boost: not available on a hypothesis-group context (the states do not follow the beam's reorder)" ); return WH_E_INVALIDARG; }
+	if( c->flags & WH_FLAG_PARITY_EXACT ) { setError( "context_set_boost: not available under WH_FLAG_PARITY_EXACT" ); return WH_E_INVALIDARG; }
+	const wh_hparams& hp = c->m->hp;
+	int64_t nInts = 0;
+	WH_CHECK( wh_boost_compile( tokens, lens, count, nMax, specialIds( hp ).sot - 1, hp.n_vocab, boost, nullptr, 0, &nInts ) );
+	std::vector<int32_t> up( (size_t)nInts );
+	WH_CHECK( wh_boost_compile( tokens, lens, count, nMax, specialIds( hp ).sot - 1, hp.n_vocab, boost, up.data(), nInts, &nInts ) );
+	WH_BIND( c->m );
+	if( !c->boostTables ) WH_CHECK( c->alloc( c->boostTables, (int64_t)BOOST_TABLE_INTS, wh_context::MUST_BE_ZERO, "boostTables" ) );
+	if( !c->boostStates ) WH_CHECK( c->alloc( c->boostStates, (int64_t)c->maxSeq, wh_context::MUST_BE_ZERO, "boostStates" ) );
+	WH_HIP( hipMemcpyAsync( c->boostTables, up.data(), sizeof( int32_t ) * up.size(), hipMemcpyHostToDevice, c->stream ) );
+	WH_HIP( hipStreamSynchronize( c->stream ) );	 // `up` is this call's
+	c->boostOn = true;
 	return 0;
 }
 

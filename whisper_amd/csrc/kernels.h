@@ -488,6 +488,18 @@ namespace wh
 	// One step of the filter on logits [rows][nVocab], in place: reset 0 folds fed[ row ] (device) into records[ row ] and writes -inf over the ranges the rules give,
 	// 1 makes every record the empty history and 2 arms it, both without touching the logits. The grid depends on the rows alone.
 	int launchTimestampRules( float* logits, int rows, int nVocab, int tokenEot, int tokenBeg, const int* fed, int reset, TimestampRecord* records, hipStream_t stream );
+	// Phrase boosting (wh_context_set_boost; DESIGN.md section 7 "Phrase boosting"). The automaton's flat tables are one int32 array, written by wh_boost_compile
+	// (boost.hip, where the layout is explained): a header of four, off [nodes + 1], tok [entries], next [entries]. The limits of one set:
+	constexpr int BOOST_MAX_PHRASES = 1024, BOOST_MAX_LEN = 16, BOOST_MAX_NODES = BOOST_MAX_PHRASES * BOOST_MAX_LEN + 1, BOOST_MAX_ENTRIES = 262144, BOOST_MAX_VOCAB = 65536;
+	struct BoostTables { int off, tok, next, total; };
+	constexpr BoostTables boostTables( int nodes, int entries ) { return BoostTables{ 4, 4 + nodes + 1, 4 + nodes + 1 + entries, 4 + nodes + 1 + 2 * entries }; }
+	constexpr int BOOST_TABLE_INTS = boostTables( BOOST_MAX_NODES, BOOST_MAX_ENTRIES ).total;	  // what a context allocates, once
+	constexpr int BOOST_THREADS = 256;
+	// One step of the filter on logits [rows][nVocab], in place. states [rows] (device): the node each row's history stands on, -1 = armed. reset 0 moves
+	// states[ row ] over fed[ row ] (an armed state, or a fed id outside [0, tokenEot), gives the root), 1 makes every state the root, 2 arms it; then in every case
+	// the boost is added ONCE to each token the new state offers (an armed state offers what the root does). tables holds tableInts int32 (device); every index read
+	// from it is held inside it. The grid depends on the rows alone.
+	int launchBoostLogits( float* logits, int rows, int nVocab, int tokenEot, const int* tables, int tableInts, const int* fed, int reset, int* states, hipStream_t stream );
 	int launchNoSpeechGather( const float* probs, const void* spreadScratch, int rows, int nVocab, int tokenSolm, float* out, hipStream_t stream );
 	// Prompt steps whose sequences differ in length (rows right-padded to nTok tokens): the normalised row of sequence b's LAST real
 	// token, lastPos[b] (device), is copied over its row nTok - 1, where the vocabulary product of a prompt step reads. In place, f16 rows.

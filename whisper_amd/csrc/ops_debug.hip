@@ -439,6 +439,17 @@ int wh_op_timestamp_rules( void* stream, float* logits, int rows, int nVocab, in
 	return launchTimestampRules( logits, rows, nVocab, tokenEot, tokenBeg, fedTokensDev, reset, (TimestampRecord*)recordsDev, (hipStream_t)stream );
 }
 
+int wh_op_boost_logits( void* stream, float* logits, int rows, int nVocab, int tokenEot, const int32_t* tablesDev, int64_t tableInts, const int32_t* fedTokensDev, int reset, int32_t* statesDev )
+{
+	if( !logits || !tablesDev || !statesDev || ( !reset && !fedTokensDev ) || rows < 1 || nVocab < 1 || nVocab > BOOST_MAX_VOCAB || tokenEot < 0 || tokenEot > nVocab ||
+		tableInts < 4 || tableInts > BOOST_TABLE_INTS || reset < 0 || reset > 2 )
+	{
+		setError( "boost_logits: null pointer, empty shape, more than 65536 columns, eot outside the row, tables of fewer than 4 ints or a reset outside 0 .. 2" );
+		return WH_E_INVALIDARG;
+	}
+	return launchBoostLogits( logits, rows, nVocab, tokenEot, tablesDev, (int)tableInts, fedTokensDev, reset, statesDev, (hipStream_t)stream );
+}
+
 int wh_op_lang_probs( void* stream, const float* logits, int rows, int nVocab, int tokenSot, int nLang, float* langP, int32_t* best )
 {
 	if( !logits || !langP || !best || rows < 1 || nVocab < 1 || nVocab > 52224 || nLang < 1 || nLang > 1024 || tokenSot < 0 || (int64_t)tokenSot + 1 + nLang > nVocab )
@@ -898,9 +909,13 @@ int wh_debug_probe( wh_context* c, int kind, int variant, int M, int N, int K, i
 		// Variant 4 = the filter of wh_context_set_timestamp_rules in front of the fused greedy sampler, 5 = that filter alone (tools/timestamp_rules_probe.py); K is
 		// the history the timed launch meets: 0 = text only, nothing masked; 1 = a closed pair, the timestamps masked (1501 columns); 2 = text then a timestamp, the
 		// text tokens and the earlier timestamps masked (the widest mask; an untimed launch that feeds a text token goes in front of every timed one).
+		// Variant 6 = the filter of wh_context_set_boost alone (tools/phrase_boost_probe.py); K is the set: 0 = one phrase of two tokens, 1 = 64 phrases, 2 = 1024
+		// phrases of two tokens with 1024 distinct first tokens. Every row has just sampled the first token of phrase 0, so the timed launch searches the fed token,
+		// boosts the node's offer and holds every root token against the node's table.
 		const int rows = M, nVocab = N;
-		if( rows < 1 || rows > 4096 || nVocab < 2048 || nVocab > 52224 || variant < 0 || variant > 5 ) return WH_E_INVALIDARG;
-		const bool tsr = variant >= 4;
+		if( rows < 1 || rows > 4096 || nVocab < 2048 || nVocab > 52224 || variant < 0 || variant > 6 ) return WH_E_INVALIDARG;
+		const bool tsr = variant == 4 || variant == 5, boostOnly = variant == 6;
+		if( boostOnly && ( K < 0 || K > 2 ) ) return WH_E_INVALIDARG;
 		if( tsr && ( K < 0 || K > 2 ) ) return WH_E_INVALIDARG;
 		const int nIds = ( variant == 2 || variant == 3 ) ? K : 0;
 		if( ( variant == 2 || variant == 3 ) && ( nIds < 1 || nIds > nVocab - 1607 ) ) return WH_E_INVALIDARG;
@@ -948,8 +963,29 @@ int wh_debug_probe( wh_context* c, int kind, int variant, int M, int N, int K, i
 			WH_HIP( hipMemcpy( fedTs, stamp.data(), sizeof( int ) * (size_t)rows, hipMemcpyHostToDevice ) );
 			WH_CHECK( launchTimestampRules( probs, rows, nVocab, sot - 1, beg, nullptr, 1, records, st ) );
 		}
+		int *boostTab = nullptr, *boostStates = nullptr, *boostFed = nullptr;
+		int boostInts = 0;
+		if( boostOnly )
+		{
+			const int nPhrases = K == 0 ? 1 : K == 1 ? 64 : 1024;
+			std::vector<int32_t> phr( (size_t)nPhrases * 2 ), lens( (size_t)nPhrases, 2 );
+			for( int i = 0; i < nPhrases; i++ ) { phr[ (size_t)2 * i ] = 100 + 37 * i; phr[ (size_t)2 * i + 1 ] = 50 + i; }
+			int64_t nInts = 0;
+			WH_CHECK( wh_boost_compile( phr.data(), lens.data(), nPhrases, 2, sot - 1, nVocab, 2.5f, nullptr, 0, &nInts ) );
+			std::vector<int32_t> tab( (size_t)nInts );
+			WH_CHECK( wh_boost_compile( phr.data(), lens.data(), nPhrases, 2, sot - 1, nVocab, 2.5f, tab.data(), nInts, &nInts ) );
+			boostInts = (int)nInts;
+			WH_CHECK( mem.alloc( &boostTab, sizeof( int ) * (size_t)nInts ) );
+			WH_CHECK( mem.alloc( &boostStates, sizeof( int ) * (size_t)rows ) );
+			WH_CHECK( mem.alloc( &boostFed, sizeof( int ) * (size_t)rows ) );
+			const std::vector<int> fedHost( (size_t)rows, phr[ 0 ] );
+			WH_HIP( hipMemcpy( boostTab, tab.data(), sizeof( int ) * (size_t)nInts, hipMemcpyHostToDevice ) );
+			WH_HIP( hipMemcpy( boostFed, fedHost.data(), sizeof( int ) * (size_t)rows, hipMemcpyHostToDevice ) );
+			WH_CHECK( launchBoostLogits( probs, rows, nVocab, sot - 1, boostTab, boostInts, nullptr, 1, boostStates, st ) );
+		}
 		const auto launch = [ & ]( float* x ) -> int
 		{
+			if( boostOnly ) return launchBoostLogits( x, rows, nVocab, sot - 1, boostTab, boostInts, boostFed, 0, boostStates, st );
 			if( tsr )
 			{
 				// K == 2: the untimed fold of a text token goes to the scratch row `probs`

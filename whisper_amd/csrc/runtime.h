@@ -215,6 +215,11 @@ struct wh_context
 	// and never again. Only the device-side loop launches it: wh_decode, wh_lang_detect, wh_align_tokens and the beam step do not.
 	bool tsRules = false;
 	TimestampRecord* tsRecords = nullptr;
+	// phrase boosting (wh_context_set_boost): boostOn = the prompt step of a window and every step of the device-side loop run one launch that moves the row's
+	// automaton state over the fed token and adds the boost to the offered columns of c->logits. boostTables [BOOST_TABLE_INTS] and boostStates [maxSeq] are
+	// allocated by the first non-empty call (before any capture) and never again; a captured step reads the tables and the boost from device memory.
+	bool boostOn = false;
+	int *boostTables = nullptr, *boostStates = nullptr;
 	// wh_context_set_no_speech: p[ solm ] of the prompt step's rows, gathered behind the first sample of every window (allocated by the first call that turns it on)
 	bool noSpeech = false;
 	float* noSpeechDev = nullptr;
@@ -436,7 +441,7 @@ namespace wh
 	int alignDebugRead( wh_context* c, const std::string& w, int layer, float* dstHost, int64_t dstCapFloats );
 
 	// captured decode steps (step_graph.hip, where each of these is explained)
-	constexpr uint32_t STEP_KEY_ROWS = 0x40000u, STEP_KEY_SUPPRESS = 0x80000u, STEP_KEY_TS_RULES = 0x100000u, STEP_KEY_BEAM = 0x200000u;
+	constexpr uint32_t STEP_KEY_ROWS = 0x40000u, STEP_KEY_SUPPRESS = 0x80000u, STEP_KEY_TS_RULES = 0x100000u, STEP_KEY_BEAM = 0x200000u, STEP_KEY_BOOST = 0x4000000u;
 	using StepFn = std::function<int()>;
 	enum eWarmUp { WARM_FRESH, WARM_PRESERVE };
 	bool stepsReplayable( const wh_context* c );
@@ -445,7 +450,7 @@ namespace wh
 	int idleLoopState( wh_context* c, int batch );
 	int enqueueSteps( wh_context* c, hipGraphExec_t exec, int nSteps, int firstKeys, const StepFn& step );
 	// what WARM_PRESERVE carries over the warm-up step: the list is stated next to the step that mutates it (decode.hip)
-	struct LoopState { DecodeState state; std::vector<int32_t> pos, tok; std::vector<TimestampRecord> rec; };
+	struct LoopState { DecodeState state; std::vector<int32_t> pos, tok; std::vector<TimestampRecord> rec; std::vector<int32_t> boost; };
 	int saveLoopState( wh_context* c, int batch, LoopState& s );
 	int restoreLoopState( wh_context* c, int batch, const LoopState& s );
 }

@@ -756,6 +756,86 @@ namespace wh
 			if( r.lastId > 0 ) fillNegInf( x, tokenBeg, min( open ? r.lastId : r.lastId + 1, nVocab ) );
 		}
 
+		// ---- phrase boosting (wh_context_set_boost; DESIGN.md section 7 "Phrase boosting") ----------------------
+		// logits[ row ][ t ] += boost for every token t that continues a phrase after some suffix of what the row has sampled since its last non-text token, one
+		// workgroup per row. The suffixes are one state of an Aho-Corasick automaton per row in device memory; the tables (boost.hip) fold the failure chains in, so
+		// the step is two searches: delta( n, t ) = n's entry, else the root's, else the root; offered( n ) = n's tokens and the root's.
+		// reset 0 (a step of the device-side loop): move the state over fed[ row ], the previous step's sample; an armed state (-1: the fed token is no sample) or a
+		// fed id that is no text token gives the root. reset 1 (the prompt step): the root. reset 2: armed. In all three the new state's offers are boosted.
+		// Every thread reads the state and the fed token, the barrier follows, and only then thread 0 writes the state back: no lane can see the new one.
+		// ONCE per token by construction: a node's tokens are distinct (ascending in the table), and a root token is added only when a search of the node's tokens
+		// does not find it -- so no two lanes of the launch store to one float, and plain loads and stores do. The header, the offsets and the nodes read from
+		// device memory are held to the limits of a set and every index into the tables to [0, cap): tables and states that are not a compiler's (the idle state a
+		// warm-up step runs on) cost wrong floats, never a fault.
+		__device__ __forceinline__ int boostLoad( const int* __restrict__ tables, int cap, int i )
+		{
+			return tables[ min( max( i, 0 ), cap - 1 ) ];
+		}
+		// the first entry of tok[ lo, hi ) that is not below t, hi when there is none (findEntry of boost.hip)
+		__device__ __forceinline__ int boostFind( const int* __restrict__ tables, int cap, int tokBase, int lo, int hi, int t )
+		{
+			while( lo < hi )
+			{
+				const int mid = lo + ( ( hi - lo ) >> 1 );
+				if( boostLoad( tables, cap, tokBase + mid ) < t ) lo = mid + 1;
+				else hi = mid;
+			}
+			return lo;
+		}
+		__global__ void __launch_bounds__( BOOST_THREADS ) boostLogitsKernel( float* __restrict__ logits, int nVocab, int tokenEot, const int* __restrict__ tables, int cap,
+			const int* __restrict__ fed, int reset, int* __restrict__ states )
+		{
+			const int row = blockIdx.x;
+			const int nodes = min( max( boostLoad( tables, cap, 0 ), 1 ), BOOST_MAX_NODES ), entries = min( max( boostLoad( tables, cap, 1 ), 0 ), BOOST_MAX_ENTRIES );
+			const float boost = __int_as_float( boostLoad( tables, cap, 2 ) );
+			const BoostTables L = boostTables( nodes, entries );
+			const auto span = [ & ]( int n, int& lo, int& hi )
+			{
+				lo = min( max( boostLoad( tables, cap, L.off + n ), 0 ), entries );
+				hi = min( max( boostLoad( tables, cap, L.off + n + 1 ), lo ), entries );
+			};
+			int rootLo, rootHi;
+			span( 0, rootLo, rootHi );
+			int state = reset == 2 ? -1 : 0;
+			if( !reset )
+			{
+				const int old = states[ row ];
+				const int tok = fed[ row ];
+				__syncthreads();
+				if( old >= 0 && tok >= 0 && tok < tokenEot )
+				{
+					int lo, hi;
+					span( min( old, nodes - 1 ), lo, hi );
+					int e = boostFind( tables, cap, L.tok, lo, hi, tok );
+					if( !( e < hi && boostLoad( tables, cap, L.tok + e ) == tok ) )
+					{
+						e = boostFind( tables, cap, L.tok, rootLo, rootHi, tok );
+						if( !( e < rootHi && boostLoad( tables, cap, L.tok + e ) == tok ) ) e = -1;
+					}
+					state = e < 0 ? 0 : min( max( boostLoad( tables, cap, L.next + e ), 0 ), nodes - 1 );
+				}
+			}
+			if( threadIdx.x == 0 ) states[ row ] = state;
+			float* const x = logits + (long long)row * nVocab;
+			const int lim = min( tokenEot, nVocab );	  // text tokens only, and inside the row
+			const int at = max( state, 0 );
+			int lo, hi;
+			span( at, lo, hi );
+			for( int e = lo + (int)threadIdx.x; e < hi; e += BOOST_THREADS )
+			{
+				const int t = boostLoad( tables, cap, L.tok + e );
+				if( (unsigned)t < (unsigned)lim ) x[ t ] = x[ t ] + boost;
+			}
+			if( at == 0 ) return;
+			for( int e = rootLo + (int)threadIdx.x; e < rootHi; e += BOOST_THREADS )
+			{
+				const int t = boostLoad( tables, cap, L.tok + e );
+				const int mine = boostFind( tables, cap, L.tok, lo, hi, t );
+				if( mine < hi && boostLoad( tables, cap, L.tok + mine ) == t ) continue;
+				if( (unsigned)t < (unsigned)lim ) x[ t ] = x[ t ] + boost;
+			}
+		}
+
 		bool drawShapeOk( int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot )
 		{
 			return rows >= 1 && nVocab >= 1 && nVocab <= SAMPLE_DRAW_MAX_VOCAB && tokenBeg >= 1 && tokenBeg < nVocab && tokenSot >= 0 && tokenSot < tokenBeg &&
@@ -808,6 +888,18 @@ namespace wh
 			return -1;
 		}
 		hipLaunchKernelGGL( timestampRulesKernel, dim3( rows ), dim3( TSR_THREADS ), 0, stream, logits, nVocab, tokenEot, tokenBeg, fed, reset, records );
+		WH_HIP( hipGetLastError() );
+		return 0;
+	}
+
+	int launchBoostLogits( float* logits, int rows, int nVocab, int tokenEot, const int* tables, int tableInts, const int* fed, int reset, int* states, hipStream_t stream )
+	{
+		if( !logits || !tables || !states || ( !reset && !fed ) || rows < 1 || nVocab < 1 || nVocab > BOOST_MAX_VOCAB || tokenEot < 0 || tokenEot > nVocab || tableInts < 4 || reset < 0 || reset > 2 )
+		{
+			setError( "boostLogits: bad argument" );
+			return -1;
+		}
+		hipLaunchKernelGGL( boostLogitsKernel, dim3( rows ), dim3( BOOST_THREADS ), 0, stream, logits, nVocab, tokenEot, tables, tableInts, fed, reset, states );
 		WH_HIP( hipGetLastError() );
 		return 0;
 	}

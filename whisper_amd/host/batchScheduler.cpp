@@ -25,6 +25,8 @@
 #include "batchSampling.h"
 #include "batchSuppress.h"
 #include "batchTimestampRules.h"
+#include "batchBoost.h"
+#include "phraseBoost.h"
 #include "decodeFallback.h"
 #include "languageDetect.h"
 #include "scoreRequest.h"
@@ -46,6 +48,8 @@ namespace Whisper
 	pfnBatchSuppress g_batchSuppress = nullptr;
 	// ... and for the timestamp rules (batchTimestampRules.h)
 	pfnBatchTimestampRules g_batchTimestampRules = nullptr;
+	// ... and for boosted phrases (batchBoost.h)
+	pfnBatchBoost g_batchBoost = nullptr;
 	// ... and to the scorer of given transcripts (scoreRequest.h)
 	pfnBatchScorer g_batchScorer = nullptr;
 
@@ -199,6 +203,8 @@ namespace Whisper
 			uint32_t suppressVersion = 0;
 			// timestamp rules: the version of the runner's switch this group's context holds (0 = never told: a new context has them off)
 			uint32_t timestampRulesVersion = 0;
+			// boosted phrases: the version of the runner's set this group's context holds (0 = never told: a new context holds none)
+			uint32_t boostVersion = 0;
 		};
 
 		// One call of iBatchRunner::run over the runner's groups (their wh_contexts outlive the call: KV caches, captured graphs)
@@ -683,7 +689,30 @@ namespace Whisper
 			// Whisper::setBatchTimestampRules: one switch for every stream; each group's context is told once, before the first round that follows a change
 			bool timestampRulesOn = false;
 			uint32_t timestampRulesVersion = 0;
+			// Whisper::setBatchBoostedPhrases: one set for every stream; each group's context is told once, before the first round that follows a change
+			phraseBoost::Set boostSet;
+			uint32_t boostVersion = 0;
 		public:
+			HRESULT setBoosted( const sBoostedPhrases* p )
+			{
+				phraseBoost::Set set;
+				std::string text;
+				if( p )
+					if( const char* const why = phraseBoost::check( p->tokens, p->lengths, p->count, p->maxLength, p->boost, model->vocab.token_eot, set, text ) )
+					{
+						logError( "setBatchBoostedPhrases: %s", why );
+						return E_INVALIDARG;
+					}
+				if( set.count() && !g_batchBoost )
+				{
+					logError( "setBatchBoostedPhrases: this build of the scheduler was not given the device's phrase filter" );
+					return E_NOTIMPL;
+				}
+				if( set.count() == 0 && boostSet.count() == 0 ) return S_OK;
+				boostSet = std::move( set );
+				boostVersion++;
+				return S_OK;
+			}
 			HRESULT setTimestampRulesMode( bool on )
 			{
 				if( on && !g_batchTimestampRules )
@@ -887,6 +916,12 @@ namespace Whisper
 						CHECK_WH( g_batchTimestampRules( g.gpu, timestampRulesOn ? 1 : 0 ) );
 						g.timestampRulesVersion = timestampRulesVersion;
 					}
+				for( Group& g : groups )
+					if( g.boostVersion != boostVersion && g_batchBoost )
+					{
+						CHECK_WH( g_batchBoost( g.gpu, boostSet.tokens.data(), boostSet.lens.data(), boostSet.count(), boostSet.nMax, boostSet.boost ) );
+						g.boostVersion = boostVersion;
+					}
 				if( modesDirty && !fallbackOn )
 				{
 					// the feature was turned off: the contexts go back to the greedy sampler and gather nothing
@@ -964,6 +999,17 @@ namespace Whisper
 			return E_INVALIDARG;
 		}
 		return r->setTimestampRulesMode( on );
+	}
+	HRESULT setBatchBoostedPhrases( iBatchRunner* runner, const sBoostedPhrases* phrases )
+	{
+		if( !runner ) return E_POINTER;
+		BatchRunner* const r = dynamic_cast<BatchRunner*>( runner );
+		if( !r )
+		{
+			logError( "setBatchBoostedPhrases: not a runner of this library's createBatchRunner" );
+			return E_INVALIDARG;
+		}
+		return r->setBoosted( phrases );
 	}
 	HRESULT getResultWindowStats( const iTranscribeResult* result, sWindowStats* stats, uint32_t* count )
 	{

@@ -20,6 +20,7 @@
 #include <thread>
 #include <vector>
 #include "subtitles.h"
+#include "phraseFile.h"
 using namespace Whisper;
 
 namespace
@@ -429,8 +430,10 @@ int main( int argc, char** argv )
 	// -tsr / --timestamp-rules (the same way): Whisper::setTimestampRules, openai-whisper's ApplyTimestampRules on the device
 	// --score FILE (the same way): instead of transcribing, Whisper::scoreTokens of the text in FILE against every input (a clip of 1 to 30 s): one line per
 	// token -- its time with --align (forced alignment), log-probability, rank, text -- and a summary line
-	bool align = false, useFallback = false, suppressNst = false, timestampRules = false;
-	std::string scoreFile;
+	// --boost-phrases FILE --boost N (the same way; one needs the other): Whisper::setBoostedPhrases with the spellings of the file's phrases, one per line
+	bool align = false, useFallback = false, suppressNst = false, timestampRules = false, haveBoost = false;
+	std::string scoreFile, boostFile;
+	float boost = 0.0f;
 	sDecodingFallback fallbackParams;
 	{
 		int kept = 1;
@@ -446,6 +449,12 @@ int main( int argc, char** argv )
 				if( i + 1 >= argc ) { fprintf( stderr, "error: --score needs a file\n" ); return 2; }
 				scoreFile = argv[ ++i ];
 			}
+			else if( !strcmp( argv[ i ], "--boost-phrases" ) )
+			{
+				if( i + 1 >= argc ) { fprintf( stderr, "error: --boost-phrases needs a file\n" ); return 2; }
+				boostFile = argv[ ++i ];
+			}
+			else if( !strcmp( argv[ i ], "--boost" ) ) { value = &boost; haveBoost = true; }
 			else if( !strcmp( argv[ i ], "-tpi" ) ) value = &fallbackParams.temperatureInc;
 			else if( !strcmp( argv[ i ], "-lpt" ) ) value = &fallbackParams.logprobThold;
 			else if( !strcmp( argv[ i ], "-et" ) ) value = &fallbackParams.entropyThold;
@@ -458,6 +467,11 @@ int main( int argc, char** argv )
 			}
 		}
 		argc = kept;
+	}
+	if( boostFile.empty() != !haveBoost )
+	{
+		fprintf( stderr, "error: --boost-phrases FILE and --boost N go together (there is no default boost)\n" );
+		return 2;
 	}
 	if( const int stop = parse( argc, argv, o ) ) return stop - 1;
 	if( dump ) { dumpOptions( o ); return 0; }
@@ -515,6 +529,16 @@ int main( int argc, char** argv )
 	{
 		hr = setTimestampRules( context, true );
 		if( FAILED( hr ) ) { printFailure( "failed to turn the timestamp rules on", hr ); return 6; }
+	}
+	if( !boostFile.empty() )
+	{
+		phraseFile::Rows rows;
+		std::string why;
+		hr = phraseFile::load( model, boostFile, rows, why );
+		if( FAILED( hr ) ) { printFailure( why.c_str(), hr ); return 6; }
+		const sBoostedPhrases set = rows.set( boost );
+		hr = setBoostedPhrases( context, &set );
+		if( FAILED( hr ) ) { printFailure( "failed to set the boosted phrases", hr ); return 6; }
 	}
 
 	ComLight::CComPtr<iMediaFoundation> media;

@@ -148,6 +148,8 @@ namespace Whisper
 		wh_comm* comm = nullptr, int root = 0 );
 	// only the vocabulary of a model file (no device needed)
 	HRESULT loadVocabulary( const std::string& path, Vocabulary& vocab );
+	// Whisper::phraseSpellings on a vocabulary (support.cpp; phraseBoost.h holds the rule)
+	HRESULT phraseSpellingsOf( const Vocabulary& vocab, const char* text, int32_t* tokens, int32_t* lengths, uint32_t* count );
 
 	// what runFullBatch needs from an iModel of this library: the loaded weights behind it
 	// {8c1f0d3a-52b7-4e0e-9a64-0f6d2b7c41e5}

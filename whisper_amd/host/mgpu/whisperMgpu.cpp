@@ -34,6 +34,7 @@
 #include <vector>
 #include "whisperApi.h"
 #include "whisper_hip.h"
+#include "../cli/phraseFile.h"
 using namespace Whisper;
 
 namespace
@@ -57,6 +58,10 @@ namespace
 		bool suppressNst = false;
 		// -tsr / --timestamp-rules: Whisper::setBatchTimestampRules on every rank's runner
 		bool timestampRules = false;
+		// -boost-phrases FILE -boost N (one needs the other): Whisper::setBatchBoostedPhrases on every rank's runner with the spellings of the file's phrases
+		std::string boostFile;
+		bool haveBoost = false;
+		float boost = 0.0f;
 	};
 	std::wstring widen( const std::string& s )
 	{
@@ -269,6 +274,16 @@ namespace
 			hr = setBatchTimestampRules( runner, true );
 			if( FAILED( hr ) ) { fprintf( stderr, "[rank %d] setBatchTimestampRules failed 0x%08x\n", rank, (unsigned)hr ); return 6; }
 		}
+		if( runner && !a.boostFile.empty() )
+		{
+			phraseFile::Rows rows;
+			std::string why;
+			hr = phraseFile::load( model, a.boostFile, rows, why );
+			if( FAILED( hr ) ) { fprintf( stderr, "[rank %d] %s 0x%08x\n", rank, why.c_str(), (unsigned)hr ); return 6; }
+			const sBoostedPhrases set = rows.set( a.boost );
+			hr = setBatchBoostedPhrases( runner, &set );
+			if( FAILED( hr ) ) { fprintf( stderr, "[rank %d] setBatchBoostedPhrases failed 0x%08x\n", rank, (unsigned)hr ); return 6; }
+		}
 
 		if( 0 != wh_comm_barrier( comm ) ) { fprintf( stderr, "[rank %d] %s\n", rank, wh_last_error() ); return 8; }
 		const double tStart = since();
@@ -418,6 +433,8 @@ int main( int argc, char** argv )
 		else if( !strcmp( argv[ i ], "-fallback" ) || !strcmp( argv[ i ], "--fallback" ) ) a.useFallback = true;
 		else if( !strcmp( argv[ i ], "-sns" ) || !strcmp( argv[ i ], "--suppress-nst" ) ) a.suppressNst = true;
 		else if( !strcmp( argv[ i ], "-tsr" ) || !strcmp( argv[ i ], "--timestamp-rules" ) ) a.timestampRules = true;
+		else if( !strcmp( argv[ i ], "-boost-phrases" ) || !strcmp( argv[ i ], "--boost-phrases" ) ) a.boostFile = val();
+		else if( !strcmp( argv[ i ], "-boost" ) || !strcmp( argv[ i ], "--boost" ) ) { a.boost = (float)atof( val() ); a.haveBoost = true; }
 		else if( !strcmp( argv[ i ], "-tpi" ) ) a.fallback.temperatureInc = (float)atof( val() );
 		else if( !strcmp( argv[ i ], "-lpt" ) ) a.fallback.logprobThold = (float)atof( val() );
 		else if( !strcmp( argv[ i ], "-et" ) ) a.fallback.entropyThold = (float)atof( val() );
@@ -454,6 +471,7 @@ int main( int argc, char** argv )
 		else { fputs( USAGE, stderr ); return 1; }
 	}
 	if( a.splitSilence && a.perRecording ) { fprintf( stderr, "whisper-mgpu: -split silence cuts ONE recording into chunks; -per-recording keeps recordings whole\n%s", USAGE ); return 1; }
+	if( a.boostFile.empty() != !a.haveBoost ) { fprintf( stderr, "whisper-mgpu: -boost-phrases FILE and -boost N go together (there is no default boost)\n" ); return 1; }
 	if( a.model.empty() || a.wav.empty() || a.ranks < 1 ) { fprintf( stderr, "whisper-mgpu: -m and -f are required\n" ); return 1; }
 	if( !a.perRecording && a.wavs.size() > 1 ) { fprintf( stderr, "whisper-mgpu: several -f recordings need -per-recording (the chunk mode shards ONE recording)\n" ); return 1; }
 	if( a.timeout <= 0 ) a.timeout = 300.0;

@@ -2,6 +2,7 @@
 #include "hostCommon.h"
 #include "ggmlTensor.h"
 #include "nonSpeechTokens.h"
+#include "phraseBoost.h"
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -490,5 +491,43 @@ namespace Whisper
 		if( cap < all.size() ) return E_BOUNDS;
 		std::copy( all.begin(), all.end(), ids );
 		return S_OK;
+	}
+
+	// Whisper::phraseSpellings on a vocabulary (phraseBoost.h holds the rule)
+	HRESULT phraseSpellingsOf( const Vocabulary& vocab, const char* text, int32_t* tokens, int32_t* lengths, uint32_t* count )
+	{
+		if( !text || !count ) return E_POINTER;
+		std::vector<std::vector<int>> rows;
+		std::string why;
+		const auto tokenize = [ & ]( const char* t, std::vector<int>& out ) { return SUCCEEDED( vocab.tokenize( t, out ) ); };
+		if( !phraseBoost::spellings( text, tokenize, rows, why ) )
+		{
+			logError( "phraseSpellings: %s", why.c_str() );
+			*count = 0;
+			return E_INVALIDARG;
+		}
+		const uint32_t cap = *count;
+		*count = (uint32_t)rows.size();
+		if( !tokens || !lengths ) return S_OK;
+		if( cap < rows.size() ) return E_BOUNDS;
+		for( size_t r = 0; r < rows.size(); r++ )
+		{
+			lengths[ r ] = (int32_t)rows[ r ].size();
+			for( size_t i = 0; i < phraseBoost::MAX_LENGTH; i++ ) tokens[ r * phraseBoost::MAX_LENGTH + i ] = i < rows[ r ].size() ? rows[ r ][ i ] : 0;
+		}
+		return S_OK;
+	}
+	HRESULT phraseSpellings( iModel* model, const char* text, int32_t* tokens, int32_t* lengths, uint32_t* count )
+	{
+		if( !model || !text || !count ) return E_POINTER;
+		iModelInternals* in = nullptr;
+		if( FAILED( model->QueryInterface( iModelInternals::iid(), (void**)&in ) ) || !in )
+		{
+			logError( "phraseSpellings: the model was not created by this library" );
+			return E_INVALIDARG;
+		}
+		const HRESULT hr = phraseSpellingsOf( in->loaded()->vocab, text, tokens, lengths, count );
+		model->Release();	  // QueryInterface's reference
+		return hr;
 	}
 }

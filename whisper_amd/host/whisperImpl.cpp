@@ -12,6 +12,8 @@
 #include "batchSampling.h"
 #include "batchSuppress.h"
 #include "batchTimestampRules.h"
+#include "batchBoost.h"
+#include "phraseBoost.h"
 #include "languageDetect.h"
 #include "scoreRequest.h"
 #include "results.h"
@@ -132,6 +134,8 @@ namespace Whisper
 			std::vector<int32_t> suppressIds;
 			// Whisper::setTimestampRules: off unless set. The stream's device context holds the mode; the hypothesis-group context of beam search cannot (runFull refuses)
 			bool timestampRulesOn = false;
+			// Whisper::setBoostedPhrases: off unless set. The stream's device context holds the set; the hypothesis-group context of beam search cannot (runFull refuses)
+			bool boostOn = false;
 
 			using Clock = std::chrono::steady_clock;
 			static double msSince( Clock::time_point t ) { return std::chrono::duration<double, std::milli>( Clock::now() - t ).count(); }
@@ -260,6 +264,20 @@ namespace Whisper
 			{
 				CHECK_WH( wh_context_set_timestamp_rules( gpu, on ? 1 : 0 ) );
 				timestampRulesOn = on;
+				return S_OK;
+			}
+			HRESULT setBoosted( const sBoostedPhrases* p )
+			{
+				phraseBoost::Set set;
+				std::string text;
+				if( p )
+					if( const char* const why = phraseBoost::check( p->tokens, p->lengths, p->count, p->maxLength, p->boost, model->vocab.token_eot, set, text ) )
+					{
+						logError( "setBoostedPhrases: %s", why );
+						return E_INVALIDARG;
+					}
+				CHECK_WH( wh_context_set_boost( gpu, set.tokens.data(), set.lens.data(), set.count(), set.nMax, set.boost ) );
+				boostOn = set.count() > 0;
 				return S_OK;
 			}
 			const std::vector<sWindowStats>& lastWindowStats() const { return windowStats; }
@@ -887,6 +905,12 @@ namespace Whisper
 				logError( "runFull: the timestamp rules (setTimestampRules) are not available with eSamplingStrategy::BeamSearch" );
 				return E_NOTIMPL;
 			}
+			// boosted phrases: the device-side loop only (the per-sequence states would have to follow the beam's parent reorder: a follow-up)
+			if( boostOn && params.strategy == eSamplingStrategy::BeamSearch && params.beam_search.beam_width >= 1 )
+			{
+				logError( "runFull: boosted phrases (setBoostedPhrases) are not available with eSamplingStrategy::BeamSearch" );
+				return E_NOTIMPL;
+			}
 			StreamRun run( params, vocab, hp, this, progress, resultAll, promptPast, &stamper );
 			// the run's audio is current until this function returns; the stereo PCM is the caller's and is not referred to afterwards
 			struct CurrentRun
@@ -1230,6 +1254,8 @@ namespace Whisper
 	static const bool g_suppressInstalled = ( g_batchSuppress = &wh_context_set_suppress, true );
 	// ... and to the timestamp rules (batchTimestampRules.h)
 	static const bool g_timestampRulesInstalled = ( g_batchTimestampRules = &wh_context_set_timestamp_rules, true );
+	// ... and to the phrase filter (batchBoost.h)
+	static const bool g_boostInstalled = ( g_batchBoost = &wh_context_set_boost, true );
 	// ... and to the scorer of given transcripts (scoreRequest.h)
 	static const bool g_scorerInstalled = ( g_batchScorer = &wh_score_tokens, true );
 
@@ -1288,6 +1314,17 @@ namespace Whisper
 			return E_INVALIDARG;
 		}
 		return c->setTimestampRulesMode( on );
+	}
+	HRESULT setBoostedPhrases( iContext* context, const sBoostedPhrases* phrases )
+	{
+		if( !context ) return E_POINTER;
+		ContextImpl* const c = dynamic_cast<ContextImpl*>( context );
+		if( !c )
+		{
+			logError( "setBoostedPhrases: not a context of this library's createContext (a batch runner takes setBatchBoostedPhrases)" );
+			return E_INVALIDARG;
+		}
+		return c->setBoosted( phrases );
 	}
 	HRESULT contextScoreClip( iContext* context, const float* pcm, int64_t nSamples, const int32_t* tokens, int32_t len, int32_t firstScored, wh_token_score* recs, int32_t* frames )
 	{
@@ -1512,6 +1549,25 @@ WHISPER_EXPORT int32_t whisperc_batch_set_suppress_tokens( void* runner, const i
 {
 	if( !runner ) return E_POINTER;
 	return setBatchSuppressedTokens( (iBatchRunner*)runner, ids, count );
+}
+// Whisper::setBoostedPhrases / setBatchBoostedPhrases / phraseSpellings: count == 0 turns boosting off (the pointers may be NULL)
+WHISPER_EXPORT int32_t whisperc_set_boost_phrases( void* ctx, const int32_t* tokens, const int32_t* lens, uint32_t count, uint32_t nMax, float boost )
+{
+	if( !ctx ) return E_POINTER;
+	const sBoostedPhrases p{ tokens, lens, count, nMax, boost };
+	return setBoostedPhrases( (iContext*)ctx, count ? &p : nullptr );
+}
+WHISPER_EXPORT int32_t whisperc_batch_set_boost_phrases( void* runner, const int32_t* tokens, const int32_t* lens, uint32_t count, uint32_t nMax, float boost )
+{
+	if( !runner ) return E_POINTER;
+	const sBoostedPhrases p{ tokens, lens, count, nMax, boost };
+	return setBatchBoostedPhrases( (iBatchRunner*)runner, count ? &p : nullptr );
+}
+WHISPER_EXPORT int32_t whisperc_phrase_spellings( void* model, const char* text, int32_t* tokens, int32_t* lens, uint32_t cap, uint32_t* count )
+{
+	if( !model || !count ) return E_POINTER;
+	*count = cap;
+	return phraseSpellings( (iModel*)model, text, tokens, lens, count );
 }
 // Whisper::setTimestampRules / setBatchTimestampRules
 WHISPER_EXPORT int32_t whisperc_set_timestamp_rules( void* ctx, int32_t on )
@@ -2057,6 +2113,16 @@ WHISPER_EXPORT int32_t whisperc_debug_tokenize( const char* modelPath, const cha
 	if( (int)toks.size() > cap ) return E_BOUNDS;
 	for( size_t i = 0; i < toks.size(); i++ ) out[ i ] = toks[ i ];
 	return (int32_t)toks.size();
+}
+// Whisper::phraseSpellings on the vocabulary of a model file (host only): the arguments of whisperc_phrase_spellings
+WHISPER_EXPORT int32_t whisperc_debug_phrase_spellings( const char* modelPath, const char* text, int32_t* tokens, int32_t* lens, uint32_t cap, uint32_t* count )
+{
+	if( !modelPath || !count ) return E_POINTER;
+	Whisper::Vocabulary vocab;
+	const HRESULT hr = Whisper::loadVocabulary( modelPath, vocab );
+	if( FAILED( hr ) ) return hr;
+	*count = cap;
+	return Whisper::phraseSpellingsOf( vocab, text, tokens, lens, count );
 }
 WHISPER_EXPORT int32_t whisperc_debug_token_string( const char* modelPath, int32_t token, char* out, uint32_t outCap, int32_t* specials8 )
 {
