@@ -26,7 +26,7 @@
 #include "batchSuppress.h"
 #include "batchTimestampRules.h"
 #include "batchBoost.h"
-#include "phraseBoost.h"
+#include "optionRules.h"
 #include "decodeFallback.h"
 #include "languageDetect.h"
 #include "scoreRequest.h"
@@ -693,21 +693,12 @@ namespace Whisper
 			phraseBoost::Set boostSet;
 			uint32_t boostVersion = 0;
 		public:
+			// The setters answer in one order: the argument check (optionRules.h), E_NOTIMPL without the device entry, "nothing changes", then the new version
 			HRESULT setBoosted( const sBoostedPhrases* p )
 			{
 				phraseBoost::Set set;
-				std::string text;
-				if( p )
-					if( const char* const why = phraseBoost::check( p->tokens, p->lengths, p->count, p->maxLength, p->boost, model->vocab.token_eot, set, text ) )
-					{
-						logError( "setBatchBoostedPhrases: %s", why );
-						return E_INVALIDARG;
-					}
-				if( set.count() && !g_batchBoost )
-				{
-					logError( "setBatchBoostedPhrases: this build of the scheduler was not given the device's phrase filter" );
-					return E_NOTIMPL;
-				}
+				CHECK( optionRules::checkBoosted( "setBatchBoostedPhrases", p, model->vocab.token_eot, set ) );
+				if( set.count() && !g_batchBoost ) return optionRules::notGiven( "setBatchBoostedPhrases", "phrase filter" );
 				if( set.count() == 0 && boostSet.count() == 0 ) return S_OK;
 				boostSet = std::move( set );
 				boostVersion++;
@@ -715,11 +706,7 @@ namespace Whisper
 			}
 			HRESULT setTimestampRulesMode( bool on )
 			{
-				if( on && !g_batchTimestampRules )
-				{
-					logError( "setBatchTimestampRules: this build of the scheduler was not given the device's timestamp filter" );
-					return E_NOTIMPL;
-				}
+				if( on && !g_batchTimestampRules ) return optionRules::notGiven( "setBatchTimestampRules", "timestamp filter" );
 				if( on == timestampRulesOn ) return S_OK;
 				timestampRulesOn = on;
 				timestampRulesVersion++;
@@ -727,18 +714,8 @@ namespace Whisper
 			}
 			HRESULT setSuppressed( const int32_t* ids, uint32_t count )
 			{
-				if( count && !ids ) return E_POINTER;
-				for( uint32_t i = 0; i < count; i++ )
-					if( ids[ i ] < 0 || ids[ i ] >= model->vocab.token_eot )
-					{
-						logError( "setBatchSuppressedTokens: id %i is outside [ 0, %i ): only text tokens can be suppressed", (int)ids[ i ], model->vocab.token_eot );
-						return E_INVALIDARG;
-					}
-				if( count && !g_batchSuppress )
-				{
-					logError( "setBatchSuppressedTokens: this build of the scheduler was not given the device's logit filter" );
-					return E_NOTIMPL;
-				}
+				CHECK( optionRules::checkSuppressed( "setBatchSuppressedTokens", ids, count, model->vocab.token_eot ) );
+				if( count && !g_batchSuppress ) return optionRules::notGiven( "setBatchSuppressedTokens", "logit filter" );
 				if( count == 0 && suppressIds.empty() ) return S_OK;
 				suppressIds.assign( ids, ids + count );
 				suppressVersion++;
@@ -747,17 +724,8 @@ namespace Whisper
 			HRESULT setFallback( const sDecodingFallback* p )
 			{
 				if( !p ) { fallbackOn = false; return S_OK; }
-				const bool nan = std::isnan( p->temperatureInc ) || std::isnan( p->logprobThold ) || std::isnan( p->entropyThold ) || std::isnan( p->noSpeechThold );
-				if( nan || ( p->temperatureInc > 0.0f && p->temperatureInc < 0.01f ) )
-				{
-					logError( "setBatchDecodingFallback: a threshold is NaN, or temperatureInc lies in ( 0, 0.01 )" );
-					return E_INVALIDARG;
-				}
-				if( !g_batchSamplingHooks )
-				{
-					logError( "setBatchDecodingFallback: this build of the scheduler was not given the device's per-row sampler" );
-					return E_NOTIMPL;
-				}
+				CHECK( optionRules::checkFallback( "setBatchDecodingFallback", *p ) );
+				if( !g_batchSamplingHooks ) return optionRules::notGiven( "setBatchDecodingFallback", "per-row sampler" );
 				fallbackParams = *p;
 				fallbackOn = true;
 				return S_OK;
@@ -796,11 +764,7 @@ namespace Whisper
 			HRESULT score( const sScoreRequest* requests, uint32_t count, sTokenScore* const* scores, HRESULT* perRequest )
 			{
 				if( count && ( !requests || !scores ) ) return E_POINTER;
-				if( !g_batchScorer )
-				{
-					logError( "scoreBatch: this build of the scheduler was not given the device's scorer" );
-					return E_NOTIMPL;
-				}
+				if( !g_batchScorer ) return optionRules::notGiven( "scoreBatch", "scorer" );
 				const score::Limits lim{ model->hp.n_vocab, model->vocab.token_eot, model->vocab.token_not, model->hp.n_text_ctx };
 				std::vector<HRESULT> status( count, S_OK );
 				std::vector<score::Row> rows( count );
@@ -904,24 +868,25 @@ namespace Whisper
 				// one sFullParams for every stream of the batch: its audio_ctx is the groups' (ContextImpl.cpp:488-489)
 				if( params.audio_ctx < 0 || params.audio_ctx > model->hp.n_audio_ctx ) return E_INVALIDARG;
 				for( Group& g : groups ) CHECK_WH( wh_context_set_audio_ctx( g.gpu, params.audio_ctx ) );
+				// a context is told what changed since it was last told: the set, the rules, the phrases
 				for( Group& g : groups )
+				{
 					if( g.suppressVersion != suppressVersion && g_batchSuppress )
 					{
 						CHECK_WH( g_batchSuppress( g.gpu, suppressIds.data(), (int)suppressIds.size() ) );
 						g.suppressVersion = suppressVersion;
 					}
-				for( Group& g : groups )
 					if( g.timestampRulesVersion != timestampRulesVersion && g_batchTimestampRules )
 					{
 						CHECK_WH( g_batchTimestampRules( g.gpu, timestampRulesOn ? 1 : 0 ) );
 						g.timestampRulesVersion = timestampRulesVersion;
 					}
-				for( Group& g : groups )
 					if( g.boostVersion != boostVersion && g_batchBoost )
 					{
 						CHECK_WH( g_batchBoost( g.gpu, boostSet.tokens.data(), boostSet.lens.data(), boostSet.count(), boostSet.nMax, boostSet.boost ) );
 						g.boostVersion = boostVersion;
 					}
+				}
 				if( modesDirty && !fallbackOn )
 				{
 					// the feature was turned off: the contexts go back to the greedy sampler and gather nothing
@@ -941,16 +906,12 @@ namespace Whisper
 		};
 	}	// namespace
 
+	// the options of a runner: the public function on the BatchRunner behind `runner` (optionRules::forward)
+	static const char* const NOT_A_RUNNER = "not a runner of this library's createBatchRunner";
 	HRESULT runnerScore( iBatchRunner* runner, const sScoreRequest* requests, uint32_t count, sTokenScore* const* scores, HRESULT* perRequest )
 	{
-		if( !runner ) return E_POINTER;
-		BatchRunner* const r = dynamic_cast<BatchRunner*>( runner );
-		if( !r )
-		{
-			logError( "scoreBatch: not a runner of this library's createBatchRunner" );
-			return E_INVALIDARG;
-		}
-		return r->score( requests, count, scores, perRequest );
+		return optionRules::forward<BatchRunner>( runner, "scoreBatch", NOT_A_RUNNER, nullptr,
+			[ = ]( BatchRunner& r ) { return r.score( requests, count, scores, perRequest ); } );
 	}
 	HRESULT createBatchRunner( iModel* model, const sBatchSetup* setup, iBatchRunner** pp )
 	{
@@ -969,47 +930,23 @@ namespace Whisper
 
 	HRESULT setBatchDecodingFallback( iBatchRunner* runner, const sDecodingFallback* params )
 	{
-		if( !runner ) return E_POINTER;
-		BatchRunner* const r = dynamic_cast<BatchRunner*>( runner );
-		if( !r )
-		{
-			logError( "setBatchDecodingFallback: not a runner of this library's createBatchRunner" );
-			return E_INVALIDARG;
-		}
-		return r->setFallback( params );
+		return optionRules::forward<BatchRunner>( runner, "setBatchDecodingFallback", NOT_A_RUNNER, nullptr,
+			[ = ]( BatchRunner& r ) { return r.setFallback( params ); } );
 	}
 	HRESULT setBatchSuppressedTokens( iBatchRunner* runner, const int32_t* ids, uint32_t count )
 	{
-		if( !runner ) return E_POINTER;
-		BatchRunner* const r = dynamic_cast<BatchRunner*>( runner );
-		if( !r )
-		{
-			logError( "setBatchSuppressedTokens: not a runner of this library's createBatchRunner" );
-			return E_INVALIDARG;
-		}
-		return r->setSuppressed( ids, count );
+		return optionRules::forward<BatchRunner>( runner, "setBatchSuppressedTokens", NOT_A_RUNNER, nullptr,
+			[ = ]( BatchRunner& r ) { return r.setSuppressed( ids, count ); } );
 	}
 	HRESULT setBatchTimestampRules( iBatchRunner* runner, bool on )
 	{
-		if( !runner ) return E_POINTER;
-		BatchRunner* const r = dynamic_cast<BatchRunner*>( runner );
-		if( !r )
-		{
-			logError( "setBatchTimestampRules: not a runner of this library's createBatchRunner" );
-			return E_INVALIDARG;
-		}
-		return r->setTimestampRulesMode( on );
+		return optionRules::forward<BatchRunner>( runner, "setBatchTimestampRules", NOT_A_RUNNER, nullptr,
+			[ = ]( BatchRunner& r ) { return r.setTimestampRulesMode( on ); } );
 	}
 	HRESULT setBatchBoostedPhrases( iBatchRunner* runner, const sBoostedPhrases* phrases )
 	{
-		if( !runner ) return E_POINTER;
-		BatchRunner* const r = dynamic_cast<BatchRunner*>( runner );
-		if( !r )
-		{
-			logError( "setBatchBoostedPhrases: not a runner of this library's createBatchRunner" );
-			return E_INVALIDARG;
-		}
-		return r->setBoosted( phrases );
+		return optionRules::forward<BatchRunner>( runner, "setBatchBoostedPhrases", NOT_A_RUNNER, nullptr,
+			[ = ]( BatchRunner& r ) { return r.setBoosted( phrases ); } );
 	}
 	HRESULT getResultWindowStats( const iTranscribeResult* result, sWindowStats* stats, uint32_t* count )
 	{

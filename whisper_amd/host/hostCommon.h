@@ -167,4 +167,16 @@ namespace Whisper
 	HRESULT createContextImpl( const std::shared_ptr<LoadedModel>& model, iModel* owner, iContext** pp );
 	HRESULT createModelImpl( const std::shared_ptr<LoadedModel>& model, iModel** pp );
 	HRESULT createAudioBuffer( std::vector<float>&& mono, std::vector<float>&& stereo, iAudioBuffer** pp );
+
+	// ---- what flatApi.cpp takes from whisperImpl.cpp beyond whisperApi.h ----
+	// iContext::fullDefaultParams without a context
+	HRESULT defaultFullParams( eSamplingStrategy strategy, sFullParams* rdi );
+	// a reader over PCM that is decoded already: what loadAudioFileData makes of a WAV image, with the caller's stereo PCM
+	HRESULT createPcmReader( std::vector<float>&& mono, std::vector<float>&& stereo, iAudioReader** pp );
+	// eSamplingStrategy::BeamSearch: candidates ranked on the host after every step (the checker) instead of on the device
+	void setBeamRankingOnHost( bool onHost );
+	// methods of ContextImpl that are not part of iContext's vtable; ctx is an iContext of this library
+	HRESULT contextDetectLanguage( void* ctx, const float* pcm, uint32_t nSamples, int offsetMs, float* probs, uint32_t probsCap, int& langId );
+	int contextDetectedLanguage( void* ctx, float& p );
+	HRESULT contextSetDeviceFlags( void* ctx, uint32_t flags, int parityThreads );
 }
