@@ -448,6 +448,15 @@ namespace Whisper
 	// One set for all streams of every later run of the runner. E_INVALIDARG as above; E_NOTIMPL for a non-empty set where the scheduler was built without the
 	// device's filter.
 	WHISPER_EXPORT HRESULT setBatchBoostedPhrases( iBatchRunner* runner, const sBoostedPhrases* phrases );
+	// Extension: no-repeat n-grams, Hugging Face generation's no_repeat_ngram_size restricted to text tokens, applied to the logits on the device in every step of
+	// the decoding loop. n = 0: off, the state of every new context; 1 .. 8: a text token cannot be sampled when it would complete an n-gram that the tokens sampled
+	// in the current window, timestamps included, already hold. eot and the timestamps are never forbidden, the prompt does not count, and no history survives into
+	// the next window. It holds for greedy runs and for the sampled attempts of the decoding fallback. There is no default n. With n != 0 a run with
+	// eSamplingStrategy::BeamSearch answers E_NOTIMPL (the per-sequence history would have to follow the beam's reorder); language detection, scoring and
+	// eFullParamsFlags::AlignTokens read unfiltered passes as before. E_INVALIDARG for n outside 0 .. 8 and for a context of another library.
+	WHISPER_EXPORT HRESULT setNoRepeatNgram( iContext* context, int n );
+	// One n for all streams of every later run of the runner. E_INVALIDARG as above; E_NOTIMPL for n != 0 where the scheduler was built without the device's filter.
+	WHISPER_EXPORT HRESULT setBatchNoRepeatNgram( iBatchRunner* runner, int n );
 	// One text phrase as rows for sBoostedPhrases: the text as written and, when it does not begin with a space, also the text behind one space, which is how a
 	// word is spelled in mid-sentence; rows that come out equal collapse. tokens [ cap ][ 16 ], lengths [ cap ]; count in: cap, out: the rows written (1 or 2);
 	// E_BOUNDS when cap is too small. E_INVALIDARG, the log naming the phrase, when a spelling is empty or longer than 16 tokens.

@@ -94,6 +94,10 @@ int32_t whisperc_batch_set_suppress_tokens( void* runner, const int32_t* ids, ui
 int32_t whisperc_set_boost_phrases( void* ctx, const int32_t* tokens, const int32_t* lens, uint32_t count, uint32_t nMax, float boost );
 int32_t whisperc_batch_set_boost_phrases( void* runner, const int32_t* tokens, const int32_t* lens, uint32_t count, uint32_t nMax, float boost );
 int32_t whisperc_phrase_spellings( void* model, const char* text, int32_t* tokens, int32_t* lens, uint32_t cap, uint32_t* count );
+/* No-repeat n-grams (Whisper::setNoRepeatNgram / setBatchNoRepeatNgram of whisperApi.h): n = 1 .. 8 = every later run forbids a text token that would complete an
+ * n-gram its window has already sampled; 0 = off, the state of every new context and runner. */
+int32_t whisperc_set_no_repeat_ngram( void* ctx, int32_t n );
+int32_t whisperc_batch_set_no_repeat_ngram( void* runner, int32_t n );
 /* Timestamp rules (Whisper::setTimestampRules / setBatchTimestampRules of whisperApi.h): on != 0 = every later run masks the logits so that timestamps come in
  * pairs, never go back in time and close segments of non-zero length. Off is the state of every new context and runner. */
 int32_t whisperc_set_timestamp_rules( void* ctx, int32_t on );

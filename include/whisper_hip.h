@@ -539,6 +539,21 @@ WH_API int wh_boost_compile( const int32_t* tokens, const int32_t* lens, int cou
 /* Host only: the twin of one step of the kernel on one row. state: a node or -1 (armed); reset as in wh_op_boost_logits. *newState and row [nVocab] in place.
  * Every call validates the whole of `tables` first, O( entries ): a twin for tests and tools, not a hot path. */
 WH_API int wh_boost_step_host( const int32_t* tables, int64_t nInts, int32_t state, int32_t fed, int reset, float* row, int nVocab, int tokenEot, int32_t* newState );
+/* No-repeat n-grams (Hugging Face generation's no_repeat_ngram_size, restricted to text columns): n = 0 off, 1 .. 8 on. With h[ 0, L ) the tokens a row has
+ * sampled in the current window -- all of them, timestamps included, from the first sample behind the prompt -- the sample at position L finds -inf at every column
+ * t < eot for which some i in [ 0, L - n ] has h[ i, i + n - 1 ) == h[ L - n + 1, L ) and h[ i + n - 1 ] == t: emitting t would complete an n-gram the window already
+ * holds. With L < n nothing is masked; eot, the special ids and the timestamps are never masked, so a row always keeps mass and a window can always end; the prompt
+ * (text carried over from the previous window included) does not count and no history survives into the next window. n = 1: no text token twice in a window.
+ * The context keeps the history, n_text_ctx int32 per sequence, and a count per sequence in device memory. ONE small launch in front of the sampler appends the
+ * token just fed -- the previous step's sample -- and masks the row; the prompt step of a window empties the histories and masks nothing. It applies to
+ * wh_decode_greedy (the history starts at the call's first sample: firstTokens are not counted), wh_decode_window_start, _start_ragged and _continue, whatever the
+ * sampler: greedy, wh_context_set_sampling, wh_context_set_sampling_rows. Unfiltered: wh_decode, wh_lang_detect, wh_align_tokens, wh_score_tokens and the beam step.
+ * The buffers, for maxSeq sequences, are allocated by the first call that turns the option on and never again. n is an argument of the kernel and the captured step
+ * graphs are keyed on it: a graph captured for one n never serves another, and a change of n captures again on the next window. The call waits for the stream: what
+ * was queued runs under the n it was queued with. WH_E_INVALIDARG for n outside 0 .. 8, and to turn it on on a hypothesis-group context (the histories would have
+ * to follow the beam's reorder) or under WH_FLAG_PARITY_EXACT (wh_context_set_flags in turn refuses that flag while the option is on). A context that never turns
+ * it on launches, allocates and captures what it always did. */
+WH_API int wh_context_set_no_repeat( wh_context* c, int n );
 WH_API int wh_context_set_no_speech( wh_context* c, int on );
 WH_API int wh_decode_window_no_speech( wh_context* c, float* out );
 
@@ -669,6 +684,14 @@ WH_API int wh_op_timestamp_rules( void* stream, float* logits, int rows, int nVo
  * float keeps its bits. Plain loads and stores: no atomics, no LDS; every index read from device memory is held inside its buffer. */
 WH_API int wh_op_boost_logits( void* stream, float* logits, int rows, int nVocab, int tokenEot, const int32_t* tablesDev, int64_t tableInts, const int32_t* fedTokensDev,
 	int reset, int32_t* statesDev );
+/* One step of the kernel of wh_context_set_no_repeat outside a context, on logits [rows][nVocab] in place. historyDev: DEVICE int32 [rows][cap], the tokens each row
+ * has sampled; countsDev: DEVICE int32 [rows], how many of them (-1 = armed). reset 0: fedDev[ row ] (DEVICE; the token each row sampled last) is appended to the
+ * row's history -- an armed row appends nothing and becomes the empty history, a full one (count == cap) drops the token -- and every column t < tokenEot that would
+ * complete an n-gram the history holds becomes -inf; every other float keeps its bits. reset 1: every history becomes empty; 2: armed; neither touches the logits,
+ * fedDev may be NULL. 1 <= n <= 8, 0 <= tokenEot <= nVocab, cap >= 1, or WH_E_INVALIDARG. Plain loads and stores: no atomics, no LDS; a count above cap or below
+ * -1, history entries and fed ids outside the row are held inside their buffers. */
+WH_API int wh_op_no_repeat_ngram( void* stream, float* logits, int rows, int nVocab, int tokenEot, int n, const int32_t* fedDev, int reset, int32_t* historyDev,
+	int32_t* countsDev, int cap );
 /* The language-detection kernel of wh_lang_detect on logits [rows][nVocab]: langP [rows][nLang] = the probabilities wh_op_vocab_soft_max gives at columns
  * tokenSot + 1 .. tokenSot + nLang, bit for bit, without writing the other columns; best [rows] = the index (0 .. nLang - 1) of the largest, exact ties
  * to the lower index. The row stays in registers: nVocab <= 52224; 1 <= nLang <= 1024 and the block inside the row, or WH_E_INVALIDARG. */

@@ -84,6 +84,8 @@ def lib():
         L.whisperc_batch_set_suppress_tokens.argtypes = [vp, vp, C.c_uint32]
         L.whisperc_set_boost_phrases.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_float]
         L.whisperc_batch_set_boost_phrases.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_float]
+        L.whisperc_set_no_repeat_ngram.argtypes = [vp, C.c_int32]
+        L.whisperc_batch_set_no_repeat_ngram.argtypes = [vp, C.c_int32]
         L.whisperc_phrase_spellings.argtypes = [vp, C.c_char_p, vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
         L.whisperc_debug_phrase_spellings.argtypes = [C.c_char_p, C.c_char_p, vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
         L.whisperc_set_timestamp_rules.argtypes = [vp, C.c_int32]
@@ -509,6 +511,12 @@ class Context:
         a = _suppress_ids(self.model, ids)
         _check(lib().whisperc_set_suppress_tokens(self.h, a.ctypes.data_as(C.c_void_p) if len(a) else None, len(a)), "setSuppressedTokens")
 
+    def set_no_repeat_ngram(self, n: Optional[int]):
+        """Whisper::setNoRepeatNgram (Hugging Face's no_repeat_ngram_size on text tokens): in every later run of this context -- greedy, and each sampled attempt
+        of the fallback -- a text token that would complete an n-gram the window has already sampled is forbidden on the device. n = 1 .. 8; 0 or None turns it
+        off, the state of a new context. There is no default n: none has been measured on a real checkpoint. With it on, beam search raises (E_NOTIMPL)."""
+        _check(lib().whisperc_set_no_repeat_ngram(self.h, int(n or 0)), "setNoRepeatNgram")
+
     def set_boost_phrases(self, phrases=None, boost: Optional[float] = None):
         """Whisper::setBoostedPhrases ("hotwords"): in every later run of this context -- greedy, and each sampled attempt of the fallback -- `boost` is added to
         the logit of every token that continues one of `phrases` after what was just emitted. phrases: strings (Model.phrase_spellings gives each its two
@@ -636,6 +644,10 @@ class BatchRunner:
         """Whisper::setBatchSuppressedTokens: Context.set_suppress_tokens for every stream of this runner's later runs (one set for all of them)."""
         a = _suppress_ids(self.model, ids)
         _check(lib().whisperc_batch_set_suppress_tokens(self.h, a.ctypes.data_as(C.c_void_p) if len(a) else None, len(a)), "setBatchSuppressedTokens")
+
+    def set_no_repeat_ngram(self, n: Optional[int]):
+        """Whisper::setBatchNoRepeatNgram: Context.set_no_repeat_ngram for every stream of this runner's later runs (one n for all of them)."""
+        _check(lib().whisperc_batch_set_no_repeat_ngram(self.h, int(n or 0)), "setBatchNoRepeatNgram")
 
     def set_boost_phrases(self, phrases=None, boost: Optional[float] = None):
         """Whisper::setBatchBoostedPhrases: Context.set_boost_phrases for every stream of this runner's later runs (one set and one boost for all of them)."""

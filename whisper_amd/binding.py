@@ -59,6 +59,7 @@ EXPORTS = [
     "wh_context_set_suppress", "wh_op_suppress_logits",
     "wh_context_set_timestamp_rules", "wh_op_timestamp_rules",
     "wh_context_set_boost", "wh_boost_compile", "wh_boost_step_host", "wh_op_boost_logits",
+    "wh_context_set_no_repeat", "wh_op_no_repeat_ngram",
     "wh_op_gemv_small", "wh_op_cross_split", "wh_op_self_block_dec",
     "wh_score_tokens", "wh_op_token_scores",
 ]
@@ -251,6 +252,8 @@ def lib():
         L.wh_boost_compile.argtypes = [vp, vp, i32, i32, i32, i32, C.c_float, vp, i64, C.POINTER(i64)]
         L.wh_boost_step_host.argtypes = [vp, i64, i32, i32, i32, vp, i32, i32, C.POINTER(C.c_int32)]
         L.wh_op_boost_logits.argtypes = [vp, vp, i32, i32, i32, vp, i64, vp, i32, vp]
+        L.wh_context_set_no_repeat.argtypes = [vp, i32]
+        L.wh_op_no_repeat_ngram.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, i32]
         L.wh_op_gemv_small.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, C.c_float]
         L.wh_op_cross_split.argtypes = [vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, i32, i32, i32, i32]
         L.wh_op_self_block_dec.argtypes = [vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, i32, i32, i32, i32, vp]
@@ -431,6 +434,11 @@ class HipContext:
     def set_timestamp_rules(self, on: bool):
         """on: every later step of the device-side loop masks the logits by openai-whisper's timestamp rules (pairs, non-decreasing, non-zero segments)."""
         check(lib().wh_context_set_timestamp_rules(self.handle, 1 if on else 0))
+
+    def set_no_repeat(self, n: int):
+        """No-repeat n-grams: n = 1 .. 8, every later step of the device-side loop masks the text tokens that would complete an n-gram the row has already sampled
+        in its window; 0 = off."""
+        check(lib().wh_context_set_no_repeat(self.handle, int(n)))
 
     def set_boost(self, phrases=None, boost: float = 0.0):
         """Phrase boosting: `boost` is added to the logits of every token that continues one of `phrases` (lists of 1 .. 16 text-token ids) after what the row

@@ -54,6 +54,18 @@ static int boostLogits( wh_context* c, int batch, int reset )
 		[ & ]() { return launchBoostLogits( c->logits, batch, hp.n_vocab, specialIds( hp ).sot - 1, c->boostTables, BOOST_TABLE_INTS, c->tokensDev, reset, c->boostStates, c->stream ); } );
 }
 
+// No-repeat n-grams (wh_context_set_no_repeat): the filter whose mask depends on everything each row has sampled in its window. Only the device-side loop calls
+// it, behind the boost and in front of the sampler -- the order among the filters does not change the row: this one and the two masks only write -inf, and
+// -inf + boost stays -inf. reset 1 behind a window's prompt step (the histories become empty, nothing is masked: the prompt does not count), 0 in every step
+// (c->tokensDev[ row ], the previous step's sample, is appended and the row masked), 2 in wh_decode_greedy. n is an argument of the kernel: stepKey holds it.
+static int noRepeat( wh_context* c, int batch, int reset )
+{
+	if( !c->noRepeatN ) return 0;
+	const wh_hparams& hp = c->m->hp;
+	return profiled( c, KC_SAMPLE, 0.0, 4.0 * batch * hp.n_text_ctx,
+		[ & ]() { return launchNoRepeat( c->logits, batch, hp.n_vocab, specialIds( hp ).sot - 1, c->noRepeatN, c->tokensDev, reset, c->nrnHistory, c->nrnCounts, hp.n_text_ctx, c->stream ); } );
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // decoder
 // ------------------------------------------------------------------------------------------------------------------
@@ -535,11 +547,12 @@ static int greedyStep( wh_context* c, int batch )
 	WH_CHECK( decodeGraph( c, batch, 1, 0, true ) );
 	WH_CHECK( timestampRules( c, batch, 0 ) );
 	WH_CHECK( boostLogits( c, batch, 0 ) );
+	WH_CHECK( noRepeat( c, batch, 0 ) );
 	WH_CHECK( sampleStep( c, batch, c->stream ) );
 	return launchAdvanceState( c->state, c->seqPos, batch, c->stream );
 }
 // Everything in device memory that a greedyStep mutates and a window in progress still needs (obtainStepGraph's WARM_PRESERVE; the stream is idle): the sampler
-// state, the positions, the fed tokens, -- when the rules are on -- the timestamp records and -- when a set of phrases is held -- the boost states. Per-row device state a later feature adds to the step joins HERE.
+// state, the positions, the fed tokens, -- when the rules are on -- the timestamp records, -- when a set of phrases is held -- the boost states and -- when no-repeat n-grams are on -- the histories and their counts. Per-row device state a later feature adds to the step joins HERE.
 // (The cache row and the sample the warm-up writes are rewritten by the first real step.)
 int wh::saveLoopState( wh_context* c, int batch, LoopState& s )
 {
@@ -552,6 +565,14 @@ int wh::saveLoopState( wh_context* c, int batch, LoopState& s )
 	if( c->tsRules ) WH_HIP( hipMemcpy( s.rec.data(), c->tsRecords, sizeof( TimestampRecord ) * batch, hipMemcpyDeviceToHost ) );
 	s.boost.resize( c->boostOn ? (size_t)batch : 0 );
 	if( c->boostOn ) WH_HIP( hipMemcpy( s.boost.data(), c->boostStates, sizeof( int32_t ) * batch, hipMemcpyDeviceToHost ) );
+	const size_t nrnInts = c->noRepeatN ? (size_t)batch * c->m->hp.n_text_ctx : 0;
+	s.nrnHistory.resize( nrnInts );
+	s.nrnCounts.resize( c->noRepeatN ? (size_t)batch : 0 );
+	if( c->noRepeatN )
+	{
+		WH_HIP( hipMemcpy( s.nrnHistory.data(), c->nrnHistory, sizeof( int32_t ) * nrnInts, hipMemcpyDeviceToHost ) );
+		WH_HIP( hipMemcpy( s.nrnCounts.data(), c->nrnCounts, sizeof( int32_t ) * batch, hipMemcpyDeviceToHost ) );
+	}
 	return 0;
 }
 int wh::restoreLoopState( wh_context* c, int batch, const LoopState& s )
@@ -561,6 +582,11 @@ int wh::restoreLoopState( wh_context* c, int batch, const LoopState& s )
 	WH_HIP( hipMemcpy( c->tokensDev, s.tok.data(), sizeof( int32_t ) * batch, hipMemcpyHostToDevice ) );
 	if( c->tsRules ) WH_HIP( hipMemcpy( c->tsRecords, s.rec.data(), sizeof( TimestampRecord ) * batch, hipMemcpyHostToDevice ) );
 	if( c->boostOn ) WH_HIP( hipMemcpy( c->boostStates, s.boost.data(), sizeof( int32_t ) * batch, hipMemcpyHostToDevice ) );
+	if( c->noRepeatN )
+	{
+		WH_HIP( hipMemcpy( c->nrnHistory, s.nrnHistory.data(), sizeof( int32_t ) * s.nrnHistory.size(), hipMemcpyHostToDevice ) );
+		WH_HIP( hipMemcpy( c->nrnCounts, s.nrnCounts.data(), sizeof( int32_t ) * batch, hipMemcpyHostToDevice ) );
+	}
 	return 0;
 }
 
@@ -590,6 +616,8 @@ int wh_decode_greedy( wh_context* c, int batch, const int32_t* firstTokens, int 
 	WH_CHECK( timestampRules( c, batch, 2 ) );
 	// the same for the phrases' history: every state becomes -1, armed. No launch: there is no row to boost yet, the first step boosts its own
 	if( c->boostOn ) WH_HIP( hipMemsetAsync( c->boostStates, 0xFF, sizeof( int32_t ) * (size_t)batch, st ) );
+	// ... and for the n-grams' history: armed, it starts empty at this call's first sample
+	WH_CHECK( noRepeat( c, batch, 2 ) );
 	WH_CHECK( enqueueSteps( c, exec, nSteps, nPast + 1, step ) );
 	c->lastBatch = batch;
 	static_assert( sizeof( wh_token_data ) == sizeof( TokenData ), "token data layout" );
@@ -666,6 +694,7 @@ static int windowStart( wh_context* c, int batch, const int32_t* promptTokens, c
 	{
 		WH_CHECK( timestampRules( c, batch, 1 ) );	 // a new window: no record survives into it, and the first sample is unfiltered
 		WH_CHECK( boostLogits( c, batch, 1 ) );		 // ... but boosted: the history is empty and the root's offers count for the first sample
+		WH_CHECK( noRepeat( c, batch, 1 ) );		 // the n-grams' history starts at this sample: the prompt does not count, nothing is masked yet
 		WH_CHECK( sampleStep( c, batch, st ) );
 		WH_CHECK( launchAdvanceState( c->state, c->seqPos, batch, st ) );
 		c->noSpeechRows = 0;
@@ -929,6 +958,30 @@ int wh_context_set_boost( wh_context* c, const int32_t* tokens, const int32_t* l
 	WH_HIP( hipMemcpyAsync( c->boostTables, up.data(), sizeof( int32_t ) * up.size(), hipMemcpyHostToDevice, c->stream ) );
 	WH_HIP( hipStreamSynchronize( c->stream ) );	 // `up` is this call's
 	c->boostOn = true;
+	return 0;
+}
+
+// No-repeat n-grams. The histories and counts are allocated once, before any capture; the captured graphs are keyed on n, which is an
+// argument of the kernel. The call waits for the stream, so a chunk queued earlier has run under the n it was enqueued with before the value changes.
+int wh_context_set_no_repeat( wh_context* c, int n )
+{
+	if( !c ) { setError( "context_set_no_repeat: null context" ); return WH_E_INVALIDARG; }
+	if( n < 0 || n > NRN_MAX_N ) { setError( "context_set_no_repeat: n outside 0 .. 8" ); return WH_E_INVALIDARG; }
+	if( n == c->noRepeatN ) return 0;
+	if( n == 0 )
+	{
+		WH_BIND( c->m );
+		WH_HIP( hipStreamSynchronize( c->stream ) );
+		c->noRepeatN = 0;
+		return 0;
+	}
+	if( c->hyp != 1 ) { setError( "context_set_no_repeat: not available on a hypothesis-group context (the histories do not follow the beam's reorder)" ); return WH_E_INVALIDARG; }
+	if( c->flags & WH_FLAG_PARITY_EXACT ) { setError( "context_set_no_repeat: not available under WH_FLAG_PARITY_EXACT" ); return WH_E_INVALIDARG; }
+	WH_BIND( c->m );
+	if( !c->nrnHistory ) WH_CHECK( c->alloc( c->nrnHistory, (int64_t)c->maxSeq * c->m->hp.n_text_ctx, wh_context::MUST_BE_ZERO, "nrnHistory" ) );
+	if( !c->nrnCounts ) WH_CHECK( c->alloc( c->nrnCounts, (int64_t)c->maxSeq, wh_context::MUST_BE_ZERO, "nrnCounts" ) );
+	WH_HIP( hipStreamSynchronize( c->stream ) );
+	c->noRepeatN = n;
 	return 0;
 }
 

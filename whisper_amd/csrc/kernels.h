@@ -500,6 +500,13 @@ namespace wh
 	// the boost is added ONCE to each token the new state offers (an armed state offers what the root does). tables holds tableInts int32 (device); every index read
 	// from it is held inside it. The grid depends on the rows alone.
 	int launchBoostLogits( float* logits, int rows, int nVocab, int tokenEot, const int* tables, int tableInts, const int* fed, int reset, int* states, hipStream_t stream );
+	// No-repeat n-grams (wh_context_set_no_repeat; DESIGN.md section 7 "No-repeat n-grams"). history [rows][cap] (device): the tokens each row has sampled in this
+	// window, timestamps included; counts [rows]: how many of them, -1 = armed (the next fed token is no sample and is not appended). n is 1 .. NRN_MAX_N.
+	constexpr int NRN_MAX_N = 8, NRN_THREADS = 256;
+	// One step of the filter on logits [rows][nVocab], in place: reset 0 appends fed[ row ] (device) to the row's history -- a full history drops it -- and writes -inf
+	// to every column t < tokenEot that would complete an n-gram the history already holds; 1 empties every history and 2 arms it, both without touching the logits.
+	// Every index read from device memory is held inside the row's history and inside the row. The grid depends on the rows alone.
+	int launchNoRepeat( float* logits, int rows, int nVocab, int tokenEot, int n, const int* fed, int reset, int* history, int* counts, int cap, hipStream_t stream );
 	int launchNoSpeechGather( const float* probs, const void* spreadScratch, int rows, int nVocab, int tokenSolm, float* out, hipStream_t stream );
 	// Prompt steps whose sequences differ in length (rows right-padded to nTok tokens): the normalised row of sequence b's LAST real
 	// token, lastPos[b] (device), is copied over its row nTok - 1, where the vocabulary product of a prompt step reads. In place, f16 rows.

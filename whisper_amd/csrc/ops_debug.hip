@@ -450,6 +450,16 @@ int wh_op_boost_logits( void* stream, float* logits, int rows, int nVocab, int t
 	return launchBoostLogits( logits, rows, nVocab, tokenEot, tablesDev, (int)tableInts, fedTokensDev, reset, statesDev, (hipStream_t)stream );
 }
 
+int wh_op_no_repeat_ngram( void* stream, float* logits, int rows, int nVocab, int tokenEot, int n, const int32_t* fedDev, int reset, int32_t* historyDev, int32_t* countsDev, int cap )
+{
+	if( !logits || !historyDev || !countsDev || ( !reset && !fedDev ) || rows < 1 || nVocab < 1 || tokenEot < 0 || tokenEot > nVocab || n < 1 || n > NRN_MAX_N || reset < 0 || reset > 2 || cap < 1 )
+	{
+		setError( "no_repeat_ngram: null pointer, empty shape, eot outside the row, n outside 1 .. 8, a reset outside 0 .. 2 or a history without room" );
+		return WH_E_INVALIDARG;
+	}
+	return launchNoRepeat( logits, rows, nVocab, tokenEot, n, fedDev, reset, historyDev, countsDev, cap, (hipStream_t)stream );
+}
+
 int wh_op_lang_probs( void* stream, const float* logits, int rows, int nVocab, int tokenSot, int nLang, float* langP, int32_t* best )
 {
 	if( !logits || !langP || !best || rows < 1 || nVocab < 1 || nVocab > 52224 || nLang < 1 || nLang > 1024 || tokenSot < 0 || (int64_t)tokenSot + 1 + nLang > nVocab )
@@ -912,9 +922,14 @@ int wh_debug_probe( wh_context* c, int kind, int variant, int M, int N, int K, i
 		// Variant 6 = the filter of wh_context_set_boost alone (tools/phrase_boost_probe.py); K is the set: 0 = one phrase of two tokens, 1 = 64 phrases, 2 = 1024
 		// phrases of two tokens with 1024 distinct first tokens. Every row has just sampled the first token of phrase 0, so the timed launch searches the fed token,
 		// boosts the node's offer and holds every root token against the node's table.
+		// Variant 7 = the filter of wh_context_set_no_repeat with n = 3 in front of the fused greedy sampler, 8 = that filter alone (tools/no_repeat_probe.py); K is
+		// the length of the history the timed launch masks by, 3 .. 448, the fed token included: tokens of a five-letter alphabet, so every lane's n-gram recurs and
+		// stores. An untimed copy puts the counts back to K - 1 in front of every timed launch.
 		const int rows = M, nVocab = N;
-		if( rows < 1 || rows > 4096 || nVocab < 2048 || nVocab > 52224 || variant < 0 || variant > 6 ) return WH_E_INVALIDARG;
-		const bool tsr = variant == 4 || variant == 5, boostOnly = variant == 6;
+		if( rows < 1 || rows > 4096 || nVocab < 2048 || nVocab > 52224 || variant < 0 || variant > 8 ) return WH_E_INVALIDARG;
+		const bool tsr = variant == 4 || variant == 5, boostOnly = variant == 6, nrn = variant == 7 || variant == 8;
+		constexpr int nrnCap = 448, nrnN = 3;
+		if( nrn && ( K < nrnN || K > nrnCap ) ) return WH_E_INVALIDARG;
 		if( boostOnly && ( K < 0 || K > 2 ) ) return WH_E_INVALIDARG;
 		if( tsr && ( K < 0 || K > 2 ) ) return WH_E_INVALIDARG;
 		const int nIds = ( variant == 2 || variant == 3 ) ? K : 0;
@@ -983,8 +998,29 @@ int wh_debug_probe( wh_context* c, int kind, int variant, int M, int N, int K, i
 			WH_HIP( hipMemcpy( boostFed, fedHost.data(), sizeof( int ) * (size_t)rows, hipMemcpyHostToDevice ) );
 			WH_CHECK( launchBoostLogits( probs, rows, nVocab, sot - 1, boostTab, boostInts, nullptr, 1, boostStates, st ) );
 		}
+		int *nrnHistory = nullptr, *nrnCounts = nullptr, *nrnCounts0 = nullptr, *nrnFed = nullptr;
+		if( nrn )
+		{
+			WH_CHECK( mem.alloc( &nrnHistory, sizeof( int ) * (size_t)rows * nrnCap ) );
+			WH_CHECK( mem.alloc( &nrnCounts, sizeof( int ) * (size_t)rows ) );
+			WH_CHECK( mem.alloc( &nrnCounts0, sizeof( int ) * (size_t)rows ) );
+			WH_CHECK( mem.alloc( &nrnFed, sizeof( int ) * (size_t)rows ) );
+			std::vector<int> hist( (size_t)rows * nrnCap );
+			for( size_t i = 0; i < hist.size(); i++ ) hist[ i ] = 100 + 37 * (int)( ( i % nrnCap ) % 5 );
+			const std::vector<int> counts0( (size_t)rows, K - 1 ), fedHost( (size_t)rows, 100 + 37 * ( ( K - 1 ) % 5 ) );
+			WH_HIP( hipMemcpy( nrnHistory, hist.data(), sizeof( int ) * hist.size(), hipMemcpyHostToDevice ) );
+			WH_HIP( hipMemcpy( nrnCounts0, counts0.data(), sizeof( int ) * (size_t)rows, hipMemcpyHostToDevice ) );
+			WH_HIP( hipMemcpy( nrnCounts, counts0.data(), sizeof( int ) * (size_t)rows, hipMemcpyHostToDevice ) );
+			WH_HIP( hipMemcpy( nrnFed, fedHost.data(), sizeof( int ) * (size_t)rows, hipMemcpyHostToDevice ) );
+		}
 		const auto launch = [ & ]( float* x ) -> int
 		{
+			if( nrn )
+			{
+				WH_CHECK( launchNoRepeat( x, rows, nVocab, sot - 1, nrnN, nrnFed, 0, nrnHistory, nrnCounts, nrnCap, st ) );
+				if( variant == 8 ) return 0;
+				return launchSoftMaxSample( x, probs, rows, nVocab, beg, sot, solm, tnot, state, out, next, noMail, st );
+			}
 			if( boostOnly ) return launchBoostLogits( x, rows, nVocab, sot - 1, boostTab, boostInts, boostFed, 0, boostStates, st );
 			if( tsr )
 			{
@@ -1005,6 +1041,7 @@ int wh_debug_probe( wh_context* c, int kind, int variant, int M, int N, int K, i
 		for( int i = 0; i < iters; i++ )
 		{
 			if( tsr && K == 2 ) WH_CHECK( launchTimestampRules( probs, rows, nVocab, sot - 1, beg, fedText, 0, records, st ) );
+			if( nrn ) WH_HIP( hipMemcpyAsync( nrnCounts, nrnCounts0, sizeof( int ) * (size_t)rows, hipMemcpyDeviceToDevice, st ) );
 			WH_HIP( hipEventRecord( e0, st ) );
 			WH_CHECK( launch( logits[ (size_t)( ( 5 + i ) % nBuf ) ] ) );
 			WH_HIP( hipEventRecord( e1, st ) );

@@ -220,6 +220,11 @@ struct wh_context
 	// allocated by the first non-empty call (before any capture) and never again; a captured step reads the tables and the boost from device memory.
 	bool boostOn = false;
 	int *boostTables = nullptr, *boostStates = nullptr;
+	// no-repeat n-grams (wh_context_set_no_repeat): noRepeatN != 0 = the prompt step of a window empties the histories and every step of the device-side loop runs one
+	// launch that appends the fed token to its row's history and masks the n-grams' completions in c->logits. nrnHistory [maxSeq][n_text_ctx] and nrnCounts [maxSeq]
+	// are allocated by the first call that turns the option on (before any capture) and never again. n is a kernel argument, so the captured graphs are keyed on it.
+	int noRepeatN = 0;
+	int *nrnHistory = nullptr, *nrnCounts = nullptr;
 	// wh_context_set_no_speech: p[ solm ] of the prompt step's rows, gathered behind the first sample of every window (allocated by the first call that turns it on)
 	bool noSpeech = false;
 	float* noSpeechDev = nullptr;
@@ -442,6 +447,7 @@ namespace wh
 
 	// captured decode steps (step_graph.hip, where each of these is explained)
 	constexpr uint32_t STEP_KEY_ROWS = 0x40000u, STEP_KEY_SUPPRESS = 0x80000u, STEP_KEY_TS_RULES = 0x100000u, STEP_KEY_BEAM = 0x200000u, STEP_KEY_BOOST = 0x4000000u;
+	constexpr uint32_t STEP_KEY_NO_REPEAT = 0x8000000u;	 // times n, 1 .. 8: bits 27-30
 	using StepFn = std::function<int()>;
 	enum eWarmUp { WARM_FRESH, WARM_PRESERVE };
 	bool stepsReplayable( const wh_context* c );
@@ -450,7 +456,7 @@ namespace wh
 	int idleLoopState( wh_context* c, int batch );
 	int enqueueSteps( wh_context* c, hipGraphExec_t exec, int nSteps, int firstKeys, const StepFn& step );
 	// what WARM_PRESERVE carries over the warm-up step: the list is stated next to the step that mutates it (decode.hip)
-	struct LoopState { DecodeState state; std::vector<int32_t> pos, tok; std::vector<TimestampRecord> rec; std::vector<int32_t> boost; };
+	struct LoopState { DecodeState state; std::vector<int32_t> pos, tok; std::vector<TimestampRecord> rec; std::vector<int32_t> boost, nrnHistory, nrnCounts; };
 	int saveLoopState( wh_context* c, int batch, LoopState& s );
 	int restoreLoopState( wh_context* c, int batch, const LoopState& s );
 }

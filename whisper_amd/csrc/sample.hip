@@ -836,6 +836,59 @@ namespace wh
 			}
 		}
 
+		// ---- no-repeat n-grams (wh_context_set_no_repeat; DESIGN.md section 7 "No-repeat n-grams") ----------------------
+		// logits[ row ][ t ] = -inf for every text token t (t < tokenEot) that would complete an n-gram the row has already sampled in this window: with h[ 0, L ) the
+		// history, every t = h[ i + n - 1 ] whose n - 1 predecessors h[ i, i + n - 1 ) equal the last n - 1 tokens h[ L - n + 1, L ), 0 <= i <= L - n. One workgroup per
+		// row; the history is one row of `history` [rows][cap] and one count per row in device memory.
+		// reset 0 (a step of the device-side loop): append fed[ row ], the previous step's sample, then mask. A count that is negative is armed: the fed token is no
+		// sample (wh_decode_greedy's first token), nothing is appended and the history starts empty. A full history (count == cap) drops the token and masks by what
+		// it holds. reset 1 (the prompt step): the history becomes empty and nothing is masked. reset 2: armed.
+		// Every thread reads the count and the fed token, the barrier follows, and only then thread 0 writes the token and the count back: no lane can see the new
+		// count, and the one history entry that is written in this launch, h[ old count ], is never loaded -- the lanes take it from the register that holds the fed token.
+		// Each lane owns start positions i: n - 1 compares against the suffix, which is wave-uniform and kept in registers, then one plain store. The history is
+		// under 2 KB per row and every lane reads each entry at most n times through L1 / L2; it is not staged in LDS. Several lanes may find the same t (an n-gram that
+		// occurs more than once) and store the same -inf to one float: intended, the result is the same whichever store lands last, as in suppressLogitsKernel with a
+		// repeated id. The count, the history entries and the fed id come from device memory: the count is held to [ -1, cap ], positions follow from it and stay inside
+		// [ 0, cap ), and a token is used as a column only inside [ 0, min( tokenEot, nVocab ) ). A record that is nobody's history (the idle state a warm-up step runs
+		// on) costs wrong floats, never a fault.
+		__global__ void __launch_bounds__( NRN_THREADS ) noRepeatKernel( float* __restrict__ logits, int nVocab, int tokenEot, int n, const int* __restrict__ fed, int reset,
+			int* __restrict__ history, int* __restrict__ counts, int cap )
+		{
+			const int row = blockIdx.x;
+			if( reset )
+			{
+				if( threadIdx.x == 0 ) counts[ row ] = reset == 2 ? -1 : 0;
+				return;
+			}
+			const int old = min( counts[ row ], cap );
+			const int tok = fed[ row ];
+			__syncthreads();
+			int* const h = history + (long long)row * cap;
+			const bool append = old >= 0 && old < cap;
+			const int L = old < 0 ? 0 : append ? old + 1 : cap;
+			if( threadIdx.x == 0 )
+			{
+				if( append ) h[ old ] = tok;
+				counts[ row ] = L;
+			}
+			if( L < n ) return;
+			const auto at = [ & ]( int j ) { return ( append && j == old ) ? tok : h[ j ]; };
+			int suffix[ NRN_MAX_N - 1 ];
+#pragma unroll
+			for( int k = 0; k < NRN_MAX_N - 1; k++ ) suffix[ k ] = k < n - 1 ? at( L - n + 1 + k ) : 0;
+			float* const x = logits + (long long)row * nVocab;
+			const int lim = min( tokenEot, nVocab );	  // text tokens only, and inside the row
+			for( int i = (int)threadIdx.x; i <= L - n; i += NRN_THREADS )
+			{
+				bool same = true;
+#pragma unroll
+				for( int k = 0; k < NRN_MAX_N - 1; k++ )
+					if( k < n - 1 && same ) same = at( i + k ) == suffix[ k ];
+				const int t = at( i + n - 1 );
+				if( same && (unsigned)t < (unsigned)lim ) x[ t ] = -INFINITY;
+			}
+		}
+
 		bool drawShapeOk( int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot )
 		{
 			return rows >= 1 && nVocab >= 1 && nVocab <= SAMPLE_DRAW_MAX_VOCAB && tokenBeg >= 1 && tokenBeg < nVocab && tokenSot >= 0 && tokenSot < tokenBeg &&
@@ -900,6 +953,18 @@ namespace wh
 			return -1;
 		}
 		hipLaunchKernelGGL( boostLogitsKernel, dim3( rows ), dim3( BOOST_THREADS ), 0, stream, logits, nVocab, tokenEot, tables, tableInts, fed, reset, states );
+		WH_HIP( hipGetLastError() );
+		return 0;
+	}
+
+	int launchNoRepeat( float* logits, int rows, int nVocab, int tokenEot, int n, const int* fed, int reset, int* history, int* counts, int cap, hipStream_t stream )
+	{
+		if( !logits || !history || !counts || ( !reset && !fed ) || rows < 1 || nVocab < 1 || tokenEot < 0 || tokenEot > nVocab || n < 1 || n > NRN_MAX_N || reset < 0 || reset > 2 || cap < 1 )
+		{
+			setError( "noRepeat: bad argument" );
+			return -1;
+		}
+		hipLaunchKernelGGL( noRepeatKernel, dim3( rows ), dim3( NRN_THREADS ), 0, stream, logits, nVocab, tokenEot, n, fed, reset, history, counts, cap );
 		WH_HIP( hipGetLastError() );
 		return 0;
 	}

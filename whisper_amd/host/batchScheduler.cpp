@@ -26,6 +26,7 @@
 #include "batchSuppress.h"
 #include "batchTimestampRules.h"
 #include "batchBoost.h"
+#include "batchNoRepeat.h"
 #include "optionRules.h"
 #include "decodeFallback.h"
 #include "languageDetect.h"
@@ -50,6 +51,8 @@ namespace Whisper
 	pfnBatchTimestampRules g_batchTimestampRules = nullptr;
 	// ... and for boosted phrases (batchBoost.h)
 	pfnBatchBoost g_batchBoost = nullptr;
+	// ... and for no-repeat n-grams (batchNoRepeat.h)
+	pfnBatchNoRepeat g_batchNoRepeat = nullptr;
 	// ... and to the scorer of given transcripts (scoreRequest.h)
 	pfnBatchScorer g_batchScorer = nullptr;
 
@@ -205,6 +208,8 @@ namespace Whisper
 			uint32_t timestampRulesVersion = 0;
 			// boosted phrases: the version of the runner's set this group's context holds (0 = never told: a new context holds none)
 			uint32_t boostVersion = 0;
+			// no-repeat n-grams: the n this group's context holds (a new context holds 0, off)
+			int noRepeatN = 0;
 		};
 
 		// One call of iBatchRunner::run over the runner's groups (their wh_contexts outlive the call: KV caches, captured graphs)
@@ -692,6 +697,8 @@ namespace Whisper
 			// Whisper::setBatchBoostedPhrases: one set for every stream; each group's context is told once, before the first round that follows a change
 			phraseBoost::Set boostSet;
 			uint32_t boostVersion = 0;
+			// Whisper::setBatchNoRepeatNgram: one n for every stream, 0 = off; a group's context is told before the first round in which it holds another n
+			int noRepeatN = 0;
 		public:
 			// The setters answer in one order: the argument check (optionRules.h), E_NOTIMPL without the device entry, "nothing changes", then the new version
 			HRESULT setBoosted( const sBoostedPhrases* p )
@@ -702,6 +709,13 @@ namespace Whisper
 				if( set.count() == 0 && boostSet.count() == 0 ) return S_OK;
 				boostSet = std::move( set );
 				boostVersion++;
+				return S_OK;
+			}
+			HRESULT setNoRepeat( int n )
+			{
+				CHECK( optionRules::checkNoRepeat( "setBatchNoRepeatNgram", n ) );
+				if( n && !g_batchNoRepeat ) return optionRules::notGiven( "setBatchNoRepeatNgram", "n-gram filter" );
+				noRepeatN = n;
 				return S_OK;
 			}
 			HRESULT setTimestampRulesMode( bool on )
@@ -868,7 +882,7 @@ namespace Whisper
 				// one sFullParams for every stream of the batch: its audio_ctx is the groups' (ContextImpl.cpp:488-489)
 				if( params.audio_ctx < 0 || params.audio_ctx > model->hp.n_audio_ctx ) return E_INVALIDARG;
 				for( Group& g : groups ) CHECK_WH( wh_context_set_audio_ctx( g.gpu, params.audio_ctx ) );
-				// a context is told what changed since it was last told: the set, the rules, the phrases
+				// a context is told what changed since it was last told: the set, the rules, the phrases, the n-gram size
 				for( Group& g : groups )
 				{
 					if( g.suppressVersion != suppressVersion && g_batchSuppress )
@@ -885,6 +899,11 @@ namespace Whisper
 					{
 						CHECK_WH( g_batchBoost( g.gpu, boostSet.tokens.data(), boostSet.lens.data(), boostSet.count(), boostSet.nMax, boostSet.boost ) );
 						g.boostVersion = boostVersion;
+					}
+					if( g.noRepeatN != noRepeatN && g_batchNoRepeat )
+					{
+						CHECK_WH( g_batchNoRepeat( g.gpu, noRepeatN ) );
+						g.noRepeatN = noRepeatN;
 					}
 				}
 				if( modesDirty && !fallbackOn )
@@ -947,6 +966,11 @@ namespace Whisper
 	{
 		return optionRules::forward<BatchRunner>( runner, "setBatchBoostedPhrases", NOT_A_RUNNER, nullptr,
 			[ = ]( BatchRunner& r ) { return r.setBoosted( phrases ); } );
+	}
+	HRESULT setBatchNoRepeatNgram( iBatchRunner* runner, int n )
+	{
+		return optionRules::forward<BatchRunner>( runner, "setBatchNoRepeatNgram", NOT_A_RUNNER, nullptr,
+			[ = ]( BatchRunner& r ) { return r.setNoRepeat( n ); } );
 	}
 	HRESULT getResultWindowStats( const iTranscribeResult* result, sWindowStats* stats, uint32_t* count )
 	{

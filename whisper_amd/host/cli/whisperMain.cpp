@@ -431,7 +431,9 @@ int main( int argc, char** argv )
 	// --score FILE (the same way): instead of transcribing, Whisper::scoreTokens of the text in FILE against every input (a clip of 1 to 30 s): one line per
 	// token -- its time with --align (forced alignment), log-probability, rank, text -- and a summary line
 	// --boost-phrases FILE --boost N (the same way; one needs the other): Whisper::setBoostedPhrases with the spellings of the file's phrases, one per line
+	// -nrn N / --no-repeat-ngram N (the same way): Whisper::setNoRepeatNgram, no text token that would complete an n-gram its window already holds (0 = off)
 	bool align = false, useFallback = false, suppressNst = false, timestampRules = false, haveBoost = false;
+	int noRepeatNgram = 0;
 	std::string scoreFile, boostFile;
 	float boost = 0.0f;
 	sDecodingFallback fallbackParams;
@@ -455,6 +457,11 @@ int main( int argc, char** argv )
 				boostFile = argv[ ++i ];
 			}
 			else if( !strcmp( argv[ i ], "--boost" ) ) { value = &boost; haveBoost = true; }
+			else if( !strcmp( argv[ i ], "-nrn" ) || !strcmp( argv[ i ], "--no-repeat-ngram" ) )
+			{
+				if( i + 1 >= argc ) { fprintf( stderr, "error: %s needs a number\n", argv[ i ] ); return 2; }
+				noRepeatNgram = atoi( argv[ ++i ] );
+			}
 			else if( !strcmp( argv[ i ], "-tpi" ) ) value = &fallbackParams.temperatureInc;
 			else if( !strcmp( argv[ i ], "-lpt" ) ) value = &fallbackParams.logprobThold;
 			else if( !strcmp( argv[ i ], "-et" ) ) value = &fallbackParams.entropyThold;
@@ -529,6 +536,11 @@ int main( int argc, char** argv )
 	{
 		hr = setTimestampRules( context, true );
 		if( FAILED( hr ) ) { printFailure( "failed to turn the timestamp rules on", hr ); return 6; }
+	}
+	if( noRepeatNgram )
+	{
+		hr = setNoRepeatNgram( context, noRepeatNgram );
+		if( FAILED( hr ) ) { printFailure( "failed to set the no-repeat n-gram size", hr ); return 6; }
 	}
 	if( !boostFile.empty() )
 	{

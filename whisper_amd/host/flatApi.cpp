@@ -241,6 +241,17 @@ WHISPER_EXPORT int32_t whisperc_phrase_spellings( void* model, const char* text,
 	*count = cap;
 	return phraseSpellings( (iModel*)model, text, tokens, lens, count );
 }
+// Whisper::setNoRepeatNgram / setBatchNoRepeatNgram: n == 0 turns the rule off
+WHISPER_EXPORT int32_t whisperc_set_no_repeat_ngram( void* ctx, int32_t n )
+{
+	if( !ctx ) return E_POINTER;
+	return setNoRepeatNgram( (iContext*)ctx, n );
+}
+WHISPER_EXPORT int32_t whisperc_batch_set_no_repeat_ngram( void* runner, int32_t n )
+{
+	if( !runner ) return E_POINTER;
+	return setBatchNoRepeatNgram( (iBatchRunner*)runner, n );
+}
 // Whisper::setTimestampRules / setBatchTimestampRules
 WHISPER_EXPORT int32_t whisperc_set_timestamp_rules( void* ctx, int32_t on )
 {

@@ -58,6 +58,8 @@ namespace
 		bool suppressNst = false;
 		// -tsr / --timestamp-rules: Whisper::setBatchTimestampRules on every rank's runner
 		bool timestampRules = false;
+		// -nrn N / --no-repeat-ngram N: Whisper::setBatchNoRepeatNgram on every rank's runner (0 = off)
+		int noRepeatNgram = 0;
 		// -boost-phrases FILE -boost N (one needs the other): Whisper::setBatchBoostedPhrases on every rank's runner with the spellings of the file's phrases
 		std::string boostFile;
 		bool haveBoost = false;
@@ -274,6 +276,11 @@ namespace
 			hr = setBatchTimestampRules( runner, true );
 			if( FAILED( hr ) ) { fprintf( stderr, "[rank %d] setBatchTimestampRules failed 0x%08x\n", rank, (unsigned)hr ); return 6; }
 		}
+		if( runner && a.noRepeatNgram )
+		{
+			hr = setBatchNoRepeatNgram( runner, a.noRepeatNgram );
+			if( FAILED( hr ) ) { fprintf( stderr, "[rank %d] setBatchNoRepeatNgram failed 0x%08x\n", rank, (unsigned)hr ); return 6; }
+		}
 		if( runner && !a.boostFile.empty() )
 		{
 			phraseFile::Rows rows;
@@ -433,6 +440,7 @@ int main( int argc, char** argv )
 		else if( !strcmp( argv[ i ], "-fallback" ) || !strcmp( argv[ i ], "--fallback" ) ) a.useFallback = true;
 		else if( !strcmp( argv[ i ], "-sns" ) || !strcmp( argv[ i ], "--suppress-nst" ) ) a.suppressNst = true;
 		else if( !strcmp( argv[ i ], "-tsr" ) || !strcmp( argv[ i ], "--timestamp-rules" ) ) a.timestampRules = true;
+		else if( !strcmp( argv[ i ], "-nrn" ) || !strcmp( argv[ i ], "--no-repeat-ngram" ) ) a.noRepeatNgram = atoi( val() );
 		else if( !strcmp( argv[ i ], "-boost-phrases" ) || !strcmp( argv[ i ], "--boost-phrases" ) ) a.boostFile = val();
 		else if( !strcmp( argv[ i ], "-boost" ) || !strcmp( argv[ i ], "--boost" ) ) { a.boost = (float)atof( val() ); a.haveBoost = true; }
 		else if( !strcmp( argv[ i ], "-tpi" ) ) a.fallback.temperatureInc = (float)atof( val() );

@@ -1,5 +1,5 @@
 // The decoding options of whisperApi.h that are functions over an iContext or an iBatchRunner instead of methods (fallback, suppressed tokens, timestamp rules,
-// boosted phrases, scoring): what the two share, stated once. Host only and header only, no device symbol is named -- ContextImpl (whisperImpl.cpp) and
+// boosted phrases, no-repeat n-grams, scoring): what the two share, stated once. Host only and header only, no device symbol is named -- ContextImpl (whisperImpl.cpp) and
 // BatchRunner (batchScheduler.cpp, which is also compiled into CPU test libraries) both call it. `name` is the public function's, for the log:
 // "setSuppressedTokens: ..." against "setBatchSuppressedTokens: ...".
 #pragma once
@@ -37,6 +37,13 @@ namespace Whisper
 			const char* const why = p ? phraseBoost::check( p->tokens, p->lengths, p->count, p->maxLength, p->boost, tokenEot, set, text ) : nullptr;
 			if( !why ) return S_OK;
 			logError( "%s: %s", name, why );
+			return E_INVALIDARG;
+		}
+		// n of the no-repeat n-gram rule: 0 = off, 1 .. 8 on (the compute layer's NRN_MAX_N)
+		inline HRESULT checkNoRepeat( const char* name, int n )
+		{
+			if( n >= 0 && n <= 8 ) return S_OK;
+			logError( "%s: n = %i is outside 0 .. 8", name, n );
 			return E_INVALIDARG;
 		}
 		// BatchRunner without the injected device entry an option needs (batchSampling.h and its like)

@@ -14,6 +14,7 @@
 #include "batchSuppress.h"
 #include "batchTimestampRules.h"
 #include "batchBoost.h"
+#include "batchNoRepeat.h"
 #include "optionRules.h"
 #include "languageDetect.h"
 #include "scoreRequest.h"
@@ -137,6 +138,8 @@ namespace Whisper
 			bool timestampRulesOn = false;
 			// Whisper::setBoostedPhrases: off unless set. The stream's device context holds the set; the hypothesis-group context of beam search cannot (runFull refuses)
 			bool boostOn = false;
+			// Whisper::setNoRepeatNgram: 0 = off unless set. The stream's device context holds n; the hypothesis-group context of beam search cannot (runFull refuses)
+			int noRepeatN = 0;
 
 			using Clock = std::chrono::steady_clock;
 			static double msSince( Clock::time_point t ) { return std::chrono::duration<double, std::milli>( Clock::now() - t ).count(); }
@@ -254,6 +257,13 @@ namespace Whisper
 			{
 				CHECK_WH( wh_context_set_timestamp_rules( gpu, on ? 1 : 0 ) );
 				timestampRulesOn = on;
+				return S_OK;
+			}
+			HRESULT setNoRepeat( int n )
+			{
+				CHECK( optionRules::checkNoRepeat( "setNoRepeatNgram", n ) );
+				CHECK_WH( wh_context_set_no_repeat( gpu, n ) );
+				noRepeatN = n;
 				return S_OK;
 			}
 			HRESULT setBoosted( const sBoostedPhrases* p )
@@ -869,6 +879,12 @@ namespace Whisper
 				logError( "runFull: boosted phrases (setBoostedPhrases) are not available with eSamplingStrategy::BeamSearch" );
 				return E_NOTIMPL;
 			}
+			// no-repeat n-grams: the device-side loop only (the per-sequence histories would have to follow the beam's parent reorder)
+			if( noRepeatN && params.strategy == eSamplingStrategy::BeamSearch && params.beam_search.beam_width >= 1 )
+			{
+				logError( "runFull: no-repeat n-grams (setNoRepeatNgram) are not available with eSamplingStrategy::BeamSearch" );
+				return E_NOTIMPL;
+			}
 			StreamRun run( params, vocab, hp, this, progress, resultAll, promptPast, &stamper );
 			// the run's audio is current until this function returns; the stereo PCM is the caller's and is not referred to afterwards
 			struct CurrentRun
@@ -1241,6 +1257,8 @@ namespace Whisper
 	static const bool g_timestampRulesInstalled = ( g_batchTimestampRules = &wh_context_set_timestamp_rules, true );
 	// ... and to the phrase filter (batchBoost.h)
 	static const bool g_boostInstalled = ( g_batchBoost = &wh_context_set_boost, true );
+	// ... and to the n-gram filter (batchNoRepeat.h)
+	static const bool g_noRepeatInstalled = ( g_batchNoRepeat = &wh_context_set_no_repeat, true );
 	// ... and to the scorer of given transcripts (scoreRequest.h)
 	static const bool g_scorerInstalled = ( g_batchScorer = &wh_score_tokens, true );
 
@@ -1288,6 +1306,11 @@ namespace Whisper
 	{
 		return optionRules::forward<ContextImpl>( context, "setBoostedPhrases", NOT_A_CONTEXT, "a batch runner takes setBatchBoostedPhrases",
 			[ = ]( ContextImpl& c ) { return c.setBoosted( phrases ); } );
+	}
+	HRESULT setNoRepeatNgram( iContext* context, int n )
+	{
+		return optionRules::forward<ContextImpl>( context, "setNoRepeatNgram", NOT_A_CONTEXT, "a batch runner takes setBatchNoRepeatNgram",
+			[ = ]( ContextImpl& c ) { return c.setNoRepeat( n ); } );
 	}
 	HRESULT contextScoreClip( iContext* context, const float* pcm, int64_t nSamples, const int32_t* tokens, int32_t len, int32_t firstScored, wh_token_score* recs, int32_t* frames )
 	{
