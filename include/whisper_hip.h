@@ -634,6 +634,55 @@ WH_API int wh_op_decoder_cross_attention( void* stream, const float* x, const fl
 /* softMax over rows with the reference's FP16 exp table semantics (softMax.hlsl / ggml.c:5030-5090): in place, FP32 */
 WH_API int wh_op_soft_max( void* stream, float* x, int rows, int cols );
 
+/* ---- op-level entry points of the encoder's fused products (what wh_encode builds by hand: conv1, conv2, Q/K/V, cross-K/V of every decoder layer) and of the
+ * producer of conv1's operand. Device pointers; restated in numpy by tests/encoder_ops_ref.py. ---- */
+
+/* The kernel family a product went to */
+typedef enum wh_gemm_family
+{
+	WH_GEMM_TILED_128 = 0,	/* gemmTiled, a workgroup per 128 x 128 tile */
+	WH_GEMM_TILED_256 = 1,	/* gemmTiled, a workgroup per 256 x 256 tile */
+	WH_GEMM_TILED8 = 2,		/* gemmTiled8: persistent, 8 waves */
+	WH_GEMM_TILED4 = 3		/* gemmTiled4: persistent, 4 waves */
+} wh_gemm_family;
+/* acc[m][n] = sum_k A(m)[k] * w[n][k] in FP32, then the epilogue `epi`. Row m of A starts at a + ( m / Mb ) * aBatchStride + ( m % Mb ) * lda and is K halves long
+ * (rows may overlap: conv1 reads lda = n_mels apart); w: FP16 [N][K]. epi:
+ *   0  out32[ o ] = ( acc + bias[n] ) + res[ o ], o = ( m / Mb ) * cBatchStride + ( m % Mb ) * ldc + n; bias, res may be NULL
+ *   1  out16[ o ] = gelu16( acc + bias[n] ), the same o
+ *   2  out32[ m * ldc + n ] = pe[ ( m % Mb ) * N + n ] + float( gelu16( acc + bias[n] ) )
+ *   3  N = 3 * 64 * H, x = fp16( acc + bias[n] ), window b = m / T, t = m % T, column n = sel * 64 H + h * 64 + dd: sel 0 -> q, sel 1 -> k, both FP16 [b][h][T][64];
+ *      sel 2 -> v, FP16 [b][h][64 * Tpad], at the index(t, dd) of wh_op_flash_attention. Nothing else of v is written.
+ *   4  N = layers * 2 * 64 * H, column n = layer * 128 H + isV * 64 H + h * 64 + dd: k / v FP16 [layer][B][h][T][64] at window b = m / T; k = fp16( acc * scale ),
+ *      v = fp16( acc + bias[n] ). Windows M / T .. B - 1 of every layer are not written (k and v may point at a later window of larger caches).
+ * Checked here, since the launchers cannot see it: the operands the epilogue needs are non-NULL; M is whole segments of Mb rows (Mb >= M: one segment) and the
+ * output segments do not overlap; ldc >= N; for epi 3 and 4 N as above, M % T == 0, and Tpad >= T a multiple of 16 (3) or B >= M / T (4). K a multiple of 64,
+ * lda and aBatchStride multiples of 8. Otherwise WH_E_INVALIDARG and nothing is launched.
+ * The product goes through the chooser wh_encode's products go through; *family (may be NULL) = the wh_gemm_family it chose under the tuning bits and options of
+ * the moment, *wideEpi (may be NULL) = how the tiles leave: 0 column stores, 1 through LDS as 16-byte row stores, 2 = 1 with the lean epilogue on interior tiles. */
+typedef struct wh_gemm_encoder_args
+{
+	const void* a;
+	const void* w;
+	const float* bias;
+	const float* res;
+	const float* pe;
+	float* out32;
+	void* out16;
+	void* q;
+	void* k;
+	void* v;
+	int64_t aBatchStride, cBatchStride;
+	int32_t M, N, K, lda, Mb, ldc, epi, T, Tpad, H, B;
+	float scale;
+} wh_gemm_encoder_args;
+WH_API int wh_op_gemm_encoder( void* stream, const wh_gemm_encoder_args* args, int32_t* family, int32_t* wideEpi );
+/* The producer of conv1's operand: x16[ b * xBatchStride + ( t + 1 ) * nMels + c ] = fp16( mel_b[ c ][ off_b + t ] ) for t < rows, c < nMels, zero where
+ * off_b + t is at or beyond the spectrogram's length; rows 0 and rows + 1 of every window (conv1's padding) are not written. Either offsetsHost (HOST int32 [batch],
+ * NULL = all 0) with mel_b = melDev + b * melStride, FP32 [nMels][melLen]; or windowsHost (HOST [batch], what wh_encode_windows takes; a window with a NULL
+ * melDev is silence). Offsets are >= 0, lengths > 0, xBatchStride >= ( rows + 2 ) * nMels, or WH_E_INVALIDARG. The call waits for the stream. */
+WH_API int wh_op_mel_to_conv_input( void* stream, const float* melDev, int64_t melStride, int64_t melLen, const int32_t* offsetsHost, const wh_mel_window* windowsHost,
+	void* x16, int64_t xBatchStride, int nMels, int rows, int batch );
+
 /* ---- op-level entry points of the single-token step's own kernels (what wh_decode launches for 1 .. 4 sequences, and the fused self-attention half of a
  * lock-step batch of 9 .. 32): WhisperContext.cpp:412-520. Device pointers; no prefetch hints; restated in float64 by tests/decode_step_ref.py. ---- */
 

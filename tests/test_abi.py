@@ -121,6 +121,49 @@ def test_decode_step_entry_points_reject_bad_arguments_before_any_launch():
     rejected(L.wh_op_self_block_dec(None, p, p, p, p, p, one, p, p, p, 0, 2, 448, 0, None), "selfBlockDec")
 
 
+def test_encoder_product_entry_points_reject_bad_arguments_before_any_launch():
+    """wh_op_gemm_encoder / wh_op_mel_to_conv_input: what the launchers cannot see -- a null operand of the epilogue, N against H, windows that are not whole, a V padding
+    or a cache too small for what the product writes, overlapping output segments -- is an error with a message, checked on the host alone (the pointers below are
+    never dereferenced: every call is turned away first)."""
+    import ctypes as C
+    import numpy as np
+    B = binding
+    p = 0x1000
+
+    def rejected(word, **kw):
+        args = dict(a=p, w=p, bias=p, M=256, N=384, K=128, lda=128, Mb=256, ldc=384, scale=1.0)
+        args.update(kw)
+        with pytest.raises(B.WhisperHipError, match=word):
+            B.op_gemm_encoder(**args)
+
+    rejected("Q/K/V needs", epi=B.EPI_QKV_ENC, q=p, k=p, T=128, Tpad=256, H=2)
+    rejected("3 \\* 64 \\* H", epi=B.EPI_QKV_ENC, q=p, k=p, v=p, T=128, Tpad=256, H=3)
+    rejected("M % T", epi=B.EPI_QKV_ENC, q=p, k=p, v=p, T=100, Tpad=256, H=2)
+    rejected("Tpad", epi=B.EPI_QKV_ENC, q=p, k=p, v=p, T=128, Tpad=127, H=2)
+    rejected("Tpad", epi=B.EPI_QKV_ENC, q=p, k=p, v=p, T=128, Tpad=136, H=2)
+    rejected("cross-K/V needs", epi=B.EPI_CROSS_KV, k=p, T=128, H=2, B=2)
+    rejected("2 \\* 64 \\* H", epi=B.EPI_CROSS_KV, k=p, v=p, T=128, H=2, B=2)
+    rejected("B must hold", epi=B.EPI_CROSS_KV, k=p, v=p, N=512, T=128, H=2, B=1)
+    rejected("conv2 needs", epi=B.EPI_CONV2, out32=p)
+    rejected("whole segments", epi=B.EPI_F16_GELU, out16=p, Mb=100)
+    rejected("do not overlap", epi=B.EPI_F16_GELU, out16=p, Mb=128, cBatchStride=127 * 384)
+    rejected("ldc >= N", epi=B.EPI_F16_GELU, out16=p, ldc=383)
+    rejected("must not be null", epi=B.EPI_F16_GELU)
+    rejected("unknown epilogue", epi=5)
+    rejected("K a positive multiple of 64", epi=B.EPI_F16_GELU, out16=p, K=96)
+    rejected("16-byte aligned", epi=B.EPI_F16_GELU, out16=p, lda=100)
+    L = B.lib()
+    for args in ((None, p, 0, 100, None, None, None, 1000, 80, 10, 1),            # no output
+                 (None, p, 0, 100, None, None, p, 959, 80, 10, 1),                # the window does not fit its stride
+                 (None, None, 0, 100, None, None, p, 960, 80, 10, 1),             # no spectrogram
+                 (None, p, 0, 0, None, None, p, 960, 80, 10, 1)):                 # no length
+        assert L.wh_op_mel_to_conv_input(*args) != 0 and b"mel_to_conv_input" in L.wh_last_error()
+    neg = np.array([-1], np.int32)
+    assert L.wh_op_mel_to_conv_input(None, p, 0, 100, neg.ctypes.data, None, p, 960, 80, 10, 1) != 0 and b"negative" in L.wh_last_error()
+    wins = (B.MelWindowC * 1)(B.MelWindowC(p, 100, -1, 0))
+    assert L.wh_op_mel_to_conv_input(None, None, 0, 0, None, C.cast(wins, C.c_void_p), p, 960, 80, 10, 1) != 0 and b"bad window" in L.wh_last_error()
+
+
 def test_tuning_bits_of_the_binding_match_the_library_header():
     """whisper_amd/binding.py mirrors csrc/kernels.h eTuning by hand; tests restore binding.TUNE_DEFAULT after an A/B, so a bit that is in one default
     and not in the other would silently change what the rest of a test session measures."""

@@ -323,6 +323,60 @@ def test_audio_ctx_override(ref_lib_available, tmp_path):
     m.close()
 
 
+def test_timed_encoder_at_reduced_audio_ctx_against_the_exact_mode():
+    """The encoder a context actually launches at a reduced audio_ctx, where its fused products sit on the other side of their epilogues' conditions (T % 4 != 0,
+    T < 128, segments of fewer than 256 rows; op level, bit for bit: tests/test_gpu_encoder_ops.py). d = 128 test model, 2 windows, audio_ctx 375, 130 and 100: the
+    cross-K/V of the first and the last decoder layer from the timed path (T) against the exact mode's (E0), held to the floor measured in the same run exactly as
+    test_timed_path_against_the_exact_mode holds the logits: max and mean |T - E0| within 1.5 x of |E0alt - E0|, E0alt being E0 with the weight products' 32 chains
+    added left to right (option exact_alt_order), the smallest re-ordering of the reference's own FP32 sums. Then back to audio_ctx 0: the full-size caches are
+    the bits they were before."""
+    import bench
+    model = gf.synth_model("test-d128", seed=1234, attn_sharpness=2.0)
+    hp = model.hparams
+    m = binding.HipModel.from_ggml(model)
+    ctx = binding.HipContext(m, 2)
+    pcm_dev = torch.from_numpy(bench.synth_pcm(2, seed=100)).cuda()
+    mels = torch.stack([ctx.mel_spectrogram(pcm_dev[b]) for b in range(2)])
+    layers = (0, hp.n_text_layer - 1)
+    X = binding.WH_FLAG_PARITY_EXACT
+
+    def caches(flags, n_ctx):
+        ctx.set_flags(*flags)
+        ctx.encode(mels)
+        n = 2 * n_ctx * hp.n_audio_state         # [windows][audio_ctx][d], packed at the front of the full-size host array
+        got = np.stack([np.asarray(ctx.debug_read(what, layer), np.float32).reshape(-1)[:n] for layer in layers for what in ("cross-k", "cross-v")])
+        ctx.set_flags(0, 1)
+        return got
+
+    def dist(a, b):
+        d = np.abs(a - b)
+        return float(d.max()), float(d.mean())
+
+    full = caches((0, 1), hp.n_audio_ctx)
+    try:
+        for n_ctx in (375, 130, 100):
+            ctx.set_audio_ctx(n_ctx)
+            T = caches((0, 1), n_ctx)
+            E0 = caches((X, 0), n_ctx)
+            binding.set_option("exact_alt_order", 1)
+            try:
+                E0alt = caches((X, 0), n_ctx)
+            finally:
+                binding.set_option("exact_alt_order", 0)
+            floor_max, floor_mean = dist(E0alt, E0)
+            t_max, t_mean = dist(T, E0)
+            print("audio_ctx %d, cross-K/V of decoder layers %d and %d: re-ordered reference vs E0 %.3e / %.3e; timed vs E0 %.3e / %.3e (max / mean)"
+                  % (n_ctx, layers[0], layers[1], floor_max, floor_mean, t_max, t_mean))
+            assert np.isfinite(T).all() and np.isfinite(E0).all()
+            assert t_max <= 1.5 * floor_max and t_mean <= 1.5 * floor_mean, (n_ctx, t_max, t_mean, floor_max, floor_mean)
+        ctx.set_audio_ctx(0)
+        again = caches((0, 1), hp.n_audio_ctx)
+        assert np.array_equal(again, full), "the full-size caches changed after a round trip through reduced audio contexts"
+    finally:
+        ctx.close()
+        m.close()
+
+
 def test_exact_decoder_scratch_is_freed_when_it_grows():
     """The exact decoder's score scratch holds seqs * H * N * max(audio_ctx, n_past + N) floats, so with a small audio_ctx it grows while a host-stepped
     decode advances. A buffer that is replaced is given back: with U = 4 * seqs * n_text_head bytes, the two-token prompt at n_past = 0 needs 4 U, the steps

@@ -62,6 +62,7 @@ EXPORTS = [
     "wh_context_set_no_repeat", "wh_op_no_repeat_ngram",
     "wh_op_gemv_small", "wh_op_cross_split", "wh_op_self_block_dec",
     "wh_score_tokens", "wh_op_token_scores",
+    "wh_op_gemm_encoder", "wh_op_mel_to_conv_input",
 ]
 
 
@@ -103,6 +104,26 @@ class HParamsC(C.Structure):
 
 class TokenDataC(C.Structure):
     _fields_ = [("id", C.c_int32), ("tid", C.c_int32), ("p", C.c_float), ("pt", C.c_float), ("ptsum", C.c_float)]
+
+
+class GemmEncoderArgsC(C.Structure):
+    """wh_gemm_encoder_args: one of the encoder's fused products as wh_encode builds it (include/whisper_hip.h)."""
+    _fields_ = ([(k, C.c_void_p) for k in ("a", "w", "bias", "res", "pe", "out32", "out16", "q", "k", "v")] +
+                [("aBatchStride", C.c_int64), ("cBatchStride", C.c_int64)] +
+                [(k, C.c_int32) for k in ("M", "N", "K", "lda", "Mb", "ldc", "epi", "T", "Tpad", "H", "B")] + [("scale", C.c_float)])
+
+
+# wh_gemm_family, and the epilogues wh_op_gemm_encoder takes (csrc/kernels.h eEpilogue)
+GEMM_TILED_128, GEMM_TILED_256, GEMM_TILED8, GEMM_TILED4 = 0, 1, 2, 3
+EPI_F32, EPI_F16_GELU, EPI_CONV2, EPI_QKV_ENC, EPI_CROSS_KV = 0, 1, 2, 3, 4
+
+
+def op_gemm_encoder(stream=None, **fields):
+    """wh_op_gemm_encoder: the fields of wh_gemm_encoder_args by name (device addresses as ints, the rest 0); returns ( family, wideEpi )."""
+    args = GemmEncoderArgsC(**fields)
+    fam, wide = C.c_int32(-1), C.c_int32(-1)
+    check(lib().wh_op_gemm_encoder(stream, C.byref(args), C.byref(fam), C.byref(wide)))
+    return fam.value, wide.value
 
 
 class TokenScoreC(C.Structure):
@@ -259,6 +280,8 @@ def lib():
         L.wh_op_self_block_dec.argtypes = [vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, i32, i32, i32, i32, vp]
         L.wh_score_tokens.argtypes = [vp, i32, vp, vp, vp, i32, vp]
         L.wh_op_token_scores.argtypes = [vp, vp, i64, i32, i32, vp, vp]
+        L.wh_op_gemm_encoder.argtypes = [vp, C.POINTER(GemmEncoderArgsC), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.wh_op_mel_to_conv_input.argtypes = [vp, vp, i64, i64, vp, vp, vp, i64, i32, i32, i32]
         _lib = L
     return _lib
 

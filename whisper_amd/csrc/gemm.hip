@@ -26,9 +26,10 @@ namespace wh
 		return 0;
 	}
 
-	int launchGemm( const GemmArgs& a, hipStream_t stream )
+	thread_local int t_gemmWideEpi = 0;
+
+	eGemmFamily chooseGemmFamily( const GemmArgs& a )
 	{
-		WH_CHECK( checkGemmArgs( a ) );
 		// big tiles only when they still give every CU a workgroup and M is several clips deep
 		const bool big = (long long)( ( a.M + 255 ) / 256 ) * ( ( a.N + 255 ) / 256 ) >= 300 && a.M >= g_opt.gemmBigMinRows && ( g_tuning & TUNE_GEMM_BIG );
 		// gemmTiled8 addresses its operands as a 64-bit base + 32-bit byte offsets
@@ -40,9 +41,22 @@ namespace wh
 		static const int epis4 = []() { const char* e = getenv( "WH_GEMM_4WAVE_EPIS" ); return e ? atoi( e ) : 0; }();
 		const bool w4 = w8 && a.K >= 256 && ( ( g_tuning & TUNE_GEMM_4WAVE ) != 0 || ( ( epis4 >> a.epi ) & 1 ) != 0 ) &&	   // (K >= 256: the FP16 epilogues leave under the next tile's first four K tiles)
 			( a.Mb <= 0 || a.Mb >= a.M || ( a.Mb >= 256 && a.aBatchStride >= (long long)a.Mb * a.lda ) );
-		if( w4 ) return launchTiled4( a, stream );
-		if( w8 ) return launchTiled8( a, g_opt.gemmMf16 == 1, stream );
-		return launchTiled( a, big, stream );
+		if( w4 ) return GEMM_TILED4;
+		if( w8 ) return GEMM_TILED8;
+		return big && tiledBigEpilogue( a.epi ) ? GEMM_TILED_256 : GEMM_TILED_128;	   // (gemmTiled ignores `big` for the epilogues it has no 256-wide instance of)
+	}
+
+	int launchGemm( const GemmArgs& a, hipStream_t stream )
+	{
+		WH_CHECK( checkGemmArgs( a ) );
+		switch( chooseGemmFamily( a ) )
+		{
+		case GEMM_TILED4: return launchTiled4( a, stream );
+		case GEMM_TILED8: return launchTiled8( a, g_opt.gemmMf16 == 1, stream );
+		case GEMM_TILED_256: return launchTiled( a, true, stream );
+		case GEMM_TILED_128: break;
+		}
+		return launchTiled( a, false, stream );
 	}
 
 	// Tile-shape experiments on the plain FP32 epilogue (tools/gemm_probe.py): the persistent kernels here, gemmTiled's configurations in its unit

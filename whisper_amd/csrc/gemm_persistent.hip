@@ -1541,7 +1541,7 @@ namespace wh
 		GemmArgs b = a;
 		if( b.groupM == 0 ) b.groupM = defaultGroupM();
 		const bool wide = wideEpilogueOk( a, EPI, WITH_V );
-		b.wideEpi = wide ? ( fastEpi && fastEpilogueOk<EPI>( a ) ? 2 : 1 ) : 0;
+		b.wideEpi = t_gemmWideEpi = wide ? ( fastEpi && fastEpilogueOk<EPI>( a ) ? 2 : 1 ) : 0;
 		// persistent: one workgroup per CU (gemmTiled8's takes all 160 KiB of LDS, gemmTiled4's 512 registers per lane: one wave per SIMD), each walks its share of the tiles
 		const int tiles = ( ( b.M + C::BM - 1 ) / C::BM ) * ( ( b.N + C::BN - 1 ) / C::BN );
 		int cus = 0;

@@ -588,10 +588,10 @@ namespace wh
 		if constexpr( canWide )
 			if( wideEpilogueOk( a, EPI ) )
 			{
-				b.wideEpi = 1;
+				b.wideEpi = t_gemmWideEpi = 1;
 				return launchLds<gemmTiled<EPI, C, true>>( dim3( tilesM * tilesN ), dim3( C::NT ), C::LDS_BYTES, stream, b );
 			}
-		b.wideEpi = 0;
+		b.wideEpi = t_gemmWideEpi = 0;
 		return launchLds<gemmTiled<EPI, C, false>>( dim3( tilesM * tilesN ), dim3( C::NT ), C::LDS_BYTES, stream, b );
 	}
 
@@ -613,17 +613,21 @@ namespace wh
 		return launchTiledT<EPI>( a, stream );
 	}
 
+	// the epilogues built with the 256x256x64 tiles too; the others take 128x128x32 whatever `big` says
+	static constexpr bool bigTiles( int epi ) { return epi == EPI_F32 || epi == EPI_F16_GELU || epi == EPI_QKV_ENC || epi == EPI_CROSS_KV; }
+	bool tiledBigEpilogue( int epi ) { return bigTiles( epi ); }
+
 	int launchTiled( const GemmArgs& a, bool big, hipStream_t stream )
 	{
 		switch( a.epi )
 		{
-		case EPI_F32: return launchTiledE<EPI_F32, true, true>( a, big, stream );
-		case EPI_F16_GELU: return launchTiledE<EPI_F16_GELU, true, true>( a, big, stream );
-		case EPI_CONV2: return launchTiledE<EPI_CONV2, false, true>( a, big, stream );
-		case EPI_QKV_ENC: return launchTiledE<EPI_QKV_ENC, true, true>( a, big, stream );
-		case EPI_CROSS_KV: return launchTiledE<EPI_CROSS_KV, true, true>( a, big, stream );
-		case EPI_QKV_DEC: return launchTiledE<EPI_QKV_DEC, false, false>( a, big, stream );
-		case EPI_Q_DEC: return launchTiledE<EPI_Q_DEC, false, false>( a, big, stream );
+		case EPI_F32: return launchTiledE<EPI_F32, bigTiles( EPI_F32 ), true>( a, big, stream );
+		case EPI_F16_GELU: return launchTiledE<EPI_F16_GELU, bigTiles( EPI_F16_GELU ), true>( a, big, stream );
+		case EPI_CONV2: return launchTiledE<EPI_CONV2, bigTiles( EPI_CONV2 ), true>( a, big, stream );
+		case EPI_QKV_ENC: return launchTiledE<EPI_QKV_ENC, bigTiles( EPI_QKV_ENC ), true>( a, big, stream );
+		case EPI_CROSS_KV: return launchTiledE<EPI_CROSS_KV, bigTiles( EPI_CROSS_KV ), true>( a, big, stream );
+		case EPI_QKV_DEC: return launchTiledE<EPI_QKV_DEC, bigTiles( EPI_QKV_DEC ), false>( a, big, stream );
+		case EPI_Q_DEC: return launchTiledE<EPI_Q_DEC, bigTiles( EPI_Q_DEC ), false>( a, big, stream );
 		}
 		setError( "gemm: unknown epilogue" );
 		return -1;

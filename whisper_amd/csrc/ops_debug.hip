@@ -1,6 +1,7 @@
 // Diagnostics and development aids: the profiler's switches, wh_debug_read, the op-level entry points (wh_op_*) and the micro-benchmarks of
 // wh_debug_probe with their kernels.
 #include "runtime.h"
+#include "gemm_launch.h"
 
 namespace
 {
@@ -275,6 +276,104 @@ int wh_op_mul_mat_gelu( void* stream, const void* aF16, const void* wF16, const 
 	g.epi = EPI_F16_GELU; g.bias = bias; g.out16 = (f16*)outF16;
 	if( M <= GEMV_MAX_ROWS && ( K % 128 ) == 0 ) return launchGemv( g, (hipStream_t)stream );	   // the op-level entry is the decode-step product: up to 512 rows on the weight-streaming kernels
 	return M <= 32 ? launchGemmSkinny( g, (hipStream_t)stream ) : launchGemm( g, (hipStream_t)stream );
+}
+
+// ---- the encoder's fused products as wh_encode builds them (encode.hip), through the same chooser. Thin, but everything the launchers cannot see and a kernel
+// would turn into an address is checked here: a call either describes buffers the product stays inside, or launches nothing.
+int wh_op_gemm_encoder( void* stream, const wh_gemm_encoder_args* p, int32_t* family, int32_t* wideEpi )
+{
+	const auto bad = []( const char* what ) { setError( std::string( "gemm_encoder: " ) + what ); return (int)WH_E_INVALIDARG; };
+	if( !p || !p->a || !p->w ) return bad( "null argument" );
+	if( p->M <= 0 || p->N <= 0 || p->K <= 0 || p->lda <= 0 || p->Mb <= 0 || p->aBatchStride < 0 || p->cBatchStride < 0 ) return bad( "M, N, K, lda and Mb must be positive, the strides non-negative" );
+	const bool segmented = p->Mb < p->M;
+	if( segmented && ( p->M % p->Mb ) != 0 ) return bad( "M must be whole segments of Mb rows" );
+	GemmArgs g = plainGemm( (const f16*)p->a, (const f16*)p->w, p->M, p->N, p->K );
+	g.lda = p->lda; g.Mb = p->Mb; g.aBatchStride = p->aBatchStride;
+	g.ldc = p->ldc; g.cBatchStride = p->cBatchStride;
+	g.epi = p->epi; g.bias = p->bias; g.scale = p->scale;
+	const long long d = 64ll * p->H;
+	switch( p->epi )
+	{
+	case EPI_F32:
+	case EPI_F16_GELU:
+		if( p->epi == EPI_F32 ? !p->out32 : ( !p->out16 || !p->bias ) ) return bad( "the epilogue's output (and the GELU's bias) must not be null" );
+		if( p->ldc < p->N || ( segmented && p->cBatchStride < (long long)p->Mb * p->ldc ) ) return bad( "ldc >= N and output segments that do not overlap" );
+		g.res = p->epi == EPI_F32 ? p->res : nullptr; g.out32 = p->out32; g.out16 = (f16*)p->out16;
+		break;
+	case EPI_CONV2:
+		if( !p->out32 || !p->bias || !p->pe ) return bad( "conv2 needs out32, bias and pe" );
+		if( p->ldc < p->N ) return bad( "ldc >= N" );
+		g.pe = p->pe; g.out32 = p->out32;
+		break;
+	case EPI_QKV_ENC:
+		if( !p->q || !p->k || !p->v || !p->bias ) return bad( "Q/K/V needs q, k, v and bias" );
+		if( p->H <= 0 || p->N != 3 * d ) return bad( "Q/K/V: N must be 3 * 64 * H" );
+		if( p->T <= 0 || ( p->M % p->T ) != 0 ) return bad( "M % T must be 0" );
+		if( p->Tpad < p->T || ( p->Tpad % 16 ) != 0 ) return bad( "Tpad must be a multiple of 16 and at least T" );
+		g.q = (f16*)p->q; g.k = (f16*)p->k; g.v = (f16*)p->v;
+		g.T = p->T; g.Tpad = p->Tpad; g.H = p->H; g.B = p->M / p->T;
+		break;
+	case EPI_CROSS_KV:
+		if( !p->k || !p->v || !p->bias ) return bad( "cross-K/V needs k, v and bias" );
+		if( p->H <= 0 || ( p->N % ( 2 * d ) ) != 0 ) return bad( "cross-K/V: N % ( 2 * 64 * H ) must be 0" );
+		if( p->T <= 0 || ( p->M % p->T ) != 0 ) return bad( "M % T must be 0" );
+		if( p->B < p->M / p->T ) return bad( "cross-K/V: B must hold the M / T windows" );
+		g.k = (f16*)p->k; g.v = (f16*)p->v;
+		g.T = p->T; g.H = p->H; g.B = p->B;
+		break;
+	default:
+		return bad( "unknown epilogue" );
+	}
+	WH_CHECK( checkGemmArgs( g ) );
+	const int fam = chooseGemmFamily( g );
+	WH_CHECK( launchGemm( g, (hipStream_t)stream ) );
+	if( family ) *family = fam;
+	if( wideEpi ) *wideEpi = t_gemmWideEpi;
+	return 0;
+}
+
+int wh_op_mel_to_conv_input( void* stream, const float* melDev, int64_t melStride, int64_t melLen, const int32_t* offsetsHost, const wh_mel_window* windowsHost,
+	void* x16, int64_t xBatchStride, int nMels, int rows, int batch )
+{
+	const auto bad = []( const char* what ) { setError( std::string( "mel_to_conv_input: " ) + what ); return (int)WH_E_INVALIDARG; };
+	if( !x16 || nMels <= 0 || rows <= 0 || batch <= 0 || batch > 4096 ) return bad( "bad argument" );
+	if( xBatchStride < ( (int64_t)rows + 2 ) * nMels ) return bad( "xBatchStride must hold rows + 2 rows" );
+	static_assert( sizeof( MelWindow ) == 24 && sizeof( wh_mel_window ) == 24, "window descriptor layout" );
+	std::vector<MelWindow> wins;
+	std::vector<int32_t> offs;
+	if( windowsHost )
+	{
+		for( int i = 0; i < batch; i++ )
+		{
+			if( windowsHost[ i ].melDev && ( windowsHost[ i ].melLen <= 0 || windowsHost[ i ].offset < 0 ) ) return bad( "bad window" );
+			wins.push_back( MelWindow{ windowsHost[ i ].melDev, (long long)windowsHost[ i ].melLen, windowsHost[ i ].offset, 0 } );
+		}
+	}
+	else
+	{
+		if( !melDev || melLen <= 0 || melStride < 0 ) return bad( "bad spectrogram" );
+		for( int i = 0; i < batch; i++ )
+		{
+			if( offsetsHost && offsetsHost[ i ] < 0 ) return bad( "negative offset" );
+			offs.push_back( offsetsHost ? offsetsHost[ i ] : 0 );
+		}
+	}
+	ProbeMemory mem;
+	MelWindow* winsDev = nullptr;
+	int32_t* offsDev = nullptr;
+	if( windowsHost )
+	{
+		WH_CHECK( mem.alloc( &winsDev, sizeof( MelWindow ) * batch ) );
+		WH_HIP( hipMemcpy( winsDev, wins.data(), sizeof( MelWindow ) * batch, hipMemcpyHostToDevice ) );
+	}
+	else
+	{
+		WH_CHECK( mem.alloc( &offsDev, sizeof( int32_t ) * batch ) );
+		WH_HIP( hipMemcpy( offsDev, offs.data(), sizeof( int32_t ) * batch, hipMemcpyHostToDevice ) );
+	}
+	WH_CHECK( launchMelToConvInput( melDev, melStride, melLen, offsDev, winsDev, (f16*)x16, xBatchStride, nMels, rows, batch, (hipStream_t)stream ) );
+	WH_HIP( hipStreamSynchronize( (hipStream_t)stream ) );	   // the descriptors are released on return
+	return 0;
 }
 
 int wh_op_layer_norm( void* stream, const float* x, const float* w, const float* b, void* outF16, int rows, int d )
