@@ -228,9 +228,35 @@ namespace Whisper
 		pfnReportProgress pfn;
 		void* pv;
 	};
-	struct sCaptureCallbacks;
-	struct sCaptureParams;
 	struct sCaptureDevice;
+	// ---- audio capture (Whisper/API/MfStructs.h) ----
+	enum struct eCaptureFlags : uint32_t
+	{
+		Stereo = 1,		// keep stereo PCM in addition to mono: detectSpeaker then works from the callbacks of a piece
+		// Extension (the bit is free in the reference's enum): where the loop would post a piece while the previous one is still being transcribed, it waits
+		// instead of growing the buffer and dropping samples; iPcmCapture::write then blocks instead of dropping. For a source that is not real time (a file, a pipe).
+		NoDrop = 2,
+	};
+	// seconds; runCapture turns them into samples at 16 kHz, rounded to nearest even
+	struct sCaptureParams
+	{
+		float minDuration = 2.0f;		   // a piece is not fired at a pause before it is this long; 0.125 .. 30
+		float maxDuration = 3.0f;		   // a piece of continuous speech is fired at this length; 0.125 .. 30
+		float dropStartSilence = 0.25f;	   // a buffer without any voice is dropped when it reaches this length
+		float pauseDuration = 0.333f;	   // voice is "recent" when the last speech frame ended at most this long before the read
+		uint32_t flags = 0;				   // eCaptureFlags
+	};
+	enum struct eCaptureStatus : uint8_t { Listening = 1, Voice = 2, Transcribing = 4, Stalled = 0x80 };
+	// S_OK to continue, anything else to stop the capture session
+	using pfnShouldCancel = HRESULT ( * )( void* pv ) noexcept;
+	// called only when a bit changes, with the whole new word
+	using pfnCaptureStatus = HRESULT ( * )( void* pv, eCaptureStatus status ) noexcept;
+	struct sCaptureCallbacks
+	{
+		pfnShouldCancel shouldCancel;
+		pfnCaptureStatus captureStatus;
+		void* pv;
+	};
 	using pfnFoundCaptureDevices = HRESULT ( * )( int len, const sCaptureDevice* buffer, void* pv ) noexcept;
 
 	// ---- interfaces ----------------------------------------------------------------------------------------------
@@ -266,6 +292,22 @@ namespace Whisper
 		static constexpr ComLight::GUID iid() { return { 0x747752c2, 0xd9fd, 0x40df, { 0x88, 0x47, 0x58, 0x3c, 0x78, 0x1b, 0xf0, 0x13 } }; }
 		virtual HRESULT getReader( IMFSourceReader** pp ) const = 0;
 		virtual const sCaptureParams& getParams() const = 0;
+	};
+	// Extension (no counterpart in the reference, whose captures are sound cards): a capture fed by the caller -- a pipe, a socket, its own code. 16 kHz only.
+	// The only kind of capture iContext::runCapture of this library takes. write may be called from any thread while runCapture runs on another.
+	// {3a9e5c72-1b4d-4f08-b6a1-7c2e9d5f8a13}
+	struct iPcmCapture : public iAudioCapture
+	{
+		static constexpr ComLight::GUID iid() { return { 0x3a9e5c72, 0x1b4d, 0x4f08, { 0xb6, 0xa1, 0x7c, 0x2e, 0x9d, 0x5f, 0x8a, 0x13 } }; }
+		// `frames` interleaved sample frames; format: 1 = signed 16 bit, 4 = 32 bit float (wh_pcm_format of whisper_hip.h); channels 1 or 2, the same in every
+		// call. The chunk is queued as it is; runCapture takes one queued chunk per read. While more than maxDuration + 1 s is queued: with eCaptureFlags::NoDrop
+		// the call blocks until the loop has caught up, otherwise the OLDEST queued chunk is dropped and counted (droppedChunks). A chunk dropped here never
+		// reaches the loop and is not part of the stream's sample clock: the times behind it are early by its length. E_INVALIDARG for another
+		// format or channel count, E_UNEXPECTED after close.
+		virtual HRESULT write( const void* samples, int format, int channels, uint32_t frames ) = 0;
+		// the end of the stream: runCapture drains the queue, transcribes what is buffered if it holds voice, and returns S_OK
+		virtual HRESULT close() = 0;
+		virtual uint64_t droppedChunks() const = 0;
 	};
 	// {fb9763a5-d77d-4b6e-aff8-f494813cebd8}  -- on Linux: a WAV / raw-PCM loader stands in for Media Foundation
 	struct iMediaFoundation : public ComLight::IUnknown
@@ -512,6 +554,11 @@ namespace Whisper
 	// receives the pieces as ready streams over the buffer (params nullptr = the call's common parameters), valid during the call; its result is splitAtPauses's
 	using pfnSplitChunks = HRESULT ( * )( const sBatchStream* streams, uint32_t count, void* pv );
 	WHISPER_EXPORT HRESULT splitAtPauses( const iAudioBuffer* buffer, const sSplitParams* params /* nullptr = defaults */, pfnSplitChunks pfnChunks, void* pv );
+	// Extension: live transcription. iContext::runCapture runs the reference's capture loop (Whisper/Whisper/ContextImpl.capture.cpp; DESIGN.md section 7 "Live
+	// capture") over an iPcmCapture: every piece the loop fires is a runFull on a worker thread of the library, with the buffer's media time set to the piece's
+	// first sample, so segment times are stream times and the context's decoding options apply to every piece. OS capture devices (listCaptureDevices,
+	// openCaptureDevice) stay E_NOTIMPL; input at other rates than 16 kHz is out of scope.
+	WHISPER_EXPORT HRESULT createPcmCapture( const sCaptureParams& params, iPcmCapture** pp );
 	WHISPER_EXPORT HRESULT initMediaFoundation( iMediaFoundation** pp );
 	WHISPER_EXPORT uint32_t findLanguageKeyW( const wchar_t* lang );
 	WHISPER_EXPORT uint32_t findLanguageKeyA( const char* lang );

@@ -46,6 +46,31 @@ int32_t whisperc_run_streamed( void* ctx, const void* wavBytes, uint64_t wavSize
  * *nOut = ceil( nFrames * 16000 / rate ); dst == NULL only counts, cap (floats of dst) < *nOut is E_INVALIDARG. rate 16000 converts without filtering. */
 int32_t whisperc_resample( const void* src, int32_t format, int32_t channels, int32_t channel, int32_t rate, int64_t nFrames, float* dst, int64_t cap,
 	int64_t* nOut );
+/* Live transcription (Whisper::createPcmCapture, iPcmCapture, iContext::runCapture of whisperApi.h): a capture is a queue of 16 kHz PCM chunks that the caller
+ * writes from any thread -- format 1 = s16, 4 = float32; 1 or 2 interleaved channels, the same in every call -- and whisperc_run_capture drains on another:
+ * the reference's capture loop (voice activity per chunk on the GPU; a piece is fired at a pause once minDuration is buffered, or at maxDuration) with every
+ * piece transcribed by iContext::runFull on a worker thread, segment times being stream times. Durations in seconds (the reference's defaults are 2, 3, 0.25,
+ * 0.333); flags: 1 = keep stereo (whisperc_result_speakers then answers per piece), 2 = NoDrop: never discard samples, wait for the running transcription
+ * instead (a source that is not real time; whisperc_capture_write then blocks while more than maxDuration + 1 s is queued and a loop is draining).
+ * whisperc_capture_close marks the end of the stream: the loop drains the queue, transcribes what is left if it holds voice and returns 0.
+ * whisperc_run_capture: language and flags as whisperc_run_full. pfnShouldCancel is asked before every read, anything but 0 ends the call with 0;
+ * pfnCaptureStatus receives the status word (Listening 1, Voice 2, Transcribing 4, Stalled 0x80) whenever a bit changes -- on the calling thread, but for the fall of Transcribing without NoDrop, which
+ * comes from the worker thread when the piece's transcription ends, as in the reference;
+ * pfnPiece( pv, startSample, nSamples ) is called behind each piece's transcription, on the library's worker thread, while whisperc_result_* answer for
+ * that piece. Each may be NULL. E_POINTER for a NULL capture, E_INVALIDARG for minDuration or maxDuration outside [0.125, 30]. */
+int32_t whisperc_capture_create( float minDuration, float maxDuration, float dropStartSilence, float pauseDuration, uint32_t flags, void** captureOut );
+int32_t whisperc_capture_write( void* capture, const void* samples, int32_t format, int32_t channels, uint32_t frames );
+int32_t whisperc_capture_close( void* capture );
+/* chunks dropped by whisperc_capture_write because the loop did not keep up (never under NoDrop) */
+uint64_t whisperc_capture_dropped( void* capture );
+void whisperc_capture_destroy( void* capture );
+int32_t whisperc_run_capture( void* ctx, void* capture, const char* language, uint32_t flags, int32_t ( *pfnShouldCancel )( void* pv ),
+	int32_t ( *pfnCaptureStatus )( void* pv, uint8_t status ), void ( *pfnPiece )( void* pv, int64_t startSample, int64_t nSamples ), void* pv );
+/* The same with the further parameters of whisperc_run_full / _audio_ctx / _beam, which then hold for every piece: maxTokens, the prompt, nMaxTextCtx (< 0 keeps
+ * the default), audioCtx (0 = the model's), beamWidth (0 = greedy). */
+int32_t whisperc_run_capture_params( void* ctx, void* capture, const char* language, uint32_t flags, int maxTokens, const int32_t* promptTokens, int nPrompt,
+	int nMaxTextCtx, int audioCtx, int beamWidth, int32_t ( *pfnShouldCancel )( void* pv ), int32_t ( *pfnCaptureStatus )( void* pv, uint8_t status ),
+	void ( *pfnPiece )( void* pv, int64_t startSample, int64_t nSamples ), void* pv );
 /* Splitting a long recording at pauses (Whisper::splitAtPauses of whisperApi.h), on mono FP32 16 kHz PCM:
  * whisperc_vad: voice-activity features on the calling thread's current device (wh_vad_features_host of whisper_hip.h), then the reference's decision loop
  *   (Whisper/Whisper/voiceActivityDetection.cpp:121-205) on the host: speech[ f ] = 1 where frame f = samples [256 f, 256 f + 256) is speech, *lastSpeech =

@@ -265,6 +265,35 @@ WH_API int wh_vad_features( void* stream, const float* pcmDev, int64_t nSamples,
 /* host -> host on the current device: upload of the whole frames, kernel, download. */
 WH_API int wh_vad_features_host( const float* pcm, int64_t nSamples, float* feat );
 
+/* A live PCM stream, chunk by chunk: the buffer of the capture loop of iContext::runCapture (Whisper/Whisper/ContextImpl.capture.cpp: readSample appends
+ * the converted samples, detectVoice looks at the whole buffer). A wh_capture is made for 1 or 2 input channels at 16 kHz and owns, each for capSamples
+ * samples: a device buffer of mono FP32, with keepStereo one of interleaved stereo FP32, and a pinned host mirror of both -- twice, see wh_capture_take.
+ * It has a stream of its own (the context only names the device), so an append never waits for a transcription that runs on a context's stream.
+ * A context that never captures allocates and launches nothing of this.
+ *
+ * wh_capture_append: src (HOST) holds `frames` interleaved sample frames of the capture's channel count in `format`, WH_PCM_S16 or WH_PCM_F32. One upload of
+ * the chunk in its own format, ONE kernel launch, one download of the features; the call waits for the capture's stream only. With n the samples buffered:
+ *   - samples [n, n + frames) of the mono buffer, of the stereo buffer if kept and of the mirror are written by wh_resample's rules for inRate == 16000:
+ *     s16 is v / 32768, f32 as is; mono of two channels is the FP32 sum in channel order times 0.5f; a mono source whose stereo is kept gets its channel twice;
+ *   - featHost [nNewFrames][3] receives the voice-activity features of the 256-sample frames the chunk completes, frames [n / 256, ( n + frames ) / 256) of the
+ *     buffer -- a frame that began in an earlier chunk takes its older samples from the buffer --, with the bits wh_vad_features gives for the same 256 samples:
+ *     both kernels call the same device function (csrc/vad_device.h).
+ * A workgroup owns 16 consecutive frames of buffer positions, as in wh_vad_features: it converts the part of the chunk that falls into them, then computes the
+ * features of the frames among them that the chunk completes. WH_E_BOUNDS, and no launch, when the chunk does not fit; WH_E_INVALIDARG, and no launch, for
+ * another format, a null pointer with frames > 0, or featCap (frames of 3 floats) below the number of completed frames. frames == 0 succeeds with no launch.
+ * wh_capture_clear empties the buffer: position 0, no partial frame. wh_capture_take hands out the host mirror of what is buffered (stereoHost receives NULL
+ * when stereo is not kept; the argument itself may be NULL) and empties the buffer; the mirror is two buffers that swap, so what was handed out stays valid
+ * until the take after the next (the reference's pcm.swap( buffer.pcm )): the piece under transcription is not overwritten while the next one fills.
+ * One thread at a time per capture. */
+typedef struct wh_capture wh_capture;
+WH_API int wh_capture_create( wh_context* c, int channels, int keepStereo, int64_t capSamples, wh_capture** out );
+WH_API int wh_capture_append( wh_capture* cap, const void* src, int format, int64_t frames, float* featHost, int64_t featCap, int64_t* nNewFrames );
+WH_API int wh_capture_clear( wh_capture* cap );
+WH_API int wh_capture_take( wh_capture* cap, const float** monoHost, const float** stereoHost, int64_t* nSamples );
+WH_API int wh_capture_size( const wh_capture* cap, int64_t* nSamples );
+/* 0 or WH_E_BOUNDS when a guard region of a device buffer was written (WH_DEBUG_POISON) */
+WH_API int wh_capture_destroy( wh_capture* cap );
+
 /* Encoder. Replaces WhisperContext::encode (WhisperContext.cpp:310-399) == whisper_encode (whisper.cpp:1084-1496).
  * melDev: FP32 device, `batch` spectrograms each [n_mel][melLen] (melStride floats apart); for each the window
  * [melOffset, melOffset + 2*n_audio_ctx) is taken and zero-padded (MelInputTensor.cpp:8-63).  Fills the
@@ -810,6 +839,12 @@ WH_API int wh_op_align_matrix( void* stream, const void* qF16, int64_t qLayerStr
  * row 0 of the trace is 2, column 0 is 1; walked back from ( R, nKeys ). framesDev: int32 [windows][rowMax], the smallest key index of the path inside each row
  * (a path cell in column 0 of the table counts as key 0), -1 for rows >= R; a window with R == 0 or nKeys == 0 is all -1. */
 WH_API int wh_op_dtw( void* stream, const float* xDev, int windows, int rowMax, int keyMax, const int32_t* rowsDev, const int32_t* keysDev, int32_t* framesDev );
+/* The kernel of wh_capture_append on device pointers: srcDev holds the chunk (`frames` sample frames, s16 or f32, 1 or 2 channels, aligned to its sample type),
+ * n is the buffer position in front of it. Writes monoDev [n, n + frames), stereoDev (may be NULL: stereo not kept) [2 n, 2 ( n + frames )) and
+ * featDev [( n + frames ) / 256 - n / 256][3]; reads monoDev [256 ( n / 256 ), n). WH_E_BOUNDS when n + frames > capSamples, WH_E_INVALIDARG for another format
+ * or channel count, negative sizes, a null or misaligned pointer with frames > 0: nothing is launched. frames == 0 launches nothing and succeeds. */
+WH_API int wh_op_capture_append( void* stream, const void* srcDev, int format, int channels, int64_t n, int64_t frames, int64_t capSamples, float* monoDev,
+	float* stereoDev, float* featDev );
 
 #ifdef __cplusplus
 }

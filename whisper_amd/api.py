@@ -105,6 +105,15 @@ def lib():
         L.whisperc_vad.argtypes = [vp, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.whisperc_plan_chunks.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, vp, vp, C.c_int32, C.POINTER(C.c_int32)]
         L.whisperc_debug_vad_decide.argtypes = [vp, C.c_int64, vp, C.POINTER(C.c_int64)]
+        L.whisperc_capture_create.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32, C.POINTER(vp)]
+        L.whisperc_capture_write.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_uint32]
+        L.whisperc_capture_close.argtypes = [vp]
+        L.whisperc_capture_dropped.argtypes = [vp]
+        L.whisperc_capture_dropped.restype = C.c_uint64
+        L.whisperc_capture_destroy.argtypes = [vp]
+        L.whisperc_capture_destroy.restype = None
+        L.whisperc_run_capture.argtypes = [vp, vp, C.c_char_p, C.c_uint32, vp, vp, vp, vp]
+        L.whisperc_run_capture_params.argtypes = [vp, vp, C.c_char_p, C.c_uint32, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -249,6 +258,52 @@ def plan_chunks(pcm: np.ndarray, max_len: int = 480000, min_len: int = 240000, p
     first, count = np.zeros(n.value, np.int64), np.zeros(n.value, np.int64)
     _check(lib().whisperc_plan_chunks(*args, first.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p), n.value, C.byref(n)), "plan_chunks")
     return [(int(f), int(c)) for f, c in zip(first, count)]
+
+
+CAPTURE_STEREO, CAPTURE_NO_DROP = 1, 2                      # eCaptureFlags
+LISTENING, VOICE, TRANSCRIBING, STALLED = 1, 2, 4, 0x80     # eCaptureStatus bits
+_SHOULD_CANCEL_T = C.CFUNCTYPE(C.c_int32, C.c_void_p)
+_CAPTURE_STATUS_T = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_uint8)
+_CAPTURE_PIECE_T = C.CFUNCTYPE(None, C.c_void_p, C.c_int64, C.c_int64)
+
+
+class Capture:
+    """iPcmCapture: a stream of 16 kHz PCM that the caller writes, from any thread, while Context.run_capture transcribes it on another. Durations in seconds
+    (the reference's sCaptureParams). stereo: keep the two channels, so that Context.speakers() answers for every piece. no_drop: never discard samples when
+    transcription falls behind -- the loop waits for the running piece, and write() blocks while more than max_duration + 1 s is queued and a loop is
+    draining: for a source that is not real time."""
+
+    def __init__(self, min_duration: float = 2.0, max_duration: float = 3.0, drop_start_silence: float = 0.25, pause_duration: float = 0.333,
+                 stereo: bool = False, no_drop: bool = False):
+        self.h = C.c_void_p()
+        self.stereo, self.no_drop = stereo, no_drop
+        _check(lib().whisperc_capture_create(min_duration, max_duration, drop_start_silence, pause_duration,
+                                             (CAPTURE_STEREO if stereo else 0) | (CAPTURE_NO_DROP if no_drop else 0), C.byref(self.h)), "createPcmCapture")
+
+    def write(self, samples: np.ndarray):
+        """int16 or float32, [n] (mono) or [n, 2] (interleaved stereo); the dtype and the channel count of a capture do not change"""
+        a = np.ascontiguousarray(samples)
+        if a.dtype.name not in ("int16", "float32") or a.ndim not in (1, 2) or (a.ndim == 2 and a.shape[1] != 2):
+            raise ValueError("Capture.write: int16 or float32 of shape [n] or [n, 2]")
+        _check(lib().whisperc_capture_write(self.h, a.ctypes.data_as(C.c_void_p), _PCM_FORMATS[a.dtype.name], 1 if a.ndim == 1 else 2, a.shape[0]), "iPcmCapture.write")
+
+    def close(self):
+        """the end of the stream: run_capture drains what is queued, transcribes what is left if it holds voice, and returns"""
+        _check(lib().whisperc_capture_close(self.h), "iPcmCapture.close")
+
+    def dropped_chunks(self) -> int:
+        return int(lib().whisperc_capture_dropped(self.h))
+
+    def release(self):
+        if self.h:
+            lib().whisperc_capture_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
 
 
 class Model:
@@ -476,6 +531,53 @@ class Context:
                                                 pt.ctypes.data_as(C.c_void_p) if len(pt) else None, len(pt), n_max_text_ctx,
                                                 prog, 4096, C.byref(n)), "runStreamed")
         return hr, list(prog[:min(n.value, 4096)])
+
+    def run_capture(self, capture: "Capture", on_piece=None, on_status=None, should_cancel=None, language: str = "en", flags: int = 0, max_tokens: int = 0,
+                    prompt: Optional[Sequence[int]] = None, n_max_text_ctx: int = -1, beam_width: int = 0, audio_ctx: int = 0):
+        """iContext::runCapture: the reference's capture loop over `capture` until it is closed and drained, or should_cancel() returns true. Every piece the
+        loop fires -- at a pause once min_duration is buffered, or at max_duration -- is a run_full on a worker thread of the library with this context's
+        decoding options; segment times are stream times. Returns the pieces as [(start_sample, n_samples, results)].
+        on_piece(start_sample, n_samples, results) is called behind each piece, on the worker thread, while results() / speakers() of the context are that
+        piece's; on_status(word) whenever a bit of LISTENING | VOICE | TRANSCRIBING | STALLED changes: on the calling thread, but for the fall of TRANSCRIBING
+        of a capture without no_drop, which comes from the worker thread when the piece's job ends.
+        language, flags, max_tokens, prompt, n_max_text_ctx, beam_width and audio_ctx are run_full's and hold for every piece. The other keywords of run_full
+        belong elsewhere: stereo is the capture's, another sample_rate is out of scope, and a piece has no offset or duration of its own."""
+        pt = np.ascontiguousarray(prompt if prompt is not None else [], np.int32)
+        pieces = []
+        errors = []
+
+        def piece(_pv, start, n):
+            try:
+                res = self.results()
+                pieces.append((int(start), int(n), res))
+                if on_piece is not None:
+                    on_piece(int(start), int(n), res)
+            except BaseException as e:        # an exception cannot cross the C frames
+                errors.append(e)
+
+        def status(_pv, word):
+            try:
+                if on_status is not None:
+                    on_status(int(word))
+            except BaseException as e:
+                errors.append(e)
+            return 0
+
+        def cancel(_pv):
+            try:
+                return 1 if (errors or (should_cancel is not None and should_cancel())) else 0
+            except BaseException as e:
+                errors.append(e)
+                return 1
+
+        cbs = (_SHOULD_CANCEL_T(cancel), _CAPTURE_STATUS_T(status), _CAPTURE_PIECE_T(piece))
+        hr = lib().whisperc_run_capture_params(self.h, capture.h if capture is not None else None, language.encode(), flags, max_tokens,
+                                               pt.ctypes.data_as(C.c_void_p) if len(pt) else None, len(pt), n_max_text_ctx, audio_ctx, beam_width,
+                                               C.cast(cbs[0], C.c_void_p), C.cast(cbs[1], C.c_void_p), C.cast(cbs[2], C.c_void_p), None)
+        if errors:
+            raise errors[0]
+        _check(hr, "runCapture")
+        return pieces
 
     def detect_language(self, pcm: np.ndarray, offset_ms: int = 0, sample_rate: int = 16000):
         """whisper_lang_auto_detect on the 30 s window at offset_ms of mono float32 16 kHz PCM: (code, {code: p}). The p are the reference's

@@ -52,6 +52,7 @@ EXPORTS = [
     "wh_lang_detect", "wh_model_lang_count", "wh_op_lang_probs",
     "wh_resample_out_len", "wh_resample", "wh_resample_host", "wh_resample_host_multi", "wh_resample_taps",
     "wh_vad_frame_count", "wh_vad_features", "wh_vad_features_host",
+    "wh_capture_create", "wh_capture_append", "wh_capture_clear", "wh_capture_take", "wh_capture_size", "wh_capture_destroy", "wh_op_capture_append",
     "wh_dequantize",
     "wh_model_set_alignment_heads", "wh_align_tokens", "wh_op_align_matrix", "wh_op_dtw",
     "wh_op_vocab_soft_max_scaled", "wh_op_sample_draw", "wh_op_philox_u", "wh_context_set_sampling", "wh_context_set_no_speech", "wh_decode_window_no_speech",
@@ -252,6 +253,13 @@ def lib():
         L.wh_vad_frame_count.argtypes = [i64, C.POINTER(i64)]
         L.wh_vad_features.argtypes = [vp, vp, i64, vp]
         L.wh_vad_features_host.argtypes = [vp, i64, vp]
+        L.wh_capture_create.argtypes = [vp, i32, i32, i64, C.POINTER(vp)]
+        L.wh_capture_append.argtypes = [vp, vp, i32, i64, vp, i64, C.POINTER(i64)]
+        L.wh_capture_clear.argtypes = [vp]
+        L.wh_capture_take.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
+        L.wh_capture_size.argtypes = [vp, C.POINTER(i64)]
+        L.wh_capture_destroy.argtypes = [vp]
+        L.wh_op_capture_append.argtypes = [vp, vp, i32, i32, i64, i64, i64, vp, vp, vp]
         L.wh_dequantize.argtypes = [vp, i32, vp, i64, vp]
         L.wh_model_set_alignment_heads.argtypes = [vp, vp, i32]
         L.wh_align_tokens.argtypes = [vp, i32, vp, vp, vp, i32, vp]

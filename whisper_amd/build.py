@@ -23,10 +23,10 @@ CLI_BIN = os.path.join(LIB_DIR, "whisper-main")
 
 # the runtime behind the C ABI, one unit per responsibility; runtime.h holds what they share (host code: the kernel units do not include it)
 RUNTIME_SOURCES = ["options.hip", "model.hip", "comm.hip", "context.hip", "encode.hip", "exact_graphs.hip", "step_graph.hip", "decode.hip", "beam.hip", "ops_debug.hip"]
-# resample.hip and vad.hip keep their kernels next to the entry points that own their tables, dequant.hip next to wh_dequantize, align.hip next to wh_align_tokens; boost.hip is the host half of phrase boosting: kernel units that do include runtime.h
-HIP_SOURCES = ["gemm_persistent.hip", "gemm_decode.hip", "gemm_tiled.hip", "attn_dec.hip", "decode1.hip", "attn_enc.hip", "gemm.hip", "elementwise.hip", "sample.hip", "mel.hip", "exact.hip", "resample.hip", "vad.hip", "dequant.hip",
+# resample.hip and vad.hip keep their kernels next to the entry points that own their tables, capture.hip next to the wh_capture it fills, dequant.hip next to wh_dequantize, align.hip next to wh_align_tokens; boost.hip is the host half of phrase boosting: kernel units that do include runtime.h
+HIP_SOURCES = ["gemm_persistent.hip", "gemm_decode.hip", "gemm_tiled.hip", "attn_dec.hip", "decode1.hip", "attn_enc.hip", "gemm.hip", "elementwise.hip", "sample.hip", "mel.hip", "exact.hip", "resample.hip", "vad.hip", "capture.hip", "dequant.hip",
                "align.hip", "boost.hip"] + RUNTIME_SOURCES
-RUNTIME_H_USERS = RUNTIME_SOURCES + ["resample.hip", "vad.hip", "dequant.hip", "align.hip", "boost.hip"]
+RUNTIME_H_USERS = RUNTIME_SOURCES + ["resample.hip", "vad.hip", "capture.hip", "dequant.hip", "align.hip", "boost.hip"]
 # exact.hip restates the reference CPU path's summation order: a fused multiply-add only where the source says fma()
 EXTRA_FLAGS = {"exact.hip": ["-ffp-contract=off"]}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

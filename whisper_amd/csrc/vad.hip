@@ -16,123 +16,35 @@
 // cos( pi n ) instead of -sin( 0 ), and 8 tiles of 16 bins cover all 129. A wave owns tiles `wave` and `wave + 4`: four accumulator chains per A operand.
 // |X|^2 goes to LDS [16][129]; then a wave reduces four frames, a lane two bins of each (lane 0 a third), through xor butterflies -- no atomics, and lane 0
 // writes the frame's three floats.
+// Everything behind the staging of the 16 frames is vadTileFeatures of vad_device.h, which the capture kernel (capture.hip) calls on its own staging: a frame's
+// three floats are the same bits from either kernel.
 #include "runtime.h"
+#include "vad_device.h"
 
 namespace wh
 {
 	namespace
 	{
-		constexpr int VAD_N = 256, VAD_FR = 16, VAD_THREADS = 256, VAD_WAVES = VAD_THREADS / 64;
-		// Frames start 256 floats apart = a multiple of the 32 LDS banks, and the A operand reads one sample of each of the 16 frames per instruction:
-		// sample s of the workgroup lives at s + 2 ( s / 256 ), so lane ( frame, kq ) of a half wave reads bank 2 frame + kq + n0 -- 32 different ones.
-		constexpr int VAD_X_STRIDE = VAD_N + 2;
-		constexpr int VAD_P_STRIDE = 129;	 // |X|^2 of bins 0 .. 128
 		constexpr int64_t VAD_MAX_SAMPLES = (int64_t)1 << 40;
-		typedef double vadF64x4 __attribute__( ( ext_vector_type( 4 ) ) );
 
 		__global__ void __launch_bounds__( VAD_THREADS ) vadFeaturesKernel( const float* __restrict__ pcm, long long nFrames, const double* __restrict__ twiddles,
 			float* __restrict__ feat )
 		{
-			__shared__ double tw[ 2 ][ VAD_N ];	  // cos, -sin of 2 pi i / 256
-			__shared__ float xs[ VAD_FR * VAD_X_STRIDE ];
-			__shared__ double pw[ VAD_FR ][ VAD_P_STRIDE ];
+			__shared__ VadTile t;
 
-			const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+			const int tid = threadIdx.x;
 			const long long f0 = (long long)blockIdx.x * VAD_FR;
-			for( int i = tid; i < 2 * VAD_N; i += VAD_THREADS ) ( &tw[ 0 ][ 0 ] )[ i ] = twiddles[ i ];
+			for( int i = tid; i < 2 * VAD_N; i += VAD_THREADS ) ( &t.tw[ 0 ][ 0 ] )[ i ] = twiddles[ i ];
 			for( int i = tid; i < VAD_FR * VAD_N; i += VAD_THREADS )
 			{
 				const int f = i >> 8, n = i & 255;
 				// a frame at or beyond nFrames is all zeros: nothing of the ignored tail, nor anything behind the buffer, is read
-				xs[ f * VAD_X_STRIDE + n ] = f0 + f < nFrames ? __fmul_rn( pcm[ ( f0 + f ) * VAD_N + n ], 32768.0f ) : 0.0f;
+				t.xs[ f * VAD_X_STRIDE + n ] = f0 + f < nFrames ? __fmul_rn( pcm[ ( f0 + f ) * VAD_N + n ], 32768.0f ) : 0.0f;
 			}
 			__syncthreads();
-
-			// ---- DFT bins 0 .. 128: A lane & 15 = frame, lane >> 4 = sample within the 4-deep K step; B lane & 15 = bin, lane >> 4 = sample ----
-			const int row = lane & 15, kq = lane >> 4;
-			{
-				const int bin0 = wave * 16 + row, bin1 = ( wave + VAD_WAVES ) * 16 + row;
-				// the column of bin 0 carries bin 128 in its imaginary accumulator: cos( 2 pi ( 128 n ) / 256 ) = cos( pi n )
-				const double* const imTab0 = &tw[ 0 ][ 0 ] + ( bin0 == 0 ? 0 : VAD_N );
-				const int imBin0 = bin0 == 0 ? 128 : bin0;
-				int re0i = ( kq * bin0 ) & 255, im0i = ( kq * imBin0 ) & 255, b1i = ( kq * bin1 ) & 255;
-				const int re0s = ( 4 * bin0 ) & 255, im0s = ( 4 * imBin0 ) & 255, b1s = ( 4 * bin1 ) & 255;
-				const float* const px = xs + row * VAD_X_STRIDE + kq;
-				vadF64x4 re0 = { 0.0, 0.0, 0.0, 0.0 }, im0 = re0, re1 = re0, im1 = re0;
-				for( int n0 = 0; n0 < VAD_N; n0 += 4 )
-				{
-					const double a = (double)px[ n0 ];
-					re0 = __builtin_amdgcn_mfma_f64_16x16x4f64( a, tw[ 0 ][ re0i ], re0, 0, 0, 0 );
-					im0 = __builtin_amdgcn_mfma_f64_16x16x4f64( a, imTab0[ im0i ], im0, 0, 0, 0 );
-					re1 = __builtin_amdgcn_mfma_f64_16x16x4f64( a, tw[ 0 ][ b1i ], re1, 0, 0, 0 );
-					im1 = __builtin_amdgcn_mfma_f64_16x16x4f64( a, tw[ 1 ][ b1i ], im1, 0, 0, 0 );
-					re0i = ( re0i + re0s ) & 255;
-					im0i = ( im0i + im0s ) & 255;
-					b1i = ( b1i + b1s ) & 255;
-				}
-				// D: column = lane & 15 = bin of the tile, row = ( lane >> 4 ) + 4 r = frame
-#pragma unroll
-				for( int r = 0; r < 4; r++ )
-				{
-					const int f = kq + 4 * r;
-					if( bin0 == 0 )
-					{
-						pw[ f ][ 0 ] = re0[ r ] * re0[ r ];
-						pw[ f ][ 128 ] = im0[ r ] * im0[ r ];
-					}
-					else pw[ f ][ bin0 ] = fma( re0[ r ], re0[ r ], im0[ r ] * im0[ r ] );
-					pw[ f ][ bin1 ] = fma( re1[ r ], re1[ r ], im1[ r ] * im1[ r ] );
-				}
-			}
-			__syncthreads();
-
-			// ---- per frame: energy, the dominant bin, the two spectral sums. Wave w owns frames 4 w .. 4 w + 3 ----
-			for( int j = 0; j < VAD_FR / VAD_WAVES; j++ )
-			{
-				const int f = wave * ( VAD_FR / VAD_WAVES ) + j;
-				if( f0 + f >= nFrames ) break;	  // wave-uniform
-				const float* const x = xs + f * VAD_X_STRIDE;
-				double e = 0.0;
-#pragma unroll
-				for( int q = 0; q < 4; q++ )
-				{
-					const float v = x[ lane + 64 * q ];
-					e += (double)__fmul_rn( v, v );
-				}
-				const double pa = pw[ f ][ lane ], pb = pw[ f ][ lane + 64 ];
-				// bins 1 .. 127 stand for two of the 256, bins 0 and 128 for one
-				const double wa = lane == 0 ? 1.0 : 2.0;
-				double sumAbs = wa * sqrt( pa ) + 2.0 * sqrt( pb );
-				double sumLn = wa * ( 0.5 * log( pa ) ) + 2.0 * ( 0.5 * log( pb ) );
-				if( lane == 0 )
-				{
-					const double pn = pw[ f ][ 128 ];
-					sumAbs += sqrt( pn );
-					sumLn += 0.5 * log( pn );
-				}
-				// the first maximum of bins 0 .. 127: a strictly greater value, or an equal one at a lower bin, replaces
-				double best = pa;
-				int bestBin = lane;
-				if( pb > pa ) { best = pb; bestBin = lane + 64; }
-#pragma unroll
-				for( int o = 32; o > 0; o >>= 1 )
-				{
-					e += __shfl_xor( e, o, 64 );
-					sumAbs += __shfl_xor( sumAbs, o, 64 );
-					sumLn += __shfl_xor( sumLn, o, 64 );
-					const double ob = __shfl_xor( best, o, 64 );
-					const int oi = __shfl_xor( bestBin, o, 64 );
-					if( ob > best || ( ob == best && oi < bestBin ) ) { best = ob; bestBin = oi; }
-				}
-				if( lane == 0 )
-				{
-					float* const out = feat + ( f0 + f ) * 3;
-					out[ 0 ] = (float)sqrt( (double)(float)( e * ( 1.0 / VAD_N ) ) );
-					out[ 1 ] = __fmul_rn( 62.5f, (float)bestBin );
-					const float ratio = (float)( exp( sumLn * ( 1.0 / VAD_N ) ) / ( sumAbs * ( 1.0 / VAD_N ) ) );
-					out[ 2 ] = __fmul_rn( -10.0f, (float)log10( (double)ratio ) );
-				}
-			}
+			// the arithmetic is vad_device.h's, shared with the capture kernel
+			const long long left = nFrames - f0;
+			vadTileFeatures( t, 0, left < VAD_FR ? (int)left : VAD_FR, feat, f0 );
 		}
 
 		// The twiddle table: one per device, built in double on the host, uploaded on first use under the lock and kept for the life of the process
@@ -140,36 +52,39 @@ namespace wh
 		std::mutex g_vadMutex;
 		std::map<int, const double*> g_vadTables;
 		std::vector<Allocation> g_vadAllocations;
+	}	// namespace
 
-		int vadTable( hipStream_t stream, const double*& out )
+	int vadTable( hipStream_t stream, const double*& out )
+	{
+		int dev = 0;
+		WH_HIP( hipGetDevice( &dev ) );
+		std::lock_guard<std::mutex> lk( g_vadMutex );
+		const auto it = g_vadTables.find( dev );
+		if( it != g_vadTables.end() ) { out = it->second; return 0; }
+		const double PI = 3.14159265358979323846;
+		std::vector<double> host( 2 * VAD_N );
+		for( int i = 0; i < VAD_N; i++ )
 		{
-			int dev = 0;
-			WH_HIP( hipGetDevice( &dev ) );
-			std::lock_guard<std::mutex> lk( g_vadMutex );
-			const auto it = g_vadTables.find( dev );
-			if( it != g_vadTables.end() ) { out = it->second; return 0; }
-			const double PI = 3.14159265358979323846;
-			std::vector<double> host( 2 * VAD_N );
-			for( int i = 0; i < VAD_N; i++ )
-			{
-				const double t = 2.0 * PI * (double)i / (double)VAD_N;
-				host[ i ] = std::cos( t );
-				host[ VAD_N + i ] = -std::sin( t );
-			}
-			// the quarter points exactly: bins 0 and 128 are sums of +-x[n]
-			host[ 0 ] = 1.0; host[ 64 ] = 0.0; host[ 128 ] = -1.0; host[ 192 ] = 0.0;
-			host[ VAD_N + 0 ] = 0.0; host[ VAD_N + 64 ] = -1.0; host[ VAD_N + 128 ] = 0.0; host[ VAD_N + 192 ] = 1.0;
-			Allocation a;
-			WH_HIP( guardedAlloc( a, (int64_t)host.size() * 8, -1, "vad twiddles", stream ) );
-			// synchronous: `host` dies with this call, and every stream may read the table afterwards
-			hipError_t e = hipMemcpyAsync( a.body, host.data(), host.size() * 8, hipMemcpyHostToDevice, stream );
-			if( e == hipSuccess ) e = hipStreamSynchronize( stream );
-			if( e != hipSuccess ) { (void)guardedFree( a ); return hipFail( e, "vad twiddles upload", __FILE__, __LINE__ ); }
-			g_vadAllocations.push_back( a );
-			out = g_vadTables[ dev ] = (const double*)a.body;
-			return 0;
+			const double t = 2.0 * PI * (double)i / (double)VAD_N;
+			host[ i ] = std::cos( t );
+			host[ VAD_N + i ] = -std::sin( t );
 		}
+		// the quarter points exactly: bins 0 and 128 are sums of +-x[n]
+		host[ 0 ] = 1.0; host[ 64 ] = 0.0; host[ 128 ] = -1.0; host[ 192 ] = 0.0;
+		host[ VAD_N + 0 ] = 0.0; host[ VAD_N + 64 ] = -1.0; host[ VAD_N + 128 ] = 0.0; host[ VAD_N + 192 ] = 1.0;
+		Allocation a;
+		WH_HIP( guardedAlloc( a, (int64_t)host.size() * 8, -1, "vad twiddles", stream ) );
+		// synchronous: `host` dies with this call, and every stream may read the table afterwards
+		hipError_t e = hipMemcpyAsync( a.body, host.data(), host.size() * 8, hipMemcpyHostToDevice, stream );
+		if( e == hipSuccess ) e = hipStreamSynchronize( stream );
+		if( e != hipSuccess ) { (void)guardedFree( a ); return hipFail( e, "vad twiddles upload", __FILE__, __LINE__ ); }
+		g_vadAllocations.push_back( a );
+		out = g_vadTables[ dev ] = (const double*)a.body;
+		return 0;
+	}
 
+	namespace
+	{
 		int launchVadFeatures( hipStream_t stream, const float* pcm, long long nFrames, float* feat )
 		{
 			if( nFrames <= 0 ) return 0;

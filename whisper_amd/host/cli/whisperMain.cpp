@@ -408,6 +408,61 @@ static int scoreInput( iModel* model, iContext* context, iMediaFoundation* media
 	return 0;
 }
 
+// --capture: live transcription of raw 16 kHz PCM from a file or a pipe (Whisper::createPcmCapture + iContext::runCapture)
+struct CaptureOptions
+{
+	std::string path;	 // "-" = standard input
+	int format = 1, channels = 1;	 // wh_pcm_format: 1 = s16, 4 = f32
+	sCaptureParams params;
+};
+
+// The reader thread writes what it reads, 100 ms at a time, and closes the capture at the end of the input; every piece's segments are printed by the
+// run's new_segment_callback when its transcription produces them, with stream times.
+static int runCaptureInput( iContext* context, const sFullParams& p, const CaptureOptions& co )
+{
+	FILE* in = co.path == "-" ? stdin : fopen( co.path.c_str(), "rb" );
+	if( !in ) { fprintf( stderr, "error: cannot read '%s'\n", co.path.c_str() ); return 10; }
+	ComLight::CComPtr<iPcmCapture> capture;
+	HRESULT hr = createPcmCapture( co.params, &capture );
+	if( FAILED( hr ) ) { printFailure( "failed to create the capture", hr ); return 7; }
+	iPcmCapture* const cap = capture;
+	std::atomic<HRESULT> writeResult{ S_OK };
+	std::thread reader( [ & ]() {
+		const size_t frameBytes = (size_t)co.channels * ( co.format == 1 ? 2 : 4 );
+		std::vector<char> chunk( 1600 * frameBytes );
+		size_t have = 0;
+		while( true )
+		{
+			const size_t got = fread( chunk.data() + have, 1, chunk.size() - have, in );
+			have += got;
+			if( have == chunk.size() || ( got == 0 && have >= frameBytes ) )
+			{
+				const HRESULT w = cap->write( chunk.data(), co.format, co.channels, (uint32_t)( have / frameBytes ) );
+				if( FAILED( w ) ) { writeResult = w; break; }
+				have = 0;	  // a trailing partial sample frame is dropped
+			}
+			if( got == 0 ) break;
+		}
+		cap->close();
+	} );
+	const sCaptureCallbacks callbacks{ nullptr, nullptr, nullptr };
+	hr = context->runCapture( p, callbacks, cap );
+	if( FAILED( hr ) )
+	{
+		// The reader may sit in a read of a pipe that nobody writes to any more: it is not waited for. The failure ends the process here, before anything
+		// the reader uses goes out of scope.
+		printFailure( "Unable to transcribe the stream", hr );
+		fflush( stdout );
+		fflush( stderr );
+		_exit( 10 );
+	}
+	reader.join();
+	if( in != stdin ) fclose( in );
+	if( FAILED( writeResult.load() ) ) { printFailure( "Unable to queue the stream", writeResult.load() ); return 10; }
+	if( const uint64_t dropped = cap->droppedChunks() ) fprintf( stderr, "main: WARNING: %llu chunks were dropped, transcription did not keep up\n", (unsigned long long)dropped );
+	return 0;
+}
+
 int main( int argc, char** argv )
 {
 	if( argc == 3 && !strcmp( argv[ 1 ], "--format-sample" ) ) return formatSample( argv[ 2 ] );
@@ -432,6 +487,10 @@ int main( int argc, char** argv )
 	// token -- its time with --align (forced alignment), log-probability, rank, text -- and a summary line
 	// --boost-phrases FILE --boost N (the same way; one needs the other): Whisper::setBoostedPhrases with the spellings of the file's phrases, one per line
 	// -nrn N / --no-repeat-ngram N (the same way): Whisper::setNoRepeatNgram, no text token that would complete an n-gram its window already holds (0 = off)
+	// --capture PATH (the same way; PATH "-" = standard input): live transcription of raw 16 kHz PCM instead of input files -- --capture-format s16|f32 (s16),
+	// --capture-channels 1|2 (1); --capture-min-duration / --capture-max-duration / --capture-drop-start-silence / --capture-pause-duration N seconds
+	// (sCaptureParams: 2, 3, 0.25, 0.333); --capture-no-drop: eCaptureFlags::NoDrop, for input that arrives faster than real time; -di keeps the stereo
+	CaptureOptions capture;
 	bool align = false, useFallback = false, suppressNst = false, timestampRules = false, haveBoost = false;
 	int noRepeatNgram = 0;
 	std::string scoreFile, boostFile;
@@ -457,6 +516,28 @@ int main( int argc, char** argv )
 				boostFile = argv[ ++i ];
 			}
 			else if( !strcmp( argv[ i ], "--boost" ) ) { value = &boost; haveBoost = true; }
+			else if( !strcmp( argv[ i ], "--capture" ) )
+			{
+				if( i + 1 >= argc ) { fprintf( stderr, "error: --capture needs a path (- = standard input)\n" ); return 2; }
+				capture.path = argv[ ++i ];
+			}
+			else if( !strcmp( argv[ i ], "--capture-format" ) )
+			{
+				const char* const v = i + 1 < argc ? argv[ ++i ] : "";
+				if( !strcmp( v, "s16" ) ) capture.format = 1;
+				else if( !strcmp( v, "f32" ) ) capture.format = 4;
+				else { fprintf( stderr, "error: --capture-format takes s16 or f32\n" ); return 2; }
+			}
+			else if( !strcmp( argv[ i ], "--capture-channels" ) )
+			{
+				capture.channels = i + 1 < argc ? atoi( argv[ ++i ] ) : 0;
+				if( capture.channels != 1 && capture.channels != 2 ) { fprintf( stderr, "error: --capture-channels takes 1 or 2\n" ); return 2; }
+			}
+			else if( !strcmp( argv[ i ], "--capture-no-drop" ) ) capture.params.flags |= (uint32_t)eCaptureFlags::NoDrop;
+			else if( !strcmp( argv[ i ], "--capture-min-duration" ) ) value = &capture.params.minDuration;
+			else if( !strcmp( argv[ i ], "--capture-max-duration" ) ) value = &capture.params.maxDuration;
+			else if( !strcmp( argv[ i ], "--capture-drop-start-silence" ) ) value = &capture.params.dropStartSilence;
+			else if( !strcmp( argv[ i ], "--capture-pause-duration" ) ) value = &capture.params.pauseDuration;
 			else if( !strcmp( argv[ i ], "-nrn" ) || !strcmp( argv[ i ], "--no-repeat-ngram" ) )
 			{
 				if( i + 1 >= argc ) { fprintf( stderr, "error: %s needs a number\n", argv[ i ] ); return 2; }
@@ -481,8 +562,24 @@ int main( int argc, char** argv )
 		return 2;
 	}
 	if( const int stop = parse( argc, argv, o ) ) return stop - 1;
-	if( dump ) { dumpOptions( o ); return 0; }
+	if( dump )
+	{
+		dumpOptions( o );
+		// a second line, only with --capture: the reference's parser has no such options
+		if( !capture.path.empty() )
+			printf( "{\"capture\":\"%s\",\"format\":\"%s\",\"channels\":%d,\"min_duration\":%g,\"max_duration\":%g,\"drop_start_silence\":%g,\"pause_duration\":%g,\"flags\":%u}\n",
+				capture.path.c_str(), capture.format == 1 ? "s16" : "f32", capture.channels, capture.params.minDuration, capture.params.maxDuration,
+				capture.params.dropStartSilence, capture.params.pauseDuration, capture.params.flags | ( o.diarize ? (uint32_t)eCaptureFlags::Stereo : 0u ) );
+		return 0;
+	}
 	if( o.colors && !isatty( STDOUT_FILENO ) ) o.colors = false;
+	if( !capture.path.empty() )
+	{
+		if( !o.inputs.empty() ) { fprintf( stderr, "error: --capture takes no input files\n" ); return 2; }
+		if( !scoreFile.empty() ) { fprintf( stderr, "error: --capture and --score do not go together\n" ); return 2; }
+		if( o.diarize ) capture.params.flags |= (uint32_t)eCaptureFlags::Stereo;
+		o.inputs.push_back( "" );	 // one pass of the loop below: the stream
+	}
 
 	if( o.inputs.empty() )
 	{
@@ -600,6 +697,12 @@ int main( int argc, char** argv )
 		std::atomic_bool aborted{ false };
 		p.encoder_begin_callback = &onEncoderBegin;
 		p.encoder_begin_callback_user_data = &aborted;
+
+		if( !capture.path.empty() )
+		{
+			if( const int rc = runCaptureInput( context, p, capture ) ) return rc;
+			continue;
+		}
 
 		hr = E_NOTIMPL;
 		if( !p.flag( eFullParamsFlags::TokenTimestamps ) )

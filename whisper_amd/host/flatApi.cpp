@@ -353,6 +353,61 @@ WHISPER_EXPORT int32_t whisperc_run_streamed_stereo( void* ctx, const float* pcm
 	CHECK( createPcmReader( std::vector<float>( pcm, pcm + nSamples ), stereoCopy( stereo, nSamples ), &reader ) );
 	return runStreamedOn( ctx, p, reader, progressOut, progressCap, progressCount );
 }
+// Live capture (Whisper::createPcmCapture, iPcmCapture, iContext::runCapture). durations in seconds, flags: eCaptureFlags (Stereo 1, NoDrop 2)
+WHISPER_EXPORT int32_t whisperc_capture_create( float minDuration, float maxDuration, float dropStartSilence, float pauseDuration, uint32_t flags, void** captureOut )
+{
+	if( !captureOut ) return E_POINTER;
+	sCaptureParams cp;
+	cp.minDuration = minDuration;
+	cp.maxDuration = maxDuration;
+	cp.dropStartSilence = dropStartSilence;
+	cp.pauseDuration = pauseDuration;
+	cp.flags = flags;
+	iPcmCapture* cap = nullptr;
+	CHECK( createPcmCapture( cp, &cap ) );
+	*captureOut = cap;
+	return S_OK;
+}
+WHISPER_EXPORT int32_t whisperc_capture_write( void* capture, const void* samples, int32_t format, int32_t channels, uint32_t frames )
+{
+	if( !capture ) return E_POINTER;
+	return ( (iPcmCapture*)capture )->write( samples, format, channels, frames );
+}
+WHISPER_EXPORT int32_t whisperc_capture_close( void* capture )
+{
+	if( !capture ) return E_POINTER;
+	return ( (iPcmCapture*)capture )->close();
+}
+WHISPER_EXPORT uint64_t whisperc_capture_dropped( void* capture )
+{
+	return capture ? ( (iPcmCapture*)capture )->droppedChunks() : 0;
+}
+WHISPER_EXPORT void whisperc_capture_destroy( void* capture )
+{
+	if( capture ) ( (iPcmCapture*)capture )->Release();
+}
+// iContext::runCapture with the parameters of whisperc_run_full; pfnPiece( pv, startSample, nSamples ) is called behind each piece's job, on the library's
+// worker thread, while whisperc_result_* still answer for that piece. Any of the three callbacks may be NULL.
+WHISPER_EXPORT int32_t whisperc_run_capture_params( void* ctx, void* capture, const char* language, uint32_t flags, int maxTokens, const int32_t* promptTokens,
+	int nPrompt, int nMaxTextCtx, int audioCtx, int beamWidth, int32_t ( *pfnShouldCancelC )( void* ), int32_t ( *pfnCaptureStatusC )( void*, uint8_t ),
+	void ( *pfnPiece )( void*, int64_t, int64_t ), void* pv )
+{
+	if( !ctx ) return E_POINTER;
+	sFullParams p;
+	CHECK( fullParams( beamWidth > 0 ? eSamplingStrategy::BeamSearch : eSamplingStrategy::Greedy, language, flags, maxTokens, promptTokens, nPrompt, nMaxTextCtx, p ) );
+	p.audio_ctx = audioCtx;
+	if( beamWidth > 0 ) p.beam_search.beam_width = beamWidth;
+	sCaptureCallbacks cb;
+	cb.shouldCancel = reinterpret_cast<pfnShouldCancel>( pfnShouldCancelC );
+	cb.captureStatus = reinterpret_cast<pfnCaptureStatus>( pfnCaptureStatusC );
+	cb.pv = pv;
+	return contextRunCapture( ctx, p, cb, (const iPcmCapture*)capture, pfnPiece, pv );
+}
+WHISPER_EXPORT int32_t whisperc_run_capture( void* ctx, void* capture, const char* language, uint32_t flags, int32_t ( *pfnShouldCancelC )( void* ),
+	int32_t ( *pfnCaptureStatusC )( void*, uint8_t ), void ( *pfnPiece )( void*, int64_t, int64_t ), void* pv )
+{
+	return whisperc_run_capture_params( ctx, capture, language, flags, 0, nullptr, 0, -1, 0, 0, pfnShouldCancelC, pfnCaptureStatusC, pfnPiece, pv );
+}
 // iContext::detectSpeaker( { t0, t1 } in 100 ns ticks ): *channel = eSpeakerChannel (0 unsure, 1 left, 2 right, 0xFF no stereo data). Outside a run's
 // callbacks: OLE_E_BLANK, like the reference.
 WHISPER_EXPORT int32_t whisperc_detect_speaker( void* ctx, uint64_t t0, uint64_t t1, uint8_t* channel )

@@ -179,4 +179,13 @@ namespace Whisper
 	HRESULT contextDetectLanguage( void* ctx, const float* pcm, uint32_t nSamples, int offsetMs, float* probs, uint32_t probsCap, int& langId );
 	int contextDetectedLanguage( void* ctx, float& p );
 	HRESULT contextSetDeviceFlags( void* ctx, uint32_t flags, int parityThreads );
+
+	// ---- live capture (capture.cpp; captureLoop.h holds the loop) ----
+	// called on the worker thread behind every piece whose runFull succeeded, while the context's results are that piece's
+	using pfnCapturePiece = void ( * )( void* pv, int64_t startSample, int64_t nSamples );
+	// iContext::runCapture of `context`, whose device context is `gpu` (it names the device of the capture buffer; nothing is queued on its stream)
+	HRESULT runCaptureLoop( iContext* context, wh_context* gpu, const sFullParams& params, const sCaptureCallbacks& callbacks, const iAudioCapture* reader,
+		pfnCapturePiece pfnPiece, void* pvPiece );
+	// the same through an iContext of this library (flatApi.cpp: whisperc_run_capture)
+	HRESULT contextRunCapture( void* ctx, const sFullParams& params, const sCaptureCallbacks& callbacks, const iAudioCapture* reader, pfnCapturePiece pfnPiece, void* pvPiece );
 }

@@ -277,7 +277,15 @@ namespace Whisper
 			const std::vector<sWindowStats>& lastWindowStats() const { return windowStats; }
 			HRESULT runFull( const sFullParams& params, const iAudioBuffer* buffer ) override;
 			HRESULT runStreamed( const sFullParams& params, const sProgressSink& progress, const iAudioReader* reader ) override;
-			HRESULT runCapture( const sFullParams&, const sCaptureCallbacks&, const iAudioCapture* ) override { return E_NOTIMPL; }
+			// capture.cpp: the reference's capture loop over an iPcmCapture, every piece a runFull of this context on a worker thread
+			HRESULT runCapture( const sFullParams& params, const sCaptureCallbacks& callbacks, const iAudioCapture* reader ) override
+			{
+				return runCaptureLoop( this, gpu, params, callbacks, reader, nullptr, nullptr );
+			}
+			HRESULT runCapturePieces( const sFullParams& params, const sCaptureCallbacks& callbacks, const iAudioCapture* reader, pfnCapturePiece pfnPiece, void* pvPiece )
+			{
+				return runCaptureLoop( this, gpu, params, callbacks, reader, pfnPiece, pvPiece );
+			}
 			HRESULT getResults( eResultFlags flags, iTranscribeResult** pp ) const override;
 			HRESULT detectSpeaker( const sTimeInterval& time, eSpeakerChannel& result ) const override
 			{
@@ -1237,6 +1245,10 @@ namespace Whisper
 	HRESULT contextSetDeviceFlags( void* ctx, uint32_t flags, int parityThreads )
 	{
 		return static_cast<ContextImpl*>( (iContext*)ctx )->setDeviceFlags( flags, parityThreads );
+	}
+	HRESULT contextRunCapture( void* ctx, const sFullParams& params, const sCaptureCallbacks& callbacks, const iAudioCapture* reader, pfnCapturePiece pfnPiece, void* pvPiece )
+	{
+		return static_cast<ContextImpl*>( (iContext*)ctx )->runCapturePieces( params, callbacks, reader, pfnPiece, pvPiece );
 	}
 	// a reader over PCM that is decoded already (whisperc_run_streamed_stereo): what loadAudioFileData makes of a WAV image, with the caller's stereo PCM
 	HRESULT createPcmReader( std::vector<float>&& mono, std::vector<float>&& stereo, iAudioReader** pp )
