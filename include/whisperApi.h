@@ -293,14 +293,15 @@ namespace Whisper
 		virtual HRESULT getReader( IMFSourceReader** pp ) const = 0;
 		virtual const sCaptureParams& getParams() const = 0;
 	};
-	// Extension (no counterpart in the reference, whose captures are sound cards): a capture fed by the caller -- a pipe, a socket, its own code. 16 kHz only.
+	// Extension (no counterpart in the reference, whose captures are sound cards): a capture fed by the caller -- a pipe, a socket, its own code -- at 16 kHz or,
+	// made by createPcmCaptureAtRate, at any rate from 1000 to 384000 Hz, which the capture buffer resamples chunk by chunk with the filter of the file path.
 	// The only kind of capture iContext::runCapture of this library takes. write may be called from any thread while runCapture runs on another.
 	// {3a9e5c72-1b4d-4f08-b6a1-7c2e9d5f8a13}
 	struct iPcmCapture : public iAudioCapture
 	{
 		static constexpr ComLight::GUID iid() { return { 0x3a9e5c72, 0x1b4d, 0x4f08, { 0xb6, 0xa1, 0x7c, 0x2e, 0x9d, 0x5f, 0x8a, 0x13 } }; }
 		// `frames` interleaved sample frames; format: 1 = signed 16 bit, 4 = 32 bit float (wh_pcm_format of whisper_hip.h); channels 1 or 2, the same in every
-		// call. The chunk is queued as it is; runCapture takes one queued chunk per read. While more than maxDuration + 1 s is queued: with eCaptureFlags::NoDrop
+		// call. The chunk is queued as it is, a write of more than a second in pieces of a second; runCapture takes one queued chunk per read. While more than maxDuration + 1 s is queued: with eCaptureFlags::NoDrop
 		// the call blocks until the loop has caught up, otherwise the OLDEST queued chunk is dropped and counted (droppedChunks). A chunk dropped here never
 		// reaches the loop and is not part of the stream's sample clock: the times behind it are early by its length. E_INVALIDARG for another
 		// format or channel count, E_UNEXPECTED after close.
@@ -557,8 +558,14 @@ namespace Whisper
 	// Extension: live transcription. iContext::runCapture runs the reference's capture loop (Whisper/Whisper/ContextImpl.capture.cpp; DESIGN.md section 7 "Live
 	// capture") over an iPcmCapture: every piece the loop fires is a runFull on a worker thread of the library, with the buffer's media time set to the piece's
 	// first sample, so segment times are stream times and the context's decoding options apply to every piece. OS capture devices (listCaptureDevices,
-	// openCaptureDevice) stay E_NOTIMPL; input at other rates than 16 kHz is out of scope.
+	// openCaptureDevice) stay E_NOTIMPL.
+	// createPcmCaptureAtRate: what is written has `sampleRate` frames per second, 1000 .. 384000 or E_INVALIDARG; createPcmCapture means 16000. At another rate
+	// than 16000 every chunk is resampled to 16 kHz on the device by the launch that looks for voice in it, with the resampler of the file path made resumable:
+	// the 16 kHz samples the loop sees are, bit for bit, those the file path gives for the whole stream at once, whatever the chunk sizes. The durations of
+	// sCaptureParams, the pieces' start samples and the segment times are those of the 16 kHz stream. The filter looks ahead half + 1 input frames (2.1 to 2.2 ms
+	// from 22.05 kHz up, 4.4 ms at 8 kHz): a sample reaches the loop that much later. Reads discarded while the loop is stalled count as silence for the filter.
 	WHISPER_EXPORT HRESULT createPcmCapture( const sCaptureParams& params, iPcmCapture** pp );
+	WHISPER_EXPORT HRESULT createPcmCaptureAtRate( const sCaptureParams& params, uint32_t sampleRate, iPcmCapture** pp );
 	WHISPER_EXPORT HRESULT initMediaFoundation( iMediaFoundation** pp );
 	WHISPER_EXPORT uint32_t findLanguageKeyW( const wchar_t* lang );
 	WHISPER_EXPORT uint32_t findLanguageKeyA( const char* lang );

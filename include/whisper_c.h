@@ -46,7 +46,7 @@ int32_t whisperc_run_streamed( void* ctx, const void* wavBytes, uint64_t wavSize
  * *nOut = ceil( nFrames * 16000 / rate ); dst == NULL only counts, cap (floats of dst) < *nOut is E_INVALIDARG. rate 16000 converts without filtering. */
 int32_t whisperc_resample( const void* src, int32_t format, int32_t channels, int32_t channel, int32_t rate, int64_t nFrames, float* dst, int64_t cap,
 	int64_t* nOut );
-/* Live transcription (Whisper::createPcmCapture, iPcmCapture, iContext::runCapture of whisperApi.h): a capture is a queue of 16 kHz PCM chunks that the caller
+/* Live transcription (Whisper::createPcmCapture, iPcmCapture, iContext::runCapture of whisperApi.h): a capture is a queue of PCM chunks -- at 16 kHz, or at sampleRate with whisperc_capture_create_rate -- that the caller
  * writes from any thread -- format 1 = s16, 4 = float32; 1 or 2 interleaved channels, the same in every call -- and whisperc_run_capture drains on another:
  * the reference's capture loop (voice activity per chunk on the GPU; a piece is fired at a pause once minDuration is buffered, or at maxDuration) with every
  * piece transcribed by iContext::runFull on a worker thread, segment times being stream times. Durations in seconds (the reference's defaults are 2, 3, 0.25,
@@ -59,6 +59,10 @@ int32_t whisperc_resample( const void* src, int32_t format, int32_t channels, in
  * pfnPiece( pv, startSample, nSamples ) is called behind each piece's transcription, on the library's worker thread, while whisperc_result_* answer for
  * that piece. Each may be NULL. E_POINTER for a NULL capture, E_INVALIDARG for minDuration or maxDuration outside [0.125, 30]. */
 int32_t whisperc_capture_create( float minDuration, float maxDuration, float dropStartSilence, float pauseDuration, uint32_t flags, void** captureOut );
+/* Whisper::createPcmCaptureAtRate: what is written has sampleRate frames per second, 1000 .. 384000 or E_INVALIDARG, and is resampled to 16 kHz on the device chunk
+ * by chunk; durations, start samples and times stay those of the 16 kHz stream. 16000 is whisperc_capture_create. */
+int32_t whisperc_capture_create_rate( float minDuration, float maxDuration, float dropStartSilence, float pauseDuration, uint32_t flags, uint32_t sampleRate,
+	void** captureOut );
 int32_t whisperc_capture_write( void* capture, const void* samples, int32_t format, int32_t channels, uint32_t frames );
 int32_t whisperc_capture_close( void* capture );
 /* chunks dropped by whisperc_capture_write because the loop did not keep up (never under NoDrop) */

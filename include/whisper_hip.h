@@ -266,7 +266,7 @@ WH_API int wh_vad_features( void* stream, const float* pcmDev, int64_t nSamples,
 WH_API int wh_vad_features_host( const float* pcm, int64_t nSamples, float* feat );
 
 /* A live PCM stream, chunk by chunk: the buffer of the capture loop of iContext::runCapture (Whisper/Whisper/ContextImpl.capture.cpp: readSample appends
- * the converted samples, detectVoice looks at the whole buffer). A wh_capture is made for 1 or 2 input channels at 16 kHz and owns, each for capSamples
+ * the converted samples, detectVoice looks at the whole buffer). A wh_capture is made for 1 or 2 input channels at 16 kHz (another rate: below) and owns, each for capSamples
  * samples: a device buffer of mono FP32, with keepStereo one of interleaved stereo FP32, and a pinned host mirror of both -- twice, see wh_capture_take.
  * It has a stream of its own (the context only names the device), so an append never waits for a transcription that runs on a context's stream.
  * A context that never captures allocates and launches nothing of this.
@@ -284,9 +284,31 @@ WH_API int wh_vad_features_host( const float* pcm, int64_t nSamples, float* feat
  * wh_capture_clear empties the buffer: position 0, no partial frame. wh_capture_take hands out the host mirror of what is buffered (stereoHost receives NULL
  * when stereo is not kept; the argument itself may be NULL) and empties the buffer; the mirror is two buffers that swap, so what was handed out stays valid
  * until the take after the next (the reference's pcm.swap( buffer.pcm )): the piece under transcription is not overwritten while the next one fills.
- * One thread at a time per capture. */
+ * One thread at a time per capture.
+ *
+ * A stream at another rate: wh_capture_create_rate, inRate 1000 .. 384000 Hz (16000 gives exactly the object wh_capture_create gives). The chunk is resampled
+ * by the same launch with wh_resample's filter made resumable, and the contract is: the 16 kHz samples such a capture ever puts into its buffer are, in order,
+ * the samples wh_resample gives for the whole stream at once, bit for bit, whatever the chunk sizes. With L, M, half, K of wh_resample_taps( inRate ), the
+ * stream holds nIn (input frames accepted), nOut (outputs emitted or skipped), z (frames below it read as zero) and the last K - 1 frames of every filtered
+ * channel (the FP32 downmix; channels 0 and 1 as well when the stereo of a two-channel source is kept; a mono source whose stereo is kept gets its one
+ * filtered channel twice):
+ *   - wh_capture_append: `frames` are INPUT frames. nIn += frames; the outputs [nOut, max( nOut, ready )), ready = max( 0, ceil( ( nIn - half - 1 ) L / M ) ),
+ *     are appended at n -- those whose last tap lies inside what has arrived, so the look-ahead is half + 1 input frames (2.1 to 2.2 ms from 22.05 kHz up,
+ *     3.2 ms at 11.025 kHz, 4.4 ms at 8 kHz). A small chunk may append nothing; the caller learns what was appended from wh_capture_size. featHost must hold
+ *     the frames that ceil( frames L / M ) + 1 outputs can complete.
+ *   - wh_capture_flush, at the end of the stream: the outputs [nOut, ceil( nIn L / M )) are appended with zeros behind the last frame; the total is then
+ *     wh_resample_out_len( inRate, nIn ). The same launch with half + 1 frames of zeros for a chunk; no launch when nothing is left. Afterwards append, flush
+ *     and skip answer WH_E_NOT_READY.
+ *   - wh_capture_skip: `frames` input frames that the caller discarded (a stalled capture loop) are counted without an upload or a launch: nIn += frames,
+ *     nOut = max( nOut, ceil( nIn L / M ) ), z = nIn; *nSkippedOutputs is by how much nOut grew. What is appended afterwards are the samples of wh_resample
+ *     over the stream with frames [0, z) set to zero, from output ceil( z L / M ) on.
+ *   - wh_capture_clear and wh_capture_take reset the buffer position only: nIn, nOut, z and the history belong to the stream and go on.
+ * On a 16 kHz capture flush appends nothing and skip answers `frames`. */
 typedef struct wh_capture wh_capture;
 WH_API int wh_capture_create( wh_context* c, int channels, int keepStereo, int64_t capSamples, wh_capture** out );
+WH_API int wh_capture_create_rate( wh_context* c, int channels, int keepStereo, int64_t capSamples, int inRate, wh_capture** out );
+WH_API int wh_capture_flush( wh_capture* cap, float* featHost, int64_t featCap, int64_t* nNewFrames );
+WH_API int wh_capture_skip( wh_capture* cap, int64_t frames, int64_t* nSkippedOutputs );
 WH_API int wh_capture_append( wh_capture* cap, const void* src, int format, int64_t frames, float* featHost, int64_t featCap, int64_t* nNewFrames );
 WH_API int wh_capture_clear( wh_capture* cap );
 WH_API int wh_capture_take( wh_capture* cap, const float** monoHost, const float** stereoHost, int64_t* nSamples );
@@ -845,6 +867,15 @@ WH_API int wh_op_dtw( void* stream, const float* xDev, int windows, int rowMax, 
  * or channel count, negative sizes, a null or misaligned pointer with frames > 0: nothing is launched. frames == 0 launches nothing and succeeds. */
 WH_API int wh_op_capture_append( void* stream, const void* srcDev, int format, int channels, int64_t n, int64_t frames, int64_t capSamples, float* monoDev,
 	float* stereoDev, float* featDev );
+/* The kernel of wh_capture_append / wh_capture_flush on a stream at another rate, with every piece of the stream's state an argument: nIn input frames were
+ * accepted before this chunk, frames below z read as zero (z moves only by a skip, so the outputs emitted so far are max( ready( nIn ), ceil( z L / M ) )), and
+ * histReadDev holds stream frames [nIn - ( K - 1 ), nIn) of every filtered channel, [nf][K - 1] floats, nf = 3 for two channels with stereoDev, else 1 (frames
+ * below max( 0, z ) are never read). Appends the outputs that become ready to monoDev / stereoDev at buffer position n, writes the features of the 256-sample
+ * frames they complete to featDev and the history for nIn + frames to histWriteDev (another buffer than histReadDev); *nOutputs receives their number. flush != 0:
+ * the end of the stream, frames == 0, srcDev and histWriteDev are not used. WH_E_BOUNDS when the outputs do not fit capSamples, WH_E_INVALIDARG for a rate outside
+ * 1000 .. 384000 or 16000 itself, another format or channel count, negative sizes, z > nIn, a null or misaligned pointer: nothing is launched. */
+WH_API int wh_op_capture_append_rate( void* stream, const void* srcDev, int format, int channels, int inRate, int64_t frames, int64_t nIn, int64_t z, int flush,
+	const float* histReadDev, float* histWriteDev, int64_t n, int64_t capSamples, float* monoDev, float* stereoDev, float* featDev, int64_t* nOutputs );
 
 #ifdef __cplusplus
 }

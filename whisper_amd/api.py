@@ -106,6 +106,7 @@ def lib():
         L.whisperc_plan_chunks.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, vp, vp, C.c_int32, C.POINTER(C.c_int32)]
         L.whisperc_debug_vad_decide.argtypes = [vp, C.c_int64, vp, C.POINTER(C.c_int64)]
         L.whisperc_capture_create.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32, C.POINTER(vp)]
+        L.whisperc_capture_create_rate.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(vp)]
         L.whisperc_capture_write.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_uint32]
         L.whisperc_capture_close.argtypes = [vp]
         L.whisperc_capture_dropped.argtypes = [vp]
@@ -268,17 +269,20 @@ _CAPTURE_PIECE_T = C.CFUNCTYPE(None, C.c_void_p, C.c_int64, C.c_int64)
 
 
 class Capture:
-    """iPcmCapture: a stream of 16 kHz PCM that the caller writes, from any thread, while Context.run_capture transcribes it on another. Durations in seconds
+    """iPcmCapture: a stream of PCM at sample_rate (1000 .. 384000 Hz; other rates than 16000 are resampled on the device chunk by chunk, with the file path's
+    filter, and durations, start samples and times stay those of the 16 kHz stream) that the caller writes, from any thread, while Context.run_capture transcribes it on another. Durations in seconds
     (the reference's sCaptureParams). stereo: keep the two channels, so that Context.speakers() answers for every piece. no_drop: never discard samples when
     transcription falls behind -- the loop waits for the running piece, and write() blocks while more than max_duration + 1 s is queued and a loop is
     draining: for a source that is not real time."""
 
     def __init__(self, min_duration: float = 2.0, max_duration: float = 3.0, drop_start_silence: float = 0.25, pause_duration: float = 0.333,
-                 stereo: bool = False, no_drop: bool = False):
+                 stereo: bool = False, no_drop: bool = False, sample_rate: int = 16000):
         self.h = C.c_void_p()
-        self.stereo, self.no_drop = stereo, no_drop
-        _check(lib().whisperc_capture_create(min_duration, max_duration, drop_start_silence, pause_duration,
-                                             (CAPTURE_STEREO if stereo else 0) | (CAPTURE_NO_DROP if no_drop else 0), C.byref(self.h)), "createPcmCapture")
+        self.stereo, self.no_drop, self.sample_rate = stereo, no_drop, sample_rate
+        if not 0 <= sample_rate < 2 ** 32:
+            raise WhisperError(0x80070057, "createPcmCaptureAtRate")
+        _check(lib().whisperc_capture_create_rate(min_duration, max_duration, drop_start_silence, pause_duration,
+                                                  (CAPTURE_STEREO if stereo else 0) | (CAPTURE_NO_DROP if no_drop else 0), sample_rate, C.byref(self.h)), "createPcmCaptureAtRate")
 
     def write(self, samples: np.ndarray):
         """int16 or float32, [n] (mono) or [n, 2] (interleaved stereo); the dtype and the channel count of a capture do not change"""
@@ -541,7 +545,7 @@ class Context:
         piece's; on_status(word) whenever a bit of LISTENING | VOICE | TRANSCRIBING | STALLED changes: on the calling thread, but for the fall of TRANSCRIBING
         of a capture without no_drop, which comes from the worker thread when the piece's job ends.
         language, flags, max_tokens, prompt, n_max_text_ctx, beam_width and audio_ctx are run_full's and hold for every piece. The other keywords of run_full
-        belong elsewhere: stereo is the capture's, another sample_rate is out of scope, and a piece has no offset or duration of its own."""
+        belong elsewhere: stereo and sample_rate are the capture's, and a piece has no offset or duration of its own."""
         pt = np.ascontiguousarray(prompt if prompt is not None else [], np.int32)
         pieces = []
         errors = []

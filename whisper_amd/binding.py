@@ -53,6 +53,7 @@ EXPORTS = [
     "wh_resample_out_len", "wh_resample", "wh_resample_host", "wh_resample_host_multi", "wh_resample_taps",
     "wh_vad_frame_count", "wh_vad_features", "wh_vad_features_host",
     "wh_capture_create", "wh_capture_append", "wh_capture_clear", "wh_capture_take", "wh_capture_size", "wh_capture_destroy", "wh_op_capture_append",
+    "wh_capture_create_rate", "wh_capture_flush", "wh_capture_skip", "wh_op_capture_append_rate",
     "wh_dequantize",
     "wh_model_set_alignment_heads", "wh_align_tokens", "wh_op_align_matrix", "wh_op_dtw",
     "wh_op_vocab_soft_max_scaled", "wh_op_sample_draw", "wh_op_philox_u", "wh_context_set_sampling", "wh_context_set_no_speech", "wh_decode_window_no_speech",
@@ -260,6 +261,10 @@ def lib():
         L.wh_capture_size.argtypes = [vp, C.POINTER(i64)]
         L.wh_capture_destroy.argtypes = [vp]
         L.wh_op_capture_append.argtypes = [vp, vp, i32, i32, i64, i64, i64, vp, vp, vp]
+        L.wh_capture_create_rate.argtypes = [vp, i32, i32, i64, i32, C.POINTER(vp)]
+        L.wh_capture_flush.argtypes = [vp, vp, i64, C.POINTER(i64)]
+        L.wh_capture_skip.argtypes = [vp, i64, C.POINTER(i64)]
+        L.wh_op_capture_append_rate.argtypes = [vp, vp, i32, i32, i32, i64, i64, i64, i32, vp, vp, i64, i64, vp, vp, vp, C.POINTER(i64)]
         L.wh_dequantize.argtypes = [vp, i32, vp, i64, vp]
         L.wh_model_set_alignment_heads.argtypes = [vp, vp, i32]
         L.wh_align_tokens.argtypes = [vp, i32, vp, vp, vp, i32, vp]

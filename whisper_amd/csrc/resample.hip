@@ -14,19 +14,15 @@
 // all L phases go through LDS as well, K in chunks of kc (a lane reading its own phase's row from global memory touches 64 cache lines per wave
 // instruction); tables of more phases than the option resample_lds_phases (rates that share no large factor with 16000) are read from global memory directly.
 // LDS is at most 64 KiB per workgroup, so two or more fit a CU at every rate.
+// What the kernel shares with the per-chunk kernel of a live stream (capture.hip) -- the design, the block shape, the conversion of a frame and the per-output
+// sum -- is stated in resample_device.h; the tap tables live here.
 #include "runtime.h"
+#include "resample_device.h"
 
 namespace wh
 {
 	namespace
 	{
-		constexpr int RS_THREADS = 256, RS_PER_THREAD = 4, RS_BLOCK_MAX = RS_THREADS * RS_PER_THREAD;
-		constexpr int RS_X_CAP = 8192;	  // floats of staged input per workgroup
-		constexpr int RS_T_CAP = 7680;	  // floats of staged taps per workgroup: 62 KiB with the input, under the 64 KiB a launch gets without asking
-		constexpr int RS_MIN_RATE = 1000, RS_MAX_RATE = 384000, RS_OUT_RATE = 16000, RS_MAX_CHANNELS = 8;
-		constexpr int RS_ZEROS = 32;
-		constexpr double RS_ROLLOFF = 0.9475937167399596, RS_BETA = 14.769656459379492;
-
 		struct ResampleArgs
 		{
 			const void* src;
@@ -39,34 +35,6 @@ namespace wh
 			int xCap;	   // floats of LDS in front of the taps
 			int kc, kcp;   // taps per staged chunk and the row pitch of the staged chunk (odd: the phases of neighbouring lanes fall into different banks)
 		};
-
-		__device__ __forceinline__ float loadSample( const uint8_t* p, int format )
-		{
-			switch( format )
-			{
-			case WH_PCM_U8: return (float)( (int)*p - 128 ) / 128.0f;
-			case WH_PCM_S16: return (float)*(const int16_t*)p / 32768.0f;
-			case WH_PCM_S24:
-			{
-				const int v = (int)( ( (unsigned)p[ 0 ] | ( (unsigned)p[ 1 ] << 8 ) | ( (unsigned)p[ 2 ] << 16 ) ) << 8 ) >> 8;
-				return (float)v / 8388608.0f;
-			}
-			case WH_PCM_S32: return (float)( (double)*(const int32_t*)p * ( 1.0 / 2147483648.0 ) );
-			default: return *(const float*)p;
-			}
-		}
-		__device__ __forceinline__ int sampleBytes( int format ) { return format == WH_PCM_U8 ? 1 : format == WH_PCM_S16 ? 2 : format == WH_PCM_S24 ? 3 : 4; }
-
-		// one frame as a mono float: channel >= 0 that channel, -1 the mean -- the FP32 sum in channel order times 1.0f / C (two channels: the bits of 0.5f * ( l + r ))
-		__device__ __forceinline__ float loadFrame( const void* src, long long frame, int format, int channels, int channel )
-		{
-			const int bytes = sampleBytes( format );
-			const uint8_t* p = (const uint8_t*)src + ( frame * channels + ( channel < 0 ? 0 : channel ) ) * bytes;
-			if( channel >= 0 ) return loadSample( p, format );
-			float s = loadSample( p, format );
-			for( int c = 1; c < channels; c++ ) s = __fadd_rn( s, loadSample( p + c * bytes, format ) );
-			return __fmul_rn( s, 1.0f / (float)channels );
-		}
 
 		template<bool TAPS_LDS>
 		__global__ void __launch_bounds__( RS_THREADS ) resampleKernel( const ResampleArgs a )
@@ -107,39 +75,7 @@ namespace wh
 			}
 			__syncthreads();
 
-			if( TAPS_LDS )
-			{
-				for( int k0 = 0; k0 < a.K; k0 += a.kc )
-				{
-					const int kn = a.K - k0 < a.kc ? a.K - k0 : a.kc;
-					for( int r = tid / 32; r < a.L; r += RS_THREADS / 32 )
-						for( int kk = tid & 31; kk < kn; kk += 32 ) ts[ r * a.kcp + kk ] = a.taps[ (long long)r * a.K + k0 + kk ];
-					__syncthreads();
-					const float *t0 = ts + ph[ 0 ] * a.kcp, *t1 = ts + ph[ 1 ] * a.kcp, *t2 = ts + ph[ 2 ] * a.kcp, *t3 = ts + ph[ 3 ] * a.kcp;
-					const float *x0 = xs + off[ 0 ] + k0, *x1 = xs + off[ 1 ] + k0, *x2 = xs + off[ 2 ] + k0, *x3 = xs + off[ 3 ] + k0;
-					for( int kk = 0; kk < kn; kk++ )
-					{
-						acc[ 0 ] = fma( (double)t0[ kk ], (double)x0[ kk ], acc[ 0 ] );
-						acc[ 1 ] = fma( (double)t1[ kk ], (double)x1[ kk ], acc[ 1 ] );
-						acc[ 2 ] = fma( (double)t2[ kk ], (double)x2[ kk ], acc[ 2 ] );
-						acc[ 3 ] = fma( (double)t3[ kk ], (double)x3[ kk ], acc[ 3 ] );
-					}
-					__syncthreads();
-				}
-			}
-			else
-			{
-				const float *t0 = a.taps + (long long)ph[ 0 ] * a.K, *t1 = a.taps + (long long)ph[ 1 ] * a.K, *t2 = a.taps + (long long)ph[ 2 ] * a.K,
-							*t3 = a.taps + (long long)ph[ 3 ] * a.K;
-				const float *x0 = xs + off[ 0 ], *x1 = xs + off[ 1 ], *x2 = xs + off[ 2 ], *x3 = xs + off[ 3 ];
-				for( int k = 0; k < a.K; k++ )
-				{
-					acc[ 0 ] = fma( (double)t0[ k ], (double)x0[ k ], acc[ 0 ] );
-					acc[ 1 ] = fma( (double)t1[ k ], (double)x1[ k ], acc[ 1 ] );
-					acc[ 2 ] = fma( (double)t2[ k ], (double)x2[ k ], acc[ 2 ] );
-					acc[ 3 ] = fma( (double)t3[ k ], (double)x3[ k ], acc[ 3 ] );
-				}
-			}
+			resampleChains<TAPS_LDS>( xs, ts, a.taps, a.L, a.K, a.kc, a.kcp, off, ph, acc );
 #pragma unroll
 			for( int o = 0; o < RS_PER_THREAD; o++ )
 			{
@@ -157,19 +93,8 @@ namespace wh
 		}
 
 		// ---- the filter, on the host ----
-		struct Design { int L, M, half, K; };
-		int gcdInt( int a, int b ) { while( b ) { const int t = a % b; a = b; b = t; } return a; }
-		bool design( int inRate, Design& d )
-		{
-			if( inRate < RS_MIN_RATE || inRate > RS_MAX_RATE ) return false;
-			const int g = gcdInt( inRate, RS_OUT_RATE );
-			d.L = RS_OUT_RATE / g;
-			d.M = inRate / g;
-			const double w = RS_ROLLOFF * (double)( inRate < RS_OUT_RATE ? inRate : RS_OUT_RATE ) / (double)inRate;
-			d.half = (int)std::ceil( (double)RS_ZEROS / w );
-			d.K = 2 * d.half + 2;
-			return true;
-		}
+		using Design = ResampleDesign;
+		bool design( int inRate, Design& d ) { return resampleDesign( inRate, d ); }
 		// modified Bessel function of the first kind, order 0: the power series (all terms positive, x <= 15: ~40 terms to double precision)
 		double besselI0( double x )
 		{
@@ -204,38 +129,7 @@ namespace wh
 				}
 		}
 
-		// The tap tables: one per (device, rate), built on first use under the lock and kept for the life of the process like the op-level scratch of
-		// ops_debug.hip. A table is L * K floats: 119 KB at 44.1 kHz, 175 KB at 11.025 kHz, 104 MB at worst (a rate coprime to 16000: L = 16000).
-		struct TapTable { Design d; const float* dev; };
-		std::mutex g_tapMutex;
-		std::map<std::pair<int, int>, TapTable> g_tapTables;
-		std::vector<Allocation> g_tapAllocations;
-
-		int tapTable( int inRate, hipStream_t stream, TapTable& out )
-		{
-			int dev = 0;
-			WH_HIP( hipGetDevice( &dev ) );
-			std::lock_guard<std::mutex> lk( g_tapMutex );
-			const auto it = g_tapTables.find( { dev, inRate } );
-			if( it != g_tapTables.end() ) { out = it->second; return 0; }
-			TapTable t;
-			if( !design( inRate, t.d ) ) return WH_E_INVALIDARG;
-			std::vector<float> host( (size_t)t.d.L * t.d.K );
-			designTaps( inRate, t.d, host.data() );
-			Allocation a;
-			WH_HIP( guardedAlloc( a, (int64_t)host.size() * 4, -1, "resample taps", stream ) );
-			// synchronous: `host` dies with this call, and every stream may read the table afterwards
-			hipError_t e = hipMemcpyAsync( a.body, host.data(), host.size() * 4, hipMemcpyHostToDevice, stream );
-			if( e == hipSuccess ) e = hipStreamSynchronize( stream );
-			if( e != hipSuccess ) { (void)guardedFree( a ); return hipFail( e, "resample taps upload", __FILE__, __LINE__ ); }
-			g_tapAllocations.push_back( a );
-			t.dev = (const float*)a.body;
-			g_tapTables[ { dev, inRate } ] = t;
-			out = t;
-			return 0;
-		}
-
-		int64_t outLen( const Design& d, int64_t nFrames ) { return ( nFrames * d.L + d.M - 1 ) / d.M; }
+		int64_t outLen( const Design& d, int64_t nFrames ) { return resampleOutLen( d, nFrames ); }
 
 		bool validCall( const char* who, int format, int channels, int channel, int inRate, int64_t nFrames, int64_t dstStride, int64_t nOut, Design& d )
 		{
@@ -247,6 +141,39 @@ namespace wh
 			return true;
 		}
 	}	// namespace
+
+	// The tap tables: one per (device, rate), built on first use under the lock and kept for the life of the process like the op-level scratch of
+	// ops_debug.hip. A table is L * K floats: 119 KB at 44.1 kHz, 175 KB at 11.025 kHz, 104 MB at worst (a rate coprime to 16000: L = 16000).
+	namespace
+	{
+		std::mutex g_tapMutex;
+		std::map<std::pair<int, int>, ResampleTapTable> g_tapTables;
+		std::vector<Allocation> g_tapAllocations;
+	}
+
+	int resampleTapTable( int inRate, hipStream_t stream, ResampleTapTable& out )
+	{
+		int dev = 0;
+		WH_HIP( hipGetDevice( &dev ) );
+		std::lock_guard<std::mutex> lk( g_tapMutex );
+		const auto it = g_tapTables.find( { dev, inRate } );
+		if( it != g_tapTables.end() ) { out = it->second; return 0; }
+		ResampleTapTable t;
+		if( !design( inRate, t.d ) ) return WH_E_INVALIDARG;
+		std::vector<float> host( (size_t)t.d.L * t.d.K );
+		designTaps( inRate, t.d, host.data() );
+		Allocation a;
+		WH_HIP( guardedAlloc( a, (int64_t)host.size() * 4, -1, "resample taps", stream ) );
+		// synchronous: `host` dies with this call, and every stream may read the table afterwards
+		hipError_t e = hipMemcpyAsync( a.body, host.data(), host.size() * 4, hipMemcpyHostToDevice, stream );
+		if( e == hipSuccess ) e = hipStreamSynchronize( stream );
+		if( e != hipSuccess ) { (void)guardedFree( a ); return hipFail( e, "resample taps upload", __FILE__, __LINE__ ); }
+		g_tapAllocations.push_back( a );
+		t.dev = (const float*)a.body;
+		g_tapTables[ { dev, inRate } ] = t;
+		out = t;
+		return 0;
+	}
 
 	int launchResample( hipStream_t stream, const void* src, int format, int channels, int channel, int inRate, long long nFrames, float* dst,
 		long long dstStride, long long nOut )
@@ -260,31 +187,20 @@ namespace wh
 			WH_HIP( hipGetLastError() );
 			return 0;
 		}
-		TapTable t;
-		WH_CHECK( tapTable( inRate, stream, t ) );
+		ResampleTapTable t;
+		WH_CHECK( resampleTapTable( inRate, stream, t ) );
 		const Design& d = t.d;
+		ResampleShape sh;
+		if( !resampleShape( d, sh ) ) { setError( "resample: internal error (block span)" ); return WH_E_BOUNDS; }
 		ResampleArgs a;
 		a.src = src; a.dst = dst; a.taps = t.dev;
 		a.nFrames = nFrames; a.nOut = nOut; a.dstStride = dstStride;
 		a.format = format; a.channels = channels; a.channel = channel;
 		a.L = d.L; a.M = d.M; a.half = d.half; a.K = d.K;
-		// the span of `block` outputs is at most ceil( ( block - 1 ) M / L ) + K frames: the largest multiple of 64 that fits RS_X_CAP (K <= 1624, M / L <= 24: 64 always fit)
-		long long block = ( (long long)( RS_X_CAP - d.K - 1 ) * d.L / d.M + 1 ) / 64 * 64;
-		block = block > RS_BLOCK_MAX ? RS_BLOCK_MAX : ( block < 64 ? 64 : block );
-		a.block = (int)block;
-		a.xCap = (int)( ( ( block - 1 ) * d.M + d.L - 1 ) / d.L ) + d.K;
-		if( a.xCap > RS_X_CAP ) { setError( "resample: internal error (block span)" ); return WH_E_BOUNDS; }
-		a.xCap = ( a.xCap + 3 ) & ~3;
-		// taps through LDS when a chunk of at least 8 taps of every phase fits
-		const int maxRow = ( ( RS_T_CAP / d.L ) - 1 ) | 1;
-		const bool tapsLds = RS_T_CAP / d.L >= 9 && d.L <= g_opt.resampleLdsPhases;
-		a.kc = a.kcp = 0;
-		if( tapsLds )
-		{
-			a.kc = d.K < maxRow ? d.K : maxRow;
-			a.kcp = a.kc | 1;
-		}
-		const size_t lds = ( (size_t)a.xCap + ( tapsLds ? (size_t)d.L * a.kcp : 0 ) ) * sizeof( float );
+		a.block = sh.block; a.xCap = sh.xCap; a.kc = sh.kc; a.kcp = sh.kcp;
+		const long long block = sh.block;
+		const bool tapsLds = sh.tapsLds;
+		const size_t lds = sh.ldsBytes;
 		const long long blocks = ( nOut + block - 1 ) / block;
 		if( blocks > 0x7fffffffll ) { setError( "resample: too many outputs for one launch" ); return WH_E_INVALIDARG; }
 		if( tapsLds ) hipLaunchKernelGGL( resampleKernel<true>, dim3( (unsigned)blocks ), dim3( RS_THREADS ), lds, stream, a );

@@ -2,8 +2,14 @@
 // (Whisper/Whisper/ContextImpl.capture.cpp) --; this unit supplies what the loop leaves open: the source (a queue of chunks the caller writes from any
 // thread), the buffer (wh_capture of whisper_hip.h: one launch per chunk converts it and gives the voice-activity features of the frames it completes), and
 // the job (iContext::runFull of the piece's host mirror on a worker thread, media time = the piece's first sample).
+//
+// A capture at another rate than 16 kHz (createPcmCaptureAtRate) is resampled by the buffer, chunk by chunk: what a read appends is then not the chunk's frame
+// count but the 16 kHz samples the device reports, possibly none (the filter looks half + 1 input frames ahead); a discarded read moves the stream's output
+// clock (skip) without an upload; and the end of the stream is one last read, the flush. The loop counts 16 kHz samples as before, so a piece's start is an
+// index into the whole stream's resampled output. The three device entries this needs are reached through captureRate.h's table.
 #include "hostCommon.h"
 #include "captureLoop.h"
+#include "captureRate.h"
 #include <algorithm>
 #include <condition_variable>
 #include <deque>
@@ -14,9 +20,11 @@ namespace Whisper
 {
 	namespace
 	{
-		// a queued chunk is at most a second: the capture buffer is sized 30 s plus one chunk
+		// a queued chunk is at most a second of input: the capture buffer is sized 30 s plus one chunk
 		constexpr uint32_t MAX_CHUNK_FRAMES = 16000;
 		constexpr int64_t CAP_SAMPLES = 30 * captureLoop::SAMPLE_RATE + MAX_CHUNK_FRAMES;
+		// at another rate a second of input is 16000 outputs or one more, and the flush adds the look-ahead's (at most 35 * 16 + 1)
+		constexpr int64_t CAP_SAMPLES_RATE = CAP_SAMPLES + 1024;
 
 		struct Chunk
 		{
@@ -34,13 +42,16 @@ namespace Whisper
 			virtual void detach() = 0;
 			// waits for the next chunk; false: the stream was closed and the queue is empty
 			virtual bool pop( Chunk& c, int& format, int& channels ) = 0;
+			// frames per second of what is written
+			virtual uint32_t sampleRate() const = 0;
 		};
 
 		class PcmCapture : public iPcmCapture, public iPcmQueue
 		{
 			std::atomic<uint32_t> rc{ 1 };
 			const sCaptureParams params;
-			const int64_t limitFrames;	   // maxDuration + 1 s
+			const uint32_t rate;
+			const int64_t limitFrames;	   // maxDuration + 1 s, in input frames
 			mutable std::mutex mx;
 			std::condition_variable cvData, cvSpace;
 			std::deque<Chunk> queue;
@@ -49,11 +60,15 @@ namespace Whisper
 			int format = -1, channels = 0;
 			bool closed = false, attached = false;
 
-		public:
-			PcmCapture( const sCaptureParams& p )
-				: params( p ), limitFrames( (int64_t)captureLoop::samplesFromSeconds( p.maxDuration > 0 && p.maxDuration <= 30.0f ? p.maxDuration : 30.0f ) + captureLoop::SAMPLE_RATE )
+			static int64_t limitOf( const sCaptureParams& p, uint32_t rate )
 			{
+				const float seconds = p.maxDuration > 0 && p.maxDuration <= 30.0f ? p.maxDuration : 30.0f;
+				if( rate == captureLoop::SAMPLE_RATE ) return (int64_t)captureLoop::samplesFromSeconds( seconds ) + captureLoop::SAMPLE_RATE;
+				return (int64_t)( (double)seconds * (double)rate + 0.5 ) + (int64_t)rate;
 			}
+
+		public:
+			PcmCapture( const sCaptureParams& p, uint32_t sampleRate ) : params( p ), rate( sampleRate ), limitFrames( limitOf( p, sampleRate ) ) {}
 			virtual ~PcmCapture() = default;
 			HRESULT QueryInterface( const ComLight::GUID& riid, void** ppv ) override
 			{
@@ -88,7 +103,7 @@ namespace Whisper
 				const bool noDrop = 0 != ( params.flags & (uint32_t)eCaptureFlags::NoDrop );
 				for( uint32_t done = 0; done < frames; )
 				{
-					const uint32_t n = std::min( frames - done, MAX_CHUNK_FRAMES );
+					const uint32_t n = std::min( frames - done, rate );	   // MAX_CHUNK_FRAMES at 16 kHz
 					if( noDrop )
 					{
 						// with no loop attached nobody would ever make room: the queue grows
@@ -153,6 +168,7 @@ namespace Whisper
 				cvSpace.notify_all();
 				return true;
 			}
+			uint32_t sampleRate() const override { return rate; }
 		};
 
 		// TranscribeBuffer (ContextImpl.capture.cpp:15-42) over the host mirror wh_capture_take handed out; lives on runCapture's stack
@@ -186,11 +202,14 @@ namespace Whisper
 			const sCaptureCallbacks& callbacks;
 			iPcmQueue* const source;
 			const bool keepStereo;
+			const uint32_t rate;
+			const CaptureRateTable* const table;	// non-null when rate is not 16000
 			pfnCapturePiece const pfnPiece;
 			void* const pvPiece;
 
 			wh_capture* cap = nullptr;
 			captureLoop::Loop* loop = nullptr;	   // told when a job ends (workerEnded)
+			bool ended = false;					   // at another rate: the end of the stream was answered with the flush
 			std::vector<float> feat;
 			captureLoop::DetectorStep detector;
 			PieceBuffer buffer;
@@ -198,8 +217,8 @@ namespace Whisper
 			std::atomic<bool> jobDone{ true };
 			HRESULT jobResult = S_OK;
 
-			Session( iContext* c, wh_context* g, const sFullParams& fp, const sCaptureCallbacks& cb, iPcmQueue* q, bool st, pfnCapturePiece pfn, void* pv )
-				: context( c ), gpu( g ), fullParams( fp ), callbacks( cb ), source( q ), keepStereo( st ), pfnPiece( pfn ), pvPiece( pv )
+			Session( iContext* c, wh_context* g, const sFullParams& fp, const sCaptureCallbacks& cb, iPcmQueue* q, bool st, const CaptureRateTable* t, pfnCapturePiece pfn, void* pv )
+				: context( c ), gpu( g ), fullParams( fp ), callbacks( cb ), source( q ), keepStereo( st ), rate( q->sampleRate() ), table( t ), pfnPiece( pfn ), pvPiece( pv )
 			{
 			}
 			~Session()
@@ -208,8 +227,10 @@ namespace Whisper
 				if( cap ) wh_capture_destroy( cap );
 			}
 
+			// frames: the 16 kHz samples the read appended to the buffer or, when discarded, moved the stream's clock by
 			HRESULT read( bool discard, uint32_t& frames, const float*& features, int64_t& newFrames )
 			{
+				if( rate != captureLoop::SAMPLE_RATE ) return readAtRate( discard, frames, features, newFrames );
 				Chunk c;
 				int format = 0, channels = 0;
 				frames = 0;
@@ -222,6 +243,52 @@ namespace Whisper
 				if( !cap ) CHECK_WH( wh_capture_create( gpu, channels, keepStereo ? 1 : 0, CAP_SAMPLES, &cap ) );
 				feat.resize( (size_t)( c.frames / vad::FRAME_SAMPLES + 1 ) * 3 );
 				CHECK_WH( wh_capture_append( cap, c.bytes.data(), format, c.frames, feat.data(), (int64_t)feat.size() / 3, &newFrames ) );
+				features = feat.data();
+				return S_OK;
+			}
+			HRESULT readAtRate( bool discard, uint32_t& frames, const float*& features, int64_t& newFrames )
+			{
+				Chunk c;
+				int format = 0, channels = 0;
+				frames = 0;
+				features = nullptr;
+				newFrames = 0;
+				if( ended ) return S_FALSE;
+				int64_t before = 0, after = 0, grown = 0;
+				if( !source->pop( c, format, channels ) )
+				{
+					// the end of the stream is one last read: the outputs whose taps reach past the last frame. S_FALSE to the read after it.
+					ended = true;
+					if( !cap ) return S_FALSE;
+					if( discard )
+					{
+						CHECK_WH( table->skip( cap, 0, &grown ) );
+						frames = (uint32_t)grown;
+						return S_OK;
+					}
+					feat.resize( 8 * 3 );
+					CHECK_WH( wh_capture_size( cap, &before ) );
+					CHECK_WH( table->flush( cap, feat.data(), (int64_t)feat.size() / 3, &newFrames ) );
+					CHECK_WH( wh_capture_size( cap, &after ) );
+					frames = (uint32_t)( after - before );
+					features = feat.data();
+					return S_OK;
+				}
+				if( !cap ) CHECK_WH( table->createRate( gpu, channels, keepStereo ? 1 : 0, CAP_SAMPLES_RATE, (int)rate, &cap ) );
+				if( discard )
+				{
+					// nothing is uploaded: the stream counts the frames, and what follows is filtered as if they had been zeros
+					CHECK_WH( table->skip( cap, c.frames, &grown ) );
+					frames = (uint32_t)grown;
+					return S_OK;
+				}
+				// the chunk makes at most ceil( frames 16000 / rate ) + 1 outputs ready
+				const int64_t mostOutputs = ( (int64_t)c.frames * captureLoop::SAMPLE_RATE + rate - 1 ) / rate + 1;
+				feat.resize( (size_t)( mostOutputs / vad::FRAME_SAMPLES + 1 ) * 3 );
+				CHECK_WH( wh_capture_size( cap, &before ) );
+				CHECK_WH( wh_capture_append( cap, c.bytes.data(), format, c.frames, feat.data(), (int64_t)feat.size() / 3, &newFrames ) );
+				CHECK_WH( wh_capture_size( cap, &after ) );
+				frames = (uint32_t)( after - before );
 				features = feat.data();
 				return S_OK;
 			}
@@ -257,11 +324,23 @@ namespace Whisper
 		};
 	}
 
-	HRESULT createPcmCapture( const sCaptureParams& params, iPcmCapture** pp )
+	const CaptureRateTable* g_captureRateTable = nullptr;
+
+	HRESULT createPcmCaptureAtRate( const sCaptureParams& params, uint32_t sampleRate, iPcmCapture** pp )
 	{
 		if( !pp ) return E_POINTER;
-		*pp = new PcmCapture( params );
+		*pp = nullptr;
+		if( sampleRate < CAPTURE_MIN_RATE || sampleRate > CAPTURE_MAX_RATE )
+		{
+			logError( "createPcmCaptureAtRate: the sample rate must be 1000 .. 384000 Hz" );
+			return E_INVALIDARG;
+		}
+		*pp = new PcmCapture( params, sampleRate );
 		return S_OK;
+	}
+	HRESULT createPcmCapture( const sCaptureParams& params, iPcmCapture** pp )
+	{
+		return createPcmCaptureAtRate( params, (uint32_t)captureLoop::SAMPLE_RATE, pp );
 	}
 
 	HRESULT runCaptureLoop( iContext* context, wh_context* gpu, const sFullParams& params, const sCaptureCallbacks& callbacks, const iAudioCapture* reader,
@@ -290,10 +369,16 @@ namespace Whisper
 			logError( "%s parameter %g is out of range", which, which[ 1 ] == 'i' ? cp.minDuration : cp.maxDuration );
 			return E_INVALIDARG;
 		}
+		const CaptureRateTable* const table = g_captureRateTable;
+		if( source->sampleRate() != captureLoop::SAMPLE_RATE && !table )
+		{
+			logError( "runCapture: a capture at a sample rate of %u Hz needs the device resampler, which this build of the library does not install", source->sampleRate() );
+			return E_NOTIMPL;
+		}
 		CHECK( source->attach() );
 		guard.attached = true;
 
-		Session s( context, gpu, params, callbacks, source, 0 != ( cp.flags & (uint32_t)eCaptureFlags::Stereo ), pfnPiece, pvPiece );
+		Session s( context, gpu, params, callbacks, source, 0 != ( cp.flags & (uint32_t)eCaptureFlags::Stereo ), table, pfnPiece, pvPiece );
 		captureLoop::Hooks h;
 		if( callbacks.shouldCancel ) h.shouldCancel = [ & ]() { return callbacks.shouldCancel( callbacks.pv ); };
 		if( callbacks.captureStatus ) h.status = [ & ]( uint8_t word ) { return callbacks.captureStatus( callbacks.pv, (eCaptureStatus)word ); };

@@ -408,11 +408,13 @@ static int scoreInput( iModel* model, iContext* context, iMediaFoundation* media
 	return 0;
 }
 
-// --capture: live transcription of raw 16 kHz PCM from a file or a pipe (Whisper::createPcmCapture + iContext::runCapture)
+// --capture: live transcription of raw PCM, at 16 kHz or at --capture-rate, from a file or a pipe (Whisper::createPcmCaptureAtRate + iContext::runCapture)
 struct CaptureOptions
 {
 	std::string path;	 // "-" = standard input
 	int format = 1, channels = 1;	 // wh_pcm_format: 1 = s16, 4 = f32
+	uint32_t rate = 16000;
+	bool rateGiven = false;
 	sCaptureParams params;
 };
 
@@ -423,13 +425,13 @@ static int runCaptureInput( iContext* context, const sFullParams& p, const Captu
 	FILE* in = co.path == "-" ? stdin : fopen( co.path.c_str(), "rb" );
 	if( !in ) { fprintf( stderr, "error: cannot read '%s'\n", co.path.c_str() ); return 10; }
 	ComLight::CComPtr<iPcmCapture> capture;
-	HRESULT hr = createPcmCapture( co.params, &capture );
+	HRESULT hr = createPcmCaptureAtRate( co.params, co.rate, &capture );
 	if( FAILED( hr ) ) { printFailure( "failed to create the capture", hr ); return 7; }
 	iPcmCapture* const cap = capture;
 	std::atomic<HRESULT> writeResult{ S_OK };
 	std::thread reader( [ & ]() {
 		const size_t frameBytes = (size_t)co.channels * ( co.format == 1 ? 2 : 4 );
-		std::vector<char> chunk( 1600 * frameBytes );
+		std::vector<char> chunk( (size_t)( co.rate / 10 ) * frameBytes );
 		size_t have = 0;
 		while( true )
 		{
@@ -489,7 +491,7 @@ int main( int argc, char** argv )
 	// -nrn N / --no-repeat-ngram N (the same way): Whisper::setNoRepeatNgram, no text token that would complete an n-gram its window already holds (0 = off)
 	// --capture PATH (the same way; PATH "-" = standard input): live transcription of raw 16 kHz PCM instead of input files -- --capture-format s16|f32 (s16),
 	// --capture-channels 1|2 (1); --capture-min-duration / --capture-max-duration / --capture-drop-start-silence / --capture-pause-duration N seconds
-	// (sCaptureParams: 2, 3, 0.25, 0.333); --capture-no-drop: eCaptureFlags::NoDrop, for input that arrives faster than real time; -di keeps the stereo
+	// (sCaptureParams: 2, 3, 0.25, 0.333); --capture-rate N: the input has N frames per second, 1000 .. 384000 (16000); --capture-no-drop: eCaptureFlags::NoDrop, for input that arrives faster than real time; -di keeps the stereo
 	CaptureOptions capture;
 	bool align = false, useFallback = false, suppressNst = false, timestampRules = false, haveBoost = false;
 	int noRepeatNgram = 0;
@@ -533,6 +535,14 @@ int main( int argc, char** argv )
 				capture.channels = i + 1 < argc ? atoi( argv[ ++i ] ) : 0;
 				if( capture.channels != 1 && capture.channels != 2 ) { fprintf( stderr, "error: --capture-channels takes 1 or 2\n" ); return 2; }
 			}
+			else if( !strcmp( argv[ i ], "--capture-rate" ) )
+			{
+				char* end = nullptr;
+				const long v = i + 1 < argc ? strtol( argv[ ++i ], &end, 10 ) : 0;
+				if( !end || *end || v < 1000 || v > 384000 ) { fprintf( stderr, "error: --capture-rate takes 1000 .. 384000\n" ); return 2; }
+				capture.rate = (uint32_t)v;
+				capture.rateGiven = true;
+			}
 			else if( !strcmp( argv[ i ], "--capture-no-drop" ) ) capture.params.flags |= (uint32_t)eCaptureFlags::NoDrop;
 			else if( !strcmp( argv[ i ], "--capture-min-duration" ) ) value = &capture.params.minDuration;
 			else if( !strcmp( argv[ i ], "--capture-max-duration" ) ) value = &capture.params.maxDuration;
@@ -567,9 +577,14 @@ int main( int argc, char** argv )
 		dumpOptions( o );
 		// a second line, only with --capture: the reference's parser has no such options
 		if( !capture.path.empty() )
-			printf( "{\"capture\":\"%s\",\"format\":\"%s\",\"channels\":%d,\"min_duration\":%g,\"max_duration\":%g,\"drop_start_silence\":%g,\"pause_duration\":%g,\"flags\":%u}\n",
+		{
+			printf( "{\"capture\":\"%s\",\"format\":\"%s\",\"channels\":%d,\"min_duration\":%g,\"max_duration\":%g,\"drop_start_silence\":%g,\"pause_duration\":%g,\"flags\":%u",
 				capture.path.c_str(), capture.format == 1 ? "s16" : "f32", capture.channels, capture.params.minDuration, capture.params.maxDuration,
 				capture.params.dropStartSilence, capture.params.pauseDuration, capture.params.flags | ( o.diarize ? (uint32_t)eCaptureFlags::Stereo : 0u ) );
+			// only when the option was given: the line of a 16 kHz capture is what it was
+			if( capture.rateGiven ) printf( ",\"rate\":%u", capture.rate );
+			printf( "}\n" );
+		}
 		return 0;
 	}
 	if( o.colors && !isatty( STDOUT_FILENO ) ) o.colors = false;

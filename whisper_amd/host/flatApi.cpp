@@ -354,7 +354,8 @@ WHISPER_EXPORT int32_t whisperc_run_streamed_stereo( void* ctx, const float* pcm
 	return runStreamedOn( ctx, p, reader, progressOut, progressCap, progressCount );
 }
 // Live capture (Whisper::createPcmCapture, iPcmCapture, iContext::runCapture). durations in seconds, flags: eCaptureFlags (Stereo 1, NoDrop 2)
-WHISPER_EXPORT int32_t whisperc_capture_create( float minDuration, float maxDuration, float dropStartSilence, float pauseDuration, uint32_t flags, void** captureOut )
+WHISPER_EXPORT int32_t whisperc_capture_create_rate( float minDuration, float maxDuration, float dropStartSilence, float pauseDuration, uint32_t flags, uint32_t sampleRate,
+	void** captureOut )
 {
 	if( !captureOut ) return E_POINTER;
 	sCaptureParams cp;
@@ -364,9 +365,13 @@ WHISPER_EXPORT int32_t whisperc_capture_create( float minDuration, float maxDura
 	cp.pauseDuration = pauseDuration;
 	cp.flags = flags;
 	iPcmCapture* cap = nullptr;
-	CHECK( createPcmCapture( cp, &cap ) );
+	CHECK( createPcmCaptureAtRate( cp, sampleRate, &cap ) );
 	*captureOut = cap;
 	return S_OK;
+}
+WHISPER_EXPORT int32_t whisperc_capture_create( float minDuration, float maxDuration, float dropStartSilence, float pauseDuration, uint32_t flags, void** captureOut )
+{
+	return whisperc_capture_create_rate( minDuration, maxDuration, dropStartSilence, pauseDuration, flags, 16000, captureOut );
 }
 WHISPER_EXPORT int32_t whisperc_capture_write( void* capture, const void* samples, int32_t format, int32_t channels, uint32_t frames )
 {

@@ -17,6 +17,7 @@
 #include "batchNoRepeat.h"
 #include "optionRules.h"
 #include "languageDetect.h"
+#include "captureRate.h"
 #include "scoreRequest.h"
 #include "results.h"
 #include "wavFormat.h"
@@ -1258,6 +1259,9 @@ namespace Whisper
 		*pp = new WavReader( std::move( mono ), std::move( stereo ), wantStereo );
 		return S_OK;
 	}
+	// capture.cpp's way to the device half of a capture at another rate than 16 kHz (captureRate.h): installed when the library is loaded
+	static const CaptureRateTable g_captureRateEntries = { &wh_capture_create_rate, &wh_capture_flush, &wh_capture_skip };
+	static const bool g_captureRateInstalled = ( g_captureRateTable = &g_captureRateEntries, true );
 	// the lock-step scheduler's way to the device half of language detection (languageDetect.h): installed when the library is loaded
 	static const bool g_detectorInstalled = ( g_batchLanguageDetector = &wh_lang_detect, true );
 	// ... and to per-row sampling and the no-speech gather (batchSampling.h)
