@@ -555,6 +555,45 @@ namespace Whisper
 	// receives the pieces as ready streams over the buffer (params nullptr = the call's common parameters), valid during the call; its result is splitAtPauses's
 	using pfnSplitChunks = HRESULT ( * )( const sBatchStream* streams, uint32_t count, void* pv );
 	WHISPER_EXPORT HRESULT splitAtPauses( const iAudioBuffer* buffer, const sSplitParams* params /* nullptr = defaults */, pfnSplitChunks pfnChunks, void* pv );
+	// Extension: speech only -- what faster-whisper calls vad_filter and whisper.cpp --vad. The run finds the speech with the voice-activity detector above,
+	// transcribes only that, and reports every time on the recording's own clock. It acts where the samples are in device memory already: the features are
+	// computed on the uploaded buffer (wh_vad_features), 12 bytes per 256-sample frame go to the host for the decision, the spans go back, one kernel packs the
+	// kept samples (wh_speech_pack) and the spectrogram is taken from the packed buffer; the decoding loop runs on it unchanged, so every strategy and every
+	// decoding option works as before. The rules (whisper_amd/host/speechSpans.h; DESIGN.md section 7 "Speech only"), on the detector's per-frame flags:
+	// maximal runs of speech frames; neighbours closer than minSilenceFrames merge; merged runs shorter than minSpeechFrames are dropped; each run grows by
+	// padFrames on both sides (clamped; runs that now touch merge); a run that reaches the last whole frame takes the partial frame behind it. The defaults
+	// are faster-whisper's vad_filter values rounded to frames; nobody has measured them for this detector on real speech.
+	// Times: a segment's and a token's begin maps by the start rule (packed position s of span i -> a_i + s - out_i), an end by the end rule (the start rule of
+	// s - 1, plus 1), so a segment that ends exactly at a join ends where the earlier span ends; a segment that straddles a join keeps the gap inside it.
+	// Speakers (detectSpeaker, the per-segment speakers) are answered on the caller's stereo PCM at the mapped times.
+	struct sSpeechFilter
+	{
+		int32_t minSilenceFrames;	// frames of 256 samples (16 ms); 0 = 125 (2.0 s)
+		int32_t minSpeechFrames;	// 0 = 16 (0.256 s)
+		int32_t padFrames;			// 0 = 25 (0.4 s)
+		uint32_t flags;				// reserved, 0
+	};
+	struct sSpeechSpan { int64_t firstSample, endSample; };	  // [firstSample, endSample) at 16 kHz
+	// Holds for every later runFull / runStreamed of the context; nullptr = off, the state of every new context: such a run allocates, launches and computes what
+	// it always did. No speech at all: S_OK, no segments, one Info line, nothing encoded. Less than a second of speech: S_FALSE, like a recording that short.
+	// One span that covers the recording: the unfiltered run, bit for bit. While the filter is on, a run with non-zero offset_ms or duration_ms answers
+	// E_INVALIDARG and one with eFullParamsFlags::TokenTimestamps E_NOTIMPL (its stamper reads the host's PCM); runCapture ignores the filter (its pieces are
+	// fired by the same detector already). E_INVALIDARG for a parameter that is negative or above 2^20, non-zero flags, or a context of another library.
+	WHISPER_EXPORT HRESULT setSpeechFilter( iContext* context, const sSpeechFilter* params );
+	// The spans the context's last runFull / runStreamed used. count in: the capacity of `spans`; out: the number of spans (spans may be nullptr to ask for it);
+	// E_BOUNDS when the capacity is too small. Empty when the run had the filter off -- and when it found no speech.
+	WHISPER_EXPORT HRESULT getSpeechSpans( const iContext* context, sSpeechSpan* spans, uint32_t* count );
+	// The spans alone, the counterpart of splitAtPauses: features on the calling thread's current device, decision and rules on the host. pfnSpans receives
+	// them, ascending and disjoint, valid during the call; its result is speechSpans's.
+	using pfnSpeechSpans = HRESULT ( * )( const sSpeechSpan* spans, uint32_t count, void* pv );
+	WHISPER_EXPORT HRESULT speechSpans( const iAudioBuffer* buffer, const sSpeechFilter* params /* nullptr = defaults */, pfnSpeechSpans pfnSpans, void* pv );
+	// The same switch for the lock-step batch runner: every stream of every later run is filtered when it is admitted, on the device context that uploads it;
+	// its times are mapped with its own map before its own offset in the buffer is added. A stream without speech gets an empty result and S_OK and never
+	// takes a slot. The pieces splitAtPauses plans are filtered one by one, so silent pieces are dropped and the ends of the others trimmed.
+	// E_NOTIMPL where the scheduler was built without the device's packer.
+	WHISPER_EXPORT HRESULT setBatchSpeechFilter( iBatchRunner* runner, const sSpeechFilter* params );
+	// The spans the stream behind a batch runner's result object used, relative to the stream's first sample; count as getSpeechSpans.
+	WHISPER_EXPORT HRESULT getResultSpeechSpans( const iTranscribeResult* result, sSpeechSpan* spans, uint32_t* count );
 	// Extension: live transcription. iContext::runCapture runs the reference's capture loop (Whisper/Whisper/ContextImpl.capture.cpp; DESIGN.md section 7 "Live
 	// capture") over an iPcmCapture: every piece the loop fires is a runFull on a worker thread of the library, with the buffer's media time set to the piece's
 	// first sample, so segment times are stream times and the context's decoding options apply to every piece. OS capture devices (listCaptureDevices,

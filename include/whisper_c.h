@@ -127,6 +127,18 @@ int32_t whisperc_phrase_spellings( void* model, const char* text, int32_t* token
  * n-gram its window has already sampled; 0 = off, the state of every new context and runner. */
 int32_t whisperc_set_no_repeat_ngram( void* ctx, int32_t n );
 int32_t whisperc_batch_set_no_repeat_ngram( void* runner, int32_t n );
+/* Speech only (Whisper::setSpeechFilter / setBatchSpeechFilter / speechSpans / getSpeechSpans / getResultSpeechSpans of whisperApi.h): on != 0 = every later run
+ * finds the speech with the voice-activity detector, transcribes only that and reports times on the recording's clock. Parameters in frames of 256 samples,
+ * 0 = the defaults 125 / 16 / 25; negative or above 2^20 is E_INVALIDARG. on == 0 is the state of every new context and runner.
+ * whisperc_speech_spans: the spans alone for a bare 16 kHz mono buffer, features on the calling thread's current device. whisperc_result_speech_spans: the spans
+ * the context's last run used; whisperc_tr_speech_spans: those of the stream a result object of whisperc_batch_run belongs to, relative to the stream's first
+ * sample. spans / out = int64 [cap][2] = first sample, end sample, or NULL; *count = the number of spans; cap smaller than that with a non-NULL buffer is E_BOUNDS. */
+int32_t whisperc_set_speech_filter( void* ctx, int32_t on, int32_t minSilenceFrames, int32_t minSpeechFrames, int32_t padFrames );
+int32_t whisperc_batch_set_speech_filter( void* runner, int32_t on, int32_t minSilenceFrames, int32_t minSpeechFrames, int32_t padFrames );
+int32_t whisperc_speech_spans( const float* pcm, int64_t nSamples, int32_t minSilenceFrames, int32_t minSpeechFrames, int32_t padFrames, int64_t* spans,
+	uint32_t cap, uint32_t* count );
+int32_t whisperc_result_speech_spans( void* ctx, int64_t* out, uint32_t cap, uint32_t* count );
+int32_t whisperc_tr_speech_spans( void* result, int64_t* out, uint32_t cap, uint32_t* count );
 /* Timestamp rules (Whisper::setTimestampRules / setBatchTimestampRules of whisperApi.h): on != 0 = every later run masks the logits so that timestamps come in
  * pairs, never go back in time and close segments of non-zero length. Off is the state of every new context and runner. */
 int32_t whisperc_set_timestamp_rules( void* ctx, int32_t on );

@@ -265,6 +265,29 @@ WH_API int wh_vad_features( void* stream, const float* pcmDev, int64_t nSamples,
 /* host -> host on the current device: upload of the whole frames, kernel, download. */
 WH_API int wh_vad_features_host( const float* pcm, int64_t nSamples, float* feat );
 
+/* Speech only: the spans of a recording that hold speech, packed one behind the other (Whisper::setSpeechFilter of whisperApi.h).
+ * wh_speech_pack: device -> device, on `stream`: dst[ out[i] + k ] = src[ a_i + k ] for k < b_i - a_i, where spans (HOST, int64 [count][2]) holds a_i, b_i in
+ * sample frames and out[i] is the total length of the spans before i; a frame is `channels` (1 or 2, interleaved) FP32 values. A bit copy: NaN payloads
+ * survive, nothing is converted. The spans must be non-empty, ascending, disjoint and inside [0, nSamples], count <= 65536, nOut their total length, the
+ * buffers non-null and 4-byte aligned: anything else is WH_E_INVALIDARG with no launch; count == 0 succeeds with no launch. The table of count + 1 output
+ * offsets and count span starts goes to device memory behind what the stream holds, the launch behind it, and the call returns when both are done (the
+ * table is the call's own). A workgroup owns 16384 consecutive output values, finds its first span with one binary search and walks on; where both sides of
+ * a span are 16-byte aligned -- always, for spans of the span rules (multiples of 256 samples) in buffers of hipMalloc -- the body moves 128-bit vectors and
+ * only the tail of the last span single values; other spans are copied value by value. Nothing outside [0, nOut * channels) of dstDev is written. */
+WH_API int wh_speech_pack( void* stream, const float* srcDev, int channels, int64_t nSamples, const int64_t* spans, int count, float* dstDev, int64_t nOut );
+/* host -> host on the current device: upload, kernel, download. */
+WH_API int wh_speech_pack_host( const float* src, int channels, int64_t nSamples, const int64_t* spans, int count, float* dst, int64_t nOut );
+/* The whole filter on a context's stream: wh_vad_features on pcmDev (16 kHz mono FP32, nSamples), the download of the features (12 bytes per 256-sample
+ * frame), the reference's decision loop and the span rules on the host (host/vad.h, host/speechSpans.h; params in frames, 0 or params == NULL = the defaults
+ * 125 / 16 / 25), then the pack kernel for the mono buffer and, if stereoDev (interleaved, nSamples frames) is given, for the stereo buffer. The call waits
+ * for the stream. spansOut [cap][2] receives the *count spans (WH_E_BOUNDS when cap is too small; *count is set), *nPacked their total length.
+ * *packedDev / *packedStereoDev (the latter may be NULL) are buffers of the context, valid until the next call or the context's end; the first call that
+ * needs them allocates them. No span: *packedDev = NULL, *nPacked = 0. One span that covers [0, nSamples): *packedDev = pcmDev (and the stereo likewise) and
+ * nothing is launched behind the features. A context that never calls this allocates and launches nothing of it. */
+typedef struct { int32_t minSilenceFrames, minSpeechFrames, padFrames; } wh_speech_params;
+WH_API int wh_context_speech_filter( wh_context* c, const float* pcmDev, int64_t nSamples, const float* stereoDev, const wh_speech_params* params,
+	const float** packedDev, const float** packedStereoDev, int64_t* nPacked, int64_t* spansOut, int cap, int* count );
+
 /* A live PCM stream, chunk by chunk: the buffer of the capture loop of iContext::runCapture (Whisper/Whisper/ContextImpl.capture.cpp: readSample appends
  * the converted samples, detectVoice looks at the whole buffer). A wh_capture is made for 1 or 2 input channels at 16 kHz (another rate: below) and owns, each for capSamples
  * samples: a device buffer of mono FP32, with keepStereo one of interleaved stereo FP32, and a pinned host mirror of both -- twice, see wh_capture_take.

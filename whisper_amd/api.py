@@ -105,6 +105,11 @@ def lib():
         L.whisperc_vad.argtypes = [vp, C.c_int64, vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.whisperc_plan_chunks.argtypes = [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, vp, vp, C.c_int32, C.POINTER(C.c_int32)]
         L.whisperc_debug_vad_decide.argtypes = [vp, C.c_int64, vp, C.POINTER(C.c_int64)]
+        L.whisperc_set_speech_filter.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+        L.whisperc_batch_set_speech_filter.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+        L.whisperc_speech_spans.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.whisperc_result_speech_spans.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.whisperc_tr_speech_spans.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
         L.whisperc_capture_create.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32, C.POINTER(vp)]
         L.whisperc_capture_create_rate.argtypes = [C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.POINTER(vp)]
         L.whisperc_capture_write.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_uint32]
@@ -259,6 +264,31 @@ def plan_chunks(pcm: np.ndarray, max_len: int = 480000, min_len: int = 240000, p
     first, count = np.zeros(n.value, np.int64), np.zeros(n.value, np.int64)
     _check(lib().whisperc_plan_chunks(*args, first.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p), n.value, C.byref(n)), "plan_chunks")
     return [(int(f), int(c)) for f, c in zip(first, count)]
+
+
+def _speech_frames(min_silence, min_speech, pad):
+    """seconds -> frames of 256 samples at 16 kHz, rounded; 0 stays 0 (the library's default of that parameter)"""
+    return tuple(int(round(float(v) * SAMPLE_RATE / VAD_FRAME)) for v in (min_silence, min_speech, pad))
+
+
+def _spans_of(call, *front) -> list:
+    """a (..., int64 [cap][2] or NULL, cap, *count) entry point -> [(first_sample, end_sample)]"""
+    n = C.c_uint32()
+    _check(call(*front, None, 0, C.byref(n)), "speechSpans")
+    out = np.zeros((n.value, 2), np.int64)
+    if n.value:
+        _check(call(*front, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)), "speechSpans")
+    return [(int(a), int(b)) for a, b in out]
+
+
+def speech_spans(pcm: np.ndarray, min_silence: float = 2.0, min_speech: float = 0.256, pad: float = 0.4, sample_rate: int = 16000):
+    """Whisper::speechSpans: where a mono recording holds speech, [(first_sample, end_sample)] at 16 kHz, ascending and disjoint -- what a run with
+    Context.set_speech_filter of the same arguments transcribes. The detector's flags (vad()) are merged across gaps shorter than min_silence seconds, runs
+    shorter than min_speech are dropped, and what is left is padded by `pad` on both sides. Seconds, rounded to frames of 256 samples. The defaults are
+    faster-whisper's vad_filter values; nobody has measured them for this detector on real speech."""
+    pcm = _at_16k(pcm, sample_rate)
+    a, b, c = _speech_frames(min_silence, min_speech, pad)
+    return _spans_of(lib().whisperc_speech_spans, pcm.ctypes.data_as(C.c_void_p), len(pcm), a, b, c)
 
 
 CAPTURE_STEREO, CAPTURE_NO_DROP = 1, 2                      # eCaptureFlags
@@ -630,6 +660,21 @@ class Context:
         real checkpoint. Beam search with a set held is E_NOTIMPL."""
         _set_boost(lib().whisperc_set_boost_phrases, "setBoostedPhrases", self.h, self.model, phrases, boost)
 
+    def set_speech_filter(self, min_silence: Optional[float] = 2.0, min_speech: float = 0.256, pad: float = 0.4):
+        """Whisper::setSpeechFilter (faster-whisper's vad_filter, whisper.cpp's --vad): every later run_full / run_streamed of this context finds the speech on the
+        device (speech_spans' rules, the same arguments in seconds), transcribes only that and reports every time -- segments, tokens under ALIGN_TOKENS -- on
+        the recording's own clock; speakers() are answered on the original stereo PCM. speech_spans() then tells what the last run used. A recording without
+        speech gives hr 0 and no segment. set_speech_filter(None) turns it off, the state of a new context: the run is then what it always was. With it on,
+        offset_ms / duration_ms raise (E_INVALIDARG) and TOKEN_TIMESTAMPS raises (E_NOTIMPL); run_capture ignores it."""
+        if min_silence is None:
+            _check(lib().whisperc_set_speech_filter(self.h, 0, 0, 0, 0), "setSpeechFilter")
+            return
+        _check(lib().whisperc_set_speech_filter(self.h, 1, *_speech_frames(min_silence, min_speech, pad)), "setSpeechFilter")
+
+    def speech_spans(self):
+        """Whisper::getSpeechSpans: [(first_sample, end_sample)] the last run_full / run_streamed transcribed; empty with the filter off or without speech."""
+        return _spans_of(lib().whisperc_result_speech_spans, self.h)
+
     def set_timestamp_rules(self, on: bool = True):
         """Whisper::setTimestampRules: every later run masks the logits on the device so that timestamps come in pairs, never go back in time within a window
         and close segments of non-zero length (openai-whisper's ApplyTimestampRules) -- greedy runs and the fallback's sampled attempts alike. Off, the state
@@ -759,6 +804,15 @@ class BatchRunner:
         """Whisper::setBatchBoostedPhrases: Context.set_boost_phrases for every stream of this runner's later runs (one set and one boost for all of them)."""
         _set_boost(lib().whisperc_batch_set_boost_phrases, "setBatchBoostedPhrases", self.h, self.model, phrases, boost)
 
+    def set_speech_filter(self, min_silence: Optional[float] = 2.0, min_speech: float = 0.256, pad: float = 0.4):
+        """Whisper::setBatchSpeechFilter: Context.set_speech_filter for every stream of this runner's later runs. Each stream is filtered when it is admitted
+        and its times are mapped with its own map; a stream without speech gets an empty result with hr 0 and never takes a slot. After run / run_split,
+        speech_spans holds one list per stream, relative to the stream's first sample (None for a stream without a result). None turns it off."""
+        if min_silence is None:
+            _check(lib().whisperc_batch_set_speech_filter(self.h, 0, 0, 0, 0), "setBatchSpeechFilter")
+            return
+        _check(lib().whisperc_batch_set_speech_filter(self.h, 1, *_speech_frames(min_silence, min_speech, pad)), "setBatchSpeechFilter")
+
     def set_timestamp_rules(self, on: bool = True):
         """Whisper::setBatchTimestampRules: Context.set_timestamp_rules for every stream of this runner's later runs (one switch for all of them)."""
         _check(lib().whisperc_batch_set_timestamp_rules(self.h, 1 if on else 0), "setBatchTimestampRules")
@@ -806,10 +860,12 @@ class BatchRunner:
         self.languages = []
         self.speakers = []
         self.window_stats = []
+        self.speech_spans = []
         for i in range(n):
             out.append(read_result(res[i]) if (res[i] and want_results) else None)
             self.window_stats.append(_window_stats_of(lib().whisperc_tr_window_stats, res[i], "getResultWindowStats") if res[i] else None)
             self.speakers.append(_speakers_of(lib().whisperc_tr_speakers, res[i]) if (res[i] and want_results) else None)
+            self.speech_spans.append(_spans_of(lib().whisperc_tr_speech_spans, res[i]) if res[i] else None)
             code, p = C.create_string_buffer(8), C.c_float()
             detected = bool(res[i]) and lib().whisperc_tr_language(res[i], code, C.byref(p)) == 0
             self.languages.append((code.value.decode(), p.value) if detected else None)

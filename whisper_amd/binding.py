@@ -52,6 +52,7 @@ EXPORTS = [
     "wh_lang_detect", "wh_model_lang_count", "wh_op_lang_probs",
     "wh_resample_out_len", "wh_resample", "wh_resample_host", "wh_resample_host_multi", "wh_resample_taps",
     "wh_vad_frame_count", "wh_vad_features", "wh_vad_features_host",
+    "wh_speech_pack", "wh_speech_pack_host", "wh_context_speech_filter",
     "wh_capture_create", "wh_capture_append", "wh_capture_clear", "wh_capture_take", "wh_capture_size", "wh_capture_destroy", "wh_op_capture_append",
     "wh_capture_create_rate", "wh_capture_flush", "wh_capture_skip", "wh_op_capture_append_rate",
     "wh_dequantize",
@@ -254,6 +255,9 @@ def lib():
         L.wh_vad_frame_count.argtypes = [i64, C.POINTER(i64)]
         L.wh_vad_features.argtypes = [vp, vp, i64, vp]
         L.wh_vad_features_host.argtypes = [vp, i64, vp]
+        L.wh_speech_pack.argtypes = [vp, vp, i32, i64, vp, i32, vp, i64]
+        L.wh_speech_pack_host.argtypes = [vp, i32, i64, vp, i32, vp, i64]
+        L.wh_context_speech_filter.argtypes = [vp, vp, i64, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), vp, i32, C.POINTER(i32)]
         L.wh_capture_create.argtypes = [vp, i32, i32, i64, C.POINTER(vp)]
         L.wh_capture_append.argtypes = [vp, vp, i32, i64, vp, i64, C.POINTER(i64)]
         L.wh_capture_clear.argtypes = [vp]

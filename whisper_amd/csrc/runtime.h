@@ -244,6 +244,10 @@ struct wh_context
 	TokenScore* scoreOut = nullptr;
 	int *scoreTargets = nullptr, *scoreMeta = nullptr;
 	bool scoreHook = false;	   // set around the pass of wh_score_tokens only: the multi-token decoder graph ends behind the final LayerNorm of all its rows
+	// wh_context_speech_filter (speech.hip; all allocated by the first call that needs them, grown on demand, outside every captured graph): the features of
+	// the recording's frames, the span table the pack kernel reads, and the packed copies of the mono and the stereo buffer
+	float *speechFeat = nullptr, *speechMono = nullptr, *speechStereo = nullptr;
+	long long* speechTable = nullptr;
 	TokenData* beamCand = nullptr;			   // beam search: [maxSeq][8] candidates (allocated on first use)
 	f16 *selfKScratch = nullptr, *selfVScratch = nullptr;	   // beam search: the copy a cache reorder goes through (allocated on first use)
 	// beam search on the device (wh_beam_window_*): per-window rules and state, the records of every step, the parents a step's reorder reads

@@ -27,6 +27,7 @@
 #include "batchTimestampRules.h"
 #include "batchBoost.h"
 #include "batchNoRepeat.h"
+#include "batchSpeech.h"
 #include "optionRules.h"
 #include "decodeFallback.h"
 #include "languageDetect.h"
@@ -55,6 +56,8 @@ namespace Whisper
 	pfnBatchNoRepeat g_batchNoRepeat = nullptr;
 	// ... and to the scorer of given transcripts (scoreRequest.h)
 	pfnBatchScorer g_batchScorer = nullptr;
+	// ... and to the speech filter of a newly admitted stream (batchSpeech.h)
+	pfnBatchSpeechPacker g_batchSpeechPacker = nullptr;
 
 	namespace
 	{
@@ -140,6 +143,10 @@ namespace Whisper
 			bool retry = false;
 			sWindowStats window{};
 			std::vector<sWindowStats> stats;
+			// speech only: the spans the stream's spectrogram was taken from, relative to the stream's first sample, and the way from its clock back to the
+			// stream's (empty: the clocks are the same)
+			std::vector<speechRules::Span> spans;
+			speechRules::TimeMap map;
 		};
 
 		// Device buffers of the streams (PCM, spectrograms), recycled: hipFree waits for the whole device, i.e. for the OTHER group's
@@ -226,6 +233,7 @@ namespace Whisper
 			Shared& shared;
 			const int chunk, lookahead;
 			const sDecodingFallback* const fallbackParams;	   // nullptr: the feature is off
+			const sSpeechFilter* const speechParams;		   // nullptr: the feature is off
 			bool loaderBusy = false;
 			std::deque<uint32_t> pending;
 			HRESULT firstFailure = S_OK;
@@ -252,6 +260,7 @@ namespace Whisper
 					r->languageId = s->languageId;
 					r->languageP = s->languageP;
 					r->windowStats = std::move( s->stats );
+					for( const speechRules::Span& sp : s->spans ) r->spans.push_back( sSpeechSpan{ sp.a, sp.b } );
 					results[ s->index ] = r;
 				}
 				s->run.reset();
@@ -294,7 +303,19 @@ namespace Whisper
 					s->ctx->mediaTimeOffset = bufferTime + d.firstSample * 10000000ll / 16000;
 					s->melLen = s->nSamples / 160;
 					HRESULT hr = S_OK;
-					if( s->melLen > 0 )
+					if( speechParams )
+					{
+						// speech only: the stream is filtered HERE, on the context that uploads it. Its spectrogram is taken from the packed speech -- the loader's own
+						// buffer, which the next admission overwrites behind this spectrogram on the same stream -- and a stream without speech never takes a slot.
+						hr = admitSpeechOnly( *s );
+						if( hr == S_FALSE )
+						{
+							logInfo( "runFullBatch: the speech filter found no speech in stream %u (%.2f s); nothing to transcribe", i, (double)s->nSamples / 16000.0 );
+							retire( g, b );
+							continue;
+						}
+					}
+					else if( s->melLen > 0 )
 					{
 						// enqueued on the loader's stream; startRound waits for it once, after the last admission of the round
 						int64_t got = 0;
@@ -341,7 +362,46 @@ namespace Whisper
 				if( s.params.flag( eFullParamsFlags::TokenTimestamps ) ) s.stamper.begin( s.pcm, (size_t)s.nSamples );
 				const sProgressSink none{ nullptr, nullptr };
 				s.run.reset( new StreamRun( s.params, model->vocab, model->hp, s.ctx, none, s.ctx->resultAll, s.promptPast, &s.stamper ) );
+				// speech only: the stream's own map; its offset in the buffer is added where the times are reported (the context's mediaTimeOffset)
+				if( !s.map.empty() ) s.run->setTimeMap( &s.map );
 				return s.run->begin( s.melLen );
+			}
+
+			// Admission with the speech filter on: upload, filter, the spectrogram of the packed speech. S_FALSE: no speech, nothing to transcribe.
+			HRESULT admitSpeechOnly( Stream& s )
+			{
+				if( s.params.offset_ms != 0 || s.params.duration_ms != 0 )
+				{
+					logError( "runFullBatch: offset_ms and duration_ms are not available with the speech filter (setBatchSpeechFilter) on [stream %u]", s.index );
+					return E_INVALIDARG;
+				}
+				if( s.params.flag( eFullParamsFlags::TokenTimestamps ) )
+				{
+					logError( "runFullBatch: eFullParamsFlags::TokenTimestamps is not available with the speech filter (setBatchSpeechFilter) on [stream %u]", s.index );
+					return E_NOTIMPL;
+				}
+				if( s.melLen <= 0 ) return S_FALSE;
+				wh_context_bind( shared.loader );
+				CHECK( shared.pool.acquire( s.nSamples * 4, s.pcmDev ) );
+				CHECK_WH( wh_buffer_upload_async( shared.loader, s.pcmDev, s.pcm, s.nSamples * 4 ) );
+				loaderBusy = true;
+				const wh_speech_params p{ speechParams->minSilenceFrames, speechParams->minSpeechFrames, speechParams->padFrames };
+				// the spans of a recording are at least a frame long and a frame apart
+				const int cap = (int)std::min<int64_t>( 65536, s.nSamples / ( 2 * vad::FRAME_SAMPLES ) + 1 );
+				std::vector<int64_t> flat( (size_t)cap * 2 );
+				int count = 0;
+				const float* packed = nullptr;
+				int64_t nPacked = 0;
+				CHECK_WH( g_batchSpeechPacker( shared.loader, (const float*)s.pcmDev, s.nSamples, nullptr, &p, &packed, nullptr, &nPacked, flat.data(), cap, &count ) );
+				for( int k = 0; k < count; k++ ) s.spans.push_back( speechRules::Span{ flat[ (size_t)k * 2 ], flat[ (size_t)k * 2 + 1 ] } );
+				if( count == 0 || !packed ) return S_FALSE;
+				if( !speechRules::coversAll( s.spans, s.nSamples ) ) s.map.assign( s.spans );
+				s.melLen = nPacked / 160;
+				if( s.melLen <= 0 ) return S_OK;	// StreamRun::begin answers S_FALSE: less than a second
+				CHECK( shared.pool.acquire( s.melLen * model->hp.n_mels * 4, s.melDev ) );
+				int64_t got = 0;
+				CHECK_WH( wh_mel_spectrogram( shared.loader, packed, nPacked, (float*)s.melDev, &got ) );
+				return S_OK;
 			}
 
 			// The detection pre-pass of a round (the "auto" branch of whisper_full, whisper.cpp:2788-2801, for a lock-step batch): the windows at FRAME 0
@@ -611,9 +671,9 @@ namespace Whisper
 
 		public:
 			Scheduler( const std::shared_ptr<LoadedModel>& m, iModel* o, const sFullParams& p, const sBatchStream* d, uint32_t n, iTranscribeResult** r, HRESULT* per,
-				std::vector<Group>& grp, Shared& sh, int chunk_, int lookahead_, const sDecodingFallback* fallback_ )
+				std::vector<Group>& grp, Shared& sh, int chunk_, int lookahead_, const sDecodingFallback* fallback_, const sSpeechFilter* speech_ )
 				: model( m ), owner( o ), common( p ), descs( d ), count( n ), results( r ), perStream( per ), groups( grp ), shared( sh ), chunk( chunk_ ), lookahead( lookahead_ ),
-				fallbackParams( fallback_ ) {}
+				fallbackParams( fallback_ ), speechParams( speech_ ) {}
 			~Scheduler()
 			{
 				// a failure left streams in their slots: their buffers go, the device work they queued is awaited
@@ -699,6 +759,9 @@ namespace Whisper
 			uint32_t boostVersion = 0;
 			// Whisper::setBatchNoRepeatNgram: one n for every stream, 0 = off; a group's context is told before the first round in which it holds another n
 			int noRepeatN = 0;
+			// Whisper::setBatchSpeechFilter: off unless set; every stream of a run is filtered when it is admitted
+			bool speechOn = false;
+			sSpeechFilter speechParams{};
 		public:
 			// The setters answer in one order: the argument check (optionRules.h), E_NOTIMPL without the device entry, "nothing changes", then the new version
 			HRESULT setBoosted( const sBoostedPhrases* p )
@@ -709,6 +772,15 @@ namespace Whisper
 				if( set.count() == 0 && boostSet.count() == 0 ) return S_OK;
 				boostSet = std::move( set );
 				boostVersion++;
+				return S_OK;
+			}
+			HRESULT setSpeech( const sSpeechFilter* p )
+			{
+				if( !p ) { speechOn = false; return S_OK; }
+				CHECK( optionRules::checkSpeechFilter( "setBatchSpeechFilter", *p ) );
+				if( !g_batchSpeechPacker ) return optionRules::notGiven( "setBatchSpeechFilter", "speech packer" );
+				speechParams = *p;
+				speechOn = true;
 				return S_OK;
 			}
 			HRESULT setNoRepeat( int n )
@@ -917,7 +989,8 @@ namespace Whisper
 					modesDirty = false;
 				}
 				modesDirty = modesDirty || fallbackOn;
-				Scheduler s( model, owner, params, streams, count, results, perStream, groups, shared, chunk, lookahead, fallbackOn ? &fallbackParams : nullptr );
+				Scheduler s( model, owner, params, streams, count, results, perStream, groups, shared, chunk, lookahead, fallbackOn ? &fallbackParams : nullptr,
+					speechOn ? &speechParams : nullptr );
 				const HRESULT hr = s.run( (int)slots, (int)useGroups );
 				if( FAILED( hr ) ) logError( "runFullBatch: failed, HRESULT 0x%08x", (unsigned)hr );
 				return hr;
@@ -971,6 +1044,23 @@ namespace Whisper
 	{
 		return optionRules::forward<BatchRunner>( runner, "setBatchNoRepeatNgram", NOT_A_RUNNER, nullptr,
 			[ = ]( BatchRunner& r ) { return r.setNoRepeat( n ); } );
+	}
+	HRESULT setBatchSpeechFilter( iBatchRunner* runner, const sSpeechFilter* params )
+	{
+		return optionRules::forward<BatchRunner>( runner, "setBatchSpeechFilter", NOT_A_RUNNER, nullptr,
+			[ = ]( BatchRunner& r ) { return r.setSpeech( params ); } );
+	}
+	HRESULT getResultSpeechSpans( const iTranscribeResult* result, sSpeechSpan* spans, uint32_t* count )
+	{
+		if( !result || !count ) return E_POINTER;
+		const TranscribeResult* const r = dynamic_cast<const TranscribeResult*>( result );
+		if( !r ) return E_INVALIDARG;
+		const uint32_t cap = *count;
+		*count = (uint32_t)r->spans.size();
+		if( !spans ) return S_OK;
+		if( cap < r->spans.size() ) return E_BOUNDS;
+		std::copy( r->spans.begin(), r->spans.end(), spans );
+		return S_OK;
 	}
 	HRESULT getResultWindowStats( const iTranscribeResult* result, sWindowStats* stats, uint32_t* count )
 	{

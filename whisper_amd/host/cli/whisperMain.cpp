@@ -13,6 +13,7 @@
 #include <string.h>
 #include <unistd.h>
 #include <atomic>
+#include <cmath>
 #include <limits>
 #include <string>
 #include <fstream>
@@ -492,6 +493,10 @@ int main( int argc, char** argv )
 	// --capture PATH (the same way; PATH "-" = standard input): live transcription of raw 16 kHz PCM instead of input files -- --capture-format s16|f32 (s16),
 	// --capture-channels 1|2 (1); --capture-min-duration / --capture-max-duration / --capture-drop-start-silence / --capture-pause-duration N seconds
 	// (sCaptureParams: 2, 3, 0.25, 0.333); --capture-rate N: the input has N frames per second, 1000 .. 384000 (16000); --capture-no-drop: eCaptureFlags::NoDrop, for input that arrives faster than real time; -di keeps the stereo
+	// --speech-only (the same way): Whisper::setSpeechFilter, only the speech the voice-activity detector finds is transcribed and the times stay the recording's;
+	// --so-min-silence / --so-min-speech / --so-pad S: its parameters in seconds, rounded to frames of 16 ms (2.0, 0.256, 0.4)
+	bool speechOnly = false, speechTuned = false;
+	float soMinSilence = 0.0f, soMinSpeech = 0.0f, soPad = 0.0f;
 	CaptureOptions capture;
 	bool align = false, useFallback = false, suppressNst = false, timestampRules = false, haveBoost = false;
 	int noRepeatNgram = 0;
@@ -507,6 +512,10 @@ int main( int argc, char** argv )
 			else if( !strcmp( argv[ i ], "--fallback" ) ) useFallback = true;
 			else if( !strcmp( argv[ i ], "-sns" ) || !strcmp( argv[ i ], "--suppress-nst" ) ) suppressNst = true;
 			else if( !strcmp( argv[ i ], "-tsr" ) || !strcmp( argv[ i ], "--timestamp-rules" ) ) timestampRules = true;
+			else if( !strcmp( argv[ i ], "--speech-only" ) ) speechOnly = true;
+			else if( !strcmp( argv[ i ], "--so-min-silence" ) ) { value = &soMinSilence; speechTuned = true; }
+			else if( !strcmp( argv[ i ], "--so-min-speech" ) ) { value = &soMinSpeech; speechTuned = true; }
+			else if( !strcmp( argv[ i ], "--so-pad" ) ) { value = &soPad; speechTuned = true; }
 			else if( !strcmp( argv[ i ], "--score" ) )
 			{
 				if( i + 1 >= argc ) { fprintf( stderr, "error: --score needs a file\n" ); return 2; }
@@ -569,6 +578,11 @@ int main( int argc, char** argv )
 	if( boostFile.empty() != !haveBoost )
 	{
 		fprintf( stderr, "error: --boost-phrases FILE and --boost N go together (there is no default boost)\n" );
+		return 2;
+	}
+	if( speechTuned && !speechOnly )
+	{
+		fprintf( stderr, "error: --so-min-silence, --so-min-speech and --so-pad need --speech-only\n" );
 		return 2;
 	}
 	if( const int stop = parse( argc, argv, o ) ) return stop - 1;
@@ -653,6 +667,14 @@ int main( int argc, char** argv )
 	{
 		hr = setNoRepeatNgram( context, noRepeatNgram );
 		if( FAILED( hr ) ) { printFailure( "failed to set the no-repeat n-gram size", hr ); return 6; }
+	}
+	if( speechOnly )
+	{
+		// seconds to frames of 256 samples at 16 kHz; 0 = the library's default
+		auto frames = []( float seconds ) { return (int32_t)lroundf( seconds * 16000.0f / 256.0f ); };
+		const sSpeechFilter filter{ frames( soMinSilence ), frames( soMinSpeech ), frames( soPad ), 0 };
+		hr = setSpeechFilter( context, &filter );
+		if( FAILED( hr ) ) { printFailure( "failed to set the speech filter", hr ); return 6; }
 	}
 	if( !boostFile.empty() )
 	{

@@ -252,6 +252,33 @@ WHISPER_EXPORT int32_t whisperc_batch_set_no_repeat_ngram( void* runner, int32_t
 	if( !runner ) return E_POINTER;
 	return setBatchNoRepeatNgram( (iBatchRunner*)runner, n );
 }
+// Whisper::setSpeechFilter / setBatchSpeechFilter: on == 0 turns the filter off; 0 = a parameter's default
+WHISPER_EXPORT int32_t whisperc_set_speech_filter( void* ctx, int32_t on, int32_t minSilenceFrames, int32_t minSpeechFrames, int32_t padFrames )
+{
+	if( !ctx ) return E_POINTER;
+	const sSpeechFilter p{ minSilenceFrames, minSpeechFrames, padFrames, 0 };
+	return setSpeechFilter( (iContext*)ctx, on ? &p : nullptr );
+}
+WHISPER_EXPORT int32_t whisperc_batch_set_speech_filter( void* runner, int32_t on, int32_t minSilenceFrames, int32_t minSpeechFrames, int32_t padFrames )
+{
+	if( !runner ) return E_POINTER;
+	const sSpeechFilter p{ minSilenceFrames, minSpeechFrames, padFrames, 0 };
+	return setBatchSpeechFilter( (iBatchRunner*)runner, on ? &p : nullptr );
+}
+// Whisper::getSpeechSpans / getResultSpeechSpans: out = int64 [cap][2] (may be NULL), *count = the spans the last run / the result's stream used
+WHISPER_EXPORT int32_t whisperc_result_speech_spans( void* ctx, int64_t* out, uint32_t cap, uint32_t* count )
+{
+	if( !ctx || !count ) return E_POINTER;
+	*count = cap;
+	static_assert( sizeof( sSpeechSpan ) == 16, "sSpeechSpan is two int64" );
+	return getSpeechSpans( (const iContext*)ctx, (sSpeechSpan*)out, count );
+}
+WHISPER_EXPORT int32_t whisperc_tr_speech_spans( void* result, int64_t* out, uint32_t cap, uint32_t* count )
+{
+	if( !result || !count ) return E_POINTER;
+	*count = cap;
+	return getResultSpeechSpans( (const iTranscribeResult*)result, (sSpeechSpan*)out, count );
+}
 // Whisper::setTimestampRules / setBatchTimestampRules
 WHISPER_EXPORT int32_t whisperc_set_timestamp_rules( void* ctx, int32_t on )
 {

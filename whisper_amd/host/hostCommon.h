@@ -92,10 +92,14 @@ namespace Whisper
 		int id = 0, tid = 0;
 		float p = 0, pt = 0, ptsum = 0, vlen = 0;
 		int64_t t0 = -1, t1 = -1;	// 10 ms units, -1 = unknown
+		int64_t shift0 = 0, shift1 = 0;	  // 100 ns ticks added to t0 / t1 where they are reported: StreamRun's time map, 0 without one
 	};
 	struct Segment
 	{
 		int64_t t0 = 0, t1 = 0;	   // 10 ms units
+		// 100 ns ticks added to t0 / t1 where they are reported (results.h). A stream that transcribes a packed copy of its recording (speechSpans.h) keeps
+		// its own clock in t0 / t1 and the way back to the recording's clock here; 0 for every other stream.
+		int64_t shift0 = 0, shift1 = 0;
 		std::string text;
 		std::vector<TokenData> tokens;
 	};

@@ -7,6 +7,7 @@
 //   WindowScan  the tokens of one window, fed in order: timestamp tracking and the stop rules (ContextImpl.cpp:597-673).
 #pragma once
 #include "hostCommon.h"
+#include "speechSpans.h"
 
 namespace Whisper
 {
@@ -104,6 +105,7 @@ namespace Whisper
 		std::vector<int>& promptPast;
 		TokenTimestamper* const stamper;   // TokenTimestamps flag, or nullptr
 		iTokenAligner* aligner = nullptr;  // AlignTokens flag, or nullptr
+		const speechRules::TimeMap* timeMap = nullptr;	   // the stream's audio is a packed copy of its recording (Whisper::setSpeechFilter), or nullptr
 		std::vector<int> promptInit;
 		int seekStart = 0, seekEndV = 0;
 		bool stoppedPrematurely = false;
@@ -114,6 +116,10 @@ namespace Whisper
 		const sFullParams& fullParams() const { return params; }
 		// AlignTokens: who aligns a finished window's text against its audio (called once per window from finishWindow, never without the flag)
 		void setAligner( iTokenAligner* a ) { aligner = a; }
+		// Speech only: the stream's spectrogram was taken from a packed copy of the recording. The loop runs on the packed clock as it always did; every segment
+		// -- and its tokens' times, where it has them -- receives the way back to the recording's clock (Segment::shift0 / shift1) before a callback or
+		// getResults can see it: t0 by the map's start rule, t1 by its end rule. The map outlives the run. Never set: nothing changes.
+		void setTimeMap( const speechRules::TimeMap* m ) { timeMap = m; }
 		int seekEnd() const { return seekEndV; }
 		int maxTokens() const { return hp.n_text_ctx / 2 - 4; }
 
@@ -290,6 +296,18 @@ namespace Whisper
 						}
 					}
 					if( ( stamped || aligned ) && params.max_len > 0 ) nNew = (uint32_t)TokenTimestamper::wrapLast( resultAll, vocab, params.max_len );
+					if( timeMap )
+						for( size_t k = resultAll.size() - nNew; k < resultAll.size(); k++ )
+						{
+							Segment& seg = resultAll[ k ];
+							seg.shift0 = timeMap->startTicks( seg.t0 * 100000 ) - seg.t0 * 100000;
+							seg.shift1 = timeMap->endTicks( seg.t1 * 100000 ) - seg.t1 * 100000;
+							for( TokenData& t : seg.tokens )
+							{
+								if( t.t0 >= 0 ) t.shift0 = timeMap->startTicks( t.t0 * 100000 ) - t.t0 * 100000;
+								if( t.t1 >= 0 ) t.shift1 = timeMap->endTicks( t.t1 * 100000 ) - t.t1 * 100000;
+							}
+						}
 					if( params.new_segment_callback )
 					{
 						const HRESULT hr = params.new_segment_callback( self, nNew, params.new_segment_callback_user_data );

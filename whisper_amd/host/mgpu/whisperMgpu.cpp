@@ -29,6 +29,7 @@
 #include <time.h>
 #include <unistd.h>
 #include <chrono>
+#include <cmath>
 #include <string>
 #include <thread>
 #include <vector>
@@ -60,6 +61,10 @@ namespace
 		bool timestampRules = false;
 		// -nrn N / --no-repeat-ngram N: Whisper::setBatchNoRepeatNgram on every rank's runner (0 = off)
 		int noRepeatNgram = 0;
+		// -speech-only: Whisper::setBatchSpeechFilter on every rank's runner; -so-min-silence / -so-min-speech / -so-pad S (whisper-main's names) set its
+		// parameters in seconds, rounded to frames of 16 ms (0 = the library's defaults 2.0, 0.256, 0.4)
+		bool speechOnly = false;
+		float soMinSilence = 0.0f, soMinSpeech = 0.0f, soPad = 0.0f;
 		// -boost-phrases FILE -boost N (one needs the other): Whisper::setBatchBoostedPhrases on every rank's runner with the spellings of the file's phrases
 		std::string boostFile;
 		bool haveBoost = false;
@@ -281,6 +286,13 @@ namespace
 			hr = setBatchNoRepeatNgram( runner, a.noRepeatNgram );
 			if( FAILED( hr ) ) { fprintf( stderr, "[rank %d] setBatchNoRepeatNgram failed 0x%08x\n", rank, (unsigned)hr ); return 6; }
 		}
+		if( runner && a.speechOnly )
+		{
+			auto frames = []( float seconds ) { return (int32_t)lroundf( seconds * 16000.0f / 256.0f ); };
+			const sSpeechFilter filter{ frames( a.soMinSilence ), frames( a.soMinSpeech ), frames( a.soPad ), 0 };
+			hr = setBatchSpeechFilter( runner, &filter );
+			if( FAILED( hr ) ) { fprintf( stderr, "[rank %d] setBatchSpeechFilter failed 0x%08x\n", rank, (unsigned)hr ); return 6; }
+		}
 		if( runner && !a.boostFile.empty() )
 		{
 			phraseFile::Rows rows;
@@ -416,6 +428,7 @@ namespace
 int main( int argc, char** argv )
 {
 	Args a;
+	bool soTuned = false;
 	for( int i = 1; i < argc; i++ )
 	{
 		auto val = [ & ]() -> const char* { return i + 1 < argc ? argv[ ++i ] : ""; };
@@ -441,6 +454,10 @@ int main( int argc, char** argv )
 		else if( !strcmp( argv[ i ], "-sns" ) || !strcmp( argv[ i ], "--suppress-nst" ) ) a.suppressNst = true;
 		else if( !strcmp( argv[ i ], "-tsr" ) || !strcmp( argv[ i ], "--timestamp-rules" ) ) a.timestampRules = true;
 		else if( !strcmp( argv[ i ], "-nrn" ) || !strcmp( argv[ i ], "--no-repeat-ngram" ) ) a.noRepeatNgram = atoi( val() );
+		else if( !strcmp( argv[ i ], "-speech-only" ) || !strcmp( argv[ i ], "--speech-only" ) ) a.speechOnly = true;
+		else if( !strcmp( argv[ i ], "-so-min-silence" ) || !strcmp( argv[ i ], "--so-min-silence" ) ) { a.soMinSilence = (float)atof( val() ); soTuned = true; }
+		else if( !strcmp( argv[ i ], "-so-min-speech" ) || !strcmp( argv[ i ], "--so-min-speech" ) ) { a.soMinSpeech = (float)atof( val() ); soTuned = true; }
+		else if( !strcmp( argv[ i ], "-so-pad" ) || !strcmp( argv[ i ], "--so-pad" ) ) { a.soPad = (float)atof( val() ); soTuned = true; }
 		else if( !strcmp( argv[ i ], "-boost-phrases" ) || !strcmp( argv[ i ], "--boost-phrases" ) ) a.boostFile = val();
 		else if( !strcmp( argv[ i ], "-boost" ) || !strcmp( argv[ i ], "--boost" ) ) { a.boost = (float)atof( val() ); a.haveBoost = true; }
 		else if( !strcmp( argv[ i ], "-tpi" ) ) a.fallback.temperatureInc = (float)atof( val() );
@@ -479,6 +496,7 @@ int main( int argc, char** argv )
 		else { fputs( USAGE, stderr ); return 1; }
 	}
 	if( a.splitSilence && a.perRecording ) { fprintf( stderr, "whisper-mgpu: -split silence cuts ONE recording into chunks; -per-recording keeps recordings whole\n%s", USAGE ); return 1; }
+	if( soTuned && !a.speechOnly ) { fprintf( stderr, "whisper-mgpu: -so-min-silence, -so-min-speech and -so-pad need -speech-only\n" ); return 1; }
 	if( a.boostFile.empty() != !a.haveBoost ) { fprintf( stderr, "whisper-mgpu: -boost-phrases FILE and -boost N go together (there is no default boost)\n" ); return 1; }
 	if( a.model.empty() || a.wav.empty() || a.ranks < 1 ) { fprintf( stderr, "whisper-mgpu: -m and -f are required\n" ); return 1; }
 	if( !a.perRecording && a.wavs.size() > 1 ) { fprintf( stderr, "whisper-mgpu: several -f recordings need -per-recording (the chunk mode shards ONE recording)\n" ); return 1; }

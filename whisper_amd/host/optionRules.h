@@ -5,6 +5,7 @@
 #pragma once
 #include "hostCommon.h"
 #include "phraseBoost.h"
+#include "speechSpans.h"
 #include <cmath>
 
 namespace Whisper
@@ -44,6 +45,14 @@ namespace Whisper
 		{
 			if( n >= 0 && n <= 8 ) return S_OK;
 			logError( "%s: n = %i is outside 0 .. 8", name, n );
+			return E_INVALIDARG;
+		}
+		// the speech filter's parameters: frames, each 0 (the default) .. 2^20 (speechSpans.h states the defaults and the bound); flags reserved
+		inline HRESULT checkSpeechFilter( const char* name, const sSpeechFilter& p )
+		{
+			int64_t a = p.minSilenceFrames, b = p.minSpeechFrames, c = p.padFrames;
+			if( p.flags == 0 && SUCCEEDED( speechRules::resolveParams( a, b, c ) ) ) return S_OK;
+			logError( "%s: minSilenceFrames, minSpeechFrames and padFrames must each lie in 0 .. 2^20 frames, and flags must be 0", name );
 			return E_INVALIDARG;
 		}
 		// BatchRunner without the injected device entry an option needs (batchSampling.h and its like)

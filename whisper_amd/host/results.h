@@ -25,6 +25,8 @@ namespace Whisper
 		float languageP = 0;
 		// a batch runner's stream with Whisper::setBatchDecodingFallback on: what the fallback did with each of its windows (getResultWindowStats reads them)
 		std::vector<sWindowStats> windowStats;
+		// a batch runner's stream with Whisper::setBatchSpeechFilter on: the spans it was transcribed from, relative to its first sample (getResultSpeechSpans reads them)
+		std::vector<sSpeechSpan> spans;
 		HRESULT getSize( sTranscribeLength& rdi ) const override
 		{
 			rdi.countSegments = (uint32_t)segments.size();
@@ -71,15 +73,15 @@ namespace Whisper
 			if( stereo )
 			{
 				sTimeInterval time;
-				time.begin.ticks = (uint64_t)( resultAll[ i ].t0 * 100000 + mediaTimeOffset );
-				time.end.ticks = (uint64_t)( resultAll[ i ].t1 * 100000 + mediaTimeOffset );
+				time.begin.ticks = (uint64_t)( resultAll[ i ].t0 * 100000 + resultAll[ i ].shift0 + mediaTimeOffset );
+				time.end.ticks = (uint64_t)( resultAll[ i ].t1 * 100000 + resultAll[ i ].shift1 + mediaTimeOffset );
 				if( FAILED( diarize::detectSpeaker( stereo, frames, mediaTimeOffset, time, ch ) ) ) ch = eSpeakerChannel::NoStereoData;
 			}
 			speakers.push_back( (uint8_t)ch );
 		}
 	}
 
-	// Segment times: 10 ms units -> 100 ns ticks, plus the media time of the first sample (ContextImpl.misc.cpp getResults)
+	// Segment times: 10 ms units -> 100 ns ticks, plus the segment's own shift (a stream with a time map, hostLoop.h; 0 otherwise), plus the media time of the first sample (ContextImpl.misc.cpp getResults)
 	inline HRESULT fillResultData( const std::vector<Segment>& resultAll, const Vocabulary& vocab, int64_t mediaTimeOffset, eResultFlags flags, ResultData& res )
 	{
 		const bool withTokens = flags & eResultFlags::Tokens, withTimes = flags & eResultFlags::Timestamps;
@@ -95,10 +97,10 @@ namespace Whisper
 		// at 0 instead of "unknown" (hostLoop.h), so makeResults reports the media time for it (ContextImpl.misc.cpp:277-283); pinned on
 		// the reference's own makeResults, tests/golden/ref_hostloop_contextimpl.json "results".
 		const bool fromZero = g_hostLoopRules == eHostLoopRules::ContextImpl;
-		auto tokenTicks = [ & ]( int64_t t10ms ) -> uint64_t
+		auto tokenTicks = [ & ]( int64_t t10ms, int64_t shift ) -> uint64_t
 		{
 			if( !withTimes || ( t10ms < 0 && !fromZero ) ) return 0;
-			return ticks( std::max<int64_t>( t10ms, 0 ) ) + (uint64_t)mediaTimeOffset;
+			return ticks( std::max<int64_t>( t10ms, 0 ) ) + (uint64_t)shift + (uint64_t)mediaTimeOffset;
 		};
 		for( size_t i = 0; i < resultAll.size(); i++ )
 		{
@@ -106,8 +108,8 @@ namespace Whisper
 			sSegment& dst = res.segments[ i ];
 			res.texts[ i ] = src.text;
 			dst.text = res.texts[ i ].c_str();
-			dst.time.begin.ticks = withTimes ? ticks( src.t0 ) + (uint64_t)mediaTimeOffset : 0;
-			dst.time.end.ticks = withTimes ? ticks( src.t1 ) + (uint64_t)mediaTimeOffset : 0;
+			dst.time.begin.ticks = withTimes ? ticks( src.t0 ) + (uint64_t)src.shift0 + (uint64_t)mediaTimeOffset : 0;
+			dst.time.end.ticks = withTimes ? ticks( src.t1 ) + (uint64_t)src.shift1 + (uint64_t)mediaTimeOffset : 0;
 			dst.firstToken = (uint32_t)soFar;
 			dst.countTokens = (uint32_t)src.tokens.size();
 			if( withTokens )
@@ -116,8 +118,8 @@ namespace Whisper
 					const TokenData& t = src.tokens[ j ];
 					sToken& o = res.tokens[ soFar + j ];
 					o.text = vocab.string( t.id );
-					o.time.begin.ticks = tokenTicks( t.t0 );
-					o.time.end.ticks = tokenTicks( t.t1 );
+					o.time.begin.ticks = tokenTicks( t.t0, t.shift0 );
+					o.time.end.ticks = tokenTicks( t.t1, t.shift1 );
 					o.probability = t.p; o.probabilityTimestamp = t.pt; o.ptsum = t.ptsum; o.vlen = t.vlen;
 					o.id = t.id;
 					o.flags = t.id >= vocab.token_eot ? eTokenFlags::Special : eTokenFlags::None;

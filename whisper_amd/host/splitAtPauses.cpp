@@ -1,9 +1,11 @@
 // One long recording onto the batched path: voice-activity features on the device (wh_vad_features), the reference's decision loop over them (vad.h) and
-// the chunk planner (chunkPlanner.h). Whisper::splitAtPauses of whisperApi.h and its flat C mirror (whisper_c.h).
+// the chunk planner (chunkPlanner.h). Whisper::splitAtPauses of whisperApi.h and its flat C mirror (whisper_c.h). Whisper::speechSpans, the spans of the
+// speech filter alone (speechSpans.h), takes the same way to the flags.
 //
 // Known cost: the PCM goes to the device twice -- once here for the features, once per chunk by the batch runner's admission (12.8 MB for 200 s).
 #include "hostCommon.h"
 #include "chunkPlanner.h"
+#include "optionRules.h"
 #include <cstring>
 
 namespace Whisper
@@ -43,6 +45,31 @@ namespace Whisper
 			}
 			return chunkPlanner::plan( speech.data(), energy.data(), (int64_t)speech.size(), nSamples, maxLen, minLen, pauseFrames, chunks );
 		}
+	}
+
+	// the spans a run with these parameters transcribes: the same features, decision and rules as wh_context_speech_filter applies on a context's stream
+	static HRESULT spansFor( const float* pcm, int64_t nSamples, const sSpeechFilter* params, std::vector<sSpeechSpan>& out )
+	{
+		const sSpeechFilter defaults{ 0, 0, 0, 0 };
+		const sSpeechFilter& p = params ? *params : defaults;
+		// refuse bad parameters before the device is asked for anything
+		CHECK( optionRules::checkSpeechFilter( "speechSpans", p ) );
+		std::vector<uint8_t> speech;
+		std::vector<float> energy;
+		int64_t lastSpeech = 0;
+		CHECK( detect( pcm, nSamples, speech, energy, lastSpeech ) );
+		std::vector<speechRules::Span> spans;
+		CHECK( speechRules::find( speech.data(), (int64_t)speech.size(), nSamples, p.minSilenceFrames, p.minSpeechFrames, p.padFrames, spans ) );
+		out.clear();
+		for( const speechRules::Span& s : spans ) out.push_back( sSpeechSpan{ s.a, s.b } );
+		return S_OK;
+	}
+	HRESULT speechSpans( const iAudioBuffer* buffer, const sSpeechFilter* params, pfnSpeechSpans pfnSpans, void* pv )
+	{
+		if( !buffer || !pfnSpans ) return E_POINTER;
+		std::vector<sSpeechSpan> spans;
+		CHECK( spansFor( buffer->getPcmMono(), (int64_t)buffer->countSamples(), params, spans ) );
+		return pfnSpans( spans.data(), (uint32_t)spans.size(), pv );
 	}
 
 	HRESULT splitAtPauses( const iAudioBuffer* buffer, const sSplitParams* params, pfnSplitChunks pfnChunks, void* pv )
@@ -95,6 +122,21 @@ WHISPER_EXPORT int32_t whisperc_plan_chunks( const float* pcm, int64_t nSamples,
 		first[ i ] = chunks[ i ].firstSample;
 		count[ i ] = chunks[ i ].countSamples;
 	}
+	return S_OK;
+}
+
+// Whisper::speechSpans for a bare PCM buffer: *count = the spans; spans = int64 [cap][2] or NULL (count only), cap < *count is E_BOUNDS. 0 = a parameter's default
+WHISPER_EXPORT int32_t whisperc_speech_spans( const float* pcm, int64_t nSamples, int32_t minSilenceFrames, int32_t minSpeechFrames, int32_t padFrames, int64_t* spans,
+	uint32_t cap, uint32_t* count )
+{
+	if( !count ) return E_POINTER;
+	const sSpeechFilter p{ minSilenceFrames, minSpeechFrames, padFrames, 0 };
+	std::vector<sSpeechSpan> all;
+	CHECK( spansFor( pcm, nSamples, &p, all ) );
+	*count = (uint32_t)all.size();
+	if( !spans ) return S_OK;
+	if( cap < all.size() ) return E_BOUNDS;
+	for( size_t i = 0; i < all.size(); i++ ) { spans[ 2 * i ] = all[ i ].firstSample; spans[ 2 * i + 1 ] = all[ i ].endSample; }
 	return S_OK;
 }
 

@@ -15,6 +15,7 @@
 #include "batchTimestampRules.h"
 #include "batchBoost.h"
 #include "batchNoRepeat.h"
+#include "batchSpeech.h"
 #include "optionRules.h"
 #include "languageDetect.h"
 #include "captureRate.h"
@@ -141,6 +142,54 @@ namespace Whisper
 			bool boostOn = false;
 			// Whisper::setNoRepeatNgram: 0 = off unless set. The stream's device context holds n; the hypothesis-group context of beam search cannot (runFull refuses)
 			int noRepeatN = 0;
+			// Whisper::setSpeechFilter: off unless set. A run with it on packs the speech of the uploaded PCM on the device (wh_context_speech_filter) and works on the
+			// packed buffer; runSpans / runMap are what the last run used (the map is empty when the run's clock is the recording's)
+			bool speechOn = false;
+			sSpeechFilter speechParams{};
+			std::vector<speechRules::Span> runSpans;
+			speechRules::TimeMap runMap;
+			// the filter on the context's resident PCM (pcmDev, n samples). packed: what the spectrogram is taken from -- pcmDev itself when one span covers it all,
+			// nullptr when there is no speech
+			HRESULT filterSpeech( int64_t n, const float*& packed, int64_t& nPacked )
+			{
+				runSpans.clear();
+				runMap = speechRules::TimeMap{};
+				const wh_speech_params p{ speechParams.minSilenceFrames, speechParams.minSpeechFrames, speechParams.padFrames };
+				// the spans of a recording are at least a frame long and a frame apart
+				const int cap = (int)std::min<int64_t>( 65536, n / ( 2 * vad::FRAME_SAMPLES ) + 1 );
+				std::vector<int64_t> flat( (size_t)cap * 2 );
+				int count = 0;
+				CHECK_WH( wh_context_speech_filter( gpu, (const float*)pcmDev, n, nullptr, &p, &packed, nullptr, &nPacked, flat.data(), cap, &count ) );
+				for( int i = 0; i < count; i++ ) runSpans.push_back( speechRules::Span{ flat[ (size_t)i * 2 ], flat[ (size_t)i * 2 + 1 ] } );
+				if( count > 0 && !speechRules::coversAll( runSpans, n ) ) runMap.assign( runSpans );
+				return S_OK;
+			}
+			// what a run with the filter on refuses
+			HRESULT speechFilterAccepts( const char* who, const sFullParams& params ) const
+			{
+				if( params.offset_ms != 0 || params.duration_ms != 0 )
+				{
+					logError( "%s: offset_ms and duration_ms are not available with the speech filter (setSpeechFilter) on", who );
+					return E_INVALIDARG;
+				}
+				if( params.flag( eFullParamsFlags::TokenTimestamps ) )
+				{
+					logError( "%s: eFullParamsFlags::TokenTimestamps is not available with the speech filter (setSpeechFilter) on: its stamper reads the host's PCM", who );
+					return E_NOTIMPL;
+				}
+				return S_OK;
+			}
+			// no speech at all: S_OK, no segments, nothing encoded
+			HRESULT nothingToTranscribe( const char* who, int64_t n )
+			{
+				logInfo( "%s: the speech filter found no speech in %.2f s of audio; nothing to transcribe", who, (double)n / 16000.0 );
+				resultAll.clear();
+				speakers.clear();
+				windowStats.clear();
+				detectedLang = -1;
+				detectedP = 0;
+				return S_OK;
+			}
 
 			using Clock = std::chrono::steady_clock;
 			static double msSince( Clock::time_point t ) { return std::chrono::duration<double, std::milli>( Clock::now() - t ).count(); }
@@ -153,6 +202,7 @@ namespace Whisper
 				int64_t length = 0;			  // iSpectrogram::getLength(): 10 ms frames
 				int64_t nSamples = 0, nChunks = 0;
 				int64_t lastBufferEnd = -1;	  // MelStreamer::lastBufferEnd
+				const float* pcm = nullptr;	  // streamed: the resident samples the windows are taken from (the context's PCM buffer, or its packed speech)
 			};
 			MelSource mel;
 
@@ -260,6 +310,15 @@ namespace Whisper
 				timestampRulesOn = on;
 				return S_OK;
 			}
+			HRESULT setSpeech( const sSpeechFilter* p )
+			{
+				if( !p ) { speechOn = false; return S_OK; }
+				CHECK( optionRules::checkSpeechFilter( "setSpeechFilter", *p ) );
+				speechParams = *p;
+				speechOn = true;
+				return S_OK;
+			}
+			const std::vector<speechRules::Span>& lastSpeechSpans() const { return runSpans; }
 			HRESULT setNoRepeat( int n )
 			{
 				CHECK( optionRules::checkNoRepeat( "setNoRepeatNgram", n ) );
@@ -281,10 +340,18 @@ namespace Whisper
 			// capture.cpp: the reference's capture loop over an iPcmCapture, every piece a runFull of this context on a worker thread
 			HRESULT runCapture( const sFullParams& params, const sCaptureCallbacks& callbacks, const iAudioCapture* reader ) override
 			{
-				return runCaptureLoop( this, gpu, params, callbacks, reader, nullptr, nullptr );
+				return runCapturePieces( params, callbacks, reader, nullptr, nullptr );
 			}
 			HRESULT runCapturePieces( const sFullParams& params, const sCaptureCallbacks& callbacks, const iAudioCapture* reader, pfnCapturePiece pfnPiece, void* pvPiece )
 			{
+				// the speech filter does not apply to a capture: its pieces are fired by the same detector already. Off while the loop runs its runFull calls
+				struct FilterOff
+				{
+					bool& on;
+					const bool was;
+					explicit FilterOff( bool& b ) : on( b ), was( b ) { on = false; }
+					~FilterOff() { on = was; }
+				} filterOff( speechOn );
 				return runCaptureLoop( this, gpu, params, callbacks, reader, pfnPiece, pvPiece );
 			}
 			HRESULT getResults( eResultFlags flags, iTranscribeResult** pp ) const override;
@@ -357,26 +424,52 @@ namespace Whisper
 		HRESULT ContextImpl::runFull( const sFullParams& params, const iAudioBuffer* buffer )
 		{
 			if( !buffer ) return E_POINTER;
+			if( speechOn ) CHECK( speechFilterAccepts( "runFull", params ) );
 			const auto tRun = Clock::now();
 			CHECK( buffer->getTime( mediaTimeOffset ) );
 			const uint32_t n = buffer->countSamples();
 			const float* pcm = buffer->getPcmMono();
-			const int64_t melLen = n / 160;
+			int64_t melLen = n / 160;
 			mel = MelSource{};
 			mel.length = melLen;
 			stereoPcm = buffer->getPcmStereo();	   // a foreign buffer without stereo data: nullptr, NoStereoData
 			stereoFrames = stereoPcm ? n : 0;
+			runSpans.clear();
+			runMap = speechRules::TimeMap{};
 			if( melLen > 0 )
 			{
 				const auto t = Clock::now();
 				CHECK( ensureBuffer( pcmDev, pcmCapacity, (int64_t)n * 4 ) );
-				CHECK( ensureBuffer( melDev, melCapacity, melLen * model->hp.n_mels * 4 ) );
 				CHECK_WH( wh_buffer_upload( gpu, pcmDev, pcm, (int64_t)n * 4 ) );
-				int64_t got = 0;
-				CHECK_WH( wh_mel_spectrogram( gpu, (const float*)pcmDev, n, (float*)melDev, &got ) );
-				CHECK_WH( wh_context_synchronize( gpu ) );
+				// speech only: the spectrogram of the packed speech instead of the recording's; the loop below never learns the difference
+				const float* source = (const float*)pcmDev;
+				int64_t nSource = n;
+				if( speechOn )
+				{
+					CHECK( filterSpeech( n, source, nSource ) );
+					if( !source )
+					{
+						stereoPcm = nullptr;
+						stereoFrames = 0;
+						return nothingToTranscribe( "runFull", n );
+					}
+					mel.length = melLen = nSource / 160;
+				}
+				if( melLen > 0 )
+				{
+					CHECK( ensureBuffer( melDev, melCapacity, melLen * model->hp.n_mels * 4 ) );
+					int64_t got = 0;
+					CHECK_WH( wh_mel_spectrogram( gpu, source, nSource, (float*)melDev, &got ) );
+					CHECK_WH( wh_context_synchronize( gpu ) );
+				}
 				msSpectrogram += msSince( t );
 				nSpectrogram++;
+			}
+			else if( speechOn )
+			{
+				stereoPcm = nullptr;
+				stereoFrames = 0;
+				return nothingToTranscribe( "runFull", n );
 			}
 			if( params.flag( eFullParamsFlags::TokenTimestamps ) ) stamper.begin( pcm, n );
 			const sProgressSink noProgress{ nullptr, nullptr };
@@ -399,6 +492,7 @@ namespace Whisper
 				logError( "eFullParamsFlags.TokenTimestamps flag is not supported in streaming mode" );
 				return E_NOTIMPL;
 			}
+			if( speechOn ) CHECK( speechFilterAccepts( "runStreamed", params ) );
 			iPcmSource* src = nullptr;
 			if( FAILED( const_cast<iAudioReader*>( reader )->QueryInterface( iPcmSource::iid(), (void**)&src ) ) || !src )
 			{
@@ -419,13 +513,40 @@ namespace Whisper
 			stereoFrames = std::min( st.size() / 2, pcm.size() );
 			stereoPcm = stereoFrames ? st.data() : nullptr;
 			HRESULT hr = S_OK;
+			runSpans.clear();
+			runMap = speechRules::TimeMap{};
+			mel.pcm = nullptr;
+			bool noSpeech = false;
 			if( mel.nSamples > 0 )
 			{
 				hr = ensureBuffer( pcmDev, pcmCapacity, mel.nSamples * 4 );
 				if( SUCCEEDED( hr ) ) hr = ensureBuffer( melDev, melCapacity, (int64_t)std::max( CHUNK_FRAMES, 2 * model->hp.n_audio_ctx ) * model->hp.n_mels * 4 );	// encodeWindow asks for up to 2 * n_audio_ctx frames
 				if( SUCCEEDED( hr ) && 0 != wh_buffer_upload( gpu, pcmDev, pcm.data(), mel.nSamples * 4 ) ) hr = E_FAIL;
+				mel.pcm = (const float*)pcmDev;
+				// speech only: the resident PCM is packed once, the windows are taken from the packed buffer and progress counts its frames
+				if( SUCCEEDED( hr ) && speechOn )
+				{
+					const float* packed = nullptr;
+					int64_t nPacked = 0;
+					hr = filterSpeech( mel.nSamples, packed, nPacked );
+					if( SUCCEEDED( hr ) )
+					{
+						noSpeech = !packed;
+						mel.pcm = packed;
+						mel.nSamples = nPacked;
+						mel.length = nPacked / 160;
+						mel.nChunks = ( nPacked + 159 ) / 160;
+					}
+				}
 			}
-			if( SUCCEEDED( hr ) ) hr = runFullImpl( params, progress );
+			else if( speechOn ) noSpeech = true;
+			if( SUCCEEDED( hr ) && noSpeech )
+			{
+				stereoPcm = nullptr;
+				stereoFrames = 0;
+				hr = nothingToTranscribe( "runStreamed", (int64_t)pcm.size() );
+			}
+			else if( SUCCEEDED( hr ) ) hr = runFullImpl( params, progress );
 			src->Release();
 			msRun += msSince( tRun );
 			nRuns++;
@@ -447,7 +568,7 @@ namespace Whisper
 			if( i1 <= i0 ) return E_BOUNDS;
 			const auto t = Clock::now();
 			const bool reuse = mel.lastBufferEnd == i1;
-			CHECK_WH( wh_mel_spectrogram_window( gpu, (const float*)pcmDev, mel.nSamples, i0, i1 - i0, mel.nChunks, reuse ? 1 : 0, (float*)melDev ) );
+			CHECK_WH( wh_mel_spectrogram_window( gpu, mel.pcm, mel.nSamples, i0, i1 - i0, mel.nChunks, reuse ? 1 : 0, (float*)melDev ) );
 			if( !reuse ) mel.lastBufferEnd = i1;
 			msSpectrogram += msSince( t );	   // enqueue time only: the transform overlaps nothing else and is < 1 % of a window
 			nSpectrogram++;
@@ -938,6 +1059,8 @@ namespace Whisper
 				}
 			} aligner( active, vocab, mel.length, audioCtx > 0 ? audioCtx : hp.n_audio_ctx );
 			if( params.flag( eFullParamsFlags::AlignTokens ) ) run.setAligner( &aligner );
+			// speech only: the spectrogram is that of the packed speech; what the run reports is on the recording's clock
+			if( !runMap.empty() ) run.setTimeMap( &runMap );
 			// decoding fallback: whatever path leaves this function, the context is back at the greedy sampler and gathers nothing
 			struct SamplingGuard
 			{
@@ -1277,6 +1400,8 @@ namespace Whisper
 	static const bool g_noRepeatInstalled = ( g_batchNoRepeat = &wh_context_set_no_repeat, true );
 	// ... and to the scorer of given transcripts (scoreRequest.h)
 	static const bool g_scorerInstalled = ( g_batchScorer = &wh_score_tokens, true );
+	// ... and to the speech filter of a newly admitted stream (batchSpeech.h)
+	static const bool g_speechPackerInstalled = ( g_batchSpeechPacker = &wh_context_speech_filter, true );
 
 	HRESULT createContextImpl( const std::shared_ptr<LoadedModel>& model, iModel* owner, iContext** pp )
 	{
@@ -1327,6 +1452,24 @@ namespace Whisper
 	{
 		return optionRules::forward<ContextImpl>( context, "setNoRepeatNgram", NOT_A_CONTEXT, "a batch runner takes setBatchNoRepeatNgram",
 			[ = ]( ContextImpl& c ) { return c.setNoRepeat( n ); } );
+	}
+	HRESULT setSpeechFilter( iContext* context, const sSpeechFilter* params )
+	{
+		return optionRules::forward<ContextImpl>( context, "setSpeechFilter", NOT_A_CONTEXT, "a batch runner takes setBatchSpeechFilter",
+			[ = ]( ContextImpl& c ) { return c.setSpeech( params ); } );
+	}
+	HRESULT getSpeechSpans( const iContext* context, sSpeechSpan* spans, uint32_t* count )
+	{
+		if( !context || !count ) return E_POINTER;
+		const ContextImpl* const c = dynamic_cast<const ContextImpl*>( context );
+		if( !c ) return E_INVALIDARG;
+		const std::vector<speechRules::Span>& all = c->lastSpeechSpans();
+		const uint32_t cap = *count;
+		*count = (uint32_t)all.size();
+		if( !spans ) return S_OK;
+		if( cap < all.size() ) return E_BOUNDS;
+		for( size_t i = 0; i < all.size(); i++ ) spans[ i ] = sSpeechSpan{ all[ i ].a, all[ i ].b };
+		return S_OK;
 	}
 	HRESULT contextScoreClip( iContext* context, const float* pcm, int64_t nSamples, const int32_t* tokens, int32_t len, int32_t firstScored, wh_token_score* recs, int32_t* frames )
 	{
