@@ -251,6 +251,20 @@ def test_device_loop_equals_the_emulation(looping, batch, temperature):
     ctx.close()
 
 
+def _set_four(ctx, off, sp, boost, n):
+    """Turns the four filters on with a set and a phrase chosen from `off`, the records of the unfiltered run; returns the two"""
+    emitted = {int(t) for t in off["id"].ravel()}
+    text = sorted(t for t in emitted if t < sp["eot"])
+    suppressed = text[::3]                                                       # a third of the text tokens the unfiltered run emits
+    # two tokens the unfiltered run does not emit, candidates of the layout's second and third text position
+    phrase = [next((t for t in range(base, base + 4) if t not in emitted), base) for base in (2000 + 64 * 2, 2000 + 64 * 3)]
+    ctx.set_suppress(suppressed)
+    ctx.set_timestamp_rules(True)
+    ctx.set_boost([phrase], boost)
+    ctx.set_no_repeat(n)
+    return suppressed, phrase
+
+
 @pytest.mark.parametrize("temperature", [0.0, 0.8])
 def test_all_four_filters_at_once(looping, temperature):
     """A suppressed set, the timestamp rules, a boosted phrase and n = 2 on one context, 5 rows, 20 steps: the records of the emulation that applies the four
@@ -264,15 +278,7 @@ def test_all_four_filters_at_once(looping, temperature):
     if temperature > 0:
         ctx.set_sampling(temperature, seed, nonce)
     off = T._window(ctx, prompt, n_steps)
-    emitted = {int(t) for t in off["id"].ravel()}
-    text = sorted(t for t in emitted if t < sp["eot"])
-    suppressed = text[::3]                                                       # a third of the text tokens the unfiltered run emits
-    # two tokens the unfiltered run does not emit, candidates of the layout's second and third text position
-    phrase = [next((t for t in range(base, base + 4) if t not in emitted), base) for base in (2000 + 64 * 2, 2000 + 64 * 3)]
-    ctx.set_suppress(suppressed)
-    ctx.set_timestamp_rules(True)
-    ctx.set_boost([phrase], boost)
-    ctx.set_no_repeat(n)
+    suppressed, phrase = _set_four(ctx, off, sp, boost, n)
     on = T._window(ctx, prompt, n_steps)
     assert same_records(T._window(ctx, prompt, n_steps, chunk=4), on)
 
@@ -289,6 +295,43 @@ def test_all_four_filters_at_once(looping, temperature):
         assert R.violations(on["id"][:, b], n, sp["eot"]) == [] and TS.violations(on["id"][:, b], sp["eot"], sp["beg"], V) == [], b
     assert not ({int(t) for t in on["id"].ravel()} & set(suppressed)) and not np.array_equal(on["id"], off["id"])
     ctx.close()
+
+
+def test_capture_inside_continue_preserves_every_filter_state(looping):
+    """WARM_PRESERVE with all four filters live: the window of test_all_four_filters_at_once (greedy) started WITHOUT steps captures nothing, so the 20 steps of
+    the continue capture over the window's live state. The warm-up step appends a token to every history, moves every boost state and folds a token into every
+    record, and the restore must undo it. The records equal, bit for bit, those of a context that enqueued the window in one piece -- which that test holds
+    against the emulation -- and differ from the unfiltered run's. Behind the first sample, a timestamp, a token folded or appended twice shows in no mask, so the
+    same is asked in mid-window: the first `split` steps run eagerly under WH_FLAG_NO_GRAPH and capture nothing, the flag goes, and the continue captures over
+    records and histories that hold text. Tried with a restore that skips one buffer: without the counts the window differs at split 6 (the fed token completes
+    the bigram that bans the next sample), without the records at split 14 (the fed token closes a pair). A history that is not restored holds what the first
+    replayed step writes again, and moving a state twice over one token of the single two-token phrase offers the same tokens: neither can show here."""
+    c, sp = looping, looping.sp
+    batch, n, n_steps, boost = 5, 2, 20, 8.0
+    prompt = T._prompts4(sp, batch)
+    whole = binding.HipContext(c.model, batch)
+    whole.encode(T._mels(batch))
+    off = T._window(whole, prompt, n_steps)
+    _set_four(whole, off, sp, boost, n)
+    want = T._window(whole, prompt, n_steps)
+    whole.close()
+    print("row 0: off %s | on %s" % (off["id"][:, 0].tolist(), want["id"][:, 0].tolist()))
+    assert not np.array_equal(want["id"], off["id"])
+    for split in (0, 6, 14):
+        ctx = binding.HipContext(c.model, batch)
+        ctx.encode(T._mels(batch))
+        _set_four(ctx, off, sp, boost, n)
+        if split:
+            ctx.set_flags(binding.WH_FLAG_NO_GRAPH)
+        ctx.decode_window_start(prompt, split)
+        ctx.set_flags(0)
+        assert ctx.step_captures() == 0
+        ctx.decode_window_continue(n_steps - split)
+        assert ctx.step_captures() == 1
+        got = ctx.decode_window_fetch_data(0, 1 + n_steps)
+        ctx.decode_window_finish()
+        ctx.close()
+        assert same_records(got, want), split
 
 
 def test_ragged_per_row_batch_equals_the_emulation(looping):

@@ -5,7 +5,8 @@ WH_PROBES define): keep it in step when build.py changes.
     python tools/kernel_resources.py elementwise.hip sample.hip beam.hip [--root OTHER_CHECKOUT] [--against OTHER_CHECKOUT]
 
 --against prints the two trees side by side, one row per kernel, and exits 1 when a kernel differs in one of the six columns (VGPRs, AGPRs, scratch bytes
-per lane, VGPR spills, occupancy, LDS bytes); SGPR spills are shown and not compared."""
+per lane, VGPR spills, occupancy, LDS bytes); SGPR spills are shown and not compared. A unit that one of the trees does not have contributes no kernels
+there, so kernels that moved between units are compared by name."""
 import argparse
 import os
 import re
@@ -36,6 +37,8 @@ def short_name(mangled):
 def resources(root, units):
     out = {}
     for u in units:
+        if not os.path.exists(os.path.join(root, "whisper_amd", "csrc", u)):
+            continue                        # a unit one tree does not have (a kernel moved between units): no kernels from it
         cmd = [B.HIPCC, "--offload-arch=" + B.ARCH, "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wno-unused-result"] + B.EXTRA_FLAGS.get(u, []) + \
               ["-I" + os.path.join(root, "include"), "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(root, "whisper_amd", "csrc", u), "-o", os.devnull]
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)

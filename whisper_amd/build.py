@@ -23,10 +23,10 @@ CLI_BIN = os.path.join(LIB_DIR, "whisper-main")
 
 # the runtime behind the C ABI, one unit per responsibility; runtime.h holds what they share (host code: the kernel units do not include it)
 RUNTIME_SOURCES = ["options.hip", "model.hip", "comm.hip", "context.hip", "encode.hip", "exact_graphs.hip", "step_graph.hip", "decode.hip", "beam.hip", "ops_debug.hip"]
-# resample.hip and vad.hip keep their kernels next to the entry points that own their tables, capture.hip next to the wh_capture it fills, dequant.hip next to wh_dequantize, align.hip next to wh_align_tokens, speech.hip next to wh_speech_pack; boost.hip is the host half of phrase boosting: kernel units that do include runtime.h
+# resample.hip and vad.hip keep their kernels next to the entry points that own their tables, capture.hip next to the wh_capture it fills, dequant.hip next to wh_dequantize, align.hip next to wh_align_tokens, speech.hip next to wh_speech_pack, filters.hip next to the owner of the decode-step logit filters; boost.hip is the host half of phrase boosting: kernel units that do include runtime.h
 HIP_SOURCES = ["gemm_persistent.hip", "gemm_decode.hip", "gemm_tiled.hip", "attn_dec.hip", "decode1.hip", "attn_enc.hip", "gemm.hip", "elementwise.hip", "sample.hip", "mel.hip", "exact.hip", "resample.hip", "vad.hip", "capture.hip", "dequant.hip",
-               "align.hip", "boost.hip", "speech.hip"] + RUNTIME_SOURCES
-RUNTIME_H_USERS = RUNTIME_SOURCES + ["resample.hip", "vad.hip", "capture.hip", "dequant.hip", "align.hip", "boost.hip", "speech.hip"]
+               "align.hip", "boost.hip", "speech.hip", "filters.hip"] + RUNTIME_SOURCES
+RUNTIME_H_USERS = RUNTIME_SOURCES + ["resample.hip", "vad.hip", "capture.hip", "dequant.hip", "align.hip", "boost.hip", "speech.hip", "filters.hip"]
 # speech.hip applies the host's decision loop and span rules between its two kernels: the two header-only files that state them
 EXTRA_DEPS = {"speech.hip": [os.path.join(HOST, "vad.h"), os.path.join(HOST, "speechSpans.h"), os.path.join(ROOT, "include", "whisperApi.h")]}
 # exact.hip restates the reference CPU path's summation order: a fused multiply-add only where the source says fma()

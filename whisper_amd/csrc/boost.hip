@@ -1,5 +1,5 @@
 // Phrase boosting (DESIGN.md section 7 "Phrase boosting"): the host half. An Aho-Corasick automaton over token ids, compiled into the flat tables that
-// boostLogitsKernel (sample.hip) reads, and the host twin of one step of that kernel. Host code only: both entries work without a device.
+// boostLogitsKernel (filters.hip) reads, and the host twin of one step of that kernel. Host code only: both entries work without a device.
 //
 // Tables, int32 (BoostTables of kernels.h states the offsets):
 //   [0] nodes  [1] entries  [2] the bits of the boost, FP32  [3] 0
@@ -23,7 +23,7 @@ namespace wh
 
 		int refuse( const char* text ) { setError( text ); return WH_E_INVALIDARG; }
 
-		// the first entry of tok[ lo, hi ) that is not below t (hi when there is none). The device runs the same search (boostFind of sample.hip)
+		// the first entry of tok[ lo, hi ) that is not below t (hi when there is none). The device runs the same search (boostFind of filters.hip)
 		int findEntry( const int32_t* tok, int lo, int hi, int32_t t )
 		{
 			while( lo < hi )

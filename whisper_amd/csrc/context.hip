@@ -288,10 +288,7 @@ int wh_context_set_audio_ctx( wh_context* c, int audioCtx )
 int wh_context_set_flags( wh_context* c, uint32_t flags, int parityThreads )
 {
 	if( !c ) return WH_E_INVALIDARG;
-	if( ( flags & WH_FLAG_PARITY_EXACT ) && c->suppressCount > 0 ) { setError( "context_set_flags: WH_FLAG_PARITY_EXACT is not available while wh_context_set_suppress holds a set" ); return WH_E_INVALIDARG; }
-	if( ( flags & WH_FLAG_PARITY_EXACT ) && c->boostOn ) { setError( "context_set_flags: WH_FLAG_PARITY_EXACT is not available while wh_context_set_boost holds a set" ); return WH_E_INVALIDARG; }
-	if( ( flags & WH_FLAG_PARITY_EXACT ) && c->noRepeatN ) { setError( "context_set_flags: WH_FLAG_PARITY_EXACT is not available while wh_context_set_no_repeat is on" ); return WH_E_INVALIDARG; }
-	if( ( flags & WH_FLAG_PARITY_EXACT ) && c->tsRules ) { setError( "context_set_flags: WH_FLAG_PARITY_EXACT is not available while wh_context_set_timestamp_rules is on" ); return WH_E_INVALIDARG; }
+	WH_CHECK( filtersAllowFlags( c, flags ) );
 	c->flags = flags;
 	// WH_FLAG_PARITY_EXACT with 0 threads: the decoder's P.V as ONE correctly rounded sum per output (double accumulation) instead of the reference's
 	// FP16 accumulation -- the thread-count-independent value every thread count of the reference approximates

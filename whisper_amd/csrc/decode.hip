@@ -1,6 +1,5 @@
 // The decoder graph, host-stepped decoding (wh_decode), language detection, the sampler step, the greedy loop and its window.
 #include "runtime.h"
-#include <algorithm>
 
 static int attnDecP( wh_context* c, const DecAttnArgs& a, int keysHint = -1 )
 {
@@ -18,52 +17,6 @@ static int attnDecP( wh_context* c, const DecAttnArgs& a, int keysHint = -1 )
 		flops += 2.0 * a.batch * a.nTok * d * d;
 	}
 	return profiled( c, a.causal ? KC_ATTN_DEC : KC_ATTN_DEC_CROSS, flops, bytes, [ & ]() { return launchAttentionDec( a, c->stream ); } );
-}
-
-// The ONE place suppressed tokens take effect (wh_context_set_suppress): behind the launch that finishes c->logits, -inf over the set's columns of every row. Every
-// consumer -- wh_decode's softmax, the greedy, tempered and per-row samplers, the beam step, the no-speech gather -- reads the filtered row and none of them changes.
-// Accounted under the sampler's class: timingsPrint's sections are the reference's.
-static int suppressLogits( wh_context* c, int batch )
-{
-	if( c->suppressCount <= 0 || c->suppressBypass ) return 0;
-	const int nVocab = c->m->hp.n_vocab, cap = specialIds( c->m->hp ).sot - 1;
-	return profiled( c, KC_SAMPLE, 0.0, 4.0 * batch * c->suppressCount,
-		[ & ]() { return launchSuppressLogits( c->logits, batch, nVocab, c->suppress + 1, c->suppress, 0, cap, c->stream ); } );
-}
-
-// Timestamp rules (wh_context_set_timestamp_rules): the filter whose mask depends on what each row has sampled. Only the device-side loop calls it, right behind
-// decodeGraph -- so behind the suppress launch -- and in front of the sampler: reset 1 behind a window's prompt step (the records become empty, nothing is masked),
-// 0 in every step (the fed token c->tokensDev[ row ], the previous step's sample, is folded in and the row masked). The replayed step reads device memory only.
-static int timestampRules( wh_context* c, int batch, int reset )
-{
-	if( !c->tsRules ) return 0;
-	const wh_hparams& hp = c->m->hp;
-	const SpecialIds sp = specialIds( hp );
-	return profiled( c, KC_SAMPLE, 0.0, 4.0 * batch * hp.n_vocab,
-		[ & ]() { return launchTimestampRules( c->logits, batch, hp.n_vocab, sp.sot - 1, sp.beg, c->tokensDev, reset, c->tsRecords, c->stream ); } );
-}
-
-// Phrase boosting (wh_context_set_boost): the filter whose bonus depends on a string-matching state per row. Only the device-side loop calls it, behind the
-// timestamp rules -- so what they and the suppress launch made -inf stays -inf -- and in front of the sampler: reset 1 behind a window's prompt step (every state
-// becomes the root and the root's offers are boosted: the first sample counts), 0 in every step (the state moves over c->tokensDev[ row ], the previous step's sample).
-static int boostLogits( wh_context* c, int batch, int reset )
-{
-	if( !c->boostOn ) return 0;
-	const wh_hparams& hp = c->m->hp;
-	return profiled( c, KC_SAMPLE, 0.0, 8.0 * batch * BOOST_MAX_PHRASES,
-		[ & ]() { return launchBoostLogits( c->logits, batch, hp.n_vocab, specialIds( hp ).sot - 1, c->boostTables, BOOST_TABLE_INTS, c->tokensDev, reset, c->boostStates, c->stream ); } );
-}
-
-// No-repeat n-grams (wh_context_set_no_repeat): the filter whose mask depends on everything each row has sampled in its window. Only the device-side loop calls
-// it, behind the boost and in front of the sampler -- the order among the filters does not change the row: this one and the two masks only write -inf, and
-// -inf + boost stays -inf. reset 1 behind a window's prompt step (the histories become empty, nothing is masked: the prompt does not count), 0 in every step
-// (c->tokensDev[ row ], the previous step's sample, is appended and the row masked), 2 in wh_decode_greedy. n is an argument of the kernel: stepKey holds it.
-static int noRepeat( wh_context* c, int batch, int reset )
-{
-	if( !c->noRepeatN ) return 0;
-	const wh_hparams& hp = c->m->hp;
-	return profiled( c, KC_SAMPLE, 0.0, 4.0 * batch * hp.n_text_ctx,
-		[ & ]() { return launchNoRepeat( c->logits, batch, hp.n_vocab, specialIds( hp ).sot - 1, c->noRepeatN, c->tokensDev, reset, c->nrnHistory, c->nrnCounts, hp.n_text_ctx, c->stream ); } );
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -241,7 +194,7 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 			a.pro = 1; a.g.lnX = c->dx; a.g.lnW = m->at<float>( L.decLnW ); a.g.lnB = m->at<float>( L.decLnB );
 			WH_CHECK( smallGemv( a ) );
 		}
-		return suppressLogits( c, batch );
+		return filterLogits( c, batch );
 	}
 
 	for( int il = 0; il < hp.n_text_layer; il++ )
@@ -381,7 +334,7 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 		else
 			WH_CHECK( product( g, nullptr, nullptr ) );
 	}
-	return suppressLogits( c, batch );
+	return filterLogits( c, batch );
 }
 
 // Token ids index the embedding table: anything outside [0, n_vocab) is rejected at the boundary (the reference's addRows
@@ -471,9 +424,9 @@ int wh_lang_detect( wh_context* c, int batch, float* langP, int32_t* best )
 	else
 	{
 		// detection is the model's own distribution at [sot]: the pass runs unfiltered whatever set the context holds (set around the call like AlignHook)
-		c->suppressBypass = true;
+		bypassFilterLogits( c, true );
 		const int rcGraph = decodeGraph( c, seqs, 1, 0, false );
-		c->suppressBypass = false;
+		bypassFilterLogits( c, false );
 		WH_CHECK( rcGraph );
 		WH_CHECK( profiled( c, KC_SOFTMAX, 10.0 * batch * hp.n_vocab, 4.0 * batch * hp.n_vocab,
 			[ & ]() { return launchLangProbs( c->logits, rowStride, batch, hp.n_vocab, sot, nLang, c->langP, c->langBest, st ); } ) );
@@ -545,49 +498,28 @@ static int sampleStep( wh_context* c, int batch, hipStream_t st )
 static int greedyStep( wh_context* c, int batch )
 {
 	WH_CHECK( decodeGraph( c, batch, 1, 0, true ) );
-	WH_CHECK( timestampRules( c, batch, 0 ) );
-	WH_CHECK( boostLogits( c, batch, 0 ) );
-	WH_CHECK( noRepeat( c, batch, 0 ) );
+	WH_CHECK( filterLoopRows( c, batch, FILTER_STEP ) );
 	WH_CHECK( sampleStep( c, batch, c->stream ) );
 	return launchAdvanceState( c->state, c->seqPos, batch, c->stream );
 }
 // Everything in device memory that a greedyStep mutates and a window in progress still needs (obtainStepGraph's WARM_PRESERVE; the stream is idle): the sampler
-// state, the positions, the fed tokens, -- when the rules are on -- the timestamp records, -- when a set of phrases is held -- the boost states and -- when no-repeat n-grams are on -- the histories and their counts. Per-row device state a later feature adds to the step joins HERE.
+// state, the positions, the fed tokens, and what the filters keep per row, which is their owner's to list (filters.hip).
 // (The cache row and the sample the warm-up writes are rewritten by the first real step.)
 int wh::saveLoopState( wh_context* c, int batch, LoopState& s )
 {
 	s.pos.resize( (size_t)batch );
 	s.tok.resize( (size_t)batch );
-	s.rec.resize( c->tsRules ? (size_t)batch : 0 );
 	WH_HIP( hipMemcpy( &s.state, c->state, sizeof( DecodeState ), hipMemcpyDeviceToHost ) );
 	WH_HIP( hipMemcpy( s.pos.data(), c->seqPos, sizeof( int32_t ) * batch, hipMemcpyDeviceToHost ) );
 	WH_HIP( hipMemcpy( s.tok.data(), c->tokensDev, sizeof( int32_t ) * batch, hipMemcpyDeviceToHost ) );
-	if( c->tsRules ) WH_HIP( hipMemcpy( s.rec.data(), c->tsRecords, sizeof( TimestampRecord ) * batch, hipMemcpyDeviceToHost ) );
-	s.boost.resize( c->boostOn ? (size_t)batch : 0 );
-	if( c->boostOn ) WH_HIP( hipMemcpy( s.boost.data(), c->boostStates, sizeof( int32_t ) * batch, hipMemcpyDeviceToHost ) );
-	const size_t nrnInts = c->noRepeatN ? (size_t)batch * c->m->hp.n_text_ctx : 0;
-	s.nrnHistory.resize( nrnInts );
-	s.nrnCounts.resize( c->noRepeatN ? (size_t)batch : 0 );
-	if( c->noRepeatN )
-	{
-		WH_HIP( hipMemcpy( s.nrnHistory.data(), c->nrnHistory, sizeof( int32_t ) * nrnInts, hipMemcpyDeviceToHost ) );
-		WH_HIP( hipMemcpy( s.nrnCounts.data(), c->nrnCounts, sizeof( int32_t ) * batch, hipMemcpyDeviceToHost ) );
-	}
-	return 0;
+	return saveFilterState( c, batch, s.filters );
 }
 int wh::restoreLoopState( wh_context* c, int batch, const LoopState& s )
 {
 	WH_HIP( hipMemcpy( c->state, &s.state, sizeof( DecodeState ), hipMemcpyHostToDevice ) );
 	WH_HIP( hipMemcpy( c->seqPos, s.pos.data(), sizeof( int32_t ) * batch, hipMemcpyHostToDevice ) );
 	WH_HIP( hipMemcpy( c->tokensDev, s.tok.data(), sizeof( int32_t ) * batch, hipMemcpyHostToDevice ) );
-	if( c->tsRules ) WH_HIP( hipMemcpy( c->tsRecords, s.rec.data(), sizeof( TimestampRecord ) * batch, hipMemcpyHostToDevice ) );
-	if( c->boostOn ) WH_HIP( hipMemcpy( c->boostStates, s.boost.data(), sizeof( int32_t ) * batch, hipMemcpyHostToDevice ) );
-	if( c->noRepeatN )
-	{
-		WH_HIP( hipMemcpy( c->nrnHistory, s.nrnHistory.data(), sizeof( int32_t ) * s.nrnHistory.size(), hipMemcpyHostToDevice ) );
-		WH_HIP( hipMemcpy( c->nrnCounts, s.nrnCounts.data(), sizeof( int32_t ) * batch, hipMemcpyHostToDevice ) );
-	}
-	return 0;
+	return restoreFilterState( c, batch, s.filters );
 }
 
 extern "C" {
@@ -612,12 +544,8 @@ int wh_decode_greedy( wh_context* c, int batch, const int32_t* firstTokens, int 
 	hipGraphExec_t exec = nullptr;
 	// nPast may be above 0 over the cache rows of an earlier wh_decode, and the state is uploaded: the warm-up must preserve both
 	if( stepsReplayable( c ) ) WH_CHECK( obtainStepGraph( c, batch, stepKey( c, 0 ), WARM_PRESERVE, nullptr, step, exec ) );
-	// the first token is the caller's, not a sample: the records are armed, the history starts at this call's first sample
-	WH_CHECK( timestampRules( c, batch, 2 ) );
-	// the same for the phrases' history: every state becomes -1, armed. No launch: there is no row to boost yet, the first step boosts its own
-	if( c->boostOn ) WH_HIP( hipMemsetAsync( c->boostStates, 0xFF, sizeof( int32_t ) * (size_t)batch, st ) );
-	// ... and for the n-grams' history: armed, it starts empty at this call's first sample
-	WH_CHECK( noRepeat( c, batch, 2 ) );
+	// the first token is the caller's, not a sample: the filters' histories are armed and start at this call's first sample
+	WH_CHECK( filterLoopRows( c, batch, FILTER_ARM ) );
 	WH_CHECK( enqueueSteps( c, exec, nSteps, nPast + 1, step ) );
 	c->lastBatch = batch;
 	static_assert( sizeof( wh_token_data ) == sizeof( TokenData ), "token data layout" );
@@ -692,9 +620,7 @@ static int windowStart( wh_context* c, int batch, const int32_t* promptTokens, c
 	c->raggedLastPos = nullptr;
 	WH_CHECK( rcGraph );
 	{
-		WH_CHECK( timestampRules( c, batch, 1 ) );	 // a new window: no record survives into it, and the first sample is unfiltered
-		WH_CHECK( boostLogits( c, batch, 1 ) );		 // ... but boosted: the history is empty and the root's offers count for the first sample
-		WH_CHECK( noRepeat( c, batch, 1 ) );		 // the n-grams' history starts at this sample: the prompt does not count, nothing is masked yet
+		WH_CHECK( filterLoopRows( c, batch, FILTER_WINDOW ) );	 // a new window: no history survives into it, the prompt does not count, the first sample is unmasked and boosted from the root
 		WH_CHECK( sampleStep( c, batch, st ) );
 		WH_CHECK( launchAdvanceState( c->state, c->seqPos, batch, st ) );
 		c->noSpeechRows = 0;
@@ -881,107 +807,6 @@ int wh_context_set_sampling_rows( wh_context* c, int rows, const float* temperat
 	WH_HIP( hipMemcpyAsync( c->sampleRows, c->sampleRowsPin, sizeof( SampleRowParams ) * (size_t)c->maxSeq, hipMemcpyHostToDevice, c->stream ) );
 	WH_HIP( hipEventRecord( c->sampleRowsEv, c->stream ) );
 	c->sampleRowsOn = rows;
-	return 0;
-}
-
-// Suppressed tokens. The sorted unique set and its count go to device memory behind what the stream holds; the captured steps of every kind are
-// keyed on "a set is held" only.
-int wh_context_set_suppress( wh_context* c, const int32_t* ids, int count )
-{
-	if( !c || count < 0 || ( count > 0 && !ids ) ) { setError( "context_set_suppress: null context, a negative count or null ids" ); return WH_E_INVALIDARG; }
-	const int eot = specialIds( c->m->hp ).sot - 1;
-	for( int i = 0; i < count; i++ )
-		if( ids[ i ] < 0 || ids[ i ] >= eot )
-		{
-			char buf[ 160 ];
-			snprintf( buf, sizeof( buf ), "context_set_suppress: id %d at index %d is outside [0, %d): only text tokens can be suppressed", (int)ids[ i ], i, eot );
-			setError( buf );
-			return WH_E_INVALIDARG;
-		}
-	if( count > 0 && ( c->flags & WH_FLAG_PARITY_EXACT ) ) { setError( "context_set_suppress: not available under WH_FLAG_PARITY_EXACT" ); return WH_E_INVALIDARG; }
-	if( count == 0 && !c->suppress ) return 0;
-	WH_BIND( c->m );
-	std::vector<int32_t> up( 1 );
-	up.insert( up.end(), ids, ids + count );
-	std::sort( up.begin() + 1, up.end() );
-	up.erase( std::unique( up.begin() + 1, up.end() ), up.end() );
-	up[ 0 ] = (int32_t)up.size() - 1;
-	if( !c->suppress ) WH_CHECK( c->alloc( c->suppress, (int64_t)eot + 1, wh_context::MUST_BE_ZERO, "suppress" ) );
-	WH_HIP( hipMemcpyAsync( c->suppress, up.data(), sizeof( int32_t ) * up.size(), hipMemcpyHostToDevice, c->stream ) );
-	WH_HIP( hipStreamSynchronize( c->stream ) );	 // `up` is this call's
-	c->suppressCount = up[ 0 ];
-	return 0;
-}
-
-// Timestamp rules. The records are allocated once, before any capture; the captured graphs are keyed on the mode. The call waits for the
-// stream, so a chunk queued earlier has run under the mode it was enqueued in before the flag changes.
-int wh_context_set_timestamp_rules( wh_context* c, int on )
-{
-	if( !c ) { setError( "context_set_timestamp_rules: null context" ); return WH_E_INVALIDARG; }
-	if( !on )
-	{
-		if( c->tsRules ) { WH_BIND( c->m ); WH_HIP( hipStreamSynchronize( c->stream ) ); }
-		c->tsRules = false;
-		return 0;
-	}
-	if( c->hyp != 1 ) { setError( "context_set_timestamp_rules: not available on a hypothesis-group context (the records do not follow the beam's reorder)" ); return WH_E_INVALIDARG; }
-	if( c->flags & WH_FLAG_PARITY_EXACT ) { setError( "context_set_timestamp_rules: not available under WH_FLAG_PARITY_EXACT" ); return WH_E_INVALIDARG; }
-	WH_BIND( c->m );
-	if( !c->tsRecords ) WH_CHECK( c->alloc( c->tsRecords, (int64_t)c->maxSeq, wh_context::MUST_BE_ZERO, "tsRecords" ) );
-	WH_HIP( hipStreamSynchronize( c->stream ) );
-	c->tsRules = true;
-	return 0;
-}
-
-// Phrase boosting. The set is compiled on the host (boost.hip) and uploaded behind what the stream holds; the tables and the states are
-// allocated once, before any capture, and the captured graphs are keyed on "a set is held". The call waits for the stream, so a chunk queued earlier has run
-// under the set it was enqueued with.
-int wh_context_set_boost( wh_context* c, const int32_t* tokens, const int32_t* lens, int count, int nMax, float boost )
-{
-	if( !c || count < 0 ) { setError( "context_set_boost: null context or a negative count" ); return WH_E_INVALIDARG; }
-	if( count == 0 )
-	{
-		if( c->boostOn ) { WH_BIND( c->m ); WH_HIP( hipStreamSynchronize( c->stream ) ); }
-		c->boostOn = false;
-		return 0;
-	}
-	if( c->hyp != 1 ) { setError( "context_set_boost: not available on a hypothesis-group context (the states do not follow the beam's reorder)" ); return WH_E_INVALIDARG; }
-	if( c->flags & WH_FLAG_PARITY_EXACT ) { setError( "context_set_boost: not available under WH_FLAG_PARITY_EXACT" ); return WH_E_INVALIDARG; }
-	const wh_hparams& hp = c->m->hp;
-	int64_t nInts = 0;
-	WH_CHECK( wh_boost_compile( tokens, lens, count, nMax, specialIds( hp ).sot - 1, hp.n_vocab, boost, nullptr, 0, &nInts ) );
-	std::vector<int32_t> up( (size_t)nInts );
-	WH_CHECK( wh_boost_compile( tokens, lens, count, nMax, specialIds( hp ).sot - 1, hp.n_vocab, boost, up.data(), nInts, &nInts ) );
-	WH_BIND( c->m );
-	if( !c->boostTables ) WH_CHECK( c->alloc( c->boostTables, (int64_t)BOOST_TABLE_INTS, wh_context::MUST_BE_ZERO, "boostTables" ) );
-	if( !c->boostStates ) WH_CHECK( c->alloc( c->boostStates, (int64_t)c->maxSeq, wh_context::MUST_BE_ZERO, "boostStates" ) );
-	WH_HIP( hipMemcpyAsync( c->boostTables, up.data(), sizeof( int32_t ) * up.size(), hipMemcpyHostToDevice, c->stream ) );
-	WH_HIP( hipStreamSynchronize( c->stream ) );	 // `up` is this call's
-	c->boostOn = true;
-	return 0;
-}
-
-// No-repeat n-grams. The histories and counts are allocated once, before any capture; the captured graphs are keyed on n, which is an
-// argument of the kernel. The call waits for the stream, so a chunk queued earlier has run under the n it was enqueued with before the value changes.
-int wh_context_set_no_repeat( wh_context* c, int n )
-{
-	if( !c ) { setError( "context_set_no_repeat: null context" ); return WH_E_INVALIDARG; }
-	if( n < 0 || n > NRN_MAX_N ) { setError( "context_set_no_repeat: n outside 0 .. 8" ); return WH_E_INVALIDARG; }
-	if( n == c->noRepeatN ) return 0;
-	if( n == 0 )
-	{
-		WH_BIND( c->m );
-		WH_HIP( hipStreamSynchronize( c->stream ) );
-		c->noRepeatN = 0;
-		return 0;
-	}
-	if( c->hyp != 1 ) { setError( "context_set_no_repeat: not available on a hypothesis-group context (the histories do not follow the beam's reorder)" ); return WH_E_INVALIDARG; }
-	if( c->flags & WH_FLAG_PARITY_EXACT ) { setError( "context_set_no_repeat: not available under WH_FLAG_PARITY_EXACT" ); return WH_E_INVALIDARG; }
-	WH_BIND( c->m );
-	if( !c->nrnHistory ) WH_CHECK( c->alloc( c->nrnHistory, (int64_t)c->maxSeq * c->m->hp.n_text_ctx, wh_context::MUST_BE_ZERO, "nrnHistory" ) );
-	if( !c->nrnCounts ) WH_CHECK( c->alloc( c->nrnCounts, (int64_t)c->maxSeq, wh_context::MUST_BE_ZERO, "nrnCounts" ) );
-	WH_HIP( hipStreamSynchronize( c->stream ) );
-	c->noRepeatN = n;
 	return 0;
 }
 

@@ -477,6 +477,12 @@ namespace wh
 	int launchPhiloxU( unsigned long long seed, unsigned nonce, int rows, const int* positions, double* uOut, hipStream_t stream );
 	// out[ row ] = p[ tokenSolm ] of the row the sampler left in `probs`; spreadScratch non-null: the row holds the spread sampler's unnormalised e and is
 	// normalised by the sum of its slice records (what sampleSpreadFinal multiplies by)
+	int launchNoSpeechGather( const float* probs, const void* spreadScratch, int rows, int nVocab, int tokenSolm, float* out, hipStream_t stream );
+	// Prompt steps whose sequences differ in length (rows right-padded to nTok tokens): the normalised row of sequence b's LAST real
+	// token, lastPos[b] (device), is copied over its row nTok - 1, where the vocabulary product of a prompt step reads. In place, f16 rows.
+	int launchGatherLastRows( f16* xn, const int* lastPos, int batch, int nTok, int d, hipStream_t stream );
+
+	// ---- the decode-step logit filters (filters.hip, next to their owner; DESIGN.md section 7 "The filters' owner") ----
 	// Suppressed tokens: logits [rows][nVocab] get -inf at columns ids[ 0 .. count ) (device, ascending), count = *countDev when countDev is non-null, at most cap;
 	// the grid depends on the rows alone
 	int launchSuppressLogits( float* logits, int rows, int nVocab, const int* ids, const int* countDev, int count, int cap, hipStream_t stream );
@@ -507,10 +513,6 @@ namespace wh
 	// to every column t < tokenEot that would complete an n-gram the history already holds; 1 empties every history and 2 arms it, both without touching the logits.
 	// Every index read from device memory is held inside the row's history and inside the row. The grid depends on the rows alone.
 	int launchNoRepeat( float* logits, int rows, int nVocab, int tokenEot, int n, const int* fed, int reset, int* history, int* counts, int cap, hipStream_t stream );
-	int launchNoSpeechGather( const float* probs, const void* spreadScratch, int rows, int nVocab, int tokenSolm, float* out, hipStream_t stream );
-	// Prompt steps whose sequences differ in length (rows right-padded to nTok tokens): the normalised row of sequence b's LAST real
-	// token, lastPos[b] (device), is copied over its row nTok - 1, where the vocabulary product of a prompt step reads. In place, f16 rows.
-	int launchGatherLastRows( f16* xn, const int* lastPos, int batch, int nTok, int d, hipStream_t stream );
 
 	// ---------------------------------------------------------------------------------------------------------------
 	// mel spectrogram

@@ -5,7 +5,7 @@
 // (Whisper/Whisper/WhisperContext.cpp: encode :310-399, encodeLayer :158-289, decode :578-639, decodeLayer :407-576),
 // ModelBuffers (Whisper/Whisper/ModelBuffers.h:8-112) and KeyValueBuffers (KeyValueBuffers.h:7-53). It is host code
 // only: every arithmetic step is a kernel from gemm*.hip / attn_enc.hip / attn_dec.hip / elementwise.hip / sample.hip / mel.hip
-// (beam.hip keeps the beam ranking and the cache reorder next to its entry points).
+// (beam.hip keeps the beam ranking and the cache reorder next to its entry points, filters.hip the logit filters next to their owner).
 //
 // Memory model (sized for 288 GB of HBM3E, no allocation in steady state):
 //   * ONE packed weight arena per model, layout a pure function of the hparams, so a rank that did not read the file
@@ -159,6 +159,26 @@ struct Profiler
 // to q + ( layer - layer0 ) * layerStride, and the pass ends behind layer1's query (nothing later is read: no MLP, no vocabulary product).
 struct AlignHook { int layer0, layer1; wh::f16* q; int64_t layerStride; };
 
+// What a context holds of the decode-step logit filters (filters.hip, the only unit that names a member; the interface the other units use is further down).
+// A switch per filter and its device buffers, each allocated by the first call that turns its filter on -- before any capture -- and never again: a captured step
+// keeps the addresses and reads the values behind them, so a new set, boost or window recaptures nothing.
+struct LogitFilters
+{
+	// wh_context_set_suppress: suppressSet = [ count ][ ids: eot ] int32, suppressHeld its count on the host; suppressOff: bypassFilterLogits
+	int suppressHeld = 0;
+	int* suppressSet = nullptr;
+	bool suppressOff = false;
+	// wh_context_set_timestamp_rules: ruleRecords [maxSeq]
+	bool rulesOn = false;
+	wh::TimestampRecord* ruleRecords = nullptr;
+	// wh_context_set_boost: phraseTables [BOOST_TABLE_INTS], phraseStates [maxSeq]
+	bool phrasesOn = false;
+	int *phraseTables = nullptr, *phraseStates = nullptr;
+	// wh_context_set_no_repeat: ngramN = n, 0 = off; ngramHistory [maxSeq][n_text_ctx], ngramCounts [maxSeq]
+	int ngramN = 0;
+	int *ngramHistory = nullptr, *ngramCounts = nullptr;
+};
+
 struct wh_context
 {
 	wh_model* m = nullptr;
@@ -204,27 +224,7 @@ struct wh_context
 	int sampleRowsOn = 0;
 	SampleRowParams *sampleRows = nullptr, *sampleRowsPin = nullptr;
 	hipEvent_t sampleRowsEv = nullptr;
-	// suppressed tokens (wh_context_set_suppress): suppressCount != 0 = decodeGraph ends with one launch that writes -inf over those columns of c->logits. suppress =
-	// [ count ][ ids: eot ] int32 in device memory, allocated by the first call with a non-empty set (before any capture) and never again: a captured step reads the
-	// count and the ids from it, so a change of the set recaptures nothing. suppressBypass is set around the one pass that must see the model's own row (wh_lang_detect).
-	int suppressCount = 0;
-	int* suppress = nullptr;
-	bool suppressBypass = false;
-	// timestamp rules (wh_context_set_timestamp_rules): on = the prompt step of a window resets tsRecords and every step of the device-side loop runs one launch that
-	// folds the fed token into its row's record and masks c->logits. tsRecords [maxSeq] is allocated by the first call that turns the mode on (before any capture)
-	// and never again. Only the device-side loop launches it: wh_decode, wh_lang_detect, wh_align_tokens and the beam step do not.
-	bool tsRules = false;
-	TimestampRecord* tsRecords = nullptr;
-	// phrase boosting (wh_context_set_boost): boostOn = the prompt step of a window and every step of the device-side loop run one launch that moves the row's
-	// automaton state over the fed token and adds the boost to the offered columns of c->logits. boostTables [BOOST_TABLE_INTS] and boostStates [maxSeq] are
-	// allocated by the first non-empty call (before any capture) and never again; a captured step reads the tables and the boost from device memory.
-	bool boostOn = false;
-	int *boostTables = nullptr, *boostStates = nullptr;
-	// no-repeat n-grams (wh_context_set_no_repeat): noRepeatN != 0 = the prompt step of a window empties the histories and every step of the device-side loop runs one
-	// launch that appends the fed token to its row's history and masks the n-grams' completions in c->logits. nrnHistory [maxSeq][n_text_ctx] and nrnCounts [maxSeq]
-	// are allocated by the first call that turns the option on (before any capture) and never again. n is a kernel argument, so the captured graphs are keyed on it.
-	int noRepeatN = 0;
-	int *nrnHistory = nullptr, *nrnCounts = nullptr;
+	LogitFilters filters;	   // the decode-step logit filters: filters.hip alone reads or writes a member
 	// wh_context_set_no_speech: p[ solm ] of the prompt step's rows, gathered behind the first sample of every window (allocated by the first call that turns it on)
 	bool noSpeech = false;
 	float* noSpeechDev = nullptr;
@@ -450,8 +450,7 @@ namespace wh
 	int alignDebugRead( wh_context* c, const std::string& w, int layer, float* dstHost, int64_t dstCapFloats );
 
 	// captured decode steps (step_graph.hip, where each of these is explained)
-	constexpr uint32_t STEP_KEY_ROWS = 0x40000u, STEP_KEY_SUPPRESS = 0x80000u, STEP_KEY_TS_RULES = 0x100000u, STEP_KEY_BEAM = 0x200000u, STEP_KEY_BOOST = 0x4000000u;
-	constexpr uint32_t STEP_KEY_NO_REPEAT = 0x8000000u;	 // times n, 1 .. 8: bits 27-30
+	constexpr uint32_t STEP_KEY_ROWS = 0x40000u, STEP_KEY_BEAM = 0x200000u;	  // bits 19, 20 and 26-30 are the filters' (filterGraphKey, filterLoopKey)
 	using StepFn = std::function<int()>;
 	enum eWarmUp { WARM_FRESH, WARM_PRESERVE };
 	bool stepsReplayable( const wh_context* c );
@@ -459,10 +458,21 @@ namespace wh
 	int obtainStepGraph( wh_context* c, int batch, uint32_t key, eWarmUp warm, const StepFn& idle, const StepFn& step, hipGraphExec_t& exec );
 	int idleLoopState( wh_context* c, int batch );
 	int enqueueSteps( wh_context* c, hipGraphExec_t exec, int nSteps, int firstKeys, const StepFn& step );
-	// what WARM_PRESERVE carries over the warm-up step: the list is stated next to the step that mutates it (decode.hip)
-	struct LoopState { DecodeState state; std::vector<int32_t> pos, tok; std::vector<TimestampRecord> rec; std::vector<int32_t> boost, nrnHistory, nrnCounts; };
+	// what WARM_PRESERVE carries over the warm-up step: the list is stated next to the step that mutates it (decode.hip); `filters` is saveFilterState's
+	struct LoopState { DecodeState state; std::vector<int32_t> pos, tok; std::vector<uint8_t> filters; };
 	int saveLoopState( wh_context* c, int batch, LoopState& s );
 	int restoreLoopState( wh_context* c, int batch, const LoopState& s );
+
+	// the decode-step logit filters (filters.hip, where each of these is explained): all that the other units know of them
+	enum eFilterPhase { FILTER_STEP = 0, FILTER_WINDOW = 1, FILTER_ARM = 2 };	  // a step of the loop; behind a window's prompt step; wh_decode_greedy, whose first token is no sample
+	int filterLogits( wh_context* c, int batch );							  // the end of decodeGraph
+	void bypassFilterLogits( wh_context* c, bool on );						  // around wh_lang_detect's pass
+	int filterLoopRows( wh_context* c, int batch, eFilterPhase phase );	  // between decodeGraph and the sampler of the device-side loop
+	uint32_t filterGraphKey( const wh_context* c );							  // stepKey's bits of every step that runs decodeGraph
+	uint32_t filterLoopKey( const wh_context* c );							  // ... and of a step of the greedy loop
+	int saveFilterState( const wh_context* c, int batch, std::vector<uint8_t>& s );
+	int restoreFilterState( wh_context* c, int batch, const std::vector<uint8_t>& s );
+	int filtersAllowFlags( const wh_context* c, uint32_t flags );			  // wh_context_set_flags: 0, or the refusal with its error set
 }
 
 static inline uint16_t f32ToF16Bits( float f )

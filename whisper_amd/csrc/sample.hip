@@ -693,202 +693,6 @@ namespace wh
 			if( tid == 0 ) publish( pick );
 		}
 
-		// ---- suppressed tokens (wh_context_set_suppress; DESIGN.md section 7 "Suppressed tokens") ----------------------
-		// logits[ row ][ ids[ i ] ] = -inf for i < count, one workgroup per row: every kernel above reads -inf as probability 0, so nothing downstream changes. The
-		// count comes from device memory when countDev is non-null (a captured step graph outlives a change of the set) and is held to `cap`, the ids' allocation;
-		// an id outside the row is skipped. The ids are ascending, so neighbouring lanes store to ascending addresses of a row the vocabulary product just wrote.
-		__global__ void __launch_bounds__( 256 ) suppressLogitsKernel( float* __restrict__ logits, int nVocab, const int* __restrict__ ids, const int* __restrict__ countDev,
-			int count, int cap )
-		{
-			float* const x = logits + (long long)blockIdx.x * nVocab;
-			if( countDev ) count = *countDev;
-			count = min( count, cap );
-			for( int i = threadIdx.x; i < count; i += 256 )
-			{
-				const int id = ids[ i ];
-				if( (unsigned)id < (unsigned)nVocab ) x[ id ] = -INFINITY;
-			}
-		}
-
-		// ---- timestamp rules (wh_context_set_timestamp_rules; DESIGN.md section 7 "Timestamp rules") ----------------------
-		// The three clauses of openai-whisper's ApplyTimestampRules that sampleBest does not hold -- pairs, non-decreasing timestamps, segments of non-zero length --
-		// as -inf over ranges of the row, one workgroup per row. The mask depends on what the row has sampled so far: one TimestampRecord per row in device memory.
-		// reset 0 (a step of the device-side loop): fold fed[ row ], the previous step's sample, into the record, then mask what the record gives. A record whose
-		// count is negative is armed: the fed token is no sample (wh_decode_greedy's first token), nothing is folded and the history starts empty.
-		// reset 1 (the prompt step): the record becomes the empty history and nothing is masked -- the first sample is sampleTimestamp( true )'s business. reset 2: armed.
-		// Every thread reads the record and the fed token, the barrier follows, and only then thread 0 writes the record back: no lane can see the new one.
-		// Plain stores, consecutive lanes to consecutive floats of the row; ranges are held to [0, nVocab).
-		__device__ __forceinline__ void fillNegInf( float* __restrict__ x, int lo, int hi )
-		{
-			for( int i = lo + (int)threadIdx.x; i < hi; i += TSR_THREADS ) x[ i ] = -INFINITY;
-		}
-		__global__ void __launch_bounds__( TSR_THREADS ) timestampRulesKernel( float* __restrict__ logits, int nVocab, int tokenEot, int tokenBeg, const int* __restrict__ fed,
-			int reset, TimestampRecord* __restrict__ records )
-		{
-			const int row = blockIdx.x;
-			if( reset )
-			{
-				if( threadIdx.x == 0 ) records[ row ] = TimestampRecord{ 0, 0, 0, reset == 2 ? -1 : 0 };
-				return;
-			}
-			TimestampRecord r = records[ row ];
-			const int tok = fed[ row ];
-			__syncthreads();
-			if( r.count < 0 ) r = TimestampRecord{ 0, 0, 0, 0 };
-			else
-			{
-				const int isTs = tok >= tokenBeg ? 1 : 0;
-				r.prevTs = r.lastTs;
-				r.lastTs = isTs;
-				if( isTs ) r.lastId = min( tok, nVocab - 1 );
-				r.count = min( r.count + 1, 0x7ffffffe );
-			}
-			if( threadIdx.x == 0 ) records[ row ] = r;
-			float* const x = logits + (long long)row * nVocab;
-			// "the one before it" counts as a timestamp while fewer than two tokens have been sampled
-			const bool open = r.lastTs && !( r.count < 2 || r.prevTs );	  // text, <|t|>: the pair must close
-			if( r.lastTs )
-			{
-				if( open ) fillNegInf( x, 0, min( tokenEot, nVocab ) );
-				else fillNegInf( x, tokenBeg, nVocab );
-			}
-			// lastId: 0 = no timestamp yet (tokenBeg >= 1). A pair may close at the time it opened; everything else must move on
-			if( r.lastId > 0 ) fillNegInf( x, tokenBeg, min( open ? r.lastId : r.lastId + 1, nVocab ) );
-		}
-
-		// ---- phrase boosting (wh_context_set_boost; DESIGN.md section 7 "Phrase boosting") ----------------------
-		// logits[ row ][ t ] += boost for every token t that continues a phrase after some suffix of what the row has sampled since its last non-text token, one
-		// workgroup per row. The suffixes are one state of an Aho-Corasick automaton per row in device memory; the tables (boost.hip) fold the failure chains in, so
-		// the step is two searches: delta( n, t ) = n's entry, else the root's, else the root; offered( n ) = n's tokens and the root's.
-		// reset 0 (a step of the device-side loop): move the state over fed[ row ], the previous step's sample; an armed state (-1: the fed token is no sample) or a
-		// fed id that is no text token gives the root. reset 1 (the prompt step): the root. reset 2: armed. In all three the new state's offers are boosted.
-		// Every thread reads the state and the fed token, the barrier follows, and only then thread 0 writes the state back: no lane can see the new one.
-		// ONCE per token by construction: a node's tokens are distinct (ascending in the table), and a root token is added only when a search of the node's tokens
-		// does not find it -- so no two lanes of the launch store to one float, and plain loads and stores do. The header, the offsets and the nodes read from
-		// device memory are held to the limits of a set and every index into the tables to [0, cap): tables and states that are not a compiler's (the idle state a
-		// warm-up step runs on) cost wrong floats, never a fault.
-		__device__ __forceinline__ int boostLoad( const int* __restrict__ tables, int cap, int i )
-		{
-			return tables[ min( max( i, 0 ), cap - 1 ) ];
-		}
-		// the first entry of tok[ lo, hi ) that is not below t, hi when there is none (findEntry of boost.hip)
-		__device__ __forceinline__ int boostFind( const int* __restrict__ tables, int cap, int tokBase, int lo, int hi, int t )
-		{
-			while( lo < hi )
-			{
-				const int mid = lo + ( ( hi - lo ) >> 1 );
-				if( boostLoad( tables, cap, tokBase + mid ) < t ) lo = mid + 1;
-				else hi = mid;
-			}
-			return lo;
-		}
-		__global__ void __launch_bounds__( BOOST_THREADS ) boostLogitsKernel( float* __restrict__ logits, int nVocab, int tokenEot, const int* __restrict__ tables, int cap,
-			const int* __restrict__ fed, int reset, int* __restrict__ states )
-		{
-			const int row = blockIdx.x;
-			const int nodes = min( max( boostLoad( tables, cap, 0 ), 1 ), BOOST_MAX_NODES ), entries = min( max( boostLoad( tables, cap, 1 ), 0 ), BOOST_MAX_ENTRIES );
-			const float boost = __int_as_float( boostLoad( tables, cap, 2 ) );
-			const BoostTables L = boostTables( nodes, entries );
-			const auto span = [ & ]( int n, int& lo, int& hi )
-			{
-				lo = min( max( boostLoad( tables, cap, L.off + n ), 0 ), entries );
-				hi = min( max( boostLoad( tables, cap, L.off + n + 1 ), lo ), entries );
-			};
-			int rootLo, rootHi;
-			span( 0, rootLo, rootHi );
-			int state = reset == 2 ? -1 : 0;
-			if( !reset )
-			{
-				const int old = states[ row ];
-				const int tok = fed[ row ];
-				__syncthreads();
-				if( old >= 0 && tok >= 0 && tok < tokenEot )
-				{
-					int lo, hi;
-					span( min( old, nodes - 1 ), lo, hi );
-					int e = boostFind( tables, cap, L.tok, lo, hi, tok );
-					if( !( e < hi && boostLoad( tables, cap, L.tok + e ) == tok ) )
-					{
-						e = boostFind( tables, cap, L.tok, rootLo, rootHi, tok );
-						if( !( e < rootHi && boostLoad( tables, cap, L.tok + e ) == tok ) ) e = -1;
-					}
-					state = e < 0 ? 0 : min( max( boostLoad( tables, cap, L.next + e ), 0 ), nodes - 1 );
-				}
-			}
-			if( threadIdx.x == 0 ) states[ row ] = state;
-			float* const x = logits + (long long)row * nVocab;
-			const int lim = min( tokenEot, nVocab );	  // text tokens only, and inside the row
-			const int at = max( state, 0 );
-			int lo, hi;
-			span( at, lo, hi );
-			for( int e = lo + (int)threadIdx.x; e < hi; e += BOOST_THREADS )
-			{
-				const int t = boostLoad( tables, cap, L.tok + e );
-				if( (unsigned)t < (unsigned)lim ) x[ t ] = x[ t ] + boost;
-			}
-			if( at == 0 ) return;
-			for( int e = rootLo + (int)threadIdx.x; e < rootHi; e += BOOST_THREADS )
-			{
-				const int t = boostLoad( tables, cap, L.tok + e );
-				const int mine = boostFind( tables, cap, L.tok, lo, hi, t );
-				if( mine < hi && boostLoad( tables, cap, L.tok + mine ) == t ) continue;
-				if( (unsigned)t < (unsigned)lim ) x[ t ] = x[ t ] + boost;
-			}
-		}
-
-		// ---- no-repeat n-grams (wh_context_set_no_repeat; DESIGN.md section 7 "No-repeat n-grams") ----------------------
-		// logits[ row ][ t ] = -inf for every text token t (t < tokenEot) that would complete an n-gram the row has already sampled in this window: with h[ 0, L ) the
-		// history, every t = h[ i + n - 1 ] whose n - 1 predecessors h[ i, i + n - 1 ) equal the last n - 1 tokens h[ L - n + 1, L ), 0 <= i <= L - n. One workgroup per
-		// row; the history is one row of `history` [rows][cap] and one count per row in device memory.
-		// reset 0 (a step of the device-side loop): append fed[ row ], the previous step's sample, then mask. A count that is negative is armed: the fed token is no
-		// sample (wh_decode_greedy's first token), nothing is appended and the history starts empty. A full history (count == cap) drops the token and masks by what
-		// it holds. reset 1 (the prompt step): the history becomes empty and nothing is masked. reset 2: armed.
-		// Every thread reads the count and the fed token, the barrier follows, and only then thread 0 writes the token and the count back: no lane can see the new
-		// count, and the one history entry that is written in this launch, h[ old count ], is never loaded -- the lanes take it from the register that holds the fed token.
-		// Each lane owns start positions i: n - 1 compares against the suffix, which is wave-uniform and kept in registers, then one plain store. The history is
-		// under 2 KB per row and every lane reads each entry at most n times through L1 / L2; it is not staged in LDS. Several lanes may find the same t (an n-gram that
-		// occurs more than once) and store the same -inf to one float: intended, the result is the same whichever store lands last, as in suppressLogitsKernel with a
-		// repeated id. The count, the history entries and the fed id come from device memory: the count is held to [ -1, cap ], positions follow from it and stay inside
-		// [ 0, cap ), and a token is used as a column only inside [ 0, min( tokenEot, nVocab ) ). A record that is nobody's history (the idle state a warm-up step runs
-		// on) costs wrong floats, never a fault.
-		__global__ void __launch_bounds__( NRN_THREADS ) noRepeatKernel( float* __restrict__ logits, int nVocab, int tokenEot, int n, const int* __restrict__ fed, int reset,
-			int* __restrict__ history, int* __restrict__ counts, int cap )
-		{
-			const int row = blockIdx.x;
-			if( reset )
-			{
-				if( threadIdx.x == 0 ) counts[ row ] = reset == 2 ? -1 : 0;
-				return;
-			}
-			const int old = min( counts[ row ], cap );
-			const int tok = fed[ row ];
-			__syncthreads();
-			int* const h = history + (long long)row * cap;
-			const bool append = old >= 0 && old < cap;
-			const int L = old < 0 ? 0 : append ? old + 1 : cap;
-			if( threadIdx.x == 0 )
-			{
-				if( append ) h[ old ] = tok;
-				counts[ row ] = L;
-			}
-			if( L < n ) return;
-			const auto at = [ & ]( int j ) { return ( append && j == old ) ? tok : h[ j ]; };
-			int suffix[ NRN_MAX_N - 1 ];
-#pragma unroll
-			for( int k = 0; k < NRN_MAX_N - 1; k++ ) suffix[ k ] = k < n - 1 ? at( L - n + 1 + k ) : 0;
-			float* const x = logits + (long long)row * nVocab;
-			const int lim = min( tokenEot, nVocab );	  // text tokens only, and inside the row
-			for( int i = (int)threadIdx.x; i <= L - n; i += NRN_THREADS )
-			{
-				bool same = true;
-#pragma unroll
-				for( int k = 0; k < NRN_MAX_N - 1; k++ )
-					if( k < n - 1 && same ) same = at( i + k ) == suffix[ k ];
-				const int t = at( i + n - 1 );
-				if( same && (unsigned)t < (unsigned)lim ) x[ t ] = -INFINITY;
-			}
-		}
-
 		bool drawShapeOk( int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot )
 		{
 			return rows >= 1 && nVocab >= 1 && nVocab <= SAMPLE_DRAW_MAX_VOCAB && tokenBeg >= 1 && tokenBeg < nVocab && tokenSot >= 0 && tokenSot < tokenBeg &&
@@ -921,50 +725,6 @@ namespace wh
 			hipLaunchKernelGGL( softMaxRowsReg<true>, dim3( rows ), dim3( 1024 ), 0, stream, logits, probs, nVocab, invT, invTDev );
 		else
 			hipLaunchKernelGGL( softMaxRows<true>, dim3( rows ), dim3( 1024 ), 0, stream, logits, probs, nVocab, invT, invTDev );
-		WH_HIP( hipGetLastError() );
-		return 0;
-	}
-
-	int launchSuppressLogits( float* logits, int rows, int nVocab, const int* ids, const int* countDev, int count, int cap, hipStream_t stream )
-	{
-		if( !logits || !ids || rows < 1 || nVocab < 1 || count < 0 || cap < 0 ) { setError( "suppressLogits: bad argument" ); return -1; }
-		hipLaunchKernelGGL( suppressLogitsKernel, dim3( rows ), dim3( 256 ), 0, stream, logits, nVocab, ids, countDev, count, cap );
-		WH_HIP( hipGetLastError() );
-		return 0;
-	}
-
-	int launchTimestampRules( float* logits, int rows, int nVocab, int tokenEot, int tokenBeg, const int* fed, int reset, TimestampRecord* records, hipStream_t stream )
-	{
-		if( !logits || !records || ( !reset && !fed ) || rows < 1 || nVocab < 2 || tokenBeg < 1 || tokenBeg >= nVocab || tokenEot < 0 || tokenEot >= tokenBeg || reset < 0 || reset > 2 )
-		{
-			setError( "timestampRules: bad argument" );
-			return -1;
-		}
-		hipLaunchKernelGGL( timestampRulesKernel, dim3( rows ), dim3( TSR_THREADS ), 0, stream, logits, nVocab, tokenEot, tokenBeg, fed, reset, records );
-		WH_HIP( hipGetLastError() );
-		return 0;
-	}
-
-	int launchBoostLogits( float* logits, int rows, int nVocab, int tokenEot, const int* tables, int tableInts, const int* fed, int reset, int* states, hipStream_t stream )
-	{
-		if( !logits || !tables || !states || ( !reset && !fed ) || rows < 1 || nVocab < 1 || nVocab > BOOST_MAX_VOCAB || tokenEot < 0 || tokenEot > nVocab || tableInts < 4 || reset < 0 || reset > 2 )
-		{
-			setError( "boostLogits: bad argument" );
-			return -1;
-		}
-		hipLaunchKernelGGL( boostLogitsKernel, dim3( rows ), dim3( BOOST_THREADS ), 0, stream, logits, nVocab, tokenEot, tables, tableInts, fed, reset, states );
-		WH_HIP( hipGetLastError() );
-		return 0;
-	}
-
-	int launchNoRepeat( float* logits, int rows, int nVocab, int tokenEot, int n, const int* fed, int reset, int* history, int* counts, int cap, hipStream_t stream )
-	{
-		if( !logits || !history || !counts || ( !reset && !fed ) || rows < 1 || nVocab < 1 || tokenEot < 0 || tokenEot > nVocab || n < 1 || n > NRN_MAX_N || reset < 0 || reset > 2 || cap < 1 )
-		{
-			setError( "noRepeat: bad argument" );
-			return -1;
-		}
-		hipLaunchKernelGGL( noRepeatKernel, dim3( rows ), dim3( NRN_THREADS ), 0, stream, logits, nVocab, tokenEot, n, fed, reset, history, counts, cap );
 		WH_HIP( hipGetLastError() );
 		return 0;
 	}

@@ -9,24 +9,19 @@ bool wh::stepsReplayable( const wh_context* c )
 	return !c->prof.on && !( c->flags & WH_FLAG_NO_GRAPH ) && !debugSync();
 }
 
-// Everything besides the batch that changes the launch sequence of a step -- whatever is added to a step's launches under a context switch gets a bit HERE, for
-// every kind of step. Values (temperatures, seeds, the suppressed ids, the records) live in device memory and are no part of it: one graph serves them all.
+// Everything besides the batch that changes the launch sequence of a step, for every kind of step. Values (temperatures, seeds) live in device memory and are
+// no part of it: one graph serves them all.
 //   bits 0-15 + 0x10000  WH_FLAG_PARITY_PV and its thread count (other attention kernels)
 //   0x20000              a temperature is set (wh_context_set_sampling: other sampler kernels, the same for every temperature)
 //   STEP_KEY_ROWS        per-row sampling (wh_context_set_sampling_rows)
-//   STEP_KEY_SUPPRESS    a suppressed set is held (wh_context_set_suppress): one more node behind the logits, the same for every set
-//   STEP_KEY_TS_RULES    the timestamp rules are on (wh_context_set_timestamp_rules): one more node, the same for every window
-//   STEP_KEY_BOOST       a set of boosted phrases is held (wh_context_set_boost): one more node in front of the sampler, the same for every set and boost
-//   STEP_KEY_NO_REPEAT * n  no-repeat n-grams are on (wh_context_set_no_repeat), n = 1 .. 8 in bits 27-30: one more node in front of the sampler, and n is an argument
-//                        of its kernel, so a graph captured for one n never serves another
-//   STEP_KEY_BEAM + width in bits 22-25: a beam step of that width. It runs decodeGraph like the greedy step, so it shares the parity and suppress inputs; it has no
-//                        sampler, no timestamp rules, no boost and no n-gram filter, so those bits stay clear
+//   the logit filters    filterGraphKey / filterLoopKey (filters.hip, where their bits are explained)
+//   STEP_KEY_BEAM + width in bits 22-25: a beam step of that width. It runs decodeGraph like the greedy step, so it shares the parity input and filterGraphKey; it
+//                        has no sampler and none of the filters in front of one, so the other bits stay clear
 uint32_t wh::stepKey( const wh_context* c, int beamWidth )
 {
-	const uint32_t graph = ( ( c->flags & WH_FLAG_PARITY_PV ) ? ( 0x10000u | (uint32_t)c->parityThreads ) : 0u ) | ( c->suppressCount > 0 ? STEP_KEY_SUPPRESS : 0u );
+	const uint32_t graph = ( ( c->flags & WH_FLAG_PARITY_PV ) ? ( 0x10000u | (uint32_t)c->parityThreads ) : 0u ) | filterGraphKey( c );
 	if( beamWidth > 0 ) return graph | STEP_KEY_BEAM | ( (uint32_t)beamWidth << 22 );
-	return graph | ( c->temperature > 0.0f ? 0x20000u : 0u ) | ( c->sampleRowsOn ? STEP_KEY_ROWS : 0u ) | ( c->tsRules ? STEP_KEY_TS_RULES : 0u ) | ( c->boostOn ? STEP_KEY_BOOST : 0u ) |
-		STEP_KEY_NO_REPEAT * (uint32_t)c->noRepeatN;
+	return graph | ( c->temperature > 0.0f ? 0x20000u : 0u ) | ( c->sampleRowsOn ? STEP_KEY_ROWS : 0u ) | filterLoopKey( c );
 }
 
 // Retention, applied when ( batch, key ) is about to be captured. Entries of the other kind stay: a hypothesis-group context may run greedy and beam windows in
