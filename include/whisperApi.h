@@ -379,6 +379,9 @@ namespace Whisper
 		uint32_t groups;		// lock-step batches in flight; 0 = 2
 		uint32_t greedyChunk;	// greedy steps enqueued at a time; 0 = 4. The host applies its stop rules chunk by chunk, so up to one chunk is decoded past the end of a round
 		uint32_t flags;			// 1 = keep one more chunk queued behind the one in flight (the device never waits for the host; up to two chunks are decoded in vain)
+								// 2 = FP8 cross-attention caches: the groups' contexts are created with wh_context_create_kv8 (E4M3 bytes and a power-of-two scale per key row:
+								//     about half the cache memory per slot and half the bytes the decode step's dominant kernel reads; the one-window loader context stays
+								//     as it is). Off unless set. Nobody has measured recognition accuracy with FP8 caches on a real checkpoint.
 	};
 	// {6f0c9a1e-3b52-4d7c-8e21-9a4f5c7d2b10}
 	struct iBatchRunner : public ComLight::IUnknown

@@ -162,6 +162,17 @@ WH_API int wh_context_create( wh_model* m, int maxBatch, void* stream, wh_contex
  * "every hypothesis computes what a lone sequence fed the same tokens computes". In every decode entry point `batch`
  * then counts SEQUENCES (a multiple of `hypotheses`); wh_encode's `batch` keeps counting windows. */
 WH_API int wh_context_create_hyp( wh_model* m, int maxBatch, int hypotheses, void* stream, wh_context** out );
+/* wh_context_create with FP8 cross-attention caches (whisper_amd/csrc/kv8.hip; DESIGN.md section 7 "FP8 cross-attention caches"). The FP16 cross-attention
+ * caches are never allocated: the encoder's cross-K/V product runs one decoder layer at a time into an FP16 staging of one layer x one encoder chunk, and
+ * quantizeCrossKV turns it into OCP E4M3 bytes [layer][window][head][T][64] with one power-of-two FP32 scale per key row, s = 2^ceil( log2( amax / 448 ) )
+ * (1 for a row of zeros): the bytes are the E4M3 rounding (to nearest even) of exactly the FP16 values wh_context_create's caches hold, divided by s. Every
+ * decode step takes the batch path, whose cross-attention is attentionDecG8; the single-stream step kernels stay FP16-only. About half the cache memory
+ * (wh_context_memory) and half the bytes the decode step's dominant kernel reads. Captured step graphs, per-row sampling, the logit filters, language detection
+ * and wh_score_tokens work on top as on any context. WH_E_INVALIDARG, with the reason in wh_last_error: wh_context_set_flags with WH_FLAG_PARITY_PV or
+ * WH_FLAG_PARITY_EXACT, wh_align_tokens, wh_debug_read of "cross-k" / "cross-v", and -- wh_context_create_kv8_hyp -- any `hypotheses` other than 1
+ * (the hypothesis-group kernel attentionDecM reads FP16 rows). Nobody has measured recognition accuracy with FP8 caches on a real checkpoint. */
+WH_API int wh_context_create_kv8( wh_model* m, int maxBatch, void* stream, wh_context** out );
+WH_API int wh_context_create_kv8_hyp( wh_model* m, int maxBatch, int hypotheses, void* stream, wh_context** out );
 WH_API void wh_context_destroy( wh_context* c );
 /* Binds the model's device to the calling thread (every wh_* call on a model or context does it as well): the
  * counterpart of Device::setForCurrentThread (Whisper/ML/Device.cpp:163-177). Call it before wh_buffer_alloc /
@@ -649,6 +660,9 @@ WH_API int wh_profile_read( wh_context* c, wh_profile_entry* out, int cap, int* 
  *          "exp-table"   [0x5000]: the model's copy of the reference's table_exp_f16 (ggml.c:1375-1385), entry i = fp16( expf( -|fp16 bits i| ) )
  *          "cross-k" / "cross-v"   layer, [batch][n_ctx][d] token-major like the reference's kvCross
  *          "self-k" / "self-v"     layer, [sequences][rows][d]
+ *   on a wh_context_create_kv8 context (which refuses "cross-k" / "cross-v"), one layer in the cache's own order, RAW (dstCapFloats still counts floats):
+ *          "cross-k8" / "cross-v8"              [batch][heads][n_ctx][64] E4M3 bytes, batch * n_ctx * d bytes packed into dstHost
+ *          "cross-k8-scale" / "cross-v8-scale"  [batch][heads][n_ctx] FP32 row scales
  * and, captured under WH_FLAG_DEBUG_CAPTURE by the wh_encode / wh_decode call that follows the flag:
  *          "enc.temp1"      conv1 + bias + GELU, [batch][2*n_ctx][d] (time-major; the reference's tensor is [d][2*n_ctx])
  *          "enc.layer0.in"  conv2 + GELU + positional embedding = input of encoder layer 0, [batch][n_ctx][d]
@@ -705,6 +719,14 @@ WH_API int wh_op_decoder_attention( void* stream, const void* qF16, const void* 
  * * lnW + lnB ) + qB ) * qScale ) per head inside the attention kernel; x: FP32 [sequences][heads*64]. */
 WH_API int wh_op_decoder_cross_attention( void* stream, const float* x, const float* lnW, const float* lnB, const void* qW, const float* qB,
 	float qScale, const void* kCache, const void* vCache, void* outF16, int sequences, int heads, int nKeys, int keyStride, int group );
+/* quantizeCrossKV on its own (kv8.hip): `rows` FP16 rows of 64 -> E4M3 bytes [rows][64] and FP32 scales [rows], the format of wh_context_create_kv8's caches */
+WH_API int wh_op_quantize_kv( void* stream, const void* rowsF16, void* bytesOut, float* scalesOut, int64_t rows );
+/* wh_op_decoder_attention (x == NULL: qF16 holds the scaled query rows) or wh_op_decoder_cross_attention (x non-NULL: the query is formed in the kernel) over FP8
+ * caches: kBytes / vBytes E4M3 [sequences / group][heads][keyStride][64], kScales / vScales FP32 [sequences / group][heads][keyStride]; never causal.
+ * qF16, x and out hold sequences * nTok rows. */
+WH_API int wh_op_decoder_cross_attention_f8( void* stream, const void* qF16, const float* x, const float* lnW, const float* lnB, const void* qW, const float* qB,
+	float qScale, const void* kBytes, const float* kScales, const void* vBytes, const float* vScales, void* outF16, int sequences, int heads, int nTok, int nKeys,
+	int keyStride, int group );
 /* softMax over rows with the reference's FP16 exp table semantics (softMax.hlsl / ggml.c:5030-5090): in place, FP32 */
 WH_API int wh_op_soft_max( void* stream, float* x, int rows, int cols );
 

@@ -44,7 +44,7 @@ EXPORTS = [
     "wh_model_arena_bytes", "wh_model_create", "wh_model_destroy", "wh_model_set_tensor", "wh_model_set_filters",
     "wh_model_finalize", "wh_model_arena", "wh_model_hparams",
     "wh_comm_runtime_check", "wh_comm_unique_id", "wh_comm_create", "wh_comm_destroy", "wh_comm_info", "wh_comm_barrier", "wh_comm_create_timeout", "wh_comm_set_timeout", "wh_comm_broadcast_i32", "wh_model_broadcast",
-    "wh_context_create", "wh_context_create_hyp", "wh_context_destroy", "wh_context_bind", "wh_context_set_flags", "wh_context_set_audio_ctx", "wh_context_synchronize", "wh_context_memory",
+    "wh_context_create", "wh_context_create_hyp", "wh_context_create_kv8", "wh_context_create_kv8_hyp", "wh_context_destroy", "wh_context_bind", "wh_context_set_flags", "wh_context_set_audio_ctx", "wh_context_synchronize", "wh_context_memory",
     "wh_buffer_alloc", "wh_buffer_free", "wh_buffer_upload", "wh_buffer_upload_async", "wh_buffer_download",
     "wh_mel_spectrogram", "wh_encode", "wh_encode_windows", "wh_decode", "wh_sample_best", "wh_beam_candidates", "wh_reorder_self_cache", "wh_beam_window_start", "wh_beam_window_continue", "wh_beam_window_status", "wh_beam_window_records", "wh_decode_greedy", "wh_decode_window_start", "wh_decode_window_finish", "wh_decode_window_continue", "wh_decode_window_fetch", "wh_decode_window_start_ragged", "wh_decode_window_ready", "wh_mel_spectrogram_window", "wh_mel_spectrogram_batch", "wh_profile_enable", "wh_profile_read", "wh_debug_read", "wh_debug_step_captures", "wh_debug_probe", "wh_debug_set_tuning", "wh_debug_set_option", "wh_debug_get_option",
     "wh_op_mul_mat", "wh_op_mul_mat_gelu", "wh_op_layer_norm", "wh_op_flash_attention", "wh_op_soft_max", "wh_op_decoder_attention", "wh_op_decoder_cross_attention",
@@ -66,6 +66,7 @@ EXPORTS = [
     "wh_op_gemv_small", "wh_op_cross_split", "wh_op_self_block_dec",
     "wh_score_tokens", "wh_op_token_scores",
     "wh_op_gemm_encoder", "wh_op_mel_to_conv_input",
+    "wh_op_quantize_kv", "wh_op_decoder_cross_attention_f8",
 ]
 
 
@@ -204,6 +205,8 @@ def lib():
         L.wh_model_hparams.argtypes = [vp, C.POINTER(HParamsC)]
         L.wh_context_create.argtypes = [vp, i32, vp, C.POINTER(vp)]
         L.wh_context_create_hyp.argtypes = [vp, i32, i32, vp, C.POINTER(vp)]
+        L.wh_context_create_kv8.argtypes = [vp, i32, vp, C.POINTER(vp)]
+        L.wh_context_create_kv8_hyp.argtypes = [vp, i32, i32, vp, C.POINTER(vp)]
         L.wh_context_bind.argtypes = [vp]
         L.wh_context_destroy.argtypes = [vp]
         L.wh_context_destroy.restype = None
@@ -240,6 +243,8 @@ def lib():
         L.wh_op_soft_max.argtypes = [vp, vp, i32, i32]
         L.wh_op_decoder_attention.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32]
         L.wh_op_decoder_cross_attention.argtypes = [vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, i32, i32, i32, i32, i32]
+        L.wh_op_quantize_kv.argtypes = [vp, vp, vp, vp, i64]
+        L.wh_op_decoder_cross_attention_f8.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32]
         L.wh_op_vocab_soft_max.argtypes = [vp, vp, vp, i32, i32]
         L.wh_op_sample_best.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
         L.wh_op_beam_candidates.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
@@ -423,15 +428,18 @@ class HipModel:
 class HipContext:
     """Activations + KV caches for up to max_batch 30 s windows processed in lock step (WhisperContext of the reference)."""
 
-    def __init__(self, model: HipModel, max_batch: int = 1, stream: int = 0, hypotheses: int = 1):
+    def __init__(self, model: HipModel, max_batch: int = 1, stream: int = 0, hypotheses: int = 1, cross_fp8: bool = False):
         """max_batch windows; `hypotheses` decoder sequences per window share the window's cross-attention K/V (then every
-        decode entry point counts sequences = windows * hypotheses, window-major)."""
+        decode entry point counts sequences = windows * hypotheses, window-major). cross_fp8: the cross-attention caches as E4M3 bytes with a
+        power-of-two scale per key row (wh_context_create_kv8: half the cache memory; one hypothesis per window only)."""
         self.model = model
         self.hp = model.hp
         self.max_batch = max_batch
         self.hypotheses = hypotheses
+        self.cross_fp8 = cross_fp8
         self.handle = C.c_void_p()
-        check(lib().wh_context_create_hyp(model.handle, max_batch, hypotheses, C.c_void_p(stream) if stream else None, C.byref(self.handle)))
+        create = lib().wh_context_create_kv8_hyp if cross_fp8 else lib().wh_context_create_hyp
+        check(create(model.handle, max_batch, hypotheses, C.c_void_p(stream) if stream else None, C.byref(self.handle)))
         self.batch = 0
 
     def close(self):
@@ -824,6 +832,13 @@ class HipContext:
             shape = (ab, an, keys) if what == "align-matrix" else (ab, an, d)
             out = np.empty(shape, np.float32)
             check(lib().wh_debug_read(self.handle, what.encode(), layer, 0, out.ctypes.data_as(C.c_void_p), out.size))
+            return out
+        if what in ("cross-k8", "cross-v8", "cross-k8-scale", "cross-v8-scale"):
+            # one layer of the FP8 caches, raw, in the cache's own order: bytes [batch][heads][keys][64] uint8, scales [batch][heads][keys] float32
+            keys = getattr(self, "_audio_ctx", 0) or self.hp.n_audio_ctx
+            shape = (b, self.hp.n_audio_head, keys)
+            out = np.empty(shape, np.float32) if what.endswith("scale") else np.empty(shape + (64,), np.uint8)
+            check(lib().wh_debug_read(self.handle, what.encode(), layer, 0, out.ctypes.data_as(C.c_void_p), out.nbytes // 4))
             return out
         if what in ("logits", "probs"):
             shape = (rows, self.hp.n_vocab)         # rows = sequences of the last decode step

@@ -63,7 +63,30 @@ int wh_context_create( wh_model* m, int maxBatch, void* stream, wh_context** out
 	return wh_context_create_hyp( m, maxBatch, 1, stream, out );
 }
 
+static int createContext( wh_model* m, int maxBatch, int hypotheses, bool kv8, void* stream, wh_context** out );
+
 int wh_context_create_hyp( wh_model* m, int maxBatch, int hypotheses, void* stream, wh_context** out )
+{
+	return createContext( m, maxBatch, hypotheses, false, stream, out );
+}
+
+// FP8 cross-attention caches: greedy contexts only -- the matrix-core kernel of a hypothesis group (attentionDecM) reads FP16 rows
+int wh_context_create_kv8( wh_model* m, int maxBatch, void* stream, wh_context** out )
+{
+	return wh_context_create_kv8_hyp( m, maxBatch, 1, stream, out );
+}
+
+int wh_context_create_kv8_hyp( wh_model* m, int maxBatch, int hypotheses, void* stream, wh_context** out )
+{
+	if( hypotheses != 1 )
+	{
+		setError( "context_create_kv8: FP8 cross-attention caches serve one hypothesis per window (the hypothesis-group kernel attentionDecM reads FP16 caches)" );
+		return WH_E_INVALIDARG;
+	}
+	return createContext( m, maxBatch, 1, true, stream, out );
+}
+
+static int createContext( wh_model* m, int maxBatch, int hypotheses, bool kv8, void* stream, wh_context** out )
 {
 	if( !m || !out || maxBatch <= 0 || hypotheses <= 0 || hypotheses > 8 || hypotheses == 6 || hypotheses == 7 )
 	{
@@ -77,6 +100,7 @@ int wh_context_create_hyp( wh_model* m, int maxBatch, int hypotheses, void* stre
 	c->m = m;
 	(void)hipDeviceGetAttribute( &c->totalCus, hipDeviceAttributeMultiprocessorCount, m->device );
 	c->maxBatch = maxBatch;
+	c->kv8 = kv8;
 	c->hyp = hypotheses;
 	c->maxSeq = maxBatch * hypotheses;
 	c->stream = (hipStream_t)stream;
@@ -152,8 +176,22 @@ int wh_context_create_hyp( wh_model* m, int maxBatch, int hypotheses, void* stre
 	rc = rc ? rc : c->alloc( c->vT, Be * H * HEAD_DIM * c->Tpad, wh_context::MUST_BE_ZERO, "vT" );
 	rc = rc ? rc : c->alloc( c->attn, rowsE * d, wh_context::DONT_CARE, "attn" );
 	rc = rc ? rc : c->alloc( c->h, rowsE * 4 * d, wh_context::DONT_CARE, "h" );
-	rc = rc ? rc : c->alloc( c->crossK, (int64_t)hp.n_text_layer * B * T * d, wh_context::MUST_BE_ZERO, "crossK" );
-	rc = rc ? rc : c->alloc( c->crossV, (int64_t)hp.n_text_layer * B * T * d, wh_context::MUST_BE_ZERO, "crossV" );
+	if( !kv8 )
+	{
+		rc = rc ? rc : c->alloc( c->crossK, (int64_t)hp.n_text_layer * B * T * d, wh_context::MUST_BE_ZERO, "crossK" );
+		rc = rc ? rc : c->alloc( c->crossV, (int64_t)hp.n_text_layer * B * T * d, wh_context::MUST_BE_ZERO, "crossV" );
+	}
+	else
+	{
+		// a byte per element and a scale per key row (zero bytes under any scale are zeros: finite, like the FP16 caches' zero fill), and the staging
+		// of one layer x one encoder chunk that the quantizer reads: any more staging would give back what the format saves
+		const int64_t keyRows = (int64_t)hp.n_text_layer * B * hp.n_text_head * T;
+		rc = rc ? rc : c->alloc( c->crossK8, keyRows * HEAD_DIM, wh_context::MUST_BE_ZERO, "crossK8" );
+		rc = rc ? rc : c->alloc( c->crossV8, keyRows * HEAD_DIM, wh_context::MUST_BE_ZERO, "crossV8" );
+		rc = rc ? rc : c->alloc( c->crossKScale, keyRows, wh_context::MUST_BE_ZERO, "crossKScale" );
+		rc = rc ? rc : c->alloc( c->crossVScale, keyRows, wh_context::MUST_BE_ZERO, "crossVScale" );
+		rc = rc ? rc : c->alloc( c->crossStage, 2 * Be * T * d, wh_context::DONT_CARE, "crossStage" );
+	}
 	rc = rc ? rc : c->alloc( c->selfK, (int64_t)hp.n_text_layer * S * hp.n_text_ctx * d, wh_context::MUST_BE_ZERO, "selfK" );
 	rc = rc ? rc : c->alloc( c->selfV, (int64_t)hp.n_text_layer * S * hp.n_text_ctx * d, wh_context::MUST_BE_ZERO, "selfV" );
 	const int64_t rowsD = c->maxRows;
@@ -288,6 +326,11 @@ int wh_context_set_audio_ctx( wh_context* c, int audioCtx )
 int wh_context_set_flags( wh_context* c, uint32_t flags, int parityThreads )
 {
 	if( !c ) return WH_E_INVALIDARG;
+	if( c->kv8 && ( flags & ( WH_FLAG_PARITY_EXACT | WH_FLAG_PARITY_PV ) ) )
+	{
+		setError( "context_set_flags: the parity modes restate the reference's FP16 caches and are not available on a context with FP8 cross-attention caches" );
+		return WH_E_INVALIDARG;
+	}
 	WH_CHECK( filtersAllowFlags( c, flags ) );
 	c->flags = flags;
 	// WH_FLAG_PARITY_EXACT with 0 threads: the decoder's P.V as ONE correctly rounded sum per output (double accumulation) instead of the reference's

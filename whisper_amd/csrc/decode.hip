@@ -9,7 +9,8 @@ static int attnDecP( wh_context* c, const DecAttnArgs& a, int keysHint = -1 )
 	const int group = a.group > 0 ? a.group : 1;
 	const double keys = (double)( keysHint > 0 ? keysHint : a.nKeys );
 	const double d = (double)a.H * HEAD_DIM;
-	double bytes = 2.0 * 2.0 * ( a.batch / group ) * a.H * keys * HEAD_DIM + 2.0 * 2.0 * a.batch * a.nTok * d;
+	const double rowBytes = a.kc8 ? HEAD_DIM + 4.0 : 2.0 * HEAD_DIM;	  // FP8 caches: a byte per element and the row's scale
+	double bytes = 2.0 * ( a.batch / group ) * a.H * keys * rowBytes + 2.0 * 2.0 * a.batch * a.nTok * d;
 	double flops = 4.0 * a.batch * a.H * keys * HEAD_DIM * a.nTok;
 	if( a.lnX )
 	{
@@ -71,8 +72,9 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 
 	// ---- single-token steps of up to 4 sequences (one stream through iContext::runFull): decode1.hip. Eight launches per layer,
 	// each of ~256 workgroups, each pulling the weights of the next one into the L2 of the XCD that will read them.
+	// (FP8 cross-attention caches take the batch path at every batch size: crossScores / crossSoftmaxPV read FP16 rows)
 	const bool small = nTokens == 1 && batch <= SMALL_MAX_ROWS && c->hyp == 1 && parity == 0 && d <= 1280 && ( d % 64 ) == 0 && c->T <= 1536 &&
-		!( c->flags & WH_FLAG_DEBUG_CAPTURE ) && ( g_tuning & TUNE_DECODE_SMALL );
+		!( c->flags & WH_FLAG_DEBUG_CAPTURE ) && ( g_tuning & TUNE_DECODE_SMALL ) && !c->kv8;
 	if( small )
 	{
 #ifdef WH_PROBES
@@ -269,7 +271,17 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 		}
 		{
 			DecAttnArgs a = {};
-			a.q = c->dq; a.kc = c->crossK + crossLayer; a.vc = c->crossV + crossLayer; a.out = c->dattn;
+			a.q = c->dq; a.out = c->dattn;
+			if( c->kv8 )
+			{
+				// a byte per element: the layer's offset in bytes is crossLayer, in key rows crossLayer / 64
+				a.kc8 = c->crossK8 + crossLayer; a.vc8 = c->crossV8 + crossLayer;
+				a.kScale = c->crossKScale + crossLayer / HEAD_DIM; a.vScale = c->crossVScale + crossLayer / HEAD_DIM;
+			}
+			else
+			{
+				a.kc = c->crossK + crossLayer; a.vc = c->crossV + crossLayer;
+			}
 			a.batch = batch; a.H = H; a.nTok = nTokens; a.nKeys = c->T; a.keyStride = c->T;
 			a.causal = 0; a.nPast = 0; a.parityThreads = parity; a.nPastDev = nullptr;
 			a.group = c->hyp;

@@ -191,6 +191,28 @@ static int encodeImpl( wh_context* c, const float* melDev, int batch, int64_t me
 		}
 	}
 	WH_CHECK( lnP( c, c->x, m->at<float>( L.lnPostW ), m->at<float>( L.lnPostB ), c->xn, M, d ) );
+	// FP8 caches: the same product one decoder layer at a time (the layer's 2 d rows of wcross / bcross, the same kernel and epilogue) into the FP16
+	// staging of one layer, which quantizeCrossKV turns into that layer's bytes and scales at the chunk's window offset
+	if( c->kv8 )
+	{
+		f16* const stageK = c->crossStage;
+		f16* const stageV = c->crossStage + (int64_t)c->encChunk * T * d;
+		const int64_t rows = (int64_t)batch * H * T;
+		for( int il = 0; il < hp.n_text_layer; il++ )
+		{
+			GemmArgs g = plainGemm( c->xn, m->at<f16>( L.wcross ) + (int64_t)il * 2 * d * d, M, 2 * d, d );
+			g.epi = EPI_CROSS_KV;
+			g.bias = m->at<float>( L.bcross ) + (int64_t)il * 2 * d;
+			g.scale = (float)pow( (double)( (float)d / (float)H ), -0.25 );
+			g.k = stageK; g.v = stageV;
+			g.T = T; g.H = H; g.B = batch;
+			WH_CHECK( gemmP( c, g, false ) );
+			const int64_t row0 = ( (int64_t)il * c->maxBatch + b0 ) * H * T;
+			WH_CHECK( profiled( c, KC_QUANT_KV, 0.0, 2.0 * rows * ( 2.0 * HEAD_DIM + HEAD_DIM + 4.0 ), [ & ]() { return launchQuantizeCrossKV( stageK, c->crossK8 + row0 * HEAD_DIM,
+				c->crossKScale + row0, stageV, c->crossV8 + row0 * HEAD_DIM, c->crossVScale + row0, rows, st ); } ) );
+		}
+	}
+	else
 	// cross-attention K/V of every decoder layer in one product (whisper.cpp:1448-1487)
 	{
 		GemmArgs g = plainGemm( c->xn, m->at<f16>( L.wcross ), M, 2 * hp.n_text_layer * d, d );

@@ -239,8 +239,18 @@ namespace wh
 		const f16* qW;		   // [d][d]
 		const float* qB;	   // [d]
 		float qScale;
+		// FP8 cross-attention caches (kv8.hip): when kc8 is non-null, kc / vc are ignored and the keys are E4M3 bytes [batch / group][H][keyStride][64] with one
+		// power-of-two scale per row, [batch / group][H][keyStride]; cross-attention only (causal == 0, parityThreads == 0)
+		const uint8_t* kc8;
+		const uint8_t* vc8;
+		const float* kScale;
+		const float* vScale;
 	};
 	int launchAttentionDec( const DecAttnArgs& a, hipStream_t stream );
+	// kv8.hip: launchAttentionDec's branch for FP8 caches (attentionDecG8), and the quantizer behind the encoder's cross-K/V product: `rows` FP16 rows of 64 ->
+	// E4M3 bytes [rows][64] + scales [rows], s = 2^ceil( log2( amax / 448 ) ) (1 for a row of zeros), bytes = e4m3( x / s ) to nearest even. The V set may be null.
+	int launchAttentionDec8( const DecAttnArgs& a, hipStream_t stream );
+	int launchQuantizeCrossKV( const f16* srcK, uint8_t* dstK, float* scaleK, const f16* srcV, uint8_t* dstV, float* scaleV, long long rows, hipStream_t stream );
 
 	// The self-attention half of a single-token decode step as one launch: LayerNorm -> per-head Q/K/V rows of the fused
 	// [3d][d] weight -> cache append at the current position -> causal attention -> out (FP16 [batch][d]).

@@ -177,6 +177,25 @@ int wh_debug_read( wh_context* c, const char* what, int layer, int rows, float* 
 		WH_HIP( hipMemcpy( dstHost, w == "logits" ? c->logits : c->probs, (size_t)n * 4, hipMemcpyDeviceToHost ) );
 		return 0;
 	}
+	if( c->kv8 && ( w == "cross-k" || w == "cross-v" || w == "cross-k1" || w == "cross-v1" ) )
+	{
+		setError( "debug_read: this context holds FP8 cross-attention caches: read cross-k8 / cross-v8 and cross-k8-scale / cross-v8-scale" );
+		return WH_E_INVALIDARG;
+	}
+	if( w == "cross-k8" || w == "cross-v8" || w == "cross-k8-scale" || w == "cross-v8-scale" )
+	{
+		// one layer of the FP8 caches in their own order, raw: bytes [batch][heads][n_ctx][64], scales [batch][heads][n_ctx]
+		if( !c->kv8 ) { setError( "debug_read: this context holds FP16 cross-attention caches (wh_context_create_kv8 creates the FP8 ones)" ); return WH_E_INVALIDARG; }
+		if( layer < 0 || layer >= hp.n_text_layer ) return WH_E_BOUNDS;
+		const bool isK = w[ 6 ] == 'k', scales = w.size() > 8;
+		const int64_t keyRows = (int64_t)batch * hp.n_text_head * c->T, row0 = (int64_t)layer * c->maxBatch * hp.n_text_head * c->T;
+		const int64_t bytes = scales ? keyRows * 4 : keyRows * HEAD_DIM;
+		if( bytes <= 0 || dstCapFloats * 4 < bytes ) return WH_E_BOUNDS;
+		const void* const src = scales ? (const void*)( ( isK ? c->crossKScale : c->crossVScale ) + row0 ) : (const void*)( ( isK ? c->crossK8 : c->crossV8 ) + row0 * HEAD_DIM );
+		WH_HIP( hipStreamSynchronize( c->stream ) );
+		WH_HIP( hipMemcpy( dstHost, src, (size_t)bytes, hipMemcpyDeviceToHost ) );
+		return 0;
+	}
 	if( w == "cross-k1" || w == "cross-v1" )
 	{
 		// ONE window (index `rows`) of a layer's cross-attention cache: [n_ctx][d] -- contexts of hundreds of windows
@@ -425,6 +444,28 @@ int wh_op_decoder_cross_attention( void* stream, const float* x, const float* ln
 	a.batch = sequences; a.H = heads; a.nTok = 1; a.nKeys = nKeys; a.keyStride = keyStride;
 	a.group = group;
 	a.lnX = x; a.lnW = lnW; a.lnB = lnB; a.qW = (const f16*)qW; a.qB = qB; a.qScale = qScale;
+	return launchAttentionDec( a, (hipStream_t)stream );
+}
+
+int wh_op_quantize_kv( void* stream, const void* rowsF16, void* bytesOut, float* scalesOut, int64_t rows )
+{
+	return launchQuantizeCrossKV( (const f16*)rowsF16, (uint8_t*)bytesOut, scalesOut, nullptr, nullptr, nullptr, rows, (hipStream_t)stream );
+}
+
+int wh_op_decoder_cross_attention_f8( void* stream, const void* qF16, const float* x, const float* lnW, const float* lnB, const void* qW, const float* qB, float qScale,
+	const void* kBytes, const float* kScales, const void* vBytes, const float* vScales, void* outF16, int sequences, int heads, int nTok, int nKeys, int keyStride, int group )
+{
+	if( !kBytes || !kScales || !vBytes || !vScales || !outF16 || ( !x && !qF16 ) || ( x && ( !lnW || !lnB || !qW || !qB ) ) )
+	{
+		setError( "decoder_cross_attention_f8: null argument" );
+		return WH_E_INVALIDARG;
+	}
+	DecAttnArgs a = {};
+	a.q = (const f16*)qF16; a.out = (f16*)outF16;
+	a.kc8 = (const uint8_t*)kBytes; a.vc8 = (const uint8_t*)vBytes; a.kScale = kScales; a.vScale = vScales;
+	a.batch = sequences; a.H = heads; a.nTok = nTok; a.nKeys = nKeys; a.keyStride = keyStride;
+	a.group = group;
+	if( x ) { a.lnX = x; a.lnW = lnW; a.lnB = lnB; a.qW = (const f16*)qW; a.qB = qB; a.qScale = qScale; }
 	return launchAttentionDec( a, (hipStream_t)stream );
 }
 

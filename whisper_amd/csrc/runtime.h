@@ -12,7 +12,7 @@
 //     can receive it with a single RCCL broadcast. Q/K/V weights of a layer are concatenated to one [3d][d] matrix, the
 //     cross-attention K/V weights of ALL decoder layers to one [2*L*d][d] matrix (one big GEMM per window).
 //   * per context: activations for maxBatch windows in lock step + FP16 KV caches
-//       cross  [layer][batch][head][n_audio_ctx][64]   (K pre-scaled by (d/H)^-0.25, whisper.cpp:1465)
+//       cross  [layer][batch][head][n_audio_ctx][64]   (K pre-scaled by (d/H)^-0.25, whisper.cpp:1465; wh_context_create_kv8: E4M3 bytes + row scales)
 //       self   [layer][batch][head][n_text_ctx][64]
 #pragma once
 #include "kernels.h"
@@ -107,13 +107,13 @@ namespace wh { int bindDevice( const wh_model* m ); }
 enum eKernelClass : int
 {
 	KC_GEMM_TILED = 0, KC_GEMM_SKINNY, KC_GEMV, KC_ATTN_ENC, KC_ATTN_DEC, KC_ATTN_DEC_CROSS, KC_SELF_BLOCK, KC_LAYER_NORM, KC_MEL, KC_MEL_TO_CONV, KC_EMBED, KC_SOFTMAX,
-	KC_SAMPLE, KC_EVENT_PAIR, KC_LAYER_NORM_DEC, KC_GEMM_DEC, KC_COUNT
+	KC_SAMPLE, KC_EVENT_PAIR, KC_LAYER_NORM_DEC, KC_GEMM_DEC, KC_QUANT_KV, KC_COUNT
 };
 // "attentionDecCross" = cross-attention launches (attentionDecG<NQ, true> / <NQ, false> with group or nKeys = n_audio_ctx),
 // "attentionDec" = causal self-attention; "eventPair" = the calibration launches of wh_profile_enable (an empty kernel
 // between the same two event records: what the bracket itself costs, to be subtracted from every per-launch average).
 static const char* const kernelClassNames[ KC_COUNT ] = { "gemmTiled", "gemmSkinny", "gemvFused", "attentionEnc", "attentionDec", "attentionDecCross",
-	"selfBlockDec", "layerNorm", "mel", "melToConvInput", "embed", "vocabSoftMax", "softMaxSample", "eventPair", "layerNormDec", "gemmDecode" };
+	"selfBlockDec", "layerNorm", "mel", "melToConvInput", "embed", "vocabSoftMax", "softMaxSample", "eventPair", "layerNormDec", "gemmDecode", "quantizeCrossKV" };
 // "layerNormDec" / "gemmDecode" = the LayerNorm launches and the M-tiled products of the DECODER graph (prompt steps; the vocabulary product of more than
 // 128 sequences): kept apart from the encoder's, whose classes are the MFMA roofline of the bench line
 
@@ -202,6 +202,12 @@ struct wh_context
 	int64_t convInStride = 0, conv1Stride = 0;
 	// caches
 	f16 *crossK = nullptr, *crossV = nullptr, *selfK = nullptr, *selfV = nullptr;
+	// wh_context_create_kv8 (kv8.hip): crossK / crossV stay null; E4M3 bytes in the same [layer][window][head][T][64] order, one FP32 power-of-two scale per
+	// key row [layer][window][head][T], and the FP16 staging of ONE layer x one encoder chunk the quantizer reads (K rows, then V rows at encChunk windows)
+	bool kv8 = false;
+	uint8_t *crossK8 = nullptr, *crossV8 = nullptr;
+	float *crossKScale = nullptr, *crossVScale = nullptr;
+	f16* crossStage = nullptr;
 	// decoder activations
 	float *dx = nullptr, *logits = nullptr, *probs = nullptr;
 	f16 *dxn = nullptr, *dq = nullptr, *dattn = nullptr, *dh = nullptr;

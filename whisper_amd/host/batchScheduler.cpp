@@ -28,6 +28,7 @@
 #include "batchBoost.h"
 #include "batchNoRepeat.h"
 #include "batchSpeech.h"
+#include "batchCrossFp8.h"
 #include "optionRules.h"
 #include "decodeFallback.h"
 #include "languageDetect.h"
@@ -58,6 +59,8 @@ namespace Whisper
 	pfnBatchScorer g_batchScorer = nullptr;
 	// ... and to the speech filter of a newly admitted stream (batchSpeech.h)
 	pfnBatchSpeechPacker g_batchSpeechPacker = nullptr;
+	// ... and to the creation of a group's context with FP8 cross-attention caches (batchCrossFp8.h)
+	pfnBatchCreateKv8 g_batchCreateKv8 = nullptr;
 
 	namespace
 	{
@@ -743,6 +746,7 @@ namespace Whisper
 			iModel* const owner;
 			uint32_t maxSlots = 64, nGroups = 2;
 			int chunk = 4, lookahead = 0;
+			bool crossFp8 = false;	   // sBatchSetup::flags bit 2: the groups' contexts hold FP8 cross-attention caches (the one-window loader context stays as it is)
 			std::vector<Group> groups;
 			Shared shared;
 			// Whisper::setBatchDecodingFallback: off unless set. modesDirty: a run with the feature on left the groups' contexts in its modes
@@ -764,6 +768,10 @@ namespace Whisper
 			sSpeechFilter speechParams{};
 		public:
 			// The setters answer in one order: the argument check (optionRules.h), E_NOTIMPL without the device entry, "nothing changes", then the new version
+			int createGroupContext( wh_context** out ) const
+			{
+				return crossFp8 ? g_batchCreateKv8( model->gpu, (int)maxSlots, nullptr, out ) : wh_context_create( model->gpu, (int)maxSlots, nullptr, out );
+			}
 			HRESULT setBoosted( const sBoostedPhrases* p )
 			{
 				phraseBoost::Set set;
@@ -823,6 +831,7 @@ namespace Whisper
 				if( setup && setup->groups ) nGroups = setup->groups;
 				if( setup && setup->greedyChunk ) chunk = (int)setup->greedyChunk;
 				if( setup && ( setup->flags & 1u ) ) lookahead = 1;
+				if( setup && ( setup->flags & 2u ) ) crossFp8 = true;
 				if( const char* e = getenv( "WHISPER_BATCH_SLOTS" ) ) maxSlots = (uint32_t)std::max( 1, atoi( e ) );
 				if( const char* e = getenv( "WHISPER_BATCH_GROUPS" ) ) nGroups = (uint32_t)std::max( 1, atoi( e ) );
 				if( const char* e = getenv( "WHISPER_BATCH_CHUNK" ) ) chunk = atoi( e );
@@ -876,7 +885,7 @@ namespace Whisper
 					if( groups.empty() )
 					{
 						Group g;
-						CHECK_WH( wh_context_create( model->gpu, (int)maxSlots, nullptr, &g.gpu ) );
+						CHECK_WH( createGroupContext( &g.gpu ) );
 						groups.push_back( std::move( g ) );
 					}
 					if( !shared.loader ) CHECK_WH( wh_context_create( model->gpu, 1, nullptr, &shared.loader ) );
@@ -928,26 +937,17 @@ namespace Whisper
 				// the lock-step batch decodes greedily (one sequence per stream); beam search is iContext::runFull's (hypotheses of ONE window in lock step)
 				bool beam = params.strategy == eSamplingStrategy::BeamSearch;
 				for( uint32_t i = 0; i < count; i++ ) beam = beam || ( streams[ i ].params && streams[ i ].params->strategy == eSamplingStrategy::BeamSearch );
-				if( beam )
-				{
-					logError( "runFullBatch: eSamplingStrategy::BeamSearch is not available in a lock-step batch; use iContext::runFull" );
-					return E_NOTIMPL;
-				}
 				// AlignTokens: the scheduler keeps two batches in flight and a group's caches may be gone when a window is scanned (a follow-up)
 				bool align = params.flag( eFullParamsFlags::AlignTokens );
 				for( uint32_t i = 0; i < count; i++ ) align = align || ( streams[ i ].params && streams[ i ].params->flag( eFullParamsFlags::AlignTokens ) );
-				if( align )
-				{
-					logError( "runFullBatch: eFullParamsFlags::AlignTokens is not available in a lock-step batch; use iContext::runFull" );
-					return E_NOTIMPL;
-				}
+				CHECK( optionRules::checkBatchDecoding( "runFullBatch", beam, align ) );
 				// streams dealt evenly: no more groups than hold two streams each, every group the same number of slots
 				const uint32_t useGroups = std::max<uint32_t>( 1, std::min<uint32_t>( nGroups, count / 2 ) );
 				const uint32_t slots = std::max<uint32_t>( 1, std::min<uint32_t>( maxSlots, ( count + useGroups - 1 ) / useGroups ) );
 				while( groups.size() < useGroups )
 				{
 					Group g;
-					CHECK_WH( wh_context_create( model->gpu, (int)maxSlots, nullptr, &g.gpu ) );
+					CHECK_WH( createGroupContext( &g.gpu ) );
 					groups.push_back( std::move( g ) );
 				}
 				if( !shared.loader ) CHECK_WH( wh_context_create( model->gpu, 1, nullptr, &shared.loader ) );
@@ -1016,6 +1016,7 @@ namespace Whisper
 		}
 		const std::shared_ptr<LoadedModel> lm = mi->loaded();
 		mi->Release();
+		if( setup && ( setup->flags & 2u ) && !g_batchCreateKv8 ) return optionRules::notGiven( "createBatchRunner", "FP8 cross-attention caches" );
 		*pp = new BatchRunner( lm, model, setup );
 		return S_OK;
 	}

@@ -55,6 +55,14 @@ namespace Whisper
 			logError( "%s: minSilenceFrames, minSpeechFrames and padFrames must each lie in 0 .. 2^20 frames, and flags must be 0", name );
 			return E_INVALIDARG;
 		}
+		// What a lock-step batch does not decode, whatever its caches: beam search and AlignTokens are iContext::runFull's. A runner with FP8 cross-attention caches
+		// (sBatchSetup::flags bit 2) could serve neither -- the hypothesis-group kernel and the alignment kernels read FP16 rows -- and answers the same E_NOTIMPL.
+		inline HRESULT checkBatchDecoding( const char* name, bool beam, bool align )
+		{
+			if( beam ) logError( "%s: eSamplingStrategy::BeamSearch is not available in a lock-step batch; use iContext::runFull", name );
+			else if( align ) logError( "%s: eFullParamsFlags::AlignTokens is not available in a lock-step batch; use iContext::runFull", name );
+			return beam || align ? E_NOTIMPL : S_OK;
+		}
 		// BatchRunner without the injected device entry an option needs (batchSampling.h and its like)
 		inline HRESULT notGiven( const char* name, const char* what )
 		{

@@ -16,6 +16,7 @@
 #include "batchBoost.h"
 #include "batchNoRepeat.h"
 #include "batchSpeech.h"
+#include "batchCrossFp8.h"
 #include "optionRules.h"
 #include "languageDetect.h"
 #include "captureRate.h"
@@ -1402,6 +1403,8 @@ namespace Whisper
 	static const bool g_scorerInstalled = ( g_batchScorer = &wh_score_tokens, true );
 	// ... and to the speech filter of a newly admitted stream (batchSpeech.h)
 	static const bool g_speechPackerInstalled = ( g_batchSpeechPacker = &wh_context_speech_filter, true );
+	// ... and to the creation of a group's context with FP8 cross-attention caches (batchCrossFp8.h)
+	static const bool g_createKv8Installed = ( g_batchCreateKv8 = &wh_context_create_kv8, true );
 
 	HRESULT createContextImpl( const std::shared_ptr<LoadedModel>& model, iModel* owner, iContext** pp )
 	{
