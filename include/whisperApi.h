@@ -382,6 +382,9 @@ namespace Whisper
 								// 2 = FP8 cross-attention caches: the groups' contexts are created with wh_context_create_kv8 (E4M3 bytes and a power-of-two scale per key row:
 								//     about half the cache memory per slot and half the bytes the decode step's dominant kernel reads; the one-window loader context stays
 								//     as it is). Off unless set. Nobody has measured recognition accuracy with FP8 caches on a real checkpoint.
+								// 4 = INT8 encoder products: wh_context_set_encoder_i8 on the groups' contexts (the encoder's Q/K/V, attention-out and MLP products as
+								//     int8 x int8 -> int32 with one scale per activation row and per weight row; models whose state size is a multiple of 128). May be
+								//     combined with 2. Off unless set. Nobody has measured recognition accuracy with INT8 encoder products on a real checkpoint.
 	};
 	// {6f0c9a1e-3b52-4d7c-8e21-9a4f5c7d2b10}
 	struct iBatchRunner : public ComLight::IUnknown

@@ -173,6 +173,17 @@ WH_API int wh_context_create_hyp( wh_model* m, int maxBatch, int hypotheses, voi
  * (the hypothesis-group kernel attentionDecM reads FP16 rows). Nobody has measured recognition accuracy with FP8 caches on a real checkpoint. */
 WH_API int wh_context_create_kv8( wh_model* m, int maxBatch, void* stream, wh_context** out );
 WH_API int wh_context_create_kv8_hyp( wh_model* m, int maxBatch, int hypotheses, void* stream, wh_context** out );
+/* INT8 encoder products (whisper_amd/csrc/quant_i8.hip, gemm_i8.hip; DESIGN.md section 7 "INT8 encoder products"). on != 0: the encoder's Q/K/V, attention-out,
+ * MLP-up and MLP-down products of every layer run as int8 x int8 -> int32 on the matrix cores (gemmI8) with one FP32 scale per activation row and per weight
+ * row: s = amax / 127 (1 for a row of zeros), q = rint( x / s ) clamped to [-127, 127]; y = ( (float)acc * sa[m] ) * sw[n] takes the FP32 accumulator's place in
+ * the same epilogues. The LayerNorms in front of Q/K/V and MLP-up write int8 directly (layerNormI8), the attention output and the GELU output are quantized by
+ * quantizeRowsI8. The convolutions, the cross-K/V product and the decoder stay FP16, so FP8 caches (wh_context_create_kv8) still hold the quantization of what
+ * the FP16 cross-K/V product writes. The first enable for a model quantizes int8 copies of the four weight families on the device (contexts share them, the FP16
+ * weights stay); the first enable on a context allocates its int8 activations (wh_context_memory counts them). on == 0: the FP16 path, launch for launch what a
+ * context that never had the setting runs. Off unless set. WH_E_INVALIDARG with the reason in wh_last_error: together with WH_FLAG_PARITY_PV or
+ * WH_FLAG_PARITY_EXACT (in either order of setting), or on a model whose n_audio_state is not a multiple of 128. Nobody has measured recognition accuracy with
+ * INT8 encoder products on a real checkpoint. */
+WH_API int wh_context_set_encoder_i8( wh_context* c, int on );
 WH_API void wh_context_destroy( wh_context* c );
 /* Binds the model's device to the calling thread (every wh_* call on a model or context does it as well): the
  * counterpart of Device::setForCurrentThread (Whisper/ML/Device.cpp:163-177). Call it before wh_buffer_alloc /
@@ -772,6 +783,16 @@ typedef struct wh_gemm_encoder_args
 	float scale;
 } wh_gemm_encoder_args;
 WH_API int wh_op_gemm_encoder( void* stream, const wh_gemm_encoder_args* args, int32_t* family, int32_t* wideEpi );
+/* The INT8 encoder products at op level (device pointers). wh_op_quantize_rows_i8: FP16 rows of K values (a multiple of 128, at most 5120), ldx halves apart ->
+ * int8 [rows][K] and FP32 scale [rows], s = amax / 127 (1 for a row of zeros), q = rint( x / s ) in [-127, 127]. wh_op_layer_norm_i8: exactly
+ * wh_op_quantize_rows_i8 of what wh_op_layer_norm writes, without the FP16 row in between. */
+WH_API int wh_op_quantize_rows_i8( void* stream, const void* xF16, int64_t ldx, void* qOut, float* scaleOut, int rows, int K );
+WH_API int wh_op_layer_norm_i8( void* stream, const float* x, const float* w, const float* b, void* qOut, float* scaleOut, int rows, int d );
+/* wh_op_gemm_encoder on gemmI8: args->a int8 [M][K] (lda = K, one segment), args->w int8 [N][K], scaleA [M], scaleW [N];
+ * y = ( (float)( sum_k a[m][k] * w[n][k] ) * scaleA[m] ) * scaleW[n] (the sum exact in int32, each multiplication rounded) takes acc's place in epi 0, 1 or 3
+ * as stated above. N and K multiples of 128, any M. Any other epi, a segmented operand, or what wh_op_gemm_encoder refuses: WH_E_INVALIDARG, nothing launched.
+ * *wideEpi (may be NULL): 1 = the tiles left as 16-byte row stores, 0 = column stores (a buffer was not 16-byte aligned). */
+WH_API int wh_op_gemm_encoder_i8( void* stream, const wh_gemm_encoder_args* args, const float* scaleA, const float* scaleW, int32_t* wideEpi );
 /* The producer of conv1's operand: x16[ b * xBatchStride + ( t + 1 ) * nMels + c ] = fp16( mel_b[ c ][ off_b + t ] ) for t < rows, c < nMels, zero where
  * off_b + t is at or beyond the spectrogram's length; rows 0 and rows + 1 of every window (conv1's padding) are not written. Either offsetsHost (HOST int32 [batch],
  * NULL = all 0) with mel_b = melDev + b * melStride, FP32 [nMels][melLen]; or windowsHost (HOST [batch], what wh_encode_windows takes; a window with a NULL

@@ -44,7 +44,7 @@ EXPORTS = [
     "wh_model_arena_bytes", "wh_model_create", "wh_model_destroy", "wh_model_set_tensor", "wh_model_set_filters",
     "wh_model_finalize", "wh_model_arena", "wh_model_hparams",
     "wh_comm_runtime_check", "wh_comm_unique_id", "wh_comm_create", "wh_comm_destroy", "wh_comm_info", "wh_comm_barrier", "wh_comm_create_timeout", "wh_comm_set_timeout", "wh_comm_broadcast_i32", "wh_model_broadcast",
-    "wh_context_create", "wh_context_create_hyp", "wh_context_create_kv8", "wh_context_create_kv8_hyp", "wh_context_destroy", "wh_context_bind", "wh_context_set_flags", "wh_context_set_audio_ctx", "wh_context_synchronize", "wh_context_memory",
+    "wh_context_create", "wh_context_create_hyp", "wh_context_create_kv8", "wh_context_create_kv8_hyp", "wh_context_destroy", "wh_context_bind", "wh_context_set_flags", "wh_context_set_encoder_i8", "wh_context_set_audio_ctx", "wh_context_synchronize", "wh_context_memory",
     "wh_buffer_alloc", "wh_buffer_free", "wh_buffer_upload", "wh_buffer_upload_async", "wh_buffer_download",
     "wh_mel_spectrogram", "wh_encode", "wh_encode_windows", "wh_decode", "wh_sample_best", "wh_beam_candidates", "wh_reorder_self_cache", "wh_beam_window_start", "wh_beam_window_continue", "wh_beam_window_status", "wh_beam_window_records", "wh_decode_greedy", "wh_decode_window_start", "wh_decode_window_finish", "wh_decode_window_continue", "wh_decode_window_fetch", "wh_decode_window_start_ragged", "wh_decode_window_ready", "wh_mel_spectrogram_window", "wh_mel_spectrogram_batch", "wh_profile_enable", "wh_profile_read", "wh_debug_read", "wh_debug_step_captures", "wh_debug_probe", "wh_debug_set_tuning", "wh_debug_set_option", "wh_debug_get_option",
     "wh_op_mul_mat", "wh_op_mul_mat_gelu", "wh_op_layer_norm", "wh_op_flash_attention", "wh_op_soft_max", "wh_op_decoder_attention", "wh_op_decoder_cross_attention",
@@ -67,6 +67,7 @@ EXPORTS = [
     "wh_score_tokens", "wh_op_token_scores",
     "wh_op_gemm_encoder", "wh_op_mel_to_conv_input",
     "wh_op_quantize_kv", "wh_op_decoder_cross_attention_f8",
+    "wh_op_quantize_rows_i8", "wh_op_layer_norm_i8", "wh_op_gemm_encoder_i8",
 ]
 
 
@@ -128,6 +129,14 @@ def op_gemm_encoder(stream=None, **fields):
     fam, wide = C.c_int32(-1), C.c_int32(-1)
     check(lib().wh_op_gemm_encoder(stream, C.byref(args), C.byref(fam), C.byref(wide)))
     return fam.value, wide.value
+
+
+def op_gemm_encoder_i8(scale_a, scale_w, stream=None, **fields):
+    """wh_op_gemm_encoder_i8: op_gemm_encoder with int8 a / w and the device addresses of the row and column scales; returns wideEpi."""
+    args = GemmEncoderArgsC(**fields)
+    wide = C.c_int32(-1)
+    check(lib().wh_op_gemm_encoder_i8(stream, C.byref(args), scale_a, scale_w, C.byref(wide)))
+    return wide.value
 
 
 class TokenScoreC(C.Structure):
@@ -212,6 +221,7 @@ def lib():
         L.wh_context_destroy.restype = None
         L.wh_context_set_flags.argtypes = [vp, C.c_uint32, i32]
         L.wh_context_set_audio_ctx.argtypes = [vp, i32]
+        L.wh_context_set_encoder_i8.argtypes = [vp, i32]
         L.wh_context_memory.argtypes = [vp, C.POINTER(i64)]
         L.wh_context_synchronize.argtypes = [vp]
         L.wh_buffer_upload_async.argtypes = [vp, vp, vp, i64]
@@ -303,6 +313,9 @@ def lib():
         L.wh_score_tokens.argtypes = [vp, i32, vp, vp, vp, i32, vp]
         L.wh_op_token_scores.argtypes = [vp, vp, i64, i32, i32, vp, vp]
         L.wh_op_gemm_encoder.argtypes = [vp, C.POINTER(GemmEncoderArgsC), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.wh_op_quantize_rows_i8.argtypes = [vp, vp, i64, vp, vp, i32, i32]
+        L.wh_op_layer_norm_i8.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32]
+        L.wh_op_gemm_encoder_i8.argtypes = [vp, C.POINTER(GemmEncoderArgsC), vp, vp, C.POINTER(C.c_int32)]
         L.wh_op_mel_to_conv_input.argtypes = [vp, vp, i64, i64, vp, vp, vp, i64, i32, i32, i32]
         _lib = L
     return _lib
@@ -786,6 +799,10 @@ class HipContext:
 
     def set_flags(self, flags: int, parity_threads: int = 1):
         check(lib().wh_context_set_flags(self.handle, flags, parity_threads))
+
+    def set_encoder_i8(self, on: bool = True):
+        """wh_context_set_encoder_i8: the encoder's Q/K/V, attention-out and MLP products as int8 x int8 -> int32 with a scale per row (off unless set)."""
+        check(lib().wh_context_set_encoder_i8(self.handle, 1 if on else 0))
 
     def step_captures(self) -> int:
         """Decode-step graphs this context has captured since it was created (wh_debug_step_captures)."""

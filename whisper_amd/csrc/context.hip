@@ -47,6 +47,54 @@ namespace wh
 		const hipError_t e = hipFree( a.base );
 		return e == hipSuccess ? bad : hipFail( e, "hipFree", __FILE__, __LINE__ );
 	}
+
+	// The int8 copies of the encoder's weights (wh_context_set_encoder_i8): per layer Q/K/V [3d][d], out [d][d], MLP up [4d][d], MLP down [d][4d] as bytes, then
+	// one FP32 scale per output row of each, quantized by quantizeRowsI8 from the FP16 arena. Once per model, under the model's lock; the call returns when the
+	// copies are complete, so a context on any stream may read them.
+	int ensureEncoderI8Weights( wh_model* m )
+	{
+		std::lock_guard<std::mutex> lock( m->i8Mutex );
+		if( m->i8Weights.base ) return 0;
+		const int64_t d = m->hp.n_audio_state;
+		const int nl = m->hp.n_audio_layer;
+		std::vector<wh_model::EncLayerI8> layers( (size_t)nl );
+		int64_t bytes = 0, scales = 0;
+		for( wh_model::EncLayerI8& l : layers )
+		{
+			l.wqkv = bytes; bytes += 3 * d * d;
+			l.wo = bytes; bytes += d * d;
+			l.w1 = bytes; bytes += 4 * d * d;
+			l.w2 = bytes; bytes += 4 * d * d;
+			l.sqkv = scales; scales += 3 * d;
+			l.so = scales; scales += d;
+			l.s1 = scales; scales += 4 * d;
+			l.s2 = scales; scales += d;
+		}
+		Allocation a;
+		WH_HIP( guardedAlloc( a, bytes + scales * 4, 0, "int8 encoder weights", nullptr ) );
+		int8_t* const q = (int8_t*)a.body;
+		float* const s = (float*)( (uint8_t*)a.body + bytes );	   // bytes is a multiple of 128 * 128
+		int rc = 0;
+		for( int il = 0; il < nl && !rc; il++ )
+		{
+			const EncLayer& e = m->L.enc[ il ];
+			const wh_model::EncLayerI8& l = layers[ (size_t)il ];
+			rc = rc ? rc : launchQuantizeRowsI8( m->at<f16>( e.wqkv ), d, q + l.wqkv, s + l.sqkv, (int)( 3 * d ), (int)d, nullptr );
+			rc = rc ? rc : launchQuantizeRowsI8( m->at<f16>( e.wo ), d, q + l.wo, s + l.so, (int)d, (int)d, nullptr );
+			rc = rc ? rc : launchQuantizeRowsI8( m->at<f16>( e.w1 ), d, q + l.w1, s + l.s1, (int)( 4 * d ), (int)d, nullptr );
+			rc = rc ? rc : launchQuantizeRowsI8( m->at<f16>( e.w2 ), 4 * d, q + l.w2, s + l.s2, (int)d, (int)( 4 * d ), nullptr );
+		}
+		const hipError_t e = hipStreamSynchronize( nullptr );
+		if( rc || e != hipSuccess )
+		{
+			(void)guardedFree( a );
+			return rc ? rc : hipFail( e, "quantizeRowsI8(weights)", __FILE__, __LINE__ );
+		}
+		m->i8ScalesAt = bytes;
+		m->i8Layers = std::move( layers );
+		m->i8Weights = a;
+		return 0;
+	}
 }
 namespace
 {
@@ -331,11 +379,43 @@ int wh_context_set_flags( wh_context* c, uint32_t flags, int parityThreads )
 		setError( "context_set_flags: the parity modes restate the reference's FP16 caches and are not available on a context with FP8 cross-attention caches" );
 		return WH_E_INVALIDARG;
 	}
+	if( c->encI8 && ( flags & ( WH_FLAG_PARITY_EXACT | WH_FLAG_PARITY_PV ) ) )
+	{
+		setError( "context_set_flags: the parity modes restate the reference's FP16 products and are not available while the INT8 encoder products are on" );
+		return WH_E_INVALIDARG;
+	}
 	WH_CHECK( filtersAllowFlags( c, flags ) );
 	c->flags = flags;
 	// WH_FLAG_PARITY_EXACT with 0 threads: the decoder's P.V as ONE correctly rounded sum per output (double accumulation) instead of the reference's
 	// FP16 accumulation -- the thread-count-independent value every thread count of the reference approximates
 	c->parityThreads = parityThreads > 0 ? parityThreads : ( ( flags & WH_FLAG_PARITY_EXACT ) && parityThreads == 0 ? 0 : 1 );
+	return 0;
+}
+
+int wh_context_set_encoder_i8( wh_context* c, int on )
+{
+	if( !c ) return WH_E_INVALIDARG;
+	if( !on ) { c->encI8 = false; return 0; }
+	const wh_hparams& hp = c->m->hp;
+	if( c->flags & ( WH_FLAG_PARITY_EXACT | WH_FLAG_PARITY_PV ) )
+	{
+		setError( "context_set_encoder_i8: the parity modes restate the reference's FP16 products and are not available together with the INT8 encoder products" );
+		return WH_E_INVALIDARG;
+	}
+	if( ( hp.n_audio_state % 128 ) != 0 || 4 * hp.n_audio_state > 5120 )
+	{
+		setError( "context_set_encoder_i8: the INT8 encoder products need n_audio_state to be a multiple of 128, at most 1280" );
+		return WH_E_INVALIDARG;
+	}
+	WH_BIND( c->m );
+	WH_CHECK( ensureEncoderI8Weights( c->m ) );
+	// first enable: the int8 activations and their row scales, sized like xn and h
+	const int64_t rowsE = (int64_t)c->encChunk * hp.n_audio_ctx, d = hp.n_audio_state;
+	if( !c->xq ) WH_CHECK( c->alloc( c->xq, rowsE * d, wh_context::DONT_CARE, "xq" ) );
+	if( !c->hq ) WH_CHECK( c->alloc( c->hq, rowsE * 4 * d, wh_context::DONT_CARE, "hq" ) );
+	if( !c->xqScale ) WH_CHECK( c->alloc( c->xqScale, rowsE, wh_context::DONT_CARE, "xqScale" ) );
+	if( !c->hqScale ) WH_CHECK( c->alloc( c->hqScale, rowsE, wh_context::DONT_CARE, "hqScale" ) );
+	c->encI8 = true;
 	return 0;
 }
 

@@ -31,6 +31,23 @@ int wh::lnP( wh_context* c, const float* x, const float* w, const float* b, f16*
 	return profiled( c, decoder ? KC_LAYER_NORM_DEC : KC_LAYER_NORM, 8.0 * rows * d, 6.0 * rows * d, [ & ]() { return launchLayerNorm( x, w, b, out, rows, d, c->stream ); } );
 }
 
+// wh_context_set_encoder_i8: a product on gemmI8 (g carries the shape and the epilogue, its FP16 operands are not read), and the two quantizer passes
+static int gemmI8P( wh_context* c, const GemmArgs& g, const int8_t* A8, const float* sa, const int8_t* W8, const float* sw )
+{
+	GemmI8Args p = { g, A8, W8, sa, sw };
+	p.g.A = nullptr; p.g.W = nullptr;
+	const double bytes = (double)g.N * g.K + (double)g.M * g.K + 4.0 * ( g.M + g.N ) + ( g.out32 ? 4.0 : 2.0 ) * g.M * g.N;
+	return profiled( c, KC_GEMM_I8, 2.0 * g.M * g.N * g.K, bytes, [ & ]() { return launchGemmI8( p, c->stream ); } );
+}
+static int quantizeP( wh_context* c, const f16* x, int8_t* q, float* scale, int rows, int K )
+{
+	return profiled( c, KC_QUANT_I8, 0.0, rows * ( 3.0 * K + 4.0 ), [ & ]() { return launchQuantizeRowsI8( x, K, q, scale, rows, K, c->stream ); } );
+}
+static int lnI8P( wh_context* c, const float* x, const float* w, const float* b, int rows, int d )
+{
+	return profiled( c, KC_QUANT_I8, 8.0 * rows * d, rows * ( 5.0 * d + 4.0 ), [ & ]() { return launchLayerNormI8( x, w, b, c->xq, c->xqScale, rows, d, c->stream ); } );
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // encoder
 // ------------------------------------------------------------------------------------------------------------------
@@ -155,14 +172,24 @@ static int encodeImpl( wh_context* c, const float* melDev, int batch, int64_t me
 	for( int il = 0; il < hp.n_audio_layer; il++ )
 	{
 		const EncLayer& e = L.enc[ il ];
-		WH_CHECK( lnP( c, c->x, m->at<float>( e.ln1w ), m->at<float>( e.ln1b ), c->xn, M, d ) );
+		// INT8 encoder products (wh_context_set_encoder_i8): each of the layer's four products branches on the setting. The LayerNorms write int8 rows and row
+		// scales directly; the attention output and the GELU output, whose row maxima span the tiles of their producers, go through quantizeRowsI8
+		const bool i8 = c->encI8;
+		const wh_model::EncLayerI8* const q8 = i8 ? &m->i8Layers[ (size_t)il ] : nullptr;
+		if( i8 )
+			WH_CHECK( lnI8P( c, c->x, m->at<float>( e.ln1w ), m->at<float>( e.ln1b ), M, d ) );
+		else
+			WH_CHECK( lnP( c, c->x, m->at<float>( e.ln1w ), m->at<float>( e.ln1b ), c->xn, M, d ) );
 		{
 			GemmArgs g = plainGemm( c->xn, m->at<f16>( e.wqkv ), M, 3 * d, d );
 			g.epi = EPI_QKV_ENC;
 			g.bias = m->at<float>( e.bqkv );
 			g.q = c->q; g.k = c->k; g.v = c->vT;
 			g.T = T; g.Tpad = c->Tpad; g.H = H; g.B = batch;
-			WH_CHECK( gemmP( c, g, false ) );
+			if( i8 )
+				WH_CHECK( gemmI8P( c, g, c->xq, c->xqScale, m->i8At( q8->wqkv ), m->i8Scale( q8->sqkv ) ) );
+			else
+				WH_CHECK( gemmP( c, g, false ) );
 		}
 		WH_CHECK( profiled( c, KC_ATTN_ENC, 4.0 * batch * H * (double)T * T * HEAD_DIM, 2.0 * 4.0 * batch * H * (double)T * HEAD_DIM,
 			[ & ]() { return launchAttentionEnc( c->q, c->k, c->vT, c->attn, batch, H, T, c->Tpad, ( c->flags & WH_FLAG_PARITY_PV ) != 0, m->at<f16>( L.expTab ), st ); } ) );
@@ -172,22 +199,40 @@ static int encodeImpl( wh_context* c, const float* melDev, int batch, int64_t me
 			g.epi = EPI_F32;
 			g.bias = m->at<float>( e.bo );
 			g.res = c->x; g.out32 = c->x;
-			WH_CHECK( gemmP( c, g, false ) );
+			if( i8 )
+			{
+				WH_CHECK( quantizeP( c, c->attn, c->xq, c->xqScale, M, d ) );
+				WH_CHECK( gemmI8P( c, g, c->xq, c->xqScale, m->i8At( q8->wo ), m->i8Scale( q8->so ) ) );
+			}
+			else
+				WH_CHECK( gemmP( c, g, false ) );
 		}
-		WH_CHECK( lnP( c, c->x, m->at<float>( e.ln2w ), m->at<float>( e.ln2b ), c->xn, M, d ) );
+		if( i8 )
+			WH_CHECK( lnI8P( c, c->x, m->at<float>( e.ln2w ), m->at<float>( e.ln2b ), M, d ) );
+		else
+			WH_CHECK( lnP( c, c->x, m->at<float>( e.ln2w ), m->at<float>( e.ln2b ), c->xn, M, d ) );
 		{
 			GemmArgs g = plainGemm( c->xn, m->at<f16>( e.w1 ), M, 4 * d, d );
 			g.epi = EPI_F16_GELU;
 			g.bias = m->at<float>( e.b1 );
 			g.out16 = c->h;
-			WH_CHECK( gemmP( c, g, false ) );
+			if( i8 )
+				WH_CHECK( gemmI8P( c, g, c->xq, c->xqScale, m->i8At( q8->w1 ), m->i8Scale( q8->s1 ) ) );
+			else
+				WH_CHECK( gemmP( c, g, false ) );
 		}
 		{
 			GemmArgs g = plainGemm( c->h, m->at<f16>( e.w2 ), M, d, 4 * d );
 			g.epi = EPI_F32;
 			g.bias = m->at<float>( e.b2 );
 			g.res = c->x; g.out32 = c->x;
-			WH_CHECK( gemmP( c, g, false ) );
+			if( i8 )
+			{
+				WH_CHECK( quantizeP( c, c->h, c->hq, c->hqScale, M, 4 * d ) );
+				WH_CHECK( gemmI8P( c, g, c->hq, c->hqScale, m->i8At( q8->w2 ), m->i8Scale( q8->s2 ) ) );
+			}
+			else
+				WH_CHECK( gemmP( c, g, false ) );
 		}
 	}
 	WH_CHECK( lnP( c, c->x, m->at<float>( L.lnPostW ), m->at<float>( L.lnPostB ), c->xn, M, d ) );

@@ -164,6 +164,26 @@ namespace wh
 	int launchGemmVariant( const GemmArgs& a, int variant, hipStream_t stream );	// tile-shape experiments, EPI_F32 only
 
 	// ---------------------------------------------------------------------------------------------------------------
+	// INT8 encoder products (quant_i8.hip, gemm_i8.hip; DESIGN.md section 7 "INT8 encoder products"). Symmetric int8 with one FP32 scale per row of K values:
+	// s = amax / 127 (1 for a row of zeros), q = rint( x / s ) clamped to [-127, 127], both divisions IEEE FP32. Weights [N][K] by the same rule per output row.
+	// ---------------------------------------------------------------------------------------------------------------
+	// x: FP16 rows of K values (a multiple of 128, at most 5120), ldx halves apart -> q int8 [rows][K], scale [rows]
+	int launchQuantizeRowsI8( const f16* x, long long ldx, int8_t* q, float* scale, int rows, int K, hipStream_t stream );
+	// quantizeRowsI8 of what launchLayerNorm would have written, bit for bit; the FP16 row is never stored
+	int launchLayerNormI8( const float* x, const float* w, const float* b, int8_t* q, float* scale, int rows, int d, hipStream_t stream );
+	// y[m][n] = ( (float)( sum_k A8[m][k] * W8[n][k] ) * sa[m] ) * sw[n], then g's epilogue (EPI_F32, EPI_F16_GELU or EPI_QKV_ENC) on y. Of g: M, N, K, lda (bytes
+	// between the rows of A8), epi and the epilogue's fields; g.A, g.W and g.scale are not read. Any M; N and K multiples of 128.
+	struct GemmI8Args
+	{
+		GemmArgs g;
+		const int8_t* A8;	  // [M] rows of K bytes, g.lda apart
+		const int8_t* W8;	  // [N][K]
+		const float* sa;	  // [M]
+		const float* sw;	  // [N]
+	};
+	int launchGemmI8( const GemmI8Args& a, hipStream_t stream );
+
+	// ---------------------------------------------------------------------------------------------------------------
 	// elementwise / normalisation (elementwise.hip)
 	// ---------------------------------------------------------------------------------------------------------------
 	// out16[row] = fp16( norm(x[row]) * w + b ); rows of length d (multiple of 4, <= 2048). norm.hlsl + fmaRepeat1.hlsl

@@ -351,6 +351,51 @@ int wh_op_gemm_encoder( void* stream, const wh_gemm_encoder_args* p, int32_t* fa
 	return 0;
 }
 
+// ---- the INT8 encoder products (quant_i8.hip, gemm_i8.hip): the same checks, then launchGemmI8's own
+int wh_op_gemm_encoder_i8( void* stream, const wh_gemm_encoder_args* p, const float* scaleA, const float* scaleW, int32_t* wideEpi )
+{
+	const auto bad = []( const char* what ) { setError( std::string( "gemm_encoder_i8: " ) + what ); return (int)WH_E_INVALIDARG; };
+	if( !p || !p->a || !p->w || !scaleA || !scaleW ) return bad( "null argument" );
+	if( p->M <= 0 || p->N <= 0 || p->K <= 0 || ( p->N % 128 ) != 0 || ( p->K % 128 ) != 0 ) return bad( "M must be positive, N and K positive multiples of 128" );
+	if( p->lda != p->K || p->Mb < p->M || p->aBatchStride != 0 || p->cBatchStride != 0 ) return bad( "the int8 operand is one segment of dense rows (lda = K, Mb >= M, no batch strides)" );
+	GemmI8Args q = { plainGemm( nullptr, nullptr, p->M, p->N, p->K ), (const int8_t*)p->a, (const int8_t*)p->w, scaleA, scaleW };
+	GemmArgs& g = q.g;
+	g.ldc = p->ldc; g.epi = p->epi; g.bias = p->bias;
+	const long long d = 64ll * p->H;
+	switch( p->epi )
+	{
+	case EPI_F32:
+	case EPI_F16_GELU:
+		if( p->epi == EPI_F32 ? !p->out32 : ( !p->out16 || !p->bias ) ) return bad( "the epilogue's output (and the GELU's bias) must not be null" );
+		if( p->ldc < p->N ) return bad( "ldc >= N" );
+		g.res = p->epi == EPI_F32 ? p->res : nullptr; g.out32 = p->out32; g.out16 = (f16*)p->out16;
+		break;
+	case EPI_QKV_ENC:
+		if( !p->q || !p->k || !p->v || !p->bias ) return bad( "Q/K/V needs q, k, v and bias" );
+		if( p->H <= 0 || p->N != 3 * d ) return bad( "Q/K/V: N must be 3 * 64 * H" );
+		if( p->T <= 0 || ( p->M % p->T ) != 0 ) return bad( "M % T must be 0" );
+		if( p->Tpad < p->T || ( p->Tpad % 16 ) != 0 ) return bad( "Tpad must be a multiple of 16 and at least T" );
+		g.q = (f16*)p->q; g.k = (f16*)p->k; g.v = (f16*)p->v;
+		g.T = p->T; g.Tpad = p->Tpad; g.H = p->H; g.B = p->M / p->T;
+		break;
+	default:
+		return bad( "the INT8 path has the epilogues 0, 1 and 3" );
+	}
+	WH_CHECK( launchGemmI8( q, (hipStream_t)stream ) );
+	if( wideEpi ) *wideEpi = t_gemmWideEpi;
+	return 0;
+}
+
+int wh_op_quantize_rows_i8( void* stream, const void* xF16, int64_t ldx, void* qOut, float* scaleOut, int rows, int K )
+{
+	return launchQuantizeRowsI8( (const f16*)xF16, ldx, (int8_t*)qOut, scaleOut, rows, K, (hipStream_t)stream );
+}
+
+int wh_op_layer_norm_i8( void* stream, const float* x, const float* w, const float* b, void* qOut, float* scaleOut, int rows, int d )
+{
+	return launchLayerNormI8( x, w, b, (int8_t*)qOut, scaleOut, rows, d, (hipStream_t)stream );
+}
+
 int wh_op_mel_to_conv_input( void* stream, const float* melDev, int64_t melStride, int64_t melLen, const int32_t* offsetsHost, const wh_mel_window* windowsHost,
 	void* x16, int64_t xBatchStride, int nMels, int rows, int batch )
 {

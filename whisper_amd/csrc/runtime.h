@@ -90,6 +90,16 @@ struct wh_model
 	bool filtersSet = false;
 	Allocation staging = { nullptr, nullptr, 0, nullptr };	   // raw blocks of the quantized tensor being loaded; freed by wh_model_finalize / wh_model_destroy
 	int device = 0;	   // the HIP device the arena lives on; every entry point binds the calling thread to it
+	// wh_context_set_encoder_i8 (quant_i8.hip, gemm_i8.hip): int8 copies of the encoder's four weight families with one FP32 scale per output row, made on the device
+	// from the FP16 arena by the first context that turns the setting on; every context of the model shares them, the FP16 weights stay. i8Layers[ il ]: byte
+	// offsets of the layer's matrices into i8Weights.body, and float offsets of their scales behind them (i8Scale)
+	struct EncLayerI8 { int64_t wqkv, wo, w1, w2, sqkv, so, s1, s2; };
+	Allocation i8Weights = { nullptr, nullptr, 0, nullptr };
+	int64_t i8ScalesAt = 0;
+	std::vector<EncLayerI8> i8Layers;
+	std::mutex i8Mutex;
+	const int8_t* i8At( int64_t off ) const { return (const int8_t*)i8Weights.body + off; }
+	const float* i8Scale( int64_t off ) const { return (const float*)( (const uint8_t*)i8Weights.body + i8ScalesAt ) + off; }
 	std::vector<int32_t> alignHeads;	   // wh_model_set_alignment_heads: (layer, head) pairs, ascending; empty = every head of the upper half of the decoder
 	template<class T> T* at( int64_t off ) const { return (T*)( arena + off ); }
 	size_t expectedTensors() const { return 11 + 15 * (size_t)hp.n_audio_layer + 24 * (size_t)hp.n_text_layer; }
@@ -107,13 +117,14 @@ namespace wh { int bindDevice( const wh_model* m ); }
 enum eKernelClass : int
 {
 	KC_GEMM_TILED = 0, KC_GEMM_SKINNY, KC_GEMV, KC_ATTN_ENC, KC_ATTN_DEC, KC_ATTN_DEC_CROSS, KC_SELF_BLOCK, KC_LAYER_NORM, KC_MEL, KC_MEL_TO_CONV, KC_EMBED, KC_SOFTMAX,
-	KC_SAMPLE, KC_EVENT_PAIR, KC_LAYER_NORM_DEC, KC_GEMM_DEC, KC_QUANT_KV, KC_COUNT
+	KC_SAMPLE, KC_EVENT_PAIR, KC_LAYER_NORM_DEC, KC_GEMM_DEC, KC_QUANT_KV, KC_GEMM_I8, KC_QUANT_I8, KC_COUNT
 };
 // "attentionDecCross" = cross-attention launches (attentionDecG<NQ, true> / <NQ, false> with group or nKeys = n_audio_ctx),
 // "attentionDec" = causal self-attention; "eventPair" = the calibration launches of wh_profile_enable (an empty kernel
 // between the same two event records: what the bracket itself costs, to be subtracted from every per-launch average).
 static const char* const kernelClassNames[ KC_COUNT ] = { "gemmTiled", "gemmSkinny", "gemvFused", "attentionEnc", "attentionDec", "attentionDecCross",
-	"selfBlockDec", "layerNorm", "mel", "melToConvInput", "embed", "vocabSoftMax", "softMaxSample", "eventPair", "layerNormDec", "gemmDecode", "quantizeCrossKV" };
+	"selfBlockDec", "layerNorm", "mel", "melToConvInput", "embed", "vocabSoftMax", "softMaxSample", "eventPair", "layerNormDec", "gemmDecode", "quantizeCrossKV", "gemmI8", "quantizeRowsI8" };
+// "gemmI8" / "quantizeRowsI8" = the products and the quantizer passes (layerNormI8 included) of wh_context_set_encoder_i8
 // "layerNormDec" / "gemmDecode" = the LayerNorm launches and the M-tiled products of the DECODER graph (prompt steps; the vocabulary product of more than
 // 128 sequences): kept apart from the encoder's, whose classes are the MFMA roofline of the bench line
 
@@ -208,6 +219,11 @@ struct wh_context
 	uint8_t *crossK8 = nullptr, *crossV8 = nullptr;
 	float *crossKScale = nullptr, *crossVScale = nullptr;
 	f16* crossStage = nullptr;
+	// wh_context_set_encoder_i8: the encoder's QKV, out, MLP-up and MLP-down products on gemmI8. xq / xqScale: the int8 rows and row scales of the LayerNorm
+	// output, then of the attention output (the first is consumed before the second is formed); hq / hqScale: of the GELU output. Allocated by the first enable.
+	bool encI8 = false;
+	int8_t *xq = nullptr, *hq = nullptr;
+	float *xqScale = nullptr, *hqScale = nullptr;
 	// decoder activations
 	float *dx = nullptr, *logits = nullptr, *probs = nullptr;
 	f16 *dxn = nullptr, *dq = nullptr, *dattn = nullptr, *dh = nullptr;
@@ -447,6 +463,7 @@ namespace wh
 	int gemmP( wh_context* c, const GemmArgs& g, bool skinny, bool decoder = false );
 	int lnP( wh_context* c, const float* x, const float* w, const float* b, f16* out, int rows, int d, bool decoder = false );
 	GemmArgs plainGemm( const f16* A, const f16* W, int M, int N, int K );
+	int ensureEncoderI8Weights( wh_model* m );	   // context.hip: the model's int8 encoder weights, made once
 	int exactTables( wh_context* c );
 	int encodeExact( wh_context* c, const float* melDev, int batch, int64_t melLen, int64_t melStride, const int32_t* melOffsets, const wh_mel_window* wins );
 	int decodeExact( wh_context* c, int batch, int nTokens, int nPast );

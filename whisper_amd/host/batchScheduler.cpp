@@ -29,6 +29,7 @@
 #include "batchNoRepeat.h"
 #include "batchSpeech.h"
 #include "batchCrossFp8.h"
+#include "batchEncoderI8.h"
 #include "optionRules.h"
 #include "decodeFallback.h"
 #include "languageDetect.h"
@@ -61,6 +62,8 @@ namespace Whisper
 	pfnBatchSpeechPacker g_batchSpeechPacker = nullptr;
 	// ... and to the creation of a group's context with FP8 cross-attention caches (batchCrossFp8.h)
 	pfnBatchCreateKv8 g_batchCreateKv8 = nullptr;
+	// ... and to the INT8 encoder products of a group's context (batchEncoderI8.h)
+	pfnBatchSetEncoderI8 g_batchSetEncoderI8 = nullptr;
 
 	namespace
 	{
@@ -747,6 +750,7 @@ namespace Whisper
 			uint32_t maxSlots = 64, nGroups = 2;
 			int chunk = 4, lookahead = 0;
 			bool crossFp8 = false;	   // sBatchSetup::flags bit 2: the groups' contexts hold FP8 cross-attention caches (the one-window loader context stays as it is)
+			bool encoderI8 = false;	   // sBatchSetup::flags bit value 4: the groups' contexts run the encoder's products in INT8 (may be combined with bit 2)
 			std::vector<Group> groups;
 			Shared shared;
 			// Whisper::setBatchDecodingFallback: off unless set. modesDirty: a run with the feature on left the groups' contexts in its modes
@@ -770,7 +774,15 @@ namespace Whisper
 			// The setters answer in one order: the argument check (optionRules.h), E_NOTIMPL without the device entry, "nothing changes", then the new version
 			int createGroupContext( wh_context** out ) const
 			{
-				return crossFp8 ? g_batchCreateKv8( model->gpu, (int)maxSlots, nullptr, out ) : wh_context_create( model->gpu, (int)maxSlots, nullptr, out );
+				const int rc = crossFp8 ? g_batchCreateKv8( model->gpu, (int)maxSlots, nullptr, out ) : wh_context_create( model->gpu, (int)maxSlots, nullptr, out );
+				if( rc || !encoderI8 ) return rc;
+				const int rc8 = g_batchSetEncoderI8( *out, 1 );
+				if( rc8 )
+				{
+					wh_context_destroy( *out );
+					*out = nullptr;
+				}
+				return rc8;
 			}
 			HRESULT setBoosted( const sBoostedPhrases* p )
 			{
@@ -832,6 +844,7 @@ namespace Whisper
 				if( setup && setup->greedyChunk ) chunk = (int)setup->greedyChunk;
 				if( setup && ( setup->flags & 1u ) ) lookahead = 1;
 				if( setup && ( setup->flags & 2u ) ) crossFp8 = true;
+				if( setup && ( setup->flags & 4u ) ) encoderI8 = true;
 				if( const char* e = getenv( "WHISPER_BATCH_SLOTS" ) ) maxSlots = (uint32_t)std::max( 1, atoi( e ) );
 				if( const char* e = getenv( "WHISPER_BATCH_GROUPS" ) ) nGroups = (uint32_t)std::max( 1, atoi( e ) );
 				if( const char* e = getenv( "WHISPER_BATCH_CHUNK" ) ) chunk = atoi( e );
@@ -1017,6 +1030,7 @@ namespace Whisper
 		const std::shared_ptr<LoadedModel> lm = mi->loaded();
 		mi->Release();
 		if( setup && ( setup->flags & 2u ) && !g_batchCreateKv8 ) return optionRules::notGiven( "createBatchRunner", "FP8 cross-attention caches" );
+		if( setup && ( setup->flags & 4u ) && !g_batchSetEncoderI8 ) return optionRules::notGiven( "createBatchRunner", "INT8 encoder products" );
 		*pp = new BatchRunner( lm, model, setup );
 		return S_OK;
 	}
