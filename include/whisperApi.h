@@ -506,6 +506,22 @@ namespace Whisper
 	WHISPER_EXPORT HRESULT setNoRepeatNgram( iContext* context, int n );
 	// One n for all streams of every later run of the runner. E_INVALIDARG as above; E_NOTIMPL for n != 0 where the scheduler was built without the device's filter.
 	WHISPER_EXPORT HRESULT setBatchNoRepeatNgram( iBatchRunner* runner, int n );
+	// Extension: token alternatives. k = 0: off, the state of every new context; 1 .. 8: every later run of the context keeps, for every token in its results, the
+	// k likeliest tokens of the decoding step that emitted it and their log-probabilities under the model's filtered distribution at temperature 1 (computed on the
+	// device next to the sampler: wh_context_set_alternatives), descending, equal logits in ascending id; { -1, -inf } where fewer than k tokens were possible.
+	// THE EMITTED TOKEN NEED NOT BE ENTRY 0, nor be listed: the sampler's timestamp rule and a sampled attempt of the decoding fallback choose otherwise. With the
+	// decoding fallback on, the records are those of the attempt that was accepted; runStreamed and the pieces of runCapture keep those of the last run, like
+	// getWindowStats. With k != 0 a run with eSamplingStrategy::BeamSearch answers E_NOTIMPL. Not covered: the batch runner, scoreTokens, the command-line tools.
+	// E_INVALIDARG for k outside 0 .. 8 and for a context of another library.
+	struct sTokenAlternative
+	{
+		int32_t id;
+		float logprob;
+	};
+	WHISPER_EXPORT HRESULT setTokenAlternatives( iContext* context, uint32_t k );
+	// The records of the last run, flat: k per token, in the order of the results' token array. cap: the capacity of `out` in records; *count: tokens x k (out may be
+	// nullptr to ask for it; E_BOUNDS when the capacity is too small). *k: the k of that run. Empty when the run had the setting off.
+	WHISPER_EXPORT HRESULT getTokenAlternatives( const iContext* context, sTokenAlternative* out, uint32_t cap, uint32_t* count, uint32_t* k );
 	// One text phrase as rows for sBoostedPhrases: the text as written and, when it does not begin with a space, also the text behind one space, which is how a
 	// word is spelled in mid-sentence; rows that come out equal collapse. tokens [ cap ][ 16 ], lengths [ cap ]; count in: cap, out: the rows written (1 or 2);
 	// E_BOUNDS when cap is too small. E_INVALIDARG, the log naming the phrase, when a spelling is empty or longer than 16 tokens.

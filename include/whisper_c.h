@@ -127,6 +127,11 @@ int32_t whisperc_phrase_spellings( void* model, const char* text, int32_t* token
  * n-gram its window has already sampled; 0 = off, the state of every new context and runner. */
 int32_t whisperc_set_no_repeat_ngram( void* ctx, int32_t n );
 int32_t whisperc_batch_set_no_repeat_ngram( void* runner, int32_t n );
+/* Token alternatives (Whisper::setTokenAlternatives / getTokenAlternatives of whisperApi.h): k = 1 .. 8 = every later run keeps the k likeliest tokens, with their
+ * log-probabilities, of the step that emitted each token of its results; 0 = off. whisperc_alternatives: out = sTokenAlternative [cap] (may be NULL), *count =
+ * tokens x k of the last run in the order of the results' token array, *k = that run's k. */
+int32_t whisperc_set_alternatives( void* ctx, uint32_t k );
+int32_t whisperc_alternatives( void* ctx, void* out, uint32_t cap, uint32_t* count, uint32_t* k );
 /* Speech only (Whisper::setSpeechFilter / setBatchSpeechFilter / speechSpans / getSpeechSpans / getResultSpeechSpans of whisperApi.h): on != 0 = every later run
  * finds the speech with the voice-activity detector, transcribes only that and reports times on the recording's clock. Parameters in frames of 256 samples,
  * 0 = the defaults 125 / 16 / 25; negative or above 2^20 is E_INVALIDARG. on == 0 is the state of every new context and runner.

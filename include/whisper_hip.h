@@ -652,6 +652,33 @@ WH_API int wh_boost_step_host( const int32_t* tables, int64_t nInts, int32_t sta
 WH_API int wh_context_set_no_repeat( wh_context* c, int n );
 WH_API int wh_context_set_no_speech( wh_context* c, int on );
 WH_API int wh_decode_window_no_speech( wh_context* c, float* out );
+/* Token alternatives: the k likeliest tokens at each decoded position (DESIGN.md section 7 "Token alternatives" holds the definition; tests/alternatives_ref.py
+ * restates it in float64). For a row x of FP32 logits, lse = max + log( sum exp( x - max ) ) with the sum in double; listed are the k largest logits, descending,
+ * equal values in ascending id, each as { id, logprob = float( double( x[ id ] ) - lse ) }. -inf and NaN entries are never listed; when fewer than k entries are
+ * finite the remaining records are { -1, -inf }. A row's records depend on that row alone -- not on the other rows, on its place among them or on k: the first j
+ * records at k = j are the first j at k = 8, bit for bit.
+ *   wh_context_set_alternatives  k = 0 is the state of every new context, 1 .. 8 turns it on: every sample of the device-side loop then queues ONE launch on the
+ *     row its sampler read -- wh_decode_window_start, _start_ragged (the prompt step's first sample included) and _continue; greedy, tempered and per-row steps
+ *     alike -- behind the filters: the records describe the model's filtered distribution at temperature 1, whatever temperature the draw uses. THE EMITTED TOKEN
+ *     NEED NOT BE ENTRY 0, nor listed at all: sampleBest's timestamp rule and special-token rounds, and a tempered draw, choose otherwise. The records of sample s
+ *     of sequence b go to a device ring [n_text_ctx][sequences][k], indexed like the sampler's wh_token_data with the step index read from device memory; it
+ *     is allocated (for k = 8) by the first call that turns the setting on and never again. k is an argument of the kernel and a part of the captured step graphs'
+ *     key; the graphs of k = 0 stay next to those of one k above 0, so turning the setting on and off again recaptures nothing. The call waits for the stream.
+ *     WH_E_INVALIDARG for k outside 0 .. 8, and to turn it on on a hypothesis-group context, under WH_FLAG_PARITY_EXACT (wh_context_set_flags in turn refuses
+ *     that flag while the setting is on) or for a vocabulary above 53248 (the kernel holds the row in registers). A context that never calls it allocates,
+ *     captures and launches what it always did. Not covered: wh_decode and the beam entries; the steps of wh_decode_greedy are the window's steps, so with the
+ *     setting on they launch the kernel and write the ring too (in bounds, keyed on k), and nothing reads those records. A +inf logit is not supported: it is
+ *     listed, and every log-probability of its row is NaN. A change of k while a window is in progress ends the reading of that window's records.
+ *   wh_decode_window_alternatives  the records of samples [first, first + count) of the window in progress: HOST [count][batch][k]. Waits for those samples only,
+ *     like wh_decode_window_fetch; call it before wh_decode_window_finish, which ends the window. WH_E_INVALIDARG when the window was started with the setting off
+ *     or the setting changed since. */
+typedef struct wh_token_alternative
+{
+	int32_t id;
+	float logprob;
+} wh_token_alternative;
+WH_API int wh_context_set_alternatives( wh_context* c, int k );
+WH_API int wh_decode_window_alternatives( wh_context* c, int first, int count, wh_token_alternative* outHost );
 
 /* Per-kernel-class GPU timings, the counterpart of the reference's GpuProfiler / iContext::timingsPrint
  * (Whisper/Utils/GpuProfiler.h:21-188, Whisper/Whisper/ContextImpl.misc.cpp:170-182). hipEvent pairs around every launch
@@ -867,6 +894,11 @@ WH_API int wh_op_lang_probs( void* stream, const float* logits, int rows, int nV
  * option "score_regs" 0): the same bits. The targets are downloaded and checked first, so the call waits for the stream: a target outside [0, nVocab),
  * rowStride < nVocab, a null pointer or rows < 1 is WH_E_INVALIDARG and nothing is launched. No atomics, no scratch memory. */
 WH_API int wh_op_token_scores( void* stream, const float* logits, int64_t rowStride, int rows, int nVocab, const int32_t* targetsDev, wh_token_score* outDev );
+/* The kernel of wh_context_set_alternatives outside a context: outDev [rows][k] = the records (see wh_token_alternative) of row r of the FP32 logits, rowStride >=
+ * nVocab floats apart (rows need 4-byte alignment only; floats between the rows are never read). One 1024-thread workgroup per row, the row read once and kept in
+ * registers: nVocab <= 53248. A null operand, k outside 1 .. 8, rows < 1, nVocab < 1 or above 53248, or rowStride < nVocab is WH_E_INVALIDARG with a message and
+ * nothing is launched. Vector stores only: no atomics, no scratch memory. */
+WH_API int wh_op_top_logprobs( void* stream, const float* logitsDev, int64_t rowStride, int rows, int nVocab, int k, wh_token_alternative* outDev );
 /* wh_sample_best on probabilities [rows][nVocab]: out [rows]. tokenBeg .. nVocab - 1 are the timestamps; the specials are < tokenBeg. */
 WH_API int wh_op_sample_best( void* stream, const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot,
 	int forceTimestamp, int isInitial, wh_token_data* out );

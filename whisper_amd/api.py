@@ -86,6 +86,8 @@ def lib():
         L.whisperc_batch_set_boost_phrases.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_float]
         L.whisperc_set_no_repeat_ngram.argtypes = [vp, C.c_int32]
         L.whisperc_batch_set_no_repeat_ngram.argtypes = [vp, C.c_int32]
+        L.whisperc_set_alternatives.argtypes = [vp, C.c_uint32]
+        L.whisperc_alternatives.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.whisperc_phrase_spellings.argtypes = [vp, C.c_char_p, vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
         L.whisperc_debug_phrase_spellings.argtypes = [C.c_char_p, C.c_char_p, vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
         L.whisperc_set_timestamp_rules.argtypes = [vp, C.c_int32]
@@ -652,6 +654,27 @@ class Context:
         of the fallback -- a text token that would complete an n-gram the window has already sampled is forbidden on the device. n = 1 .. 8; 0 or None turns it
         off, the state of a new context. There is no default n: none has been measured on a real checkpoint. With it on, beam search raises (E_NOTIMPL)."""
         _check(lib().whisperc_set_no_repeat_ngram(self.h, int(n or 0)), "setNoRepeatNgram")
+
+    def set_alternatives(self, k: Optional[int]):
+        """Whisper::setTokenAlternatives: every later run of this context keeps, for every token of its results, the k (1 .. 8) likeliest tokens of the step that
+        emitted it and their log-probabilities (alternatives()). 0 or None turns it off, the state of a new context. With it on, beam search raises (E_NOTIMPL)."""
+        _check(lib().whisperc_set_alternatives(self.h, int(k or 0)), "setTokenAlternatives")
+
+    def alternatives(self):
+        """Whisper::getTokenAlternatives of the last run, parallel to results(): per segment, per token, a list of k ( id, logprob ), likeliest first; ( -1, -inf )
+        where fewer than k tokens were possible. The emitted token need not be entry 0. Empty when the run had the setting off."""
+        n, k = C.c_uint32(), C.c_uint32()
+        _check(lib().whisperc_alternatives(self.h, None, 0, C.byref(n), C.byref(k)), "getTokenAlternatives")
+        if n.value == 0:
+            return []
+        flat = np.empty(n.value, np.dtype([("id", "<i4"), ("logprob", "<f4")]))
+        _check(lib().whisperc_alternatives(self.h, flat.ctypes.data_as(C.c_void_p), n.value, C.byref(n), C.byref(k)), "getTokenAlternatives")
+        per_token = [[(int(r["id"]), float(r["logprob"])) for r in flat[j:j + k.value]] for j in range(0, n.value, k.value)]
+        out, at = [], 0
+        for seg in self.results():
+            out.append(per_token[at:at + len(seg["tokens"])])
+            at += len(seg["tokens"])
+        return out
 
     def set_boost_phrases(self, phrases=None, boost: Optional[float] = None):
         """Whisper::setBoostedPhrases ("hotwords"): in every later run of this context -- greedy, and each sampled attempt of the fallback -- `boost` is added to

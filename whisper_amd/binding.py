@@ -68,6 +68,7 @@ EXPORTS = [
     "wh_op_gemm_encoder", "wh_op_mel_to_conv_input",
     "wh_op_quantize_kv", "wh_op_decoder_cross_attention_f8",
     "wh_op_quantize_rows_i8", "wh_op_layer_norm_i8", "wh_op_gemm_encoder_i8",
+    "wh_context_set_alternatives", "wh_decode_window_alternatives", "wh_op_top_logprobs",
 ]
 
 
@@ -317,6 +318,9 @@ def lib():
         L.wh_op_layer_norm_i8.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32]
         L.wh_op_gemm_encoder_i8.argtypes = [vp, C.POINTER(GemmEncoderArgsC), vp, vp, C.POINTER(C.c_int32)]
         L.wh_op_mel_to_conv_input.argtypes = [vp, vp, i64, i64, vp, vp, vp, i64, i32, i32, i32]
+        L.wh_context_set_alternatives.argtypes = [vp, i32]
+        L.wh_decode_window_alternatives.argtypes = [vp, i32, i32, vp]
+        L.wh_op_top_logprobs.argtypes = [vp, vp, i64, i32, i32, i32, vp]
         _lib = L
     return _lib
 
@@ -340,6 +344,15 @@ def op_token_scores(logits_ptr, row_stride: int, rows: int, n_vocab: int, target
     """wh_op_token_scores on device memory: out[r] (16 bytes, TOKEN_SCORE_DTYPE) = the record of row r of the FP32 logits, row_stride floats apart, against the
     int32 target r. The arguments are device addresses (ctypes.c_void_p or int). Waits for the stream: the targets are checked on the host before the launch."""
     check(lib().wh_op_token_scores(stream, logits_ptr, int(row_stride), int(rows), int(n_vocab), targets_ptr, out_ptr))
+
+
+TOKEN_ALTERNATIVE_DTYPE = np.dtype([("id", "<i4"), ("logprob", "<f4")])
+
+
+def op_top_logprobs(logits_ptr, row_stride: int, rows: int, n_vocab: int, k: int, out_ptr, stream=None):
+    """wh_op_top_logprobs on device memory: out[r][0 .. k) (8 bytes each, TOKEN_ALTERNATIVE_DTYPE) = the k likeliest tokens of row r of the FP32 logits, row_stride
+    floats apart, and their log-probabilities. The arguments are device addresses (ctypes.c_void_p or int)."""
+    check(lib().wh_op_top_logprobs(stream, logits_ptr, int(row_stride), int(rows), int(n_vocab), int(k), out_ptr))
 
 
 def get_option(name: str) -> int:
@@ -454,6 +467,7 @@ class HipContext:
         create = lib().wh_context_create_kv8_hyp if cross_fp8 else lib().wh_context_create_hyp
         check(create(model.handle, max_batch, hypotheses, C.c_void_p(stream) if stream else None, C.byref(self.handle)))
         self.batch = 0
+        self._alt_k = 0                                  # the k of set_alternatives, the one place window_alternatives sizes its buffer from
 
     def close(self):
         if self.handle:
@@ -516,6 +530,20 @@ class HipContext:
         """P( <|nospeech|> ) of the `batch` sequences of the window in progress; waits for its first sample only."""
         out = np.empty(batch, np.float32)
         check(lib().wh_decode_window_no_speech(self.handle, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def set_alternatives(self, k: Optional[int]):
+        """k = 1 .. 8: every sample of the device-side loop also records the k likeliest tokens of the row its sampler read, with their log-probabilities
+        (window_alternatives); 0 or None = off."""
+        check(lib().wh_context_set_alternatives(self.handle, int(k or 0)))
+        self._alt_k = int(k or 0)
+
+    def window_alternatives(self, first: int, count: int):
+        """The records of samples [first, first + count) of the window in progress: structured array [count][batch][k] (TOKEN_ALTERNATIVE_DTYPE). Waits for those
+        samples only; call it before decode_window_finish."""
+        b, _ = self._win
+        out = np.empty((count, b, self._alt_k), TOKEN_ALTERNATIVE_DTYPE)
+        check(lib().wh_decode_window_alternatives(self.handle, first, count, out.ctypes.data_as(C.c_void_p)))
         return out
 
     def upload_async(self, dst_dev, src_host_pinned):

@@ -385,6 +385,7 @@ int wh_context_set_flags( wh_context* c, uint32_t flags, int parityThreads )
 		return WH_E_INVALIDARG;
 	}
 	WH_CHECK( filtersAllowFlags( c, flags ) );
+	WH_CHECK( alternativesAllowFlags( c, flags ) );
 	c->flags = flags;
 	// WH_FLAG_PARITY_EXACT with 0 threads: the decoder's P.V as ONE correctly rounded sum per output (double accumulation) instead of the reference's
 	// FP16 accumulation -- the thread-count-independent value every thread count of the reference approximates

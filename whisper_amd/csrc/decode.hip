@@ -512,6 +512,7 @@ static int greedyStep( wh_context* c, int batch )
 	WH_CHECK( decodeGraph( c, batch, 1, 0, true ) );
 	WH_CHECK( filterLoopRows( c, batch, FILTER_STEP ) );
 	WH_CHECK( sampleStep( c, batch, c->stream ) );
+	WH_CHECK( alternativesStep( c, batch ) );
 	return launchAdvanceState( c->state, c->seqPos, batch, c->stream );
 }
 // Everything in device memory that a greedyStep mutates and a window in progress still needs (obtainStepGraph's WARM_PRESERVE; the stream is idle): the sampler
@@ -634,6 +635,7 @@ static int windowStart( wh_context* c, int batch, const int32_t* promptTokens, c
 	{
 		WH_CHECK( filterLoopRows( c, batch, FILTER_WINDOW ) );	 // a new window: no history survives into it, the prompt does not count, the first sample is unmasked and boosted from the root
 		WH_CHECK( sampleStep( c, batch, st ) );
+		WH_CHECK( alternativesStep( c, batch, true ) );
 		WH_CHECK( launchAdvanceState( c->state, c->seqPos, batch, st ) );
 		c->noSpeechRows = 0;
 		if( c->noSpeech )

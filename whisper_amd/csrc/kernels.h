@@ -508,6 +508,19 @@ namespace wh
 	// out[ row ] = p[ tokenSolm ] of the row the sampler left in `probs`; spreadScratch non-null: the row holds the spread sampler's unnormalised e and is
 	// normalised by the sum of its slice records (what sampleSpreadFinal multiplies by)
 	int launchNoSpeechGather( const float* probs, const void* spreadScratch, int rows, int nVocab, int tokenSolm, float* out, hipStream_t stream );
+	// Token alternatives (alternatives.hip; DESIGN.md section 7 "Token alternatives"): the k (1 .. ALT_MAX_K) largest logits of every row, descending, equal values
+	// in ascending id, with logprob = float( double( x ) - lse ); the layout is wh_token_alternative's. Row r stands at logits + r * rowStride, nVocab <= ALT_MAX_VOCAB.
+	// state null: out [rows][k]. state non-null (a step of the device-side loop): row r's records go to out[ ( state->step * rows + r ) * k ], and a step index
+	// outside [0, maxSteps) writes nothing.
+	struct TokenAlternative
+	{
+		int id;
+		float logprob;
+	};
+	constexpr int ALT_MAX_K = 8, ALT_MAX_VOCAB = 53248;
+	int launchTopLogprobs( const float* logits, long long rowStride, int rows, int nVocab, int k, const DecodeState* state, int maxSteps, TokenAlternative* out, hipStream_t stream );
+	// the form that lost the measurement (per-thread sorted insertion): out [rows][k], the same ids, logprobs equal up to rounding; wh_debug_probe alone calls it
+	int launchTopLogprobsInsert( const float* logits, long long rowStride, int rows, int nVocab, int k, TokenAlternative* out, hipStream_t stream );
 	// Prompt steps whose sequences differ in length (rows right-padded to nTok tokens): the normalised row of sequence b's LAST real
 	// token, lastPos[b] (device), is copied over its row nTok - 1, where the vocabulary product of a prompt step reads. In place, f16 rows.
 	int launchGatherLastRows( f16* xn, const int* lastPos, int batch, int nTok, int d, hipStream_t stream );

@@ -1110,8 +1110,12 @@ int wh_debug_probe( wh_context* c, int kind, int variant, int M, int N, int K, i
 		// Variant 7 = the filter of wh_context_set_no_repeat with n = 3 in front of the fused greedy sampler, 8 = that filter alone (tools/no_repeat_probe.py); K is
 		// the length of the history the timed launch masks by, 3 .. 448, the fed token included: tokens of a five-letter alphabet, so every lane's n-gram recurs and
 		// stores. An untimed copy puts the counts back to K - 1 in front of every timed launch.
+		// Variant 9 = topLogprobsKernel alone (wh_context_set_alternatives), 10 = its per-thread sorted-insertion form (tools/alternatives_probe.py); K is k, 1 .. 8.
+		// Behind the timed launches of variant 10 both forms run on one buffer and their ids are compared: a difference fails the probe.
 		const int rows = M, nVocab = N;
-		if( rows < 1 || rows > 4096 || nVocab < 2048 || nVocab > 52224 || variant < 0 || variant > 8 ) return WH_E_INVALIDARG;
+		if( rows < 1 || rows > 4096 || nVocab < 2048 || nVocab > 52224 || variant < 0 || variant > 10 ) return WH_E_INVALIDARG;
+		const bool alt = variant >= 9;
+		if( alt && ( K < 1 || K > ALT_MAX_K ) ) return WH_E_INVALIDARG;
 		const bool tsr = variant == 4 || variant == 5, boostOnly = variant == 6, nrn = variant == 7 || variant == 8;
 		constexpr int nrnCap = 448, nrnN = 3;
 		if( nrn && ( K < nrnN || K > nrnCap ) ) return WH_E_INVALIDARG;
@@ -1198,8 +1202,11 @@ int wh_debug_probe( wh_context* c, int kind, int variant, int M, int N, int K, i
 			WH_HIP( hipMemcpy( nrnCounts, counts0.data(), sizeof( int ) * (size_t)rows, hipMemcpyHostToDevice ) );
 			WH_HIP( hipMemcpy( nrnFed, fedHost.data(), sizeof( int ) * (size_t)rows, hipMemcpyHostToDevice ) );
 		}
+		TokenAlternative* const altOut = (TokenAlternative*)probs;	  // rows * 8 records, twice: far below a row of floats per row
 		const auto launch = [ & ]( float* x ) -> int
 		{
+			if( variant == 9 ) return launchTopLogprobs( x, nVocab, rows, nVocab, K, nullptr, 0, altOut, st );
+			if( variant == 10 ) return launchTopLogprobsInsert( x, nVocab, rows, nVocab, K, altOut, st );
 			if( nrn )
 			{
 				WH_CHECK( launchNoRepeat( x, rows, nVocab, sot - 1, nrnN, nrnFed, 0, nrnHistory, nrnCounts, nrnCap, st ) );
@@ -1237,6 +1244,21 @@ int wh_debug_probe( wh_context* c, int kind, int variant, int M, int N, int K, i
 		}
 		std::sort( each.begin(), each.end() );
 		ms = each[ each.size() / 2 ] * (float)iters;	  // (the caller gets ms / iters)
+		if( variant == 10 )
+		{
+			const size_t n = (size_t)rows * K;
+			std::vector<TokenAlternative> both( 2 * n );
+			WH_CHECK( launchTopLogprobs( logits[ 0 ], nVocab, rows, nVocab, K, nullptr, 0, altOut, st ) );
+			WH_CHECK( launchTopLogprobsInsert( logits[ 0 ], nVocab, rows, nVocab, K, altOut + n, st ) );
+			WH_HIP( hipMemcpyAsync( both.data(), altOut, sizeof( TokenAlternative ) * 2 * n, hipMemcpyDeviceToHost, st ) );
+			WH_HIP( hipStreamSynchronize( st ) );
+			for( size_t i = 0; i < n; i++ )
+				if( both[ i ].id != both[ n + i ].id || fabsf( both[ i ].logprob - both[ n + i ].logprob ) > 1e-4f )
+				{
+					setError( "debug_probe: the two forms of topLogprobsKernel differ" );
+					rc = WH_E_INVALIDARG;
+				}
+		}
 	}
 	else
 		rc = WH_E_INVALIDARG;

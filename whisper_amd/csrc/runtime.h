@@ -252,6 +252,10 @@ struct wh_context
 	float* noSpeechDev = nullptr;
 	hipEvent_t noSpeechEv = nullptr;
 	int noSpeechRows = 0;	   // rows the window in progress gathered (0 = none)
+	// wh_context_set_alternatives (alternatives.hip alone reads or writes these): altK = k, 0 = off; altRing [n_text_ctx][maxSeq][ALT_MAX_K] records, allocated by the first
+	// call that turns it on, indexed [sample][sequence of the window][k]; windowAltK: the k the window in progress was started with
+	int altK = 0, windowAltK = 0;
+	wh::TokenAlternative* altRing = nullptr;
 	// wh_align_tokens (align.hip; all allocated on first use, outside every captured graph): the query rows of the selected layers, the last call's matrix,
 	// the softmax maxima and sums of sweep 1, the frames, and the call's head list and per-window sizes
 	f16* alignQ = nullptr;
@@ -496,6 +500,12 @@ namespace wh
 	int saveFilterState( const wh_context* c, int batch, std::vector<uint8_t>& s );
 	int restoreFilterState( wh_context* c, int batch, const std::vector<uint8_t>& s );
 	int filtersAllowFlags( const wh_context* c, uint32_t flags );			  // wh_context_set_flags: 0, or the refusal with its error set
+
+	// token alternatives (alternatives.hip, where each of these is explained)
+	int alternativesStep( wh_context* c, int batch, bool windowStart = false );  // between the sampler and the advance of every sample of the device-side loop
+	uint32_t alternativesLoopKey( const wh_context* c );					  // stepKey's bits of a step of the greedy loop
+	constexpr uint32_t STEP_KEY_ALT_MASK = 0xFu << 22;
+	int alternativesAllowFlags( const wh_context* c, uint32_t flags );		  // wh_context_set_flags: 0, or the refusal with its error set
 }
 
 static inline uint16_t f32ToF16Bits( float f )

@@ -15,13 +15,14 @@ bool wh::stepsReplayable( const wh_context* c )
 //   0x20000              a temperature is set (wh_context_set_sampling: other sampler kernels, the same for every temperature)
 //   STEP_KEY_ROWS        per-row sampling (wh_context_set_sampling_rows)
 //   the logit filters    filterGraphKey / filterLoopKey (filters.hip, where their bits are explained)
+//   token alternatives   alternativesLoopKey (alternatives.hip): k in bits 22-25 of a greedy step's key
 //   STEP_KEY_BEAM + width in bits 22-25: a beam step of that width. It runs decodeGraph like the greedy step, so it shares the parity input and filterGraphKey; it
 //                        has no sampler and none of the filters in front of one, so the other bits stay clear
 uint32_t wh::stepKey( const wh_context* c, int beamWidth )
 {
 	const uint32_t graph = ( ( c->flags & WH_FLAG_PARITY_PV ) ? ( 0x10000u | (uint32_t)c->parityThreads ) : 0u ) | filterGraphKey( c );
 	if( beamWidth > 0 ) return graph | STEP_KEY_BEAM | ( (uint32_t)beamWidth << 22 );
-	return graph | ( c->temperature > 0.0f ? 0x20000u : 0u ) | ( c->sampleRowsOn ? STEP_KEY_ROWS : 0u ) | filterLoopKey( c );
+	return graph | ( c->temperature > 0.0f ? 0x20000u : 0u ) | ( c->sampleRowsOn ? STEP_KEY_ROWS : 0u ) | filterLoopKey( c ) | alternativesLoopKey( c );
 }
 
 // Retention, applied when ( batch, key ) is about to be captured. Entries of the other kind stay: a hypothesis-group context may run greedy and beam windows in
@@ -31,11 +32,15 @@ uint32_t wh::stepKey( const wh_context* c, int beamWidth )
 static void dropStaleStepGraphs( wh_context* c, int batch, uint32_t key )
 {
 	const uint32_t sibling = ( key & STEP_KEY_BEAM ) ? 0u : STEP_KEY_ROWS;
+	// ... and in the k of wh_context_set_alternatives, as long as one of the two has k = 0: turning the setting on and off again recaptures nothing, another k
+	// above 0 replaces the one before it
+	const uint32_t alt = ( key & STEP_KEY_BEAM ) ? 0u : STEP_KEY_ALT_MASK;
 	for( size_t i = 0; i < c->stepGraphs.size(); )
 	{
 		const wh_context::StepGraph& g = c->stepGraphs[ i ];
 		const bool sameKind = ( ( g.key ^ key ) & STEP_KEY_BEAM ) == 0;
-		if( sameKind && ( g.batch != batch || ( ( g.key ^ key ) & ~sibling ) != 0 ) )
+		const bool altClash = ( g.key & alt ) && ( key & alt ) && ( ( g.key ^ key ) & alt );
+		if( sameKind && ( g.batch != batch || ( ( g.key ^ key ) & ~( sibling | alt ) ) != 0 || altClash ) )
 		{
 			(void)hipGraphExecDestroy( g.exec );
 			c->stepGraphs.erase( c->stepGraphs.begin() + (ptrdiff_t)i );

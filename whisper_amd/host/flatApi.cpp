@@ -252,6 +252,17 @@ WHISPER_EXPORT int32_t whisperc_batch_set_no_repeat_ngram( void* runner, int32_t
 	if( !runner ) return E_POINTER;
 	return setBatchNoRepeatNgram( (iBatchRunner*)runner, n );
 }
+// Whisper::setTokenAlternatives / getTokenAlternatives: k == 0 turns the setting off; out = sTokenAlternative [cap] (may be NULL), *count = tokens x k of the last run
+WHISPER_EXPORT int32_t whisperc_set_alternatives( void* ctx, uint32_t k )
+{
+	if( !ctx ) return E_POINTER;
+	return setTokenAlternatives( (iContext*)ctx, k );
+}
+WHISPER_EXPORT int32_t whisperc_alternatives( void* ctx, void* out, uint32_t cap, uint32_t* count, uint32_t* k )
+{
+	if( !ctx || !count || !k ) return E_POINTER;
+	return getTokenAlternatives( (const iContext*)ctx, (sTokenAlternative*)out, cap, count, k );
+}
 // Whisper::setSpeechFilter / setBatchSpeechFilter: on == 0 turns the filter off; 0 = a parameter's default
 WHISPER_EXPORT int32_t whisperc_set_speech_filter( void* ctx, int32_t on, int32_t minSilenceFrames, int32_t minSpeechFrames, int32_t padFrames )
 {

@@ -144,6 +144,10 @@ namespace Whisper
 			bool boostOn = false;
 			// Whisper::setNoRepeatNgram: 0 = off unless set. The stream's device context holds n; the hypothesis-group context of beam search cannot (runFull refuses)
 			int noRepeatN = 0;
+			// Whisper::setTokenAlternatives: 0 = off unless set. The stream's device context holds k; tokenAlts: k records per token of resultAll, in its order, and
+			// the k they were made with (those of the last run)
+			int alternativesK = 0, tokenAltsK = 0;
+			std::vector<sTokenAlternative> tokenAlts;
 			// Whisper::setSpeechFilter: off unless set. A run with it on packs the speech of the uploaded PCM on the device (wh_context_speech_filter) and works on the
 			// packed buffer; runSpans / runMap are what the last run used (the map is empty when the run's clock is the recording's)
 			bool speechOn = false;
@@ -188,6 +192,7 @@ namespace Whisper
 				resultAll.clear();
 				speakers.clear();
 				windowStats.clear();
+				tokenAlts.clear();
 				detectedLang = -1;
 				detectedP = 0;
 				return S_OK;
@@ -337,6 +342,18 @@ namespace Whisper
 				return S_OK;
 			}
 			const std::vector<sWindowStats>& lastWindowStats() const { return windowStats; }
+			HRESULT setAlternatives( uint32_t k )
+			{
+				if( k > 8 )
+				{
+					logError( "setTokenAlternatives: k = %u is outside 0 .. 8", k );
+					return E_INVALIDARG;
+				}
+				CHECK_WH( wh_context_set_alternatives( gpu, (int)k ) );
+				alternativesK = (int)k;
+				return S_OK;
+			}
+			const std::vector<sTokenAlternative>& lastTokenAlternatives( uint32_t& k ) const { k = (uint32_t)tokenAltsK; return tokenAlts; }
 			HRESULT runFull( const sFullParams& params, const iAudioBuffer* buffer ) override;
 			HRESULT runStreamed( const sFullParams& params, const sProgressSink& progress, const iAudioReader* reader ) override;
 			// capture.cpp: the reference's capture loop over an iPcmCapture, every piece a runFull of this context on a worker thread
@@ -1017,6 +1034,14 @@ namespace Whisper
 				logError( "runFull: no-repeat n-grams (setNoRepeatNgram) are not available with eSamplingStrategy::BeamSearch" );
 				return E_NOTIMPL;
 			}
+			// token alternatives: the device-side loop only (the ring is indexed by the greedy loop's samples)
+			tokenAlts.clear();
+			tokenAltsK = alternativesK;
+			if( alternativesK && params.strategy == eSamplingStrategy::BeamSearch && params.beam_search.beam_width >= 1 )
+			{
+				logError( "runFull: token alternatives (setTokenAlternatives) are not available with eSamplingStrategy::BeamSearch" );
+				return E_NOTIMPL;
+			}
 			StreamRun run( params, vocab, hp, this, progress, resultAll, promptPast, &stamper );
 			// the run's audio is current until this function returns; the stereo PCM is the caller's and is not referred to afterwards
 			struct CurrentRun
@@ -1167,7 +1192,36 @@ namespace Whisper
 						msSince( tDec ), dec.steps, dec.msFetch, dec.msEnqueue );
 				nDecodeSteps += dec.steps;	   // tokens the loop consumed (the reference counts one DecodeStep per token)
 				nDecodeWindows++;
+				// token alternatives: the records of the window's kept samples, read while the window -- the accepted attempt's -- is still the one in progress.
+				// scan.tokens[ i ] is sample i. finishWindow then cuts those tokens into segments, in order and possibly leaving some out, so every token of the new
+				// segments is found again by walking the window's tokens forward and comparing all five sampler fields.
+				std::vector<wh_token_alternative> windowAlts;
+				std::vector<TokenData> sampled;
+				if( alternativesK ) sampled = scan.tokens;
+				const size_t nKept = scan.failed ? 0 : std::min( (size_t)std::max( scan.resultLen, 0 ), sampled.size() );
+				if( alternativesK && nKept > 0 )
+				{
+					windowAlts.resize( nKept * (size_t)alternativesK );
+					CHECK_WH( wh_decode_window_alternatives( active, 0, (int)nKept, windowAlts.data() ) );
+				}
+				const size_t segmentsBefore = resultAll.size();
 				const HRESULT hrWindow = run.finishWindow( scan );
+				if( alternativesK )
+				{
+					size_t j = 0;
+					for( size_t s = std::min( segmentsBefore, resultAll.size() ); s < resultAll.size(); s++ )
+						for( const TokenData& t : resultAll[ s ].tokens )
+						{
+							const auto same = [ & ]( const TokenData& o ) { return o.id == t.id && o.tid == t.tid && o.p == t.p && o.pt == t.pt && o.ptsum == t.ptsum; };
+							while( j < nKept && !same( sampled[ j ] ) ) j++;
+						// (cannot happen while finishWindow only copies the window's tokens; a token that is nobody's sample gets { -1, -inf } and a line in the log)
+						if( j >= nKept ) logError( "runFull: token %d of the window just finished matches none of its %d samples: it gets no alternatives", t.id, (int)nKept );
+							for( int r = 0; r < alternativesK; r++ )
+								tokenAlts.push_back( j < nKept ? sTokenAlternative{ windowAlts[ j * (size_t)alternativesK + r ].id, windowAlts[ j * (size_t)alternativesK + r ].logprob }
+															   : sTokenAlternative{ -1, -INFINITY } );
+							if( j < nKept ) j++;
+						}
+				}
 				appendSpeakers( resultAll, mediaTimeOffset, stereoPcm, stereoFrames, speakers );
 				CHECK( hrWindow );
 			}
@@ -1494,6 +1548,23 @@ namespace Whisper
 		if( !stats ) return S_OK;
 		if( cap < all.size() ) return E_BOUNDS;
 		std::copy( all.begin(), all.end(), stats );
+		return S_OK;
+	}
+	HRESULT setTokenAlternatives( iContext* context, uint32_t k )
+	{
+		return optionRules::forward<ContextImpl>( context, "setTokenAlternatives", NOT_A_CONTEXT, "a batch runner has no token alternatives",
+			[ = ]( ContextImpl& c ) { return c.setAlternatives( k ); } );
+	}
+	HRESULT getTokenAlternatives( const iContext* context, sTokenAlternative* out, uint32_t cap, uint32_t* count, uint32_t* k )
+	{
+		if( !context || !count || !k ) return E_POINTER;
+		const ContextImpl* const c = dynamic_cast<const ContextImpl*>( context );
+		if( !c ) return E_INVALIDARG;
+		const std::vector<sTokenAlternative>& all = c->lastTokenAlternatives( *k );
+		*count = (uint32_t)all.size();
+		if( !out ) return S_OK;
+		if( cap < all.size() ) return E_BOUNDS;
+		std::copy( all.begin(), all.end(), out );
 		return S_OK;
 	}
 	HRESULT createModelImpl( const std::shared_ptr<LoadedModel>& model, iModel** pp )
