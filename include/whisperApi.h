@@ -385,6 +385,9 @@ namespace Whisper
 								// 4 = INT8 encoder products: wh_context_set_encoder_i8 on the groups' contexts (the encoder's Q/K/V, attention-out and MLP products as
 								//     int8 x int8 -> int32 with one scale per activation row and per weight row; models whose state size is a multiple of 128). May be
 								//     combined with 2. Off unless set. Nobody has measured recognition accuracy with INT8 encoder products on a real checkpoint.
+								// 8 = INT4 cross-attention caches: the groups' contexts are created with wh_context_create_kv4 (4-bit codes and one scale per key row:
+								//     36 bytes per key row where FP16 takes 128 and FP8 68). May be combined with 4; together with 2 createBatchRunner answers E_INVALIDARG.
+								//     Off unless set. Four-bit K and V move the logits more than FP8 does; nobody has measured recognition accuracy with them on a real checkpoint.
 	};
 	// {6f0c9a1e-3b52-4d7c-8e21-9a4f5c7d2b10}
 	struct iBatchRunner : public ComLight::IUnknown

@@ -173,6 +173,15 @@ WH_API int wh_context_create_hyp( wh_model* m, int maxBatch, int hypotheses, voi
  * (the hypothesis-group kernel attentionDecM reads FP16 rows). Nobody has measured recognition accuracy with FP8 caches on a real checkpoint. */
 WH_API int wh_context_create_kv8( wh_model* m, int maxBatch, void* stream, wh_context** out );
 WH_API int wh_context_create_kv8_hyp( wh_model* m, int maxBatch, int hypotheses, void* stream, wh_context** out );
+/* wh_context_create with INT4 cross-attention caches (whisper_amd/csrc/kv4.hip; DESIGN.md section 7 "INT4 cross-attention caches"): as wh_context_create_kv8 --
+ * the same layer-at-a-time FP16 staging, the batch decode path at every batch size, the same refusals (the parity flags, wh_align_tokens, wh_debug_read of
+ * "cross-k" / "cross-v", any `hypotheses` other than 1), each WH_E_INVALIDARG with its reason -- but the caches are signed 4-bit codes n = rint( x / s ) in [-7, 7]
+ * with one FP32 scale s = amax / 7 per key row (1 for a row of zeros), stored as nibbles n + 8: 36 bytes per key row where FP16 takes 128 and FP8 68. They hold
+ * exactly that quantization of the FP16 values wh_context_create's caches hold. The decode step's cross-attention is attentionDecG4: every multiply-add on
+ * v_mfma_i32_32x32x32_i8, the query and the softmax weights entering as sums of int8 terms. Four-bit K and V move the logits far more than FP8 does; nobody has
+ * measured recognition accuracy with these caches on a real checkpoint. */
+WH_API int wh_context_create_kv4( wh_model* m, int maxBatch, void* stream, wh_context** out );
+WH_API int wh_context_create_kv4_hyp( wh_model* m, int maxBatch, int hypotheses, void* stream, wh_context** out );
 /* INT8 encoder products (whisper_amd/csrc/quant_i8.hip, gemm_i8.hip; DESIGN.md section 7 "INT8 encoder products"). on != 0: the encoder's Q/K/V, attention-out,
  * MLP-up and MLP-down products of every layer run as int8 x int8 -> int32 on the matrix cores (gemmI8) with one FP32 scale per activation row and per weight
  * row: s = amax / 127 (1 for a row of zeros), q = rint( x / s ) clamped to [-127, 127]; y = ( (float)acc * sa[m] ) * sw[n] takes the FP32 accumulator's place in
@@ -701,6 +710,10 @@ WH_API int wh_profile_read( wh_context* c, wh_profile_entry* out, int cap, int* 
  *   on a wh_context_create_kv8 context (which refuses "cross-k" / "cross-v"), one layer in the cache's own order, RAW (dstCapFloats still counts floats):
  *          "cross-k8" / "cross-v8"              [batch][heads][n_ctx][64] E4M3 bytes, batch * n_ctx * d bytes packed into dstHost
  *          "cross-k8-scale" / "cross-v8-scale"  [batch][heads][n_ctx] FP32 row scales
+ *   on a wh_context_create_kv4 context (which refuses "cross-k" / "cross-v"), likewise:
+ *          "cross-k4"                           [batch][heads][n_ctx][32] bytes: dim 2 t in the low nibble of byte t, dim 2 t + 1 in the high one
+ *          "cross-v4"                           [batch][heads][ceil( n_ctx / 64 )][64 dims][32] bytes: blocks of 64 keys (tests/cross_i4_ref.py pack_v)
+ *          "cross-k4-scale" / "cross-v4-scale"  [batch][heads][n_ctx] FP32 row scales
  * and, captured under WH_FLAG_DEBUG_CAPTURE by the wh_encode / wh_decode call that follows the flag:
  *          "enc.temp1"      conv1 + bias + GELU, [batch][2*n_ctx][d] (time-major; the reference's tensor is [d][2*n_ctx])
  *          "enc.layer0.in"  conv2 + GELU + positional embedding = input of encoder layer 0, [batch][n_ctx][d]
@@ -764,6 +777,14 @@ WH_API int wh_op_quantize_kv( void* stream, const void* rowsF16, void* bytesOut,
  * qF16, x and out hold sequences * nTok rows. */
 WH_API int wh_op_decoder_cross_attention_f8( void* stream, const void* qF16, const float* x, const float* lnW, const float* lnB, const void* qW, const float* qB,
 	float qScale, const void* kBytes, const float* kScales, const void* vBytes, const float* vScales, void* outF16, int sequences, int heads, int nTok, int nKeys,
+	int keyStride, int group );
+/* quantizeCrossKV4 on its own (kv4.hip): `heads` blocks of nKeys FP16 rows of 64 -> K nibbles [heads][nKeys][32], V nibbles [heads][ceil( nKeys / 64 )][64][32]
+ * (either may be NULL) and FP32 scales [heads][nKeys], the format of wh_context_create_kv4's caches */
+WH_API int wh_op_quantize_cross_kv_i4( void* stream, const void* rowsF16, void* kNibbles, void* vNibbles, float* scalesOut, int64_t heads, int nKeys );
+/* wh_op_decoder_cross_attention_f8 over INT4 caches: kNibbles [sequences / group][heads][keyStride][32], vNibbles [sequences / group][heads]
+ * [ceil( keyStride / 64 )][64][32], kScales / vScales FP32 [sequences / group][heads][keyStride] */
+WH_API int wh_op_decoder_cross_attention_i4( void* stream, const void* qF16, const float* x, const float* lnW, const float* lnB, const void* qW, const float* qB,
+	float qScale, const void* kNibbles, const float* kScales, const void* vNibbles, const float* vScales, void* outF16, int sequences, int heads, int nTok, int nKeys,
 	int keyStride, int group );
 /* softMax over rows with the reference's FP16 exp table semantics (softMax.hlsl / ggml.c:5030-5090): in place, FP32 */
 WH_API int wh_op_soft_max( void* stream, float* x, int rows, int cols );

@@ -44,7 +44,7 @@ EXPORTS = [
     "wh_model_arena_bytes", "wh_model_create", "wh_model_destroy", "wh_model_set_tensor", "wh_model_set_filters",
     "wh_model_finalize", "wh_model_arena", "wh_model_hparams",
     "wh_comm_runtime_check", "wh_comm_unique_id", "wh_comm_create", "wh_comm_destroy", "wh_comm_info", "wh_comm_barrier", "wh_comm_create_timeout", "wh_comm_set_timeout", "wh_comm_broadcast_i32", "wh_model_broadcast",
-    "wh_context_create", "wh_context_create_hyp", "wh_context_create_kv8", "wh_context_create_kv8_hyp", "wh_context_destroy", "wh_context_bind", "wh_context_set_flags", "wh_context_set_encoder_i8", "wh_context_set_audio_ctx", "wh_context_synchronize", "wh_context_memory",
+    "wh_context_create", "wh_context_create_hyp", "wh_context_create_kv8", "wh_context_create_kv8_hyp", "wh_context_create_kv4", "wh_context_create_kv4_hyp", "wh_context_destroy", "wh_context_bind", "wh_context_set_flags", "wh_context_set_encoder_i8", "wh_context_set_audio_ctx", "wh_context_synchronize", "wh_context_memory",
     "wh_buffer_alloc", "wh_buffer_free", "wh_buffer_upload", "wh_buffer_upload_async", "wh_buffer_download",
     "wh_mel_spectrogram", "wh_encode", "wh_encode_windows", "wh_decode", "wh_sample_best", "wh_beam_candidates", "wh_reorder_self_cache", "wh_beam_window_start", "wh_beam_window_continue", "wh_beam_window_status", "wh_beam_window_records", "wh_decode_greedy", "wh_decode_window_start", "wh_decode_window_finish", "wh_decode_window_continue", "wh_decode_window_fetch", "wh_decode_window_start_ragged", "wh_decode_window_ready", "wh_mel_spectrogram_window", "wh_mel_spectrogram_batch", "wh_profile_enable", "wh_profile_read", "wh_debug_read", "wh_debug_step_captures", "wh_debug_probe", "wh_debug_set_tuning", "wh_debug_set_option", "wh_debug_get_option",
     "wh_op_mul_mat", "wh_op_mul_mat_gelu", "wh_op_layer_norm", "wh_op_flash_attention", "wh_op_soft_max", "wh_op_decoder_attention", "wh_op_decoder_cross_attention",
@@ -66,7 +66,7 @@ EXPORTS = [
     "wh_op_gemv_small", "wh_op_cross_split", "wh_op_self_block_dec",
     "wh_score_tokens", "wh_op_token_scores",
     "wh_op_gemm_encoder", "wh_op_mel_to_conv_input",
-    "wh_op_quantize_kv", "wh_op_decoder_cross_attention_f8",
+    "wh_op_quantize_kv", "wh_op_decoder_cross_attention_f8", "wh_op_quantize_cross_kv_i4", "wh_op_decoder_cross_attention_i4",
     "wh_op_quantize_rows_i8", "wh_op_layer_norm_i8", "wh_op_gemm_encoder_i8",
     "wh_context_set_alternatives", "wh_decode_window_alternatives", "wh_op_top_logprobs",
 ]
@@ -217,6 +217,8 @@ def lib():
         L.wh_context_create_hyp.argtypes = [vp, i32, i32, vp, C.POINTER(vp)]
         L.wh_context_create_kv8.argtypes = [vp, i32, vp, C.POINTER(vp)]
         L.wh_context_create_kv8_hyp.argtypes = [vp, i32, i32, vp, C.POINTER(vp)]
+        L.wh_context_create_kv4.argtypes = [vp, i32, vp, C.POINTER(vp)]
+        L.wh_context_create_kv4_hyp.argtypes = [vp, i32, i32, vp, C.POINTER(vp)]
         L.wh_context_bind.argtypes = [vp]
         L.wh_context_destroy.argtypes = [vp]
         L.wh_context_destroy.restype = None
@@ -256,6 +258,8 @@ def lib():
         L.wh_op_decoder_cross_attention.argtypes = [vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, i32, i32, i32, i32, i32]
         L.wh_op_quantize_kv.argtypes = [vp, vp, vp, vp, i64]
         L.wh_op_decoder_cross_attention_f8.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32]
+        L.wh_op_quantize_cross_kv_i4.argtypes = [vp, vp, vp, vp, vp, i64, i32]
+        L.wh_op_decoder_cross_attention_i4.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32]
         L.wh_op_vocab_soft_max.argtypes = [vp, vp, vp, i32, i32]
         L.wh_op_sample_best.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]
         L.wh_op_beam_candidates.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
@@ -454,17 +458,21 @@ class HipModel:
 class HipContext:
     """Activations + KV caches for up to max_batch 30 s windows processed in lock step (WhisperContext of the reference)."""
 
-    def __init__(self, model: HipModel, max_batch: int = 1, stream: int = 0, hypotheses: int = 1, cross_fp8: bool = False):
+    def __init__(self, model: HipModel, max_batch: int = 1, stream: int = 0, hypotheses: int = 1, cross_fp8: bool = False, cross_i4: bool = False):
         """max_batch windows; `hypotheses` decoder sequences per window share the window's cross-attention K/V (then every
         decode entry point counts sequences = windows * hypotheses, window-major). cross_fp8: the cross-attention caches as E4M3 bytes with a
-        power-of-two scale per key row (wh_context_create_kv8: half the cache memory; one hypothesis per window only)."""
+        power-of-two scale per key row (wh_context_create_kv8: half the cache memory; one hypothesis per window only). cross_i4: as 4-bit codes with
+        one scale per key row (wh_context_create_kv4: 36 bytes per key row; the same restrictions)."""
+        if cross_fp8 and cross_i4:
+            raise ValueError("cross_fp8 and cross_i4 exclude each other")
         self.model = model
         self.hp = model.hp
         self.max_batch = max_batch
         self.hypotheses = hypotheses
         self.cross_fp8 = cross_fp8
+        self.cross_i4 = cross_i4
         self.handle = C.c_void_p()
-        create = lib().wh_context_create_kv8_hyp if cross_fp8 else lib().wh_context_create_hyp
+        create = lib().wh_context_create_kv4_hyp if cross_i4 else lib().wh_context_create_kv8_hyp if cross_fp8 else lib().wh_context_create_hyp
         check(create(model.handle, max_batch, hypotheses, C.c_void_p(stream) if stream else None, C.byref(self.handle)))
         self.batch = 0
         self._alt_k = 0                                  # the k of set_alternatives, the one place window_alternatives sizes its buffer from
@@ -883,6 +891,16 @@ class HipContext:
             keys = getattr(self, "_audio_ctx", 0) or self.hp.n_audio_ctx
             shape = (b, self.hp.n_audio_head, keys)
             out = np.empty(shape, np.float32) if what.endswith("scale") else np.empty(shape + (64,), np.uint8)
+            check(lib().wh_debug_read(self.handle, what.encode(), layer, 0, out.ctypes.data_as(C.c_void_p), out.nbytes // 4))
+            return out
+        if what in ("cross-k4", "cross-v4", "cross-k4-scale", "cross-v4-scale"):
+            # one layer of the INT4 caches, raw: K bytes [batch][heads][keys][32], V bytes [batch][heads][ceil(keys / 64)][64][32], scales [batch][heads][keys]
+            keys = getattr(self, "_audio_ctx", 0) or self.hp.n_audio_ctx
+            shape = (b, self.hp.n_audio_head, keys)
+            if what.endswith("scale"):
+                out = np.empty(shape, np.float32)
+            else:
+                out = np.empty(shape + (32,) if what == "cross-k4" else (b, self.hp.n_audio_head, (keys + 63) // 64, 64, 32), np.uint8)
             check(lib().wh_debug_read(self.handle, what.encode(), layer, 0, out.ctypes.data_as(C.c_void_p), out.nbytes // 4))
             return out
         if what in ("logits", "probs"):

@@ -451,6 +451,7 @@ int wh_align_tokens( wh_context* c, int batch, const int32_t* tokens, const int3
 	if( !c || !tokens || !lens || !nKeys || !framesHost || batch <= 0 || nMax <= 0 ) { setError( "align_tokens: bad argument" ); return WH_E_INVALIDARG; }
 	if( c->hyp != 1 ) { setError( "align_tokens: greedy contexts only (one hypothesis per window)" ); return WH_E_INVALIDARG; }
 	if( c->flags & WH_FLAG_PARITY_EXACT ) { setError( "align_tokens: not under WH_FLAG_PARITY_EXACT" ); return WH_E_INVALIDARG; }
+	if( c->kv4 ) { setError( "align_tokens: the alignment kernels read FP16 cross-attention keys; not available on a context with INT4 cross-attention caches" ); return WH_E_INVALIDARG; }
 	if( c->kv8 ) { setError( "align_tokens: the alignment kernels read FP16 cross-attention keys; not available on a context with FP8 cross-attention caches" ); return WH_E_INVALIDARG; }
 	if( !c->encoded ) { setError( "align_tokens: wh_encode has not run" ); return WH_E_NOT_READY; }
 	if( batch > c->lastEncBatch ) { setError( "align_tokens: more windows than the last wh_encode filled" ); return WH_E_INVALIDARG; }

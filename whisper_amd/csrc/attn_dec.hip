@@ -1391,6 +1391,7 @@ namespace wh
 	int launchAttentionDec( const DecAttnArgs& a, hipStream_t stream )
 	{
 		if( a.kc8 ) return launchAttentionDec8( a, stream );	  // FP8 cross-attention caches: kv8.hip
+		if( a.kc4 ) return launchAttentionDec4( a, stream );	  // INT4 cross-attention caches: kv4.hip
 		if( a.nKeys <= 0 || a.nKeys > MAX_KEYS || a.nTok <= 0 || a.batch <= 0 )
 		{
 			setError( "attentionDec: key count out of range" );

@@ -111,11 +111,11 @@ int wh_context_create( wh_model* m, int maxBatch, void* stream, wh_context** out
 	return wh_context_create_hyp( m, maxBatch, 1, stream, out );
 }
 
-static int createContext( wh_model* m, int maxBatch, int hypotheses, bool kv8, void* stream, wh_context** out );
+static int createContext( wh_model* m, int maxBatch, int hypotheses, bool kv8, bool kv4, void* stream, wh_context** out );
 
 int wh_context_create_hyp( wh_model* m, int maxBatch, int hypotheses, void* stream, wh_context** out )
 {
-	return createContext( m, maxBatch, hypotheses, false, stream, out );
+	return createContext( m, maxBatch, hypotheses, false, false, stream, out );
 }
 
 // FP8 cross-attention caches: greedy contexts only -- the matrix-core kernel of a hypothesis group (attentionDecM) reads FP16 rows
@@ -131,10 +131,26 @@ int wh_context_create_kv8_hyp( wh_model* m, int maxBatch, int hypotheses, void* 
 		setError( "context_create_kv8: FP8 cross-attention caches serve one hypothesis per window (the hypothesis-group kernel attentionDecM reads FP16 caches)" );
 		return WH_E_INVALIDARG;
 	}
-	return createContext( m, maxBatch, 1, true, stream, out );
+	return createContext( m, maxBatch, 1, true, false, stream, out );
 }
 
-static int createContext( wh_model* m, int maxBatch, int hypotheses, bool kv8, void* stream, wh_context** out )
+// INT4 cross-attention caches: greedy contexts only, for the same reason
+int wh_context_create_kv4( wh_model* m, int maxBatch, void* stream, wh_context** out )
+{
+	return wh_context_create_kv4_hyp( m, maxBatch, 1, stream, out );
+}
+
+int wh_context_create_kv4_hyp( wh_model* m, int maxBatch, int hypotheses, void* stream, wh_context** out )
+{
+	if( hypotheses != 1 )
+	{
+		setError( "context_create_kv4: INT4 cross-attention caches serve one hypothesis per window (the hypothesis-group kernel attentionDecM reads FP16 caches)" );
+		return WH_E_INVALIDARG;
+	}
+	return createContext( m, maxBatch, 1, false, true, stream, out );
+}
+
+static int createContext( wh_model* m, int maxBatch, int hypotheses, bool kv8, bool kv4, void* stream, wh_context** out )
 {
 	if( !m || !out || maxBatch <= 0 || hypotheses <= 0 || hypotheses > 8 || hypotheses == 6 || hypotheses == 7 )
 	{
@@ -149,6 +165,7 @@ static int createContext( wh_model* m, int maxBatch, int hypotheses, bool kv8, v
 	(void)hipDeviceGetAttribute( &c->totalCus, hipDeviceAttributeMultiprocessorCount, m->device );
 	c->maxBatch = maxBatch;
 	c->kv8 = kv8;
+	c->kv4 = kv4;
 	c->hyp = hypotheses;
 	c->maxSeq = maxBatch * hypotheses;
 	c->stream = (hipStream_t)stream;
@@ -224,7 +241,19 @@ static int createContext( wh_model* m, int maxBatch, int hypotheses, bool kv8, v
 	rc = rc ? rc : c->alloc( c->vT, Be * H * HEAD_DIM * c->Tpad, wh_context::MUST_BE_ZERO, "vT" );
 	rc = rc ? rc : c->alloc( c->attn, rowsE * d, wh_context::DONT_CARE, "attn" );
 	rc = rc ? rc : c->alloc( c->h, rowsE * 4 * d, wh_context::DONT_CARE, "h" );
-	if( !kv8 )
+	if( kv4 )
+	{
+		// half a byte per element -- K rows of 32 bytes, V in blocks of 64 keys x 64 dims (the last block of a head padded) -- a scale per key row, and the
+		// FP8 contexts' staging of one layer x one encoder chunk. Zero nibbles under any scale are finite.
+		const int64_t keyRows = (int64_t)hp.n_text_layer * B * hp.n_text_head * T;
+		const int64_t vBlocks = (int64_t)hp.n_text_layer * B * hp.n_text_head * ( ( T + 63 ) / 64 );
+		rc = rc ? rc : c->alloc( c->crossK4, keyRows * ( HEAD_DIM / 2 ), wh_context::MUST_BE_ZERO, "crossK4" );
+		rc = rc ? rc : c->alloc( c->crossV4, vBlocks * 64 * ( HEAD_DIM / 2 ), wh_context::MUST_BE_ZERO, "crossV4" );
+		rc = rc ? rc : c->alloc( c->crossKScale, keyRows, wh_context::MUST_BE_ZERO, "crossKScale" );
+		rc = rc ? rc : c->alloc( c->crossVScale, keyRows, wh_context::MUST_BE_ZERO, "crossVScale" );
+		rc = rc ? rc : c->alloc( c->crossStage, 2 * Be * T * d, wh_context::DONT_CARE, "crossStage" );
+	}
+	else if( !kv8 )
 	{
 		rc = rc ? rc : c->alloc( c->crossK, (int64_t)hp.n_text_layer * B * T * d, wh_context::MUST_BE_ZERO, "crossK" );
 		rc = rc ? rc : c->alloc( c->crossV, (int64_t)hp.n_text_layer * B * T * d, wh_context::MUST_BE_ZERO, "crossV" );
@@ -374,6 +403,11 @@ int wh_context_set_audio_ctx( wh_context* c, int audioCtx )
 int wh_context_set_flags( wh_context* c, uint32_t flags, int parityThreads )
 {
 	if( !c ) return WH_E_INVALIDARG;
+	if( c->kv4 && ( flags & ( WH_FLAG_PARITY_EXACT | WH_FLAG_PARITY_PV ) ) )
+	{
+		setError( "context_set_flags: the parity modes restate the reference's FP16 caches and are not available on a context with INT4 cross-attention caches" );
+		return WH_E_INVALIDARG;
+	}
 	if( c->kv8 && ( flags & ( WH_FLAG_PARITY_EXACT | WH_FLAG_PARITY_PV ) ) )
 	{
 		setError( "context_set_flags: the parity modes restate the reference's FP16 caches and are not available on a context with FP8 cross-attention caches" );

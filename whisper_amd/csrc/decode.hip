@@ -9,7 +9,7 @@ static int attnDecP( wh_context* c, const DecAttnArgs& a, int keysHint = -1 )
 	const int group = a.group > 0 ? a.group : 1;
 	const double keys = (double)( keysHint > 0 ? keysHint : a.nKeys );
 	const double d = (double)a.H * HEAD_DIM;
-	const double rowBytes = a.kc8 ? HEAD_DIM + 4.0 : 2.0 * HEAD_DIM;	  // FP8 caches: a byte per element and the row's scale
+	const double rowBytes = a.kc4 ? HEAD_DIM / 2 + 4.0 : a.kc8 ? HEAD_DIM + 4.0 : 2.0 * HEAD_DIM;	  // FP8 caches: a byte per element and the row's scale; INT4: a nibble
 	double bytes = 2.0 * ( a.batch / group ) * a.H * keys * rowBytes + 2.0 * 2.0 * a.batch * a.nTok * d;
 	double flops = 4.0 * a.batch * a.H * keys * HEAD_DIM * a.nTok;
 	if( a.lnX )
@@ -72,9 +72,9 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 
 	// ---- single-token steps of up to 4 sequences (one stream through iContext::runFull): decode1.hip. Eight launches per layer,
 	// each of ~256 workgroups, each pulling the weights of the next one into the L2 of the XCD that will read them.
-	// (FP8 cross-attention caches take the batch path at every batch size: crossScores / crossSoftmaxPV read FP16 rows)
+	// (FP8 and INT4 cross-attention caches take the batch path at every batch size: crossScores / crossSoftmaxPV read FP16 rows)
 	const bool small = nTokens == 1 && batch <= SMALL_MAX_ROWS && c->hyp == 1 && parity == 0 && d <= 1280 && ( d % 64 ) == 0 && c->T <= 1536 &&
-		!( c->flags & WH_FLAG_DEBUG_CAPTURE ) && ( g_tuning & TUNE_DECODE_SMALL ) && !c->kv8;
+		!( c->flags & WH_FLAG_DEBUG_CAPTURE ) && ( g_tuning & TUNE_DECODE_SMALL ) && !c->kv8 && !c->kv4;
 	if( small )
 	{
 #ifdef WH_PROBES
@@ -272,7 +272,14 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 		{
 			DecAttnArgs a = {};
 			a.q = c->dq; a.out = c->dattn;
-			if( c->kv8 )
+			if( c->kv4 )
+			{
+				// half a byte per element; V in whole 64-key blocks per head
+				a.kc4 = c->crossK4 + crossLayer / 2;
+				a.vc4 = c->crossV4 + (int64_t)il * c->maxBatch * H * ( ( c->T + 63 ) / 64 ) * ( 64 * HEAD_DIM / 2 );
+				a.kScale = c->crossKScale + crossLayer / HEAD_DIM; a.vScale = c->crossVScale + crossLayer / HEAD_DIM;
+			}
+			else if( c->kv8 )
 			{
 				// a byte per element: the layer's offset in bytes is crossLayer, in key rows crossLayer / 64
 				a.kc8 = c->crossK8 + crossLayer; a.vc8 = c->crossV8 + crossLayer;

@@ -236,9 +236,9 @@ static int encodeImpl( wh_context* c, const float* melDev, int batch, int64_t me
 		}
 	}
 	WH_CHECK( lnP( c, c->x, m->at<float>( L.lnPostW ), m->at<float>( L.lnPostB ), c->xn, M, d ) );
-	// FP8 caches: the same product one decoder layer at a time (the layer's 2 d rows of wcross / bcross, the same kernel and epilogue) into the FP16
+	// FP8 and INT4 caches: the same product one decoder layer at a time (the layer's 2 d rows of wcross / bcross, the same kernel and epilogue) into the FP16
 	// staging of one layer, which quantizeCrossKV turns into that layer's bytes and scales at the chunk's window offset
-	if( c->kv8 )
+	if( c->kv8 || c->kv4 )
 	{
 		f16* const stageK = c->crossStage;
 		f16* const stageV = c->crossStage + (int64_t)c->encChunk * T * d;
@@ -253,6 +253,13 @@ static int encodeImpl( wh_context* c, const float* melDev, int batch, int64_t me
 			g.T = T; g.H = H; g.B = batch;
 			WH_CHECK( gemmP( c, g, false ) );
 			const int64_t row0 = ( (int64_t)il * c->maxBatch + b0 ) * H * T;
+			if( c->kv4 )
+			{
+				const int64_t heads = (int64_t)batch * H, vBlock0 = ( (int64_t)il * c->maxBatch + b0 ) * H * ( ( T + 63 ) / 64 );
+				WH_CHECK( profiled( c, KC_QUANT_KV, 0.0, 2.0 * rows * ( 2.0 * HEAD_DIM + HEAD_DIM / 2 + 4.0 ), [ & ]() { return launchQuantizeCrossKV4( stageK,
+					c->crossK4 + row0 * ( HEAD_DIM / 2 ), c->crossKScale + row0, stageV, c->crossV4 + vBlock0 * ( 64 * HEAD_DIM / 2 ), c->crossVScale + row0, heads, T, st ); } ) );
+			}
+			else
 			WH_CHECK( profiled( c, KC_QUANT_KV, 0.0, 2.0 * rows * ( 2.0 * HEAD_DIM + HEAD_DIM + 4.0 ), [ & ]() { return launchQuantizeCrossKV( stageK, c->crossK8 + row0 * HEAD_DIM,
 				c->crossKScale + row0, stageV, c->crossV8 + row0 * HEAD_DIM, c->crossVScale + row0, rows, st ); } ) );
 		}

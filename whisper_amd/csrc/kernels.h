@@ -265,12 +265,21 @@ namespace wh
 		const uint8_t* vc8;
 		const float* kScale;
 		const float* vScale;
+		// INT4 cross-attention caches (kv4.hip): when kc4 is non-null, kc / vc are ignored; K nibbles [batch / group][H][keyStride][32 bytes], V nibbles
+		// [batch / group][H][ceil( keyStride / 64 )][64 dims][32 bytes] (64-key blocks, dim-major), one FP32 scale per key row in kScale / vScale as above
+		const uint8_t* kc4;
+		const uint8_t* vc4;
 	};
 	int launchAttentionDec( const DecAttnArgs& a, hipStream_t stream );
 	// kv8.hip: launchAttentionDec's branch for FP8 caches (attentionDecG8), and the quantizer behind the encoder's cross-K/V product: `rows` FP16 rows of 64 ->
 	// E4M3 bytes [rows][64] + scales [rows], s = 2^ceil( log2( amax / 448 ) ) (1 for a row of zeros), bytes = e4m3( x / s ) to nearest even. The V set may be null.
 	int launchAttentionDec8( const DecAttnArgs& a, hipStream_t stream );
 	int launchQuantizeCrossKV( const f16* srcK, uint8_t* dstK, float* scaleK, const f16* srcV, uint8_t* dstV, float* scaleV, long long rows, hipStream_t stream );
+	// kv4.hip: the branch for INT4 caches (attentionDecG4, scores and P.V on v_mfma_i32_32x32x32_i8), and their quantizer: `heads` (window, head) blocks of T FP16
+	// rows of 64 -> nibbles n + 8, n = rint( x / s ) in [-7, 7], s = amax / 7 (1 for a row of zeros), in the two orders DecAttnArgs states, + scales [heads][T].
+	// Either set may be left out (null destination).
+	int launchAttentionDec4( const DecAttnArgs& a, hipStream_t stream );
+	int launchQuantizeCrossKV4( const f16* srcK, uint8_t* dstK, float* scaleK, const f16* srcV, uint8_t* dstV, float* scaleV, long long heads, int T, hipStream_t stream );
 
 	// The self-attention half of a single-token decode step as one launch: LayerNorm -> per-head Q/K/V rows of the fused
 	// [3d][d] weight -> cache append at the current position -> causal attention -> out (FP16 [batch][d]).

@@ -177,6 +177,27 @@ int wh_debug_read( wh_context* c, const char* what, int layer, int rows, float* 
 		WH_HIP( hipMemcpy( dstHost, w == "logits" ? c->logits : c->probs, (size_t)n * 4, hipMemcpyDeviceToHost ) );
 		return 0;
 	}
+	if( c->kv4 && ( w == "cross-k" || w == "cross-v" || w == "cross-k1" || w == "cross-v1" ) )
+	{
+		setError( "debug_read: this context holds INT4 cross-attention caches: read cross-k4 / cross-v4 and cross-k4-scale / cross-v4-scale" );
+		return WH_E_INVALIDARG;
+	}
+	if( w == "cross-k4" || w == "cross-v4" || w == "cross-k4-scale" || w == "cross-v4-scale" )
+	{
+		// one layer of the INT4 caches in their own order, raw: K nibbles [batch][heads][n_ctx][32 bytes], V nibbles [batch][heads][ceil( n_ctx / 64 )][64][32 bytes],
+		// scales [batch][heads][n_ctx]
+		if( !c->kv4 ) { setError( "debug_read: this context does not hold INT4 cross-attention caches (wh_context_create_kv4 creates them)" ); return WH_E_INVALIDARG; }
+		if( layer < 0 || layer >= hp.n_text_layer ) return WH_E_BOUNDS;
+		const bool isK = w[ 6 ] == 'k', scales = w.size() > 8;
+		const int64_t heads = (int64_t)batch * hp.n_text_head, heads0 = (int64_t)layer * c->maxBatch * hp.n_text_head, vBlocks = ( c->T + 63 ) / 64;
+		const int64_t bytes = scales ? heads * c->T * 4 : isK ? heads * c->T * ( HEAD_DIM / 2 ) : heads * vBlocks * 64 * ( HEAD_DIM / 2 );
+		if( bytes <= 0 || dstCapFloats * 4 < bytes ) return WH_E_BOUNDS;
+		const void* const src = scales ? (const void*)( ( isK ? c->crossKScale : c->crossVScale ) + heads0 * c->T ) :
+			isK ? (const void*)( c->crossK4 + heads0 * c->T * ( HEAD_DIM / 2 ) ) : (const void*)( c->crossV4 + heads0 * vBlocks * 64 * ( HEAD_DIM / 2 ) );
+		WH_HIP( hipStreamSynchronize( c->stream ) );
+		WH_HIP( hipMemcpy( dstHost, src, (size_t)bytes, hipMemcpyDeviceToHost ) );
+		return 0;
+	}
 	if( c->kv8 && ( w == "cross-k" || w == "cross-v" || w == "cross-k1" || w == "cross-v1" ) )
 	{
 		setError( "debug_read: this context holds FP8 cross-attention caches: read cross-k8 / cross-v8 and cross-k8-scale / cross-v8-scale" );
@@ -508,6 +529,28 @@ int wh_op_decoder_cross_attention_f8( void* stream, const void* qF16, const floa
 	DecAttnArgs a = {};
 	a.q = (const f16*)qF16; a.out = (f16*)outF16;
 	a.kc8 = (const uint8_t*)kBytes; a.vc8 = (const uint8_t*)vBytes; a.kScale = kScales; a.vScale = vScales;
+	a.batch = sequences; a.H = heads; a.nTok = nTok; a.nKeys = nKeys; a.keyStride = keyStride;
+	a.group = group;
+	if( x ) { a.lnX = x; a.lnW = lnW; a.lnB = lnB; a.qW = (const f16*)qW; a.qB = qB; a.qScale = qScale; }
+	return launchAttentionDec( a, (hipStream_t)stream );
+}
+
+int wh_op_quantize_cross_kv_i4( void* stream, const void* rowsF16, void* kNibbles, void* vNibbles, float* scalesOut, int64_t heads, int nKeys )
+{
+	return launchQuantizeCrossKV4( (const f16*)rowsF16, (uint8_t*)kNibbles, scalesOut, (const f16*)rowsF16, (uint8_t*)vNibbles, scalesOut, heads, nKeys, (hipStream_t)stream );
+}
+
+int wh_op_decoder_cross_attention_i4( void* stream, const void* qF16, const float* x, const float* lnW, const float* lnB, const void* qW, const float* qB, float qScale,
+	const void* kNibbles, const float* kScales, const void* vNibbles, const float* vScales, void* outF16, int sequences, int heads, int nTok, int nKeys, int keyStride, int group )
+{
+	if( !kNibbles || !kScales || !vNibbles || !vScales || !outF16 || ( !x && !qF16 ) || ( x && ( !lnW || !lnB || !qW || !qB ) ) )
+	{
+		setError( "decoder_cross_attention_i4: null argument" );
+		return WH_E_INVALIDARG;
+	}
+	DecAttnArgs a = {};
+	a.q = (const f16*)qF16; a.out = (f16*)outF16;
+	a.kc4 = (const uint8_t*)kNibbles; a.vc4 = (const uint8_t*)vNibbles; a.kScale = kScales; a.vScale = vScales;
 	a.batch = sequences; a.H = heads; a.nTok = nTok; a.nKeys = nKeys; a.keyStride = keyStride;
 	a.group = group;
 	if( x ) { a.lnX = x; a.lnW = lnW; a.lnB = lnB; a.qW = (const f16*)qW; a.qB = qB; a.qScale = qScale; }

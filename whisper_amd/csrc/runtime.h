@@ -12,7 +12,7 @@
 //     can receive it with a single RCCL broadcast. Q/K/V weights of a layer are concatenated to one [3d][d] matrix, the
 //     cross-attention K/V weights of ALL decoder layers to one [2*L*d][d] matrix (one big GEMM per window).
 //   * per context: activations for maxBatch windows in lock step + FP16 KV caches
-//       cross  [layer][batch][head][n_audio_ctx][64]   (K pre-scaled by (d/H)^-0.25, whisper.cpp:1465; wh_context_create_kv8: E4M3 bytes + row scales)
+//       cross  [layer][batch][head][n_audio_ctx][64]   (K pre-scaled by (d/H)^-0.25, whisper.cpp:1465; wh_context_create_kv8: E4M3 bytes + row scales; wh_context_create_kv4: nibbles + row scales)
 //       self   [layer][batch][head][n_text_ctx][64]
 #pragma once
 #include "kernels.h"
@@ -219,6 +219,10 @@ struct wh_context
 	uint8_t *crossK8 = nullptr, *crossV8 = nullptr;
 	float *crossKScale = nullptr, *crossVScale = nullptr;
 	f16* crossStage = nullptr;
+	// wh_context_create_kv4 (kv4.hip): nibbles n + 8 under the same scales and staging; K [layer][window][head][T][32 bytes], V [layer][window][head][ceil( T / 64 )]
+	// [64 dims][32 bytes] in blocks of 64 keys
+	bool kv4 = false;
+	uint8_t *crossK4 = nullptr, *crossV4 = nullptr;
 	// wh_context_set_encoder_i8: the encoder's QKV, out, MLP-up and MLP-down products on gemmI8. xq / xqScale: the int8 rows and row scales of the LayerNorm
 	// output, then of the attention output (the first is consumed before the second is formed); hq / hqScale: of the GELU output. Allocated by the first enable.
 	bool encI8 = false;

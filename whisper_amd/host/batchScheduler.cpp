@@ -29,6 +29,7 @@
 #include "batchNoRepeat.h"
 #include "batchSpeech.h"
 #include "batchCrossFp8.h"
+#include "batchCrossInt4.h"
 #include "batchEncoderI8.h"
 #include "optionRules.h"
 #include "decodeFallback.h"
@@ -62,6 +63,8 @@ namespace Whisper
 	pfnBatchSpeechPacker g_batchSpeechPacker = nullptr;
 	// ... and to the creation of a group's context with FP8 cross-attention caches (batchCrossFp8.h)
 	pfnBatchCreateKv8 g_batchCreateKv8 = nullptr;
+	// ... or with INT4 ones (batchCrossInt4.h)
+	pfnBatchCreateKv4 g_batchCreateKv4 = nullptr;
 	// ... and to the INT8 encoder products of a group's context (batchEncoderI8.h)
 	pfnBatchSetEncoderI8 g_batchSetEncoderI8 = nullptr;
 
@@ -750,6 +753,7 @@ namespace Whisper
 			uint32_t maxSlots = 64, nGroups = 2;
 			int chunk = 4, lookahead = 0;
 			bool crossFp8 = false;	   // sBatchSetup::flags bit 2: the groups' contexts hold FP8 cross-attention caches (the one-window loader context stays as it is)
+			bool crossInt4 = false;	   // sBatchSetup::flags bit value 8: INT4 cross-attention caches instead (never with bit 2: createBatchRunner refuses the pair)
 			bool encoderI8 = false;	   // sBatchSetup::flags bit value 4: the groups' contexts run the encoder's products in INT8 (may be combined with bit 2)
 			std::vector<Group> groups;
 			Shared shared;
@@ -774,7 +778,8 @@ namespace Whisper
 			// The setters answer in one order: the argument check (optionRules.h), E_NOTIMPL without the device entry, "nothing changes", then the new version
 			int createGroupContext( wh_context** out ) const
 			{
-				const int rc = crossFp8 ? g_batchCreateKv8( model->gpu, (int)maxSlots, nullptr, out ) : wh_context_create( model->gpu, (int)maxSlots, nullptr, out );
+				const int rc = crossInt4 ? g_batchCreateKv4( model->gpu, (int)maxSlots, nullptr, out ) :
+					crossFp8 ? g_batchCreateKv8( model->gpu, (int)maxSlots, nullptr, out ) : wh_context_create( model->gpu, (int)maxSlots, nullptr, out );
 				if( rc || !encoderI8 ) return rc;
 				const int rc8 = g_batchSetEncoderI8( *out, 1 );
 				if( rc8 )
@@ -845,6 +850,7 @@ namespace Whisper
 				if( setup && ( setup->flags & 1u ) ) lookahead = 1;
 				if( setup && ( setup->flags & 2u ) ) crossFp8 = true;
 				if( setup && ( setup->flags & 4u ) ) encoderI8 = true;
+				if( setup && ( setup->flags & 8u ) ) crossInt4 = true;
 				if( const char* e = getenv( "WHISPER_BATCH_SLOTS" ) ) maxSlots = (uint32_t)std::max( 1, atoi( e ) );
 				if( const char* e = getenv( "WHISPER_BATCH_GROUPS" ) ) nGroups = (uint32_t)std::max( 1, atoi( e ) );
 				if( const char* e = getenv( "WHISPER_BATCH_CHUNK" ) ) chunk = atoi( e );
@@ -1030,6 +1036,12 @@ namespace Whisper
 		const std::shared_ptr<LoadedModel> lm = mi->loaded();
 		mi->Release();
 		if( setup && ( setup->flags & 2u ) && !g_batchCreateKv8 ) return optionRules::notGiven( "createBatchRunner", "FP8 cross-attention caches" );
+		if( setup && ( setup->flags & 10u ) == 10u )
+		{
+			logError( "createBatchRunner: sBatchSetup::flags 2 (FP8 cross-attention caches) and 8 (INT4 cross-attention caches) exclude each other" );
+			return E_INVALIDARG;
+		}
+		if( setup && ( setup->flags & 8u ) && !g_batchCreateKv4 ) return optionRules::notGiven( "createBatchRunner", "INT4 cross-attention caches" );
 		if( setup && ( setup->flags & 4u ) && !g_batchSetEncoderI8 ) return optionRules::notGiven( "createBatchRunner", "INT8 encoder products" );
 		*pp = new BatchRunner( lm, model, setup );
 		return S_OK;

@@ -17,6 +17,7 @@
 #include "batchNoRepeat.h"
 #include "batchSpeech.h"
 #include "batchCrossFp8.h"
+#include "batchCrossInt4.h"
 #include "batchEncoderI8.h"
 #include "optionRules.h"
 #include "languageDetect.h"
@@ -1460,6 +1461,8 @@ namespace Whisper
 	static const bool g_speechPackerInstalled = ( g_batchSpeechPacker = &wh_context_speech_filter, true );
 	// ... and to the creation of a group's context with FP8 cross-attention caches (batchCrossFp8.h)
 	static const bool g_createKv8Installed = ( g_batchCreateKv8 = &wh_context_create_kv8, true );
+	// ... or with INT4 ones (batchCrossInt4.h)
+	static const bool g_createKv4Installed = ( g_batchCreateKv4 = &wh_context_create_kv4, true );
 	// ... and to the INT8 encoder products of a group's context (batchEncoderI8.h)
 	static const bool g_setEncoderI8Installed = ( g_batchSetEncoderI8 = &wh_context_set_encoder_i8, true );
 
