@@ -509,6 +509,16 @@ namespace Whisper
 	WHISPER_EXPORT HRESULT setNoRepeatNgram( iContext* context, int n );
 	// One n for all streams of every later run of the runner. E_INVALIDARG as above; E_NOTIMPL for n != 0 where the scheduler was built without the device's filter.
 	WHISPER_EXPORT HRESULT setBatchNoRepeatNgram( iBatchRunner* runner, int n );
+	// Extension: top-k and nucleus sampling for the SAMPLED attempts of the decoding fallback (Hugging Face's TopKLogitsWarper and TopPLogitsWarper behind the
+	// temperature, applied to the logits on the device: wh_context_set_nucleus). topK = 0 and topP = 1: off, the state of every new context. Otherwise every sampled
+	// step draws from the topK likeliest tokens (equal logits in ascending id) and, of those, from the shortest prefix whose probability at the attempt's temperature
+	// reaches topP, never fewer than one. Greedy decoding -- the first attempt, a run without the fallback, beam search -- is not touched, so without
+	// setDecodingFallback the setting has no effect; a window's first token, a forced timestamp, is never narrowed. THERE IS NO DEFAULT PAIR: none has been measured on
+	// a real checkpoint. E_INVALIDARG for topK outside 0 .. 1024, topP outside ( 0, 1 ] or NaN, and for a context of another library.
+	WHISPER_EXPORT HRESULT setSamplingFilter( iContext* context, int topK, float topP );
+	// One pair for all streams of every later run of the runner; a retried stream is narrowed at its own temperature, its greedy neighbours are not read. E_INVALIDARG
+	// as above; E_NOTIMPL for a pair that turns it on where the scheduler was built without the device's filter.
+	WHISPER_EXPORT HRESULT setBatchSamplingFilter( iBatchRunner* runner, int topK, float topP );
 	// Extension: token alternatives. k = 0: off, the state of every new context; 1 .. 8: every later run of the context keeps, for every token in its results, the
 	// k likeliest tokens of the decoding step that emitted it and their log-probabilities under the model's filtered distribution at temperature 1 (computed on the
 	// device next to the sampler: wh_context_set_alternatives), descending, equal logits in ascending id; { -1, -inf } where fewer than k tokens were possible.

@@ -127,6 +127,11 @@ int32_t whisperc_phrase_spellings( void* model, const char* text, int32_t* token
  * n-gram its window has already sampled; 0 = off, the state of every new context and runner. */
 int32_t whisperc_set_no_repeat_ngram( void* ctx, int32_t n );
 int32_t whisperc_batch_set_no_repeat_ngram( void* runner, int32_t n );
+/* Top-k and nucleus sampling (Whisper::setSamplingFilter / setBatchSamplingFilter of whisperApi.h): the sampled attempts of the decoding fallback draw from the topK
+ * likeliest tokens (0 = all, up to 1024) and, of those, the shortest prefix whose probability reaches topP (1 = all); ( 0, 1 ) = off, the state of every new context
+ * and runner. There is no default pair. */
+int32_t whisperc_set_sampling_filter( void* ctx, int32_t topK, float topP );
+int32_t whisperc_batch_set_sampling_filter( void* runner, int32_t topK, float topP );
 /* Token alternatives (Whisper::setTokenAlternatives / getTokenAlternatives of whisperApi.h): k = 1 .. 8 = every later run keeps the k likeliest tokens, with their
  * log-probabilities, of the step that emitted each token of its results; 0 = off. whisperc_alternatives: out = sTokenAlternative [cap] (may be NULL), *count =
  * tokens x k of the last run in the order of the results' token array, *k = that run's k. */

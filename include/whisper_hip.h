@@ -687,6 +687,18 @@ typedef struct wh_token_alternative
 	float logprob;
 } wh_token_alternative;
 WH_API int wh_context_set_alternatives( wh_context* c, int k );
+
+/* Top-k and nucleus sampling (Hugging Face's TopKLogitsWarper and TopPLogitsWarper behind the temperature; DESIGN.md section 7 "Top-k and nucleus sampling" holds
+ * the definition, tests/nucleus_ref.py restates it in float64). topK = 0 and topP = 1 are off, the state of every new context; there is NO recommended pair -- none
+ * was measured on a real checkpoint. With either on, every step of the device-side loop whose rows SAMPLE (a temperature from wh_context_set_sampling, or a row
+ * that wh_context_set_sampling_rows gave one) queues one launch behind the other logit filters and in front of the sampler: in the order ( logit descending, id
+ * ascending ) the first topK entries of the row stay (a row with topK or fewer entries above -inf is left alone), of those the shortest prefix whose share of
+ * softmax( x / T ) reaches topP -- T the row's own temperature, read on the device -- and never fewer than one; the rest becomes -inf. A greedy row is neither read
+ * nor written, a greedy context launches nothing, and the first sample of a window (the prompt step's forced timestamp, whose row the no-speech gather reads)
+ * is never narrowed. Token alternatives record the narrowed row, as with every other filter. The two values live in device memory: one captured step serves
+ * every pair. WH_E_INVALIDARG with a message: topK outside 0 .. 1024, topP outside (0, 1] or NaN, and -- for a pair that turns it on -- a hypothesis-group
+ * context, WH_FLAG_PARITY_EXACT, or a vocabulary above 53248. */
+WH_API int wh_context_set_nucleus( wh_context* c, int topK, float topP );
 WH_API int wh_decode_window_alternatives( wh_context* c, int first, int count, wh_token_alternative* outHost );
 
 /* Per-kernel-class GPU timings, the counterpart of the reference's GpuProfiler / iContext::timingsPrint
@@ -920,6 +932,11 @@ WH_API int wh_op_token_scores( void* stream, const float* logits, int64_t rowStr
  * registers: nVocab <= 53248. A null operand, k outside 1 .. 8, rows < 1, nVocab < 1 or above 53248, or rowStride < nVocab is WH_E_INVALIDARG with a message and
  * nothing is launched. Vector stores only: no atomics, no scratch memory. */
 WH_API int wh_op_top_logprobs( void* stream, const float* logitsDev, int64_t rowStride, int rows, int nVocab, int k, wh_token_alternative* outDev );
+/* The kernel of wh_context_set_nucleus outside a context, in place on rows of FP32 logits rowStride >= nVocab floats apart (4-byte alignment; floats between the rows
+ * are never touched). invTDev: DEVICE float [rows], 1 / T of every row; a row whose factor is 0 comes back bit for bit. Only discarded entries are written (-inf).
+ * One 1024-thread workgroup per row, the row read once and kept in registers: nVocab <= 53248. LDS atomics on integers only: the same input gives the same bits.
+ * A null operand, rows < 1, nVocab < 1 or above 53248, rowStride < nVocab, topK outside 0 .. 1024 or topP outside (0, 1] is WH_E_INVALIDARG with a message. */
+WH_API int wh_op_nucleus_logits( void* stream, float* logitsDev, int rows, int64_t rowStride, int nVocab, int topK, float topP, const float* invTDev );
 /* wh_sample_best on probabilities [rows][nVocab]: out [rows]. tokenBeg .. nVocab - 1 are the timestamps; the specials are < tokenBeg. */
 WH_API int wh_op_sample_best( void* stream, const float* probs, int rows, int nVocab, int tokenBeg, int tokenSot, int tokenSolm, int tokenNot,
 	int forceTimestamp, int isInitial, wh_token_data* out );

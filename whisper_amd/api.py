@@ -86,6 +86,8 @@ def lib():
         L.whisperc_batch_set_boost_phrases.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_float]
         L.whisperc_set_no_repeat_ngram.argtypes = [vp, C.c_int32]
         L.whisperc_batch_set_no_repeat_ngram.argtypes = [vp, C.c_int32]
+        L.whisperc_set_sampling_filter.argtypes = [vp, C.c_int32, C.c_float]
+        L.whisperc_batch_set_sampling_filter.argtypes = [vp, C.c_int32, C.c_float]
         L.whisperc_set_alternatives.argtypes = [vp, C.c_uint32]
         L.whisperc_alternatives.argtypes = [vp, vp, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.whisperc_phrase_spellings.argtypes = [vp, C.c_char_p, vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]
@@ -655,6 +657,13 @@ class Context:
         off, the state of a new context. There is no default n: none has been measured on a real checkpoint. With it on, beam search raises (E_NOTIMPL)."""
         _check(lib().whisperc_set_no_repeat_ngram(self.h, int(n or 0)), "setNoRepeatNgram")
 
+    def set_sampling_filter(self, top_k: int = 0, top_p: float = 1.0):
+        """Whisper::setSamplingFilter (Hugging Face's top_k and top_p behind the temperature): the sampled attempts of the decoding fallback draw from the top_k
+        likeliest tokens (0 = all, up to 1024) and, of those, from the shortest prefix whose probability at the attempt's temperature reaches top_p (1 = all).
+        (0, 1.0) turns it off, the state of a new context. Greedy decoding is not touched, so without set_fallback it has no effect. There is no default pair: none
+        has been measured on a real checkpoint."""
+        _check(lib().whisperc_set_sampling_filter(self.h, int(top_k), float(top_p)), "setSamplingFilter")
+
     def set_alternatives(self, k: Optional[int]):
         """Whisper::setTokenAlternatives: every later run of this context keeps, for every token of its results, the k (1 .. 8) likeliest tokens of the step that
         emitted it and their log-probabilities (alternatives()). 0 or None turns it off, the state of a new context. With it on, beam search raises (E_NOTIMPL)."""
@@ -829,6 +838,11 @@ class BatchRunner:
     def set_no_repeat_ngram(self, n: Optional[int]):
         """Whisper::setBatchNoRepeatNgram: Context.set_no_repeat_ngram for every stream of this runner's later runs (one n for all of them)."""
         _check(lib().whisperc_batch_set_no_repeat_ngram(self.h, int(n or 0)), "setBatchNoRepeatNgram")
+
+    def set_sampling_filter(self, top_k: int = 0, top_p: float = 1.0):
+        """Whisper::setBatchSamplingFilter: Context.set_sampling_filter for every stream of this runner's later runs (one pair for all of them; a retried stream is
+        narrowed at its own temperature)."""
+        _check(lib().whisperc_batch_set_sampling_filter(self.h, int(top_k), float(top_p)), "setBatchSamplingFilter")
 
     def set_boost_phrases(self, phrases=None, boost: Optional[float] = None):
         """Whisper::setBatchBoostedPhrases: Context.set_boost_phrases for every stream of this runner's later runs (one set and one boost for all of them)."""

@@ -69,6 +69,7 @@ EXPORTS = [
     "wh_op_quantize_kv", "wh_op_decoder_cross_attention_f8", "wh_op_quantize_cross_kv_i4", "wh_op_decoder_cross_attention_i4",
     "wh_op_quantize_rows_i8", "wh_op_layer_norm_i8", "wh_op_gemm_encoder_i8",
     "wh_context_set_alternatives", "wh_decode_window_alternatives", "wh_op_top_logprobs",
+    "wh_context_set_nucleus", "wh_op_nucleus_logits",
 ]
 
 
@@ -325,6 +326,8 @@ def lib():
         L.wh_context_set_alternatives.argtypes = [vp, i32]
         L.wh_decode_window_alternatives.argtypes = [vp, i32, i32, vp]
         L.wh_op_top_logprobs.argtypes = [vp, vp, i64, i32, i32, i32, vp]
+        L.wh_context_set_nucleus.argtypes = [vp, i32, C.c_float]
+        L.wh_op_nucleus_logits.argtypes = [vp, vp, i32, i64, i32, i32, C.c_float, vp]
         _lib = L
     return _lib
 
@@ -351,6 +354,12 @@ def op_token_scores(logits_ptr, row_stride: int, rows: int, n_vocab: int, target
 
 
 TOKEN_ALTERNATIVE_DTYPE = np.dtype([("id", "<i4"), ("logprob", "<f4")])
+
+
+def op_nucleus_logits(logits_ptr, rows: int, row_stride: int, n_vocab: int, top_k: int, top_p: float, inv_t_ptr, stream=None):
+    """wh_op_nucleus_logits on device memory, in place: of row r of the FP32 logits (row_stride floats apart) the top_k largest entries stay, of those the shortest
+    prefix whose share of softmax(x * inv_t[r]) reaches top_p, the rest becomes -inf; a row whose inv_t is 0 is not touched."""
+    check(lib().wh_op_nucleus_logits(stream, logits_ptr, int(rows), int(row_stride), int(n_vocab), int(top_k), float(top_p), inv_t_ptr))
 
 
 def op_top_logprobs(logits_ptr, row_stride: int, rows: int, n_vocab: int, k: int, out_ptr, stream=None):
@@ -539,6 +548,11 @@ class HipContext:
         out = np.empty(batch, np.float32)
         check(lib().wh_decode_window_no_speech(self.handle, out.ctypes.data_as(C.c_void_p)))
         return out
+
+    def set_nucleus(self, top_k: int = 0, top_p: float = 1.0):
+        """Top-k and nucleus sampling for the rows that sample (set_sampling, set_sampling_rows): the top_k likeliest tokens stay (0 = all), of those the shortest
+        prefix whose probability at the row's temperature reaches top_p (1 = all). (0, 1.0) = off, the default; there is no recommended pair."""
+        check(lib().wh_context_set_nucleus(self.handle, int(top_k), float(top_p)))
 
     def set_alternatives(self, k: Optional[int]):
         """k = 1 .. 8: every sample of the device-side loop also records the k likeliest tokens of the row its sampler read, with their log-probabilities

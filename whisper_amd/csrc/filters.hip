@@ -2,6 +2,7 @@
 // n-grams. Kernels next to the entry points that own their buffers, like align.hip, resample.hip and speech.hip; boost.hip is the host half of phrase boosting.
 // All four write c->logits in place between the vocabulary product and the sampler. This unit alone names a member of wh_context::filters; the other units call
 // the functions of runtime.h defined below the kernels. A filter added here touches this file, the struct and its setter's declaration -- no other unit.
+// The fifth, top-k and nucleus sampling, has its kernel in a unit of its own (nucleus.hip); its launch and its owner are here like the others'.
 #include "runtime.h"
 #include <algorithm>
 
@@ -273,6 +274,7 @@ void wh::bypassFilterLogits( wh_context* c, bool on ) { c->filters.suppressOff =
 // wh_align_tokens and the beam step do not. The order -- rules, boost, n-grams -- does not change the row: the two masks only write -inf, and -inf + boost stays
 // -inf. `phase` is the kernels' reset argument (their header comments say what 0, 1 and 2 do). The one asymmetry: FILTER_ARM arms the boost states with a memset
 // (-1 in every int), not a launch: a boost launch adds the new state's offers in every phase, and wh_decode_greedy has no row yet -- the first step boosts its own.
+static bool nucleusLaunches( const wh_context* c ) { return c->filters.nucleusOn && ( c->temperature > 0.0f || c->sampleRowsOn ); }
 int wh::filterLoopRows( wh_context* c, int batch, eFilterPhase phase )
 {
 	const LogitFilters& f = c->filters;
@@ -288,6 +290,19 @@ int wh::filterLoopRows( wh_context* c, int batch, eFilterPhase phase )
 	if( f.ngramN )
 		WH_CHECK( profiled( c, KC_SAMPLE, 0.0, 4.0 * batch * hp.n_text_ctx,
 			[ & ]() { return launchNoRepeat( c->logits, batch, hp.n_vocab, eot, f.ngramN, c->tokensDev, reset, f.ngramHistory, f.ngramCounts, hp.n_text_ctx, c->stream ); } ) );
+	// Top-k and nucleus sampling: LAST, so that it ranks the row the sampler reads, and on loop steps only -- the prompt step's sample is a forced timestamp and the
+	// no-speech gather reads its row. Only where a row samples: under wh_context_set_sampling every row at the context's factor, under wh_context_set_sampling_rows
+	// each row at its record's, a greedy row (sampled == 0) neither read nor written. A greedy context launches nothing.
+	if( nucleusLaunches( c ) && phase == FILTER_STEP )
+	{
+		const bool perRow = c->sampleRowsOn != 0;
+		const float* const invT = perRow ? &c->sampleRows->invT : &c->sampleParams->invT;
+		const unsigned* const on = perRow ? &c->sampleRows->sampled : nullptr;
+		constexpr int stride = (int)( sizeof( SampleRowParams ) / sizeof( float ) );
+		// (bytes: the row read once and written at most once; with per-row records only the sampled rows do either, so this is an upper bound)
+		WH_CHECK( profiled( c, KC_SAMPLE, 0.0, 8.0 * batch * hp.n_vocab,
+			[ & ]() { return launchNucleusLogits( c->logits, hp.n_vocab, batch, hp.n_vocab, f.nucleusParams, 0, 1.0f, invT, perRow ? stride : 0, on, perRow ? stride : 0, c->stream ); } ) );
+	}
 	return 0;
 }
 
@@ -296,17 +311,19 @@ int wh::filterLoopRows( wh_context* c, int batch, eFilterPhase phase )
 //   STEP_KEY_TS_RULES       the timestamp rules are on: one more node in front of the sampler, the same for every window
 //   STEP_KEY_BOOST          a set of boosted phrases is held: one more node in front of the sampler, the same for every set and boost
 //   STEP_KEY_NO_REPEAT * n  no-repeat n-grams are on, n = 1 .. 8 in bits 27-30: one more node there, and n is its kernel's argument, so no graph serves another n
-// The last three are the greedy loop's alone: a beam step has no sampler in front of which they would run, and their bits stay clear in its key.
-static constexpr uint32_t STEP_KEY_SUPPRESS = 0x80000u, STEP_KEY_TS_RULES = 0x100000u, STEP_KEY_BOOST = 0x4000000u, STEP_KEY_NO_REPEAT = 0x8000000u;
+//   STEP_KEY_NUCLEUS        top-k / nucleus sampling is on AND the step samples (a temperature, or per-row records): one more node there, the same for every k and p
+// The last four are the greedy loop's alone: a beam step has no sampler in front of which they would run, and their bits stay clear in its key.
+static constexpr uint32_t STEP_KEY_SUPPRESS = 0x80000u, STEP_KEY_TS_RULES = 0x100000u, STEP_KEY_BOOST = 0x4000000u, STEP_KEY_NO_REPEAT = 0x8000000u, STEP_KEY_NUCLEUS = 0x80000000u;
 uint32_t wh::filterGraphKey( const wh_context* c ) { return c->filters.suppressHeld > 0 ? STEP_KEY_SUPPRESS : 0u; }
 uint32_t wh::filterLoopKey( const wh_context* c )
 {
 	const LogitFilters& f = c->filters;
-	return ( f.rulesOn ? STEP_KEY_TS_RULES : 0u ) | ( f.phrasesOn ? STEP_KEY_BOOST : 0u ) | STEP_KEY_NO_REPEAT * (uint32_t)f.ngramN;
+	return ( f.rulesOn ? STEP_KEY_TS_RULES : 0u ) | ( f.phrasesOn ? STEP_KEY_BOOST : 0u ) | STEP_KEY_NO_REPEAT * (uint32_t)f.ngramN | ( nucleusLaunches( c ) ? STEP_KEY_NUCLEUS : 0u );
 }
 
 // Everything in the filters' device memory that a step of the loop mutates, for `batch` rows: the ONE list of which buffers there are and how big each is,
-// handed to `f` in a fixed order. (The suppressed set and the boost tables are read only.)
+// handed to `f` in a fixed order. (The suppressed set, the boost tables and the nucleus filter's two values are read only: that filter keeps nothing per row,
+// and the logits a warm-up step's launch narrows are written anew by every step.)
 template<class F> static int eachRowBuffer( const wh_context* c, int batch, F&& f )
 {
 	const LogitFilters& s = c->filters;
@@ -342,7 +359,7 @@ int wh::filtersAllowFlags( const wh_context* c, uint32_t flags )
 {
 	const LogitFilters& f = c->filters;
 	const char* const held = f.suppressHeld > 0 ? "wh_context_set_suppress holds a set" : f.phrasesOn ? "wh_context_set_boost holds a set" :
-		f.ngramN ? "wh_context_set_no_repeat is on" : f.rulesOn ? "wh_context_set_timestamp_rules is on" : nullptr;
+		f.ngramN ? "wh_context_set_no_repeat is on" : f.rulesOn ? "wh_context_set_timestamp_rules is on" : f.nucleusOn ? "wh_context_set_nucleus is on" : nullptr;
 	return ( flags & WH_FLAG_PARITY_EXACT ) && held ? refuse( std::string( "context_set_flags: WH_FLAG_PARITY_EXACT is not available while " ) + held ) : 0;
 }
 // a filter with a state per row changes its switch behind the stream -- a chunk queued earlier has run under the mode it was enqueued in: the off path's wait
@@ -418,5 +435,25 @@ extern "C" int wh_context_set_no_repeat( wh_context* c, int n )
 	if( !f.ngramCounts ) WH_CHECK( c->alloc( f.ngramCounts, (int64_t)c->maxSeq, wh_context::MUST_BE_ZERO, "nrnCounts" ) );
 	WH_HIP( hipStreamSynchronize( c->stream ) );
 	f.ngramN = n;
+	return 0;
+}
+
+// Top-k and nucleus sampling. The two values go to device memory behind what the stream holds; the kernel (nucleus.hip) reads them there.
+extern "C" int wh_context_set_nucleus( wh_context* c, int topK, float topP )
+{
+	if( !c ) return refuse( "context_set_nucleus: null context" );
+	if( topK < 0 || topK > NUCLEUS_MAX_K ) return refuse( "context_set_nucleus: top_k outside 0 .. 1024" );
+	if( !( topP > 0.0f && topP <= 1.0f ) ) return refuse( "context_set_nucleus: top_p outside (0, 1]" );
+	LogitFilters& f = c->filters;
+	if( topK == 0 && topP == 1.0f ) { if( f.nucleusOn ) WH_CHECK( waitForStream( c ) ); f.nucleusOn = false; return 0; }
+	if( c->hyp != 1 ) return refuse( "context_set_nucleus: not available on a hypothesis-group context (no row samples there: wh_context_set_sampling is refused too)" );
+	WH_CHECK( mayTurnOn( c, "context_set_nucleus", nullptr ) );
+	if( c->m->hp.n_vocab > NUCLEUS_MAX_VOCAB ) return refuse( "context_set_nucleus: vocabulary larger than 53248 (the row is held in registers)" );
+	WH_BIND( c->m );
+	if( !f.nucleusParams ) WH_CHECK( c->alloc( f.nucleusParams, 1, wh_context::DONT_CARE, "nucleusParams" ) );
+	const NucleusParams p = { topK, topP };
+	WH_HIP( hipMemcpyAsync( f.nucleusParams, &p, sizeof( p ), hipMemcpyHostToDevice, c->stream ) );
+	WH_HIP( hipStreamSynchronize( c->stream ) );	 // `p` is on this stack
+	f.nucleusOn = true;
 	return 0;
 }

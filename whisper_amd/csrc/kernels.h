@@ -565,6 +565,19 @@ namespace wh
 	// to every column t < tokenEot that would complete an n-gram the history already holds; 1 empties every history and 2 arms it, both without touching the logits.
 	// Every index read from device memory is held inside the row's history and inside the row. The grid depends on the rows alone.
 	int launchNoRepeat( float* logits, int rows, int nVocab, int tokenEot, int n, const int* fed, int reset, int* history, int* counts, int cap, hipStream_t stream );
+	// Top-k and nucleus sampling (nucleus.hip; wh_context_set_nucleus; DESIGN.md section 7 "Top-k and nucleus sampling"): of row r at logits + r * rowStride, in place,
+	// the topK largest entries stay (0 = all; equal values in ascending id), of those the shortest prefix whose share of sum exp( ( x - max ) * invT ) reaches topP
+	// (1 = all), and the rest becomes -inf. prmDev non-null: topK and topP are read from device memory instead (a captured step graph outlives a change of either).
+	// Row r's factor is invTDev[ r * invTStride ] (device); a row whose factor is not above 0, or -- onDev non-null -- whose word onDev[ r * onStride ] is 0, is
+	// neither read nor written. nVocab <= NUCLEUS_MAX_VOCAB. The grid depends on the rows alone.
+	struct NucleusParams
+	{
+		int topK;
+		float topP;
+	};
+	constexpr int NUCLEUS_MAX_K = 1024, NUCLEUS_MAX_VOCAB = 53248;
+	int launchNucleusLogits( float* logits, long long rowStride, int rows, int nVocab, const NucleusParams* prmDev, int topK, float topP, const float* invTDev, int invTStride,
+		const unsigned* onDev, int onStride, hipStream_t stream );
 
 	// ---------------------------------------------------------------------------------------------------------------
 	// mel spectrogram

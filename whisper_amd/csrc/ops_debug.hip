@@ -688,6 +688,16 @@ int wh_op_no_repeat_ngram( void* stream, float* logits, int rows, int nVocab, in
 	return launchNoRepeat( logits, rows, nVocab, tokenEot, n, fedDev, reset, historyDev, countsDev, cap, (hipStream_t)stream );
 }
 
+int wh_op_nucleus_logits( void* stream, float* logitsDev, int rows, int64_t rowStride, int nVocab, int topK, float topP, const float* invTDev )
+{
+	if( !logitsDev || !invTDev || rows < 1 || nVocab < 1 || nVocab > NUCLEUS_MAX_VOCAB || rowStride < nVocab || topK < 0 || topK > NUCLEUS_MAX_K || !( topP > 0.0f && topP <= 1.0f ) )
+	{
+		setError( "nucleus_logits: null pointer, empty shape, more than 53248 columns, rowStride < nVocab, top_k outside 0 .. 1024 or top_p outside (0, 1]" );
+		return WH_E_INVALIDARG;
+	}
+	return launchNucleusLogits( logitsDev, rowStride, rows, nVocab, nullptr, topK, topP, invTDev, 1, nullptr, 0, (hipStream_t)stream );
+}
+
 int wh_op_lang_probs( void* stream, const float* logits, int rows, int nVocab, int tokenSot, int nLang, float* langP, int32_t* best )
 {
 	if( !logits || !langP || !best || rows < 1 || nVocab < 1 || nVocab > 52224 || nLang < 1 || nLang > 1024 || tokenSot < 0 || (int64_t)tokenSot + 1 + nLang > nVocab )
@@ -1155,9 +1165,16 @@ int wh_debug_probe( wh_context* c, int kind, int variant, int M, int N, int K, i
 		// stores. An untimed copy puts the counts back to K - 1 in front of every timed launch.
 		// Variant 9 = topLogprobsKernel alone (wh_context_set_alternatives), 10 = its per-thread sorted-insertion form (tools/alternatives_probe.py); K is k, 1 .. 8.
 		// Behind the timed launches of variant 10 both forms run on one buffer and their ids are compared: a difference fails the probe.
+		// Variant 11 = nucleusLogitsKernel alone (wh_context_set_nucleus; tools/nucleus_probe.py) at T = 1; K = top_k + 2048 * round( 100 * top_p ). The kernel narrows
+		// its input, and a narrowed row is no work: the warm-up launches use up buffers 0 .. 4, the timed ones start on buffer 5, and all buffers are filled anew
+		// (untimed) whenever the rotation comes back to buffer 0. At 448 rows the 7 buffers exceed the last-level cache; at 1 row the 64 buffers are 13 MB and stay
+		// cached: that figure is the kernel's latency on a cached row, which is what a step's vocabulary product leaves it.
 		const int rows = M, nVocab = N;
-		if( rows < 1 || rows > 4096 || nVocab < 2048 || nVocab > 52224 || variant < 0 || variant > 10 ) return WH_E_INVALIDARG;
-		const bool alt = variant >= 9;
+		if( rows < 1 || rows > 4096 || nVocab < 2048 || nVocab > 52224 || variant < 0 || variant > 11 ) return WH_E_INVALIDARG;
+		const bool alt = variant == 9 || variant == 10, nuc = variant == 11;
+		const int nucK = K & 2047;
+		const float nucP = (float)( K >> 11 ) * 0.01f;
+		if( nuc && ( K < 0 || nucK > NUCLEUS_MAX_K || !( nucP > 0.0f && nucP <= 1.0f ) ) ) return WH_E_INVALIDARG;
 		if( alt && ( K < 1 || K > ALT_MAX_K ) ) return WH_E_INVALIDARG;
 		const bool tsr = variant == 4 || variant == 5, boostOnly = variant == 6, nrn = variant == 7 || variant == 8;
 		constexpr int nrnCap = 448, nrnN = 3;
@@ -1246,8 +1263,18 @@ int wh_debug_probe( wh_context* c, int kind, int variant, int M, int N, int K, i
 			WH_HIP( hipMemcpy( nrnFed, fedHost.data(), sizeof( int ) * (size_t)rows, hipMemcpyHostToDevice ) );
 		}
 		TokenAlternative* const altOut = (TokenAlternative*)probs;	  // rows * 8 records, twice: far below a row of floats per row
+		float* const nucInvT = probs;	  // rows factors
+		const std::vector<float> nucOnes( (size_t)rows, 1.0f );
+		if( nuc ) WH_HIP( hipMemcpy( nucInvT, nucOnes.data(), sizeof( float ) * (size_t)rows, hipMemcpyHostToDevice ) );
+		const auto refill = [ & ]() -> int
+		{
+			for( int b = 0; b < nBuf; b++ ) hipLaunchKernelGGL( probeFillF32, dim3( 1024 ), dim3( 256 ), 0, st, logits[ b ], (long long)rows * nVocab, 11u + (unsigned)b );
+			WH_HIP( hipGetLastError() );
+			return 0;
+		};
 		const auto launch = [ & ]( float* x ) -> int
 		{
+			if( nuc ) return launchNucleusLogits( x, nVocab, rows, nVocab, nullptr, nucK, nucP, nucInvT, 1, nullptr, 0, st );
 			if( variant == 9 ) return launchTopLogprobs( x, nVocab, rows, nVocab, K, nullptr, 0, altOut, st );
 			if( variant == 10 ) return launchTopLogprobsInsert( x, nVocab, rows, nVocab, K, altOut, st );
 			if( nrn )
@@ -1277,6 +1304,7 @@ int wh_debug_probe( wh_context* c, int kind, int variant, int M, int N, int K, i
 		{
 			if( tsr && K == 2 ) WH_CHECK( launchTimestampRules( probs, rows, nVocab, sot - 1, beg, fedText, 0, records, st ) );
 			if( nrn ) WH_HIP( hipMemcpyAsync( nrnCounts, nrnCounts0, sizeof( int ) * (size_t)rows, hipMemcpyDeviceToDevice, st ) );
+			if( nuc && ( 5 + i ) % nBuf == 0 ) WH_CHECK( refill() );
 			WH_HIP( hipEventRecord( e0, st ) );
 			WH_CHECK( launch( logits[ (size_t)( ( 5 + i ) % nBuf ) ] ) );
 			WH_HIP( hipEventRecord( e1, st ) );

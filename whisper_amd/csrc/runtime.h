@@ -188,6 +188,9 @@ struct LogitFilters
 	// wh_context_set_no_repeat: ngramN = n, 0 = off; ngramHistory [maxSeq][n_text_ctx], ngramCounts [maxSeq]
 	int ngramN = 0;
 	int *ngramHistory = nullptr, *ngramCounts = nullptr;
+	// wh_context_set_nucleus: nucleusOn = top_k above 0 or top_p below 1; nucleusParams: the two values in device memory (one captured step serves every pair)
+	bool nucleusOn = false;
+	wh::NucleusParams* nucleusParams = nullptr;
 };
 
 struct wh_context
@@ -481,7 +484,7 @@ namespace wh
 	int alignDebugRead( wh_context* c, const std::string& w, int layer, float* dstHost, int64_t dstCapFloats );
 
 	// captured decode steps (step_graph.hip, where each of these is explained)
-	constexpr uint32_t STEP_KEY_ROWS = 0x40000u, STEP_KEY_BEAM = 0x200000u;	  // bits 19, 20 and 26-30 are the filters' (filterGraphKey, filterLoopKey)
+	constexpr uint32_t STEP_KEY_ROWS = 0x40000u, STEP_KEY_BEAM = 0x200000u;	  // bits 19, 20 and 26-31 are the filters' (filterGraphKey, filterLoopKey)
 	using StepFn = std::function<int()>;
 	enum eWarmUp { WARM_FRESH, WARM_PRESERVE };
 	bool stepsReplayable( const wh_context* c );

@@ -27,6 +27,7 @@
 #include "batchTimestampRules.h"
 #include "batchBoost.h"
 #include "batchNoRepeat.h"
+#include "batchNucleus.h"
 #include "batchSpeech.h"
 #include "batchCrossFp8.h"
 #include "batchCrossInt4.h"
@@ -57,6 +58,8 @@ namespace Whisper
 	pfnBatchBoost g_batchBoost = nullptr;
 	// ... and for no-repeat n-grams (batchNoRepeat.h)
 	pfnBatchNoRepeat g_batchNoRepeat = nullptr;
+	// ... and for top-k and nucleus sampling (batchNucleus.h)
+	pfnBatchNucleus g_batchNucleus = nullptr;
 	// ... and to the scorer of given transcripts (scoreRequest.h)
 	pfnBatchScorer g_batchScorer = nullptr;
 	// ... and to the speech filter of a newly admitted stream (batchSpeech.h)
@@ -226,6 +229,9 @@ namespace Whisper
 			uint32_t boostVersion = 0;
 			// no-repeat n-grams: the n this group's context holds (a new context holds 0, off)
 			int noRepeatN = 0;
+			// top-k and nucleus sampling: the pair this group's context holds (a new context holds 0 and 1, off)
+			int topK = 0;
+			float topP = 1.0f;
 		};
 
 		// One call of iBatchRunner::run over the runner's groups (their wh_contexts outlive the call: KV caches, captured graphs)
@@ -771,6 +777,10 @@ namespace Whisper
 			uint32_t boostVersion = 0;
 			// Whisper::setBatchNoRepeatNgram: one n for every stream, 0 = off; a group's context is told before the first round in which it holds another n
 			int noRepeatN = 0;
+			// Whisper::setBatchSamplingFilter: one pair for every stream, ( 0, 1 ) = off; a group's context is told before the first round in which it holds another.
+			// It narrows the rows a round's fallback samples, each at its own temperature; greedy rows are not touched
+			int topK = 0;
+			float topP = 1.0f;
 			// Whisper::setBatchSpeechFilter: off unless set; every stream of a run is filtered when it is admitted
 			bool speechOn = false;
 			sSpeechFilter speechParams{};
@@ -813,6 +823,14 @@ namespace Whisper
 				CHECK( optionRules::checkNoRepeat( "setBatchNoRepeatNgram", n ) );
 				if( n && !g_batchNoRepeat ) return optionRules::notGiven( "setBatchNoRepeatNgram", "n-gram filter" );
 				noRepeatN = n;
+				return S_OK;
+			}
+			HRESULT setSamplingFilter( int k, float p )
+			{
+				CHECK( optionRules::checkSamplingFilter( "setBatchSamplingFilter", k, p ) );
+				if( ( k != 0 || p != 1.0f ) && !g_batchNucleus ) return optionRules::notGiven( "setBatchSamplingFilter", "top-k / nucleus filter" );
+				topK = k;
+				topP = p;
 				return S_OK;
 			}
 			HRESULT setTimestampRulesMode( bool on )
@@ -996,6 +1014,12 @@ namespace Whisper
 						CHECK_WH( g_batchNoRepeat( g.gpu, noRepeatN ) );
 						g.noRepeatN = noRepeatN;
 					}
+					if( ( g.topK != topK || g.topP != topP ) && g_batchNucleus )
+					{
+						CHECK_WH( g_batchNucleus( g.gpu, topK, topP ) );
+						g.topK = topK;
+						g.topP = topP;
+					}
 				}
 				if( modesDirty && !fallbackOn )
 				{
@@ -1071,6 +1095,11 @@ namespace Whisper
 	{
 		return optionRules::forward<BatchRunner>( runner, "setBatchNoRepeatNgram", NOT_A_RUNNER, nullptr,
 			[ = ]( BatchRunner& r ) { return r.setNoRepeat( n ); } );
+	}
+	HRESULT setBatchSamplingFilter( iBatchRunner* runner, int topK, float topP )
+	{
+		return optionRules::forward<BatchRunner>( runner, "setBatchSamplingFilter", NOT_A_RUNNER, nullptr,
+			[ = ]( BatchRunner& r ) { return r.setSamplingFilter( topK, topP ); } );
 	}
 	HRESULT setBatchSpeechFilter( iBatchRunner* runner, const sSpeechFilter* params )
 	{

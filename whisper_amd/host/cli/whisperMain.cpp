@@ -490,6 +490,8 @@ int main( int argc, char** argv )
 	// token -- its time with --align (forced alignment), log-probability, rank, text -- and a summary line
 	// --boost-phrases FILE --boost N (the same way; one needs the other): Whisper::setBoostedPhrases with the spellings of the file's phrases, one per line
 	// -nrn N / --no-repeat-ngram N (the same way): Whisper::setNoRepeatNgram, no text token that would complete an n-gram its window already holds (0 = off)
+	// --top-k N --top-p X (the same way; either alone is fine): Whisper::setSamplingFilter, the sampled attempts of --fallback draw from the N likeliest tokens and, of
+	// those, the shortest prefix whose probability reaches X (0 and 1 = off). Legal without --fallback, and then WITHOUT EFFECT: greedy decoding samples nothing
 	// --capture PATH (the same way; PATH "-" = standard input): live transcription of raw 16 kHz PCM instead of input files -- --capture-format s16|f32 (s16),
 	// --capture-channels 1|2 (1); --capture-min-duration / --capture-max-duration / --capture-drop-start-silence / --capture-pause-duration N seconds
 	// (sCaptureParams: 2, 3, 0.25, 0.333); --capture-rate N: the input has N frames per second, 1000 .. 384000 (16000); --capture-no-drop: eCaptureFlags::NoDrop, for input that arrives faster than real time; -di keeps the stereo
@@ -499,7 +501,8 @@ int main( int argc, char** argv )
 	float soMinSilence = 0.0f, soMinSpeech = 0.0f, soPad = 0.0f;
 	CaptureOptions capture;
 	bool align = false, useFallback = false, suppressNst = false, timestampRules = false, haveBoost = false;
-	int noRepeatNgram = 0;
+	int noRepeatNgram = 0, topK = 0;
+	float topP = 1.0f;
 	std::string scoreFile, boostFile;
 	float boost = 0.0f;
 	sDecodingFallback fallbackParams;
@@ -562,6 +565,12 @@ int main( int argc, char** argv )
 				if( i + 1 >= argc ) { fprintf( stderr, "error: %s needs a number\n", argv[ i ] ); return 2; }
 				noRepeatNgram = atoi( argv[ ++i ] );
 			}
+			else if( !strcmp( argv[ i ], "--top-k" ) )
+			{
+				if( i + 1 >= argc ) { fprintf( stderr, "error: %s needs a number\n", argv[ i ] ); return 2; }
+				topK = atoi( argv[ ++i ] );
+			}
+			else if( !strcmp( argv[ i ], "--top-p" ) ) value = &topP;
 			else if( !strcmp( argv[ i ], "-tpi" ) ) value = &fallbackParams.temperatureInc;
 			else if( !strcmp( argv[ i ], "-lpt" ) ) value = &fallbackParams.logprobThold;
 			else if( !strcmp( argv[ i ], "-et" ) ) value = &fallbackParams.entropyThold;
@@ -667,6 +676,11 @@ int main( int argc, char** argv )
 	{
 		hr = setNoRepeatNgram( context, noRepeatNgram );
 		if( FAILED( hr ) ) { printFailure( "failed to set the no-repeat n-gram size", hr ); return 6; }
+	}
+	if( topK != 0 || topP != 1.0f )
+	{
+		hr = setSamplingFilter( context, topK, topP );
+		if( FAILED( hr ) ) { printFailure( "failed to set --top-k / --top-p", hr ); return 6; }
 	}
 	if( speechOnly )
 	{

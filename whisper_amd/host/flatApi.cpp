@@ -252,6 +252,17 @@ WHISPER_EXPORT int32_t whisperc_batch_set_no_repeat_ngram( void* runner, int32_t
 	if( !runner ) return E_POINTER;
 	return setBatchNoRepeatNgram( (iBatchRunner*)runner, n );
 }
+// Whisper::setSamplingFilter / setBatchSamplingFilter: ( 0, 1 ) turns the filter off
+WHISPER_EXPORT int32_t whisperc_set_sampling_filter( void* ctx, int32_t topK, float topP )
+{
+	if( !ctx ) return E_POINTER;
+	return setSamplingFilter( (iContext*)ctx, topK, topP );
+}
+WHISPER_EXPORT int32_t whisperc_batch_set_sampling_filter( void* runner, int32_t topK, float topP )
+{
+	if( !runner ) return E_POINTER;
+	return setBatchSamplingFilter( (iBatchRunner*)runner, topK, topP );
+}
 // Whisper::setTokenAlternatives / getTokenAlternatives: k == 0 turns the setting off; out = sTokenAlternative [cap] (may be NULL), *count = tokens x k of the last run
 WHISPER_EXPORT int32_t whisperc_set_alternatives( void* ctx, uint32_t k )
 {

@@ -64,6 +64,9 @@ namespace
 		bool timestampRules = false;
 		// -nrn N / --no-repeat-ngram N: Whisper::setBatchNoRepeatNgram on every rank's runner (0 = off)
 		int noRepeatNgram = 0;
+		// -top-k N -top-p X: Whisper::setBatchSamplingFilter on every rank's runner (0 and 1 = off); without -fallback nothing samples and they have no effect
+		int topK = 0;
+		float topP = 1.0f;
 		// -speech-only: Whisper::setBatchSpeechFilter on every rank's runner; -so-min-silence / -so-min-speech / -so-pad S (whisper-main's names) set its
 		// parameters in seconds, rounded to frames of 16 ms (0 = the library's defaults 2.0, 0.256, 0.4)
 		bool speechOnly = false;
@@ -289,6 +292,11 @@ namespace
 			hr = setBatchNoRepeatNgram( runner, a.noRepeatNgram );
 			if( FAILED( hr ) ) { fprintf( stderr, "[rank %d] setBatchNoRepeatNgram failed 0x%08x\n", rank, (unsigned)hr ); return 6; }
 		}
+		if( runner && ( a.topK != 0 || a.topP != 1.0f ) )
+		{
+			hr = setBatchSamplingFilter( runner, a.topK, a.topP );
+			if( FAILED( hr ) ) { fprintf( stderr, "[rank %d] setBatchSamplingFilter failed 0x%08x\n", rank, (unsigned)hr ); return 6; }
+		}
 		if( runner && a.speechOnly )
 		{
 			auto frames = []( float seconds ) { return (int32_t)lroundf( seconds * 16000.0f / 256.0f ); };
@@ -460,6 +468,8 @@ int main( int argc, char** argv )
 		else if( !strcmp( argv[ i ], "-sns" ) || !strcmp( argv[ i ], "--suppress-nst" ) ) a.suppressNst = true;
 		else if( !strcmp( argv[ i ], "-tsr" ) || !strcmp( argv[ i ], "--timestamp-rules" ) ) a.timestampRules = true;
 		else if( !strcmp( argv[ i ], "-nrn" ) || !strcmp( argv[ i ], "--no-repeat-ngram" ) ) a.noRepeatNgram = atoi( val() );
+		else if( !strcmp( argv[ i ], "-top-k" ) || !strcmp( argv[ i ], "--top-k" ) ) a.topK = atoi( val() );
+		else if( !strcmp( argv[ i ], "-top-p" ) || !strcmp( argv[ i ], "--top-p" ) ) a.topP = (float)atof( val() );
 		else if( !strcmp( argv[ i ], "-speech-only" ) || !strcmp( argv[ i ], "--speech-only" ) ) a.speechOnly = true;
 		else if( !strcmp( argv[ i ], "-so-min-silence" ) || !strcmp( argv[ i ], "--so-min-silence" ) ) { a.soMinSilence = (float)atof( val() ); soTuned = true; }
 		else if( !strcmp( argv[ i ], "-so-min-speech" ) || !strcmp( argv[ i ], "--so-min-speech" ) ) { a.soMinSpeech = (float)atof( val() ); soTuned = true; }

@@ -47,6 +47,13 @@ namespace Whisper
 			logError( "%s: n = %i is outside 0 .. 8", name, n );
 			return E_INVALIDARG;
 		}
+		// top-k and nucleus sampling: topK 0 (off) .. 1024 (the compute layer's NUCLEUS_MAX_K), topP in ( 0, 1 ], 1 = off
+		inline HRESULT checkSamplingFilter( const char* name, int topK, float topP )
+		{
+			if( topK >= 0 && topK <= 1024 && topP > 0.0f && topP <= 1.0f ) return S_OK;
+			logError( "%s: topK = %i is outside 0 .. 1024, or topP = %g is outside ( 0, 1 ]", name, topK, (double)topP );
+			return E_INVALIDARG;
+		}
 		// the speech filter's parameters: frames, each 0 (the default) .. 2^20 (speechSpans.h states the defaults and the bound); flags reserved
 		inline HRESULT checkSpeechFilter( const char* name, const sSpeechFilter& p )
 		{

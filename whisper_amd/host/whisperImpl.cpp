@@ -15,6 +15,7 @@
 #include "batchTimestampRules.h"
 #include "batchBoost.h"
 #include "batchNoRepeat.h"
+#include "batchNucleus.h"
 #include "batchSpeech.h"
 #include "batchCrossFp8.h"
 #include "batchCrossInt4.h"
@@ -332,6 +333,14 @@ namespace Whisper
 				CHECK( optionRules::checkNoRepeat( "setNoRepeatNgram", n ) );
 				CHECK_WH( wh_context_set_no_repeat( gpu, n ) );
 				noRepeatN = n;
+				return S_OK;
+			}
+			// Whisper::setSamplingFilter: the stream's device context holds the pair; it acts on the sampled attempts of the decoding fallback alone (beam search and
+			// greedy runs sample nothing, so nothing is refused with it on)
+			HRESULT setSamplingFilter( int topK, float topP )
+			{
+				CHECK( optionRules::checkSamplingFilter( "setSamplingFilter", topK, topP ) );
+				CHECK_WH( wh_context_set_nucleus( gpu, topK, topP ) );
 				return S_OK;
 			}
 			HRESULT setBoosted( const sBoostedPhrases* p )
@@ -1455,6 +1464,8 @@ namespace Whisper
 	static const bool g_boostInstalled = ( g_batchBoost = &wh_context_set_boost, true );
 	// ... and to the n-gram filter (batchNoRepeat.h)
 	static const bool g_noRepeatInstalled = ( g_batchNoRepeat = &wh_context_set_no_repeat, true );
+	// ... and to top-k and nucleus sampling (batchNucleus.h)
+	static const bool g_nucleusInstalled = ( g_batchNucleus = &wh_context_set_nucleus, true );
 	// ... and to the scorer of given transcripts (scoreRequest.h)
 	static const bool g_scorerInstalled = ( g_batchScorer = &wh_score_tokens, true );
 	// ... and to the speech filter of a newly admitted stream (batchSpeech.h)
@@ -1515,6 +1526,11 @@ namespace Whisper
 	{
 		return optionRules::forward<ContextImpl>( context, "setNoRepeatNgram", NOT_A_CONTEXT, "a batch runner takes setBatchNoRepeatNgram",
 			[ = ]( ContextImpl& c ) { return c.setNoRepeat( n ); } );
+	}
+	HRESULT setSamplingFilter( iContext* context, int topK, float topP )
+	{
+		return optionRules::forward<ContextImpl>( context, "setSamplingFilter", NOT_A_CONTEXT, "a batch runner takes setBatchSamplingFilter",
+			[ = ]( ContextImpl& c ) { return c.setSamplingFilter( topK, topP ); } );
 	}
 	HRESULT setSpeechFilter( iContext* context, const sSpeechFilter* params )
 	{
