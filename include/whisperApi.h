@@ -500,6 +500,29 @@ namespace Whisper
 	// One set for all streams of every later run of the runner. E_INVALIDARG as above; E_NOTIMPL for a non-empty set where the scheduler was built without the
 	// device's filter.
 	WHISPER_EXPORT HRESULT setBatchBoostedPhrases( iBatchRunner* runner, const sBoostedPhrases* phrases );
+	// Extension: constrained decoding -- the text of every window must be a prefix of a word of a language the caller gives as a deterministic automaton over
+	// BYTES (whisper.cpp's --grammar, with the grammar already compiled). In every step of the decoding loop `penalty` is subtracted on the device from the logit of
+	// every text token whose bytes the automaton cannot read from where the stream's text stands, and from the end-of-text token unless the automaton accepts
+	// there. The library supplies the vocabulary's bytes. DESIGN.md section 7 "Constrained decoding" holds the definition. Greedy runs and the sampled attempts
+	// of the decoding fallback are constrained, each window from the start state. Nobody has measured this on a real checkpoint and THE PENALTY HAS NO TUNED
+	// VALUE: 100 is whisper.cpp's default, +inf forbids. Off unless set. Free functions: the vtables are the reference's.
+	struct sDecodingConstraint
+	{
+		uint32_t states;			   // 1 .. 4096
+		uint32_t classes;			   // 1 .. 256, states * classes <= 65536
+		uint32_t start;				   // the state a window starts in
+		const uint8_t* classOf;		   // [ 256 ]: a byte's class, below `classes`
+		const int32_t* transitions;	   // [ states ][ classes ]: the next state, or -1
+		const uint8_t* accept;		   // [ states ]: non-zero where the text may end
+		float penalty;				   // > 0, +inf allowed
+	};
+	// The constraint holds for every later runFull / runStreamed of the context. nullptr = off, the state of every new context. With one held, a run with
+	// eSamplingStrategy::BeamSearch answers E_NOTIMPL; language detection, AlignTokens and scoreTokens read unconstrained passes. E_INVALIDARG, the log naming
+	// the limit, for sizes outside the limits above, a transition outside [ -1, states ), a class outside [ 0, classes ), a start outside the states, a penalty that
+	// is NaN or not positive, or a context of another library.
+	WHISPER_EXPORT HRESULT setDecodingConstraint( iContext* context, const sDecodingConstraint* constraint );
+	// One constraint for all streams of every later run of the runner. E_INVALIDARG as above; E_NOTIMPL where the scheduler was built without the device's filter.
+	WHISPER_EXPORT HRESULT setBatchDecodingConstraint( iBatchRunner* runner, const sDecodingConstraint* constraint );
 	// Extension: no-repeat n-grams, Hugging Face generation's no_repeat_ngram_size restricted to text tokens, applied to the logits on the device in every step of
 	// the decoding loop. n = 0: off, the state of every new context; 1 .. 8: a text token cannot be sampled when it would complete an n-gram that the tokens sampled
 	// in the current window, timestamps included, already hold. eot and the timestamps are never forbidden, the prompt does not count, and no history survives into

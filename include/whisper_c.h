@@ -122,6 +122,10 @@ int32_t whisperc_batch_set_suppress_tokens( void* runner, const int32_t* ids, ui
  * context and runner. whisperc_phrase_spellings: tokens = int32 [cap][16], lens = int32 [cap], *count = the rows written (1 or 2). */
 int32_t whisperc_set_boost_phrases( void* ctx, const int32_t* tokens, const int32_t* lens, uint32_t count, uint32_t nMax, float boost );
 int32_t whisperc_batch_set_boost_phrases( void* runner, const int32_t* tokens, const int32_t* lens, uint32_t count, uint32_t nMax, float boost );
+/* Constrained decoding (Whisper::setDecodingConstraint / setBatchDecodingConstraint of whisperApi.h, whose sDecodingConstraint the arguments are): a byte-level
+ * automaton and a penalty; states == 0 turns it off (the pointers may be NULL), the state of every new context and runner. */
+int32_t whisperc_set_constraint( void* ctx, uint32_t states, uint32_t classes, uint32_t start, const uint8_t* classOf, const int32_t* transitions, const uint8_t* accept, float penalty );
+int32_t whisperc_batch_set_constraint( void* runner, uint32_t states, uint32_t classes, uint32_t start, const uint8_t* classOf, const int32_t* transitions, const uint8_t* accept, float penalty );
 int32_t whisperc_phrase_spellings( void* model, const char* text, int32_t* tokens, int32_t* lens, uint32_t cap, uint32_t* count );
 /* No-repeat n-grams (Whisper::setNoRepeatNgram / setBatchNoRepeatNgram of whisperApi.h): n = 1 .. 8 = every later run forbids a text token that would complete an
  * n-gram its window has already sampled; 0 = off, the state of every new context and runner. */

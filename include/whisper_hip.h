@@ -659,6 +659,38 @@ WH_API int wh_boost_step_host( const int32_t* tables, int64_t nInts, int32_t sta
  * to follow the beam's reorder) or under WH_FLAG_PARITY_EXACT (wh_context_set_flags in turn refuses that flag while the option is on). A context that never turns
  * it on launches, allocates and captures what it always did. */
 WH_API int wh_context_set_no_repeat( wh_context* c, int n );
+/* Constrained decoding (DESIGN.md section 7 "Constrained decoding" holds the definition; tests/constraint_ref.py restates it in plain Python): the text of a window
+ * must be a prefix of a word of a language given as a deterministic automaton over BYTES. A constraint is
+ *   the automaton   nStates states, a start state, classOf[ 256 ] mapping a byte to a class below nClasses, trans[ nStates ][ nClasses ] the next state or -1,
+ *                   accept[ nStates ];
+ *   the vocabulary  token t < eot spells tokBytes[ tokOffsets[ t ] .. tokOffsets[ t + 1 ] ): the compute layer holds no vocabulary, the caller passes it;
+ *   a penalty       > 0, finite or +inf.
+ * Every sequence of the device-side loop keeps one state s, -1 = dead. walk( s, t ) feeds token t's bytes through trans from s and is -1 as soon as a transition is
+ * missing, when s is -1, or when the token has no bytes. Before the softmax of each step, in ONE launch: the state first moves over the token just fed, the previous
+ * step's sample -- a text token gives walk( s, t ), an id >= eot leaves s -- and then logits[ row ][ t ] -= penalty for every text token t with walk( s, t ) == -1,
+ * and for eot itself unless accept[ s ] holds or s is -1: a dead row can always end its window. -inf stays -inf, and x - inf is -inf. Ids above eot are never
+ * touched. The prompt step of a window sets every state to start and masks nothing (its sample is the forced timestamp); no state survives into the next window;
+ * wh_decode_greedy starts from `start` at its first step and does not count firstTokens: until that step its states hold -2, "armed", a value a state can hold
+ * besides -1 and [0, nStates) -- the next step turns it into `start` without reading the fed token. The order is vocabulary product -> suppress -> timestamp rules -> boost ->
+ * no-repeat -> constraint -> nucleus -> sampler, whatever the sampler. Unconstrained: wh_decode, wh_lang_detect, wh_score_tokens, wh_align_tokens, the beam step.
+ * The pointers are HOST memory and nTokens must equal the model's eot. NULL turns it off (the state of every new context). Limits: 1 .. 4096 states, 1 .. 256
+ * classes, nStates * nClasses <= 65536 (the table is staged in LDS as 16-bit entries), at most 65536 text tokens of at most 255 bytes each -- WH_E_INVALIDARG names
+ * the one violated, as for a trans entry outside [-1, nStates), a classOf entry outside [0, nClasses), a penalty that is NaN or not > 0, a hypothesis-group context
+ * and WH_FLAG_PARITY_EXACT (wh_context_set_flags in turn refuses that flag while a constraint is held).
+ * The call uploads the tables, builds allowed[ nStates ][ ceil( eot / 32 ) ] (bit t of line s = walk( s, t ) survives) with one launch and waits for the stream; a
+ * step then reads one line per row. The buffers are allocated by the first non-NULL call, sized for that constraint, and regrown only for a larger one; the tables,
+ * their addresses and the penalty live in device memory and the captured step graphs are keyed on "a constraint is held" only. */
+typedef struct wh_constraint
+{
+	int32_t nStates, nClasses, start, nTokens;
+	const uint8_t* classOf;		   /* [256] */
+	const int32_t* trans;		   /* [nStates][nClasses] */
+	const uint8_t* accept;		   /* [nStates] */
+	const int32_t* tokOffsets;	   /* [nTokens + 1], ascending */
+	const uint8_t* tokBytes;
+	float penalty;
+} wh_constraint;
+WH_API int wh_context_set_constraint( wh_context* c, const wh_constraint* k );
 WH_API int wh_context_set_no_speech( wh_context* c, int on );
 WH_API int wh_decode_window_no_speech( wh_context* c, float* out );
 /* Token alternatives: the k likeliest tokens at each decoded position (DESIGN.md section 7 "Token alternatives" holds the definition; tests/alternatives_ref.py
@@ -918,6 +950,29 @@ WH_API int wh_op_boost_logits( void* stream, float* logits, int rows, int nVocab
  * -1, history entries and fed ids outside the row are held inside their buffers. */
 WH_API int wh_op_no_repeat_ngram( void* stream, float* logits, int rows, int nVocab, int tokenEot, int n, const int32_t* fedDev, int reset, int32_t* historyDev,
 	int32_t* countsDev, int cap );
+/* The two kernels of wh_context_set_constraint outside a context. The tables are wh_constraint's with DEVICE pointers (the struct itself is host memory, read
+ * before the call returns); nBytes = the bytes tokBytes holds.
+ * wh_op_constraint_mask: allowedDev [nStates][ceil( nTokens / 32 )] u32, bit t % 32 of word t / 32 of line s = walk( s, t ) != -1; every word of the array is
+ * written (bits of absent tokens are 0) and nothing behind it; accept may be NULL. Workgroups of 1024 threads stage the transition table in LDS as int16.
+ * wh_op_constraint_apply: one step on logits [rows][nVocab] in place, eot = the tables' nTokens <= nVocab. statesDev: DEVICE int32 [rows], -1 = dead, -2 = armed.
+ * reset 0: statesDev[ row ] moves over fedTokensDev[ row ] (DEVICE; a text token walks its bytes, an id >= eot leaves the state, an armed state becomes start
+ * whatever the token), then penalty is subtracted from every column t < eot whose bit in the new state's line of allowedDev is 0 and from column eot unless the
+ * state accepts or is dead; every other float keeps its bits. reset 1: every state becomes start; 2: armed; neither touches the logits, fedTokensDev may be NULL.
+ * The limits of wh_context_set_constraint, or WH_E_INVALIDARG. Table entries, offsets and states read from device memory are held inside their buffers: tables that
+ * are nobody's automaton cost wrong bits, never a fault. Plain vector loads and stores, no atomics. */
+typedef struct wh_constraint_tables
+{
+	int32_t nStates, nClasses, start, nTokens;
+	const uint8_t* classOf;
+	const int32_t* trans;
+	const uint8_t* accept;
+	const int32_t* tokOffsets;
+	const uint8_t* tokBytes;
+	int64_t nBytes;
+} wh_constraint_tables;
+WH_API int wh_op_constraint_mask( void* stream, const wh_constraint_tables* tablesDev, uint32_t* allowedDev );
+WH_API int wh_op_constraint_apply( void* stream, float* logits, int rows, int nVocab, int eot, const wh_constraint_tables* tablesDev, const uint32_t* allowedDev,
+	int32_t* statesDev, const int32_t* fedTokensDev, int reset, float penalty );
 /* The language-detection kernel of wh_lang_detect on logits [rows][nVocab]: langP [rows][nLang] = the probabilities wh_op_vocab_soft_max gives at columns
  * tokenSot + 1 .. tokenSot + nLang, bit for bit, without writing the other columns; best [rows] = the index (0 .. nLang - 1) of the largest, exact ties
  * to the lower index. The row stays in registers: nVocab <= 52224; 1 <= nLang <= 1024 and the block inside the row, or WH_E_INVALIDARG. */

@@ -21,7 +21,7 @@ ALIGN_TOKENS = 0x1000      # extension: token times from the decoder's cross-att
 
 CPP_EXPORTS = ["setupLogger", "loadModel", "initMediaFoundation", "findLanguageKeyW", "findLanguageKeyA", "getSupportedLanguages", "listGPUs"]
 # extensions next to the seven names of whisper.def: one process per GPU, and K streams in lock step on one GPU
-CPP_EXTENSIONS = ["loadModelShared", "createBatchRunner", "runFullBatch", "splitAtPauses", "setAlignmentHeads"]
+CPP_EXTENSIONS = ["loadModelShared", "createBatchRunner", "runFullBatch", "splitAtPauses", "setAlignmentHeads", "setDecodingConstraint", "setBatchDecodingConstraint"]
 
 _lib = None
 
@@ -84,6 +84,8 @@ def lib():
         L.whisperc_batch_set_suppress_tokens.argtypes = [vp, vp, C.c_uint32]
         L.whisperc_set_boost_phrases.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_float]
         L.whisperc_batch_set_boost_phrases.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_float]
+        L.whisperc_set_constraint.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_float]
+        L.whisperc_batch_set_constraint.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_float]
         L.whisperc_set_no_repeat_ngram.argtypes = [vp, C.c_int32]
         L.whisperc_batch_set_no_repeat_ngram.argtypes = [vp, C.c_int32]
         L.whisperc_set_sampling_filter.argtypes = [vp, C.c_int32, C.c_float]
@@ -437,6 +439,76 @@ def _set_boost(fn, who: str, h, model: Model, phrases, boost):
     _check(fn(h, tokens.ctypes.data_as(C.c_void_p), lens.ctypes.data_as(C.c_void_p), len(lens), tokens.shape[1], float(boost)), who)
 
 
+def compile_phrases(phrases, leading_space: str = "optional", repeat: bool = False):
+    """The byte-level automaton of a phrase list, as the arrays set_constraint takes: ( class_of u8 [256], trans i32 [states][classes], accept u8 [states], start ).
+    It reads the UTF-8 bytes of one phrase and accepts at a phrase's end. leading_space: "optional" (one space may come first, as Whisper spells the first word of
+    a segment), "always" or "never". repeat: behind a complete phrase one space leads to the next phrase -- sequences of commands or digits. Built as a trie with
+    those extra edges and made deterministic by the subset construction; a byte no phrase uses falls into one class without transitions. Callers with a regex
+    engine of their own pass a DFA to set_constraint directly. host/phraseAutomaton.h builds the same automaton in C++ for the command-line tools (--allow-phrases):
+    THE TWO MUST AGREE, state for state; tests/test_gpu_constraint_library.py compares them through the transcript."""
+    if leading_space not in ("optional", "always", "never"):
+        raise ValueError("compile_phrases: leading_space is 'optional', 'always' or 'never'")
+    kids, ends = [{}], set()                                                     # the trie: node 0 is its root
+    for p in phrases:
+        data, n = (p.encode("utf-8") if isinstance(p, str) else bytes(p)), 0
+        if not data:
+            raise ValueError("compile_phrases: an empty phrase")
+        for b in data:
+            if b not in kids[n]:
+                kids[n][b] = len(kids)
+                kids.append({})
+            n = kids[n][b]
+        ends.add(n)
+    if len(kids) == 1:
+        raise ValueError("compile_phrases: no phrases")
+    START = -1                                                                   # in front of the optional space; the subsets below are frozensets of nodes
+
+    def step(subset, b):
+        out = set()
+        for n in subset:
+            if n == START:
+                if b == 32 and leading_space != "never":
+                    out.add(0)
+                if leading_space != "always" and b in kids[0]:
+                    out.add(kids[0][b])
+                continue
+            if b in kids[n]:
+                out.add(kids[n][b])
+            if repeat and b == 32 and n in ends:
+                out.add(0)
+        return frozenset(out)
+
+    used = sorted({b for k in kids for b in k} | {32})
+    class_of = np.full(256, len(used), np.uint8)                                 # the last class: every other byte, no transitions
+    class_of[used] = np.arange(len(used))
+    first = frozenset([START])
+    index, order, rows = {first: 0}, [first], []
+    for subset in order:                                                         # grows while it is walked
+        row = [-1] * (len(used) + 1)
+        for c, b in enumerate(used):
+            nxt = step(subset, b)
+            if nxt:
+                if nxt not in index:
+                    index[nxt] = len(order)
+                    order.append(nxt)
+                row[c] = index[nxt]
+        rows.append(row)
+    accept = np.array([1 if any(n in ends for n in s) else 0 for s in order], np.uint8)
+    return class_of, np.array(rows, np.int32), accept, 0
+
+
+def _set_constraint(fn, who: str, h, class_of, trans, accept, start, penalty):
+    if class_of is None:
+        _check(fn(h, 0, 0, 0, None, None, None, 0.0), who)
+        return
+    class_of, accept = np.ascontiguousarray(class_of, np.uint8).reshape(-1), np.ascontiguousarray(accept, np.uint8).reshape(-1)
+    trans = np.ascontiguousarray(trans, np.int32)
+    if trans.ndim != 2 or len(class_of) != 256 or len(accept) != trans.shape[0]:
+        raise ValueError(who + ": class_of holds 256 classes, trans is [states][classes] and accept [states]")
+    _check(fn(h, trans.shape[0], trans.shape[1], int(start), class_of.ctypes.data_as(C.c_void_p), trans.ctypes.data_as(C.c_void_p), accept.ctypes.data_as(C.c_void_p),
+              float(penalty)), who)
+
+
 def _suppress_ids(model: Model, ids) -> np.ndarray:
     """ids | "non_speech" | None -> int32 array"""
     if ids is None:
@@ -692,6 +764,13 @@ class Context:
         real checkpoint. Beam search with a set held is E_NOTIMPL."""
         _set_boost(lib().whisperc_set_boost_phrases, "setBoostedPhrases", self.h, self.model, phrases, boost)
 
+    def set_constraint(self, class_of=None, trans=None, accept=None, start: int = 0, penalty: float = 100.0):
+        """Whisper::setDecodingConstraint: in every later run of this context the text of each window must be a prefix the byte-level automaton ( class_of [256],
+        trans [states][classes] with -1 = none, accept [states], start ) reads: `penalty` is subtracted from the logit of every text token it cannot read, and
+        from end-of-text unless it accepts. set_constraint(*compile_phrases([...])) allows a phrase list. No arguments turn it off, the state of a new context.
+        Nobody has measured this on a real checkpoint and the penalty has no tuned value (100 is whisper.cpp's; inf forbids). Beam search is then E_NOTIMPL."""
+        _set_constraint(lib().whisperc_set_constraint, "setDecodingConstraint", self.h, class_of, trans, accept, start, penalty)
+
     def set_speech_filter(self, min_silence: Optional[float] = 2.0, min_speech: float = 0.256, pad: float = 0.4):
         """Whisper::setSpeechFilter (faster-whisper's vad_filter, whisper.cpp's --vad): every later run_full / run_streamed of this context finds the speech on the
         device (speech_spans' rules, the same arguments in seconds), transcribes only that and reports every time -- segments, tokens under ALIGN_TOKENS -- on
@@ -847,6 +926,10 @@ class BatchRunner:
     def set_boost_phrases(self, phrases=None, boost: Optional[float] = None):
         """Whisper::setBatchBoostedPhrases: Context.set_boost_phrases for every stream of this runner's later runs (one set and one boost for all of them)."""
         _set_boost(lib().whisperc_batch_set_boost_phrases, "setBatchBoostedPhrases", self.h, self.model, phrases, boost)
+
+    def set_constraint(self, class_of=None, trans=None, accept=None, start: int = 0, penalty: float = 100.0):
+        """Whisper::setBatchDecodingConstraint: Context.set_constraint for every stream of this runner's later runs (one constraint for all of them)."""
+        _set_constraint(lib().whisperc_batch_set_constraint, "setBatchDecodingConstraint", self.h, class_of, trans, accept, start, penalty)
 
     def set_speech_filter(self, min_silence: Optional[float] = 2.0, min_speech: float = 0.256, pad: float = 0.4):
         """Whisper::setBatchSpeechFilter: Context.set_speech_filter for every stream of this runner's later runs. Each stream is filtered when it is admitted

@@ -70,6 +70,7 @@ EXPORTS = [
     "wh_op_quantize_rows_i8", "wh_op_layer_norm_i8", "wh_op_gemm_encoder_i8",
     "wh_context_set_alternatives", "wh_decode_window_alternatives", "wh_op_top_logprobs",
     "wh_context_set_nucleus", "wh_op_nucleus_logits",
+    "wh_context_set_constraint", "wh_op_constraint_mask", "wh_op_constraint_apply",
 ]
 
 
@@ -103,6 +104,29 @@ def boost_step_host(tables, state: int, fed: int, reset: int, row, token_eot: in
     new = C.c_int32(0)
     check(lib().wh_boost_step_host(tables.ctypes.data_as(C.c_void_p), len(tables), state, fed, reset, out.ctypes.data_as(C.c_void_p), len(out), token_eot, C.byref(new)))
     return new.value, out
+
+
+class ConstraintC(C.Structure):
+    """wh_constraint (HOST pointers) and, with nBytes behind it, wh_constraint_tables (DEVICE pointers)."""
+    _fields_ = [("nStates", C.c_int32), ("nClasses", C.c_int32), ("start", C.c_int32), ("nTokens", C.c_int32), ("classOf", C.c_void_p), ("trans", C.c_void_p),
+                ("accept", C.c_void_p), ("tokOffsets", C.c_void_p), ("tokBytes", C.c_void_p), ("penalty", C.c_float)]
+
+
+class ConstraintTablesC(C.Structure):
+    _fields_ = ConstraintC._fields_[:-1] + [("nBytes", C.c_int64)]
+
+
+def pack_constraint(class_of, trans, accept, start, tok_offsets, tok_bytes):
+    """The arrays of a constraint in the types and shapes wh_constraint takes: ( classOf u8 [256], trans i32 [nStates][nClasses], accept u8 [nStates], start,
+    tokOffsets i32 [nTokens + 1], tokBytes u8 ). tok_bytes may be a bytes object."""
+    trans = np.ascontiguousarray(trans, np.int32)
+    assert trans.ndim == 2
+    tok_bytes = np.frombuffer(bytes(tok_bytes), np.uint8) if isinstance(tok_bytes, (bytes, bytearray)) else np.ascontiguousarray(tok_bytes, np.uint8)
+    tok_bytes = np.concatenate([tok_bytes, np.zeros(1, np.uint8)])            # never an empty array: its pointer is passed
+    class_of = np.ascontiguousarray(class_of, np.uint8).reshape(-1)
+    accept = np.ascontiguousarray(accept, np.uint8).reshape(-1)
+    assert len(class_of) == 256 and len(accept) == trans.shape[0]
+    return class_of, trans, accept, int(start), np.ascontiguousarray(tok_offsets, np.int32).reshape(-1), tok_bytes
 
 
 class HParamsC(C.Structure):
@@ -328,6 +352,9 @@ def lib():
         L.wh_op_top_logprobs.argtypes = [vp, vp, i64, i32, i32, i32, vp]
         L.wh_context_set_nucleus.argtypes = [vp, i32, C.c_float]
         L.wh_op_nucleus_logits.argtypes = [vp, vp, i32, i64, i32, i32, C.c_float, vp]
+        L.wh_context_set_constraint.argtypes = [vp, C.POINTER(ConstraintC)]
+        L.wh_op_constraint_mask.argtypes = [vp, C.POINTER(ConstraintTablesC), vp]
+        L.wh_op_constraint_apply.argtypes = [vp, vp, i32, i32, i32, C.POINTER(ConstraintTablesC), vp, vp, vp, i32, C.c_float]
         _lib = L
     return _lib
 
@@ -553,6 +580,18 @@ class HipContext:
         """Top-k and nucleus sampling for the rows that sample (set_sampling, set_sampling_rows): the top_k likeliest tokens stay (0 = all), of those the shortest
         prefix whose probability at the row's temperature reaches top_p (1 = all). (0, 1.0) = off, the default; there is no recommended pair."""
         check(lib().wh_context_set_nucleus(self.handle, int(top_k), float(top_p)))
+
+    def set_constraint(self, class_of=None, trans=None, accept=None, start: int = 0, tok_offsets=None, tok_bytes=None, penalty: float = 100.0):
+        """Constrained decoding: in every later step of the device-side loop `penalty` (> 0, inf allowed) is subtracted from the logit of every text token whose
+        bytes the byte-level automaton ( class_of [256], trans [nStates][nClasses] with -1 = none, accept [nStates], start ) cannot read from the row's state, and
+        from eot's unless the state accepts. tok_offsets [eot + 1] / tok_bytes: the vocabulary's byte strings. No arguments (or class_of None) turns it off."""
+        if class_of is None:
+            check(lib().wh_context_set_constraint(self.handle, None))
+            return
+        class_of, trans, accept, start, tok_offsets, tok_bytes = pack_constraint(class_of, trans, accept, start, tok_offsets, tok_bytes)
+        k = ConstraintC(trans.shape[0], trans.shape[1], start, len(tok_offsets) - 1, class_of.ctypes.data, trans.ctypes.data, accept.ctypes.data,
+                        tok_offsets.ctypes.data, tok_bytes.ctypes.data, float(penalty))
+        check(lib().wh_context_set_constraint(self.handle, C.byref(k)))
 
     def set_alternatives(self, k: Optional[int]):
         """k = 1 .. 8: every sample of the device-side loop also records the k likeliest tokens of the row its sampler read, with their log-probabilities

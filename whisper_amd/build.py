@@ -25,7 +25,7 @@ CLI_BIN = os.path.join(LIB_DIR, "whisper-main")
 RUNTIME_SOURCES = ["options.hip", "model.hip", "comm.hip", "context.hip", "encode.hip", "exact_graphs.hip", "step_graph.hip", "decode.hip", "beam.hip", "ops_debug.hip"]
 # resample.hip and vad.hip keep their kernels next to the entry points that own their tables, capture.hip next to the wh_capture it fills, dequant.hip next to wh_dequantize, align.hip next to wh_align_tokens, speech.hip next to wh_speech_pack, filters.hip next to the owner of the decode-step logit filters; boost.hip is the host half of phrase boosting: kernel units that do include runtime.h
 HIP_SOURCES = ["gemm_persistent.hip", "gemm_decode.hip", "gemm_tiled.hip", "attn_dec.hip", "kv8.hip", "kv4.hip", "gemm_i8.hip", "quant_i8.hip", "decode1.hip", "attn_enc.hip", "gemm.hip", "elementwise.hip", "sample.hip", "mel.hip", "exact.hip", "resample.hip", "vad.hip", "capture.hip", "dequant.hip",
-               "align.hip", "boost.hip", "speech.hip", "filters.hip", "alternatives.hip", "nucleus.hip"] + RUNTIME_SOURCES
+               "align.hip", "boost.hip", "speech.hip", "filters.hip", "alternatives.hip", "nucleus.hip", "constraint.hip"] + RUNTIME_SOURCES
 RUNTIME_H_USERS = RUNTIME_SOURCES + ["resample.hip", "vad.hip", "capture.hip", "dequant.hip", "align.hip", "boost.hip", "speech.hip", "filters.hip", "alternatives.hip"]
 # speech.hip applies the host's decision loop and span rules between its two kernels: the two header-only files that state them
 EXTRA_DEPS = {"speech.hip": [os.path.join(HOST, "vad.h"), os.path.join(HOST, "speechSpans.h"), os.path.join(ROOT, "include", "whisperApi.h")]}
@@ -103,7 +103,7 @@ def build_cli(force: bool = False):
     if not os.path.isdir(cli):
         return None
     srcs = sorted(os.path.join(cli, f) for f in os.listdir(cli) if f.endswith(".cpp"))
-    hdrs = [os.path.join(cli, f) for f in os.listdir(cli) if f.endswith(".h")] + [os.path.join(ROOT, "include", "whisperApi.h")]
+    hdrs = [os.path.join(cli, f) for f in os.listdir(cli) if f.endswith(".h")] + [os.path.join(ROOT, "include", "whisperApi.h"), os.path.join(HOST, "phraseAutomaton.h")]
     if force or _newer(CLI_BIN, srcs + hdrs + [HOST_LIB]):
         _run(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "include"), "-I" + cli, "-o", CLI_BIN] + srcs +
              ["-L" + LIB_DIR, "-lWhisper", "-Wl,-rpath,$ORIGIN"])
@@ -118,7 +118,7 @@ def build_mgpu(force: bool = False):
     src = os.path.join(HOST, "mgpu", "whisperMgpu.cpp")
     if not os.path.exists(src):
         return None
-    hdrs = [os.path.join(ROOT, "include", "whisperApi.h"), os.path.join(ROOT, "include", "whisper_hip.h"), os.path.join(HOST, "cli", "phraseFile.h")]
+    hdrs = [os.path.join(ROOT, "include", "whisperApi.h"), os.path.join(ROOT, "include", "whisper_hip.h"), os.path.join(HOST, "cli", "phraseFile.h"), os.path.join(HOST, "phraseAutomaton.h")]
     if force or _newer(MGPU_BIN, [src, HOST_LIB, HIP_LIB] + hdrs):
         _run(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "include"), "-o", MGPU_BIN, src,
               "-L" + LIB_DIR, "-lWhisper", "-lwhisper_hip", "-Wl,-rpath,$ORIGIN", "-lpthread"])

@@ -2,7 +2,8 @@
 // n-grams. Kernels next to the entry points that own their buffers, like align.hip, resample.hip and speech.hip; boost.hip is the host half of phrase boosting.
 // All four write c->logits in place between the vocabulary product and the sampler. This unit alone names a member of wh_context::filters; the other units call
 // the functions of runtime.h defined below the kernels. A filter added here touches this file, the struct and its setter's declaration -- no other unit.
-// The fifth, top-k and nucleus sampling, has its kernel in a unit of its own (nucleus.hip); its launch and its owner are here like the others'.
+// The fifth, top-k and nucleus sampling, has its kernel in a unit of its own (nucleus.hip); its launch and its owner are here like the others'. So has the
+// sixth, constrained decoding (constraint.hip).
 #include "runtime.h"
 #include <algorithm>
 
@@ -290,6 +291,11 @@ int wh::filterLoopRows( wh_context* c, int batch, eFilterPhase phase )
 	if( f.ngramN )
 		WH_CHECK( profiled( c, KC_SAMPLE, 0.0, 4.0 * batch * hp.n_text_ctx,
 			[ & ]() { return launchNoRepeat( c->logits, batch, hp.n_vocab, eot, f.ngramN, c->tokensDev, reset, f.ngramHistory, f.ngramCounts, hp.n_text_ctx, c->stream ); } ) );
+	// Constrained decoding: behind the other four, so that its state moves over a token they let through, and in front of the nucleus filter, which then ranks
+	// the penalised row. The kernel resets (FILTER_WINDOW: `start`, nothing masked) and arms (FILTER_ARM) its states itself: `start` is device memory's.
+	if( f.constraintOn )
+		WH_CHECK( profiled( c, KC_SAMPLE, 0.0, 8.0 * batch * hp.n_vocab,
+			[ & ]() { return launchConstraintApply( c->logits, batch, hp.n_vocab, eot, f.constraintHeader, ConstraintTables{}, c->tokensDev, reset, f.constraintStates, c->stream ); } ) );
 	// Top-k and nucleus sampling: LAST, so that it ranks the row the sampler reads, and on loop steps only -- the prompt step's sample is a forced timestamp and the
 	// no-speech gather reads its row. Only where a row samples: under wh_context_set_sampling every row at the context's factor, under wh_context_set_sampling_rows
 	// each row at its record's, a greedy row (sampled == 0) neither read nor written. A greedy context launches nothing.
@@ -312,13 +318,16 @@ int wh::filterLoopRows( wh_context* c, int batch, eFilterPhase phase )
 //   STEP_KEY_BOOST          a set of boosted phrases is held: one more node in front of the sampler, the same for every set and boost
 //   STEP_KEY_NO_REPEAT * n  no-repeat n-grams are on, n = 1 .. 8 in bits 27-30: one more node there, and n is its kernel's argument, so no graph serves another n
 //   STEP_KEY_NUCLEUS        top-k / nucleus sampling is on AND the step samples (a temperature, or per-row records): one more node there, the same for every k and p
-// The last four are the greedy loop's alone: a beam step has no sampler in front of which they would run, and their bits stay clear in its key.
+//   STEP_KEY_CONSTRAINT     a constraint is held: one more node there, the same for every automaton, vocabulary and penalty (bit 32: the key's low word was full)
+// The last five are the greedy loop's alone: a beam step has no sampler in front of which they would run, and their bits stay clear in its key.
 static constexpr uint32_t STEP_KEY_SUPPRESS = 0x80000u, STEP_KEY_TS_RULES = 0x100000u, STEP_KEY_BOOST = 0x4000000u, STEP_KEY_NO_REPEAT = 0x8000000u, STEP_KEY_NUCLEUS = 0x80000000u;
+static constexpr uint64_t STEP_KEY_CONSTRAINT = 1ull << 32;
 uint32_t wh::filterGraphKey( const wh_context* c ) { return c->filters.suppressHeld > 0 ? STEP_KEY_SUPPRESS : 0u; }
-uint32_t wh::filterLoopKey( const wh_context* c )
+uint64_t wh::filterLoopKey( const wh_context* c )
 {
 	const LogitFilters& f = c->filters;
-	return ( f.rulesOn ? STEP_KEY_TS_RULES : 0u ) | ( f.phrasesOn ? STEP_KEY_BOOST : 0u ) | STEP_KEY_NO_REPEAT * (uint32_t)f.ngramN | ( nucleusLaunches( c ) ? STEP_KEY_NUCLEUS : 0u );
+	return ( f.rulesOn ? STEP_KEY_TS_RULES : 0u ) | ( f.phrasesOn ? STEP_KEY_BOOST : 0u ) | STEP_KEY_NO_REPEAT * (uint32_t)f.ngramN | ( nucleusLaunches( c ) ? STEP_KEY_NUCLEUS : 0u ) |
+		( f.constraintOn ? STEP_KEY_CONSTRAINT : 0ull );
 }
 
 // Everything in the filters' device memory that a step of the loop mutates, for `batch` rows: the ONE list of which buffers there are and how big each is,
@@ -331,6 +340,7 @@ template<class F> static int eachRowBuffer( const wh_context* c, int batch, F&& 
 	if( s.phrasesOn ) WH_CHECK( f( s.phraseStates, sizeof( int32_t ) * batch ) );
 	if( s.ngramN ) WH_CHECK( f( s.ngramHistory, sizeof( int32_t ) * batch * c->m->hp.n_text_ctx ) );
 	if( s.ngramN ) WH_CHECK( f( s.ngramCounts, sizeof( int32_t ) * batch ) );
+	if( s.constraintOn ) WH_CHECK( f( s.constraintStates, sizeof( int32_t ) * batch ) );
 	return 0;
 }
 // The filters' share of LoopState (obtainStepGraph's WARM_PRESERVE; the stream is idle and no setter runs in between): those buffers, one behind the other
@@ -359,7 +369,8 @@ int wh::filtersAllowFlags( const wh_context* c, uint32_t flags )
 {
 	const LogitFilters& f = c->filters;
 	const char* const held = f.suppressHeld > 0 ? "wh_context_set_suppress holds a set" : f.phrasesOn ? "wh_context_set_boost holds a set" :
-		f.ngramN ? "wh_context_set_no_repeat is on" : f.rulesOn ? "wh_context_set_timestamp_rules is on" : f.nucleusOn ? "wh_context_set_nucleus is on" : nullptr;
+		f.ngramN ? "wh_context_set_no_repeat is on" : f.rulesOn ? "wh_context_set_timestamp_rules is on" : f.nucleusOn ? "wh_context_set_nucleus is on" :
+		f.constraintOn ? "wh_context_set_constraint holds a constraint" : nullptr;
 	return ( flags & WH_FLAG_PARITY_EXACT ) && held ? refuse( std::string( "context_set_flags: WH_FLAG_PARITY_EXACT is not available while " ) + held ) : 0;
 }
 // a filter with a state per row changes its switch behind the stream -- a chunk queued earlier has run under the mode it was enqueued in: the off path's wait
@@ -455,5 +466,77 @@ extern "C" int wh_context_set_nucleus( wh_context* c, int topK, float topP )
 	WH_HIP( hipMemcpyAsync( f.nucleusParams, &p, sizeof( p ), hipMemcpyHostToDevice, c->stream ) );
 	WH_HIP( hipStreamSynchronize( c->stream ) );	 // `p` is on this stack
 	f.nucleusOn = true;
+	return 0;
+}
+
+// Constrained decoding. The tables go to device memory behind what the stream holds, the mask is built there by one launch, and the header
+// the captured steps read is written last. The buffers are sized for this constraint and regrown only for a larger one: a live graph holds the header's address
+// and the states', which never move, and reads the other addresses from the header.
+static int checkConstraint( const wh_constraint* k, int eot )
+{
+	const std::string who = "context_set_constraint: ";
+	if( !k->classOf || !k->trans || !k->accept || !k->tokOffsets || !k->tokBytes ) return refuse( who + "a null table" );
+	if( k->nStates < 1 || k->nStates > CON_MAX_STATES ) return refuse( who + std::to_string( k->nStates ) + " states, a constraint has 1 .. 4096" );
+	if( k->nClasses < 1 || k->nClasses > CON_MAX_CLASSES ) return refuse( who + std::to_string( k->nClasses ) + " byte classes, a constraint has 1 .. 256" );
+	if( (int64_t)k->nStates * k->nClasses > CON_MAX_ENTRIES ) return refuse( who + "nStates * nClasses above 65536, the transition table of one constraint" );
+	if( k->start < 0 || k->start >= k->nStates ) return refuse( who + "the start state is outside [0, nStates)" );
+	if( eot > CON_MAX_VOCAB ) return refuse( who + "a vocabulary of more than 65536 text tokens" );
+	if( k->nTokens != eot ) return refuse( who + "nTokens is " + std::to_string( k->nTokens ) + ", the model's eot is " + std::to_string( eot ) );
+	if( !( k->penalty > 0.0f ) ) return refuse( who + "the penalty must be greater than 0 (+inf is allowed, NaN is not)" );
+	for( int i = 0; i < 256; i++ )
+		if( k->classOf[ i ] >= k->nClasses ) return refuse( who + "classOf[ " + std::to_string( i ) + " ] is outside [0, nClasses)" );
+	for( int64_t i = 0; i < (int64_t)k->nStates * k->nClasses; i++ )
+		if( k->trans[ i ] < -1 || k->trans[ i ] >= k->nStates ) return refuse( who + "trans entry " + std::to_string( i ) + " is outside [-1, nStates)" );
+	if( k->tokOffsets[ 0 ] < 0 ) return refuse( who + "tokOffsets[ 0 ] is negative" );
+	for( int t = 0; t < eot; t++ )
+	{
+		const int64_t len = (int64_t)k->tokOffsets[ t + 1 ] - k->tokOffsets[ t ];
+		if( len < 0 || len > CON_MAX_TOKEN_BYTES ) return refuse( who + "token " + std::to_string( t ) + " has " + std::to_string( len ) + " bytes, a token has 0 .. 255" );
+	}
+	return 0;
+}
+
+extern "C" int wh_context_set_constraint( wh_context* c, const wh_constraint* k )
+{
+	if( !c ) return refuse( "context_set_constraint: null context" );
+	LogitFilters& f = c->filters;
+	if( !k ) { if( f.constraintOn ) WH_CHECK( waitForStream( c ) ); f.constraintOn = false; return 0; }
+	const int eot = tokenEot( c );
+	WH_CHECK( checkConstraint( k, eot ) );
+	WH_CHECK( mayTurnOn( c, "context_set_constraint", "the states" ) );
+	WH_BIND( c->m );
+	// the blob: every table at a multiple of 16 bytes
+	const auto pad = []( size_t n ) { return ( n + 15 ) & ~(size_t)15; };
+	const size_t entries = (size_t)k->nStates * k->nClasses, nBytes = (size_t)k->tokOffsets[ eot ], base = (size_t)k->tokOffsets[ 0 ];
+	const size_t atAccept = 256, atTrans = atAccept + pad( (size_t)k->nStates ), atOffsets = atTrans + pad( entries * 4 ), atBytes = atOffsets + pad( ( (size_t)eot + 1 ) * 4 );
+	const size_t blobBytes = atBytes + pad( nBytes - base + 1 );
+	const int nWords = ( eot + 31 ) / 32;
+	std::vector<uint8_t> up( blobBytes, 0 );
+	memcpy( up.data(), k->classOf, 256 );
+	for( int s = 0; s < k->nStates; s++ ) up[ atAccept + s ] = k->accept[ s ] ? 1 : 0;
+	memcpy( up.data() + atTrans, k->trans, entries * 4 );
+	for( int t = 0; t <= eot; t++ ) ( (int32_t*)( up.data() + atOffsets ) )[ t ] = k->tokOffsets[ t ] - (int32_t)base;
+	memcpy( up.data() + atBytes, k->tokBytes + base, nBytes - base );
+	WH_HIP( hipStreamSynchronize( c->stream ) );	 // no step may run between a regrown buffer and the header that names it
+	f.constraintOn = false;							 // ... and a call that fails below leaves the filter off, not on over a header that names a released buffer
+	if( !f.constraintHeader ) WH_CHECK( c->alloc( f.constraintHeader, 1, wh_context::MUST_BE_ZERO, "constraintHeader" ) );
+	if( !f.constraintStates ) WH_CHECK( c->alloc( f.constraintStates, (int64_t)c->maxSeq, wh_context::MUST_BE_ZERO, "constraintStates" ) );
+	WH_CHECK( c->grow( f.constraintBlob, (int64_t)blobBytes, wh_context::MUST_BE_ZERO, "constraintTables" ) );
+	WH_CHECK( c->grow( f.constraintAllowed, (int64_t)k->nStates * nWords, wh_context::MUST_BE_ZERO, "constraintAllowed" ) );
+	ConstraintTables t = {};
+	t.classOf = f.constraintBlob;
+	t.accept = f.constraintBlob + atAccept;
+	t.trans = (const int*)( f.constraintBlob + atTrans );
+	t.tokOffsets = (const int*)( f.constraintBlob + atOffsets );
+	t.tokBytes = f.constraintBlob + atBytes;
+	t.allowed = f.constraintAllowed;
+	t.nBytes = (long long)( nBytes - base );
+	t.nStates = k->nStates; t.nClasses = k->nClasses; t.start = k->start; t.nWords = nWords;
+	t.penalty = k->penalty;
+	WH_HIP( hipMemcpyAsync( f.constraintBlob, up.data(), blobBytes, hipMemcpyHostToDevice, c->stream ) );
+	WH_CHECK( launchConstraintMask( t, eot, f.constraintAllowed, c->stream ) );
+	WH_HIP( hipMemcpyAsync( f.constraintHeader, &t, sizeof( t ), hipMemcpyHostToDevice, c->stream ) );
+	WH_HIP( hipStreamSynchronize( c->stream ) );	 // `up` and `t` are this call's
+	f.constraintOn = true;
 	return 0;
 }

@@ -578,6 +578,34 @@ namespace wh
 	constexpr int NUCLEUS_MAX_K = 1024, NUCLEUS_MAX_VOCAB = 53248;
 	int launchNucleusLogits( float* logits, long long rowStride, int rows, int nVocab, const NucleusParams* prmDev, int topK, float topP, const float* invTDev, int invTStride,
 		const unsigned* onDev, int onStride, hipStream_t stream );
+	// Constrained decoding (constraint.hip; wh_context_set_constraint; DESIGN.md section 7 "Constrained decoding"): a DFA over bytes, the vocabulary's byte strings
+	// and, made from the two by launchConstraintMask, one line of bits per state. All pointers are DEVICE memory. trans [nStates][nClasses] int32, an entry outside
+	// [0, nStates) = no transition; tokOffsets [eot + 1] into tokBytes [nBytes]; allowed [nStates][nWords], nWords = ceil( eot / 32 ), bit t of line s = walk( s, t )
+	// survives. A captured step reads this struct from device memory, so another constraint -- other tables, at other addresses -- replays the same graph.
+	struct ConstraintTables
+	{
+		const unsigned char* classOf;
+		const int* trans;
+		const unsigned char* accept;
+		const int* tokOffsets;
+		const unsigned char* tokBytes;
+		const unsigned* allowed;
+		long long nBytes;
+		int nStates, nClasses, start, nWords;
+		float penalty;
+		int reserved;
+	};
+	constexpr int CON_MAX_STATES = 4096, CON_MAX_CLASSES = 256, CON_MAX_ENTRIES = 65536, CON_MAX_VOCAB = 65536, CON_MAX_TOKEN_BYTES = 255;
+	constexpr int CON_STATE_ARMED = -2;	  // a row's state before wh_decode_greedy's first step: the fed token is no sample, the step starts from `start`
+	// allowed[ s ][ w ] for every state and word from the other tables of `t` (t.allowed is where they go; t.penalty and t.start are not read). Every word of
+	// [nStates][nWords] is written, absent tokens as 0, and nothing else. eot 1 .. CON_MAX_VOCAB and the limits above are the caller's to check.
+	int launchConstraintMask( const ConstraintTables& t, int eot, unsigned* allowed, hipStream_t stream );
+	// One step of the filter on logits [rows][nVocab], in place. The tables are *tablesDev (device) when it is non-null, else `t`. states [rows] (device): -1 = dead.
+	// reset 0: states[ row ] moves over fed[ row ] (device; a text token walks its bytes, an id >= eot leaves the state, an armed state becomes `start` and ignores
+	// the token), then penalty is subtracted from every text column whose bit in the new state's line is 0, and from column eot unless the state accepts or is dead.
+	// reset 1: every state becomes `start`; 2: armed; neither touches the logits. Every index read from device memory is held inside its buffer.
+	int launchConstraintApply( float* logits, int rows, int nVocab, int eot, const ConstraintTables* tablesDev, const ConstraintTables& t, const int* fed, int reset,
+		int* states, hipStream_t stream );
 
 	// ---------------------------------------------------------------------------------------------------------------
 	// mel spectrogram

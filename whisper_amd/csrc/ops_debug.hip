@@ -698,6 +698,46 @@ int wh_op_nucleus_logits( void* stream, float* logitsDev, int rows, int64_t rowS
 	return launchNucleusLogits( logitsDev, rowStride, rows, nVocab, nullptr, topK, topP, invTDev, 1, nullptr, 0, (hipStream_t)stream );
 }
 
+// the device tables of wh_op_constraint_mask / _apply as the kernels take them; 0 = refused, with the error set
+static bool constraintTablesOf( const wh_constraint_tables* k, const char* who, bool needAccept, ConstraintTables& t )
+{
+	if( !k || !k->classOf || !k->trans || ( needAccept && !k->accept ) || !k->tokOffsets || !k->tokBytes || k->nStates < 1 || k->nStates > CON_MAX_STATES || k->nClasses < 1 ||
+		k->nClasses > CON_MAX_CLASSES || (int64_t)k->nStates * k->nClasses > CON_MAX_ENTRIES || k->start < 0 || k->start >= k->nStates || k->nTokens < 1 ||
+		k->nTokens > CON_MAX_VOCAB || k->nBytes < 0 )
+	{
+		setError( ( std::string( who ) + ": null tables, nStates outside 1 .. 4096, nClasses outside 1 .. 256, nStates * nClasses above 65536, a start outside the states, nTokens outside 1 .. 65536 or negative nBytes" ).c_str() );
+		return false;
+	}
+	t = ConstraintTables{};
+	t.classOf = k->classOf; t.trans = k->trans; t.accept = k->accept; t.tokOffsets = k->tokOffsets; t.tokBytes = k->tokBytes;
+	t.nBytes = k->nBytes;
+	t.nStates = k->nStates; t.nClasses = k->nClasses; t.start = k->start; t.nWords = ( k->nTokens + 31 ) / 32;
+	return true;
+}
+
+int wh_op_constraint_mask( void* stream, const wh_constraint_tables* tablesDev, uint32_t* allowedDev )
+{
+	ConstraintTables t;
+	if( !constraintTablesOf( tablesDev, "constraint_mask", false, t ) ) return WH_E_INVALIDARG;
+	if( !allowedDev ) { setError( "constraint_mask: null output" ); return WH_E_INVALIDARG; }
+	return launchConstraintMask( t, tablesDev->nTokens, allowedDev, (hipStream_t)stream );
+}
+
+int wh_op_constraint_apply( void* stream, float* logits, int rows, int nVocab, int eot, const wh_constraint_tables* tablesDev, const uint32_t* allowedDev, int32_t* statesDev,
+	const int32_t* fedTokensDev, int reset, float penalty )
+{
+	ConstraintTables t;
+	if( !constraintTablesOf( tablesDev, "constraint_apply", true, t ) ) return WH_E_INVALIDARG;
+	if( !logits || !allowedDev || !statesDev || ( !reset && !fedTokensDev ) || rows < 1 || nVocab < 1 || eot != tablesDev->nTokens || eot > nVocab || reset < 0 || reset > 2 || !( penalty > 0.0f ) )
+	{
+		setError( "constraint_apply: null pointer, empty shape, an eot that is not the tables' nTokens or lies outside the row, a reset outside 0 .. 2 or a penalty that is not > 0" );
+		return WH_E_INVALIDARG;
+	}
+	t.allowed = allowedDev;
+	t.penalty = penalty;
+	return launchConstraintApply( logits, rows, nVocab, eot, nullptr, t, fedTokensDev, reset, statesDev, (hipStream_t)stream );
+}
+
 int wh_op_lang_probs( void* stream, const float* logits, int rows, int nVocab, int tokenSot, int nLang, float* langP, int32_t* best )
 {
 	if( !logits || !langP || !best || rows < 1 || nVocab < 1 || nVocab > 52224 || nLang < 1 || nLang > 1024 || tokenSot < 0 || (int64_t)tokenSot + 1 + nLang > nVocab )

@@ -191,6 +191,14 @@ struct LogitFilters
 	// wh_context_set_nucleus: nucleusOn = top_k above 0 or top_p below 1; nucleusParams: the two values in device memory (one captured step serves every pair)
 	bool nucleusOn = false;
 	wh::NucleusParams* nucleusParams = nullptr;
+	// wh_context_set_constraint: constraintHeader = the ONE ConstraintTables a captured step reads (allocated once; it names the other buffers, so they may be
+	// regrown for a larger constraint under a live graph); constraintBlob = classOf, accept, trans, tokOffsets, tokBytes behind one another; constraintAllowed
+	// [nStates][nWords]; constraintStates [maxSeq]
+	bool constraintOn = false;
+	wh::ConstraintTables* constraintHeader = nullptr;
+	uint8_t* constraintBlob = nullptr;
+	uint32_t* constraintAllowed = nullptr;
+	int* constraintStates = nullptr;
 };
 
 struct wh_context
@@ -302,10 +310,10 @@ struct wh_context
 	TokenData* greedyOut = nullptr;	   // [n_text_ctx][maxBatch]
 	// the captured decode steps of every kind, by ( batch, stepKey ): owned by step_graph.hip, which states the key and the retention rule. stepCaptures counts the
 	// graphs instantiated over the context's life (wh_debug_step_captures)
-	struct StepGraph { int batch; uint32_t key; hipGraphExec_t exec; };
+	struct StepGraph { int batch; uint64_t key; hipGraphExec_t exec; };
 	std::vector<StepGraph> stepGraphs;
 	int stepCaptures = 0;
-	hipGraphExec_t stepGraph( int batch, uint32_t key ) const
+	hipGraphExec_t stepGraph( int batch, uint64_t key ) const
 	{
 		for( const StepGraph& g : stepGraphs )
 			if( g.batch == batch && g.key == key ) return g.exec;
@@ -484,12 +492,12 @@ namespace wh
 	int alignDebugRead( wh_context* c, const std::string& w, int layer, float* dstHost, int64_t dstCapFloats );
 
 	// captured decode steps (step_graph.hip, where each of these is explained)
-	constexpr uint32_t STEP_KEY_ROWS = 0x40000u, STEP_KEY_BEAM = 0x200000u;	  // bits 19, 20 and 26-31 are the filters' (filterGraphKey, filterLoopKey)
+	constexpr uint32_t STEP_KEY_ROWS = 0x40000u, STEP_KEY_BEAM = 0x200000u;	  // bits 19, 20, 26-31 and 32 are the filters' (filterGraphKey, filterLoopKey)
 	using StepFn = std::function<int()>;
 	enum eWarmUp { WARM_FRESH, WARM_PRESERVE };
 	bool stepsReplayable( const wh_context* c );
-	uint32_t stepKey( const wh_context* c, int beamWidth );	   // beamWidth 0: a step of the greedy loop
-	int obtainStepGraph( wh_context* c, int batch, uint32_t key, eWarmUp warm, const StepFn& idle, const StepFn& step, hipGraphExec_t& exec );
+	uint64_t stepKey( const wh_context* c, int beamWidth );	   // beamWidth 0: a step of the greedy loop
+	int obtainStepGraph( wh_context* c, int batch, uint64_t key, eWarmUp warm, const StepFn& idle, const StepFn& step, hipGraphExec_t& exec );
 	int idleLoopState( wh_context* c, int batch );
 	int enqueueSteps( wh_context* c, hipGraphExec_t exec, int nSteps, int firstKeys, const StepFn& step );
 	// what WARM_PRESERVE carries over the warm-up step: the list is stated next to the step that mutates it (decode.hip); `filters` is saveFilterState's
@@ -503,7 +511,7 @@ namespace wh
 	void bypassFilterLogits( wh_context* c, bool on );						  // around wh_lang_detect's pass
 	int filterLoopRows( wh_context* c, int batch, eFilterPhase phase );	  // between decodeGraph and the sampler of the device-side loop
 	uint32_t filterGraphKey( const wh_context* c );							  // stepKey's bits of every step that runs decodeGraph
-	uint32_t filterLoopKey( const wh_context* c );							  // ... and of a step of the greedy loop
+	uint64_t filterLoopKey( const wh_context* c );							  // ... and of a step of the greedy loop
 	int saveFilterState( const wh_context* c, int batch, std::vector<uint8_t>& s );
 	int restoreFilterState( wh_context* c, int batch, const std::vector<uint8_t>& s );
 	int filtersAllowFlags( const wh_context* c, uint32_t flags );			  // wh_context_set_flags: 0, or the refusal with its error set

@@ -18,7 +18,7 @@ bool wh::stepsReplayable( const wh_context* c )
 //   token alternatives   alternativesLoopKey (alternatives.hip): k in bits 22-25 of a greedy step's key
 //   STEP_KEY_BEAM + width in bits 22-25: a beam step of that width. It runs decodeGraph like the greedy step, so it shares the parity input and filterGraphKey; it
 //                        has no sampler and none of the filters in front of one, so the other bits stay clear
-uint32_t wh::stepKey( const wh_context* c, int beamWidth )
+uint64_t wh::stepKey( const wh_context* c, int beamWidth )
 {
 	const uint32_t graph = ( ( c->flags & WH_FLAG_PARITY_PV ) ? ( 0x10000u | (uint32_t)c->parityThreads ) : 0u ) | filterGraphKey( c );
 	if( beamWidth > 0 ) return graph | STEP_KEY_BEAM | ( (uint32_t)beamWidth << 22 );
@@ -29,12 +29,12 @@ uint32_t wh::stepKey( const wh_context* c, int beamWidth )
 // turn. Of the same kind, an entry goes when it differs in the batch or in the key -- except that a greedy entry may differ in the per-row bit: at most the
 // greedy graph and the per-row graph of one batch live side by side, so a lock-step batch whose rounds enter and leave the per-row mode never recaptures, and
 // there is at most one beam entry. The caller has waited for the stream: a graph that goes may have been queued.
-static void dropStaleStepGraphs( wh_context* c, int batch, uint32_t key )
+static void dropStaleStepGraphs( wh_context* c, int batch, uint64_t key )
 {
-	const uint32_t sibling = ( key & STEP_KEY_BEAM ) ? 0u : STEP_KEY_ROWS;
+	const uint64_t sibling = ( key & STEP_KEY_BEAM ) ? 0u : STEP_KEY_ROWS;
 	// ... and in the k of wh_context_set_alternatives, as long as one of the two has k = 0: turning the setting on and off again recaptures nothing, another k
 	// above 0 replaces the one before it
-	const uint32_t alt = ( key & STEP_KEY_BEAM ) ? 0u : STEP_KEY_ALT_MASK;
+	const uint64_t alt = ( key & STEP_KEY_BEAM ) ? 0u : STEP_KEY_ALT_MASK;
 	for( size_t i = 0; i < c->stepGraphs.size(); )
 	{
 		const wh_context::StepGraph& g = c->stepGraphs[ i ];
@@ -51,7 +51,7 @@ static void dropStaleStepGraphs( wh_context* c, int batch, uint32_t key )
 
 // One run of `step`, captured on the context's stream and kept under ( batch, key ). A step that fails inside the capture still ends the capture; a failed
 // instantiate leaves no entry.
-static int captureStepGraph( wh_context* c, int batch, uint32_t key, const StepFn& step, hipGraphExec_t& exec )
+static int captureStepGraph( wh_context* c, int batch, uint64_t key, const StepFn& step, hipGraphExec_t& exec )
 {
 	hipGraph_t graph = nullptr;
 	WH_HIP( hipStreamBeginCapture( c->stream, hipStreamCaptureModeThreadLocal ) );
@@ -78,7 +78,7 @@ static int captureStepGraph( wh_context* c, int batch, uint32_t key, const StepF
 //                  over cache rows of an earlier wh_decode. The warm-up runs where the state stands -- at position 0 it would clobber row 0 of a live cache;
 //                  the row it writes instead is the one the first replayed step rewrites -- and everything else the step mutates (LoopState) is read back
 //                  before it and rewritten after the capture. `idle` is not called.
-int wh::obtainStepGraph( wh_context* c, int batch, uint32_t key, eWarmUp warm, const StepFn& idle, const StepFn& step, hipGraphExec_t& exec )
+int wh::obtainStepGraph( wh_context* c, int batch, uint64_t key, eWarmUp warm, const StepFn& idle, const StepFn& step, hipGraphExec_t& exec )
 {
 	exec = c->stepGraph( batch, key );
 	if( exec ) return 0;

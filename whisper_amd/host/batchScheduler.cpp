@@ -26,6 +26,7 @@
 #include "batchSuppress.h"
 #include "batchTimestampRules.h"
 #include "batchBoost.h"
+#include "batchConstraint.h"
 #include "batchNoRepeat.h"
 #include "batchNucleus.h"
 #include "batchSpeech.h"
@@ -56,6 +57,8 @@ namespace Whisper
 	pfnBatchTimestampRules g_batchTimestampRules = nullptr;
 	// ... and for boosted phrases (batchBoost.h)
 	pfnBatchBoost g_batchBoost = nullptr;
+	// ... and for constrained decoding (batchConstraint.h)
+	pfnBatchConstraint g_batchConstraint = nullptr;
 	// ... and for no-repeat n-grams (batchNoRepeat.h)
 	pfnBatchNoRepeat g_batchNoRepeat = nullptr;
 	// ... and for top-k and nucleus sampling (batchNucleus.h)
@@ -227,6 +230,8 @@ namespace Whisper
 			uint32_t timestampRulesVersion = 0;
 			// boosted phrases: the version of the runner's set this group's context holds (0 = never told: a new context holds none)
 			uint32_t boostVersion = 0;
+			// constrained decoding: the version of the runner's constraint this group's context holds (0 = never told: a new context holds none)
+			uint32_t constraintVersion = 0;
 			// no-repeat n-grams: the n this group's context holds (a new context holds 0, off)
 			int noRepeatN = 0;
 			// top-k and nucleus sampling: the pair this group's context holds (a new context holds 0 and 1, off)
@@ -775,6 +780,9 @@ namespace Whisper
 			// Whisper::setBatchBoostedPhrases: one set for every stream; each group's context is told once, before the first round that follows a change
 			phraseBoost::Set boostSet;
 			uint32_t boostVersion = 0;
+			// Whisper::setBatchDecodingConstraint: one constraint for every stream; each group's context is told once, before the first round that follows a change
+			HeldConstraint constraint;
+			uint32_t constraintVersion = 0;
 			// Whisper::setBatchNoRepeatNgram: one n for every stream, 0 = off; a group's context is told before the first round in which it holds another n
 			int noRepeatN = 0;
 			// Whisper::setBatchSamplingFilter: one pair for every stream, ( 0, 1 ) = off; a group's context is told before the first round in which it holds another.
@@ -807,6 +815,16 @@ namespace Whisper
 				if( set.count() == 0 && boostSet.count() == 0 ) return S_OK;
 				boostSet = std::move( set );
 				boostVersion++;
+				return S_OK;
+			}
+			HRESULT setConstraint( const sDecodingConstraint* p )
+			{
+				CHECK( optionRules::checkConstraint( "setBatchDecodingConstraint", p ) );
+				if( p && !g_batchConstraint ) return optionRules::notGiven( "setBatchDecodingConstraint", "constraint filter" );
+				if( !p && !constraint.on() ) return S_OK;
+				if( p ) constraint.assign( *p, model->vocab );
+				else constraint.clear();
+				constraintVersion++;
 				return S_OK;
 			}
 			HRESULT setSpeech( const sSpeechFilter* p )
@@ -1009,6 +1027,11 @@ namespace Whisper
 						CHECK_WH( g_batchBoost( g.gpu, boostSet.tokens.data(), boostSet.lens.data(), boostSet.count(), boostSet.nMax, boostSet.boost ) );
 						g.boostVersion = boostVersion;
 					}
+					if( g.constraintVersion != constraintVersion && g_batchConstraint )
+					{
+						CHECK_WH( g_batchConstraint( g.gpu, constraint.device() ) );
+						g.constraintVersion = constraintVersion;
+					}
 					if( g.noRepeatN != noRepeatN && g_batchNoRepeat )
 					{
 						CHECK_WH( g_batchNoRepeat( g.gpu, noRepeatN ) );
@@ -1090,6 +1113,11 @@ namespace Whisper
 	{
 		return optionRules::forward<BatchRunner>( runner, "setBatchBoostedPhrases", NOT_A_RUNNER, nullptr,
 			[ = ]( BatchRunner& r ) { return r.setBoosted( phrases ); } );
+	}
+	HRESULT setBatchDecodingConstraint( iBatchRunner* runner, const sDecodingConstraint* constraint )
+	{
+		return optionRules::forward<BatchRunner>( runner, "setBatchDecodingConstraint", NOT_A_RUNNER, nullptr,
+			[ = ]( BatchRunner& r ) { return r.setConstraint( constraint ); } );
 	}
 	HRESULT setBatchNoRepeatNgram( iBatchRunner* runner, int n )
 	{

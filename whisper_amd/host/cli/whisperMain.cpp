@@ -22,6 +22,7 @@
 #include <vector>
 #include "subtitles.h"
 #include "phraseFile.h"
+#include "../phraseAutomaton.h"
 using namespace Whisper;
 
 namespace
@@ -489,6 +490,8 @@ int main( int argc, char** argv )
 	// --score FILE (the same way): instead of transcribing, Whisper::scoreTokens of the text in FILE against every input (a clip of 1 to 30 s): one line per
 	// token -- its time with --align (forced alignment), log-probability, rank, text -- and a summary line
 	// --boost-phrases FILE --boost N (the same way; one needs the other): Whisper::setBoostedPhrases with the spellings of the file's phrases, one per line
+	// --allow-phrases FILE [--allow-repeat] [--constraint-penalty N] (the same way): Whisper::setDecodingConstraint with the byte automaton of the file's phrases, one
+	// per line (phraseAutomaton.h: one optional leading space; --allow-repeat = phrases joined by single spaces); N defaults to 100, whisper.cpp's, and may be inf
 	// -nrn N / --no-repeat-ngram N (the same way): Whisper::setNoRepeatNgram, no text token that would complete an n-gram its window already holds (0 = off)
 	// --top-k N --top-p X (the same way; either alone is fine): Whisper::setSamplingFilter, the sampled attempts of --fallback draw from the N likeliest tokens and, of
 	// those, the shortest prefix whose probability reaches X (0 and 1 = off). Legal without --fallback, and then WITHOUT EFFECT: greedy decoding samples nothing
@@ -503,8 +506,9 @@ int main( int argc, char** argv )
 	bool align = false, useFallback = false, suppressNst = false, timestampRules = false, haveBoost = false;
 	int noRepeatNgram = 0, topK = 0;
 	float topP = 1.0f;
-	std::string scoreFile, boostFile;
-	float boost = 0.0f;
+	std::string scoreFile, boostFile, allowFile;
+	float boost = 0.0f, constraintPenalty = 100.0f;
+	bool allowRepeat = false, havePenalty = false;
 	sDecodingFallback fallbackParams;
 	{
 		int kept = 1;
@@ -530,6 +534,13 @@ int main( int argc, char** argv )
 				boostFile = argv[ ++i ];
 			}
 			else if( !strcmp( argv[ i ], "--boost" ) ) { value = &boost; haveBoost = true; }
+			else if( !strcmp( argv[ i ], "--allow-phrases" ) )
+			{
+				if( i + 1 >= argc ) { fprintf( stderr, "error: --allow-phrases needs a file\n" ); return 2; }
+				allowFile = argv[ ++i ];
+			}
+			else if( !strcmp( argv[ i ], "--allow-repeat" ) ) allowRepeat = true;
+			else if( !strcmp( argv[ i ], "--constraint-penalty" ) ) { value = &constraintPenalty; havePenalty = true; }
 			else if( !strcmp( argv[ i ], "--capture" ) )
 			{
 				if( i + 1 >= argc ) { fprintf( stderr, "error: --capture needs a path (- = standard input)\n" ); return 2; }
@@ -587,6 +598,11 @@ int main( int argc, char** argv )
 	if( boostFile.empty() != !haveBoost )
 	{
 		fprintf( stderr, "error: --boost-phrases FILE and --boost N go together (there is no default boost)\n" );
+		return 2;
+	}
+	if( allowFile.empty() && ( allowRepeat || havePenalty ) )
+	{
+		fprintf( stderr, "error: --allow-repeat and --constraint-penalty need --allow-phrases FILE\n" );
 		return 2;
 	}
 	if( speechTuned && !speechOnly )
@@ -699,6 +715,16 @@ int main( int argc, char** argv )
 		const sBoostedPhrases set = rows.set( boost );
 		hr = setBoostedPhrases( context, &set );
 		if( FAILED( hr ) ) { printFailure( "failed to set the boosted phrases", hr ); return 6; }
+	}
+	if( !allowFile.empty() )
+	{
+		phraseAutomaton::Dfa dfa;
+		std::string why;
+		hr = phraseAutomaton::load( allowFile, phraseAutomaton::eLeadingSpace::Optional, allowRepeat, dfa, why );
+		if( FAILED( hr ) ) { printFailure( why.c_str(), hr ); return 6; }
+		const sDecodingConstraint constraint = dfa.constraint( constraintPenalty );
+		hr = setDecodingConstraint( context, &constraint );
+		if( FAILED( hr ) ) { printFailure( "failed to set the decoding constraint", hr ); return 6; }
 	}
 
 	ComLight::CComPtr<iMediaFoundation> media;

@@ -252,6 +252,19 @@ WHISPER_EXPORT int32_t whisperc_batch_set_no_repeat_ngram( void* runner, int32_t
 	if( !runner ) return E_POINTER;
 	return setBatchNoRepeatNgram( (iBatchRunner*)runner, n );
 }
+// Whisper::setDecodingConstraint / setBatchDecodingConstraint: states == 0 turns the constraint off (the pointers may be NULL)
+WHISPER_EXPORT int32_t whisperc_set_constraint( void* ctx, uint32_t states, uint32_t classes, uint32_t start, const uint8_t* classOf, const int32_t* transitions, const uint8_t* accept, float penalty )
+{
+	if( !ctx ) return E_POINTER;
+	const sDecodingConstraint k{ states, classes, start, classOf, transitions, accept, penalty };
+	return setDecodingConstraint( (iContext*)ctx, states ? &k : nullptr );
+}
+WHISPER_EXPORT int32_t whisperc_batch_set_constraint( void* runner, uint32_t states, uint32_t classes, uint32_t start, const uint8_t* classOf, const int32_t* transitions, const uint8_t* accept, float penalty )
+{
+	if( !runner ) return E_POINTER;
+	const sDecodingConstraint k{ states, classes, start, classOf, transitions, accept, penalty };
+	return setBatchDecodingConstraint( (iBatchRunner*)runner, states ? &k : nullptr );
+}
 // Whisper::setSamplingFilter / setBatchSamplingFilter: ( 0, 1 ) turns the filter off
 WHISPER_EXPORT int32_t whisperc_set_sampling_filter( void* ctx, int32_t topK, float topP )
 {

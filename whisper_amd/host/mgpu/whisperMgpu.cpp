@@ -36,6 +36,7 @@
 #include "whisperApi.h"
 #include "whisper_hip.h"
 #include "../cli/phraseFile.h"
+#include "../phraseAutomaton.h"
 using namespace Whisper;
 
 namespace
@@ -75,6 +76,11 @@ namespace
 		std::string boostFile;
 		bool haveBoost = false;
 		float boost = 0.0f;
+		// -allow-phrases FILE [-allow-repeat] [-constraint-penalty N] (whisper-main's options): Whisper::setBatchDecodingConstraint on every rank's runner with the
+		// byte automaton of the file's phrases (phraseAutomaton.h); N defaults to 100 and may be inf
+		std::string allowFile;
+		bool allowRepeat = false, havePenalty = false;
+		float constraintPenalty = 100.0f;
 	};
 	std::wstring widen( const std::string& s )
 	{
@@ -314,6 +320,16 @@ namespace
 			hr = setBatchBoostedPhrases( runner, &set );
 			if( FAILED( hr ) ) { fprintf( stderr, "[rank %d] setBatchBoostedPhrases failed 0x%08x\n", rank, (unsigned)hr ); return 6; }
 		}
+		if( runner && !a.allowFile.empty() )
+		{
+			phraseAutomaton::Dfa dfa;
+			std::string why;
+			hr = phraseAutomaton::load( a.allowFile, phraseAutomaton::eLeadingSpace::Optional, a.allowRepeat, dfa, why );
+			if( FAILED( hr ) ) { fprintf( stderr, "[rank %d] %s 0x%08x\n", rank, why.c_str(), (unsigned)hr ); return 6; }
+			const sDecodingConstraint constraint = dfa.constraint( a.constraintPenalty );
+			hr = setBatchDecodingConstraint( runner, &constraint );
+			if( FAILED( hr ) ) { fprintf( stderr, "[rank %d] setBatchDecodingConstraint failed 0x%08x\n", rank, (unsigned)hr ); return 6; }
+		}
 
 		if( 0 != wh_comm_barrier( comm ) ) { fprintf( stderr, "[rank %d] %s\n", rank, wh_last_error() ); return 8; }
 		const double tStart = since();
@@ -476,6 +492,9 @@ int main( int argc, char** argv )
 		else if( !strcmp( argv[ i ], "-so-pad" ) || !strcmp( argv[ i ], "--so-pad" ) ) { a.soPad = (float)atof( val() ); soTuned = true; }
 		else if( !strcmp( argv[ i ], "-boost-phrases" ) || !strcmp( argv[ i ], "--boost-phrases" ) ) a.boostFile = val();
 		else if( !strcmp( argv[ i ], "-boost" ) || !strcmp( argv[ i ], "--boost" ) ) { a.boost = (float)atof( val() ); a.haveBoost = true; }
+		else if( !strcmp( argv[ i ], "-allow-phrases" ) || !strcmp( argv[ i ], "--allow-phrases" ) ) a.allowFile = val();
+		else if( !strcmp( argv[ i ], "-allow-repeat" ) || !strcmp( argv[ i ], "--allow-repeat" ) ) a.allowRepeat = true;
+		else if( !strcmp( argv[ i ], "-constraint-penalty" ) || !strcmp( argv[ i ], "--constraint-penalty" ) ) { a.constraintPenalty = strtof( val(), nullptr ); a.havePenalty = true; }
 		else if( !strcmp( argv[ i ], "-tpi" ) ) a.fallback.temperatureInc = (float)atof( val() );
 		else if( !strcmp( argv[ i ], "-lpt" ) ) a.fallback.logprobThold = (float)atof( val() );
 		else if( !strcmp( argv[ i ], "-et" ) ) a.fallback.entropyThold = (float)atof( val() );
@@ -513,6 +532,7 @@ int main( int argc, char** argv )
 	}
 	if( a.splitSilence && a.perRecording ) { fprintf( stderr, "whisper-mgpu: -split silence cuts ONE recording into chunks; -per-recording keeps recordings whole\n%s", USAGE ); return 1; }
 	if( soTuned && !a.speechOnly ) { fprintf( stderr, "whisper-mgpu: -so-min-silence, -so-min-speech and -so-pad need -speech-only\n" ); return 1; }
+	if( a.allowFile.empty() && ( a.allowRepeat || a.havePenalty ) ) { fprintf( stderr, "whisper-mgpu: -allow-repeat and -constraint-penalty need -allow-phrases FILE\n" ); return 1; }
 	if( a.boostFile.empty() != !a.haveBoost ) { fprintf( stderr, "whisper-mgpu: -boost-phrases FILE and -boost N go together (there is no default boost)\n" ); return 1; }
 	if( a.model.empty() || a.wav.empty() || a.ranks < 1 ) { fprintf( stderr, "whisper-mgpu: -m and -f are required\n" ); return 1; }
 	if( !a.perRecording && a.wavs.size() > 1 ) { fprintf( stderr, "whisper-mgpu: several -f recordings need -per-recording (the chunk mode shards ONE recording)\n" ); return 1; }

@@ -54,6 +54,23 @@ namespace Whisper
 			logError( "%s: topK = %i is outside 0 .. 1024, or topP = %g is outside ( 0, 1 ]", name, topK, (double)topP );
 			return E_INVALIDARG;
 		}
+		// constrained decoding: the automaton's limits (the compute layer's CON_MAX_*), every transition in [ -1, states ), every class below `classes`, the penalty
+		inline HRESULT checkConstraint( const char* name, const sDecodingConstraint* p )
+		{
+			if( !p ) return S_OK;
+			if( !p->classOf || !p->transitions || !p->accept ) return E_POINTER;
+			const auto refuse = [ & ]( const char* why, long long v ) { logError( "%s: %s (%lli)", name, why, v ); return E_INVALIDARG; };
+			if( p->states < 1 || p->states > 4096 ) return refuse( "a constraint has 1 .. 4096 states", (long long)p->states );
+			if( p->classes < 1 || p->classes > 256 ) return refuse( "a constraint has 1 .. 256 byte classes", (long long)p->classes );
+			if( (uint64_t)p->states * p->classes > 65536 ) return refuse( "states * classes is above 65536, the transition table of one constraint", (long long)p->states * p->classes );
+			if( p->start >= p->states ) return refuse( "the start state is outside [ 0, states )", (long long)p->start );
+			if( !( p->penalty > 0.0f ) ) return refuse( "the penalty must be greater than 0 (+inf is allowed, NaN is not)", 0 );
+			for( int i = 0; i < 256; i++ )
+				if( p->classOf[ i ] >= p->classes ) return refuse( "a byte's class is outside [ 0, classes ), byte", i );
+			for( uint32_t i = 0; i < p->states * p->classes; i++ )
+				if( p->transitions[ i ] < -1 || p->transitions[ i ] >= (int32_t)p->states ) return refuse( "a transition is outside [ -1, states ), entry", (long long)i );
+			return S_OK;
+		}
 		// the speech filter's parameters: frames, each 0 (the default) .. 2^20 (speechSpans.h states the defaults and the bound); flags reserved
 		inline HRESULT checkSpeechFilter( const char* name, const sSpeechFilter& p )
 		{

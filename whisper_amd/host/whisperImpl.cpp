@@ -14,6 +14,7 @@
 #include "batchSuppress.h"
 #include "batchTimestampRules.h"
 #include "batchBoost.h"
+#include "batchConstraint.h"
 #include "batchNoRepeat.h"
 #include "batchNucleus.h"
 #include "batchSpeech.h"
@@ -144,6 +145,8 @@ namespace Whisper
 			bool timestampRulesOn = false;
 			// Whisper::setBoostedPhrases: off unless set. The stream's device context holds the set; the hypothesis-group context of beam search cannot (runFull refuses)
 			bool boostOn = false;
+			// Whisper::setDecodingConstraint: off unless set; like the phrases, nothing a hypothesis-group context can hold
+			bool constraintOn = false;
 			// Whisper::setNoRepeatNgram: 0 = off unless set. The stream's device context holds n; the hypothesis-group context of beam search cannot (runFull refuses)
 			int noRepeatN = 0;
 			// Whisper::setTokenAlternatives: 0 = off unless set. The stream's device context holds k; tokenAlts: k records per token of resultAll, in its order, and
@@ -349,6 +352,16 @@ namespace Whisper
 				CHECK( optionRules::checkBoosted( "setBoostedPhrases", p, model->vocab.token_eot, set ) );
 				CHECK_WH( wh_context_set_boost( gpu, set.tokens.data(), set.lens.data(), set.count(), set.nMax, set.boost ) );
 				boostOn = set.count() > 0;
+				return S_OK;
+			}
+			// Whisper::setDecodingConstraint: the stream's device context holds the tables; the vocabulary's bytes are the model's
+			HRESULT setConstraint( const sDecodingConstraint* p )
+			{
+				CHECK( optionRules::checkConstraint( "setDecodingConstraint", p ) );
+				HeldConstraint held;
+				if( p ) held.assign( *p, model->vocab );
+				CHECK_WH( wh_context_set_constraint( gpu, held.device() ) );
+				constraintOn = held.on();
 				return S_OK;
 			}
 			const std::vector<sWindowStats>& lastWindowStats() const { return windowStats; }
@@ -1038,6 +1051,12 @@ namespace Whisper
 				logError( "runFull: boosted phrases (setBoostedPhrases) are not available with eSamplingStrategy::BeamSearch" );
 				return E_NOTIMPL;
 			}
+			// a decoding constraint: the device-side loop only (the per-sequence states would have to follow the beam's parent reorder)
+			if( constraintOn && params.strategy == eSamplingStrategy::BeamSearch && params.beam_search.beam_width >= 1 )
+			{
+				logError( "runFull: a decoding constraint (setDecodingConstraint) is not available with eSamplingStrategy::BeamSearch" );
+				return E_NOTIMPL;
+			}
 			// no-repeat n-grams: the device-side loop only (the per-sequence histories would have to follow the beam's parent reorder)
 			if( noRepeatN && params.strategy == eSamplingStrategy::BeamSearch && params.beam_search.beam_width >= 1 )
 			{
@@ -1462,6 +1481,8 @@ namespace Whisper
 	static const bool g_timestampRulesInstalled = ( g_batchTimestampRules = &wh_context_set_timestamp_rules, true );
 	// ... and to the phrase filter (batchBoost.h)
 	static const bool g_boostInstalled = ( g_batchBoost = &wh_context_set_boost, true );
+	// ... and to constrained decoding (batchConstraint.h)
+	static const bool g_constraintInstalled = ( g_batchConstraint = &wh_context_set_constraint, true );
 	// ... and to the n-gram filter (batchNoRepeat.h)
 	static const bool g_noRepeatInstalled = ( g_batchNoRepeat = &wh_context_set_no_repeat, true );
 	// ... and to top-k and nucleus sampling (batchNucleus.h)
@@ -1526,6 +1547,11 @@ namespace Whisper
 	{
 		return optionRules::forward<ContextImpl>( context, "setNoRepeatNgram", NOT_A_CONTEXT, "a batch runner takes setBatchNoRepeatNgram",
 			[ = ]( ContextImpl& c ) { return c.setNoRepeat( n ); } );
+	}
+	HRESULT setDecodingConstraint( iContext* context, const sDecodingConstraint* constraint )
+	{
+		return optionRules::forward<ContextImpl>( context, "setDecodingConstraint", NOT_A_CONTEXT, "a batch runner takes setBatchDecodingConstraint",
+			[ = ]( ContextImpl& c ) { return c.setConstraint( constraint ); } );
 	}
 	HRESULT setSamplingFilter( iContext* context, int topK, float topP )
 	{
