@@ -388,6 +388,11 @@ namespace Whisper
 								// 8 = INT4 cross-attention caches: the groups' contexts are created with wh_context_create_kv4 (4-bit codes and one scale per key row:
 								//     36 bytes per key row where FP16 takes 128 and FP8 68). May be combined with 4; together with 2 createBatchRunner answers E_INVALIDARG.
 								//     Off unless set. Four-bit K and V move the logits more than FP8 does; nobody has measured recognition accuracy with them on a real checkpoint.
+								// 16 = INT8 decoder weights: wh_context_set_decoder_w8 on the groups' contexts (single-token decode steps of up to 32 slots stream int8 copies
+								//     of the decoder's Q/K/V, attention-out, MLP and vocabulary weights, one scale per weight row; the activations stay FP16; models whose
+								//     state size is a multiple of 128). May be combined with every other bit. Off unless set. A single iContext has no such switch: its
+								//     one-stream steps run kernels tuned for latency on FP16 weights. Nobody has measured recognition accuracy with INT8 decoder weights
+								//     on a real checkpoint.
 	};
 	// {6f0c9a1e-3b52-4d7c-8e21-9a4f5c7d2b10}
 	struct iBatchRunner : public ComLight::IUnknown

@@ -166,7 +166,8 @@ int32_t whisperc_result_token( void* ctx, uint32_t index, int32_t* id, float* p,
 int32_t whisperc_result_token_times( void* ctx, uint32_t index, uint64_t* t0, uint64_t* t1, float* vlen );
 /* Whisper::createBatchRunner( model, { maxSlots, groups, greedyChunk, flags } ) (0 = the defaults) -> iBatchRunner; release with whisperc_release.
  * flags: 1 = one more greedy chunk queued behind the one in flight; 2 = FP8 cross-attention caches in the groups' contexts;
- * 4 = INT8 encoder products in the groups' contexts; 8 = INT4 cross-attention caches in the groups' contexts, not together with 2 (sBatchSetup::flags) */
+ * 4 = INT8 encoder products in the groups' contexts; 8 = INT4 cross-attention caches in the groups' contexts, not together with 2;
+ * 16 = INT8 decoder weights in the groups' contexts, with any of the others (sBatchSetup::flags) */
 int32_t whisperc_batch_create( void* model, uint32_t maxSlots, uint32_t groups, uint32_t greedyChunk, uint32_t flags, void** runnerOut );
 /* iBatchRunner::run over `count` streams: stream i = samples [firstSample[i], firstSample[i] + countSamples[i]) (0 = to the end) of the mono FP32
  * 16 kHz buffer pcm[i] of nSamples[i] samples (streams may name the same buffer: the chunks of one recording); the common sFullParams are

@@ -193,6 +193,22 @@ WH_API int wh_context_create_kv4_hyp( wh_model* m, int maxBatch, int hypotheses,
  * WH_FLAG_PARITY_EXACT (in either order of setting), or on a model whose n_audio_state is not a multiple of 128. Nobody has measured recognition accuracy with
  * INT8 encoder products on a real checkpoint. */
 WH_API int wh_context_set_encoder_i8( wh_context* c, int on );
+/* INT8 decoder weights (whisper_amd/csrc/gemm_decode_w8.hip; DESIGN.md section 7 "INT8 decoder weights"). on != 0: every single-token decode step of at most 32
+ * rows (sequences; the kernel serves 128, the limit is where a whole step stops winning: see "Measured" below) runs its Q/K/V, self-attention out, cross-attention out, MLP-up, MLP-down and vocabulary products on gemvW8, which streams int8 weight rows
+ * (the format above: one FP32 scale per weight row, s = amax / 127, q = rint( x / s ) in [-127, 127]) against the FP16 activation rows: weights only are
+ * quantized, every product x * q is exact on the FP16 matrix instruction, the sum is FP32 and the row scale is applied once, to the sum. Such a context takes the
+ * batch path at every batch size (the single-stream kernels read FP16 weights). What stays FP16: steps of more than 32 rows, the multi-token passes (prompt,
+ * wh_score_tokens, wh_align_tokens), the cross-attention query weight (read inside the attention kernels), the cross-K/V product and the encoder. The first
+ * enable for a model quantizes the copies on the device with quantizeRowsI8 (contexts share them; the FP16 weights stay): 13 d^2 + 40 d bytes per decoder layer
+ * and ( d + 4 ) n_vocab for the token embedding, 380 MB on the medium model. A change of the setting voids the context's captured step graphs. on == 0: launch
+ * for launch what a context that never had the setting runs. Off unless set; works on hypothesis-group, FP8 and INT4 contexts and together with
+ * wh_context_set_encoder_i8. WH_E_INVALIDARG with the reason in wh_last_error: together with WH_FLAG_PARITY_PV or WH_FLAG_PARITY_EXACT (in either order of
+ * setting), or on a model whose n_text_state is not a multiple of 128. Measured on one MI355X, medium shapes (profiles/decoder_w8_probe.json): a whole step of the
+ * greedy loop takes 0.915 of the FP16 time at 8 sequences and 0.95 at 32; launch by launch the int8 product wins only where the bytes dominate (MLP-down 0.80 ..
+ * 0.84 and vocabulary 0.82 .. 0.85 up to 32 rows) and loses elsewhere (1.14 .. 1.54 on the d x d, Q/K/V and MLP-up products; 1.9 .. 2.1 on the vocabulary product
+ * at 64 and 128 rows). Nobody has measured recognition accuracy with INT8
+ * decoder weights on a real checkpoint. */
+WH_API int wh_context_set_decoder_w8( wh_context* c, int on );
 WH_API void wh_context_destroy( wh_context* c );
 /* Binds the model's device to the calling thread (every wh_* call on a model or context does it as well): the
  * counterpart of Device::setForCurrentThread (Whisper/ML/Device.cpp:163-177). Call it before wh_buffer_alloc /
@@ -907,6 +923,13 @@ WH_API int wh_op_mel_to_conv_input( void* stream, const float* melDev, int64_t m
  * Operands a combination does not use may be NULL. Bad shapes or missing operands: an error, nothing is launched. */
 WH_API int wh_op_gemv_small( void* stream, int M, int N, int K, int epi, int pro, const void* wF16, const void* aF16, const float* lnX, const float* lnW,
 	const float* lnB, const float* part, const float* bias, const float* residual, float* out32, void* out16, void* qF16, void* kCache, void* vCache, int heads,
+	int textCtx, int nPast, const int32_t* nPastDev, float scale );
+/* gemvW8, the product of wh_context_set_decoder_w8, alone: out[m][n] = epilogue( ( sum_k x[m][k] * (float)w[n][k] ) * scaleW[n] ), w int8 [N][K], scaleW FP32 [N],
+ * 1 <= M <= 128 rows, K a multiple of 128 and at most 5120, any N, FP32 accumulation on the matrix cores. pro: 0  x = aF16, FP16 [M][K]; 1  x = fp16( LayerNorm(
+ * lnX[m] ) * lnW + lnB ), lnX FP32 [M][K], M <= 32 and K <= 1280. epi 0, 1, 2 and their operands: as wh_op_gemv_small, with the scaled sum in acc's place. Device
+ * pointers, 16-byte aligned. Operands a combination does not use may be NULL. Bad shapes or missing operands: WH_E_INVALIDARG, nothing is launched. */
+WH_API int wh_op_gemv_w8( void* stream, int M, int N, int K, int epi, int pro, const void* wI8, const float* scaleW, const void* aF16, const float* lnX,
+	const float* lnW, const float* lnB, const float* bias, const float* residual, float* out32, void* out16, void* qF16, void* kCache, void* vCache, int heads,
 	int textCtx, int nPast, const int32_t* nPastDev, float scale );
 /* crossScores then crossSoftmaxPV: the cross-attention of up to 4 sequences over 8 key ranges per head, range length ( ( nKeys + 7 ) / 8 + 3 ) & ~3. The query is
  * wh_op_decoder_cross_attention's. scores FP32 [sequences][heads][keyStride] = K . q for key < nKeys; splitMax FP32 [sequences][heads][8] = the maximum of each

@@ -877,11 +877,12 @@ BATCH_LOOKAHEAD = 1         # sBatchSetup::flags: keep one more greedy chunk que
 BATCH_CROSS_FP8 = 2         # ... the groups' contexts hold FP8 cross-attention caches (wh_context_create_kv8): about half the cache memory per slot; off unless set
 BATCH_CROSS_INT4 = 8        # ... the groups' contexts hold INT4 cross-attention caches (wh_context_create_kv4): 36 bytes per key row instead of 128; not with BATCH_CROSS_FP8; off unless set
 BATCH_ENCODER_INT8 = 4      # ... the groups' contexts run the encoder's linear products in INT8 (wh_context_set_encoder_i8); may be combined with BATCH_CROSS_FP8; off unless set
+BATCH_DECODER_INT8 = 16     # ... the groups' contexts stream INT8 copies of the decoder's weights in their single-token steps (wh_context_set_decoder_w8); combines with every other flag; off unless set
 
 
 class BatchRunner:
     """iBatchRunner (Whisper::createBatchRunner): K streams in lock step; each keeps the semantics of iContext::runFull.
-    flags: BATCH_LOOKAHEAD, BATCH_CROSS_FP8, BATCH_ENCODER_INT8, BATCH_CROSS_INT4 (beam search and AlignTokens answer E_NOTIMPL in a batch either way)."""
+    flags: BATCH_LOOKAHEAD, BATCH_CROSS_FP8, BATCH_ENCODER_INT8, BATCH_CROSS_INT4, BATCH_DECODER_INT8 (beam search and AlignTokens answer E_NOTIMPL in a batch either way)."""
 
     def __init__(self, model: Model, max_slots: int = 0, groups: int = 0, greedy_chunk: int = 0, flags: int = 0):
         self.model = model

@@ -44,7 +44,7 @@ EXPORTS = [
     "wh_model_arena_bytes", "wh_model_create", "wh_model_destroy", "wh_model_set_tensor", "wh_model_set_filters",
     "wh_model_finalize", "wh_model_arena", "wh_model_hparams",
     "wh_comm_runtime_check", "wh_comm_unique_id", "wh_comm_create", "wh_comm_destroy", "wh_comm_info", "wh_comm_barrier", "wh_comm_create_timeout", "wh_comm_set_timeout", "wh_comm_broadcast_i32", "wh_model_broadcast",
-    "wh_context_create", "wh_context_create_hyp", "wh_context_create_kv8", "wh_context_create_kv8_hyp", "wh_context_create_kv4", "wh_context_create_kv4_hyp", "wh_context_destroy", "wh_context_bind", "wh_context_set_flags", "wh_context_set_encoder_i8", "wh_context_set_audio_ctx", "wh_context_synchronize", "wh_context_memory",
+    "wh_context_create", "wh_context_create_hyp", "wh_context_create_kv8", "wh_context_create_kv8_hyp", "wh_context_create_kv4", "wh_context_create_kv4_hyp", "wh_context_destroy", "wh_context_bind", "wh_context_set_flags", "wh_context_set_encoder_i8", "wh_context_set_decoder_w8", "wh_context_set_audio_ctx", "wh_context_synchronize", "wh_context_memory",
     "wh_buffer_alloc", "wh_buffer_free", "wh_buffer_upload", "wh_buffer_upload_async", "wh_buffer_download",
     "wh_mel_spectrogram", "wh_encode", "wh_encode_windows", "wh_decode", "wh_sample_best", "wh_beam_candidates", "wh_reorder_self_cache", "wh_beam_window_start", "wh_beam_window_continue", "wh_beam_window_status", "wh_beam_window_records", "wh_decode_greedy", "wh_decode_window_start", "wh_decode_window_finish", "wh_decode_window_continue", "wh_decode_window_fetch", "wh_decode_window_start_ragged", "wh_decode_window_ready", "wh_mel_spectrogram_window", "wh_mel_spectrogram_batch", "wh_profile_enable", "wh_profile_read", "wh_debug_read", "wh_debug_step_captures", "wh_debug_probe", "wh_debug_set_tuning", "wh_debug_set_option", "wh_debug_get_option",
     "wh_op_mul_mat", "wh_op_mul_mat_gelu", "wh_op_layer_norm", "wh_op_flash_attention", "wh_op_soft_max", "wh_op_decoder_attention", "wh_op_decoder_cross_attention",
@@ -68,6 +68,7 @@ EXPORTS = [
     "wh_op_gemm_encoder", "wh_op_mel_to_conv_input",
     "wh_op_quantize_kv", "wh_op_decoder_cross_attention_f8", "wh_op_quantize_cross_kv_i4", "wh_op_decoder_cross_attention_i4",
     "wh_op_quantize_rows_i8", "wh_op_layer_norm_i8", "wh_op_gemm_encoder_i8",
+    "wh_op_gemv_w8",
     "wh_context_set_alternatives", "wh_decode_window_alternatives", "wh_op_top_logprobs",
     "wh_context_set_nucleus", "wh_op_nucleus_logits",
     "wh_context_set_constraint", "wh_op_constraint_mask", "wh_op_constraint_apply",
@@ -165,6 +166,14 @@ def op_gemm_encoder_i8(scale_a, scale_w, stream=None, **fields):
     return wide.value
 
 
+def op_gemv_w8(M, N, K, w, scale_w, epi=0, pro=0, a=None, ln=(None, None, None), bias=None, res=None, out32=None, out16=None, q=None, kc=None, vc=None, heads=0,
+               text_ctx=0, n_past=0, n_past_dev=None, scale=1.0, stream=None):
+    """wh_op_gemv_w8: gemvW8 alone on device addresses (ints or c_void_p; None = absent). w int8 [N][K], scale_w FP32 [N]; pro 0: a FP16 [M][K], pro 1: ln =
+    (lnX, lnW, lnB); epi 0: out32 (+ bias, res), 1: out16 and bias, 2: q, kc, vc, bias, heads, text_ctx and n_past or n_past_dev."""
+    check(lib().wh_op_gemv_w8(stream, M, N, K, epi, pro, w, scale_w, a, ln[0], ln[1], ln[2], bias, res, out32, out16, q, kc, vc, heads, text_ctx, n_past, n_past_dev,
+                              C.c_float(float(scale))))
+
+
 class TokenScoreC(C.Structure):
     """wh_token_score: the score of a given token under a row of logits (include/whisper_hip.h)."""
     _fields_ = [("logprob", C.c_float), ("bestLogprob", C.c_float), ("best", C.c_int32), ("rank", C.c_int32)]
@@ -250,6 +259,7 @@ def lib():
         L.wh_context_set_flags.argtypes = [vp, C.c_uint32, i32]
         L.wh_context_set_audio_ctx.argtypes = [vp, i32]
         L.wh_context_set_encoder_i8.argtypes = [vp, i32]
+        L.wh_context_set_decoder_w8.argtypes = [vp, i32]
         L.wh_context_memory.argtypes = [vp, C.POINTER(i64)]
         L.wh_context_synchronize.argtypes = [vp]
         L.wh_buffer_upload_async.argtypes = [vp, vp, vp, i64]
@@ -346,6 +356,7 @@ def lib():
         L.wh_op_quantize_rows_i8.argtypes = [vp, vp, i64, vp, vp, i32, i32]
         L.wh_op_layer_norm_i8.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32]
         L.wh_op_gemm_encoder_i8.argtypes = [vp, C.POINTER(GemmEncoderArgsC), vp, vp, C.POINTER(C.c_int32)]
+        L.wh_op_gemv_w8.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, C.c_float]
         L.wh_op_mel_to_conv_input.argtypes = [vp, vp, i64, i64, vp, vp, vp, i64, i32, i32, i32]
         L.wh_context_set_alternatives.argtypes = [vp, i32]
         L.wh_decode_window_alternatives.argtypes = [vp, i32, i32, vp]
@@ -892,6 +903,10 @@ class HipContext:
     def set_encoder_i8(self, on: bool = True):
         """wh_context_set_encoder_i8: the encoder's Q/K/V, attention-out and MLP products as int8 x int8 -> int32 with a scale per row (off unless set)."""
         check(lib().wh_context_set_encoder_i8(self.handle, 1 if on else 0))
+
+    def set_decoder_w8(self, on: bool = True):
+        """wh_context_set_decoder_w8: single-token decode steps of up to 32 rows stream int8 copies of the decoder's weights through gemvW8 (off unless set)."""
+        check(lib().wh_context_set_decoder_w8(self.handle, 1 if on else 0))
 
     def step_captures(self) -> int:
         """Decode-step graphs this context has captured since it was created (wh_debug_step_captures)."""

@@ -95,6 +95,62 @@ namespace wh
 		m->i8Weights = a;
 		return 0;
 	}
+
+	// The int8 copies of the decoder's weights (wh_context_set_decoder_w8; the list and the added bytes: runtime.h), as bytes, then one FP32 scale per output row of
+	// each, quantized by quantizeRowsI8 from the FP16 arena. Once per model, under the model's lock; the call returns when the copies are complete.
+	int ensureDecoderW8Weights( wh_model* m )
+	{
+		std::lock_guard<std::mutex> lock( m->w8Mutex );
+		if( m->w8Weights.base ) return 0;
+		const int64_t d = m->hp.n_text_state, nv = m->hp.n_vocab;
+		const int nl = m->hp.n_text_layer;
+		std::vector<wh_model::DecLayerW8> layers( (size_t)nl );
+		int64_t bytes = 0, scales = 0;
+		for( wh_model::DecLayerW8& l : layers )
+		{
+			l.wqkv = bytes; bytes += 3 * d * d;
+			l.wo = bytes; bytes += d * d;
+			l.wco = bytes; bytes += d * d;
+			l.w1 = bytes; bytes += 4 * d * d;
+			l.w2 = bytes; bytes += 4 * d * d;
+			l.sqkv = scales; scales += 3 * d;
+			l.so = scales; scales += d;
+			l.sco = scales; scales += d;
+			l.s1 = scales; scales += 4 * d;
+			l.s2 = scales; scales += d;
+		}
+		const int64_t te = bytes, teScale = scales;
+		bytes += nv * d;	   // d is a multiple of 128: every matrix and the scales behind them stay 16-byte aligned
+		scales += nv;
+		Allocation a;
+		WH_HIP( guardedAlloc( a, bytes + scales * 4, 0, "int8 decoder weights", nullptr ) );
+		int8_t* const q = (int8_t*)a.body;
+		float* const s = (float*)( (uint8_t*)a.body + bytes );
+		int rc = 0;
+		for( int il = 0; il < nl && !rc; il++ )
+		{
+			const DecLayer& e = m->L.dec[ il ];
+			const wh_model::DecLayerW8& l = layers[ (size_t)il ];
+			rc = rc ? rc : launchQuantizeRowsI8( m->at<f16>( e.wqkv ), d, q + l.wqkv, s + l.sqkv, (int)( 3 * d ), (int)d, nullptr );
+			rc = rc ? rc : launchQuantizeRowsI8( m->at<f16>( e.wo ), d, q + l.wo, s + l.so, (int)d, (int)d, nullptr );
+			rc = rc ? rc : launchQuantizeRowsI8( m->at<f16>( e.wco ), d, q + l.wco, s + l.sco, (int)d, (int)d, nullptr );
+			rc = rc ? rc : launchQuantizeRowsI8( m->at<f16>( e.w1 ), d, q + l.w1, s + l.s1, (int)( 4 * d ), (int)d, nullptr );
+			rc = rc ? rc : launchQuantizeRowsI8( m->at<f16>( e.w2 ), 4 * d, q + l.w2, s + l.s2, (int)d, (int)( 4 * d ), nullptr );
+		}
+		rc = rc ? rc : launchQuantizeRowsI8( m->at<f16>( m->L.te ), d, q + te, s + teScale, (int)nv, (int)d, nullptr );
+		const hipError_t e = hipStreamSynchronize( nullptr );
+		if( rc || e != hipSuccess )
+		{
+			(void)guardedFree( a );
+			return rc ? rc : hipFail( e, "quantizeRowsI8(decoder weights)", __FILE__, __LINE__ );
+		}
+		m->w8ScalesAt = bytes;
+		m->w8Te = te;
+		m->w8TeScale = teScale;
+		m->w8Layers = std::move( layers );
+		m->w8Weights = a;
+		return 0;
+	}
 }
 namespace
 {
@@ -418,6 +474,11 @@ int wh_context_set_flags( wh_context* c, uint32_t flags, int parityThreads )
 		setError( "context_set_flags: the parity modes restate the reference's FP16 products and are not available while the INT8 encoder products are on" );
 		return WH_E_INVALIDARG;
 	}
+	if( c->decW8 && ( flags & ( WH_FLAG_PARITY_EXACT | WH_FLAG_PARITY_PV ) ) )
+	{
+		setError( "context_set_flags: the parity modes restate the reference's FP16 products and are not available while the INT8 decoder weights are on" );
+		return WH_E_INVALIDARG;
+	}
 	WH_CHECK( filtersAllowFlags( c, flags ) );
 	WH_CHECK( alternativesAllowFlags( c, flags ) );
 	c->flags = flags;
@@ -451,6 +512,34 @@ int wh_context_set_encoder_i8( wh_context* c, int on )
 	if( !c->xqScale ) WH_CHECK( c->alloc( c->xqScale, rowsE, wh_context::DONT_CARE, "xqScale" ) );
 	if( !c->hqScale ) WH_CHECK( c->alloc( c->hqScale, rowsE, wh_context::DONT_CARE, "hqScale" ) );
 	c->encI8 = true;
+	return 0;
+}
+
+int wh_context_set_decoder_w8( wh_context* c, int on )
+{
+	if( !c ) return WH_E_INVALIDARG;
+	const bool want = on != 0;
+	if( want )
+	{
+		const wh_hparams& hp = c->m->hp;
+		if( c->flags & ( WH_FLAG_PARITY_EXACT | WH_FLAG_PARITY_PV ) )
+		{
+			setError( "context_set_decoder_w8: the parity modes restate the reference's FP16 products and are not available together with the INT8 decoder weights" );
+			return WH_E_INVALIDARG;
+		}
+		if( ( hp.n_text_state % 128 ) != 0 || 4 * hp.n_text_state > 5120 )
+		{
+			setError( "context_set_decoder_w8: the INT8 decoder weights need n_text_state to be a multiple of 128, at most 1280" );
+			return WH_E_INVALIDARG;
+		}
+	}
+	if( want == c->decW8 ) return 0;
+	WH_BIND( c->m );
+	if( want ) WH_CHECK( ensureDecoderW8Weights( c->m ) );
+	// a captured step holds the launches of the setting it was captured under: void, as for another audio_ctx
+	WH_HIP( hipStreamSynchronize( c->stream ) );
+	c->destroyStepGraphs();
+	c->decW8 = want;
 	return 0;
 }
 

@@ -49,11 +49,16 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 	// (from 9 sequences up: with fewer, one workgroup per (head, sequence) leaves the 6 d^2 bytes of QKV weights to H CUs at
 	// ~25 GB/s each -- 15.7 us per layer at one sequence -- and the separate gemv + attention launches are faster: 74.3 vs 86.6 ms
 	// per window at batch 1, 100.4 vs 101.9 at 7)
-	const bool fuseSelf = nTokens == 1 && d <= 1280 && hp.n_text_ctx <= 512 && parity == 0 && batch > 8 && batch <= g_opt.selfFuseMaxRows && ( g_tuning & TUNE_FUSE_SELF_BLOCK );
+	// wh_context_set_decoder_w8: the products of a single-token step of up to GEMV_W8_STEP_ROWS rows read the model's int8 weight copies through gemvW8
+	// (the limit and the measurement behind it: kernels.h); selfBlockDec and decode1.hip read FP16 weights and are not taken
+	const bool w8 = c->decW8 && gemv && nTokens == 1 && M <= GEMV_W8_STEP_ROWS;
+	const wh_model::DecLayerW8* const w8Layers = w8 ? m->w8Layers.data() : nullptr;
+	const bool fuseSelf = !w8 && nTokens == 1 && d <= 1280 && hp.n_text_ctx <= 512 && parity == 0 && batch > 8 && batch <= g_opt.selfFuseMaxRows && ( g_tuning & TUNE_FUSE_SELF_BLOCK );
 	// decode steps: the cross-attention kernel normalises the residual row and projects its own head's query
 	const bool fuseCrossQ = nTokens == 1 && d <= 1280 && parity <= 8 && ( g_tuning & TUNE_FUSE_CROSS_Q );
 
-	auto product = [ & ]( GemmArgs& g, const float* lnW, const float* lnB ) -> int
+	// w8At / w8ScaleAt: the int8 copy of g.W and its row scales in the model's w8Weights (-1: the product has none and stays FP16, e.g. the cross-attention query)
+	auto product = [ & ]( GemmArgs& g, const float* lnW, const float* lnB, int64_t w8At = -1, int64_t w8ScaleAt = -1 ) -> int
 	{
 		g.nPastDev = nPastDev;
 		if( !gemv ) return gemmP( c, g, true, true );
@@ -61,6 +66,13 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 		if( lnW && fuseLn )
 		{
 			g.lnX = c->dx; g.lnW = lnW; g.lnB = lnB;
+		}
+		if( w8 && w8At >= 0 )
+		{
+			GemvW8Args a8 = {};
+			a8.g = g; a8.W8 = m->w8At( w8At ); a8.sw = m->w8Scale( w8ScaleAt );
+			const double bytes8 = 1.0 * g.N * g.K + 4.0 * g.N + 2.0 * g.M * g.K + ( g.out32 ? 4.0 : 2.0 ) * g.M * g.N;
+			return profiled( c, KC_GEMV, 2.0 * g.M * g.N * g.K, bytes8, [ & ]() { return launchGemvW8( a8, st ); } );
 		}
 		const double flops = 2.0 * g.M * g.N * g.K;
 		const double bytes = 2.0 * g.N * g.K + 2.0 * g.M * g.K + ( g.out32 ? 4.0 : 2.0 ) * g.M * g.N;
@@ -72,9 +84,10 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 
 	// ---- single-token steps of up to 4 sequences (one stream through iContext::runFull): decode1.hip. Eight launches per layer,
 	// each of ~256 workgroups, each pulling the weights of the next one into the L2 of the XCD that will read them.
-	// (FP8 and INT4 cross-attention caches take the batch path at every batch size: crossScores / crossSoftmaxPV read FP16 rows)
+	// (FP8 and INT4 cross-attention caches take the batch path at every batch size: crossScores / crossSoftmaxPV read FP16 rows; so does a context with INT8
+	// decoder weights: gemvSmall reads FP16 weights)
 	const bool small = nTokens == 1 && batch <= SMALL_MAX_ROWS && c->hyp == 1 && parity == 0 && d <= 1280 && ( d % 64 ) == 0 && c->T <= 1536 &&
-		!( c->flags & WH_FLAG_DEBUG_CAPTURE ) && ( g_tuning & TUNE_DECODE_SMALL ) && !c->kv8 && !c->kv4;
+		!( c->flags & WH_FLAG_DEBUG_CAPTURE ) && ( g_tuning & TUNE_DECODE_SMALL ) && !c->kv8 && !c->kv4 && !c->decW8;
 	if( small )
 	{
 #ifdef WH_PROBES
@@ -204,6 +217,8 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 		const DecLayer& e = L.dec[ il ];
 		const int64_t selfLayer = (int64_t)il * c->maxSeq * hp.n_text_ctx * d;
 		const int64_t crossLayer = (int64_t)il * c->maxBatch * c->T * d;
+		const wh_model::DecLayerW8 noW8 = { -1, -1, -1, -1, -1, -1, -1, -1, -1, -1 };
+		const wh_model::DecLayerW8& e8 = w8 ? w8Layers[ il ] : noW8;
 		// self-attention
 		if( fuseSelf )
 		{
@@ -233,7 +248,7 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 			g.scale = kqScale;
 			g.q = c->dq; g.k = c->selfK + selfLayer; g.v = c->selfV + selfLayer;
 			g.H = H; g.nTok = nTokens; g.nPast = nPast; g.textCtx = hp.n_text_ctx;
-			WH_CHECK( product( g, m->at<float>( e.ln1w ), m->at<float>( e.ln1b ) ) );
+			WH_CHECK( product( g, m->at<float>( e.ln1w ), m->at<float>( e.ln1b ), e8.wqkv, e8.sqkv ) );
 		}
 		{
 			DecAttnArgs a = {};
@@ -252,7 +267,7 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 		{
 			GemmArgs g = plainGemm( c->dattn, m->at<f16>( e.wo ), M, d, d );
 			g.epi = EPI_F32; g.bias = m->at<float>( e.bo ); g.res = c->dx; g.out32 = c->dx;
-			WH_CHECK( product( g, nullptr, nullptr ) );
+			WH_CHECK( product( g, nullptr, nullptr, e8.wo, e8.so ) );
 		}
 		// cross-attention
 		if( !fuseCrossQ )
@@ -314,19 +329,19 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 		{
 			GemmArgs g = plainGemm( c->dattn, m->at<f16>( e.wco ), M, d, d );
 			g.epi = EPI_F32; g.bias = m->at<float>( e.bco ); g.res = c->dx; g.out32 = c->dx;
-			WH_CHECK( product( g, nullptr, nullptr ) );
+			WH_CHECK( product( g, nullptr, nullptr, e8.wco, e8.sco ) );
 		}
 		// MLP
 		if( !fuseLn ) WH_CHECK( lnP( c, c->dx, m->at<float>( e.ln2w ), m->at<float>( e.ln2b ), c->dxn, M, d, true ) );
 		{
 			GemmArgs g = plainGemm( c->dxn, m->at<f16>( e.w1 ), M, 4 * d, d );
 			g.epi = EPI_F16_GELU; g.bias = m->at<float>( e.b1 ); g.out16 = c->dh;
-			WH_CHECK( product( g, m->at<float>( e.ln2w ), m->at<float>( e.ln2b ) ) );
+			WH_CHECK( product( g, m->at<float>( e.ln2w ), m->at<float>( e.ln2b ), e8.w1, e8.s1 ) );
 		}
 		{
 			GemmArgs g = plainGemm( c->dh, m->at<f16>( e.w2 ), M, d, 4 * d );
 			g.epi = EPI_F32; g.bias = m->at<float>( e.b2 ); g.res = c->dx; g.out32 = c->dx;
-			WH_CHECK( product( g, nullptr, nullptr ) );
+			WH_CHECK( product( g, nullptr, nullptr, e8.w2, e8.s2 ) );
 		}
 	}
 	// final norm + logits for the LAST token of every sequence only (the reference computes all rows, whisper.cpp:1840,
@@ -351,7 +366,7 @@ int wh::decodeGraph( wh_context* c, int batch, int nTokens, int nPast, bool devS
 			WH_CHECK( gemmP( c, g, true, true ) );
 		}
 		else
-			WH_CHECK( product( g, nullptr, nullptr ) );
+			WH_CHECK( product( g, nullptr, nullptr, w8 ? m->w8Te : -1, w8 ? m->w8TeScale : -1 ) );
 	}
 	return filterLogits( c, batch );
 }

@@ -94,104 +94,8 @@ namespace wh
 		// (norm.hlsl + fmaRepeat1.hlsl in the reference) runs as a prologue: each workgroup normalises the M rows into LDS
 		// (FP16, the rounding the product applies anyway) -- M*K*4 bytes of L2 reads per workgroup instead of a launch.
 		constexpr int GV_UNROLL_MAX = 16;
-		constexpr int GV_MAXK_LN = 1280;
-		constexpr int GV_XS_STRIDE = GV_MAXK_LN + 8;
 
-		// LayerNorm + affine of up to RB rows by the WHOLE workgroup (NWV waves): thread t owns the float4 columns t and
-		// t + 64 * NWV of every row, so a row is one coalesced pass and all RB rows are in flight at once; the two reductions go
-		// wave-shuffle -> LDS -> every thread. Same formula as layerNormRows (two-pass FP32, eps 1e-5, w*y + b, FP16 result);
-		// the summation tree differs, so rows are not bit-identical with the one-wave-per-row version.
-		template<int RB, int MAXC, int NWV, class Store>
-		__device__ __forceinline__ void layerNormBlock( const float* __restrict__ x, int nRows, const float* __restrict__ w, const float* __restrict__ b,
-			int d, int tid, float ( *shA )[ RB ], float ( *shB )[ RB ], Store&& store )
-		{
-			constexpr int NTH = NWV * 64;
-			const int lane = tid & 63, wave = tid >> 6;
-			const int nv = d >> 2;
-			f32x4 v[ RB ][ MAXC ], wv[ MAXC ], bv[ MAXC ];
-	#pragma unroll
-			for( int i = 0; i < MAXC; i++ )
-			{
-				const int cv = tid + i * NTH;
-				const int cc = ( cv < nv ? cv : nv - 1 ) * 4;
-				wv[ i ] = *(const f32x4*)( w + cc );
-				bv[ i ] = *(const f32x4*)( b + cc );
-	#pragma unroll
-				for( int r = 0; r < RB; r++ )
-				{
-					const int rr = r < nRows ? r : ( nRows > 0 ? nRows - 1 : 0 );
-					v[ r ][ i ] = *(const f32x4*)( x + (long long)rr * d + cc );
-				}
-			}
-			const float invD = 1.0f / (float)d;
-			float s[ RB ];
-	#pragma unroll
-			for( int r = 0; r < RB; r++ )
-			{
-				float t = 0.0f;
-	#pragma unroll
-				for( int i = 0; i < MAXC; i++ )
-					if( tid + i * NTH < nv ) t += ( v[ r ][ i ][ 0 ] + v[ r ][ i ][ 1 ] ) + ( v[ r ][ i ][ 2 ] + v[ r ][ i ][ 3 ] );
-				s[ r ] = t;
-			}
-	#pragma unroll
-			for( int o = 32; o > 0; o >>= 1 )
-	#pragma unroll
-				for( int r = 0; r < RB; r++ ) s[ r ] += __shfl_xor( s[ r ], o, 64 );
-			if( lane == 0 )
-	#pragma unroll
-				for( int r = 0; r < RB; r++ ) shA[ wave ][ r ] = s[ r ];
-			__syncthreads();
-	#pragma unroll
-			for( int r = 0; r < RB; r++ )
-			{
-				float t = shA[ 0 ][ r ];
-	#pragma unroll
-				for( int ww = 1; ww < NWV; ww++ ) t += shA[ ww ][ r ];
-				const float mean = t * invD;
-				float q = 0.0f;
-	#pragma unroll
-				for( int i = 0; i < MAXC; i++ )
-				{
-	#pragma unroll
-					for( int e = 0; e < 4; e++ ) v[ r ][ i ][ e ] -= mean;
-					if( tid + i * NTH < nv )
-	#pragma unroll
-						for( int e = 0; e < 4; e++ ) q = fmaf( v[ r ][ i ][ e ], v[ r ][ i ][ e ], q );
-				}
-				s[ r ] = q;
-			}
-	#pragma unroll
-			for( int o = 32; o > 0; o >>= 1 )
-	#pragma unroll
-				for( int r = 0; r < RB; r++ ) s[ r ] += __shfl_xor( s[ r ], o, 64 );
-			if( lane == 0 )
-	#pragma unroll
-				for( int r = 0; r < RB; r++ ) shB[ wave ][ r ] = s[ r ];
-			__syncthreads();
-	#pragma unroll
-			for( int r = 0; r < RB; r++ )
-			{
-				if( r >= nRows ) continue;
-				float t = shB[ 0 ][ r ];
-	#pragma unroll
-				for( int ww = 1; ww < NWV; ww++ ) t += shB[ ww ][ r ];
-				const float rstd = 1.0f / sqrtf( t * invD + 1e-5f );
-	#pragma unroll
-				for( int i = 0; i < MAXC; i++ )
-				{
-					const int cv = tid + i * NTH;
-					if( cv < nv )
-					{
-						f16x4 hv;
-	#pragma unroll
-						for( int e = 0; e < 4; e++ ) hv[ e ] = (f16)__fadd_rn( __fmul_rn( __fmul_rn( v[ r ][ i ][ e ], rstd ), wv[ i ][ e ] ), bv[ i ][ e ] );
-						store( r, cv * 4, hv );
-					}
-				}
-			}
-		}
-
+		// (GV_MAXK_LN, GV_XS_STRIDE and layerNormBlock, the block-wide prologue, are in gemm_device.h: gemvW8 of gemm_decode_w8.hip takes them too)
 		// PRO = 0: A rows are FP16 in global memory; 1: fused LayerNorm prologue, a wave per pair of rows (up to 16 rows);
 		// 2: fused LayerNorm prologue by the whole workgroup, 16 rows at a time (17 .. 32 rows).
 		// ROWS = weight rows per workgroup: 16 fills the MFMA; 4 (rows replicated across the operand's 16 row slots) gives 4x

@@ -44,6 +44,105 @@ namespace wh
 		}
 #define WH_BAR() asm volatile( "s_barrier" ::: "memory" )
 
+		// The fused LayerNorm prologue of the decode-step products (gemvFused, gemvW8): rows of up to GV_MAXK_LN columns, normalised into LDS rows GV_XS_STRIDE halves apart
+		constexpr int GV_MAXK_LN = 1280;
+		constexpr int GV_XS_STRIDE = GV_MAXK_LN + 8;
+
+		// LayerNorm + affine of up to RB rows by the WHOLE workgroup (NWV waves): thread t owns the float4 columns t and
+		// t + 64 * NWV of every row, so a row is one coalesced pass and all RB rows are in flight at once; the two reductions go
+		// wave-shuffle -> LDS -> every thread. Same formula as layerNormRows (two-pass FP32, eps 1e-5, w*y + b, FP16 result);
+		// the summation tree differs, so rows are not bit-identical with the one-wave-per-row version.
+		template<int RB, int MAXC, int NWV, class Store>
+		__device__ __forceinline__ void layerNormBlock( const float* __restrict__ x, int nRows, const float* __restrict__ w, const float* __restrict__ b,
+			int d, int tid, float ( *shA )[ RB ], float ( *shB )[ RB ], Store&& store )
+		{
+			constexpr int NTH = NWV * 64;
+			const int lane = tid & 63, wave = tid >> 6;
+			const int nv = d >> 2;
+			f32x4 v[ RB ][ MAXC ], wv[ MAXC ], bv[ MAXC ];
+	#pragma unroll
+			for( int i = 0; i < MAXC; i++ )
+			{
+				const int cv = tid + i * NTH;
+				const int cc = ( cv < nv ? cv : nv - 1 ) * 4;
+				wv[ i ] = *(const f32x4*)( w + cc );
+				bv[ i ] = *(const f32x4*)( b + cc );
+	#pragma unroll
+				for( int r = 0; r < RB; r++ )
+				{
+					const int rr = r < nRows ? r : ( nRows > 0 ? nRows - 1 : 0 );
+					v[ r ][ i ] = *(const f32x4*)( x + (long long)rr * d + cc );
+				}
+			}
+			const float invD = 1.0f / (float)d;
+			float s[ RB ];
+	#pragma unroll
+			for( int r = 0; r < RB; r++ )
+			{
+				float t = 0.0f;
+	#pragma unroll
+				for( int i = 0; i < MAXC; i++ )
+					if( tid + i * NTH < nv ) t += ( v[ r ][ i ][ 0 ] + v[ r ][ i ][ 1 ] ) + ( v[ r ][ i ][ 2 ] + v[ r ][ i ][ 3 ] );
+				s[ r ] = t;
+			}
+	#pragma unroll
+			for( int o = 32; o > 0; o >>= 1 )
+	#pragma unroll
+				for( int r = 0; r < RB; r++ ) s[ r ] += __shfl_xor( s[ r ], o, 64 );
+			if( lane == 0 )
+	#pragma unroll
+				for( int r = 0; r < RB; r++ ) shA[ wave ][ r ] = s[ r ];
+			__syncthreads();
+	#pragma unroll
+			for( int r = 0; r < RB; r++ )
+			{
+				float t = shA[ 0 ][ r ];
+	#pragma unroll
+				for( int ww = 1; ww < NWV; ww++ ) t += shA[ ww ][ r ];
+				const float mean = t * invD;
+				float q = 0.0f;
+	#pragma unroll
+				for( int i = 0; i < MAXC; i++ )
+				{
+	#pragma unroll
+					for( int e = 0; e < 4; e++ ) v[ r ][ i ][ e ] -= mean;
+					if( tid + i * NTH < nv )
+	#pragma unroll
+						for( int e = 0; e < 4; e++ ) q = fmaf( v[ r ][ i ][ e ], v[ r ][ i ][ e ], q );
+				}
+				s[ r ] = q;
+			}
+	#pragma unroll
+			for( int o = 32; o > 0; o >>= 1 )
+	#pragma unroll
+				for( int r = 0; r < RB; r++ ) s[ r ] += __shfl_xor( s[ r ], o, 64 );
+			if( lane == 0 )
+	#pragma unroll
+				for( int r = 0; r < RB; r++ ) shB[ wave ][ r ] = s[ r ];
+			__syncthreads();
+	#pragma unroll
+			for( int r = 0; r < RB; r++ )
+			{
+				if( r >= nRows ) continue;
+				float t = shB[ 0 ][ r ];
+	#pragma unroll
+				for( int ww = 1; ww < NWV; ww++ ) t += shB[ ww ][ r ];
+				const float rstd = 1.0f / sqrtf( t * invD + 1e-5f );
+	#pragma unroll
+				for( int i = 0; i < MAXC; i++ )
+				{
+					const int cv = tid + i * NTH;
+					if( cv < nv )
+					{
+						f16x4 hv;
+	#pragma unroll
+						for( int e = 0; e < 4; e++ ) hv[ e ] = (f16)__fadd_rn( __fmul_rn( __fmul_rn( v[ r ][ i ][ e ], rstd ), wv[ i ][ e ] ), bv[ i ][ e ] );
+						store( r, cv * 4, hv );
+					}
+				}
+			}
+		}
+
 		// Tile epilogue shared by the staging variants: D[row][col], col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5).
 		// Same arithmetic per element as epilogueOne, organised for the memory system: the row-dependent index math (the
 		// divisions by T) is done once per row instead of once per element, and everything the epilogue READS (residual,

@@ -184,6 +184,26 @@ namespace wh
 	int launchGemmI8( const GemmI8Args& a, hipStream_t stream );
 
 	// ---------------------------------------------------------------------------------------------------------------
+	// INT8 decoder weights (gemm_decode_w8.hip; DESIGN.md section 7 "INT8 decoder weights"): the decode-step product of 1 .. GEMV_W8_MAX_ROWS FP16 activation rows
+	// against int8 weight rows in the format above, out[m][n] = epilogue( ( sum_k x[m][k] * (float)W8[n][k] ) * sw[n] ): the activations are NOT quantized, every
+	// product x * q is exact on the FP16 matrix instruction, the sum is FP32. Of g: M, N, K (a multiple of 128, at most 5120), A / lda / Mb / aBatchStride or the
+	// LayerNorm prologue (lnX, lnW, lnB: up to 32 rows of up to 1280 columns), epi (EPI_F32, EPI_F16_GELU or EPI_QKV_DEC) and the epilogue's fields; g.W is not read.
+	// ---------------------------------------------------------------------------------------------------------------
+	struct GemvW8Args
+	{
+		GemmArgs g;
+		const int8_t* W8;	  // [N][K]
+		const float* sw;	  // [N]
+		int vecEpi;			  // set by the launcher: four consecutive output columns leave as one 16-byte (FP32) or 8-byte (FP16) store
+	};
+	constexpr int GEMV_W8_MAX_ROWS = 128;
+	// what a context with the setting gives to gemvW8: steps of up to this many rows. Measured (profiles/decoder_w8_probe.json): a whole step takes 0.915 of the
+	// FP16 time at 8 sequences and 0.95 at 32; at 64 and 128 rows the vocabulary product is 1.9 .. 2.1 times and the MLP down-projection 1.1 .. 1.4 times SLOWER than
+	// the FP16 path's LDS-staged kernels (gemmDecTile), so those steps keep the FP16 weights
+	constexpr int GEMV_W8_STEP_ROWS = 32;
+	int launchGemvW8( const GemvW8Args& a, hipStream_t stream );
+
+	// ---------------------------------------------------------------------------------------------------------------
 	// elementwise / normalisation (elementwise.hip)
 	// ---------------------------------------------------------------------------------------------------------------
 	// out16[row] = fp16( norm(x[row]) * w + b ); rows of length d (multiple of 4, <= 2048). norm.hlsl + fmaRepeat1.hlsl

@@ -168,6 +168,7 @@ void wh_model_destroy( wh_model* m )
 	(void)bindDevice( m );
 	freeStaging( m );
 	if( m->i8Weights.base ) (void)guardedFree( m->i8Weights );	   // wh_context_set_encoder_i8's copies: the contexts that read them are gone
+	if( m->w8Weights.base ) (void)guardedFree( m->w8Weights );	   // wh_context_set_decoder_w8's copies
 	if( m->ownsArena && m->arena ) (void)hipFree( m->arena );
 	delete m;
 }

@@ -609,6 +609,50 @@ int wh_op_gemv_small( void* stream, int M, int N, int K, int epi, int pro, const
 	return launchGemvSmall( a, (hipStream_t)stream );
 }
 
+// gemvW8 alone (gemm_decode_w8.hip): wh_op_gemv_small's arguments with the int8 weight rows and their scales in the weight's place. The launcher checks the shapes,
+// the alignment and the epilogue's operands; a position outside the cache is checked here.
+int wh_op_gemv_w8( void* stream, int M, int N, int K, int epi, int pro, const void* wI8, const float* scaleW, const void* aF16, const float* lnX, const float* lnW,
+	const float* lnB, const float* bias, const float* residual, float* out32, void* out16, void* qF16, void* kCache, void* vCache, int heads, int textCtx, int nPast,
+	const int32_t* nPastDev, float scale )
+{
+	if( !wI8 || !scaleW || ( pro != 0 && pro != 1 ) || ( pro == 0 && !aF16 ) || ( pro == 1 && ( !lnX || !lnW || !lnB ) ) )
+	{
+		setError( "gemv_w8 (gemvW8): null operand, or a prologue other than 0 (FP16 rows) or 1 (LayerNorm)" );
+		return WH_E_INVALIDARG;
+	}
+	GemvW8Args a = {};
+	a.g = plainGemm( pro == 0 ? (const f16*)aF16 : nullptr, nullptr, M, N, K );
+	a.W8 = (const int8_t*)wI8; a.sw = scaleW;
+	if( pro == 1 ) { a.g.lnX = lnX; a.g.lnW = lnW; a.g.lnB = lnB; }
+	a.g.bias = bias;
+	if( epi == 0 )
+	{
+		a.g.epi = EPI_F32; a.g.res = residual; a.g.out32 = out32;
+	}
+	else if( epi == 1 )
+	{
+		a.g.epi = EPI_F16_GELU; a.g.out16 = (f16*)out16;
+	}
+	else if( epi == 2 )
+	{
+		// every position written must lie inside the cache: a scalar is checked here, a device array is the caller's to keep in [0, textCtx)
+		if( heads < 1 || K != heads * HEAD_DIM || textCtx < 1 || ( !nPastDev && ( nPast < 0 || nPast >= textCtx ) ) )
+		{
+			setError( "gemv_w8 (gemvW8): the QKV epilogue needs N = 3 K = 3 * 64 * heads and 0 <= nPast < textCtx" );
+			return WH_E_INVALIDARG;
+		}
+		a.g.epi = EPI_QKV_DEC; a.g.scale = scale;
+		a.g.q = (f16*)qF16; a.g.k = (f16*)kCache; a.g.v = (f16*)vCache;
+		a.g.H = heads; a.g.nTok = 1; a.g.nPast = nPast; a.g.nPastDev = nPastDev; a.g.textCtx = textCtx;
+	}
+	else
+	{
+		setError( "gemv_w8 (gemvW8): epilogue 0 (FP32, bias, residual), 1 (FP16 GELU) or 2 (decoder Q/K/V)" );
+		return WH_E_INVALIDARG;
+	}
+	return launchGemvW8( a, (hipStream_t)stream );
+}
+
 int wh_op_cross_split( void* stream, const float* x, const float* lnW, const float* lnB, const void* qW, const float* qB, float qScale, const void* kCache,
 	const void* vCache, float* scores, float* splitMax, float* part, int sequences, int heads, int nKeys, int keyStride )
 {

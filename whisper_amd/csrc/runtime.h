@@ -100,6 +100,18 @@ struct wh_model
 	std::mutex i8Mutex;
 	const int8_t* i8At( int64_t off ) const { return (const int8_t*)i8Weights.body + off; }
 	const float* i8Scale( int64_t off ) const { return (const float*)( (const uint8_t*)i8Weights.body + i8ScalesAt ) + off; }
+	// wh_context_set_decoder_w8 (gemm_decode_w8.hip): int8 copies of the decoder's weight families that a decode step streams -- per layer Q/K/V [3d][d],
+	// self-attention out, cross-attention out, MLP up and MLP down, and once the token embedding [n_vocab][d] the vocabulary product reads -- with one FP32 scale
+	// per output row, made on the device by quantizeRowsI8 from the FP16 arena by the first context that turns the setting on and shared by the model's contexts.
+	// The FP16 weights stay (prompt passes, more than 128 rows, the cross-attention query inside the attention kernels). Added bytes: 13 d^2 + 40 d per layer and
+	// ( d + 4 ) n_vocab -- 380 MB on the medium model (d = 1024, 24 layers), half of what the FP16 copies of the same matrices take.
+	struct DecLayerW8 { int64_t wqkv, wo, wco, w1, w2, sqkv, so, sco, s1, s2; };
+	Allocation w8Weights = { nullptr, nullptr, 0, nullptr };
+	int64_t w8ScalesAt = 0, w8Te = 0, w8TeScale = 0;
+	std::vector<DecLayerW8> w8Layers;
+	std::mutex w8Mutex;
+	const int8_t* w8At( int64_t off ) const { return (const int8_t*)w8Weights.body + off; }
+	const float* w8Scale( int64_t off ) const { return (const float*)( (const uint8_t*)w8Weights.body + w8ScalesAt ) + off; }
 	std::vector<int32_t> alignHeads;	   // wh_model_set_alignment_heads: (layer, head) pairs, ascending; empty = every head of the upper half of the decoder
 	template<class T> T* at( int64_t off ) const { return (T*)( arena + off ); }
 	size_t expectedTensors() const { return 11 + 15 * (size_t)hp.n_audio_layer + 24 * (size_t)hp.n_text_layer; }
@@ -239,6 +251,9 @@ struct wh_context
 	bool encI8 = false;
 	int8_t *xq = nullptr, *hq = nullptr;
 	float *xqScale = nullptr, *hqScale = nullptr;
+	// wh_context_set_decoder_w8: single-token decode steps of up to GEMV_W8_STEP_ROWS rows run their Q/K/V, self-out, cross-out, MLP and vocabulary products on
+	// gemvW8 against the model's int8 copies, always on the batch path (decode1.hip reads FP16 weights). Everything else runs what it always ran.
+	bool decW8 = false;
 	// decoder activations
 	float *dx = nullptr, *logits = nullptr, *probs = nullptr;
 	f16 *dxn = nullptr, *dq = nullptr, *dattn = nullptr, *dh = nullptr;
@@ -483,6 +498,7 @@ namespace wh
 	int lnP( wh_context* c, const float* x, const float* w, const float* b, f16* out, int rows, int d, bool decoder = false );
 	GemmArgs plainGemm( const f16* A, const f16* W, int M, int N, int K );
 	int ensureEncoderI8Weights( wh_model* m );	   // context.hip: the model's int8 encoder weights, made once
+	int ensureDecoderW8Weights( wh_model* m );	   // context.hip: the model's int8 decoder weights, made once
 	int exactTables( wh_context* c );
 	int encodeExact( wh_context* c, const float* melDev, int batch, int64_t melLen, int64_t melStride, const int32_t* melOffsets, const wh_mel_window* wins );
 	int decodeExact( wh_context* c, int batch, int nTokens, int nPast );

@@ -33,6 +33,7 @@
 #include "batchCrossFp8.h"
 #include "batchCrossInt4.h"
 #include "batchEncoderI8.h"
+#include "batchDecoderW8.h"
 #include "optionRules.h"
 #include "decodeFallback.h"
 #include "languageDetect.h"
@@ -73,6 +74,8 @@ namespace Whisper
 	pfnBatchCreateKv4 g_batchCreateKv4 = nullptr;
 	// ... and to the INT8 encoder products of a group's context (batchEncoderI8.h)
 	pfnBatchSetEncoderI8 g_batchSetEncoderI8 = nullptr;
+	// ... and to the INT8 decoder weights of a group's context (batchDecoderW8.h)
+	pfnBatchSetDecoderW8 g_batchSetDecoderW8 = nullptr;
 
 	namespace
 	{
@@ -766,6 +769,7 @@ namespace Whisper
 			bool crossFp8 = false;	   // sBatchSetup::flags bit 2: the groups' contexts hold FP8 cross-attention caches (the one-window loader context stays as it is)
 			bool crossInt4 = false;	   // sBatchSetup::flags bit value 8: INT4 cross-attention caches instead (never with bit 2: createBatchRunner refuses the pair)
 			bool encoderI8 = false;	   // sBatchSetup::flags bit value 4: the groups' contexts run the encoder's products in INT8 (may be combined with bit 2)
+			bool decoderW8 = false;	   // sBatchSetup::flags bit value 16: the groups' contexts stream INT8 decoder weights in their single-token steps (combines with every other bit)
 			std::vector<Group> groups;
 			Shared shared;
 			// Whisper::setBatchDecodingFallback: off unless set. modesDirty: a run with the feature on left the groups' contexts in its modes
@@ -798,8 +802,9 @@ namespace Whisper
 			{
 				const int rc = crossInt4 ? g_batchCreateKv4( model->gpu, (int)maxSlots, nullptr, out ) :
 					crossFp8 ? g_batchCreateKv8( model->gpu, (int)maxSlots, nullptr, out ) : wh_context_create( model->gpu, (int)maxSlots, nullptr, out );
-				if( rc || !encoderI8 ) return rc;
-				const int rc8 = g_batchSetEncoderI8( *out, 1 );
+				if( rc ) return rc;
+				int rc8 = encoderI8 ? g_batchSetEncoderI8( *out, 1 ) : 0;
+				if( !rc8 && decoderW8 ) rc8 = g_batchSetDecoderW8( *out, 1 );
 				if( rc8 )
 				{
 					wh_context_destroy( *out );
@@ -887,6 +892,7 @@ namespace Whisper
 				if( setup && ( setup->flags & 2u ) ) crossFp8 = true;
 				if( setup && ( setup->flags & 4u ) ) encoderI8 = true;
 				if( setup && ( setup->flags & 8u ) ) crossInt4 = true;
+				if( setup && ( setup->flags & 16u ) ) decoderW8 = true;
 				if( const char* e = getenv( "WHISPER_BATCH_SLOTS" ) ) maxSlots = (uint32_t)std::max( 1, atoi( e ) );
 				if( const char* e = getenv( "WHISPER_BATCH_GROUPS" ) ) nGroups = (uint32_t)std::max( 1, atoi( e ) );
 				if( const char* e = getenv( "WHISPER_BATCH_CHUNK" ) ) chunk = atoi( e );
@@ -1090,6 +1096,7 @@ namespace Whisper
 		}
 		if( setup && ( setup->flags & 8u ) && !g_batchCreateKv4 ) return optionRules::notGiven( "createBatchRunner", "INT4 cross-attention caches" );
 		if( setup && ( setup->flags & 4u ) && !g_batchSetEncoderI8 ) return optionRules::notGiven( "createBatchRunner", "INT8 encoder products" );
+		if( setup && ( setup->flags & 16u ) && !g_batchSetDecoderW8 ) return optionRules::notGiven( "createBatchRunner", "INT8 decoder weights" );
 		*pp = new BatchRunner( lm, model, setup );
 		return S_OK;
 	}

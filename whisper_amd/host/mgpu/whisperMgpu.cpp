@@ -1,6 +1,6 @@
 // One process per GPU over the C ABI, no Python and no torch: the multi-GPU harness of the drop-in library.
 //
-//   whisper-mgpu -n 8 -m ggml-medium.bin -f recording.wav [-l en] [-o out.txt] [-timeout 300] [-job-timeout 0] [-slots 64] [-cross-fp8 | -cross-int4] [-encoder-int8] [-id file] [-job token]
+//   whisper-mgpu -n 8 -m ggml-medium.bin -f recording.wav [-l en] [-o out.txt] [-timeout 300] [-job-timeout 0] [-slots 64] [-cross-fp8 | -cross-int4] [-encoder-int8] [-decoder-int8] [-id file] [-job token]
 //   whisper-mgpu -n 8 -m ggml-medium.bin -per-recording -f a.wav -f b.wav ...   whole recordings, one stream each with the reference's sliding window (no words cut at 30 s)
 //   whisper-mgpu -n 8 -m ggml-medium.bin -split silence -f recording.wav        the chunks end at pauses instead of every 30 s (Whisper::splitAtPauses): no words cut either,
 //                                                                               and the chunks still run in lock step
@@ -45,6 +45,7 @@ namespace
 	{
 		int ranks = 1, slots = 64;
 		bool crossFp8 = false;	   // sBatchSetup::flags bit 2: FP8 cross-attention caches in every rank's runner
+		bool decoderInt8 = false;  // sBatchSetup::flags bit value 16: INT8 decoder weights in every rank's runner
 		bool crossInt4 = false;	   // sBatchSetup::flags bit value 8: INT4 cross-attention caches in every rank's runner (not with -cross-fp8)
 		bool encoderInt8 = false;  // sBatchSetup::flags bit value 4: INT8 encoder products in every rank's runner
 		double timeout = 300.0;		// deadline of the rendezvous and of every collective
@@ -150,7 +151,7 @@ namespace
 			while( true ) sleep( 1000 );
 	}
 
-	const char* const USAGE = "usage: whisper-mgpu -n ranks -m model.bin -f audio.wav [-l en] [-o out.txt] [-timeout seconds (rendezvous and collectives)] [-job-timeout seconds (whole job; default none)] [-slots n] [-id id-file] [-job token] [-split fixed|silence (where the chunks of the recording end: every 30 s, or at pauses)] [-per-recording -f more.wav ...] [-fallback (quality gates and temperature retries per window) [-tpi N] [-lpt N] [-et N] [-nth N]] [-sns (suppress the non-speech tokens)] [-cross-fp8 (FP8 cross-attention caches: half the cache memory per slot; accuracy on real checkpoints not measured)] [-encoder-int8 (the encoder's linear products in INT8 with a scale per row; accuracy on real checkpoints not measured)] [-cross-int4 (INT4 cross-attention caches: 36 bytes per key row instead of 128, not with -cross-fp8; accuracy on real checkpoints not measured)]\n";
+	const char* const USAGE = "usage: whisper-mgpu -n ranks -m model.bin -f audio.wav [-l en] [-o out.txt] [-timeout seconds (rendezvous and collectives)] [-job-timeout seconds (whole job; default none)] [-slots n] [-id id-file] [-job token] [-split fixed|silence (where the chunks of the recording end: every 30 s, or at pauses)] [-per-recording -f more.wav ...] [-fallback (quality gates and temperature retries per window) [-tpi N] [-lpt N] [-et N] [-nth N]] [-sns (suppress the non-speech tokens)] [-cross-fp8 (FP8 cross-attention caches: half the cache memory per slot; accuracy on real checkpoints not measured)] [-encoder-int8 (the encoder's linear products in INT8 with a scale per row; accuracy on real checkpoints not measured)] [-cross-int4 (INT4 cross-attention caches: 36 bytes per key row instead of 128, not with -cross-fp8; accuracy on real checkpoints not measured)] [-decoder-int8 (single-token decode steps stream INT8 copies of the decoder's weights; accuracy on real checkpoints not measured)]\n";
 
 	// splitAtPauses hands the plan out through a callback: keep the streams
 	HRESULT keepStreams( const sBatchStream* s, uint32_t n, void* pv )
@@ -272,7 +273,7 @@ namespace
 		p.language = findLanguageKeyA( a.lang.c_str() );
 		if( !a.perRecording ) p.setFlag( eFullParamsFlags::NoContext );	   // independent chunks carry nothing over; a whole recording keeps the reference's default
 		iBatchRunner* runner = nullptr;
-		const sBatchSetup bs{ (uint32_t)std::max( 1, std::min( a.slots, 512 ) ), 0, 0, ( a.crossFp8 ? 2u : 0u ) | ( a.encoderInt8 ? 4u : 0u ) | ( a.crossInt4 ? 8u : 0u ) };
+		const sBatchSetup bs{ (uint32_t)std::max( 1, std::min( a.slots, 512 ) ), 0, 0, ( a.crossFp8 ? 2u : 0u ) | ( a.encoderInt8 ? 4u : 0u ) | ( a.crossInt4 ? 8u : 0u ) | ( a.decoderInt8 ? 16u : 0u ) };
 		if( !streams.empty() && FAILED( createBatchRunner( model, &bs, &runner ) ) ) return 6;
 		if( runner && a.useFallback )
 		{
@@ -478,6 +479,7 @@ int main( int argc, char** argv )
 		else if( !strcmp( argv[ i ], "-job" ) ) a.job = val();
 		else if( !strcmp( argv[ i ], "-slots" ) ) a.slots = atoi( val() );
 		else if( !strcmp( argv[ i ], "-cross-fp8" ) || !strcmp( argv[ i ], "--cross-fp8" ) ) a.crossFp8 = true;
+		else if( !strcmp( argv[ i ], "-decoder-int8" ) || !strcmp( argv[ i ], "--decoder-int8" ) ) a.decoderInt8 = true;
 		else if( !strcmp( argv[ i ], "-cross-int4" ) || !strcmp( argv[ i ], "--cross-int4" ) ) a.crossInt4 = true;
 		else if( !strcmp( argv[ i ], "-encoder-int8" ) || !strcmp( argv[ i ], "--encoder-int8" ) ) a.encoderInt8 = true;
 		else if( !strcmp( argv[ i ], "-fallback" ) || !strcmp( argv[ i ], "--fallback" ) ) a.useFallback = true;

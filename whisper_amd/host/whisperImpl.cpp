@@ -21,6 +21,7 @@
 #include "batchCrossFp8.h"
 #include "batchCrossInt4.h"
 #include "batchEncoderI8.h"
+#include "batchDecoderW8.h"
 #include "optionRules.h"
 #include "languageDetect.h"
 #include "captureRate.h"
@@ -1497,6 +1498,8 @@ namespace Whisper
 	static const bool g_createKv4Installed = ( g_batchCreateKv4 = &wh_context_create_kv4, true );
 	// ... and to the INT8 encoder products of a group's context (batchEncoderI8.h)
 	static const bool g_setEncoderI8Installed = ( g_batchSetEncoderI8 = &wh_context_set_encoder_i8, true );
+	// ... and to the INT8 decoder weights of a group's context (batchDecoderW8.h)
+	static const bool g_setDecoderW8Installed = ( g_batchSetDecoderW8 = &wh_context_set_decoder_w8, true );
 
 	HRESULT createContextImpl( const std::shared_ptr<LoadedModel>& model, iModel* owner, iContext** pp )
 	{
